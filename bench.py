@@ -314,6 +314,30 @@ def _host_issue_ms(fn, reps=3):
     return 1e3 * sorted(ts)[len(ts) // 2]
 
 
+DUMP_MAX_VALUES = 4 << 20      # per array (16 MiB of float32): larger outputs are written as a fixed sample
+DUMP_MAX_BYTES = 64 << 20      # all files of one --dump-outputs together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every named tensor as <path>/<name>.npy, float64 if it is float64 and float32 otherwise, outside the timed
+    region. An array of more than DUMP_MAX_VALUES values is written flattened, as the values at DUMP_MAX_VALUES positions drawn
+    once from a fixed seed (ascending): the same positions in every run, so two builds compare output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_VALUES:
+            pick = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_VALUES].sort().values
+            t = t.reshape(-1)[pick.to(t.device)]
+        a = t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise ValueError("--dump-outputs: more than %d bytes" % DUMP_MAX_BYTES)
+        np.save(os.path.join(path, name + ".npy"), a)
+    print("bench.py: wrote %s to %s" % (", ".join(n + ".npy" for n in arrays), path), file=sys.stderr, flush=True)
+
+
 def _roofline_gemm(spec, F, timing, precision):
     """The step's best GEMM (NOT its largest kernel: ~5 % of kernel time) = the cond_transform forward product (F x Ks*D x Ef). SURVEY.md par. 8d counts 2*E*D per flow step and
     frame as written (E = 1530: every GRU output twice); the kernel runs on the folded layout (Ef = 890).
@@ -501,6 +525,9 @@ def bench_train(args, model, trainer, spec, device, world, rank, hp):
         ("gemm_cond_fwd",) + tuple("enc_fwd." + e.name for e in spec.encoders if e.enc == "rnn" and e.hid == 256))
     eng.enable_timing(True, only=roof_tags)
     elapsed, loss = _timed(step, args.steps, world, device)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step holds after the last timed one (the legs below step the model on)
+        dump_outputs(args.dump_outputs, {"loss": loss, "parameters": torch.cat([p.detach().reshape(-1) for p in model.parameters()])})
     timing = eng.timing_summary()
     if roof_tags is not None:
         eng.enable_timing(True)
@@ -760,6 +787,8 @@ def bench_sample(args, model, spec, device, world, rank, hp):
     eng = model.seq_glow.engine
     eng.enable_timing(True)
     elapsed, out_faces = _timed(step, args.steps, world, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"faces": out_faces})
     host_issue = _host_issue_ms(step)
     timing = eng.timing_summary()
     eng.enable_timing(False)
@@ -879,8 +908,10 @@ def launch_check(world, rank):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 20; 5 for --workload deep)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch (BASELINE: 256)")
     ap.add_argument("--seq-len", type=int, default=80)
     ap.add_argument("--cpu-baseline-seconds", type=float, default=70.0,
@@ -916,6 +947,10 @@ def main():
                     help="N = 1, workload train: do not append the `sampling` (configs[3]), `deep_flow` (configs[4]) and "
                          "`native_dims` (C=56 / S=30) sub-records")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 5 if args.workload == "deep" else 20
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.quick:
         args.cpu_baseline_seconds = args.torch_gpu_baseline_seconds = 0.0
         args.three_products_steps = args.graph_steps = args.strong_anchor_batch = 0
@@ -924,16 +959,9 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if world == 1 and args.gpus == 1:
-        # A process that has trained before it samples (this one: the `sampling` sub-record runs behind the training legs) binds more
-        # HIP streams to hardware queues than a process that only samples, and the sampler's ~550 dependent launches per run of frames
-        # then cost 15 us more per generated frame: 50.8 ms per 1024 x 300 call against 45.3 in a fresh process on the same box -
-        # reproduced by ONE earlier fork / join of a second stream with the default stream, and gone with three hardware queues per
-        # process instead of HIP's default four (two runs each, one box: 45.2 / 46.1 against 51.5 / 50.8 ms; the training step, its
-        # graph replay, the batch-2048 anchor and the deep flow within run-to-run noise either way:
-        # profiles/round6_sampler_stream_pick.md, tools/sample_after_train_probe.py). Read by the HIP runtime when it initialises,
-        # i.e. after this line; only for the single-process run (data-parallel ranks keep the default: RCCL's streams want queues).
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "3")
+    # The process runs with the HIP runtime's own hardware-queue count: fewer than its default four made the `sampling` sub-record
+    # faster behind the training legs (profiles/round6_sampler_stream_pick.md), but graph replays with parallel branches - the
+    # hipgraph_replay leg's - are not safe with fewer than four queues.
     if world != args.gpus:   # checked before anything touches the GPU
         if "WORLD_SIZE" not in os.environ and args.gpus > 1:
             # `python bench.py --gpus N` typed as for N = 1: this process - which has not touched the GPU and never will - starts
@@ -1013,8 +1041,6 @@ def main():
             args.batch = 128
         if args.seq_len == 80:
             args.seq_len = 512
-        if args.steps == 20:
-            args.steps = 5
     out = run(args)
     if rank == 0 and world == 1 and args.workload == "train" and not args.no_more_workloads:
         # The driver runs `bench.py --gpus 1` only: the other single-GPU workloads of BASELINE.json (configs[3] sampling, configs[4]
@@ -1028,6 +1054,7 @@ def main():
             a.cpu_baseline_seconds = a.torch_gpu_baseline_seconds = 0.0
             a.three_products_steps = a.graph_steps = a.strong_anchor_batch = 0
             a.quick = True
+            a.dump_outputs = None     # (the headline's timed path only)
             a.measure_sampling_error = workload == "sample" and args.cpu_baseline_seconds > 0   # (part of the cpu_baseline leg)
             hparams_file = kw.pop("hparams_file", None)
             for k, v in kw.items():

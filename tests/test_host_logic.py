@@ -190,6 +190,28 @@ def test_bench_gpus_n_relays_a_failing_rank():
     assert not [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")], r.stdout[-500:]
 
 
+def test_bench_refuses_fewer_than_one_timed_step():
+    r = _run_bench(["--steps", "0"])
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, r.stderr[-500:]
+
+
+def test_bench_dump_outputs_writes_the_same_sample_every_time(tmp_path):
+    """bench.py --dump-outputs: small arrays whole (float64 stays float64, anything else float32), a large one as the values at
+    the same seeded positions in every run, and never more than DUMP_MAX_BYTES in all."""
+    import bench
+    big = torch.arange(bench.DUMP_MAX_VALUES + 1000, dtype=torch.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"loss": torch.tensor([2.5]), "big": big, "f64": torch.ones(3, 2, dtype=torch.float64)})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_VALUES,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0)      # distinct positions, ascending
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [2.5]
+    f = np.load(tmp_path / "a" / "f64.npy")
+    assert f.dtype == np.float64 and f.shape == (3, 2)
+    with pytest.raises(ValueError, match="--dump-outputs"):
+        bench.dump_outputs(str(tmp_path / "c"), {"x%d" % i: big for i in range(5)})
+
+
 def test_trainer_picks_rccl_on_cuda(monkeypatch):
     """Trainer.setup_distributed(): backend "nccl" (= RCCL on ROCm) for a cuda device, gloo for the CPU rehearsal; rendezvous
     on 127.0.0.1; HSA_ENABLE_IPC_MODE_LEGACY=0 kept in the environment (dmabuf IPC only on these hosts)."""
