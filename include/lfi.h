@@ -404,6 +404,14 @@ int lfi_flow_sample_seq_from(const lfi_flow_dims* d, const lfi_flow_params* p, c
                              const float* wct, long E, int hist1, float* pre_static, const float* noise,
                              float* faces, int seq_len, int start, int nframes, int first_frame,
                              float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work, void* stream);
+/* One frame forward of a streaming sampling session (SeqGlow.open_stream; glow/models.py:567-596 one frame at a time), in ONE launch:
+ * every window i (B x hist[i] x dim[i], rows per batch entry) moves up by one frame in place, and its last row receives src[i] (B x
+ * dim[i]), or - src[i] == NULL, the prev_p1_face window of the session's own output - keeps the frame the last step generated there;
+ * noise (B x C, already * eps) is copied into noise_dst; frame_nb (B floats, NULL = no counter) += 2; max |v| of every value read
+ * is folded into *guard_bits (atomic max of the bit pattern, as lfi_absmax_f32; never cleared here, NULL = no guard). count <= 8.
+ * Allocation-free, capturable; the host never waits on guard_bits. */
+int lfi_stream_advance(int B, int count, float* const* win, const float* const* src, const int* hist, const int* dim,
+                       const float* noise, float* noise_dst, int C, float* frame_nb, unsigned* guard_bits, void* stream);
 
 /* ---------------------------------------------------------------- optimiser (configure_optimizers, glow/lets_face_it_glow.py:61-72)
  * Flat-buffer Adam with global-norm gradient clipping (Trainer gradient_clip_val, hparams/final_model.yaml:126):

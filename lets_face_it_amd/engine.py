@@ -204,6 +204,9 @@ class GlowEngine:
         self.adam_m = None
         self.adam_v = None
         self.step_count = 0
+        # bumped by every optimiser step, parameter load and data-dependent ActNorm init: a streaming sampling session (SampleStream)
+        # records it at open and refuses to step once it has moved (its prepared weights are those of the open)
+        self.param_version = 0
         self.inv_p = torch.zeros(spec.Ks, spec.C, spec.C, **f32)
         self.inv_sign = torch.zeros(spec.Ks, spec.C, **f32)
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=self.device)
@@ -266,6 +269,9 @@ class GlowEngine:
         for item in filter(None, [] if env.strip() == "none" else env.split(",")):
             name, bits = item.split("=")
             self.pass_skip[name.strip()] = int(bits)
+
+    def bump_param_version(self):
+        self.param_version += 1
 
     def _skip_bits(self, cls):
         """bf16x3 products to drop for GEMM class `cls` (bit 0: a_lo b_hi, bit 1: a_hi b_lo): an explicit pass_skip entry
@@ -893,6 +899,7 @@ class GlowEngine:
                                        gic.data_ptr() + 4 * k * F * s.G, xb.data_ptr(), s.C, hd.data_ptr(), cd.data_ptr(),
                                        None, 0, st), "lfi_flow_step")
             xa, xb = xb, xa
+        self.bump_param_version()
         self.run_prep()  # the constant log-det term depends on the new actnorm logs
 
     @translate_oom
@@ -1216,6 +1223,7 @@ class GlowEngine:
                   "lfi_flow_step")
             src = dst
         if sums is not None:
+            self.bump_param_version()
             self.run_prep(with_inverse=bool(reverse))  # the constant log-det term depends on the new actnorm logs
         const = self.prep[self._ldconst_offset()]
         return src, (ld - const if reverse else ld + const), h_new, c_new
@@ -1246,6 +1254,7 @@ class GlowEngine:
         weight_decay / amsgrad: torch.optim.Adam's (the reference forwards Optim["args"]["adam"] verbatim); the running maximum of
         the second moment lives in `opt_aux`."""
         self._claim_optimizer("adam")
+        self.bump_param_version()
         if self.adam_m is None:
             self.adam_m = torch.zeros_like(self.params)
             self.adam_v = torch.zeros_like(self.params)
@@ -1279,6 +1288,7 @@ class GlowEngine:
         """clip_grad_norm_(clip) + torch.optim.SGD on the flat buffers (lets_face_it_glow.py:61-72 with Optim.name = "sgd";
         final_model.yaml:98-99: momentum 0.9). The momentum buffer lives in `adam_m` (one optimiser per model)."""
         self._claim_optimizer("sgd")
+        self.bump_param_version()
         # torch.optim.SGD's "first step" (buf = g) is "no momentum buffer yet", not "step 1": a reference checkpoint carries a
         # buffer and no step count (ADVICE r5: the imported buffer was overwritten with g on the first resumed step)
         first = momentum and (self.adam_m is None or not self.__dict__.get("_momentum_inited", False))
@@ -1301,6 +1311,7 @@ class GlowEngine:
         """clip_grad_norm_(clip) + torch.optim.RMSprop on the flat buffers (Optim.name = "rmsprop"; final_model.yaml:96-97: eps 1e-8).
         Square average in `adam_v`, momentum buffer in `adam_m`, the centered variant's gradient average in `opt_aux`."""
         self._claim_optimizer("rmsprop")
+        self.bump_param_version()
         if self.adam_v is None:
             self.adam_v = torch.zeros_like(self.params)
         if momentum and self.adam_m is None:
@@ -1700,3 +1711,320 @@ class GlowEngine:
 
     def logdet_const(self):
         return self.prep[self._ldconst_offset()]
+
+    # ------------------------------------------------------------------ streaming sampling
+    @translate_oom
+    def open_stream(self, seed, noise_fn, masks_fn=None, bound=None):
+        """A SampleStream over this engine (SeqGlow.open_stream): seed = {modality: (B, >= start, dim)} holding the first `start`
+        frames of every modality; noise_fn(B, C) draws a step's prior noise (already * eps); masks_fn(B, N) the window encoders'
+        dropout masks (None = none); bound() is False once the owning module has re-bound to another engine."""
+        return SampleStream(self, seed, noise_fn, masks_fn, bound)
+
+
+# engine attributes that a streaming session owns while one of its steps runs (SampleStream._owned): the workspaces every launch of
+# the static part and the chain writes, and the per-parameter-state preparation they read (run_prep's outputs)
+_SESSION_ATTRS = ("_ws", "prep", "wct_f", "_wct_planes", "_wc_r", "_cond_planes", "_enc_stash_f16")
+_STREAM_GUARD_LIMIT = 1e3   # max |x| the fp16-piece per-frame arithmetic accepts (as GlowEngine._sample)
+
+
+class SampleStream:
+    """Streaming autoregressive sampling: SeqGlow.inference (models.py:567-596) one frame per call, for a live agent whose
+    conditioning arrives frame by frame. Open with `start` seed frames, then step(frame) with frame t of every modality with
+    history > 0 -> the generated p1_face frame t (B, C). Given the same inputs and noise it produces what inference() produces.
+
+    Per step: lfi_stream_advance (one eager launch: the session's conditioning windows, its window of generated faces, the noise and
+    the frame counter move forward by one frame), then the static part for B windows (window encoders + the static cond_transform
+    columns, as _sample's static()) and lfi_flow_sample_seq_from for one frame, whose recurrent state h / c carries across steps. Those
+    two touch only session-owned memory at fixed addresses: from the second step on they are ONE captured hipGraph, replayed.
+    Every workspace they write is the session's own (the engine's `_ws`, prep and folded weights are swapped for the session's while a
+    step runs), so training, inference() and other sessions can run between steps. Weights are frozen: a parameter change after the
+    open (GlowEngine.param_version) makes step() raise."""
+
+    def __init__(self, eng, seed, noise_fn, masks_fn=None, bound=None):
+        s = eng.spec
+        self.eng = eng
+        self._noise_fn, self._masks_fn, self._bound = noise_fn, masks_fn, bound
+        p1 = seed.get("p1_face") if isinstance(seed, dict) else None
+        if p1 is None:
+            raise KeyError("batch is missing modality 'p1_face'")
+        self.B = B = int(p1.shape[0]) if p1.dim() == 3 else -1
+        self.start = s.start
+        self.mods = [e for e in s.encoders if e.name not in ("p1_face", "frame_nb")]
+        self._check_seed(seed)
+        self.device = eng.device
+        self.closed = False
+        self.param_version = eng.param_version
+        self.precision = eng.precision          # GEMM arithmetic of the static part, fixed at the open
+        self.steps = 0                          # frames generated since the open / the last reset()
+        self.replays = 0                        # steps that were graph replays
+        self._graph, self._graph_key = None, None
+        self._stream = None
+        self._guard_pending = None
+        self._state = {"_ws": {}, "prep": None, "wct_f": torch.zeros_like(eng.wct_f), "_wct_planes": None, "_wc_r": None,
+                       "_cond_planes": None, "_enc_stash_f16": {}}
+        e1 = s.encoders[0]
+        self.hist1 = e1.hist
+        self.c1 = (e1.fdim + 3) // 4 * 4
+        KD = s.Ks * s.D
+        p1enc = P1Enc()
+        p1enc.kind, p1enc.hid, p1enc.col = {"none": 0, "mlp": 1, "rnn": 2, "lstm": 3}[e1.enc], e1.hid, e1.fcol
+        self._p1 = p1enc
+        with self._on_stream(), self._owned():
+            eng.run_prep(with_inverse=True)
+            if e1.enc == "mlp":
+                p1enc.w1, p1enc.b1 = eng.view("enc.p1_face.mlp_weight").data_ptr(), eng.view("enc.p1_face.mlp_bias").data_ptr()
+            elif e1.enc in ("rnn", "lstm"):
+                for leaf in ENC_LEAVES:
+                    setattr(p1enc, {"weight_ih": "w_ih", "weight_hh": "w_hh", "bias_ih": "b_ih", "bias_hh": "b_hh"}[leaf],
+                            eng.view("enc.p1_face." + leaf).data_ptr())
+            self._planes_ok = s.Ef > self.c1 and self.precision == 1 and os.environ.get("LFI_PGEMM", "1") != "0"
+            if self._planes_ok:   # the static cond_transform columns' weight planes: once per session (frozen weights)
+                self._wp = eng.planes("wct_planes_static", eng.wct_f, s.ldf, KD, s.Ef - self.c1, x_off=self.c1)
+            f = self.B * s.C
+            self.faces = eng._buf("stream_faces", f * (self.hist1 + 1))[:f * (self.hist1 + 1)].view(B, self.hist1 + 1, s.C)
+            self.noise = eng._buf("stream_noise", f)[:f].view(B, s.C)
+            self.windows = {e.name: eng._buf("stream_win." + e.name, B * e.hist * e.in_dim)[:B * e.hist * e.in_dim].view(B, e.hist, e.in_dim)
+                            for e in self.mods}
+            self.frame_nb = eng._buf("stream_frame_nb", B)[:B] if s.use_frame_nb else None
+            self.mask_bufs = {e.name: eng._buf("stream_mask." + e.name, B * e.hist)[:B * e.hist].view(1, B, e.hist)
+                              for e in s.encoders if e.dropout > 0}
+            self.cond = eng._buf("stream_cond", B * s.ldf)
+            self.pre = eng._buf("stream_pre", B * KD)
+            self.h = eng._buf("stream_h", s.Ks * B * s.H)
+            self.cs = eng._buf("stream_c", s.Ks * B * s.H) if s.rnn_type == "lstm" else None
+            dims = eng._flow_dims(B, 1)
+            self.work = eng._buf("stream_chain_work", eng.L.lfi_flow_sample_work_floats(C.byref(dims)))
+            self.p1work = eng._buf("stream_p1work", eng.L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(p1enc), self.hist1))
+            self.guard = eng._buf_i32("stream_guard_word", 1)
+            self._pinned = torch.zeros(1, dtype=torch.int32).pin_memory()
+            # per-frame arithmetic, picked once (as _sample picks it per call): fp16 pieces (9) when the parameters and the seed sit inside
+            # their range, else six bf16 products (5); exact f32 (0) in f32 engine mode; LFI_SAMPLE_FRAME_PRECISION overrides
+            fp = eng.sample_frame_precision
+            if fp is None:
+                fp = 0
+                if self.precision == 1:
+                    fp = 5
+                    if not eng._sample_fp16_unsafe:
+                        tensors = [eng.params] + [v for v in seed.values() if torch.is_tensor(v) and v.is_cuda and v.dtype == torch.float32]
+                        fp = 9 if eng._read_range_guard(eng._launch_range_guard(tensors[:8])) <= _STREAM_GUARD_LIMIT else 5
+            self.frame_precision = int(fp)
+            self._fill(seed)
+
+    # ---- validation (before any launch; the wording of GlowEngine._check_input)
+    def _check_seed(self, seed):
+        s = self.eng.spec
+        p1 = seed.get("p1_face")
+        self.eng._check_input(p1, "p1_face", self.B, s.start, s.C)
+        for e in self.mods:
+            x = seed.get(e.name)
+            if x is None:
+                raise KeyError("batch is missing modality %r" % e.name)
+            self.eng._check_input(x, e.name, self.B, s.start, e.in_dim)
+            if x.device != p1.device:
+                raise ValueError("%s: on %s, the seed's p1_face on %s" % (e.name, x.device, p1.device))
+
+    def _check_frame(self, x, name, dim):
+        if not (torch.is_tensor(x) and x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.is_contiguous()
+                and x.dim() == 2 and x.shape[0] == self.B and x.shape[1] == dim):
+            raise ValueError("%s: expected contiguous float32 GPU tensor (B=%d, %d) on %s, got %s %s on %s"
+                             % (name, self.B, dim, self.device, tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x)),
+                                getattr(x, "device", None)))
+
+    def _check_usable(self):
+        if self.closed:
+            raise RuntimeError("SampleStream: the session is closed")
+        if self.eng.param_version != self.param_version or (self._bound is not None and not self._bound()):
+            raise RuntimeError("SampleStream: the model's parameters changed since open_stream (optimiser step, parameter load or "
+                               "ActNorm init): a session samples with the weights of its open; open a new one")
+
+    # ---- session-owned engine state and stream
+    @contextlib.contextmanager
+    def _owned(self):
+        eng = self.eng
+        saved = {k: eng.__dict__.get(k) for k in _SESSION_ATTRS}
+        keep_precision = eng.precision
+        eng.__dict__.update(self._state)
+        eng.precision = self.precision
+        try:
+            yield
+        finally:
+            self._state = {k: eng.__dict__.get(k) for k in _SESSION_ATTRS}
+            eng.__dict__.update(saved)
+            eng.precision = keep_precision
+
+    @contextlib.contextmanager
+    def _on_stream(self):
+        """sample()'s rule: no replay into the legacy default stream. A caller on it gets the session's private stream, joined on both
+        sides."""
+        caller = torch.cuda.current_stream(self.device)
+        if caller != torch.cuda.default_stream(self.device):
+            yield caller
+            return
+        if self._stream is None:
+            self._stream = torch.cuda.Stream(device=self.device)
+        own = self._stream
+        own.wait_stream(caller)
+        with torch.cuda.stream(own):
+            yield own
+        caller.wait_stream(own)
+
+    # ---- public surface
+    def reset(self, seed):
+        """Start a new sequence from `seed` (same batch size); the captured graph is kept."""
+        self._check_usable()
+        self._check_seed(seed)
+        with self._on_stream(), self._owned():
+            self._fill(seed)
+
+    def _fill(self, seed):
+        s, h1 = self.eng.spec, self.hist1
+        self.faces[:, 0].zero_()    # (row 0 leaves with the first step's shift)
+        self.faces[:, 1:].copy_(seed["p1_face"][:, s.start - h1:s.start])
+        for e in self.mods:
+            self.windows[e.name].copy_(seed[e.name][:, s.start - e.hist:s.start])
+        if self.frame_nb is not None:
+            self.frame_nb.fill_(-1.0)   # the first step's + 2 makes it inference's 1
+        self.guard.zero_()
+        self.steps = 0
+        self._guard_pending = None
+
+    def close(self):
+        """Releases the session's buffers and graph; step() raises afterwards."""
+        if self.closed:
+            return
+        if self._stream is not None:
+            self._stream.synchronize()
+        self.closed = True
+        self._graph = None
+        self._state = None
+        self.faces = self.noise = self.windows = self.cond = self.pre = self.h = self.cs = self.work = self.p1work = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    @translate_oom
+    def step(self, frame, noise=None):
+        """frame: {modality: (B, dim)} = frame t of every modality with history > 0 (extra keys are ignored). noise: (B, C) prior
+        draw already * eps, or None (drawn with the session's eps). -> generated p1_face frame t, (B, C)."""
+        s, eng, B = self.eng.spec, self.eng, self.B
+        self._check_usable()
+        if not isinstance(frame, dict):
+            raise TypeError("frame must be a dict {modality: (B, dim) tensor}")
+        srcs = []
+        for e in self.mods:
+            x = frame.get(e.name)
+            if x is None:
+                raise KeyError("batch is missing modality %r" % e.name)
+            self._check_frame(x, e.name, e.in_dim)
+            srcs.append(x)
+        if noise is not None:
+            self._check_frame(noise, "noise", s.C)
+        with self._on_stream(), self._owned():
+            self._check_guard()
+            if noise is None:
+                noise = self._noise_fn(B, s.C).contiguous()
+            masks = None
+            drawn = self._masks_fn(B, 1) if self._masks_fn is not None else None
+            eng.precision = self.precision      # (the module's mask draw re-applies its own mode to the engine)
+            if drawn:
+                masks = {}
+                for name, buf in self.mask_bufs.items():
+                    m = drawn.get(name)
+                    if m is None:
+                        continue
+                    if m.dim() != 3 or tuple(m.shape[1:]) != (B, buf.shape[2]):
+                        raise ValueError("mask for %s must be (N, B, hist) = (., %d, %d), got %s" % (name, B, buf.shape[2], tuple(m.shape)))
+                    if m.shape[0] != 1 and self.steps >= m.shape[0]:
+                        raise ValueError("mask for %s holds %d frames; this is frame %d of the stream" % (name, m.shape[0], self.steps))
+                    buf.copy_(m[0 if m.shape[0] == 1 else self.steps].unsqueeze(0))
+                    masks[name] = buf
+            wins = self.mods + [None]
+            n = len(wins)
+            win_p, src_p = (C.c_void_p * n)(), (C.c_void_p * n)()
+            hist, dim = (C.c_int * n)(), (C.c_int * n)()
+            for i, e in enumerate(self.mods):
+                win_p[i], src_p[i], hist[i], dim[i] = self.windows[e.name].data_ptr(), srcs[i].data_ptr(), e.hist, e.in_dim
+            win_p[n - 1], src_p[n - 1], hist[n - 1], dim[n - 1] = self.faces.data_ptr(), None, self.hist1 + 1, s.C
+            ev = eng._tic("stream_advance")
+            check(eng.L.lfi_stream_advance(B, n, win_p, src_p, hist, dim, noise.data_ptr(), self.noise.data_ptr(), s.C,
+                                           ptr(self.frame_nb), self.guard.data_ptr(), _stream()), "lfi_stream_advance")
+            eng._toc("stream_advance", ev)
+            self._pinned.copy_(self.guard, non_blocking=True)
+            gev = torch.cuda.Event()
+            gev.record()
+            self._guard_pending = gev
+            for x in srcs + [noise]:
+                x.record_stream(torch.cuda.current_stream(self.device))
+            if self.steps == 0 or os.environ.get("LFI_NO_GRAPH") == "1":
+                self._launch(masks, 1 if self.steps > 0 else 0)
+            else:
+                key = (self.frame_precision, masks is not None)
+                if self._graph is None or self._graph_key != key:
+                    timers, eng.timers = eng.timers, None
+                    try:
+                        torch.cuda.synchronize()
+                        g = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(g):
+                            self._launch(masks, 1)
+                    finally:
+                        eng.timers = timers
+                    self._graph, self._graph_key = g, key
+                ev = eng._tic("stream_graph")
+                self._graph.replay()
+                eng._toc("stream_graph", ev)
+                self.replays += 1
+            out = self.faces[:, self.hist1].clone()
+            self.steps += 1
+        if out.device == self.device and self._stream is not None:
+            out.record_stream(torch.cuda.current_stream(self.device))
+        return out
+
+    def _launch(self, masks, first_frame):
+        """The static part for the session's B windows, then the reverse chain for one frame: session-owned memory only."""
+        eng, s, B = self.eng, self.eng.spec, self.B
+        KD = s.Ks * s.D
+        ev = eng._tic("stream_static")
+        data = dict(self.windows)
+        if self.frame_nb is not None:
+            data["frame_nb"] = self.frame_nb
+        # (sampling=False: the frame counter comes from the session's device counter, not from a host frame offset)
+        eng.build_features(data, None, B, 0, masks, self.cond, with_stash=False, skip_p1=True, sampling=False, windows=True)
+        if self._planes_ok:
+            wp, nkw = self._wp
+            cp, nkc = eng.planes("cond_planes", self.cond, s.ldf, B, s.Ef - self.c1, x_off=self.c1)
+            eng.gemm_planes(B, KD, s.Ef - self.c1, cp, nkc, wp, nkw, self.pre, KD, bias=eng.fview("bct"), cls="cond_fwd")
+        elif s.Ef > self.c1:
+            eng.gemm(B, KD, s.Ef - self.c1, self.cond, s.ldf, 1, eng.wct_f, s.ldf, 1, self.pre, KD, bias=eng.fview("bct"),
+                     a_off=self.c1, b_off=self.c1)
+        else:
+            self.pre[:B * KD].view(B, KD).copy_(eng.fview("bct").reshape(1, KD).expand(B, KD))
+        eng._toc("stream_static", ev)
+        dims = eng._flow_dims(B, 1)
+        dims.gemm_precision = self.frame_precision
+        p = eng._flow_params()
+        ev = eng._tic("stream_chain")
+        check(eng.L.lfi_flow_sample_seq_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
+                                             self.pre.data_ptr(), self.noise.data_ptr(), self.faces.data_ptr(), self.hist1 + 1,
+                                             self.hist1, 1, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
+                                             self.p1work.data_ptr(), self.work.data_ptr(), _stream()), "lfi_flow_sample_seq_from")
+        eng._toc("stream_chain", ev)
+
+    def _check_guard(self):
+        """The range guard of earlier steps (lfi_stream_advance folds max |x| of every value it moves into the session's guard word,
+        copied to pinned memory behind it): looked at once its copy has landed - never a host wait. A value beyond the fp16 pieces'
+        range (or a non-finite one) is reported with a warning, and the session samples with six bf16 products from then on."""
+        ev = self._guard_pending
+        if ev is None or not ev.query():
+            return
+        self._guard_pending = None
+        import struct
+        amax = struct.unpack("<f", struct.pack("<I", int(self._pinned.item()) & 0xffffffff))[0]
+        if self.frame_precision == 9 and not (amax <= _STREAM_GUARD_LIMIT):
+            self.frame_precision = 5
+            warnings.warn("SampleStream: an earlier step saw max |x| = %r, beyond the range of the fp16-piece per-frame arithmetic (%g): "
+                          "this session samples with six bf16 products (no range caveat) from now on; frames since that input may be "
+                          "inaccurate" % (amax, _STREAM_GUARD_LIMIT), RuntimeWarning)

@@ -275,6 +275,7 @@ class LetsFaceItGlow(nn.Module):
                                              torch.cuda.current_stream().cuda_stream), "lfi_set_step_params")
         st["graph"].replay()
         eng.step_count += 1
+        eng.bump_param_version()
         if st["dropout"]:
             eng._mask_calls += 1
         sg._fwd_counter += 1

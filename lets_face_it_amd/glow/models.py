@@ -380,6 +380,8 @@ class SeqGlow(nn.Module):
         self.allreduce_hook = None  # set by the data-parallel trainer: sums ActNorm init statistics over ranks
         self._param_map = []
         self._fwd_counter = 0
+        # a parameter load moves the engine's parameter version: open streaming sessions (open_stream) refuse to step afterwards
+        self.register_load_state_dict_post_hook(_params_loaded)
 
     # ------------------------------------------------------------------ engine binding
     def _named_flat(self):
@@ -524,6 +526,28 @@ class SeqGlow(nn.Module):
         with torch.no_grad():
             return eng.sample(seq_len, data, noise.contiguous().float(), masks)
 
+    def open_stream(self, seed, eps=None):
+        """Streaming autoregressive sampling: inference() one frame per call, for a live agent whose speech and interlocutor arrive
+        frame by frame. seed: a dict like inference()'s `data` holding the first start = get_longest_history(...) frames of every
+        modality (p1_face: B x start x C). Returns a lets_face_it_amd.engine.SampleStream: step(frame, noise=None) with frame =
+        {modality: (B, dim)} = frame t of every modality with history > 0 -> the generated p1_face frame t (B, C); without `noise`
+        a step draws GaussianDiag.sample((B, C), eps) (eps: hparams.Infer["eps"] by default). reset(seed), close(), and a context
+        manager. Same inputs and noise give what inference() gives. Dropout as inference(): masks from _draw_masks(B, 1) per step,
+        none in eval mode. The weights are frozen for the session: step() raises after an optimiser step or a parameter load."""
+        p1 = seed.get("p1_face") if isinstance(seed, dict) else None
+        if p1 is None:
+            raise KeyError("batch is missing modality 'p1_face'")
+        dev = p1.device
+        eng = self._ensure_engine(dev)
+        eps = self.hparams.Infer["eps"] if eps is None else eps
+
+        def noise_fn(B, C):
+            # GaussianDiag.sample's law; a scalar std (its tensor std's non-negativity check would wait for the device every step)
+            return torch.empty(B, C, device=dev).normal_(0.0, float(eps))
+
+        with torch.no_grad():
+            return eng.open_stream(seed, noise_fn, lambda B, N: self._draw_masks(B, N, dev), lambda: self.engine is eng)
+
     def invert(self, z_seq, data):
         """-> (reconstr_seq: list[N] of (B, C), backward_loss (1,))   (models.py:617-645)"""
         x = data["p1_face"]
@@ -558,6 +582,11 @@ class SeqGlow(nn.Module):
         masks = self._draw_masks(B, 1, dev)
         with torch.no_grad():
             return eng.encode_condition(cond, masks)
+
+
+def _params_loaded(module, incompatible_keys):
+    if module.engine is not None:
+        module.engine.bump_param_version()
 
 
 class _SlotName(str):

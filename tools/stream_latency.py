@@ -1,0 +1,151 @@
+"""Latency of one streaming sampling step (SeqGlow.open_stream -> SampleStream.step) at final_model.yaml, against the only correct
+alternative without a session: re-running SeqGlow.inference over the whole prefix for every new frame.
+
+  python tools/stream_latency.py [--batches 1,16,256] [--steps 200] [--warmup 20] [--prefixes 50,150,300] [--out FILE]
+
+Per batch size: the wall-clock time from step() to the generated frame on the host (a synchronise after every step: what a live agent
+waits for), its GPU time (HIP events around the step), and a per-kernel breakdown from the engine's enable_timing on an eager session
+(LFI_NO_GRAPH=1: inside a replayed graph there are no per-kernel events). Then inference() over a prefix of t frames in total (t - 24
+generated), the cost of frame t without a session. Prints a markdown report (and writes it to --out); the shader clock under load is
+read by bench.py's rocm-smi helper, started before this process touches the GPU."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="1,16,256")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--prefixes", default="50,150,300")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import bench
+    helper = bench.start_smi_helper()       # (before the GPU is initialised: see bench.py)
+    import copy
+    from argparse import Namespace
+
+    import torch
+    from lets_face_it_amd.glow.models import SeqGlow
+    from lets_face_it_amd.glow.utils import load_hparams_file
+
+    dev = torch.device("cuda:0")
+    hp = load_hparams_file(os.path.join(ROOT, "lets_face_it_amd", "hparams", "final_model.yaml"))
+    torch.manual_seed(1234)
+    m = SeqGlow(Namespace(**copy.deepcopy(hp)))
+    g = torch.Generator().manual_seed(4321)
+    with torch.no_grad():     # LinearZeros / ActNorm off their zero init: at init the coupling ignores its conditioning
+        for name, p in m.named_parameters():
+            if "final_linear" in name:
+                p.add_(torch.randn(p.shape, generator=g) * 0.05)
+            elif "actnorm" in name:
+                p.add_(torch.randn(p.shape, generator=g) * 0.1)
+    m.to(dev)
+    m.glow.set_actnorm_init(True)
+    m.eval()
+    s = m.spec
+    start, C = s.start, s.C
+    dims = {"p1_face": C, "p2_face": C, "p1_speech": s.S, "p2_speech": s.S}
+    batches = [int(v) for v in a.batches.split(",")]
+    prefixes = [int(v) for v in a.prefixes.split(",")]
+    total = a.warmup + a.steps
+    lines = ["# Streaming step latency (tools/stream_latency.py)", "",
+             "final_model.yaml as shipped (C = %d, S = %d, K = %d, H = %d, D = %d, longest history %d), engine precision %s, per-frame "
+             "arithmetic picked at the open; %d timed steps after %d warm-up steps per batch size; torch %s, device %s."
+             % (C, s.S, s.Ks, s.H, s.D, start, m.precision, a.steps, a.warmup, torch.__version__, torch.cuda.get_device_name(dev)), ""]
+    rows, kernels, prefix_rows = [], {}, []
+    for B in batches:
+        gd = torch.Generator().manual_seed(B)
+        T = start + total
+        data = {k: torch.randn(B, T, d, generator=gd).to(dev) for k, d in dims.items()}
+        seed = {k: v[:, :start].contiguous() for k, v in data.items()}
+        frames = [{k: v[:, start + n].contiguous() for k, v in data.items() if k != "p1_face"} for n in range(total)]
+        noise = (torch.randn(total, B, C, generator=gd) * 0.8).to(dev)
+        st = m.open_stream(seed)
+        wall, gpu = [], []
+        for n in range(total):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e0.record()
+            st.step(frames[n], noise[n])
+            e1.record()
+            e1.synchronize()
+            t1 = time.perf_counter()
+            if n >= a.warmup:
+                wall.append((t1 - t0) * 1e3)
+                gpu.append(e0.elapsed_time(e1))
+        fp = st.frame_precision
+        replays = st.replays
+        clk = None
+        if B == batches[-1]:
+            clk = bench.gpu_state_under_load(lambda i: st.step(frames[i % total], noise[i % total]), dev, helper)
+        st.close()
+        wall.sort()
+        rows.append((B, statistics.median(wall), wall[int(0.9 * (len(wall) - 1))], statistics.median(gpu), fp, replays))
+        # per-kernel breakdown: an eager session with the engine's events on
+        os.environ["LFI_NO_GRAPH"] = "1"
+        eng = m.engine
+        st = m.open_stream(seed)
+        for n in range(a.warmup):
+            st.step(frames[n], noise[n])
+        eng.enable_timing(True)
+        for n in range(a.warmup, total):
+            st.step(frames[n], noise[n])
+        kernels[B] = eng.timing_summary()
+        eng.enable_timing(False)
+        st.close()
+        del os.environ["LFI_NO_GRAPH"]
+        for t in prefixes:
+            if t <= start:
+                continue
+            pd = {k: (v[:, :start].contiguous() if k == "p1_face" else torch.randn(B, t, dims[k], generator=gd).to(dev))
+                  for k, v in data.items()}
+            pn = (torch.randn(t - start, B, C, generator=gd) * 0.8).to(dev)
+            times = []
+            for i in range(7):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                m.inference(t, pd, noise=pn)
+                torch.cuda.synchronize()
+                if i >= 2:     # (call 1 eager, call 2 captures the per-run graphs)
+                    times.append((time.perf_counter() - t0) * 1e3)
+            prefix_rows.append((B, t, statistics.median(times)))
+        if clk is not None:
+            kernels["clock"] = clk
+    bench.stop_smi_helper(helper)
+
+    lines += ["## One streaming step", "",
+              "| B | wall ms, median | wall ms, p90 | GPU ms, median (events around step) | per-frame arithmetic | replayed steps |",
+              "|---|---|---|---|---|---|"]
+    for B, med, p90, gmed, fp, rep in rows:
+        lines.append("| %d | %.3f | %.3f | %.3f | %d | %d of %d |" % (B, med, p90, gmed, fp, rep, total))
+    lines += ["", "## Per-kernel breakdown of an eager step (LFI_NO_GRAPH=1, HIP events; mean ms per step)", ""]
+    tags = sorted({t for B in batches for t in kernels[B]})
+    lines += ["| tag | " + " | ".join("B = %d" % B for B in batches) + " |", "|---|" + "---|" * len(batches)]
+    for t in tags:
+        lines.append("| %s | " % t + " | ".join("%.3f" % kernels[B][t][1] if t in kernels[B] else "-" for B in batches) + " |")
+    lines += ["", "`stream_static` spans the window encoders (`enc_fwd.*`, nested inside it) and the static cond_transform columns; "
+              "`stream_chain` is lfi_flow_sample_seq_from for one frame.", "",
+              "## Without a session: inference() over the whole prefix for frame t", "",
+              "| B | t (frames in total) | ms per call (median of 5, graphs replayed) |", "|---|---|---|"]
+    for B, t, ms in prefix_rows:
+        lines.append("| %d | %d | %.3f |" % (B, t, ms))
+    clk = kernels.get("clock")
+    lines += ["", "GPU state under streaming steps at B = %d: %s" % (batches[-1], clk if clk else "not read (no rocm-smi helper)")]
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
