@@ -9,9 +9,14 @@ Rank 0 prints ONE JSON line. `value` = frames processed by all ranks / max-over-
 (inputs resident in HBM before the timed region). `roofline` is for the step's largest kernel by time, the persistent GRU
 window-encoder forward recurrence (two launches per step), timed with HIP events on its launch stream inside the timed region;
 `roofline_best_gemm` is the cond_transform forward product (F x Ks*D x Ef, bf16 hi/lo operand planes, three bf16 MFMA products per
-k-step: the fastest kernel of the step, ~5 % of its time); `roofline_whole_step` prices the whole step. `cpu_baseline`
-(N = 1 only) times the CPU oracle — a plain-PyTorch port of the reference's per-timestep loop — on the host cores on a
-bounded sample of the same workload; it is a reported baseline, not the thing measured above.
+k-step: the fastest kernel of the step, ~5 % of its time); `roofline_whole_step` prices the whole step.
+
+A plain run does only what that line needs: set up, warm up, time the K steps, --dump-outputs if given, print. Everything that
+takes runs of its own is behind --full: the per-kernel timing of every tagged kernel, the host-issue time, the loaded-GPU clock
+reading, the data-parallel bucket record (N > 1), the hipGraph-replay and three-product legs, the batch-2048 strong-scaling anchor,
+the stock PyTorch-ROCm and CPU baselines, the measured sampling error and the `sampling` / `deep_flow` / `native_dims` sub-records.
+`cpu_baseline` (N = 1 only) times the CPU oracle — a plain-PyTorch port of the reference's per-timestep loop — on the host cores on
+a bounded sample of the same workload; it is a reported baseline, not the thing measured above.
 """
 import argparse
 import json
@@ -518,8 +523,8 @@ def bench_train(args, model, trainer, spec, device, world, rank, hp):
         step(i)
     eng = model.seq_glow.engine
     # HIP events around the `roofline` kernel inside the timed region; the other tagged kernels (`roofline_hbm`'s among them) are
-    # timed in a short region of their own afterwards: every event record is a marker packet in the queue (~6 us of dispatch
-    # gap), and with all nine tags on the timed step carried 18 of them - 0.1 ms that no training step pays (same-call A/B:
+    # timed in a short region of their own afterwards (--full): every event record is a marker packet in the queue (~6 us of
+    # dispatch gap), and with all nine tags on the timed step carried 18 of them - 0.1 ms that no training step pays (same-call A/B:
     # 7.86 ms with all tags, 7.77 with the roofline kernels' only; LFI_BENCH_ALL_TAGS=1: the old behaviour)
     roof_tags = None if os.environ.get("LFI_BENCH_ALL_TAGS") == "1" else (
         ("gemm_cond_fwd",) + tuple("enc_fwd." + e.name for e in spec.encoders if e.enc == "rnn" and e.hid == 256))
@@ -529,7 +534,7 @@ def bench_train(args, model, trainer, spec, device, world, rank, hp):
         # what a caller of the step holds after the last timed one (the legs below step the model on)
         dump_outputs(args.dump_outputs, {"loss": loss, "parameters": torch.cat([p.detach().reshape(-1) for p in model.parameters()])})
     timing = eng.timing_summary()
-    if roof_tags is not None:
+    if roof_tags is not None and args.full:
         eng.enable_timing(True)
         _timed(step, 5, world, device)
         timing_all = eng.timing_summary()
@@ -537,7 +542,7 @@ def bench_train(args, model, trainer, spec, device, world, rank, hp):
         timing = timing_all
     eng.enable_timing(False)
     dp_line = None
-    if world > 1:
+    if world > 1 and args.full:
         # a short region of its own (event records are marker packets): which bucket held the main stream for how long
         model.dp_profile = []
         _timed(step, 5, world, device)
@@ -555,7 +560,7 @@ def bench_train(args, model, trainer, spec, device, world, rank, hp):
                 "ms_per_step": 1e3 * el_g / args.graph_steps, "host_issue_ms_per_step": _host_issue_ms(step), "steps": args.graph_steps,
                 "note": "two graphs per step split at the flow bucket's launch point, both all-reduces and clip + Adam eager"}
             model.step_graph = False
-    host_issue = _host_issue_ms(step, reps=5)   # (without any per-kernel events)
+    host_issue = _host_issue_ms(step, reps=5) if args.full else None   # (without any per-kernel events)
     gpu_state = None
     if rank == 0 and not args.quick and world == 1 and getattr(args, "smi_helper", None) is not None:
         # the load is the real step at lr = 0 (parameters do not move) with Adam's moments, step count and dropout counter put
@@ -789,7 +794,7 @@ def bench_sample(args, model, spec, device, world, rank, hp):
     elapsed, out_faces = _timed(step, args.steps, world, device)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, {"faces": out_faces})
-    host_issue = _host_issue_ms(step)
+    host_issue = _host_issue_ms(step) if args.full else None
     timing = eng.timing_summary()
     eng.enable_timing(False)
     if rank != 0:
@@ -905,7 +910,7 @@ def launch_check(world, rank):
     return 0
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 20; 5 for --workload deep)")
@@ -914,12 +919,15 @@ def main():
                     help="after the timed steps, write what the last of them returned to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch (BASELINE: 256)")
     ap.add_argument("--seq-len", type=int, default=80)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures (see the module docstring); a plain run "
+                         "times the headline steps only")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=70.0,
-                    help="budget of the CPU baseline leg (oracle on the host cores at the metric's batch: 1 warm-up + 2-3 "
-                         "steps of ~20 s); 0 disables it")
+                    help="--full: budget of the CPU baseline leg (oracle on the host cores at the metric's batch: 1 warm-up + "
+                         "2-3 steps of ~20 s); 0 disables it")
     ap.add_argument("--torch-gpu-baseline-seconds", type=float, default=30.0,
-                    help="budget of the stock PyTorch-ROCm leg (the oracle's op sequence on cuda:0, 1 warm-up + 3-5 steps); "
-                         "0 disables it")
+                    help="--full: budget of the stock PyTorch-ROCm leg (the oracle's op sequence on cuda:0, 1 warm-up + 3-5 "
+                         "steps); 0 disables it")
     ap.add_argument("--precision", choices=("f32", "bf16x3"), default=os.environ.get("LFI_PRECISION", "bf16x3"),
                     help="GEMM arithmetic: exact f32 MFMA, or bf16 hi/lo split operands (3 bf16 MFMAs per product)")
     ap.add_argument("--workload", choices=("train", "sample", "deep"), default="train",
@@ -927,35 +935,42 @@ def main():
                          "inference at --batch 1024 --seq-len 300 unless given; deep: configs[4], the training step of a "
                          "K=32 x L=3 flow at --batch 128 --seq-len 512 unless given")
     ap.add_argument("--three-products-steps", type=int, default=20,
-                    help="N = 1: also time this many steps with three bf16 products in the backward GEMMs too (reported as "
-                         "three_products_everywhere); 0 disables it")
+                    help="--full, N = 1: also time this many steps with three bf16 products in the backward GEMMs too "
+                         "(reported as three_products_everywhere); 0 disables it")
     ap.add_argument("--graph-steps", type=int, default=20,
-                    help="N = 1: also time this many steps replayed as a captured hipGraph (reported as hipgraph_replay); 0 disables it")
+                    help="--full, N = 1: also time this many steps replayed as a captured hipGraph (reported as hipgraph_replay); "
+                         "0 disables it")
     ap.add_argument("--strong-anchor-batch", type=int, default=2048,
-                    help="N = 1, workload train: also time one GPU at this batch (the global batch of configs[2]) and report it "
-                         "as strong_scaling_anchor; 0 disables it")
+                    help="--full, N = 1, workload train: also time one GPU at this batch (the global batch of configs[2]) and "
+                         "report it as strong_scaling_anchor; 0 disables it")
     ap.add_argument("--hparams", default=os.path.join(ROOT, "lets_face_it_amd", "hparams", "final_model_synthetic.yaml"))
     ap.add_argument("--no-gpu-state", action="store_true",
                     help="do not start the rocm-smi helper process (runs under rocprofv3 --pmc, where the profiler has initialised the "
                          "GPU before this program starts and the box refuses every fork + exec)")
     ap.add_argument("--quick", action="store_true",
-                    help="the timed region and its roofline only: no baselines, no hipGraph / three-product / anchor legs, no "
-                         "further workloads (A/B runs)")
+                    help="--full without its long legs (A/B runs): per-kernel timing, host-issue time and (N > 1) the "
+                         "data-parallel record, but no baselines, no hipGraph / three-product / anchor legs, no further workloads "
+                         "and no loaded-GPU clock reading")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous of the ranks on gloo + rank 0's JSON line only (no GPU): checks the way --gpus N starts itself")
     ap.add_argument("--no-more-workloads", action="store_true",
-                    help="N = 1, workload train: do not append the `sampling` (configs[3]), `deep_flow` (configs[4]) and "
-                         "`native_dims` (C=56 / S=30) sub-records")
-    args = ap.parse_args()
+                    help="--full, N = 1, workload train: do not append the `sampling` (configs[3]), `deep_flow` (configs[4]) "
+                         "and `native_dims` (C=56 / S=30) sub-records")
+    args = ap.parse_args(argv)
     if args.steps is None:
         args.steps = 5 if args.workload == "deep" else 20
     if args.steps < 1:
         ap.error("--steps must be at least 1")
-    if args.quick:
+    if args.quick or not args.full:
         args.cpu_baseline_seconds = args.torch_gpu_baseline_seconds = 0.0
         args.three_products_steps = args.graph_steps = args.strong_anchor_batch = 0
         args.no_more_workloads = True
+    args.full = args.full or args.quick     # (--quick keeps the short extras of --full)
+    return args
 
+
+def main():
+    args = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -977,7 +992,8 @@ def main():
     # through the host): same code path, barriers and timing; the default is RCCL with one GPU per rank
     backend = os.environ.get("LFI_DIST_BACKEND", "nccl")
     # (before anything initialises the GPU: see start_smi_helper)
-    args.smi_helper = start_smi_helper() if (world == 1 and rank == 0 and not args.quick and not args.no_gpu_state) else None
+    args.smi_helper = start_smi_helper() if (world == 1 and rank == 0 and args.full and not args.quick
+                                             and not args.no_gpu_state) else None
     ndev = torch.cuda.device_count()
     device = torch.device("cuda", local_rank % ndev if (backend != "nccl" and ndev > 0) else local_rank)
     torch.cuda.set_device(device)

@@ -195,6 +195,23 @@ def test_bench_refuses_fewer_than_one_timed_step():
     assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, r.stderr[-500:]
 
 
+def test_bench_runs_its_extra_legs_only_with_full():
+    """A plain run times the headline only; --full turns on every other leg at its default; --quick is --full without the long
+    legs (baselines, hipGraph / three-product / anchor legs, sub-records)."""
+    import bench
+    plain, full, quick = bench.parse_args([]), bench.parse_args(["--full"]), bench.parse_args(["--quick"])
+    for a in (plain, quick):
+        assert a.cpu_baseline_seconds == a.torch_gpu_baseline_seconds == 0.0
+        assert a.three_products_steps == a.graph_steps == a.strong_anchor_batch == 0 and a.no_more_workloads
+    assert not plain.full and quick.full
+    assert full.full and not full.no_more_workloads
+    assert full.cpu_baseline_seconds > 0 and full.torch_gpu_baseline_seconds > 0
+    assert full.three_products_steps > 0 and full.graph_steps > 0 and full.strong_anchor_batch == 2048
+    assert bench.parse_args(["--full", "--graph-steps", "0"]).graph_steps == 0
+    for a in (plain, full, quick):
+        assert (a.steps, a.warmup) == (20, 3)
+
+
 def test_bench_dump_outputs_writes_the_same_sample_every_time(tmp_path):
     """bench.py --dump-outputs: small arrays whole (float64 stays float64, anything else float32), a large one as the values at
     the same seeded positions in every run, and never more than DUMP_MAX_BYTES in all."""

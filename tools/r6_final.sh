@@ -10,15 +10,15 @@ O=gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has bench; then
-  timeout -k 10 600 python bench.py > $O/bench_train.json 2> $O/bench_train.err; echo "train rc=$?"
-  timeout -k 10 300 python bench.py --workload sample > $O/bench_sample.json 2> $O/bench_sample.err; echo "sample rc=$?"
-  timeout -k 10 400 python bench.py --workload deep > $O/bench_deep.json 2> $O/bench_deep.err; echo "deep rc=$?"
-  LFI_BENCH_DP_GRAPH=1 LFI_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --steps 5 --warmup 2 --graph-steps 5 > $O/bench_n2_gloo.json 2> $O/bench_n2_gloo.err; echo "n2 gloo (self-launched) rc=$?"
+  timeout -k 10 600 python bench.py --full > $O/bench_train.json 2> $O/bench_train.err; echo "train rc=$?"
+  timeout -k 10 300 python bench.py --full --workload sample > $O/bench_sample.json 2> $O/bench_sample.err; echo "sample rc=$?"
+  timeout -k 10 400 python bench.py --full --workload deep > $O/bench_deep.json 2> $O/bench_deep.err; echo "deep rc=$?"
+  LFI_BENCH_DP_GRAPH=1 LFI_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --steps 5 --warmup 2 --graph-steps 5 > $O/bench_n2_gloo.json 2> $O/bench_n2_gloo.err; echo "n2 gloo (self-launched) rc=$?"
   bash tools/r6_ab.sh $TAG/ab_thin 2 "LFI_FLOW_WGRAD_FUSED=0" "-" > $O/ab_thin.txt 2>&1; cat $O/ab_thin.txt
 fi
 if has prof; then
   bash tools/r3_profiles.sh $TAG
-  NOBASE="--no-gpu-state --no-more-workloads --cpu-baseline-seconds 0"
+  NOBASE="--full --no-gpu-state --no-more-workloads --cpu-baseline-seconds 0"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/profs -o run -- python3 bench.py --workload sample $NOBASE --steps 3 --warmup 2 > $O/profs.log 2>&1; echo "prof sample rc=$?"
   python3 tools/rocpd_stats.py $O/profs/run_results.db 16 > $O/sampler_kernel_stats.md 2>&1
   rm -rf $O/profs

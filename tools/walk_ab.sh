@@ -5,7 +5,7 @@ set -u
 TAG=$1; shift
 O=gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
-NOBASE="--cpu-baseline-seconds 0 --torch-gpu-baseline-seconds 0 --strong-anchor-batch 0 --graph-steps 0 --three-products-steps 0"
+NOBASE="--full --cpu-baseline-seconds 0 --torch-gpu-baseline-seconds 0 --strong-anchor-batch 0 --graph-steps 0 --three-products-steps 0"
 for v in "$@"; do
   export LFI_LIB_PATH=$PWD/build/var/liblfi_$v.so
   [ -n "${SKIPT:-}" ] || timeout -k 10 200 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "pipeline or walk or abort" > $O/t_$v.log 2>&1; echo "$v tests rc=$?"
