@@ -412,6 +412,20 @@ int lfi_flow_sample_seq_from(const lfi_flow_dims* d, const lfi_flow_params* p, c
  * Allocation-free, capturable; the host never waits on guard_bits. */
 int lfi_stream_advance(int B, int count, float* const* win, const float* const* src, const int* hist, const int* dim,
                        const float* noise, float* noise_dst, int C, float* frame_nb, unsigned* guard_bits, void* stream);
+/* Reseed listed batch rows of a streaming sampling session (SampleStream.reset_rows; the start of glow/models.py:567-596 for those
+ * rows alone) between steps: each session row rows[j] (0 <= rows[j] < B, none twice, nrows >= 1) gets the state open_stream gives
+ * a row, from entry j of the caller's seed, and no other row is written. Per window i (count <= 8; the layout of lfi_stream_advance):
+ * the row's hist[i] frames are copied from seed[i] + j * seed_ld[i] (the caller's (n, T, dim) tensor read in place: seed[i] points at
+ * frame start - hist of entry 0, seed_ld[i] = T * dim), or - lead_zero[i] = 1, the prev_p1_face window - frame 0 of the row is zeroed
+ * and frames 1 .. hist[i] - 1 come from the seed. h / cstate ([Ks][B][H] each; cstate NULL = GRU): the row is zeroed in every flow
+ * step, which is what the reverse cells load for a null h_prev (first_frame = 0). frame_nb (NULL = no counter): the row is set to
+ * -1 (the next advance's + 2 gives inference's 1). max |v| of every seed value copied is folded into *guard_bits as lfi_stream_advance
+ * does; the guard is never cleared here (other rows' values live in it). Rows travel in the kernel arguments, 256 per launch (a
+ * longer list is several launches): allocation-free, no host staging and no host wait, capturable. Every argument, every row
+ * included, is checked before the first launch. */
+int lfi_stream_reset_rows(int B, int nrows, const int* rows, int count, float* const* win, const float* const* seed,
+                          const long* seed_ld, const int* hist, const int* dim, const int* lead_zero, float* h, float* cstate,
+                          int Ks, int H, float* frame_nb, unsigned* guard_bits, void* stream);
 
 /* ---------------------------------------------------------------- optimiser (configure_optimizers, glow/lets_face_it_glow.py:61-72)
  * Flat-buffer Adam with global-norm gradient clipping (Trainer gradient_clip_val, hparams/final_model.yaml:126):

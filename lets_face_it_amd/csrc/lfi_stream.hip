@@ -4,8 +4,11 @@
 // prev_p1_face window of its own output (B x (hist1 + 1) x C), the prior noise of the step and the frame counter. One launch moves
 // all of it forward by one frame on the caller's stream; the static part and the reverse chain of the step (a captured graph) then
 // read only session-owned, fixed-address memory. What SeqGlow.inference does with whole sequences (glow/models.py:567-596), one
-// frame at a time.
+// frame at a time. A second entry point puts listed batch rows back to the state of the open (SampleStream.reset_rows), between
+// steps, leaving the other rows alone: conversations join and leave one batched session independently.
 #include "lfi_common.h"
+
+#include <vector>
 
 namespace {
 
@@ -66,6 +69,76 @@ __global__ __launch_bounds__(256) void stream_advance_kernel(StreamWins w, const
   if ((threadIdx.x & 63) == 0 && m) atomicMax(guard, m);
 }
 
+// ---- per-row reseed (SampleStream.reset_rows): the state open_stream / reset() give a row, for a listed subset of rows
+//
+// Rows are passed by value in the kernel argument block (StreamReset.rows), at most kResetMaxRows per launch: no staging copy and no
+// host wait; the host entry point splits a longer list into launches of its own.
+constexpr int kResetMaxRows = 256;
+
+struct StreamReset {
+  float* win[kStreamMaxWins];         // B x hist x dim, row b at b * hist * dim
+  const float* seed[kStreamMaxWins];  // list entry j's first copied frame at seed[i] + j * seed_ld[i]
+  long seed_ld[kStreamMaxWins];
+  int hist[kStreamMaxWins];
+  int dim[kStreamMaxWins];
+  int lead[kStreamMaxWins];           // 1: the window's frame 0 is zeroed and the seed fills frames 1.. (the prev_p1_face window)
+  int count;
+  int rows[kResetMaxRows];
+};
+
+// Workgroup (i, j): window i of session row rows[j], or (i = count) that row's coupling state h / c (all Ks flow steps) and its frame
+// counter. Only the listed rows are written; max |v| of every seed value copied is folded into the guard word (never cleared here).
+__global__ __launch_bounds__(256) void stream_reset_rows_kernel(StreamReset r, float* __restrict__ h, float* __restrict__ cstate, int B,
+                                                                int Ks, int H, float* __restrict__ frame_nb, unsigned* __restrict__ guard) {
+  const int j = blockIdx.y;
+  const int i = blockIdx.x;
+  const long b = r.rows[j];
+  unsigned m = 0u;
+  if (i < r.count) {
+    const int dim = r.dim[i];
+    const long n = (long)r.hist[i] * dim;
+    const long lead = r.lead[i] ? dim : 0;
+    float* win = r.win[i] + b * n;
+    const float* src = r.seed[i] + (long)j * r.seed_ld[i];
+    for (long e = threadIdx.x; e < n; e += 256) {
+      float v = 0.0f;
+      if (e >= lead) {
+        v = src[e - lead];
+        const unsigned a = stream_abs_bits(v);
+        m = a > m ? a : m;
+      }
+      win[e] = v;
+    }
+  } else {
+    // h / c: [Ks][B][H]. A zero row is what a null h_prev / c_prev gives the reverse cells (first_frame = 0)
+    for (int k = 0; k < Ks; ++k) {
+      const long o = ((long)k * B + b) * H;
+      for (int c = threadIdx.x; c < H; c += 256) {
+        h[o + c] = 0.0f;
+        if (cstate) cstate[o + c] = 0.0f;
+      }
+    }
+    if (frame_nb && threadIdx.x == 0) frame_nb[b] = -1.0f;   // the next advance's + 2 makes it inference's 1
+  }
+  if (!guard) return;
+  // One atomic per workgroup, and none when the word already holds as much: it only grows between the session's clears (which are
+  // stream-ordered before this launch), so a read at least m means the result is at least m. Atomics on the one word serialise
+  // (~10 ns each on this chip): one per wave was most of a 64-row launch.
+  __shared__ unsigned wmax[4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
+    m = t > m ? t : m;
+  }
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = wmax[0];
+    for (int w = 1; w < 4; ++w) m = wmax[w] > m ? wmax[w] : m;
+    if (m > __atomic_load_n(guard, __ATOMIC_RELAXED)) atomicMax(guard, m);
+  }
+}
+
 }  // namespace
 
 extern "C" int lfi_stream_advance(int B, int count, float* const* win, const float* const* src, const int* hist, const int* dim,
@@ -83,5 +156,43 @@ extern "C" int lfi_stream_advance(int B, int count, float* const* win, const flo
   hipLaunchKernelGGL(stream_advance_kernel, dim3(count + 1, B), dim3(256), 0, (hipStream_t)stream, w, noise, noise_dst, C, frame_nb,
                      guard_bits);
   LFI_LAUNCH_CHECK("lfi_stream_advance");
+  return LFI_OK;
+}
+
+extern "C" int lfi_stream_reset_rows(int B, int nrows, const int* rows, int count, float* const* win, const float* const* seed,
+                                     const long* seed_ld, const int* hist, const int* dim, const int* lead_zero, float* h, float* cstate,
+                                     int Ks, int H, float* frame_nb, unsigned* guard_bits, void* stream) {
+  LFI_REQUIRE(B > 0 && B <= 65535, "lfi_stream_reset_rows: batch %d (1 .. 65535)", B);
+  LFI_REQUIRE(nrows >= 1 && nrows <= B, "lfi_stream_reset_rows: %d rows (1 .. batch %d)", nrows, B);
+  LFI_REQUIRE(rows, "lfi_stream_reset_rows: null row list");
+  LFI_REQUIRE(count >= 0 && count <= kStreamMaxWins, "lfi_stream_reset_rows: %d windows (at most %d)", count, kStreamMaxWins);
+  LFI_REQUIRE(count == 0 || (win && seed && seed_ld && hist && dim && lead_zero), "lfi_stream_reset_rows: null window table");
+  LFI_REQUIRE(h && Ks > 0 && H > 0, "lfi_stream_reset_rows: null h / Ks = %d, H = %d", Ks, H);
+  StreamReset r = {};
+  for (int i = 0; i < count; ++i) {
+    LFI_REQUIRE(win[i] && hist[i] > 0 && dim[i] > 0 && (lead_zero[i] == 0 || lead_zero[i] == 1),
+                "lfi_stream_reset_rows: window %d: hist %d, dim %d, lead_zero %d", i, hist[i], dim[i], lead_zero[i]);
+    const long frames = hist[i] - lead_zero[i];
+    LFI_REQUIRE(frames == 0 || (seed[i] && seed_ld[i] >= frames * dim[i]),
+                "lfi_stream_reset_rows: window %d: null seed or seed row stride %ld < %ld", i, seed_ld[i], frames * dim[i]);
+    r.win[i] = win[i]; r.seed[i] = frames ? seed[i] : nullptr; r.seed_ld[i] = seed_ld[i];
+    r.hist[i] = hist[i]; r.dim[i] = dim[i]; r.lead[i] = lead_zero[i];
+  }
+  r.count = count;
+  std::vector<unsigned char> seen(B, 0);
+  for (int j = 0; j < nrows; ++j) {
+    LFI_REQUIRE(rows[j] >= 0 && rows[j] < B, "lfi_stream_reset_rows: row %d of the list is %d, outside the batch (0 .. %d)", j, rows[j],
+                B - 1);
+    LFI_REQUIRE(!seen[rows[j]], "lfi_stream_reset_rows: row %d is listed twice", rows[j]);
+    seen[rows[j]] = 1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  for (int j0 = 0; j0 < nrows; j0 += kResetMaxRows) {
+    const int n = nrows - j0 < kResetMaxRows ? nrows - j0 : kResetMaxRows;
+    for (int i = 0; i < count; ++i) r.seed[i] = r.seed[i] ? seed[i] + (long)j0 * seed_ld[i] : nullptr;
+    for (int j = 0; j < n; ++j) r.rows[j] = rows[j0 + j];
+    hipLaunchKernelGGL(stream_reset_rows_kernel, dim3(count + 1, n), dim3(256), 0, st, r, h, cstate, B, Ks, H, frame_nb, guard_bits);
+    LFI_LAUNCH_CHECK("lfi_stream_reset_rows");
+  }
   return LFI_OK;
 }

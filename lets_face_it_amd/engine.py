@@ -14,9 +14,11 @@ What the reference does instead: SeqGlow.forward's Python loop over timesteps an
 (/root/reference/code/glow_pytorch/glow/models.py:534-561), ~5.4k ATen calls per timestep.
 """
 import atexit
+import collections
 import ctypes as C
 import math
 import contextlib
+import operator
 import os
 import warnings
 import weakref
@@ -1811,15 +1813,16 @@ class SampleStream:
             self._fill(seed)
 
     # ---- validation (before any launch; the wording of GlowEngine._check_input)
-    def _check_seed(self, seed):
+    def _check_seed(self, seed, B=None):
         s = self.eng.spec
+        B = self.B if B is None else B
         p1 = seed.get("p1_face")
-        self.eng._check_input(p1, "p1_face", self.B, s.start, s.C)
+        self.eng._check_input(p1, "p1_face", B, s.start, s.C)
         for e in self.mods:
             x = seed.get(e.name)
             if x is None:
                 raise KeyError("batch is missing modality %r" % e.name)
-            self.eng._check_input(x, e.name, self.B, s.start, e.in_dim)
+            self.eng._check_input(x, e.name, B, s.start, e.in_dim)
             if x.device != p1.device:
                 raise ValueError("%s: on %s, the seed's p1_face on %s" % (e.name, x.device, p1.device))
 
@@ -1875,6 +1878,56 @@ class SampleStream:
         self._check_seed(seed)
         with self._on_stream(), self._owned():
             self._fill(seed)
+
+    def reset_rows(self, rows, seed):
+        """Start new sequences in the listed batch rows only, between steps (a conversation joins a batched session in a row another
+        one left). rows: a sequence of distinct ints in [0, B), or a CPU integer tensor; seed: as reset()'s, with batch len(rows) -
+        entry j goes to session row rows[j]. Every other row carries on undisturbed. One launch (lfi_stream_reset_rows), no host wait;
+        the captured graph, `steps` (frames since the open / reset(), which also index injected masks) and the per-frame arithmetic
+        are kept. A seed beyond the fp16 pieces' range is reported by the next steps' range guard, as a frame's would be."""
+        s, eng = self.eng.spec, self.eng
+        self._check_usable()
+        if torch.is_tensor(rows):
+            if rows.is_cuda or rows.is_floating_point() or rows.is_complex() or rows.dtype == torch.bool or rows.dim() > 1:
+                raise ValueError("rows: expected a sequence of ints or a 1-D CPU integer tensor, got %s %s on %s"
+                                 % (tuple(rows.shape), rows.dtype, rows.device))
+            rows = rows.reshape(-1).tolist()
+        else:
+            try:
+                rows = [operator.index(r) for r in rows]
+            except TypeError:
+                raise ValueError("rows: expected a sequence of ints or a 1-D CPU integer tensor, got %r" % (rows,)) from None
+        if not rows:
+            raise ValueError("rows: empty list")
+        bad = [r for r in rows if not 0 <= r < self.B]
+        if bad:
+            raise ValueError("rows: %s outside the session's batch (0 .. %d)" % (bad, self.B - 1))
+        if len(set(rows)) != len(rows):
+            raise ValueError("rows: %s listed more than once" % sorted(r for r, c in collections.Counter(rows).items() if c > 1))
+        n = len(rows)
+        p1 = seed.get("p1_face") if isinstance(seed, dict) else None
+        if p1 is None:
+            raise KeyError("batch is missing modality 'p1_face'")
+        self._check_seed(seed, n)
+        if p1.device != self.device:
+            raise ValueError("p1_face: on %s, the session on %s" % (p1.device, self.device))
+        mods = [(self.windows[e.name], seed[e.name], e.hist, e.in_dim, 0) for e in self.mods]
+        mods.append((self.faces, seed["p1_face"], self.hist1 + 1, s.C, 1))
+        k = len(mods)
+        win_p, seed_p = (C.c_void_p * k)(), (C.c_void_p * k)()
+        seed_ld, hist, dim, lead = (C.c_long * k)(), (C.c_int * k)(), (C.c_int * k)(), (C.c_int * k)()
+        for i, (w, x, hi, d, z) in enumerate(mods):
+            # frames start - (hist - z) .. start - 1 of every seed entry; z = 1: the window's frame 0 is zeroed instead
+            win_p[i], seed_p[i] = w.data_ptr(), x.data_ptr() + 4 * (s.start - (hi - z)) * d
+            seed_ld[i], hist[i], dim[i], lead[i] = x.shape[1] * d, hi, d, z
+        row_a = (C.c_int * n)(*rows)
+        with self._on_stream(), self._owned():
+            check(eng.L.lfi_stream_reset_rows(self.B, n, row_a, k, win_p, seed_p, seed_ld, hist, dim, lead, self.h.data_ptr(),
+                                              ptr(self.cs), s.Ks, s.H, ptr(self.frame_nb), self.guard.data_ptr(), _stream()),
+                  "lfi_stream_reset_rows")
+            if self._stream is not None and torch.cuda.current_stream(self.device) == self._stream:
+                for _, x, _, _, _ in mods:
+                    x.record_stream(self._stream)
 
     def _fill(self, seed):
         s, h1 = self.eng.spec, self.hist1

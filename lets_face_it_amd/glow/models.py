@@ -533,7 +533,13 @@ class SeqGlow(nn.Module):
         {modality: (B, dim)} = frame t of every modality with history > 0 -> the generated p1_face frame t (B, C); without `noise`
         a step draws GaussianDiag.sample((B, C), eps) (eps: hparams.Infer["eps"] by default). reset(seed), close(), and a context
         manager. Same inputs and noise give what inference() gives. Dropout as inference(): masks from _draw_masks(B, 1) per step,
-        none in eval mode. The weights are frozen for the session: step() raises after an optimiser step or a parameter load."""
+        none in eval mode. The weights are frozen for the session: step() raises after an optimiser step or a parameter load.
+
+        reset_rows(rows, seed) starts new sequences in the listed batch rows only (seed: as reset()'s with batch len(rows), entry j
+        for row rows[j]); the other rows carry on bit for bit and a reseeded row then gives what a session opened on its seed gives.
+        `steps` still counts the steps since the open / reset(), and injected (N, B, hist) masks still give their row n to session
+        step n - not to the reseeded rows' own frame n. The range guard is per session: a reseed beyond the fp16 pieces' range moves
+        every row to six bf16 products, as such a frame does."""
         p1 = seed.get("p1_face") if isinstance(seed, dict) else None
         if p1 is None:
             raise KeyError("batch is missing modality 'p1_face'")

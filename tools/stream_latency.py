@@ -2,12 +2,18 @@
 alternative without a session: re-running SeqGlow.inference over the whole prefix for every new frame.
 
   python tools/stream_latency.py [--batches 1,16,256] [--steps 200] [--warmup 20] [--prefixes 50,150,300] [--out FILE]
+                                 [--churn 1,16,64 [--churn-batch 256]]
 
 Per batch size: the wall-clock time from step() to the generated frame on the host (a synchronise after every step: what a live agent
 waits for), its GPU time (HIP events around the step), and a per-kernel breakdown from the engine's enable_timing on an eager session
 (LFI_NO_GRAPH=1: inside a replayed graph there are no per-kernel events). Then inference() over a prefix of t frames in total (t - 24
 generated), the cost of frame t without a session. Prints a markdown report (and writes it to --out); the shader clock under load is
-read by bench.py's rocm-smi helper, started before this process touches the GPU."""
+read by bench.py's rocm-smi helper, started before this process touches the GPU.
+
+--churn r1,r2,..: a session of --churn-batch rows serving conversations that come and go - before every step r rows (a different set
+each step) are reseeded with SampleStream.reset_rows. Per r and per caller (on the legacy default stream, as the legs above, and on a
+stream of its own), interleaved step by step in one session: a plain step, reseed + step, and the reseed alone, each timed as above
+(wall clock with a synchronise after it, and HIP events around it)."""
 import argparse
 import os
 import statistics
@@ -25,6 +31,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--prefixes", default="50,150,300")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--churn", default=None, help="rows reseeded before every step, e.g. 1,16,64 (default: no churn leg)")
+    ap.add_argument("--churn-batch", type=int, default=256)
     a = ap.parse_args()
     import bench
     helper = bench.start_smi_helper()       # (before the GPU is initialised: see bench.py)
@@ -119,6 +127,9 @@ def main():
             prefix_rows.append((B, t, statistics.median(times)))
         if clk is not None:
             kernels["clock"] = clk
+    churn = []
+    if a.churn:
+        churn = churn_leg(m, dev, a.churn_batch, [int(v) for v in a.churn.split(",")], a.steps, a.warmup, dims, start, C)
     bench.stop_smi_helper(helper)
 
     lines += ["## One streaming step", "",
@@ -139,12 +150,60 @@ def main():
         lines.append("| %d | %d | %.3f |" % (B, t, ms))
     clk = kernels.get("clock")
     lines += ["", "GPU state under streaming steps at B = %d: %s" % (batches[-1], clk if clk else "not read (no rocm-smi helper)")]
+    if churn:
+        lines += ["", "## Churn: r rows reseeded before every step (B = %d, --churn)" % a.churn_batch, "",
+                  "| r | caller | leg | wall ms, median | wall ms, p90 | GPU ms, median (events) |", "|---|---|---|---|---|---|"]
+        for r, caller, leg, med, p90, gmed in churn:
+            lines.append("| %d | %s | %s | %.3f | %.3f | %.3f |" % (r, caller, leg, med, p90, gmed))
     text = "\n".join(lines) + "\n"
     print(text)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write(text)
+
+
+def churn_leg(m, dev, B, rs, steps, warmup, dims, start, C):
+    """Per r and caller: (r, caller, leg, wall median, wall p90, GPU median) for the legs step / reseed + step / reseed, interleaved
+    in one session."""
+    import torch
+    gd = torch.Generator().manual_seed(B + 1)
+    total = warmup + steps
+    data = {k: torch.randn(B, start + total, d, generator=gd).to(dev) for k, d in dims.items()}
+    seed = {k: v[:, :start].contiguous() for k, v in data.items()}
+    frames = [{k: v[:, start + n].contiguous() for k, v in data.items() if k != "p1_face"} for n in range(total)]
+    noise = (torch.randn(total, B, C, generator=gd) * 0.8).to(dev)
+    joining = {k: torch.randn(max(rs), start, d, generator=gd).to(dev) for k, d in dims.items()}   # the new conversations' seeds
+    out = []
+    own = torch.cuda.Stream(device=dev)
+    for r, caller in [(r, c) for r in rs for c in ("default stream", "own stream")]:
+        nseed = {k: v[:r].contiguous() for k, v in joining.items()}
+        order = torch.randperm(B, generator=gd).tolist()
+        legs = {"step": ([], []), "reseed + step": ([], []), "reseed": ([], [])}
+        own.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(own if caller == "own stream" else torch.cuda.current_stream(dev)), m.open_stream(seed) as st:
+            for n in range(total):
+                rows = [order[(n * r + j) % B] for j in range(r)]
+                for leg, (wall, gpu) in legs.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    e0.record()
+                    if leg != "step":
+                        st.reset_rows(rows, nseed)
+                    if leg != "reseed":
+                        st.step(frames[n], noise[n])
+                    e1.record()
+                    e1.synchronize()
+                    t1 = time.perf_counter()
+                    if n >= warmup:
+                        wall.append((t1 - t0) * 1e3)
+                        gpu.append(e0.elapsed_time(e1))
+        torch.cuda.synchronize()
+        for leg, (wall, gpu) in legs.items():
+            wall.sort()
+            out.append((r, caller, leg, statistics.median(wall), wall[int(0.9 * (len(wall) - 1))], statistics.median(gpu)))
+    return out
 
 
 if __name__ == "__main__":
