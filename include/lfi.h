@@ -426,6 +426,28 @@ int lfi_stream_advance(int B, int count, float* const* win, const float* const* 
 int lfi_stream_reset_rows(int B, int nrows, const int* rows, int count, float* const* win, const float* const* seed,
                           const long* seed_ld, const int* hist, const int* dim, const int* lead_zero, float* h, float* cstate,
                           int Ks, int H, float* frame_nb, unsigned* guard_bits, void* stream);
+/* Live rows out of and into a streaming sampling session (SampleStream.save_rows / load_rows), between steps. The reference keeps
+ * this state as plain attributes (the coupling cells' f_seq.hidden, glow/models.py:193-194, and inference()'s local windows); here it
+ * lives in session-owned buffers, and these two copy listed rows of it to and from plain fp32 records. A row's record, in order:
+ * every window i (count <= 8, the layout of lfi_stream_advance with the prev_p1_face window last; hist[i] x dim[i] floats each), h
+ * (Ks x H), c (Ks x H; only with cstate, LSTM), the frame counter (one float; only with frame_nb). lfi_stream_row_floats returns
+ * the record's length R (host arithmetic only; -1 on a bad argument) and is the single definition of that layout: both kernels take
+ * their offsets from the same table. A record does not depend on B or on the session's per-frame arithmetic.
+ * save: record j of `out` (row stride ld_out >= R floats, nrows records) receives the state of session row rows[j]; nothing of the
+ * session is written. zero_state != 0 writes zeros for h / c: a session that has not stepped since its open / reset ignores what
+ * those buffers hold (first_frame = 0), and zeros are what that means.
+ * load: session row rows[j] receives record entries[j] of `in` (nentries records, row stride ld_in >= R); an entry may be listed
+ * more than once (a branch), a row may not. Only the listed rows are written. max |v| of the windows and of c is folded into
+ * *guard_bits as lfi_stream_reset_rows does (never cleared; |h| < 1, and the counter is a frame number, not a model input).
+ * Both: rows (and entries) travel in the kernel arguments, 256 per launch - allocation-free, no host staging, no host wait,
+ * capturable; every argument, every row and entry included, is checked before the first launch. */
+long lfi_stream_row_floats(int count, const int* hist, const int* dim, int Ks, int H, int lstm, int has_frame_nb);
+int lfi_stream_save_rows(int B, int nrows, const int* rows, int count, const float* const* win, const int* hist, const int* dim,
+                         const float* h, const float* cstate, int Ks, int H, const float* frame_nb, int zero_state, float* out,
+                         long ld_out, void* stream);
+int lfi_stream_load_rows(int B, int nrows, const int* rows, const int* entries, int nentries, int count, float* const* win,
+                         const int* hist, const int* dim, float* h, float* cstate, int Ks, int H, float* frame_nb, const float* in,
+                         long ld_in, unsigned* guard_bits, void* stream);
 
 /* ---------------------------------------------------------------- optimiser (configure_optimizers, glow/lets_face_it_glow.py:61-72)
  * Flat-buffer Adam with global-norm gradient clipping (Trainer gradient_clip_val, hparams/final_model.yaml:126):

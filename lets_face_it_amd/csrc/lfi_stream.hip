@@ -5,7 +5,9 @@
 // all of it forward by one frame on the caller's stream; the static part and the reverse chain of the step (a captured graph) then
 // read only session-owned, fixed-address memory. What SeqGlow.inference does with whole sequences (glow/models.py:567-596), one
 // frame at a time. A second entry point puts listed batch rows back to the state of the open (SampleStream.reset_rows), between
-// steps, leaving the other rows alone: conversations join and leave one batched session independently.
+// steps, leaving the other rows alone: conversations join and leave one batched session independently. Two more copy listed rows'
+// live state out of a session into plain fp32 records and back into any session of the same model (SampleStream.save_rows /
+// load_rows): conversations move between sessions, pause on the host, branch and roll back.
 #include "lfi_common.h"
 
 #include <vector>
@@ -139,6 +141,133 @@ __global__ __launch_bounds__(256) void stream_reset_rows_kernel(StreamReset r, f
   }
 }
 
+// ---- live rows out of and into a session (SampleStream.save_rows / load_rows): a conversation's whole state as one record
+//
+// A row's record is plain fp32, in this order: every window (count of them, the prev_p1_face window last, hist[i] x dim[i] each), h
+// (Ks x H), c (Ks x H, LSTM only), the frame counter (one float, only with a counter). stream_record() is the one definition of that
+// layout: lfi_stream_row_floats returns its R and both kernels take their offsets from it.
+struct StreamRecord {
+  long win[kStreamMaxWins];   // first float of window i
+  long h, c, nb;              // first float of h / c / the counter (c, nb: -1 = not in the record)
+  long R;
+};
+
+StreamRecord stream_record(int count, const int* hist, const int* dim, int Ks, int H, int lstm, int has_frame_nb) {
+  StreamRecord t = {};
+  long o = 0;
+  for (int i = 0; i < count; ++i) { t.win[i] = o; o += (long)hist[i] * dim[i]; }
+  t.h = o; o += (long)Ks * H;
+  t.c = lstm ? o : -1; o += lstm ? (long)Ks * H : 0;
+  t.nb = has_frame_nb ? o : -1; o += has_frame_nb ? 1 : 0;
+  t.R = o;
+  return t;
+}
+
+struct StreamMove {
+  float* win[kStreamMaxWins];         // B x hist x dim, row b at b * hist * dim
+  int hist[kStreamMaxWins];
+  int dim[kStreamMaxWins];
+  StreamRecord rec;
+  int count;
+  int rows[kResetMaxRows];            // session row of list position j
+  int entries[kResetMaxRows];         // record of list position j (save: j itself, counted over the whole list)
+};
+
+// Workgroup (i, j): window i of session row rows[j], or (i = count) that row's coupling state h / c (all Ks flow steps) and its frame
+// counter, between the session's buffers and record entries[j] of `data` (row stride ld). LOAD = false: session -> record, nothing
+// of the session is written; zero_state writes zeros for h / c (a session that has not stepped: its first launch ignores what the
+// buffers hold). LOAD = true: record -> session, only the listed rows are written, and max |v| of the windows and of c is folded
+// into the guard word as stream_reset_rows_kernel does (|h| < 1; the counter is a frame number, which lfi_stream_advance does not
+// fold either).
+template <bool LOAD>
+__global__ __launch_bounds__(256) void stream_move_rows_kernel(StreamMove r, float* __restrict__ h, float* __restrict__ cstate, int B,
+                                                               int Ks, int H, float* __restrict__ frame_nb, int zero_state,
+                                                               float* __restrict__ data, long ld, unsigned* __restrict__ guard) {
+  const int j = blockIdx.y;
+  const int i = blockIdx.x;
+  const long b = r.rows[j];
+  float* rec = data + (long)r.entries[j] * ld;
+  unsigned m = 0u;
+  if (i < r.count) {
+    const long n = (long)r.hist[i] * r.dim[i];
+    float* win = r.win[i] + b * n;
+    float* rw = rec + r.rec.win[i];
+    for (long e = threadIdx.x; e < n; e += 256) {
+      if (LOAD) {
+        const float v = rw[e];
+        const unsigned a = stream_abs_bits(v);
+        m = a > m ? a : m;
+        win[e] = v;
+      } else {
+        rw[e] = win[e];
+      }
+    }
+  } else {
+    // h / c: [Ks][B][H] in the session, [Ks][H] in the record
+    for (int k = 0; k < Ks; ++k) {
+      const long o = ((long)k * B + b) * H;
+      const long q = (long)k * H;
+      for (int c = threadIdx.x; c < H; c += 256) {
+        if (LOAD) {
+          h[o + c] = rec[r.rec.h + q + c];
+          if (cstate) {
+            const float v = rec[r.rec.c + q + c];
+            const unsigned a = stream_abs_bits(v);
+            m = a > m ? a : m;
+            cstate[o + c] = v;
+          }
+        } else {
+          rec[r.rec.h + q + c] = zero_state ? 0.0f : h[o + c];
+          if (cstate) rec[r.rec.c + q + c] = zero_state ? 0.0f : cstate[o + c];
+        }
+      }
+    }
+    if (frame_nb && threadIdx.x == 0) {
+      if (LOAD) frame_nb[b] = rec[r.rec.nb];
+      else rec[r.rec.nb] = frame_nb[b];
+    }
+  }
+  if (!LOAD || !guard) return;
+  // (one atomic per workgroup, none when the word already holds as much: see stream_reset_rows_kernel)
+  __shared__ unsigned wmax[4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
+    m = t > m ? t : m;
+  }
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = wmax[0];
+    for (int w = 1; w < 4; ++w) m = wmax[w] > m ? wmax[w] : m;
+    if (m > __atomic_load_n(guard, __ATOMIC_RELAXED)) atomicMax(guard, m);
+  }
+}
+
+// The argument checks save and load share (everything but the record side); fills r and the layout table.
+int stream_move_args(const char* what, int B, int nrows, const int* rows, int count, float* const* win, const int* hist, const int* dim,
+                     const float* h, const float* cstate, int Ks, int H, const float* frame_nb, StreamMove* r) {
+  LFI_REQUIRE(B > 0 && B <= 65535, "%s: batch %d (1 .. 65535)", what, B);
+  LFI_REQUIRE(nrows >= 1 && nrows <= B, "%s: %d rows (1 .. batch %d)", what, nrows, B);
+  LFI_REQUIRE(rows, "%s: null row list", what);
+  LFI_REQUIRE(count >= 0 && count <= kStreamMaxWins, "%s: %d windows (at most %d)", what, count, kStreamMaxWins);
+  LFI_REQUIRE(count == 0 || (win && hist && dim), "%s: null window table", what);
+  LFI_REQUIRE(h && Ks > 0 && H > 0, "%s: null h / Ks = %d, H = %d", what, Ks, H);
+  for (int i = 0; i < count; ++i) {
+    LFI_REQUIRE(win[i] && hist[i] > 0 && dim[i] > 0, "%s: window %d: hist %d, dim %d", what, i, hist[i], dim[i]);
+    r->win[i] = win[i]; r->hist[i] = hist[i]; r->dim[i] = dim[i];
+  }
+  r->count = count;
+  r->rec = stream_record(count, hist, dim, Ks, H, cstate != nullptr, frame_nb != nullptr);
+  std::vector<unsigned char> seen(B, 0);
+  for (int j = 0; j < nrows; ++j) {
+    LFI_REQUIRE(rows[j] >= 0 && rows[j] < B, "%s: row %d of the list is %d, outside the batch (0 .. %d)", what, j, rows[j], B - 1);
+    LFI_REQUIRE(!seen[rows[j]], "%s: row %d is listed twice", what, rows[j]);
+    seen[rows[j]] = 1;
+  }
+  return LFI_OK;
+}
+
 }  // namespace
 
 extern "C" int lfi_stream_advance(int B, int count, float* const* win, const float* const* src, const int* hist, const int* dim,
@@ -193,6 +322,61 @@ extern "C" int lfi_stream_reset_rows(int B, int nrows, const int* rows, int coun
     for (int j = 0; j < n; ++j) r.rows[j] = rows[j0 + j];
     hipLaunchKernelGGL(stream_reset_rows_kernel, dim3(count + 1, n), dim3(256), 0, st, r, h, cstate, B, Ks, H, frame_nb, guard_bits);
     LFI_LAUNCH_CHECK("lfi_stream_reset_rows");
+  }
+  return LFI_OK;
+}
+
+extern "C" long lfi_stream_row_floats(int count, const int* hist, const int* dim, int Ks, int H, int lstm, int has_frame_nb) {
+  LFI_REQUIRE(count >= 0 && count <= kStreamMaxWins, "lfi_stream_row_floats: %d windows (at most %d)", count, kStreamMaxWins);
+  LFI_REQUIRE(count == 0 || (hist && dim), "lfi_stream_row_floats: null window table");
+  LFI_REQUIRE(Ks > 0 && H > 0, "lfi_stream_row_floats: Ks = %d, H = %d", Ks, H);
+  for (int i = 0; i < count; ++i)
+    LFI_REQUIRE(hist[i] > 0 && dim[i] > 0, "lfi_stream_row_floats: window %d: hist %d, dim %d", i, hist[i], dim[i]);
+  return stream_record(count, hist, dim, Ks, H, lstm != 0, has_frame_nb != 0).R;
+}
+
+extern "C" int lfi_stream_save_rows(int B, int nrows, const int* rows, int count, const float* const* win, const int* hist,
+                                    const int* dim, const float* h, const float* cstate, int Ks, int H, const float* frame_nb,
+                                    int zero_state, float* out, long ld_out, void* stream) {
+  StreamMove r = {};
+  // (the save kernel only reads the session's buffers: one kernel body serves both directions, hence the casts)
+  const int rc = stream_move_args("lfi_stream_save_rows", B, nrows, rows, count, const_cast<float* const*>(win), hist, dim, h, cstate, Ks,
+                                  H, frame_nb, &r);
+  if (rc != LFI_OK) return rc;
+  LFI_REQUIRE(out, "lfi_stream_save_rows: null out");
+  LFI_REQUIRE(ld_out >= r.rec.R, "lfi_stream_save_rows: record stride %ld below the record's %ld floats", ld_out, r.rec.R);
+  hipStream_t st = (hipStream_t)stream;
+  for (int j0 = 0; j0 < nrows; j0 += kResetMaxRows) {
+    const int n = nrows - j0 < kResetMaxRows ? nrows - j0 : kResetMaxRows;
+    for (int j = 0; j < n; ++j) { r.rows[j] = rows[j0 + j]; r.entries[j] = j0 + j; }
+    hipLaunchKernelGGL(stream_move_rows_kernel<false>, dim3(count + 1, n), dim3(256), 0, st, r, const_cast<float*>(h),
+                       const_cast<float*>(cstate), B, Ks, H, const_cast<float*>(frame_nb), zero_state ? 1 : 0, out, ld_out,
+                       (unsigned*)nullptr);
+    LFI_LAUNCH_CHECK("lfi_stream_save_rows");
+  }
+  return LFI_OK;
+}
+
+extern "C" int lfi_stream_load_rows(int B, int nrows, const int* rows, const int* entries, int nentries, int count, float* const* win,
+                                    const int* hist, const int* dim, float* h, float* cstate, int Ks, int H, float* frame_nb,
+                                    const float* in, long ld_in, unsigned* guard_bits, void* stream) {
+  StreamMove r = {};
+  const int rc = stream_move_args("lfi_stream_load_rows", B, nrows, rows, count, win, hist, dim, h, cstate, Ks, H, frame_nb, &r);
+  if (rc != LFI_OK) return rc;
+  LFI_REQUIRE(in, "lfi_stream_load_rows: null in");
+  LFI_REQUIRE(nentries >= 1, "lfi_stream_load_rows: %d saved entries (at least 1)", nentries);
+  LFI_REQUIRE(entries, "lfi_stream_load_rows: null entry list");
+  for (int j = 0; j < nrows; ++j)
+    LFI_REQUIRE(entries[j] >= 0 && entries[j] < nentries, "lfi_stream_load_rows: entry %d of the list is %d, outside the saved entries (0 .. %d)",
+                j, entries[j], nentries - 1);
+  LFI_REQUIRE(ld_in >= r.rec.R, "lfi_stream_load_rows: record stride %ld below the record's %ld floats", ld_in, r.rec.R);
+  hipStream_t st = (hipStream_t)stream;
+  for (int j0 = 0; j0 < nrows; j0 += kResetMaxRows) {
+    const int n = nrows - j0 < kResetMaxRows ? nrows - j0 : kResetMaxRows;
+    for (int j = 0; j < n; ++j) { r.rows[j] = rows[j0 + j]; r.entries[j] = entries[j0 + j]; }
+    hipLaunchKernelGGL(stream_move_rows_kernel<true>, dim3(count + 1, n), dim3(256), 0, st, r, h, cstate, B, Ks, H, frame_nb, 0,
+                       const_cast<float*>(in), ld_in, guard_bits);
+    LFI_LAUNCH_CHECK("lfi_stream_load_rows");
   }
   return LFI_OK;
 }

@@ -1727,6 +1727,64 @@ class GlowEngine:
 # the static part and the chain writes, and the per-parameter-state preparation they read (run_prep's outputs)
 _SESSION_ATTRS = ("_ws", "prep", "wct_f", "_wct_planes", "_wc_r", "_cond_planes", "_enc_stash_f16")
 _STREAM_GUARD_LIMIT = 1e3   # max |x| the fp16-piece per-frame arithmetic accepts (as GlowEngine._sample)
+_PARAMS_CHANGED = ("SampleStream: the model's parameters changed since open_stream (optimiser step, parameter load or "
+                   "ActNorm init): a session samples with the weights of its open; open a new one")
+_ROW_FIELDS = ("C", "H", "Ks", "rnn_type", "use_frame_nb", "windows", "hist1", "R")
+
+
+class StreamRows:
+    """The live state of n conversations taken out of a streaming session (SampleStream.save_rows): `data`, one contiguous float32
+    (n, R) tensor of records, and `signature`, the record layout (C, H, Ks, rnn_type, use_frame_nb, ((name, hist, dim), ...), hist1,
+    R). A record is, in order: every conditioning window of SampleStream.mods (hist x in_dim each), the faces window ((hist1 + 1) x
+    C), h (Ks x H), c (Ks x H, LSTM only), the frame counter (one float, only with use_frame_nb) - the layout lfi_stream_row_floats
+    defines. Plain fp32 values: independent of the session's batch size and per-frame arithmetic. load_rows puts entries back into
+    rows of any session of the same model; cpu() / to(device) pause and resume, state_dict() / from_state_dict() store."""
+
+    def __init__(self, data, signature, _engine=None, _param_version=None):
+        self.data = data
+        self.signature = self._canonical(signature)
+        self._engine, self._param_version = _engine, _param_version   # (same-process check only: not part of state_dict())
+
+    @staticmethod
+    def _canonical(sig):
+        sig = tuple(sig)
+        if len(sig) != len(_ROW_FIELDS):
+            raise ValueError("StreamRows: a layout signature has %d fields %s, got %d" % (len(_ROW_FIELDS), _ROW_FIELDS, len(sig)))
+        C_, H, Ks, rnn, nb, wins, hist1, R = sig
+        return (int(C_), int(H), int(Ks), str(rnn), bool(nb), tuple((str(n), int(h), int(d)) for n, h, d in wins), int(hist1), int(R))
+
+    def __len__(self):
+        return int(self.data.shape[0])
+
+    def _like(self, data):
+        return StreamRows(data, self.signature, self._engine, self._param_version)
+
+    def cpu(self):
+        return self._like(self.data.cpu())
+
+    def to(self, device):
+        return self._like(self.data.to(device).contiguous())
+
+    def select(self, indices):
+        """The listed entries (repeats allowed), as a new StreamRows."""
+        idx = torch.as_tensor(indices, dtype=torch.long, device=self.data.device).reshape(-1)
+        return self._like(self.data.index_select(0, idx))
+
+    def state_dict(self):
+        """One tensor and plain Python values (torch.save-able). Whether the weights are the ones the rows were saved under is the
+        caller's responsibility once the rows leave the process."""
+        d = dict(zip(_ROW_FIELDS, self.signature))
+        d["windows"] = [list(w) for w in d["windows"]]
+        d["data"] = self.data
+        return d
+
+    @classmethod
+    def from_state_dict(cls, d):
+        missing = [k for k in _ROW_FIELDS + ("data",) if k not in d]
+        if missing:
+            raise KeyError("StreamRows.from_state_dict: missing %s" % missing)
+        return cls(d["data"], tuple(d[k] for k in _ROW_FIELDS))
+
 
 
 class SampleStream:
@@ -1810,6 +1868,18 @@ class SampleStream:
                         tensors = [eng.params] + [v for v in seed.values() if torch.is_tensor(v) and v.is_cuda and v.dtype == torch.float32]
                         fp = 9 if eng._read_range_guard(eng._launch_range_guard(tensors[:8])) <= _STREAM_GUARD_LIMIT else 5
             self.frame_precision = int(fp)
+            # the row record of save_rows / load_rows: the windows in record order (mods, then the faces window) and its signature
+            wins = [(e.name, e.hist, e.in_dim, self.windows[e.name]) for e in self.mods] + [("p1_face", self.hist1 + 1, s.C, self.faces)]
+            k = len(wins)
+            self._row_win, self._row_hist, self._row_dim = (C.c_void_p * k)(), (C.c_int * k)(), (C.c_int * k)()
+            for i, (_, hi, d, w) in enumerate(wins):
+                self._row_win[i], self._row_hist[i], self._row_dim[i] = w.data_ptr(), hi, d
+            R = eng.L.lfi_stream_row_floats(k, self._row_hist, self._row_dim, s.Ks, s.H, int(self.cs is not None),
+                                            int(self.frame_nb is not None))
+            if R < 0:
+                check(-1, "lfi_stream_row_floats")
+            self.row_signature = (s.C, s.H, s.Ks, s.rnn_type, bool(s.use_frame_nb), tuple((e.name, e.hist, e.in_dim) for e in self.mods),
+                                  self.hist1, int(R))
             self._fill(seed)
 
     # ---- validation (before any launch; the wording of GlowEngine._check_input)
@@ -1837,8 +1907,7 @@ class SampleStream:
         if self.closed:
             raise RuntimeError("SampleStream: the session is closed")
         if self.eng.param_version != self.param_version or (self._bound is not None and not self._bound()):
-            raise RuntimeError("SampleStream: the model's parameters changed since open_stream (optimiser step, parameter load or "
-                               "ActNorm init): a session samples with the weights of its open; open a new one")
+            raise RuntimeError(_PARAMS_CHANGED)
 
     # ---- session-owned engine state and stream
     @contextlib.contextmanager
@@ -1879,14 +1948,8 @@ class SampleStream:
         with self._on_stream(), self._owned():
             self._fill(seed)
 
-    def reset_rows(self, rows, seed):
-        """Start new sequences in the listed batch rows only, between steps (a conversation joins a batched session in a row another
-        one left). rows: a sequence of distinct ints in [0, B), or a CPU integer tensor; seed: as reset()'s, with batch len(rows) -
-        entry j goes to session row rows[j]. Every other row carries on undisturbed. One launch (lfi_stream_reset_rows), no host wait;
-        the captured graph, `steps` (frames since the open / reset(), which also index injected masks) and the per-frame arithmetic
-        are kept. A seed beyond the fp16 pieces' range is reported by the next steps' range guard, as a frame's would be."""
-        s, eng = self.eng.spec, self.eng
-        self._check_usable()
+    def _check_rows(self, rows):
+        """rows of reset_rows / save_rows / load_rows -> a list of distinct ints in [0, B)."""
         if torch.is_tensor(rows):
             if rows.is_cuda or rows.is_floating_point() or rows.is_complex() or rows.dtype == torch.bool or rows.dim() > 1:
                 raise ValueError("rows: expected a sequence of ints or a 1-D CPU integer tensor, got %s %s on %s"
@@ -1904,6 +1967,17 @@ class SampleStream:
             raise ValueError("rows: %s outside the session's batch (0 .. %d)" % (bad, self.B - 1))
         if len(set(rows)) != len(rows):
             raise ValueError("rows: %s listed more than once" % sorted(r for r, c in collections.Counter(rows).items() if c > 1))
+        return rows
+
+    def reset_rows(self, rows, seed):
+        """Start new sequences in the listed batch rows only, between steps (a conversation joins a batched session in a row another
+        one left). rows: a sequence of distinct ints in [0, B), or a CPU integer tensor; seed: as reset()'s, with batch len(rows) -
+        entry j goes to session row rows[j]. Every other row carries on undisturbed. One launch (lfi_stream_reset_rows), no host wait;
+        the captured graph, `steps` (frames since the open / reset(), which also index injected masks) and the per-frame arithmetic
+        are kept. A seed beyond the fp16 pieces' range is reported by the next steps' range guard, as a frame's would be."""
+        s, eng = self.eng.spec, self.eng
+        self._check_usable()
+        rows = self._check_rows(rows)
         n = len(rows)
         p1 = seed.get("p1_face") if isinstance(seed, dict) else None
         if p1 is None:
@@ -1929,6 +2003,81 @@ class SampleStream:
                 for _, x, _, _, _ in mods:
                     x.record_stream(self._stream)
 
+    def save_rows(self, rows):
+        """The live state of the listed rows, between steps -> StreamRows with len(rows) entries, entry j = session row rows[j] (rows:
+        as reset_rows'). One launch per 256 rows (lfi_stream_save_rows) on the caller's stream, no host wait; the session is not
+        changed. A session that has not stepped since its open / reset() saves zeros for h / c: its first step ignores what those
+        buffers hold."""
+        s, eng = self.eng.spec, self.eng
+        self._check_usable()
+        rows = self._check_rows(rows)
+        n, R = len(rows), self.row_signature[-1]
+        row_a = (C.c_int * n)(*rows)
+        with self._on_stream(), self._owned():
+            out = torch.empty(n, R, dtype=torch.float32, device=self.device)
+            check(eng.L.lfi_stream_save_rows(self.B, n, row_a, len(self._row_win), self._row_win, self._row_hist, self._row_dim,
+                                             self.h.data_ptr(), ptr(self.cs), s.Ks, s.H, ptr(self.frame_nb),
+                                             int(self.steps == 0 and not self._resumed), out.data_ptr(), R, _stream()),
+                  "lfi_stream_save_rows")
+        if self._stream is not None:
+            out.record_stream(torch.cuda.current_stream(self.device))
+        return StreamRows(out, self.row_signature, weakref.ref(eng), self.param_version)
+
+    def load_rows(self, rows, saved, entries=None):
+        """Put saved conversations into the listed rows, between steps: entry entries[j] of `saved` (a StreamRows of this model, from
+        any session, batch size or device round trip) goes to session row rows[j]; entries defaults to range(len(rows)) and may
+        repeat (a branch). Only the listed rows are written; one launch per 256 rows (lfi_stream_load_rows), no host wait; `steps`,
+        the captured graph and the per-frame arithmetic are kept, and a value beyond the fp16 pieces' range is reported by the next
+        steps' range guard, as a reseed's would be. Everything is checked before the first launch: a refused call leaves the
+        session as it was. Into a session that has not stepped yet, h / c of every row are zeroed first and the first step runs as
+        a continuing one (a zeroed row is a first frame's state)."""
+        s, eng = self.eng.spec, self.eng
+        self._check_usable()
+        rows = self._check_rows(rows)
+        n = len(rows)
+        if not isinstance(saved, StreamRows):
+            raise TypeError("saved: expected a StreamRows (SampleStream.save_rows), got %s" % type(saved).__name__)
+        for name, mine, theirs in zip(_ROW_FIELDS, self.row_signature, saved.signature):
+            if mine != theirs:
+                raise ValueError("saved: layout signature differs in %s: the session's is %r, the saved rows' %r" % (name, mine, theirs))
+        R, x = self.row_signature[-1], saved.data
+        if not (torch.is_tensor(x) and x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.is_contiguous()
+                and x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] == R):
+            raise ValueError("saved.data: expected contiguous float32 GPU tensor (n>=1, R=%d) on %s, got %s %s on %s"
+                             % (R, self.device, tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x)), getattr(x, "device", None)))
+        if entries is None:
+            entries = list(range(n))
+        elif torch.is_tensor(entries):
+            if entries.is_cuda or entries.is_floating_point() or entries.is_complex() or entries.dtype == torch.bool or entries.dim() > 1:
+                raise ValueError("entries: expected a sequence of ints or a 1-D CPU integer tensor, got %s %s on %s"
+                                 % (tuple(entries.shape), entries.dtype, entries.device))
+            entries = entries.reshape(-1).tolist()
+        else:
+            try:
+                entries = [operator.index(e) for e in entries]
+            except TypeError:
+                raise ValueError("entries: expected a sequence of ints or a 1-D CPU integer tensor, got %r" % (entries,)) from None
+        if len(entries) != n:
+            raise ValueError("entries: %d listed for %d rows" % (len(entries), n))
+        bad = [e for e in entries if not 0 <= e < len(saved)]
+        if bad:
+            raise ValueError("entries: %s outside the saved rows (0 .. %d)" % (bad, len(saved) - 1))
+        if saved._engine is not None and saved._engine() is eng and saved._param_version != self.param_version:
+            raise RuntimeError(_PARAMS_CHANGED)
+        row_a, ent_a = (C.c_int * n)(*rows), (C.c_int * n)(*entries)
+        with self._on_stream(), self._owned():
+            if self.steps == 0 and not self._resumed:
+                self.h.zero_()          # (stale after a reset(); the first launch would have ignored them)
+                if self.cs is not None:
+                    self.cs.zero_()
+            check(eng.L.lfi_stream_load_rows(self.B, n, row_a, ent_a, len(saved), len(self._row_win), self._row_win, self._row_hist,
+                                             self._row_dim, self.h.data_ptr(), ptr(self.cs), s.Ks, s.H, ptr(self.frame_nb),
+                                             x.data_ptr(), R, self.guard.data_ptr(), _stream()), "lfi_stream_load_rows")
+            if self.steps == 0:
+                self._resumed = True    # the session's first _launch then keeps h / c (first_frame = 1)
+            if self._stream is not None and torch.cuda.current_stream(self.device) == self._stream:
+                x.record_stream(self._stream)
+
     def _fill(self, seed):
         s, h1 = self.eng.spec, self.hist1
         self.faces[:, 0].zero_()    # (row 0 leaves with the first step's shift)
@@ -1939,6 +2088,7 @@ class SampleStream:
             self.frame_nb.fill_(-1.0)   # the first step's + 2 makes it inference's 1
         self.guard.zero_()
         self.steps = 0
+        self._resumed = False           # load_rows into a session that has not stepped sets it: the first launch keeps h / c
         self._guard_pending = None
 
     def close(self):
@@ -2013,7 +2163,7 @@ class SampleStream:
             for x in srcs + [noise]:
                 x.record_stream(torch.cuda.current_stream(self.device))
             if self.steps == 0 or os.environ.get("LFI_NO_GRAPH") == "1":
-                self._launch(masks, 1 if self.steps > 0 else 0)
+                self._launch(masks, 1 if self.steps > 0 or self._resumed else 0)
             else:
                 key = (self.frame_precision, masks is not None)
                 if self._graph is None or self._graph_key != key:

@@ -539,7 +539,16 @@ class SeqGlow(nn.Module):
         for row rows[j]); the other rows carry on bit for bit and a reseeded row then gives what a session opened on its seed gives.
         `steps` still counts the steps since the open / reset(), and injected (N, B, hist) masks still give their row n to session
         step n - not to the reseeded rows' own frame n. The range guard is per session: a reseed beyond the fp16 pieces' range moves
-        every row to six bf16 products, as such a frame does."""
+        every row to six bf16 products, as such a frame does.
+
+        save_rows(rows) -> lets_face_it_amd.engine.StreamRows takes the listed rows' live state out (conditioning windows, the window
+        of generated faces, the coupling cells' h / c of every flow step - the reference's f_seq.hidden, models.py:193-194 - and the
+        frame counter), and load_rows(rows, saved, entries=None) puts entry entries[j] into row rows[j] of this or any other session
+        of the same model, of any batch size: conversations move between sessions, pause (saved.cpu(), .to(device), state_dict() /
+        StreamRows.from_state_dict()), branch (one entry into several rows) and roll back. Both run between steps, in one small
+        launch, without a host wait, and leave the other rows alone. Within one session, or between sessions of one batch size, a
+        moved row continues bit for bit; at another batch size within the session-against-inference() tolerance. Rows saved under
+        other weights are refused on the same engine; across processes equal weights are the caller's responsibility."""
         p1 = seed.get("p1_face") if isinstance(seed, dict) else None
         if p1 is None:
             raise KeyError("batch is missing modality 'p1_face'")

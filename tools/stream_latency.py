@@ -2,7 +2,7 @@
 alternative without a session: re-running SeqGlow.inference over the whole prefix for every new frame.
 
   python tools/stream_latency.py [--batches 1,16,256] [--steps 200] [--warmup 20] [--prefixes 50,150,300] [--out FILE]
-                                 [--churn 1,16,64 [--churn-batch 256]]
+                                 [--churn 1,16,64 [--churn-batch 256]] [--migrate 16 [--migrate-batch 256]]
 
 Per batch size: the wall-clock time from step() to the generated frame on the host (a synchronise after every step: what a live agent
 waits for), its GPU time (HIP events around the step), and a per-kernel breakdown from the engine's enable_timing on an eager session
@@ -13,8 +13,13 @@ read by bench.py's rocm-smi helper, started before this process touches the GPU.
 --churn r1,r2,..: a session of --churn-batch rows serving conversations that come and go - before every step r rows (a different set
 each step) are reseeded with SampleStream.reset_rows. Per r and per caller (on the legacy default stream, as the legs above, and on a
 stream of its own), interleaved step by step in one session: a plain step, reseed + step, and the reseed alone, each timed as above
-(wall clock with a synchronise after it, and HIP events around it)."""
+(wall clock with a synchronise after it, and HIP events around it).
+
+--migrate r1,r2,..: two sessions of --migrate-batch rows; before every step of the first, r of its rows (a different set each step) are
+saved with SampleStream.save_rows and loaded into rows of the second with load_rows - a conversation moving to another session. Per r
+and caller as --churn, interleaved step by step in one process: a plain step, save + load + step, and the save + load pair alone."""
 import argparse
+import contextlib
 import os
 import statistics
 import sys
@@ -33,6 +38,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--churn", default=None, help="rows reseeded before every step, e.g. 1,16,64 (default: no churn leg)")
     ap.add_argument("--churn-batch", type=int, default=256)
+    ap.add_argument("--migrate", default=None, help="rows saved and loaded into a second session before every step, e.g. 16")
+    ap.add_argument("--migrate-batch", type=int, default=256)
     a = ap.parse_args()
     import bench
     helper = bench.start_smi_helper()       # (before the GPU is initialised: see bench.py)
@@ -130,6 +137,9 @@ def main():
     churn = []
     if a.churn:
         churn = churn_leg(m, dev, a.churn_batch, [int(v) for v in a.churn.split(",")], a.steps, a.warmup, dims, start, C)
+    migrate = []
+    if a.migrate:
+        migrate = churn_leg(m, dev, a.migrate_batch, [int(v) for v in a.migrate.split(",")], a.steps, a.warmup, dims, start, C, migrate=True)
     bench.stop_smi_helper(helper)
 
     lines += ["## One streaming step", "",
@@ -155,6 +165,12 @@ def main():
                   "| r | caller | leg | wall ms, median | wall ms, p90 | GPU ms, median (events) |", "|---|---|---|---|---|---|"]
         for r, caller, leg, med, p90, gmed in churn:
             lines.append("| %d | %s | %s | %.3f | %.3f | %.3f |" % (r, caller, leg, med, p90, gmed))
+    if migrate:
+        lines += ["", "## Migration: r rows saved and loaded into a second session before every step (B = %d both, --migrate)"
+                  % a.migrate_batch, "",
+                  "| r | caller | leg | wall ms, median | wall ms, p90 | GPU ms, median (events) |", "|---|---|---|---|---|---|"]
+        for r, caller, leg, med, p90, gmed in migrate:
+            lines.append("| %d | %s | %s | %.3f | %.3f | %.3f |" % (r, caller, leg, med, p90, gmed))
     text = "\n".join(lines) + "\n"
     print(text)
     if a.out:
@@ -163,9 +179,10 @@ def main():
             f.write(text)
 
 
-def churn_leg(m, dev, B, rs, steps, warmup, dims, start, C):
+def churn_leg(m, dev, B, rs, steps, warmup, dims, start, C, migrate=False):
     """Per r and caller: (r, caller, leg, wall median, wall p90, GPU median) for the legs step / reseed + step / reseed, interleaved
-    in one session."""
+    in one session. migrate: the legs step / save + load + step / save + load - r rows of the session saved and loaded into other rows
+    of a second session of the same size (which has stepped once) in place of the reseed."""
     import torch
     gd = torch.Generator().manual_seed(B + 1)
     total = warmup + steps
@@ -179,9 +196,14 @@ def churn_leg(m, dev, B, rs, steps, warmup, dims, start, C):
     for r, caller in [(r, c) for r in rs for c in ("default stream", "own stream")]:
         nseed = {k: v[:r].contiguous() for k, v in joining.items()}
         order = torch.randperm(B, generator=gd).tolist()
-        legs = {"step": ([], []), "reseed + step": ([], []), "reseed": ([], [])}
+        move = "save + load" if migrate else "reseed"
+        legs = {"step": ([], []), move + " + step": ([], []), move: ([], [])}
         own.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(own if caller == "own stream" else torch.cuda.current_stream(dev)), m.open_stream(seed) as st:
+        with torch.cuda.stream(own if caller == "own stream" else torch.cuda.current_stream(dev)), m.open_stream(seed) as st, \
+                contextlib.ExitStack() as stack:
+            if migrate:
+                st2 = stack.enter_context(m.open_stream(seed))
+                st2.step(frames[0], noise[0])
             for n in range(total):
                 rows = [order[(n * r + j) % B] for j in range(r)]
                 for leg, (wall, gpu) in legs.items():
@@ -189,9 +211,11 @@ def churn_leg(m, dev, B, rs, steps, warmup, dims, start, C):
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
                     e0.record()
-                    if leg != "step":
+                    if leg != "step" and migrate:
+                        st2.load_rows([(b + 1) % B for b in rows], st.save_rows(rows))
+                    elif leg != "step":
                         st.reset_rows(rows, nseed)
-                    if leg != "reseed":
+                    if leg != move:
                         st.step(frames[n], noise[n])
                     e1.record()
                     e1.synchronize()
