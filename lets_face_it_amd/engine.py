@@ -9,17 +9,17 @@ module only sequences the C-ABI calls of include/lfi.h:
             (batched GEMM) -> anti-diagonal walk of the (timestep, flow step) grid -> per-frame NLL
   backward  reverse walk -> deferred weight-gradient GEMMs -> cond_transform / encoder BPTT -> flat gradient buffer
   step      global-norm clip + Adam on the flat parameter buffer (one kernel each)
+  sample    the batch sampler (sample) and the steps it shares with the streaming sessions of stream.py (open_stream)
 
 What the reference does instead: SeqGlow.forward's Python loop over timesteps and flow steps
 (/root/reference/code/glow_pytorch/glow/models.py:534-561), ~5.4k ATen calls per timestep.
 """
 import atexit
-import collections
+import contextlib
 import ctypes as C
 import math
-import contextlib
-import operator
 import os
+import struct
 import warnings
 import weakref
 
@@ -27,6 +27,7 @@ import torch
 
 from . import _lib
 from ._lib import EncDesc, FlowDims, FlowGrads, FlowParams, GemmDesc, P1Enc, PGemmDesc, check, ptr, translate_oom
+from .stream import SampleStream, StreamRows  # noqa: F401 - StreamRows: callers import it from here
 
 ENC_ORDER = ("p1_face", "p2_face", "p1_speech", "p2_speech")  # FeatureEncoder concat order (models.py:127-143)
 FLOW_FIELDS = ("an_bias", "an_logs", "inv_l", "inv_u", "inv_logs", "inv_w", "w_ih", "w_hh", "b_ih", "b_hh",
@@ -1371,22 +1372,33 @@ class GlowEngine:
     def sample(self, seq_len, data, noise, masks=None):
         """SeqGlow.inference (models.py:567-596); see _sample. With the static part on a partial-chip stream (LFI_SAMPLE_STATIC_CUS)
         the whole call runs on a private non-blocking stream between two joins with the caller's: hipExtStreamCreateWithCUMask makes a
-        BLOCKING stream, which takes turns with the legacy default stream - and that is the stream most callers are on."""
+        BLOCKING stream, which takes turns with the legacy default stream - and that is the stream most callers are on. (Also without
+        a partial-chip stream when the caller is on the legacy default stream: the per-run graphs are not replayed there.)"""
         caller = torch.cuda.current_stream(self.device)
-        # (also without a partial-chip stream when the caller is on the legacy default stream: the per-run graphs are not replayed
-        # there - with fewer than four hardware queues per process, GPU_MAX_HW_QUEUES=3, hipGraphLaunch into the NULL stream was seen to
-        # segfault inside the HIP runtime on the training step's graph, DESIGN.md 11.5)
-        if self._sample_static_cus(seq_len - self.spec.start) <= 0 and caller != torch.cuda.default_stream(self.device):
-            return self._sample(seq_len, data, noise, masks)
-        if self._sample_stream is None:
-            self._sample_stream = torch.cuda.Stream(device=self.device)
-        own = self._sample_stream
+        with self._off_legacy_stream(self, "_sample_stream", force=self._sample_static_cus(seq_len - self.spec.start) > 0) as st:
+            out = self._sample(seq_len, data, noise, masks)
+        if st != caller:
+            out.record_stream(caller)
+        return out
+
+    @contextlib.contextmanager
+    def _off_legacy_stream(self, owner, attr, force=False):
+        """Never replay a graph into the legacy default stream: with fewer than four hardware queues per process, GPU_MAX_HW_QUEUES=3,
+        hipGraphLaunch into the NULL stream was seen to segfault inside the HIP runtime on the training step's graph.
+        The body runs on the caller's stream unless that is the default one (or `force`): then on the private stream kept in
+        owner.<attr> (created on first use), joined with the caller's on both sides. -> the stream the body runs on."""
+        caller = torch.cuda.current_stream(self.device)
+        if not force and caller != torch.cuda.default_stream(self.device):
+            yield caller
+            return
+        own = getattr(owner, attr)
+        if own is None:
+            own = torch.cuda.Stream(device=self.device)
+            setattr(owner, attr, own)
         own.wait_stream(caller)
         with torch.cuda.stream(own):
-            out = self._sample(seq_len, data, noise, masks)
+            yield own
         caller.wait_stream(own)
-        out.record_stream(caller)
-        return out
 
     def _sample(self, seq_len, data, noise, masks=None):
         """SeqGlow.inference (models.py:567-596) with the prior noise given: (seq_len - start, B, C), already * eps.
@@ -1415,14 +1427,8 @@ class GlowEngine:
         # ---- range guard of the fp16-piece arithmetic: ONE reduction over the caller's tensors, the noise and the parameters,
         # read back through pinned memory on the side stream; the host waits for it only when it picks the per-frame arithmetic,
         # with the first run's static part already queued behind it (no drained queue, no per-tensor sync)
-        fp, guard = self.sample_frame_precision, None
-        if fp is None:
-            fp = 0
-            if self.precision == 1:
-                fp = 5 if self._sample_fp16_unsafe else None
-                if fp is None:
-                    guard = self._launch_range_guard([self.params, noise] + [v for v in data.values() if torch.is_tensor(v)
-                                                                                and v.dtype == torch.float32 and v.is_cuda])
+        fp = self._frame_precision()
+        guard = self._launch_range_guard([self.params, noise] + self._guarded(data)) if fp is None else None
         ev_static = self._tic("sample_static")
         faces = self._buf("sample_faces", B * seq_len * s.C)[:B * seq_len * s.C].view(B, seq_len, s.C)
         faces.zero_()
@@ -1432,10 +1438,7 @@ class GlowEngine:
         e1 = s.encoders[0]             # prev_p1_face: the only autoregressive input
         c1 = (e1.fdim + 3) // 4 * 4    # first column after its block (blocks start on 4-float boundaries)
         pre = self._buf("pre_static", F * KD)
-        planes_ok = s.Ef > c1 and self.precision == 1 and os.environ.get("LFI_PGEMM", "1") != "0"
-        wp = nkw = None
-        if planes_ok:
-            wp, nkw = self.planes("wct_planes_static", self.wct_f, s.ldf, KD, s.Ef - c1, x_off=c1)
+        wp = self._static_wct_planes(c1)
         part = self._sample_static_cus(nframes)
         runs = self._sample_runs(nframes, part > 0)
 
@@ -1445,19 +1448,9 @@ class GlowEngine:
             sub = {k: (v[:, o:o + s.start + n].contiguous() if (torch.is_tensor(v) and v.dim() == 3 and k != "p1_face") else v)
                    for k, v in data.items()} if (o > 0 or n < nframes) else data
             mk = None if masks is None else {k: v[o:o + n].contiguous() for k, v in masks.items()}
-            rows = n * B
             cnd = cond[o * B * s.ldf:]
-            prs = pre[o * B * KD:]
             self.build_features(sub, None, B, s.start + n, mk, cnd, with_stash=False, skip_p1=True, sampling=True, frame0=o)
-            if planes_ok:
-                # the static columns of cond_transform for the run's frames (F x Ks D x 640 at final widths: the largest product of a
-                # sampling call) on pre-split planes, as the training step's cond_transform forward
-                cp, nkc = self.planes("cond_planes", cnd, s.ldf, rows, s.Ef - c1, x_off=c1)
-                self.gemm_planes(rows, KD, s.Ef - c1, cp, nkc, wp, nkw, prs, KD, bias=self.fview("bct"), cls="cond_fwd")
-            elif s.Ef > c1:
-                self.gemm(rows, KD, s.Ef - c1, cnd, s.ldf, 1, self.wct_f, s.ldf, 1, prs, KD, bias=self.fview("bct"), a_off=c1, b_off=c1)
-            else:
-                prs[:rows * KD].view(rows, KD).copy_(self.fview("bct").reshape(1, KD).expand(rows, KD))
+            self._static_pre(cnd, pre[o * B * KD:], n * B, c1, wp)
 
         static(*runs[0])
         self._toc("sample_static", ev_static)
@@ -1476,7 +1469,7 @@ class GlowEngine:
                         ev.record(side)
                         events.append(ev)
         if guard is not None:
-            fp = 9 if self._read_range_guard(guard) <= 1e3 else 5
+            fp = self._guarded_frame_precision(guard)
         dims = self._flow_dims(B, nframes)
         dims.gemm_precision = int(fp)
         h = self._buf("sample_h", s.Ks * B * s.H, zero=True)
@@ -1486,15 +1479,7 @@ class GlowEngine:
         nz[:nframes * B * s.C].view_as(noise).copy_(noise)
         p = self._flow_params()
         hist1 = e1.hist
-        # an encoded prev_p1_face window (enc: mlp / rnn / lstm) is re-encoded for every generated frame inside the sampler
-        p1 = P1Enc()
-        p1.kind, p1.hid, p1.col = {"none": 0, "mlp": 1, "rnn": 2, "lstm": 3}[e1.enc], e1.hid, e1.fcol
-        if e1.enc == "mlp":
-            p1.w1, p1.b1 = self.view("enc.p1_face.mlp_weight").data_ptr(), self.view("enc.p1_face.mlp_bias").data_ptr()
-        elif e1.enc in ("rnn", "lstm"):
-            for leaf in ENC_LEAVES:
-                setattr(p1, {"weight_ih": "w_ih", "weight_hh": "w_hh", "bias_ih": "b_ih", "bias_hh": "b_hh"}[leaf],
-                        self.view("enc.p1_face." + leaf).data_ptr())
+        p1 = self._p1_enc()
         p1work = self._buf("scratch.sample_p1", self.L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(p1), hist1))
 
         def launch(o, n):
@@ -1534,6 +1519,65 @@ class GlowEngine:
         if fp == 9:
             self._watch_sample_output(out)
         return out
+
+    # ---- steps that sample() and the streaming sessions (stream.py) share: each rule is written here once
+    def _p1_enc(self):
+        """The prev_p1_face encoder as the sampler's kernels take it: an encoded window (enc: mlp / rnn / lstm) is re-encoded for every
+        generated frame inside the sampler."""
+        e1 = self.spec.encoders[0]
+        p1 = P1Enc()
+        p1.kind, p1.hid, p1.col = {"none": 0, "mlp": 1, "rnn": 2, "lstm": 3}[e1.enc], e1.hid, e1.fcol
+        if e1.enc == "mlp":
+            p1.w1, p1.b1 = self.view("enc.p1_face.mlp_weight").data_ptr(), self.view("enc.p1_face.mlp_bias").data_ptr()
+        elif e1.enc in ("rnn", "lstm"):
+            for leaf in ENC_LEAVES:
+                setattr(p1, {"weight_ih": "w_ih", "weight_hh": "w_hh", "bias_ih": "b_ih", "bias_hh": "b_hh"}[leaf],
+                        self.view("enc.p1_face." + leaf).data_ptr())
+        return p1
+
+    def _static_wct_planes(self, c1):
+        """(planes, k-tiles) of the static cond_transform weight columns [c1, Ef) in workspace "wct_planes_static" (one launch) where
+        their product runs on pre-split planes - bf16x3 engine mode, LFI_PGEMM not 0, and there are such columns - else None."""
+        s = self.spec
+        if not (s.Ef > c1 and self.precision == 1 and os.environ.get("LFI_PGEMM", "1") != "0"):
+            return None
+        return self.planes("wct_planes_static", self.wct_f, s.ldf, s.Ks * s.D, s.Ef - c1, x_off=c1)
+
+    def _static_pre(self, cond, pre, rows, c1, wp):
+        """`rows` feature rows of `cond` through the static cond_transform columns [c1, Ef) (no activation yet) into `pre` (rows x Ks D).
+        wp: _static_wct_planes(c1)."""
+        s = self.spec
+        KD = s.Ks * s.D
+        if wp is not None:
+            # the static columns of cond_transform for the run's frames (F x Ks D x 640 at final widths: the largest product of a
+            # sampling call) on pre-split planes, as the training step's cond_transform forward
+            cp, nkc = self.planes("cond_planes", cond, s.ldf, rows, s.Ef - c1, x_off=c1)
+            self.gemm_planes(rows, KD, s.Ef - c1, cp, nkc, wp[0], wp[1], pre, KD, bias=self.fview("bct"), cls="cond_fwd")
+        elif s.Ef > c1:
+            self.gemm(rows, KD, s.Ef - c1, cond, s.ldf, 1, self.wct_f, s.ldf, 1, pre, KD, bias=self.fview("bct"), a_off=c1, b_off=c1)
+        else:
+            pre[:rows * KD].view(rows, KD).copy_(self.fview("bct").reshape(1, KD).expand(rows, KD))
+
+    _fp16_piece_limit = 1e3   # max |x| the fp16-piece per-frame arithmetic accepts (the range guards of both samplers)
+
+    def _frame_precision(self):
+        """Per-frame arithmetic of a sampler (lfi_flow_dims.gemm_precision) as far as it is known without looking at values:
+        LFI_SAMPLE_FRAME_PRECISION's, else exact f32 (0) in f32 engine mode, else six bf16 products (5) once a call in fp16 pieces came
+        back non-finite. None: the range guard decides (_guarded_frame_precision) - the caller launches it where it suits its queue."""
+        if self.sample_frame_precision is not None or self.precision != 1:
+            return self.sample_frame_precision or 0
+        return 5 if self._sample_fp16_unsafe else None
+
+    @staticmethod
+    def _guarded(data):
+        """The float32 GPU tensors of a caller's batch / seed: what the range guard has to look at."""
+        return [v for v in data.values() if torch.is_tensor(v) and v.dtype == torch.float32 and v.is_cuda]
+
+    def _guarded_frame_precision(self, guard):
+        """fp16 pieces (9) when everything the guard looked at sits inside their range, else six bf16 products (5). Waits for the guard."""
+        pinned, ev = guard
+        ev.synchronize()
+        return 9 if self._guard_float(pinned) <= self._fp16_piece_limit else 5
 
     # ---- helpers of sample()
     def _sample_static_cus(self, nframes):
@@ -1606,11 +1650,9 @@ class GlowEngine:
         return pinned, ev
 
     @staticmethod
-    def _read_range_guard(guard):
-        """max |v| as a float (inf / nan when an input held one: both fail `<= limit`)."""
-        import struct
-        pinned, ev = guard
-        ev.synchronize()
+    def _guard_float(pinned):
+        """The guard word that has landed in pinned memory - the bit pattern of max |v| - as a float (inf / nan when an input held one:
+        both fail `<= limit`)."""
         return struct.unpack("<f", struct.pack("<I", int(pinned.item()) & 0xffffffff))[0]
 
     def _buf_i32(self, name, n):
@@ -1641,9 +1683,8 @@ class GlowEngine:
         if w is None or not w[1].query():      # never a host wait: a scan still in flight is looked at by a later call
             return
         self._sample_watch = None
-        amax = self._read_range_guard(w)
+        amax = self._guard_float(w[0])
         if not (amax <= 65504.0):     # inf or NaN in the frames of the previous fp16-piece sampling call
-            import warnings
             self._sample_fp16_unsafe = True
             warnings.warn("the previous sampling call produced non-finite frames (max |x| = %r) in its fp16-piece arithmetic: this "
                           "engine samples with six bf16 products (no range caveat) from now on; re-run that call" % amax)
@@ -1721,513 +1762,3 @@ class GlowEngine:
         frames of every modality; noise_fn(B, C) draws a step's prior noise (already * eps); masks_fn(B, N) the window encoders'
         dropout masks (None = none); bound() is False once the owning module has re-bound to another engine."""
         return SampleStream(self, seed, noise_fn, masks_fn, bound)
-
-
-# engine attributes that a streaming session owns while one of its steps runs (SampleStream._owned): the workspaces every launch of
-# the static part and the chain writes, and the per-parameter-state preparation they read (run_prep's outputs)
-_SESSION_ATTRS = ("_ws", "prep", "wct_f", "_wct_planes", "_wc_r", "_cond_planes", "_enc_stash_f16")
-_STREAM_GUARD_LIMIT = 1e3   # max |x| the fp16-piece per-frame arithmetic accepts (as GlowEngine._sample)
-_PARAMS_CHANGED = ("SampleStream: the model's parameters changed since open_stream (optimiser step, parameter load or "
-                   "ActNorm init): a session samples with the weights of its open; open a new one")
-_ROW_FIELDS = ("C", "H", "Ks", "rnn_type", "use_frame_nb", "windows", "hist1", "R")
-
-
-class StreamRows:
-    """The live state of n conversations taken out of a streaming session (SampleStream.save_rows): `data`, one contiguous float32
-    (n, R) tensor of records, and `signature`, the record layout (C, H, Ks, rnn_type, use_frame_nb, ((name, hist, dim), ...), hist1,
-    R). A record is, in order: every conditioning window of SampleStream.mods (hist x in_dim each), the faces window ((hist1 + 1) x
-    C), h (Ks x H), c (Ks x H, LSTM only), the frame counter (one float, only with use_frame_nb) - the layout lfi_stream_row_floats
-    defines. Plain fp32 values: independent of the session's batch size and per-frame arithmetic. load_rows puts entries back into
-    rows of any session of the same model; cpu() / to(device) pause and resume, state_dict() / from_state_dict() store."""
-
-    def __init__(self, data, signature, _engine=None, _param_version=None):
-        self.data = data
-        self.signature = self._canonical(signature)
-        self._engine, self._param_version = _engine, _param_version   # (same-process check only: not part of state_dict())
-
-    @staticmethod
-    def _canonical(sig):
-        sig = tuple(sig)
-        if len(sig) != len(_ROW_FIELDS):
-            raise ValueError("StreamRows: a layout signature has %d fields %s, got %d" % (len(_ROW_FIELDS), _ROW_FIELDS, len(sig)))
-        C_, H, Ks, rnn, nb, wins, hist1, R = sig
-        return (int(C_), int(H), int(Ks), str(rnn), bool(nb), tuple((str(n), int(h), int(d)) for n, h, d in wins), int(hist1), int(R))
-
-    def __len__(self):
-        return int(self.data.shape[0])
-
-    def _like(self, data):
-        return StreamRows(data, self.signature, self._engine, self._param_version)
-
-    def cpu(self):
-        return self._like(self.data.cpu())
-
-    def to(self, device):
-        return self._like(self.data.to(device).contiguous())
-
-    def select(self, indices):
-        """The listed entries (repeats allowed), as a new StreamRows."""
-        idx = torch.as_tensor(indices, dtype=torch.long, device=self.data.device).reshape(-1)
-        return self._like(self.data.index_select(0, idx))
-
-    def state_dict(self):
-        """One tensor and plain Python values (torch.save-able). Whether the weights are the ones the rows were saved under is the
-        caller's responsibility once the rows leave the process."""
-        d = dict(zip(_ROW_FIELDS, self.signature))
-        d["windows"] = [list(w) for w in d["windows"]]
-        d["data"] = self.data
-        return d
-
-    @classmethod
-    def from_state_dict(cls, d):
-        missing = [k for k in _ROW_FIELDS + ("data",) if k not in d]
-        if missing:
-            raise KeyError("StreamRows.from_state_dict: missing %s" % missing)
-        return cls(d["data"], tuple(d[k] for k in _ROW_FIELDS))
-
-
-
-class SampleStream:
-    """Streaming autoregressive sampling: SeqGlow.inference (models.py:567-596) one frame per call, for a live agent whose
-    conditioning arrives frame by frame. Open with `start` seed frames, then step(frame) with frame t of every modality with
-    history > 0 -> the generated p1_face frame t (B, C). Given the same inputs and noise it produces what inference() produces.
-
-    Per step: lfi_stream_advance (one eager launch: the session's conditioning windows, its window of generated faces, the noise and
-    the frame counter move forward by one frame), then the static part for B windows (window encoders + the static cond_transform
-    columns, as _sample's static()) and lfi_flow_sample_seq_from for one frame, whose recurrent state h / c carries across steps. Those
-    two touch only session-owned memory at fixed addresses: from the second step on they are ONE captured hipGraph, replayed.
-    Every workspace they write is the session's own (the engine's `_ws`, prep and folded weights are swapped for the session's while a
-    step runs), so training, inference() and other sessions can run between steps. Weights are frozen: a parameter change after the
-    open (GlowEngine.param_version) makes step() raise."""
-
-    def __init__(self, eng, seed, noise_fn, masks_fn=None, bound=None):
-        s = eng.spec
-        self.eng = eng
-        self._noise_fn, self._masks_fn, self._bound = noise_fn, masks_fn, bound
-        p1 = seed.get("p1_face") if isinstance(seed, dict) else None
-        if p1 is None:
-            raise KeyError("batch is missing modality 'p1_face'")
-        self.B = B = int(p1.shape[0]) if p1.dim() == 3 else -1
-        self.start = s.start
-        self.mods = [e for e in s.encoders if e.name not in ("p1_face", "frame_nb")]
-        self._check_seed(seed)
-        self.device = eng.device
-        self.closed = False
-        self.param_version = eng.param_version
-        self.precision = eng.precision          # GEMM arithmetic of the static part, fixed at the open
-        self.steps = 0                          # frames generated since the open / the last reset()
-        self.replays = 0                        # steps that were graph replays
-        self._graph, self._graph_key = None, None
-        self._stream = None
-        self._guard_pending = None
-        self._state = {"_ws": {}, "prep": None, "wct_f": torch.zeros_like(eng.wct_f), "_wct_planes": None, "_wc_r": None,
-                       "_cond_planes": None, "_enc_stash_f16": {}}
-        e1 = s.encoders[0]
-        self.hist1 = e1.hist
-        self.c1 = (e1.fdim + 3) // 4 * 4
-        KD = s.Ks * s.D
-        p1enc = P1Enc()
-        p1enc.kind, p1enc.hid, p1enc.col = {"none": 0, "mlp": 1, "rnn": 2, "lstm": 3}[e1.enc], e1.hid, e1.fcol
-        self._p1 = p1enc
-        with self._on_stream(), self._owned():
-            eng.run_prep(with_inverse=True)
-            if e1.enc == "mlp":
-                p1enc.w1, p1enc.b1 = eng.view("enc.p1_face.mlp_weight").data_ptr(), eng.view("enc.p1_face.mlp_bias").data_ptr()
-            elif e1.enc in ("rnn", "lstm"):
-                for leaf in ENC_LEAVES:
-                    setattr(p1enc, {"weight_ih": "w_ih", "weight_hh": "w_hh", "bias_ih": "b_ih", "bias_hh": "b_hh"}[leaf],
-                            eng.view("enc.p1_face." + leaf).data_ptr())
-            self._planes_ok = s.Ef > self.c1 and self.precision == 1 and os.environ.get("LFI_PGEMM", "1") != "0"
-            if self._planes_ok:   # the static cond_transform columns' weight planes: once per session (frozen weights)
-                self._wp = eng.planes("wct_planes_static", eng.wct_f, s.ldf, KD, s.Ef - self.c1, x_off=self.c1)
-            f = self.B * s.C
-            self.faces = eng._buf("stream_faces", f * (self.hist1 + 1))[:f * (self.hist1 + 1)].view(B, self.hist1 + 1, s.C)
-            self.noise = eng._buf("stream_noise", f)[:f].view(B, s.C)
-            self.windows = {e.name: eng._buf("stream_win." + e.name, B * e.hist * e.in_dim)[:B * e.hist * e.in_dim].view(B, e.hist, e.in_dim)
-                            for e in self.mods}
-            self.frame_nb = eng._buf("stream_frame_nb", B)[:B] if s.use_frame_nb else None
-            self.mask_bufs = {e.name: eng._buf("stream_mask." + e.name, B * e.hist)[:B * e.hist].view(1, B, e.hist)
-                              for e in s.encoders if e.dropout > 0}
-            self.cond = eng._buf("stream_cond", B * s.ldf)
-            self.pre = eng._buf("stream_pre", B * KD)
-            self.h = eng._buf("stream_h", s.Ks * B * s.H)
-            self.cs = eng._buf("stream_c", s.Ks * B * s.H) if s.rnn_type == "lstm" else None
-            dims = eng._flow_dims(B, 1)
-            self.work = eng._buf("stream_chain_work", eng.L.lfi_flow_sample_work_floats(C.byref(dims)))
-            self.p1work = eng._buf("stream_p1work", eng.L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(p1enc), self.hist1))
-            self.guard = eng._buf_i32("stream_guard_word", 1)
-            self._pinned = torch.zeros(1, dtype=torch.int32).pin_memory()
-            # per-frame arithmetic, picked once (as _sample picks it per call): fp16 pieces (9) when the parameters and the seed sit inside
-            # their range, else six bf16 products (5); exact f32 (0) in f32 engine mode; LFI_SAMPLE_FRAME_PRECISION overrides
-            fp = eng.sample_frame_precision
-            if fp is None:
-                fp = 0
-                if self.precision == 1:
-                    fp = 5
-                    if not eng._sample_fp16_unsafe:
-                        tensors = [eng.params] + [v for v in seed.values() if torch.is_tensor(v) and v.is_cuda and v.dtype == torch.float32]
-                        fp = 9 if eng._read_range_guard(eng._launch_range_guard(tensors[:8])) <= _STREAM_GUARD_LIMIT else 5
-            self.frame_precision = int(fp)
-            # the row record of save_rows / load_rows: the windows in record order (mods, then the faces window) and its signature
-            wins = [(e.name, e.hist, e.in_dim, self.windows[e.name]) for e in self.mods] + [("p1_face", self.hist1 + 1, s.C, self.faces)]
-            k = len(wins)
-            self._row_win, self._row_hist, self._row_dim = (C.c_void_p * k)(), (C.c_int * k)(), (C.c_int * k)()
-            for i, (_, hi, d, w) in enumerate(wins):
-                self._row_win[i], self._row_hist[i], self._row_dim[i] = w.data_ptr(), hi, d
-            R = eng.L.lfi_stream_row_floats(k, self._row_hist, self._row_dim, s.Ks, s.H, int(self.cs is not None),
-                                            int(self.frame_nb is not None))
-            if R < 0:
-                check(-1, "lfi_stream_row_floats")
-            self.row_signature = (s.C, s.H, s.Ks, s.rnn_type, bool(s.use_frame_nb), tuple((e.name, e.hist, e.in_dim) for e in self.mods),
-                                  self.hist1, int(R))
-            self._fill(seed)
-
-    # ---- validation (before any launch; the wording of GlowEngine._check_input)
-    def _check_seed(self, seed, B=None):
-        s = self.eng.spec
-        B = self.B if B is None else B
-        p1 = seed.get("p1_face")
-        self.eng._check_input(p1, "p1_face", B, s.start, s.C)
-        for e in self.mods:
-            x = seed.get(e.name)
-            if x is None:
-                raise KeyError("batch is missing modality %r" % e.name)
-            self.eng._check_input(x, e.name, B, s.start, e.in_dim)
-            if x.device != p1.device:
-                raise ValueError("%s: on %s, the seed's p1_face on %s" % (e.name, x.device, p1.device))
-
-    def _check_frame(self, x, name, dim):
-        if not (torch.is_tensor(x) and x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.is_contiguous()
-                and x.dim() == 2 and x.shape[0] == self.B and x.shape[1] == dim):
-            raise ValueError("%s: expected contiguous float32 GPU tensor (B=%d, %d) on %s, got %s %s on %s"
-                             % (name, self.B, dim, self.device, tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x)),
-                                getattr(x, "device", None)))
-
-    def _check_usable(self):
-        if self.closed:
-            raise RuntimeError("SampleStream: the session is closed")
-        if self.eng.param_version != self.param_version or (self._bound is not None and not self._bound()):
-            raise RuntimeError(_PARAMS_CHANGED)
-
-    # ---- session-owned engine state and stream
-    @contextlib.contextmanager
-    def _owned(self):
-        eng = self.eng
-        saved = {k: eng.__dict__.get(k) for k in _SESSION_ATTRS}
-        keep_precision = eng.precision
-        eng.__dict__.update(self._state)
-        eng.precision = self.precision
-        try:
-            yield
-        finally:
-            self._state = {k: eng.__dict__.get(k) for k in _SESSION_ATTRS}
-            eng.__dict__.update(saved)
-            eng.precision = keep_precision
-
-    @contextlib.contextmanager
-    def _on_stream(self):
-        """sample()'s rule: no replay into the legacy default stream. A caller on it gets the session's private stream, joined on both
-        sides."""
-        caller = torch.cuda.current_stream(self.device)
-        if caller != torch.cuda.default_stream(self.device):
-            yield caller
-            return
-        if self._stream is None:
-            self._stream = torch.cuda.Stream(device=self.device)
-        own = self._stream
-        own.wait_stream(caller)
-        with torch.cuda.stream(own):
-            yield own
-        caller.wait_stream(own)
-
-    # ---- public surface
-    def reset(self, seed):
-        """Start a new sequence from `seed` (same batch size); the captured graph is kept."""
-        self._check_usable()
-        self._check_seed(seed)
-        with self._on_stream(), self._owned():
-            self._fill(seed)
-
-    def _check_rows(self, rows):
-        """rows of reset_rows / save_rows / load_rows -> a list of distinct ints in [0, B)."""
-        if torch.is_tensor(rows):
-            if rows.is_cuda or rows.is_floating_point() or rows.is_complex() or rows.dtype == torch.bool or rows.dim() > 1:
-                raise ValueError("rows: expected a sequence of ints or a 1-D CPU integer tensor, got %s %s on %s"
-                                 % (tuple(rows.shape), rows.dtype, rows.device))
-            rows = rows.reshape(-1).tolist()
-        else:
-            try:
-                rows = [operator.index(r) for r in rows]
-            except TypeError:
-                raise ValueError("rows: expected a sequence of ints or a 1-D CPU integer tensor, got %r" % (rows,)) from None
-        if not rows:
-            raise ValueError("rows: empty list")
-        bad = [r for r in rows if not 0 <= r < self.B]
-        if bad:
-            raise ValueError("rows: %s outside the session's batch (0 .. %d)" % (bad, self.B - 1))
-        if len(set(rows)) != len(rows):
-            raise ValueError("rows: %s listed more than once" % sorted(r for r, c in collections.Counter(rows).items() if c > 1))
-        return rows
-
-    def reset_rows(self, rows, seed):
-        """Start new sequences in the listed batch rows only, between steps (a conversation joins a batched session in a row another
-        one left). rows: a sequence of distinct ints in [0, B), or a CPU integer tensor; seed: as reset()'s, with batch len(rows) -
-        entry j goes to session row rows[j]. Every other row carries on undisturbed. One launch (lfi_stream_reset_rows), no host wait;
-        the captured graph, `steps` (frames since the open / reset(), which also index injected masks) and the per-frame arithmetic
-        are kept. A seed beyond the fp16 pieces' range is reported by the next steps' range guard, as a frame's would be."""
-        s, eng = self.eng.spec, self.eng
-        self._check_usable()
-        rows = self._check_rows(rows)
-        n = len(rows)
-        p1 = seed.get("p1_face") if isinstance(seed, dict) else None
-        if p1 is None:
-            raise KeyError("batch is missing modality 'p1_face'")
-        self._check_seed(seed, n)
-        if p1.device != self.device:
-            raise ValueError("p1_face: on %s, the session on %s" % (p1.device, self.device))
-        mods = [(self.windows[e.name], seed[e.name], e.hist, e.in_dim, 0) for e in self.mods]
-        mods.append((self.faces, seed["p1_face"], self.hist1 + 1, s.C, 1))
-        k = len(mods)
-        win_p, seed_p = (C.c_void_p * k)(), (C.c_void_p * k)()
-        seed_ld, hist, dim, lead = (C.c_long * k)(), (C.c_int * k)(), (C.c_int * k)(), (C.c_int * k)()
-        for i, (w, x, hi, d, z) in enumerate(mods):
-            # frames start - (hist - z) .. start - 1 of every seed entry; z = 1: the window's frame 0 is zeroed instead
-            win_p[i], seed_p[i] = w.data_ptr(), x.data_ptr() + 4 * (s.start - (hi - z)) * d
-            seed_ld[i], hist[i], dim[i], lead[i] = x.shape[1] * d, hi, d, z
-        row_a = (C.c_int * n)(*rows)
-        with self._on_stream(), self._owned():
-            check(eng.L.lfi_stream_reset_rows(self.B, n, row_a, k, win_p, seed_p, seed_ld, hist, dim, lead, self.h.data_ptr(),
-                                              ptr(self.cs), s.Ks, s.H, ptr(self.frame_nb), self.guard.data_ptr(), _stream()),
-                  "lfi_stream_reset_rows")
-            if self._stream is not None and torch.cuda.current_stream(self.device) == self._stream:
-                for _, x, _, _, _ in mods:
-                    x.record_stream(self._stream)
-
-    def save_rows(self, rows):
-        """The live state of the listed rows, between steps -> StreamRows with len(rows) entries, entry j = session row rows[j] (rows:
-        as reset_rows'). One launch per 256 rows (lfi_stream_save_rows) on the caller's stream, no host wait; the session is not
-        changed. A session that has not stepped since its open / reset() saves zeros for h / c: its first step ignores what those
-        buffers hold."""
-        s, eng = self.eng.spec, self.eng
-        self._check_usable()
-        rows = self._check_rows(rows)
-        n, R = len(rows), self.row_signature[-1]
-        row_a = (C.c_int * n)(*rows)
-        with self._on_stream(), self._owned():
-            out = torch.empty(n, R, dtype=torch.float32, device=self.device)
-            check(eng.L.lfi_stream_save_rows(self.B, n, row_a, len(self._row_win), self._row_win, self._row_hist, self._row_dim,
-                                             self.h.data_ptr(), ptr(self.cs), s.Ks, s.H, ptr(self.frame_nb),
-                                             int(self.steps == 0 and not self._resumed), out.data_ptr(), R, _stream()),
-                  "lfi_stream_save_rows")
-        if self._stream is not None:
-            out.record_stream(torch.cuda.current_stream(self.device))
-        return StreamRows(out, self.row_signature, weakref.ref(eng), self.param_version)
-
-    def load_rows(self, rows, saved, entries=None):
-        """Put saved conversations into the listed rows, between steps: entry entries[j] of `saved` (a StreamRows of this model, from
-        any session, batch size or device round trip) goes to session row rows[j]; entries defaults to range(len(rows)) and may
-        repeat (a branch). Only the listed rows are written; one launch per 256 rows (lfi_stream_load_rows), no host wait; `steps`,
-        the captured graph and the per-frame arithmetic are kept, and a value beyond the fp16 pieces' range is reported by the next
-        steps' range guard, as a reseed's would be. Everything is checked before the first launch: a refused call leaves the
-        session as it was. Into a session that has not stepped yet, h / c of every row are zeroed first and the first step runs as
-        a continuing one (a zeroed row is a first frame's state)."""
-        s, eng = self.eng.spec, self.eng
-        self._check_usable()
-        rows = self._check_rows(rows)
-        n = len(rows)
-        if not isinstance(saved, StreamRows):
-            raise TypeError("saved: expected a StreamRows (SampleStream.save_rows), got %s" % type(saved).__name__)
-        for name, mine, theirs in zip(_ROW_FIELDS, self.row_signature, saved.signature):
-            if mine != theirs:
-                raise ValueError("saved: layout signature differs in %s: the session's is %r, the saved rows' %r" % (name, mine, theirs))
-        R, x = self.row_signature[-1], saved.data
-        if not (torch.is_tensor(x) and x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.is_contiguous()
-                and x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] == R):
-            raise ValueError("saved.data: expected contiguous float32 GPU tensor (n>=1, R=%d) on %s, got %s %s on %s"
-                             % (R, self.device, tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x)), getattr(x, "device", None)))
-        if entries is None:
-            entries = list(range(n))
-        elif torch.is_tensor(entries):
-            if entries.is_cuda or entries.is_floating_point() or entries.is_complex() or entries.dtype == torch.bool or entries.dim() > 1:
-                raise ValueError("entries: expected a sequence of ints or a 1-D CPU integer tensor, got %s %s on %s"
-                                 % (tuple(entries.shape), entries.dtype, entries.device))
-            entries = entries.reshape(-1).tolist()
-        else:
-            try:
-                entries = [operator.index(e) for e in entries]
-            except TypeError:
-                raise ValueError("entries: expected a sequence of ints or a 1-D CPU integer tensor, got %r" % (entries,)) from None
-        if len(entries) != n:
-            raise ValueError("entries: %d listed for %d rows" % (len(entries), n))
-        bad = [e for e in entries if not 0 <= e < len(saved)]
-        if bad:
-            raise ValueError("entries: %s outside the saved rows (0 .. %d)" % (bad, len(saved) - 1))
-        if saved._engine is not None and saved._engine() is eng and saved._param_version != self.param_version:
-            raise RuntimeError(_PARAMS_CHANGED)
-        row_a, ent_a = (C.c_int * n)(*rows), (C.c_int * n)(*entries)
-        with self._on_stream(), self._owned():
-            if self.steps == 0 and not self._resumed:
-                self.h.zero_()          # (stale after a reset(); the first launch would have ignored them)
-                if self.cs is not None:
-                    self.cs.zero_()
-            check(eng.L.lfi_stream_load_rows(self.B, n, row_a, ent_a, len(saved), len(self._row_win), self._row_win, self._row_hist,
-                                             self._row_dim, self.h.data_ptr(), ptr(self.cs), s.Ks, s.H, ptr(self.frame_nb),
-                                             x.data_ptr(), R, self.guard.data_ptr(), _stream()), "lfi_stream_load_rows")
-            if self.steps == 0:
-                self._resumed = True    # the session's first _launch then keeps h / c (first_frame = 1)
-            if self._stream is not None and torch.cuda.current_stream(self.device) == self._stream:
-                x.record_stream(self._stream)
-
-    def _fill(self, seed):
-        s, h1 = self.eng.spec, self.hist1
-        self.faces[:, 0].zero_()    # (row 0 leaves with the first step's shift)
-        self.faces[:, 1:].copy_(seed["p1_face"][:, s.start - h1:s.start])
-        for e in self.mods:
-            self.windows[e.name].copy_(seed[e.name][:, s.start - e.hist:s.start])
-        if self.frame_nb is not None:
-            self.frame_nb.fill_(-1.0)   # the first step's + 2 makes it inference's 1
-        self.guard.zero_()
-        self.steps = 0
-        self._resumed = False           # load_rows into a session that has not stepped sets it: the first launch keeps h / c
-        self._guard_pending = None
-
-    def close(self):
-        """Releases the session's buffers and graph; step() raises afterwards."""
-        if self.closed:
-            return
-        if self._stream is not None:
-            self._stream.synchronize()
-        self.closed = True
-        self._graph = None
-        self._state = None
-        self.faces = self.noise = self.windows = self.cond = self.pre = self.h = self.cs = self.work = self.p1work = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    @translate_oom
-    def step(self, frame, noise=None):
-        """frame: {modality: (B, dim)} = frame t of every modality with history > 0 (extra keys are ignored). noise: (B, C) prior
-        draw already * eps, or None (drawn with the session's eps). -> generated p1_face frame t, (B, C)."""
-        s, eng, B = self.eng.spec, self.eng, self.B
-        self._check_usable()
-        if not isinstance(frame, dict):
-            raise TypeError("frame must be a dict {modality: (B, dim) tensor}")
-        srcs = []
-        for e in self.mods:
-            x = frame.get(e.name)
-            if x is None:
-                raise KeyError("batch is missing modality %r" % e.name)
-            self._check_frame(x, e.name, e.in_dim)
-            srcs.append(x)
-        if noise is not None:
-            self._check_frame(noise, "noise", s.C)
-        with self._on_stream(), self._owned():
-            self._check_guard()
-            if noise is None:
-                noise = self._noise_fn(B, s.C).contiguous()
-            masks = None
-            drawn = self._masks_fn(B, 1) if self._masks_fn is not None else None
-            eng.precision = self.precision      # (the module's mask draw re-applies its own mode to the engine)
-            if drawn:
-                masks = {}
-                for name, buf in self.mask_bufs.items():
-                    m = drawn.get(name)
-                    if m is None:
-                        continue
-                    if m.dim() != 3 or tuple(m.shape[1:]) != (B, buf.shape[2]):
-                        raise ValueError("mask for %s must be (N, B, hist) = (., %d, %d), got %s" % (name, B, buf.shape[2], tuple(m.shape)))
-                    if m.shape[0] != 1 and self.steps >= m.shape[0]:
-                        raise ValueError("mask for %s holds %d frames; this is frame %d of the stream" % (name, m.shape[0], self.steps))
-                    buf.copy_(m[0 if m.shape[0] == 1 else self.steps].unsqueeze(0))
-                    masks[name] = buf
-            wins = self.mods + [None]
-            n = len(wins)
-            win_p, src_p = (C.c_void_p * n)(), (C.c_void_p * n)()
-            hist, dim = (C.c_int * n)(), (C.c_int * n)()
-            for i, e in enumerate(self.mods):
-                win_p[i], src_p[i], hist[i], dim[i] = self.windows[e.name].data_ptr(), srcs[i].data_ptr(), e.hist, e.in_dim
-            win_p[n - 1], src_p[n - 1], hist[n - 1], dim[n - 1] = self.faces.data_ptr(), None, self.hist1 + 1, s.C
-            ev = eng._tic("stream_advance")
-            check(eng.L.lfi_stream_advance(B, n, win_p, src_p, hist, dim, noise.data_ptr(), self.noise.data_ptr(), s.C,
-                                           ptr(self.frame_nb), self.guard.data_ptr(), _stream()), "lfi_stream_advance")
-            eng._toc("stream_advance", ev)
-            self._pinned.copy_(self.guard, non_blocking=True)
-            gev = torch.cuda.Event()
-            gev.record()
-            self._guard_pending = gev
-            for x in srcs + [noise]:
-                x.record_stream(torch.cuda.current_stream(self.device))
-            if self.steps == 0 or os.environ.get("LFI_NO_GRAPH") == "1":
-                self._launch(masks, 1 if self.steps > 0 or self._resumed else 0)
-            else:
-                key = (self.frame_precision, masks is not None)
-                if self._graph is None or self._graph_key != key:
-                    timers, eng.timers = eng.timers, None
-                    try:
-                        torch.cuda.synchronize()
-                        g = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(g):
-                            self._launch(masks, 1)
-                    finally:
-                        eng.timers = timers
-                    self._graph, self._graph_key = g, key
-                ev = eng._tic("stream_graph")
-                self._graph.replay()
-                eng._toc("stream_graph", ev)
-                self.replays += 1
-            out = self.faces[:, self.hist1].clone()
-            self.steps += 1
-        if out.device == self.device and self._stream is not None:
-            out.record_stream(torch.cuda.current_stream(self.device))
-        return out
-
-    def _launch(self, masks, first_frame):
-        """The static part for the session's B windows, then the reverse chain for one frame: session-owned memory only."""
-        eng, s, B = self.eng, self.eng.spec, self.B
-        KD = s.Ks * s.D
-        ev = eng._tic("stream_static")
-        data = dict(self.windows)
-        if self.frame_nb is not None:
-            data["frame_nb"] = self.frame_nb
-        # (sampling=False: the frame counter comes from the session's device counter, not from a host frame offset)
-        eng.build_features(data, None, B, 0, masks, self.cond, with_stash=False, skip_p1=True, sampling=False, windows=True)
-        if self._planes_ok:
-            wp, nkw = self._wp
-            cp, nkc = eng.planes("cond_planes", self.cond, s.ldf, B, s.Ef - self.c1, x_off=self.c1)
-            eng.gemm_planes(B, KD, s.Ef - self.c1, cp, nkc, wp, nkw, self.pre, KD, bias=eng.fview("bct"), cls="cond_fwd")
-        elif s.Ef > self.c1:
-            eng.gemm(B, KD, s.Ef - self.c1, self.cond, s.ldf, 1, eng.wct_f, s.ldf, 1, self.pre, KD, bias=eng.fview("bct"),
-                     a_off=self.c1, b_off=self.c1)
-        else:
-            self.pre[:B * KD].view(B, KD).copy_(eng.fview("bct").reshape(1, KD).expand(B, KD))
-        eng._toc("stream_static", ev)
-        dims = eng._flow_dims(B, 1)
-        dims.gemm_precision = self.frame_precision
-        p = eng._flow_params()
-        ev = eng._tic("stream_chain")
-        check(eng.L.lfi_flow_sample_seq_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
-                                             self.pre.data_ptr(), self.noise.data_ptr(), self.faces.data_ptr(), self.hist1 + 1,
-                                             self.hist1, 1, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
-                                             self.p1work.data_ptr(), self.work.data_ptr(), _stream()), "lfi_flow_sample_seq_from")
-        eng._toc("stream_chain", ev)
-
-    def _check_guard(self):
-        """The range guard of earlier steps (lfi_stream_advance folds max |x| of every value it moves into the session's guard word,
-        copied to pinned memory behind it): looked at once its copy has landed - never a host wait. A value beyond the fp16 pieces'
-        range (or a non-finite one) is reported with a warning, and the session samples with six bf16 products from then on."""
-        ev = self._guard_pending
-        if ev is None or not ev.query():
-            return
-        self._guard_pending = None
-        import struct
-        amax = struct.unpack("<f", struct.pack("<I", int(self._pinned.item()) & 0xffffffff))[0]
-        if self.frame_precision == 9 and not (amax <= _STREAM_GUARD_LIMIT):
-            self.frame_precision = 5
-            warnings.warn("SampleStream: an earlier step saw max |x| = %r, beyond the range of the fp16-piece per-frame arithmetic (%g): "
-                          "this session samples with six bf16 products (no range caveat) from now on; frames since that input may be "
-                          "inaccurate" % (amax, _STREAM_GUARD_LIMIT), RuntimeWarning)

@@ -1,0 +1,467 @@
+"""Streaming sampling sessions (SeqGlow.open_stream -> GlowEngine.open_stream): SampleStream, one generated frame per call, and
+StreamRows, the live rows that move between sessions. A session takes the engine it borrows as an argument (this module does not import
+engine.py); the steps it shares with the batch sampler GlowEngine.sample - the prev_p1_face descriptor, the static cond_transform
+product, the per-frame arithmetic and its range limit, the guard word, the stream policy - are GlowEngine's, defined there once."""
+import collections
+import contextlib
+import ctypes as C
+import operator
+import os
+import warnings
+import weakref
+
+import torch
+
+from ._lib import check, ptr, translate_oom
+
+# engine attributes that a streaming session owns while one of its steps runs (SampleStream._owned): the workspaces every launch of
+# the static part and the chain writes, and the per-parameter-state preparation they read (run_prep's outputs)
+_SESSION_ATTRS = ("_ws", "prep", "wct_f", "_wct_planes", "_wc_r", "_cond_planes", "_enc_stash_f16")
+_PARAMS_CHANGED = ("SampleStream: the model's parameters changed since open_stream (optimiser step, parameter load or "
+                   "ActNorm init): a session samples with the weights of its open; open a new one")
+_ROW_FIELDS = ("C", "H", "Ks", "rnn_type", "use_frame_nb", "windows", "hist1", "R")
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _index_list(name, idx, bound, where, count=None, distinct=True):
+    """The index-list argument `name` of reset_rows / save_rows / load_rows: a sequence of ints or a 1-D CPU integer tensor -> a list
+    of ints in [0, bound); `where` words what lies beyond. count: as many as that are wanted (None: any number but none at all);
+    distinct: none may be listed twice."""
+    wrong = "%s: expected a sequence of ints or a 1-D CPU integer tensor, got %s"
+    if torch.is_tensor(idx):
+        if idx.is_cuda or idx.is_floating_point() or idx.is_complex() or idx.dtype == torch.bool or idx.dim() > 1:
+            raise ValueError(wrong % (name, "%s %s on %s" % (tuple(idx.shape), idx.dtype, idx.device)))
+        idx = idx.reshape(-1).tolist()
+    else:
+        try:
+            idx = [operator.index(i) for i in idx]
+        except TypeError:
+            raise ValueError(wrong % (name, repr(idx))) from None
+    if count is None and not idx:
+        raise ValueError("%s: empty list" % name)
+    if count is not None and len(idx) != count:
+        raise ValueError("%s: %d listed for %d rows" % (name, len(idx), count))
+    bad = [i for i in idx if not 0 <= i < bound]
+    if bad:
+        raise ValueError("%s: %s outside %s (0 .. %d)" % (name, bad, where, bound - 1))
+    if distinct and len(set(idx)) != len(idx):
+        raise ValueError("%s: %s listed more than once" % (name, sorted(i for i, c in collections.Counter(idx).items() if c > 1)))
+    return idx
+
+
+class StreamRows:
+    """The live state of n conversations taken out of a streaming session (SampleStream.save_rows): `data`, one contiguous float32
+    (n, R) tensor of records, and `signature`, the record layout (C, H, Ks, rnn_type, use_frame_nb, ((name, hist, dim), ...), hist1,
+    R). A record is, in order: every conditioning window of SampleStream.mods (hist x in_dim each), the faces window ((hist1 + 1) x
+    C), h (Ks x H), c (Ks x H, LSTM only), the frame counter (one float, only with use_frame_nb) - the layout lfi_stream_row_floats
+    defines. Plain fp32 values: independent of the session's batch size and per-frame arithmetic. load_rows puts entries back into
+    rows of any session of the same model; cpu() / to(device) pause and resume, state_dict() / from_state_dict() store."""
+
+    def __init__(self, data, signature, _engine=None, _param_version=None):
+        self.data = data
+        self.signature = self._canonical(signature)
+        self._engine, self._param_version = _engine, _param_version   # (same-process check only: not part of state_dict())
+
+    @staticmethod
+    def _canonical(sig):
+        sig = tuple(sig)
+        if len(sig) != len(_ROW_FIELDS):
+            raise ValueError("StreamRows: a layout signature has %d fields %s, got %d" % (len(_ROW_FIELDS), _ROW_FIELDS, len(sig)))
+        C_, H, Ks, rnn, nb, wins, hist1, R = sig
+        return (int(C_), int(H), int(Ks), str(rnn), bool(nb), tuple((str(n), int(h), int(d)) for n, h, d in wins), int(hist1), int(R))
+
+    def __len__(self):
+        return int(self.data.shape[0])
+
+    def _like(self, data):
+        return StreamRows(data, self.signature, self._engine, self._param_version)
+
+    def cpu(self):
+        return self._like(self.data.cpu())
+
+    def to(self, device):
+        return self._like(self.data.to(device).contiguous())
+
+    def select(self, indices):
+        """The listed entries (repeats allowed), as a new StreamRows."""
+        idx = torch.as_tensor(indices, dtype=torch.long, device=self.data.device).reshape(-1)
+        return self._like(self.data.index_select(0, idx))
+
+    def state_dict(self):
+        """One tensor and plain Python values (torch.save-able). Whether the weights are the ones the rows were saved under is the
+        caller's responsibility once the rows leave the process."""
+        d = dict(zip(_ROW_FIELDS, self.signature))
+        d["windows"] = [list(w) for w in d["windows"]]
+        d["data"] = self.data
+        return d
+
+    @classmethod
+    def from_state_dict(cls, d):
+        missing = [k for k in _ROW_FIELDS + ("data",) if k not in d]
+        if missing:
+            raise KeyError("StreamRows.from_state_dict: missing %s" % missing)
+        return cls(d["data"], tuple(d[k] for k in _ROW_FIELDS))
+
+
+class SampleStream:
+    """Streaming autoregressive sampling: SeqGlow.inference (models.py:567-596) one frame per call, for a live agent whose
+    conditioning arrives frame by frame. Open with `start` seed frames, then step(frame) with frame t of every modality with
+    history > 0 -> the generated p1_face frame t (B, C). Given the same inputs and noise it produces what inference() produces.
+
+    Per step: lfi_stream_advance (one eager launch: the session's conditioning windows, its window of generated faces, the noise and
+    the frame counter move forward by one frame), then the static part for B windows (window encoders + the static cond_transform
+    columns, as _sample's static()) and lfi_flow_sample_seq_from for one frame, whose recurrent state h / c carries across steps. Those
+    two touch only session-owned memory at fixed addresses: from the second step on they are ONE captured hipGraph, replayed.
+    Every workspace they write is the session's own (the engine's `_ws`, prep and folded weights are swapped for the session's while a
+    step runs), so training, inference() and other sessions can run between steps. Weights are frozen: a parameter change after the
+    open (GlowEngine.param_version) makes step() raise."""
+
+    def __init__(self, eng, seed, noise_fn, masks_fn=None, bound=None):
+        s = eng.spec
+        self.eng = eng
+        self._noise_fn, self._masks_fn, self._bound = noise_fn, masks_fn, bound
+        p1 = seed.get("p1_face") if isinstance(seed, dict) else None
+        if p1 is None:
+            raise KeyError("batch is missing modality 'p1_face'")
+        self.B = B = int(p1.shape[0]) if p1.dim() == 3 else -1
+        self.start = s.start
+        self.mods = [e for e in s.encoders if e.name not in ("p1_face", "frame_nb")]
+        self._check_seed(seed)
+        self.device = eng.device
+        self.closed = False
+        self.param_version = eng.param_version
+        self.precision = eng.precision          # GEMM arithmetic of the static part, fixed at the open
+        self.steps = 0                          # frames generated since the open / the last reset()
+        self.replays = 0                        # steps that were graph replays
+        self._graph, self._graph_key = None, None
+        self._stream = None
+        self._guard_pending = None
+        self._state = {"_ws": {}, "prep": None, "wct_f": torch.zeros_like(eng.wct_f), "_wct_planes": None, "_wc_r": None,
+                       "_cond_planes": None, "_enc_stash_f16": {}}
+        e1 = s.encoders[0]
+        self.hist1 = e1.hist
+        self.c1 = (e1.fdim + 3) // 4 * 4
+        with self._owned():
+            eng.run_prep(with_inverse=True)
+            self._p1 = eng._p1_enc()
+            self._wp = eng._static_wct_planes(self.c1)   # the static cond_transform columns' weight planes: once per session (frozen weights)
+            f = self.B * s.C
+            self.faces = eng._buf("stream_faces", f * (self.hist1 + 1))[:f * (self.hist1 + 1)].view(B, self.hist1 + 1, s.C)
+            self.noise = eng._buf("stream_noise", f)[:f].view(B, s.C)
+            self.windows = {e.name: eng._buf("stream_win." + e.name, B * e.hist * e.in_dim)[:B * e.hist * e.in_dim].view(B, e.hist, e.in_dim)
+                            for e in self.mods}
+            self.frame_nb = eng._buf("stream_frame_nb", B)[:B] if s.use_frame_nb else None
+            self.mask_bufs = {e.name: eng._buf("stream_mask." + e.name, B * e.hist)[:B * e.hist].view(1, B, e.hist)
+                              for e in s.encoders if e.dropout > 0}
+            self.cond = eng._buf("stream_cond", B * s.ldf)
+            self.pre = eng._buf("stream_pre", B * s.Ks * s.D)
+            self.h = eng._buf("stream_h", s.Ks * B * s.H)
+            self.cs = eng._buf("stream_c", s.Ks * B * s.H) if s.rnn_type == "lstm" else None
+            dims = eng._flow_dims(B, 1)
+            self.work = eng._buf("stream_chain_work", eng.L.lfi_flow_sample_work_floats(C.byref(dims)))
+            self.p1work = eng._buf("stream_p1work", eng.L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
+            self.guard = eng._buf_i32("stream_guard_word", 1)
+            self._pinned = torch.zeros(1, dtype=torch.int32).pin_memory()
+            # per-frame arithmetic, picked once (as _sample picks it per call): fp16 pieces (9) when the parameters and the seed sit inside
+            # their range, else six bf16 products (5); exact f32 (0) in f32 engine mode; LFI_SAMPLE_FRAME_PRECISION overrides
+            fp = eng._frame_precision()
+            if fp is None:
+                fp = eng._guarded_frame_precision(eng._launch_range_guard(([eng.params] + eng._guarded(seed))[:8]))
+            self.frame_precision = int(fp)
+            # the session's windows in record order (mods, then the faces window), as the four entry points pass them: pointer, hist
+            # and dim are fixed at the open; step() fills the frame pointers (none for the faces window), reset_rows the seed's
+            self._wins = [(e.name, self.windows[e.name], e.hist, e.in_dim, 0) for e in self.mods] + \
+                         [("p1_face", self.faces, self.hist1 + 1, s.C, 1)]
+            k = len(self._wins)
+            self._row_win, self._row_hist, self._row_dim = (C.c_void_p * k)(), (C.c_int * k)(), (C.c_int * k)()
+            self._src_p, self._seed_p, self._seed_ld, self._lead = (C.c_void_p * k)(), (C.c_void_p * k)(), (C.c_long * k)(), (C.c_int * k)()
+            for i, (_, w, hi, d, z) in enumerate(self._wins):
+                self._row_win[i], self._row_hist[i], self._row_dim[i], self._lead[i] = w.data_ptr(), hi, d, z
+            # the row record of save_rows / load_rows and its signature
+            R = eng.L.lfi_stream_row_floats(k, self._row_hist, self._row_dim, s.Ks, s.H, int(self.cs is not None),
+                                            int(self.frame_nb is not None))
+            if R < 0:
+                check(-1, "lfi_stream_row_floats")
+            self.row_signature = (s.C, s.H, s.Ks, s.rnn_type, bool(s.use_frame_nb), tuple((e.name, e.hist, e.in_dim) for e in self.mods),
+                                  self.hist1, int(R))
+            self._fill(seed)
+
+    # ---- validation (before any launch; the wording of GlowEngine._check_input)
+    def _check_seed(self, seed, B=None):
+        s = self.eng.spec
+        B = self.B if B is None else B
+        p1 = seed.get("p1_face")
+        self.eng._check_input(p1, "p1_face", B, s.start, s.C)
+        for e in self.mods:
+            x = seed.get(e.name)
+            if x is None:
+                raise KeyError("batch is missing modality %r" % e.name)
+            self.eng._check_input(x, e.name, B, s.start, e.in_dim)
+            if x.device != p1.device:
+                raise ValueError("%s: on %s, the seed's p1_face on %s" % (e.name, x.device, p1.device))
+
+    def _check_matrix(self, x, name, cols, rows=None):
+        """A step's frame / noise (rows = B) or the records of saved rows (rows None: any number from one)."""
+        if not (torch.is_tensor(x) and x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.is_contiguous()
+                and x.dim() == 2 and (x.shape[0] >= 1 if rows is None else x.shape[0] == rows) and x.shape[1] == cols):
+            raise ValueError("%s: expected contiguous float32 GPU tensor (%s) on %s, got %s %s on %s"
+                             % (name, "n>=1, R=%d" % cols if rows is None else "B=%d, %d" % (rows, cols), self.device,
+                                tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x)), getattr(x, "device", None)))
+
+    def _check_usable(self):
+        if self.closed:
+            raise RuntimeError("SampleStream: the session is closed")
+        if self.eng.param_version != self.param_version or (self._bound is not None and not self._bound()):
+            raise RuntimeError(_PARAMS_CHANGED)
+
+    # ---- session-owned engine state, on a stream that is not the legacy default one (the session's private stream for a caller on it)
+    @contextlib.contextmanager
+    def _owned(self):
+        eng = self.eng
+        with eng._off_legacy_stream(self, "_stream"):
+            saved = {k: eng.__dict__.get(k) for k in _SESSION_ATTRS}
+            keep_precision = eng.precision
+            eng.__dict__.update(self._state)
+            eng.precision = self.precision
+            try:
+                yield
+            finally:
+                self._state = {k: eng.__dict__.get(k) for k in _SESSION_ATTRS}
+                eng.__dict__.update(saved)
+                eng.precision = keep_precision
+
+    # ---- public surface
+    def reset(self, seed):
+        """Start a new sequence from `seed` (same batch size); the captured graph is kept."""
+        self._check_usable()
+        self._check_seed(seed)
+        with self._owned():
+            self._fill(seed)
+
+    def reset_rows(self, rows, seed):
+        """Start new sequences in the listed batch rows only, between steps (a conversation joins a batched session in a row another
+        one left). rows: a sequence of distinct ints in [0, B), or a CPU integer tensor; seed: as reset()'s, with batch len(rows) -
+        entry j goes to session row rows[j]. Every other row carries on undisturbed. One launch (lfi_stream_reset_rows), no host wait;
+        the captured graph, `steps` (frames since the open / reset(), which also index injected masks) and the per-frame arithmetic
+        are kept. A seed beyond the fp16 pieces' range is reported by the next steps' range guard, as a frame's would be."""
+        s, eng = self.eng.spec, self.eng
+        self._check_usable()
+        rows = _index_list("rows", rows, self.B, "the session's batch")
+        n = len(rows)
+        p1 = seed.get("p1_face") if isinstance(seed, dict) else None
+        if p1 is None:
+            raise KeyError("batch is missing modality 'p1_face'")
+        self._check_seed(seed, n)
+        if p1.device != self.device:
+            raise ValueError("p1_face: on %s, the session on %s" % (p1.device, self.device))
+        seeds = [seed[name] for name, _, _, _, _ in self._wins]
+        for i, (x, (_, _, hi, d, z)) in enumerate(zip(seeds, self._wins)):
+            # frames start - (hist - z) .. start - 1 of every seed entry; z = 1: the window's frame 0 is zeroed instead
+            self._seed_p[i], self._seed_ld[i] = x.data_ptr() + 4 * (s.start - (hi - z)) * d, x.shape[1] * d
+        row_a = (C.c_int * n)(*rows)
+        with self._owned():
+            check(eng.L.lfi_stream_reset_rows(self.B, n, row_a, len(self._row_win), self._row_win, self._seed_p, self._seed_ld,
+                                              self._row_hist, self._row_dim, self._lead, self.h.data_ptr(), ptr(self.cs), s.Ks, s.H,
+                                              ptr(self.frame_nb), self.guard.data_ptr(), _stream()), "lfi_stream_reset_rows")
+            if self._stream is not None and torch.cuda.current_stream(self.device) == self._stream:
+                for x in seeds:
+                    x.record_stream(self._stream)
+
+    def save_rows(self, rows):
+        """The live state of the listed rows, between steps -> StreamRows with len(rows) entries, entry j = session row rows[j] (rows:
+        as reset_rows'). One launch per 256 rows (lfi_stream_save_rows) on the caller's stream, no host wait; the session is not
+        changed. A session that has not stepped since its open / reset() saves zeros for h / c: its first step ignores what those
+        buffers hold."""
+        s, eng = self.eng.spec, self.eng
+        self._check_usable()
+        rows = _index_list("rows", rows, self.B, "the session's batch")
+        n, R = len(rows), self.row_signature[-1]
+        row_a = (C.c_int * n)(*rows)
+        with self._owned():
+            out = torch.empty(n, R, dtype=torch.float32, device=self.device)
+            check(eng.L.lfi_stream_save_rows(self.B, n, row_a, len(self._row_win), self._row_win, self._row_hist, self._row_dim,
+                                             self.h.data_ptr(), ptr(self.cs), s.Ks, s.H, ptr(self.frame_nb),
+                                             int(self.steps == 0 and not self._resumed), out.data_ptr(), R, _stream()),
+                  "lfi_stream_save_rows")
+        if self._stream is not None:
+            out.record_stream(torch.cuda.current_stream(self.device))
+        return StreamRows(out, self.row_signature, weakref.ref(eng), self.param_version)
+
+    def load_rows(self, rows, saved, entries=None):
+        """Put saved conversations into the listed rows, between steps: entry entries[j] of `saved` (a StreamRows of this model, from
+        any session, batch size or device round trip) goes to session row rows[j]; entries defaults to range(len(rows)) and may
+        repeat (a branch). Only the listed rows are written; one launch per 256 rows (lfi_stream_load_rows), no host wait; `steps`,
+        the captured graph and the per-frame arithmetic are kept, and a value beyond the fp16 pieces' range is reported by the next
+        steps' range guard, as a reseed's would be. Everything is checked before the first launch: a refused call leaves the
+        session as it was. Into a session that has not stepped yet, h / c of every row are zeroed first and the first step runs as
+        a continuing one (a zeroed row is a first frame's state)."""
+        s, eng = self.eng.spec, self.eng
+        self._check_usable()
+        rows = _index_list("rows", rows, self.B, "the session's batch")
+        n = len(rows)
+        if not isinstance(saved, StreamRows):
+            raise TypeError("saved: expected a StreamRows (SampleStream.save_rows), got %s" % type(saved).__name__)
+        for name, mine, theirs in zip(_ROW_FIELDS, self.row_signature, saved.signature):
+            if mine != theirs:
+                raise ValueError("saved: layout signature differs in %s: the session's is %r, the saved rows' %r" % (name, mine, theirs))
+        R, x = self.row_signature[-1], saved.data
+        self._check_matrix(x, "saved.data", R)
+        entries = _index_list("entries", range(n) if entries is None else entries, len(saved), "the saved rows", count=n, distinct=False)
+        if saved._engine is not None and saved._engine() is eng and saved._param_version != self.param_version:
+            raise RuntimeError(_PARAMS_CHANGED)
+        row_a, ent_a = (C.c_int * n)(*rows), (C.c_int * n)(*entries)
+        with self._owned():
+            if self.steps == 0 and not self._resumed:
+                self.h.zero_()          # (stale after a reset(); the first launch would have ignored them)
+                if self.cs is not None:
+                    self.cs.zero_()
+            check(eng.L.lfi_stream_load_rows(self.B, n, row_a, ent_a, len(saved), len(self._row_win), self._row_win, self._row_hist,
+                                             self._row_dim, self.h.data_ptr(), ptr(self.cs), s.Ks, s.H, ptr(self.frame_nb),
+                                             x.data_ptr(), R, self.guard.data_ptr(), _stream()), "lfi_stream_load_rows")
+            if self.steps == 0:
+                self._resumed = True    # the session's first _launch then keeps h / c (first_frame = 1)
+            if self._stream is not None and torch.cuda.current_stream(self.device) == self._stream:
+                x.record_stream(self._stream)
+
+    def _fill(self, seed):
+        s, h1 = self.eng.spec, self.hist1
+        self.faces[:, 0].zero_()    # (row 0 leaves with the first step's shift)
+        self.faces[:, 1:].copy_(seed["p1_face"][:, s.start - h1:s.start])
+        for e in self.mods:
+            self.windows[e.name].copy_(seed[e.name][:, s.start - e.hist:s.start])
+        if self.frame_nb is not None:
+            self.frame_nb.fill_(-1.0)   # the first step's + 2 makes it inference's 1
+        self.guard.zero_()
+        self.steps = 0
+        self._resumed = False           # load_rows into a session that has not stepped sets it: the first launch keeps h / c
+        self._guard_pending = None
+
+    def close(self):
+        """Releases the session's buffers and graph; step() raises afterwards."""
+        if self.closed:
+            return
+        if self._stream is not None:
+            self._stream.synchronize()
+        self.closed = True
+        self._graph = None
+        self._state = None
+        self.faces = self.noise = self.windows = self.cond = self.pre = self.h = self.cs = self.work = self.p1work = self._wins = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    @translate_oom
+    def step(self, frame, noise=None):
+        """frame: {modality: (B, dim)} = frame t of every modality with history > 0 (extra keys are ignored). noise: (B, C) prior
+        draw already * eps, or None (drawn with the session's eps). -> generated p1_face frame t, (B, C)."""
+        s, eng, B = self.eng.spec, self.eng, self.B
+        self._check_usable()
+        if not isinstance(frame, dict):
+            raise TypeError("frame must be a dict {modality: (B, dim) tensor}")
+        srcs = []
+        for e in self.mods:
+            x = frame.get(e.name)
+            if x is None:
+                raise KeyError("batch is missing modality %r" % e.name)
+            self._check_matrix(x, e.name, e.in_dim, B)
+            srcs.append(x)
+        if noise is not None:
+            self._check_matrix(noise, "noise", s.C, B)
+        with self._owned():
+            self._check_guard()
+            if noise is None:
+                noise = self._noise_fn(B, s.C).contiguous()
+            masks = None
+            drawn = self._masks_fn(B, 1) if self._masks_fn is not None else None
+            eng.precision = self.precision      # (the module's mask draw re-applies its own mode to the engine)
+            if drawn:
+                masks = {}
+                for name, buf in self.mask_bufs.items():
+                    m = drawn.get(name)
+                    if m is None:
+                        continue
+                    if m.dim() != 3 or tuple(m.shape[1:]) != (B, buf.shape[2]):
+                        raise ValueError("mask for %s must be (N, B, hist) = (., %d, %d), got %s" % (name, B, buf.shape[2], tuple(m.shape)))
+                    if m.shape[0] != 1 and self.steps >= m.shape[0]:
+                        raise ValueError("mask for %s holds %d frames; this is frame %d of the stream" % (name, m.shape[0], self.steps))
+                    buf.copy_(m[0 if m.shape[0] == 1 else self.steps].unsqueeze(0))
+                    masks[name] = buf
+            for i, x in enumerate(srcs):
+                self._src_p[i] = x.data_ptr()
+            ev = eng._tic("stream_advance")
+            check(eng.L.lfi_stream_advance(B, len(self._row_win), self._row_win, self._src_p, self._row_hist, self._row_dim,
+                                           noise.data_ptr(), self.noise.data_ptr(), s.C, ptr(self.frame_nb), self.guard.data_ptr(),
+                                           _stream()), "lfi_stream_advance")
+            eng._toc("stream_advance", ev)
+            self._pinned.copy_(self.guard, non_blocking=True)
+            gev = torch.cuda.Event()
+            gev.record()
+            self._guard_pending = gev
+            for x in srcs + [noise]:
+                x.record_stream(torch.cuda.current_stream(self.device))
+            if self.steps == 0 or os.environ.get("LFI_NO_GRAPH") == "1":
+                self._launch(masks, 1 if self.steps > 0 or self._resumed else 0)
+            else:
+                key = (self.frame_precision, masks is not None)
+                if self._graph is None or self._graph_key != key:
+                    timers, eng.timers = eng.timers, None
+                    try:
+                        torch.cuda.synchronize()
+                        g = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(g):
+                            self._launch(masks, 1)
+                    finally:
+                        eng.timers = timers
+                    self._graph, self._graph_key = g, key
+                ev = eng._tic("stream_graph")
+                self._graph.replay()
+                eng._toc("stream_graph", ev)
+                self.replays += 1
+            out = self.faces[:, self.hist1].clone()
+            self.steps += 1
+        if out.device == self.device and self._stream is not None:
+            out.record_stream(torch.cuda.current_stream(self.device))
+        return out
+
+    def _launch(self, masks, first_frame):
+        """The static part for the session's B windows, then the reverse chain for one frame: session-owned memory only."""
+        eng, s, B = self.eng, self.eng.spec, self.B
+        ev = eng._tic("stream_static")
+        data = dict(self.windows)
+        if self.frame_nb is not None:
+            data["frame_nb"] = self.frame_nb
+        # (sampling=False: the frame counter comes from the session's device counter, not from a host frame offset)
+        eng.build_features(data, None, B, 0, masks, self.cond, with_stash=False, skip_p1=True, sampling=False, windows=True)
+        eng._static_pre(self.cond, self.pre, B, self.c1, self._wp)
+        eng._toc("stream_static", ev)
+        dims = eng._flow_dims(B, 1)
+        dims.gemm_precision = self.frame_precision
+        p = eng._flow_params()
+        ev = eng._tic("stream_chain")
+        check(eng.L.lfi_flow_sample_seq_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
+                                             self.pre.data_ptr(), self.noise.data_ptr(), self.faces.data_ptr(), self.hist1 + 1,
+                                             self.hist1, 1, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
+                                             self.p1work.data_ptr(), self.work.data_ptr(), _stream()), "lfi_flow_sample_seq_from")
+        eng._toc("stream_chain", ev)
+
+    def _check_guard(self):
+        """The range guard of earlier steps (lfi_stream_advance folds max |x| of every value it moves into the session's guard word,
+        copied to pinned memory behind it): looked at once its copy has landed - never a host wait. A value beyond the fp16 pieces'
+        range (or a non-finite one) is reported with a warning, and the session samples with six bf16 products from then on."""
+        ev = self._guard_pending
+        if ev is None or not ev.query():
+            return
+        self._guard_pending = None
+        amax, limit = self.eng._guard_float(self._pinned), self.eng._fp16_piece_limit
+        if self.frame_precision == 9 and not (amax <= limit):
+            self.frame_precision = 5
+            warnings.warn("SampleStream: an earlier step saw max |x| = %r, beyond the range of the fp16-piece per-frame arithmetic (%g): "
+                          "this session samples with six bf16 products (no range caveat) from now on; frames since that input may be "
+                          "inaccurate" % (amax, limit), RuntimeWarning)

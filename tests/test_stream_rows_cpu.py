@@ -48,3 +48,42 @@ def test_sample_stream_has_reset_rows_and_open_stream_still_refuses_cpu_tensors(
     seed = {k: v[:, :fx.start].float().contiguous() for k, v in fx.group("infer/data/").items()}
     with pytest.raises(RuntimeError, match="GPU only"):
         m.open_stream(seed)
+
+
+def test_index_list_refusals_word_for_word():
+    """The one check of `rows` (reset_rows / save_rows / load_rows: distinct, not empty) and of load_rows' `entries` (one per row,
+    repeats allowed): every refusal a caller can receive, with its full text."""
+    import torch
+    from lets_face_it_amd.stream import _index_list
+
+    def rows(v, B=4):
+        return _index_list("rows", v, B, "the session's batch")
+
+    def entries(v, n, saved=3):
+        return _index_list("entries", v, saved, "the saved rows", count=n, distinct=False)
+
+    assert rows([2, 0]) == [2, 0] and rows((3,)) == [3] and rows(torch.tensor([1, 3])) == [1, 3] and rows(torch.tensor(2)) == [2]
+    assert rows(torch.tensor([0, 1], dtype=torch.int16)) == [0, 1] and rows(range(4)) == [0, 1, 2, 3]
+    assert entries([1, 1, 2], 3) == [1, 1, 2] and entries(torch.tensor([2, 2]), 2) == [2, 2] and entries(range(2), 2) == [0, 1]
+    text = "expected a sequence of ints or a 1-D CPU integer tensor, got "
+    for call, message in (
+            (lambda: rows([]), "rows: empty list"),
+            (lambda: rows(torch.zeros(0, dtype=torch.long)), "rows: empty list"),
+            (lambda: rows([0, 4, -1]), "rows: [4, -1] outside the session's batch (0 .. 3)"),
+            (lambda: rows([2, 0, 2, 1, 1]), "rows: [1, 2] listed more than once"),
+            (lambda: rows([0, 7, 0]), "rows: [7] outside the session's batch (0 .. 3)"),   # the range before the repeats
+            (lambda: rows(3), "rows: " + text + "3"),
+            (lambda: rows([0, 1.0]), "rows: " + text + "[0, 1.0]"),
+            (lambda: rows(torch.tensor([0.0, 1.0])), "rows: " + text + "(2,) torch.float32 on cpu"),
+            (lambda: rows(torch.tensor([True, False])), "rows: " + text + "(2,) torch.bool on cpu"),
+            (lambda: rows(torch.zeros(2, 2, dtype=torch.long)), "rows: " + text + "(2, 2) torch.int64 on cpu"),
+            (lambda: entries([0], 2), "entries: 1 listed for 2 rows"),
+            (lambda: entries([], 1), "entries: 0 listed for 1 rows"),
+            (lambda: entries([0, 3], 2), "entries: [3] outside the saved rows (0 .. 2)"),
+            (lambda: entries([0, 5, 1], 2), "entries: 3 listed for 2 rows"),               # the count before the range
+            (lambda: entries(range(4), 4), "entries: [3] outside the saved rows (0 .. 2)"),
+            (lambda: entries("ab", 2), "entries: " + text + "'ab'"),
+            (lambda: entries(torch.tensor([0.5]), 1), "entries: " + text + "(1,) torch.float32 on cpu")):
+        with pytest.raises(ValueError) as err:
+            call()
+        assert str(err.value) == message
