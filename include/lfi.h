@@ -404,6 +404,18 @@ int lfi_flow_sample_seq_from(const lfi_flow_dims* d, const lfi_flow_params* p, c
                              const float* wct, long E, int hist1, float* pre_static, const float* noise,
                              float* faces, int seq_len, int start, int nframes, int first_frame,
                              float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work, void* stream);
+/* lfi_flow_sample_seq_from that also leaves nll (nframes x B, frame-major): the per-frame NLL in bits of every frame it generates,
+ * -(logdet_fwd(x) + sum_c -0.5 (z_c^2 + log 2 pi)) / ln 2 at the z it was given in `noise` - the value lfi_flow_seq_fwd's nll holds
+ * for that frame when the generated sequence is fed back teacher-forced (SeqGlow.loss, glow/models.py:563-565). The model's own
+ * density (temperature 1) of the frame, not a density of the tempered sampling distribution. The reverse cells already form every
+ * coupling log-det: on the one-launch-per-frame chain the rows' running sum crosses the chain beside the tile, with no launch and no
+ * pass added. nll_work: lfi_flow_sample_nll_work_floats(d) floats (the hand-over words). nll == NULL: lfi_flow_sample_seq_from. */
+long lfi_flow_sample_nll_work_floats(const lfi_flow_dims* d);
+int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep,
+                            const float* wct, long E, int hist1, float* pre_static, const float* noise,
+                            float* faces, int seq_len, int start, int nframes, int first_frame,
+                            float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
+                            float* nll, float* nll_work, void* stream);
 /* One frame forward of a streaming sampling session (SeqGlow.open_stream; glow/models.py:567-596 one frame at a time), in ONE launch:
  * every window i (B x hist[i] x dim[i], rows per batch entry) moves up by one frame in place, and its last row receives src[i] (B x
  * dim[i]), or - src[i] == NULL, the prev_p1_face window of the session's own output - keeps the frame the last step generated there;

@@ -1700,10 +1700,16 @@ __global__ __launch_bounds__(NT) void flow_pipe_fwd_kernel(FlowK f) {
 // need / pub_value: the progress value waited for / published (1 for the one-frame chain; timestep + 1 in the persistent reverse
 // walk). false = the wait was abandoned (abort word set): nothing was computed.
 // XW (with X3): the weights come as the fp16 fragment images lfi_flow_prep left (FlowK.hwz ..): no f32 fragments, no split here.
-template <int NG, bool X3 = false, bool XW = false>
+// NLL (the chain of a sampler that reports its frames' likelihood): the rows' running log-density log p(z) - sum of the reverse
+// coupling log-dets so far travels with the tile. q_in: one float per row from step k + 1, handed over as the tile is (null: this
+// cell starts it from the prior term of the noise tile it stages); q_out: where this cell leaves it - sc1 stores in front of the
+// publish - or, q_last, the finished -(q + logdet_const) / ln 2 of the frame in bits. One writer per word, k descending: a fixed
+// summation order. Not NLL: none of it is compiled.
+template <int NG, bool X3 = false, bool XW = false, bool NLL = false>
 __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, int b0, const unsigned* wait_flag,
                                               unsigned* abort_w, unsigned* pub_flag, int* s_ok, unsigned need = 1u,
-                                              unsigned pub_value = 1u) {
+                                              unsigned pub_value = 1u, const float* q_in = nullptr, float* q_out = nullptr,
+                                              bool q_last = false) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, kq = lane >> 4;
   const int ri = tid >> 5, cl = tid & 31;
@@ -1898,11 +1904,18 @@ __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, 
   if (wait_flag && !pipe_acquire(wait_flag, need, abort_w, tid, s_ok, false)) return false;
   REV_STAMP(2);
   // ---- R0: stage the tile [z1 | z2']
+  float q = 0.0f;   // NLL: lane cl == 0 carries its row's running log-density; the first cell's lanes their parts of sum z^2
   {
     const int row = b0 + ri;
     const bool rok = row < rows;
+    if constexpr (NLL) {
+      if (q_in && cl == 0 && rok) q = ld_tile(q_in + row, false);   // (in flight under the cell: needed in R3)
+    }
     for (int c = cl; c < C16; c += 32) {
       const float v = (c < C && rok) ? ld_tile(io.x_in + (long)row * io.ldx + c, wait_flag == nullptr) : 0.0f;
+      if constexpr (NLL) {
+        if (!q_in) q += v * v;
+      }
       if (c < C) Yrm[ri * ldy + c] = v;
       if (c < Ch) Zt[c * LT + ri] = v;
       if (c < Ch || c >= C) Yt[c * LT + ri] = v;   // z1 rows and the zero k padding; z2 rows come from R3
@@ -1981,6 +1994,18 @@ __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, 
     if (cl == 0 && row < rows && io.l_out) {
       if (io.l_accumulate) io.l_out[row] += lg; else io.l_out[row] = lg;
     }
+    if constexpr (NLL) {
+      if (!q_in) {   // log p(z) of the prior draw: sum_c -0.5 (z_c^2 + log 2 pi)
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+        q = -0.5f * (q + (float)C * LOG2PI_F);
+      }
+      if (cl == 0 && row < rows) {
+        q -= lg;   // forward log-det of this step's coupling = -lg
+        if (q_last) q_out[row] = -(q + f.ldconst[0]) / LN2_F;
+        else st_sc1(q_out + row, q);
+      }
+    }
   }
   __syncthreads();
   REV_STAMP(6);
@@ -2042,8 +2067,11 @@ struct RevChain {
   const float* faces;     // row 0 of the frames buffer (row pitch ld_frame)
   long xf_off;            // first window column of the next frame in a row: (t + 1 - hist1) * C
   int K1, NM1;
+  // NLL instantiations only: the rows' running log-density crosses the chain beside the tile (rev_fast_cell)
+  float *qa, *qb;         // B floats each: step k writes (k & 1) ? qa : qb, as the tiles ping-pong
+  float* nll;             // B floats: this frame's NLL in bits, written by step 0
 };
-template <int NG, bool X3, bool XW = false>
+template <int NG, bool X3, bool XW = false, bool NLL = false>
 __global__ __launch_bounds__(NT) void flow_rev_chain_kernel(FlowK f, RevChain rc) {
   __shared__ int s_id, s_ok;
   if (threadIdx.x == 0) s_id = (int)atomicAdd(rc.pipe, 1u);
@@ -2064,12 +2092,21 @@ __global__ __launch_bounds__(NT) void flow_rev_chain_kernel(FlowK f, RevChain rc
   if (NG == 4) { io.c_prev = rc.has_prev ? rc.cstate + (long)k * f.B * f.H : nullptr; io.c_out = rc.cstate + (long)k * f.B * f.H; }
   io.gic = rc.gic + (long)k * f.B * f.G;
   io.stamp_base = rc.frame_no < 128 ? 1024 + 16 * rc.frame_no + 1 : 0;
+  if constexpr (NLL)
+    rev_fast_cell<NG, X3, XW, true>(f, io, bt * MB, k + 1 < f.Ks ? prog + (k + 1) * nbt + bt : nullptr, rc.pipe + 1,
+                                    k > 0 ? prog + k * nbt + bt : nullptr, &s_ok, 1u, 1u,
+                                    k + 1 < f.Ks ? (((k + 1) & 1) ? rc.qa : rc.qb) : nullptr,
+                                    k == 0 ? rc.nll : ((k & 1) ? rc.qa : rc.qb), k == 0);
+  else
   rev_fast_cell<NG, X3, XW>(f, io, bt * MB, k + 1 < f.Ks ? prog + (k + 1) * nbt + bt : nullptr, rc.pipe + 1,
                     k > 0 ? prog + k * nbt + bt : nullptr, &s_ok);
   if (k == 0 && ld_agent(rc.pipe + 1) != 0u) {   // an abandoned chain must not pass for a frame
     const int row = bt * MB + (int)(threadIdx.x >> 5);
     if (row < f.B)
       for (int c = threadIdx.x & 31; c < f.C; c += 32) rc.frame[(long)row * rc.ld_frame + c] = __builtin_nanf("");
+    if constexpr (NLL) {   // (the thread that wrote the row's word in R3, if the cell got that far)
+      if (row < f.B && (threadIdx.x & 31) == 0) rc.nll[row] = __builtin_nanf("");
+    }
   }
   if (k == 0 && rc.xf) {
     // the frame's rows of this tile are on their way to memory: drain, meet, then read the window back past the L1 (agent scope)
@@ -3974,6 +4011,36 @@ extern "C" int lfi_flow_sample_seq_from(const lfi_flow_dims* d, const lfi_flow_p
                                         long E, int hist1, float* pre_static, const float* noise, float* faces, int seq_len,
                                         int start, int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1,
                                         float* p1work, float* work, void* stream) {
+  return lfi_flow_sample_seq_nll(d, p, prep, wct, E, hist1, pre_static, noise, faces, seq_len, start, nframes, first_frame, h, cstate,
+                                 p1, p1work, work, nullptr, nullptr, stream);
+}
+
+// The per-step launches' finish of a frame's NLL (LFI_SAMPLE_CHAIN=0 and the generic cell; the chain kernel does this in its cells):
+// acc[b] = sum over the flow steps of the reverse coupling log-dets, left there by the cells' l_out.
+__global__ __launch_bounds__(256) void sample_nll_finish_kernel(const float* __restrict__ noise, const float* __restrict__ acc,
+                                                                const float* __restrict__ ldconst, int B, int C,
+                                                                float* __restrict__ nll) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  float lp = 0.0f;
+  for (int c = 0; c < C; ++c) {
+    const float v = noise[(long)b * C + c];
+    lp += -0.5f * (v * v + LOG2PI_F);
+  }
+  nll[b] = -(ldconst[0] - acc[b] + lp) / LN2_F;
+}
+
+extern "C" long lfi_flow_sample_nll_work_floats(const lfi_flow_dims* d) {
+  if (!d) return 0;
+  return 2L * d->B + 8;   // the two ping-pong hand-over arrays of the chain (the first is the per-step launches' accumulator)
+}
+
+// lfi_flow_sample_seq_from that also leaves the per-frame NLL (bits) of every frame it generates in nll (nframes x B); nll == NULL:
+// lfi_flow_sample_seq_from itself - the same launches of the same kernels.
+extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct,
+                                       long E, int hist1, float* pre_static, const float* noise, float* faces, int seq_len,
+                                       int start, int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1,
+                                       float* p1work, float* work, float* nll, float* nll_work, void* stream) {
   FlowK f = {};
   int rc = fill_flow(d, p, prep, &f, "lfi_flow_sample_seq");
   if (rc) return rc;
@@ -3982,6 +4049,7 @@ extern "C" int lfi_flow_sample_seq_from(const lfi_flow_dims* d, const lfi_flow_p
   LFI_REQUIRE(hist1 >= 0 && hist1 <= start && start + nframes <= seq_len, "lfi_flow_sample_seq: bad frame range");
   LFI_REQUIRE((long)hist1 * d->C <= E, "lfi_flow_sample_seq: window wider than the feature vector");
   LFI_REQUIRE(!d->lstm || cstate, "lfi_flow_sample_seq: the LSTM cell needs cstate");
+  LFI_REQUIRE(!nll || nll_work, "lfi_flow_sample_seq_nll: nll needs nll_work (lfi_flow_sample_nll_work_floats)");
   const int p1kind = p1 ? p1->kind : 0;
   LFI_REQUIRE(p1kind >= 0 && p1kind <= 3, "lfi_flow_sample_seq: bad p1_face encoder kind %d", p1kind);
   LFI_REQUIRE(p1kind == 0 || (p1work && p1->hid > 0), "lfi_flow_sample_seq: encoded p1_face window needs p1work");
@@ -4024,11 +4092,17 @@ extern "C" int lfi_flow_sample_seq_from(const lfi_flow_dims* d, const lfi_flow_p
   const bool xf_chain = fused && chain && !(xce && xce[0] == '0');
   // the reverse cells' weights as the fp16 fragment images lfi_flow_prep left (no split in every workgroup of every frame)
   const bool xw = x3 && chain && flow_x3h_images_ok(f) && flow_sample_wfrag16_enabled();
-  if (chain) {
+  if (chain && !nll) {
     rc = f.lstm ? set_flow_lds(flow_rev_chain_kernel<4, false>, lds, "lfi_flow_sample_seq")
                 : (xw ? set_flow_lds(flow_rev_chain_kernel<3, true, true>, lds, "lfi_flow_sample_seq")
                       : (x3 ? set_flow_lds(flow_rev_chain_kernel<3, true>, lds, "lfi_flow_sample_seq")
                             : set_flow_lds(flow_rev_chain_kernel<3, false>, lds, "lfi_flow_sample_seq")));
+    if (rc) return rc;
+  } else if (chain) {
+    rc = f.lstm ? set_flow_lds(flow_rev_chain_kernel<4, false, false, true>, lds, "lfi_flow_sample_seq_nll")
+                : (xw ? set_flow_lds(flow_rev_chain_kernel<3, true, true, true>, lds, "lfi_flow_sample_seq_nll")
+                      : (x3 ? set_flow_lds(flow_rev_chain_kernel<3, true, false, true>, lds, "lfi_flow_sample_seq_nll")
+                            : set_flow_lds(flow_rev_chain_kernel<3, false, false, true>, lds, "lfi_flow_sample_seq_nll")));
     if (rc) return rc;
   }
   for (int n = 0; n < nframes; ++n) {
@@ -4109,7 +4183,14 @@ extern "C" int lfi_flow_sample_seq_from(const lfi_flow_dims* d, const lfi_flow_p
         hipError_t me = hipMemsetAsync(chain_state, 0, chain_words * sizeof(unsigned), st);
         LFI_REQUIRE(me == hipSuccess, "lfi_flow_sample_seq: hipMemsetAsync: %s", hipGetErrorString(me));
       }
-      if (f.lstm) hipLaunchKernelGGL((flow_rev_chain_kernel<4, false>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
+      if (nll) {   // the same grid; the cells also pass the rows' running log-density down the chain
+        rcn.qa = nll_work; rcn.qb = nll_work + B; rcn.nll = nll + (long)n * B;
+        if (f.lstm) hipLaunchKernelGGL((flow_rev_chain_kernel<4, false, false, true>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
+        else if (xw) hipLaunchKernelGGL((flow_rev_chain_kernel<3, true, true, true>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
+        else if (x3) hipLaunchKernelGGL((flow_rev_chain_kernel<3, true, false, true>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
+        else hipLaunchKernelGGL((flow_rev_chain_kernel<3, false, false, true>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
+      }
+      else if (f.lstm) hipLaunchKernelGGL((flow_rev_chain_kernel<4, false>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
       else if (xw) hipLaunchKernelGGL((flow_rev_chain_kernel<3, true, true>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
       else if (x3) hipLaunchKernelGGL((flow_rev_chain_kernel<3, true>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
       else hipLaunchKernelGGL((flow_rev_chain_kernel<3, false>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
@@ -4126,11 +4207,15 @@ extern "C" int lfi_flow_sample_seq_from(const lfi_flow_dims* d, const lfi_flow_p
       if (f.lstm) { io.c_prev = first_frame + n > 0 ? cstate + (long)k * B * H : nullptr; io.c_out = cstate + (long)k * B * H; }
       if (k == 0) { io.x_out = faces + (long)t * C; io.ldxo = (long)seq_len * C; }
       else { io.x_out = (k & 1) ? xa : xb; io.ldxo = C; }
+      if (nll) { io.l_out = nll_work; io.l_accumulate = k + 1 < Ks; }   // (launch after launch: no two workgroups at one word at a time)
       if (!fast) hipLaunchKernelGGL(flow_step_kernel<true>, dim3(f.nbt), dim3(NT), lds, st, f, io);
       else if (f.lstm) hipLaunchKernelGGL(flow_step_rev_fast_kernel<4>, dim3(f.nbt), dim3(NT), lds, st, f, io);
       else hipLaunchKernelGGL(flow_step_rev_fast_kernel<3>, dim3(f.nbt), dim3(NT), lds, st, f, io);
       xin = io.x_out; ldx = io.ldxo;
     }
+    if (nll)
+      hipLaunchKernelGGL(sample_nll_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, noise + (long)n * B * C, nll_work,
+                         f.ldconst, B, C, nll + (long)n * B);
   }
   LFI_LAUNCH_CHECK("lfi_flow_sample_seq");
   return LFI_OK;

@@ -27,7 +27,7 @@ import torch
 
 from . import _lib
 from ._lib import EncDesc, FlowDims, FlowGrads, FlowParams, GemmDesc, P1Enc, PGemmDesc, check, ptr, translate_oom
-from .stream import SampleStream, StreamRows  # noqa: F401 - StreamRows: callers import it from here
+from .stream import SampleStream, StreamRows, check_return_nll  # noqa: F401 - StreamRows: callers import it from here
 
 ENC_ORDER = ("p1_face", "p2_face", "p1_speech", "p2_speech")  # FeatureEncoder concat order (models.py:127-143)
 FLOW_FIELDS = ("an_bias", "an_logs", "inv_l", "inv_u", "inv_logs", "inv_w", "w_ih", "w_hh", "b_ih", "b_hh",
@@ -1369,16 +1369,21 @@ class GlowEngine:
 
     # ------------------------------------------------------------------ sampling / inversion
     @translate_oom
-    def sample(self, seq_len, data, noise, masks=None):
-        """SeqGlow.inference (models.py:567-596); see _sample. With the static part on a partial-chip stream (LFI_SAMPLE_STATIC_CUS)
+    def sample(self, seq_len, data, noise, masks=None, return_nll=False):
+        """SeqGlow.inference (models.py:567-596); see _sample. return_nll: -> (frames, nll), nll (seq_len - start, B) float32 on the
+        device, the per-frame NLL in bits of every generated frame: what forward() reports in `losses` for that frame when the
+        generated sequence is fed back teacher-forced - the model's own density (temperature 1) of the frame at the prior draw
+        `noise` it was made from, not a density of the tempered sampling distribution. With the static part on a partial-chip stream (LFI_SAMPLE_STATIC_CUS)
         the whole call runs on a private non-blocking stream between two joins with the caller's: hipExtStreamCreateWithCUMask makes a
         BLOCKING stream, which takes turns with the legacy default stream - and that is the stream most callers are on. (Also without
         a partial-chip stream when the caller is on the legacy default stream: the per-run graphs are not replayed there.)"""
+        check_return_nll(return_nll)
         caller = torch.cuda.current_stream(self.device)
         with self._off_legacy_stream(self, "_sample_stream", force=self._sample_static_cus(seq_len - self.spec.start) > 0) as st:
-            out = self._sample(seq_len, data, noise, masks)
+            out = self._sample(seq_len, data, noise, masks, return_nll)
         if st != caller:
-            out.record_stream(caller)
+            for t in (out if return_nll else (out,)):
+                t.record_stream(caller)
         return out
 
     @contextlib.contextmanager
@@ -1400,8 +1405,10 @@ class GlowEngine:
             yield own
         caller.wait_stream(own)
 
-    def _sample(self, seq_len, data, noise, masks=None):
+    def _sample(self, seq_len, data, noise, masks=None, return_nll=False):
         """SeqGlow.inference (models.py:567-596) with the prior noise given: (seq_len - start, B, C), already * eps.
+        return_nll: the chain's cells also carry every row's log-density down the flow steps (lfi_flow_sample_seq_nll: no launch
+        added per frame) -> (frames, nll (seq_len - start, B)).
 
         The generated frames are produced in a few RUNS (LFI_SAMPLE_RUNS, default 4 from 64 frames up, 6 from 96 when the static part
         has its own CUs): everything of a run that
@@ -1481,8 +1488,18 @@ class GlowEngine:
         hist1 = e1.hist
         p1 = self._p1_enc()
         p1work = self._buf("scratch.sample_p1", self.L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(p1), hist1))
+        # engine-owned at stable addresses, as everything the captured graphs touch; run o writes rows [o, o + n)
+        nll = self._buf("sample_nll", F) if return_nll else None
+        nll_work = self._buf("scratch.sample_nll", self.L.lfi_flow_sample_nll_work_floats(C.byref(dims))) if return_nll else None
 
         def launch(o, n):
+            if return_nll:
+                check(self.L.lfi_flow_sample_seq_nll(C.byref(dims), C.byref(p), self.prep.data_ptr(), self.wct_f.data_ptr(), s.ldf, hist1,
+                                                     pre.data_ptr() + 4 * o * B * KD, nz.data_ptr() + 4 * o * B * s.C, faces.data_ptr(),
+                                                     seq_len, s.start + o, n, o, h.data_ptr(), ptr(cs), C.byref(p1), p1work.data_ptr(),
+                                                     work.data_ptr(), nll.data_ptr() + 4 * o * B, nll_work.data_ptr(), _stream()),
+                      "lfi_flow_sample_seq_nll")
+                return
             check(self.L.lfi_flow_sample_seq_from(C.byref(dims), C.byref(p), self.prep.data_ptr(), self.wct_f.data_ptr(), s.ldf, hist1,
                                                   pre.data_ptr() + 4 * o * B * KD, nz.data_ptr() + 4 * o * B * s.C, faces.data_ptr(),
                                                   seq_len, s.start + o, n, o, h.data_ptr(), ptr(cs), C.byref(p1), p1work.data_ptr(),
@@ -1492,7 +1509,7 @@ class GlowEngine:
         # small batch: from the second call of a shape on, every run of it is replayed as ONE hipGraph (captured once; every buffer
         # it touches is engine-owned and keeps its address). LFI_NO_GRAPH=1 keeps eager launches.
         key = (B, seq_len, self.precision, int(dims.gemm_precision), faces.data_ptr(), pre.data_ptr(), nz.data_ptr(), h.data_ptr(),
-               self.prep.data_ptr(), tuple(runs))
+               self.prep.data_ptr(), tuple(runs), ptr(nll), ptr(nll_work))   # (return_nll flips: another kernel, a new capture)
         graphs = self._sample_graphs.get(key)
         if graphs is None and os.environ.get("LFI_NO_GRAPH") != "1" and self._sample_seen.get(key):
             torch.cuda.synchronize()
@@ -1518,6 +1535,8 @@ class GlowEngine:
         out = faces[:, s.start:].clone()
         if fp == 9:
             self._watch_sample_output(out)
+        if return_nll:
+            return out, nll[:F].view(nframes, B).clone()
         return out
 
     # ---- steps that sample() and the streaming sessions (stream.py) share: each rule is written here once
@@ -1757,8 +1776,9 @@ class GlowEngine:
 
     # ------------------------------------------------------------------ streaming sampling
     @translate_oom
-    def open_stream(self, seed, noise_fn, masks_fn=None, bound=None):
+    def open_stream(self, seed, noise_fn, masks_fn=None, bound=None, return_nll=False):
         """A SampleStream over this engine (SeqGlow.open_stream): seed = {modality: (B, >= start, dim)} holding the first `start`
         frames of every modality; noise_fn(B, C) draws a step's prior noise (already * eps); masks_fn(B, N) the window encoders'
-        dropout masks (None = none); bound() is False once the owning module has re-bound to another engine."""
-        return SampleStream(self, seed, noise_fn, masks_fn, bound)
+        dropout masks (None = none); bound() is False once the owning module has re-bound to another engine; return_nll (fixed for
+        the session): step() -> (frame, nll), as sample()'s."""
+        return SampleStream(self, seed, noise_fn, masks_fn, bound, return_nll)

@@ -513,8 +513,14 @@ class SeqGlow(nn.Module):
     def loss(self, objective, z):
         return (-(objective + modules.GaussianDiag.logp_simplified(z))) / _LN2
 
-    def inference(self, seq_len, data=None, noise=None):
-        """Autoregressive sampling (models.py:567-596). noise: optional (seq_len - start, B, C) prior draws * eps."""
+    def inference(self, seq_len, data=None, noise=None, return_nll=False):
+        """Autoregressive sampling (models.py:567-596). noise: optional (seq_len - start, B, C) prior draws * eps.
+        return_nll=True -> (frames, nll): nll (seq_len - start, B) float32 on the device, the orientation of forward()'s stacked
+        `losses`, holds every generated frame's NLL in bits - what forward() reports for that frame when the generated sequence is fed
+        back teacher-forced (loss(), models.py:563-565), at no extra pass. It is the model's own density of the frame (temperature
+        1) evaluated at the prior draw z the sampler was given (`noise`, already * eps), not a density of the tempered sampling
+        distribution."""
+        _engine.check_return_nll(return_nll)
         seed = data["p1_face"]
         eng = self._ensure_engine(seed.device)
         start = get_longest_history(self.hparams.Conditioning)
@@ -524,9 +530,9 @@ class SeqGlow(nn.Module):
             noise = modules.GaussianDiag.sample(shape, self.hparams.Infer["eps"])
         masks = self._draw_masks(B, seq_len - start, seed.device)
         with torch.no_grad():
-            return eng.sample(seq_len, data, noise.contiguous().float(), masks)
+            return eng.sample(seq_len, data, noise.contiguous().float(), masks, return_nll=return_nll)
 
-    def open_stream(self, seed, eps=None):
+    def open_stream(self, seed, eps=None, return_nll=False):
         """Streaming autoregressive sampling: inference() one frame per call, for a live agent whose speech and interlocutor arrive
         frame by frame. seed: a dict like inference()'s `data` holding the first start = get_longest_history(...) frames of every
         modality (p1_face: B x start x C). Returns a lets_face_it_amd.engine.SampleStream: step(frame, noise=None) with frame =
@@ -548,7 +554,15 @@ class SeqGlow(nn.Module):
         StreamRows.from_state_dict()), branch (one entry into several rows) and roll back. Both run between steps, in one small
         launch, without a host wait, and leave the other rows alone. Within one session, or between sessions of one batch size, a
         moved row continues bit for bit; at another batch size within the session-against-inference() tolerance. Rows saved under
-        other weights are refused on the same engine; across processes equal weights are the caller's responsibility."""
+        other weights are refused on the same engine; across processes equal weights are the caller's responsibility.
+
+        return_nll=True (fixed for the session; SampleStream.return_nll reads it back): step() returns (frame, nll), nll (B,) float32
+        = the frame's NLL in bits as inference(return_nll=True) defines it - the model's own density (temperature 1) at the prior
+        draw the step used, not a density of the tempered sampling distribution. It is an output of a step, not state: the row
+        record and reset_rows / save_rows / load_rows are unchanged, and a row reseeded or loaded between steps reports the NLL of
+        its own next frame. Best-of-N: load one saved entry into n rows, step, nll.argmin() over them, save_rows([best]) and
+        load_rows it back over the others."""
+        _engine.check_return_nll(return_nll)
         p1 = seed.get("p1_face") if isinstance(seed, dict) else None
         if p1 is None:
             raise KeyError("batch is missing modality 'p1_face'")
@@ -561,7 +575,8 @@ class SeqGlow(nn.Module):
             return torch.empty(B, C, device=dev).normal_(0.0, float(eps))
 
         with torch.no_grad():
-            return eng.open_stream(seed, noise_fn, lambda B, N: self._draw_masks(B, N, dev), lambda: self.engine is eng)
+            return eng.open_stream(seed, noise_fn, lambda B, N: self._draw_masks(B, N, dev), lambda: self.engine is eng,
+                                   return_nll=return_nll)
 
     def invert(self, z_seq, data):
         """-> (reconstr_seq: list[N] of (B, C), backward_loss (1,))   (models.py:617-645)"""

@@ -26,6 +26,12 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def check_return_nll(value):
+    """The return_nll argument of the samplers (inference / sample / open_stream): a bool, checked before any launch."""
+    if not isinstance(value, bool):
+        raise TypeError("return_nll: expected a bool, got %s %r" % (type(value).__name__, value))
+
+
 def _index_list(name, idx, bound, where, count=None, distinct=True):
     """The index-list argument `name` of reset_rows / save_rows / load_rows: a sequence of ints or a 1-D CPU integer tensor -> a list
     of ints in [0, bound); `where` words what lies beyond. count: as many as that are wanted (None: any number but none at all);
@@ -110,16 +116,22 @@ class SampleStream:
     """Streaming autoregressive sampling: SeqGlow.inference (models.py:567-596) one frame per call, for a live agent whose
     conditioning arrives frame by frame. Open with `start` seed frames, then step(frame) with frame t of every modality with
     history > 0 -> the generated p1_face frame t (B, C). Given the same inputs and noise it produces what inference() produces.
+    Opened with return_nll=True a step returns (frame, nll): nll (B,) is the frame's NLL in bits under the model, what forward() reports
+    for it teacher-forced - the model's own density (temperature 1) at the prior draw the step was given, not a density of the
+    tempered sampling distribution. It is an output of the step, not state: rows reseeded or loaded between steps report their own
+    next frame's, and the row record does not hold it.
 
     Per step: lfi_stream_advance (one eager launch: the session's conditioning windows, its window of generated faces, the noise and
     the frame counter move forward by one frame), then the static part for B windows (window encoders + the static cond_transform
-    columns, as _sample's static()) and lfi_flow_sample_seq_from for one frame, whose recurrent state h / c carries across steps. Those
+    columns, as _sample's static()) and lfi_flow_sample_seq_from (lfi_flow_sample_seq_nll with return_nll) for one frame, whose recurrent state h / c carries across steps. Those
     two touch only session-owned memory at fixed addresses: from the second step on they are ONE captured hipGraph, replayed.
     Every workspace they write is the session's own (the engine's `_ws`, prep and folded weights are swapped for the session's while a
     step runs), so training, inference() and other sessions can run between steps. Weights are frozen: a parameter change after the
     open (GlowEngine.param_version) makes step() raise."""
 
-    def __init__(self, eng, seed, noise_fn, masks_fn=None, bound=None):
+    def __init__(self, eng, seed, noise_fn, masks_fn=None, bound=None, return_nll=False):
+        check_return_nll(return_nll)
+        self.return_nll = return_nll            # fixed for the session: part of what the captured graph launches
         s = eng.spec
         self.eng = eng
         self._noise_fn, self._masks_fn, self._bound = noise_fn, masks_fn, bound
@@ -163,6 +175,8 @@ class SampleStream:
             dims = eng._flow_dims(B, 1)
             self.work = eng._buf("stream_chain_work", eng.L.lfi_flow_sample_work_floats(C.byref(dims)))
             self.p1work = eng._buf("stream_p1work", eng.L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
+            self.nll = eng._buf("stream_nll", B)[:B] if return_nll else None
+            self.nll_work = eng._buf("stream_nll_work", eng.L.lfi_flow_sample_nll_work_floats(C.byref(dims))) if return_nll else None
             self.guard = eng._buf_i32("stream_guard_word", 1)
             self._pinned = torch.zeros(1, dtype=torch.int32).pin_memory()
             # per-frame arithmetic, picked once (as _sample picks it per call): fp16 pieces (9) when the parameters and the seed sit inside
@@ -349,6 +363,7 @@ class SampleStream:
         self._graph = None
         self._state = None
         self.faces = self.noise = self.windows = self.cond = self.pre = self.h = self.cs = self.work = self.p1work = self._wins = None
+        self.nll = self.nll_work = None
 
     def __enter__(self):
         return self
@@ -360,7 +375,8 @@ class SampleStream:
     @translate_oom
     def step(self, frame, noise=None):
         """frame: {modality: (B, dim)} = frame t of every modality with history > 0 (extra keys are ignored). noise: (B, C) prior
-        draw already * eps, or None (drawn with the session's eps). -> generated p1_face frame t, (B, C)."""
+        draw already * eps, or None (drawn with the session's eps). -> generated p1_face frame t, (B, C); a session opened with
+        return_nll=True -> (frame, nll), nll (B,) float32: the frame's NLL in bits (see the class)."""
         s, eng, B = self.eng.spec, self.eng, self.B
         self._check_usable()
         if not isinstance(frame, dict):
@@ -425,10 +441,13 @@ class SampleStream:
                 eng._toc("stream_graph", ev)
                 self.replays += 1
             out = self.faces[:, self.hist1].clone()
+            nll = self.nll.clone() if self.return_nll else None
             self.steps += 1
         if out.device == self.device and self._stream is not None:
             out.record_stream(torch.cuda.current_stream(self.device))
-        return out
+            if nll is not None:
+                nll.record_stream(torch.cuda.current_stream(self.device))
+        return (out, nll) if self.return_nll else out
 
     def _launch(self, masks, first_frame):
         """The static part for the session's B windows, then the reverse chain for one frame: session-owned memory only."""
@@ -445,6 +464,14 @@ class SampleStream:
         dims.gemm_precision = self.frame_precision
         p = eng._flow_params()
         ev = eng._tic("stream_chain")
+        if self.return_nll:
+            check(eng.L.lfi_flow_sample_seq_nll(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
+                                                self.pre.data_ptr(), self.noise.data_ptr(), self.faces.data_ptr(), self.hist1 + 1,
+                                                self.hist1, 1, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
+                                                self.p1work.data_ptr(), self.work.data_ptr(), self.nll.data_ptr(),
+                                                self.nll_work.data_ptr(), _stream()), "lfi_flow_sample_seq_nll")
+            eng._toc("stream_chain", ev)
+            return
         check(eng.L.lfi_flow_sample_seq_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
                                              self.pre.data_ptr(), self.noise.data_ptr(), self.faces.data_ptr(), self.hist1 + 1,
                                              self.hist1, 1, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),

@@ -2,7 +2,7 @@
 alternative without a session: re-running SeqGlow.inference over the whole prefix for every new frame.
 
   python tools/stream_latency.py [--batches 1,16,256] [--steps 200] [--warmup 20] [--prefixes 50,150,300] [--out FILE]
-                                 [--churn 1,16,64 [--churn-batch 256]] [--migrate 16 [--migrate-batch 256]]
+                                 [--churn 1,16,64 [--churn-batch 256]] [--migrate 16 [--migrate-batch 256]] [--nll 1,256]
 
 Per batch size: the wall-clock time from step() to the generated frame on the host (a synchronise after every step: what a live agent
 waits for), its GPU time (HIP events around the step), and a per-kernel breakdown from the engine's enable_timing on an eager session
@@ -17,7 +17,11 @@ stream of its own), interleaved step by step in one session: a plain step, resee
 
 --migrate r1,r2,..: two sessions of --migrate-batch rows; before every step of the first, r of its rows (a different set each step) are
 saved with SampleStream.save_rows and loaded into rows of the second with load_rows - a conversation moving to another session. Per r
-and caller as --churn, interleaved step by step in one process: a plain step, save + load + step, and the save + load pair alone."""
+and caller as --churn, interleaved step by step in one process: a plain step, save + load + step, and the save + load pair alone.
+
+--nll b1,b2,..: per batch size two sessions on the same seed, frames and noise, one opened with return_nll=True (every step also
+returns the frame's NLL) and one without, interleaved step by step in one process: what the likelihood costs a step. Then
+inference() over --nll-frames generated frames with and without return_nll, the two alternated call by call."""
 import argparse
 import contextlib
 import os
@@ -40,6 +44,8 @@ def main():
     ap.add_argument("--churn-batch", type=int, default=256)
     ap.add_argument("--migrate", default=None, help="rows saved and loaded into a second session before every step, e.g. 16")
     ap.add_argument("--migrate-batch", type=int, default=256)
+    ap.add_argument("--nll", default=None, help="batch sizes of the return_nll leg, e.g. 1,256 (default: no such leg)")
+    ap.add_argument("--nll-frames", type=int, default=0, help="with --nll: also inference() over this many generated frames, flag off / on")
     a = ap.parse_args()
     import bench
     helper = bench.start_smi_helper()       # (before the GPU is initialised: see bench.py)
@@ -140,6 +146,9 @@ def main():
     migrate = []
     if a.migrate:
         migrate = churn_leg(m, dev, a.migrate_batch, [int(v) for v in a.migrate.split(",")], a.steps, a.warmup, dims, start, C, migrate=True)
+    nll = []
+    if a.nll:
+        nll = nll_leg(m, dev, [int(v) for v in a.nll.split(",")], a.steps, a.warmup, dims, start, C, a.nll_frames)
     bench.stop_smi_helper(helper)
 
     lines += ["## One streaming step", "",
@@ -171,6 +180,11 @@ def main():
                   "| r | caller | leg | wall ms, median | wall ms, p90 | GPU ms, median (events) |", "|---|---|---|---|---|---|"]
         for r, caller, leg, med, p90, gmed in migrate:
             lines.append("| %d | %s | %s | %.3f | %.3f | %.3f |" % (r, caller, leg, med, p90, gmed))
+    if nll:
+        lines += ["", "## Likelihood: a session opened with return_nll=True beside one without, step by step (--nll)", "",
+                  "| B | leg | wall ms, median | wall ms, p90 | GPU ms, median (events) | GPU ms, p90 |", "|---|---|---|---|---|---|"]
+        for B, leg, med, p90, gmed, gp90 in nll:
+            lines.append("| %d | %s | %.3f | %.3f | %.3f | %.3f |" % (B, leg, med, p90, gmed, gp90))
     text = "\n".join(lines) + "\n"
     print(text)
     if a.out:
@@ -227,6 +241,58 @@ def churn_leg(m, dev, B, rs, steps, warmup, dims, start, C, migrate=False):
         for leg, (wall, gpu) in legs.items():
             wall.sort()
             out.append((r, caller, leg, statistics.median(wall), wall[int(0.9 * (len(wall) - 1))], statistics.median(gpu)))
+    return out
+
+
+def nll_leg(m, dev, batches, steps, warmup, dims, start, C, nframes=0):
+    """Per batch size: (B, leg, wall median, wall p90, GPU median, GPU p90) of a step without and with return_nll, two sessions
+    interleaved step by step (which of the two goes first alternates), then of inference() over nframes generated frames likewise."""
+    import torch
+    out = []
+    total = warmup + steps
+    for B in batches:
+        gd = torch.Generator().manual_seed(B + 2)
+        data = {k: torch.randn(B, start + total, d, generator=gd).to(dev) for k, d in dims.items()}
+        seed = {k: v[:, :start].contiguous() for k, v in data.items()}
+        frames = [{k: v[:, start + n].contiguous() for k, v in data.items() if k != "p1_face"} for n in range(total)]
+        noise = (torch.randn(total, B, C, generator=gd) * 0.8).to(dev)
+        legs = {"step": ([], []), "step, return_nll": ([], [])}
+
+        def timed(fn, wall, gpu, keep):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            t1 = time.perf_counter()
+            if keep:
+                wall.append((t1 - t0) * 1e3)
+                gpu.append(e0.elapsed_time(e1))
+
+        with m.open_stream(seed) as off, m.open_stream(seed, return_nll=True) as on:
+            sessions = {"step": off, "step, return_nll": on}
+            for n in range(total):
+                for leg in (list(legs) if n % 2 == 0 else list(legs)[::-1]):
+                    timed(lambda: sessions[leg].step(frames[n], noise[n]), *legs[leg], n >= warmup)
+        if nframes > 0:
+            t = start + nframes
+            pd = {k: (v[:, :start].contiguous() if k == "p1_face" else torch.randn(B, t, dims[k], generator=gd).to(dev))
+                  for k, v in data.items()}
+            pn = (torch.randn(nframes, B, C, generator=gd) * 0.8).to(dev)
+            calls = {"inference, %d frames" % nframes: False, "inference, %d frames, return_nll" % nframes: True}
+            for leg in calls:
+                legs[leg] = ([], [])
+            for i in range(12):          # (a flip of the flag recaptures: each leg's graphs are made on its second call in a row)
+                for leg, flag in (list(calls.items()) if i % 2 == 0 else list(calls.items())[::-1]):
+                    for j in range(3):
+                        timed(lambda: m.inference(t, pd, noise=pn, return_nll=flag), *legs[leg], i >= 2 and j == 2)
+        for leg, (wall, gpu) in legs.items():
+            wall.sort()
+            gpu.sort()
+            out.append((B, leg, statistics.median(wall), wall[int(0.9 * (len(wall) - 1))], statistics.median(gpu),
+                        gpu[int(0.9 * (len(gpu) - 1))]))
     return out
 
 
