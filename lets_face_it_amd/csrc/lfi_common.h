@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "lfi.h"
 
@@ -30,6 +31,17 @@ extern unsigned long long* g_lfi_stamps;  // diagnostics only (lfi_debug_set_sta
   } while (0)
 
 static inline int lfi_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Boolean switches (environment variables), read at every call: tests and A/B runs flip them inside one process.
+// lfi_env_on: on by default, a value starting with '0' switches it off; lfi_env_set: off by default, a value starting with '1' switches it on.
+static inline bool lfi_env_on(const char* name) {
+  const char* e = getenv(name);
+  return !(e && e[0] == '0');
+}
+static inline bool lfi_env_set(const char* name) {
+  const char* e = getenv(name);
+  return e && e[0] == '1';
+}
 
 // ---- internal (not part of the C ABI): the sampler's fused per-frame conditioning (lfi_sample.hip), called by lfi_flow.hip
 extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond_ok(int D, int G, int K1);

@@ -2380,19 +2380,12 @@ int ew_blocks(long total) { return (int)(lfi_cdiv(total, 256) < 4096 ? lfi_cdiv(
 
 }  // namespace
 
-static bool enc_wide_enabled() {
-  static int wide = -1;
-  if (wide < 0) {
-    const char* e = getenv("LFI_ENC_WIDE");
-    wide = (e && e[0] == '0') ? 0 : 1;
-  }
-  return wide != 0;
-}
-static bool enc_m16_enabled() {   // the forward 64-window kernel on v_mfma_f32_16x16x32_bf16 (read at every call: tests compare)
-  const char* e = getenv("LFI_ENC_M16");
-  return !(e && e[0] == '0');
-}
-// the forward kernel with the gate epilogue under the matrix phase (read at every call: tests compare): LFI_ENC_T16 = 0 never,
+// ---- switches: all read at every call (tests and A/B runs flip them inside one process)
+static bool enc_wide_enabled() { return lfi_env_on("LFI_ENC_WIDE"); }           // the row-layout forward kernels (0: the accumulator-layout kernel)
+static bool enc_wide_bwd_enabled() { return lfi_env_on("LFI_ENC_WIDE_BWD"); }   // the row-layout backward kernels (0: the exact-f32 accumulator-layout kernel)
+static bool enc_m16_enabled() { return lfi_env_on("LFI_ENC_M16"); }             // the forward 64-window kernel on v_mfma_f32_16x16x32_bf16
+static bool enc_r64_enabled() { return lfi_env_on("LFI_ENC_R64"); }             // the two-row-tile kernels, forward and backward
+// the forward kernel with the gate epilogue under the matrix phase: LFI_ENC_T16 = 0 never,
 // 1 (default) where no stash is written (inference, validation, the sampler's static part: 0.46 against 0.51 ms on the p2_face
 // shape), 2 with a stash too (training: measured SLOWER there, 0.545 against 0.532 ms alone and +0.15 ms on the whole step - the
 // stash stores share the wave's in-order vmcnt queue with the weight stream)
@@ -2400,24 +2393,17 @@ static int enc_t16_mode() {
   const char* e = getenv("LFI_ENC_T16");
   return e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 1;
 }
-static bool enc_r64_enabled() {   // (read at every call: tests switch it inside one process)
-  const char* e = getenv("LFI_ENC_R64");
-  return !(e && e[0] == '0');
-}
-static size_t enc_bwd_r64_lds(const EncFused& q) {
-  const int R2 = 2 * q.R;
-  const long imgf = (long)R2 * (q.Kp + 8);
-  return (size_t)2 * R2 * (q.Kp + 8) * sizeof(__bf16) +
-         (size_t)(ENC_NW * 2 * 32 * ENC_TP > imgf ? ENC_NW * 2 * 32 * ENC_TP : imgf) * sizeof(float) + (size_t)2 * R2 * sizeof(unsigned);
-}
-static bool enc_wide_bwd_shape_ok(const lfi_enc_desc* d, int lddcond, EncFused* q);
-// does lfi_encode_windows_bwd run the two-row-tile kernel (enc_gru_bwd_r64_kernel) for this shape? (shape-only: the pointer
-// alignment the row-layout kernels need is REQUIREd there)
-static bool enc_bwd_uses_r64(const lfi_enc_desc* d, EncFused* q) {
-  if (!enc_r64_enabled() || !enc_wide_bwd_shape_ok(d, d->ldcond, q)) return false;
-  return enc_bwd_r64_lds(*q) <= 160 * 1024 && lfi_cdiv((long)d->N * d->B, 2 * q->R) >= 128;
-}
 
+// ---- dynamic LDS of each fused kernel, in bytes: one formula per kernel
+// accumulator-layout forward: state images (+ the bf16 hi / lo pair in bf16x3 mode) + per-row offset tables
+static size_t enc_fwd_fused_lds(const EncFused& q, bool x3) {
+  return (size_t)q.Kp * (q.R + 1) * sizeof(float) + (x3 ? (size_t)2 * q.R * (q.Kp + 8) * sizeof(__bf16) : 0) + (size_t)3 * q.R * sizeof(unsigned);
+}
+// row-layout forward, 32 windows per wave: image pair + transpose tiles + biases + offset tables (+ the mask rows)
+static size_t enc_fwd_wide_lds(const EncFused& q, int hist, bool masked) {
+  return (size_t)2 * q.R * (q.Kp + 8) * sizeof(__bf16) + (size_t)ENC_NW * 32 * ENC_TP * sizeof(float) + (size_t)6 * q.Jp * sizeof(float) +
+         (size_t)2 * q.R * sizeof(unsigned) + (masked ? (size_t)q.R * hist * sizeof(float) : 0);
+}
 static size_t enc_fwd_r64_lds(const EncFused& q, int hist, bool masked) {
   const int R2 = 2 * q.R;
   return (size_t)2 * R2 * (q.Kp + 8) * sizeof(__bf16) + (size_t)ENC_NW * 2 * 32 * ENC_TP * sizeof(float) +
@@ -2427,29 +2413,157 @@ static size_t enc_fwd_t16_lds(int hist, bool masked) {
   return (size_t)4 * 64 * 264 * sizeof(__bf16) + (size_t)6 * 256 * sizeof(float) + (size_t)2 * 64 * sizeof(unsigned) +
          (masked ? (size_t)64 * hist * sizeof(float) : 0);
 }
-// which forward kernel a descriptor takes (lfi_encode_windows_fwd_variant's numbering); fills q for the fused ones
-static int enc_fwd_variant(const lfi_enc_desc* d, bool masked, bool stashed, bool aligned, EncFused* q) {
-  if (d->lstm || !enc_fused_shape(d->hid, q)) return 0;
-  const int hid = d->hid;
+// accumulator-layout backward: state image + per-row offset / liveness tables
+static size_t enc_bwd_fused_lds(const EncFused& q) { return (size_t)q.Kp * (q.R + 1) * sizeof(float) + (size_t)2 * q.R * sizeof(unsigned); }
+// row-layout backward: image pair + the larger of the transpose tiles and one more image pair (in floats) + tables
+static size_t enc_bwd_wide_lds(const EncFused& q) {
+  const long imgf = (long)q.R * (q.Kp + 8);
+  return (size_t)2 * q.R * (q.Kp + 8) * sizeof(__bf16) + (size_t)(ENC_NW * 32 * ENC_TP > imgf ? ENC_NW * 32 * ENC_TP : imgf) * sizeof(float) +
+         (size_t)2 * q.R * sizeof(unsigned);
+}
+static size_t enc_bwd_r64_lds(const EncFused& q) {
+  const int R2 = 2 * q.R;
+  const long imgf = (long)R2 * (q.Kp + 8);
+  return (size_t)2 * R2 * (q.Kp + 8) * sizeof(__bf16) +
+         (size_t)(ENC_NW * 2 * 32 * ENC_TP > imgf ? ENC_NW * 2 * 32 * ENC_TP : imgf) * sizeof(float) + (size_t)2 * R2 * sizeof(unsigned);
+}
+
+// ---- which instantiation: the fused kernels all have one signature
+typedef void (*EncKernel)(EncArgs, EncFused);
+template <bool ST, bool MK>
+static EncKernel enc_fwd_fused_kernel_of(bool x3) { return x3 ? enc_gru_fwd_fused_kernel<ST, MK, true> : enc_gru_fwd_fused_kernel<ST, MK, false>; }
+static EncKernel enc_fwd_fused_pick(bool stash, bool mask, bool x3) {
+  if (stash) return mask ? enc_fwd_fused_kernel_of<true, true>(x3) : enc_fwd_fused_kernel_of<true, false>(x3);
+  return mask ? enc_fwd_fused_kernel_of<false, true>(x3) : enc_fwd_fused_kernel_of<false, false>(x3);
+}
+template <bool ST, bool MK, bool H>
+static EncKernel enc_fwd_row_kernel_of(int variant) {   // the row-layout forward kernels: variants 2 - 5
+  switch (variant) {
+    case 5: return enc_gru_fwd_t16_kernel<ST, MK, H>;
+    case 4: return enc_gru_fwd_r64_kernel<ST, MK, H, true>;
+    case 3: return enc_gru_fwd_r64_kernel<ST, MK, H>;
+    default: return enc_gru_fwd_wide_kernel<ST, MK, H>;
+  }
+}
+static EncKernel enc_fwd_row_pick(int variant, bool stash, bool mask, bool f16) {   // (f16: the form of the stash, so only with one)
+  if (stash && f16) return mask ? enc_fwd_row_kernel_of<true, true, true>(variant) : enc_fwd_row_kernel_of<true, false, true>(variant);
+  if (stash) return mask ? enc_fwd_row_kernel_of<true, true, false>(variant) : enc_fwd_row_kernel_of<true, false, false>(variant);
+  return mask ? enc_fwd_row_kernel_of<false, true, false>(variant) : enc_fwd_row_kernel_of<false, false, false>(variant);
+}
+template <bool A2, bool H>
+static EncKernel enc_bwd_row_kernel_of(bool r64) { return r64 ? enc_gru_bwd_r64_kernel<A2, H> : enc_gru_bwd_wide_kernel<A2, H>; }
+static EncKernel enc_bwd_row_pick(bool r64, bool a2, bool f16) {
+  if (a2) return f16 ? enc_bwd_row_kernel_of<true, true>(r64) : enc_bwd_row_kernel_of<true, false>(r64);
+  return f16 ? enc_bwd_row_kernel_of<false, true>(r64) : enc_bwd_row_kernel_of<false, false>(r64);
+}
+
+// ---- the recurrent weights as the fused kernels read them, into `work`
+enum EncWeights { ENC_W_PAD, ENC_W_FRAG, ENC_W_FRAG16 };   // zero-padded f32 | bf16 hi / lo fragments | the same in 16 x 16 x 32 order (forward only)
+static void enc_build_weights(EncWeights w, EncFused* q, const float* whh, int hid, int fwd, float* work, hipStream_t st) {
+  if (w == ENC_W_FRAG16) hipLaunchKernelGGL(enc_frag_weights16_kernel, dim3(lfi_cdiv(6L * q->Kp * q->Jp, 256)), dim3(256), 0, st, whh, hid, q->Kp,
+                                            q->Jp, reinterpret_cast<__bf16*>(work));
+  else if (w == ENC_W_FRAG) hipLaunchKernelGGL(enc_frag_weights_kernel, dim3(lfi_cdiv(6L * q->Kp * q->Jp, 256)), dim3(256), 0, st, whh, hid, q->Kp,
+                                               q->Jp, fwd, reinterpret_cast<__bf16*>(work));
+  else hipLaunchKernelGGL(enc_pad_weights_kernel, dim3(lfi_cdiv(3L * q->Kp * q->Jp, 256)), dim3(256), 0, st, whh, hid, q->Kp, q->Jp, fwd, work);
+  q->wpad = work;
+  q->wfrag = reinterpret_cast<const uint4*>(work);
+}
+
+// ---- plans: which kernel a descriptor takes, and everything sized by that choice. The size queries and the launchers both ask here.
+// `aligned`: are the buffers the row-layout kernels touch 16-byte aligned? (the queries, which see no pointers, pass true; the
+// launchers REQUIRE what the queries promised)
+struct EncFwdPlan {
+  int variant;       // lfi_encode_windows_fwd_variant's numbering: 0 unfused (hid > 256) or LSTM, 1 accumulator-layout fused, 2 row-layout
+                     // (32 windows per wave), 3 two row tiles per wave, 4 the same on 16 x 16 x 32 MFMAs, 5 epilogue under the matrix phase
+  EncFused q;
+  EncWeights weights;
+  EncKernel kernel;
+  size_t lds;
+  int grid;
+  bool wide_fits;    // the 32-window row-layout kernel takes this shape: the forward half of "may the gate stash be fp16"
+};
+static EncFwdPlan enc_plan_fwd(const lfi_enc_desc* d, bool masked, bool stashed, bool aligned) {
+  EncFwdPlan p = {};
+  if (d->lstm || !enc_fused_shape(d->hid, &p.q)) return p;
+  const EncFused& q = p.q;
   const long F = (long)d->N * d->B;
-  const bool vec_ok = d->precision == 1 && hid % 4 == 0 && d->ldcond % 4 == 0 && d->col % 4 == 0 && aligned;
-  const int R2 = 2 * q->R;
-  const bool take64 = enc_wide_enabled() && enc_r64_enabled() && vec_ok && enc_fwd_r64_lds(*q, d->hist, masked) <= 160 * 1024 &&
-                      lfi_cdiv(F, R2) >= 128;
-  const bool m16 = take64 && q->Kp == 256 && q->ncg * 64 == q->Jp && enc_m16_enabled();
-  if (m16 && hid == 256 && R2 == 64 && enc_fwd_t16_lds(d->hist, masked) <= 160 * 1024 && enc_t16_mode() >= (stashed ? 2 : 1)) return 5;
-  if (m16) return 4;
-  if (take64) return 3;
-  const size_t ldsw = (size_t)2 * q->R * (q->Kp + 8) * sizeof(__bf16) + (size_t)ENC_NW * 32 * ENC_TP * sizeof(float) +
-                      (size_t)6 * q->Jp * sizeof(float) + (size_t)2 * q->R * sizeof(unsigned) +
-                      (masked ? (size_t)q->R * d->hist * sizeof(float) : 0);
-  if (enc_wide_enabled() && vec_ok && ldsw <= 80 * 1024) return 2;
-  return 1;
+  const int R2 = 2 * q.R;
+  const bool x3 = d->precision == 1;
+  // row-layout epilogue (16-byte accesses): needs 4-float granular rows everywhere it vectorises
+  const bool wide = enc_wide_enabled() && x3 && d->hid % 4 == 0 && d->ldcond % 4 == 0 && d->col % 4 == 0 && aligned;
+  p.wide_fits = wide && enc_fwd_wide_lds(q, d->hist, masked) <= 80 * 1024;
+  // two row tiles per wave, one workgroup per CU: half the L2 -> CU weight stream per window; taken when its workgroups still cover
+  // the chip (LFI_ENC_R64=0 keeps the 32-window kernel)
+  const bool take64 = wide && enc_r64_enabled() && enc_fwd_r64_lds(q, d->hist, masked) <= 160 * 1024 && lfi_cdiv(F, R2) >= 128;
+  const bool m16 = take64 && q.Kp == 256 && q.ncg * 64 == q.Jp && enc_m16_enabled();
+  const bool t16 = m16 && d->hid == 256 && R2 == 64 && enc_fwd_t16_lds(d->hist, masked) <= 160 * 1024 && enc_t16_mode() >= (stashed ? 2 : 1);
+  p.variant = t16 ? 5 : m16 ? 4 : take64 ? 3 : p.wide_fits ? 2 : 1;
+  // (the 64-window kernels on the 16 x 16 x 32 shape want their own fragment order)
+  p.weights = !x3 ? ENC_W_PAD : (p.variant >= 4 ? ENC_W_FRAG16 : ENC_W_FRAG);
+  p.lds = p.variant == 5 ? enc_fwd_t16_lds(d->hist, masked)
+        : p.variant >= 3 ? enc_fwd_r64_lds(q, d->hist, masked)
+        : p.variant == 2 ? enc_fwd_wide_lds(q, d->hist, masked) : enc_fwd_fused_lds(q, x3);
+  p.grid = lfi_cdiv(F, p.variant >= 3 ? R2 : q.R);
+  p.kernel = p.variant >= 2 ? enc_fwd_row_pick(p.variant, stashed, masked, stashed && d->stash_f16) : enc_fwd_fused_pick(stashed, masked, x3);
+  return p;
 }
+
+struct EncBwdPlan {
+  int variant;         // 0 unfused (hid > 256) or LSTM, 1 accumulator-layout fused (exact f32, whatever the engine's GEMM mode),
+                       // 2 row-layout (bf16x3 recurrence), 3 row-layout with two row tiles per wave
+  EncFused q;
+  EncWeights weights;
+  EncKernel kernel;
+  size_t lds;
+  int grid;
+  int rows_per_wg;     // windows per workgroup: bias_part holds one row per (workgroup, row group)
+  bool grads_bf16;     // dgi / dgh are left as bf16 arrays (same shapes, half the bytes): the row-layout kernels in two-product mode. Its
+                       // consumers - the dW_hh product (A operand rounded to bf16) and the window scatter - then read bf16
+  bool stash_f16_ok;   // a row-layout kernel takes the shape: the backward half of "may the gate stash be fp16"
+};
+// lddcond: the leading dimension of the d(cond) that is passed in (the queries know d->ldcond only and pass that)
+static EncBwdPlan enc_plan_bwd(const lfi_enc_desc* d, int lddcond, bool aligned) {
+  EncBwdPlan p = {};
+  if (d->lstm || !enc_fused_shape(d->hid, &p.q)) return p;
+  const EncFused& q = p.q;
+  const long F = (long)d->N * d->B;
+  // the row-layout kernels (16-byte accesses), but for the leading dimension of d(cond)
+  const bool rows_ok = d->precision == 1 && enc_wide_bwd_enabled() && d->hid % 4 == 0 && d->col % 4 == 0 && enc_bwd_wide_lds(q) <= 80 * 1024;
+  const bool own_ld = lddcond == d->ldcond;
+  p.stash_f16_ok = rows_ok && d->ldcond % 4 == 0;
+  p.grads_bf16 = d->bwd_two_products && own_ld && p.stash_f16_ok;
+  // bf16x3 recurrence: the row-layout kernels only. What they do not take (LFI_ENC_WIDE_BWD=0, hid not a multiple of 4, unaligned
+  // buffers) runs the exact-f32 accumulator-layout kernel, whatever the engine's GEMM mode (see enc_gru_bwd_fused_kernel)
+  const bool wide = rows_ok && lddcond % 4 == 0 && aligned;
+  // two row tiles per wave, one workgroup per CU: when its workgroups still cover the chip
+  const bool r64 = wide && own_ld && enc_r64_enabled() && enc_bwd_r64_lds(q) <= 160 * 1024 && lfi_cdiv(F, 2 * q.R) >= 128;
+  p.variant = r64 ? 3 : wide ? 2 : 1;
+  p.weights = wide ? ENC_W_FRAG : ENC_W_PAD;
+  p.rows_per_wg = r64 ? 2 * q.R : q.R;
+  p.lds = r64 ? enc_bwd_r64_lds(q) : wide ? enc_bwd_wide_lds(q) : enc_bwd_fused_lds(q);
+  p.grid = lfi_cdiv(F, p.rows_per_wg);
+  p.kernel = wide ? enc_bwd_row_pick(r64, p.grads_bf16, d->stash_f16 != 0) : enc_gru_bwd_fused_kernel;
+  return p;
+}
+
 extern "C" int lfi_encode_windows_fwd_variant(const lfi_enc_desc* d, int masked, int stashed) {
-  EncFused q = {};
-  return d ? enc_fwd_variant(d, masked != 0, stashed != 0, true, &q) : 0;
+  return d ? enc_plan_fwd(d, masked != 0, stashed != 0, true).variant : 0;
 }
+// rows of the bias_part buffer lfi_encode_windows_bwd fills (0: the unfused paths leave none)
+extern "C" long lfi_encode_windows_bias_rows(const lfi_enc_desc* d) {
+  if (!d) return 0;
+  const EncBwdPlan p = enc_plan_bwd(d, d->ldcond, true);
+  return p.variant ? (long)p.grid * (ENC_NW / p.q.ncg) : 0;
+}
+// Does lfi_encode_windows_bwd leave dgi / dgh as bf16 arrays? (lfi_gemm_desc.a_bf16; lfi_encode_windows_scatter looks the same answer up itself)
+extern "C" int lfi_encode_windows_grad_stash_bf16(const lfi_enc_desc* d) { return (d && enc_plan_bwd(d, d->ldcond, true).grads_bf16) ? 1 : 0; }
+// May the gate stash between lfi_encode_windows_fwd and _bwd be fp16 ([hist][F][hid][4] halves instead of [hist][F][4][hid] floats)?
+// Only the row-layout fused GRU kernels read / write that form (asked for the masked forward kernel, the larger of the two).
+extern "C" int lfi_encode_windows_stash_f16_ok(const lfi_enc_desc* d) {
+  return (d && enc_plan_fwd(d, true, true, true).wide_fits && enc_plan_bwd(d, d->ldcond, true).stash_f16_ok) ? 1 : 0;
+}
+// Is dgi left compact ([hist][F][3 hid], with dgh beside it) for lfi_encode_windows_scatter? The fused backward kernels all do.
+extern "C" int lfi_encode_windows_compact_dgi(const lfi_enc_desc* d) { return (d && enc_plan_bwd(d, d->ldcond, true).variant != 0) ? 1 : 0; }
 
 extern "C" long lfi_encode_windows_work_floats(const lfi_enc_desc* d) {
   if (!d) return 0;
@@ -2488,107 +2602,18 @@ extern "C" int lfi_encode_windows_fwd(const lfi_enc_desc* d, const float* Xp, co
     LFI_LAUNCH_CHECK("lfi_encode_windows_fwd (lstm)");
     return LFI_OK;
   }
-  EncFused q = {};
-  if (enc_fused_shape(hid, &q)) {
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  EncFwdPlan p = enc_plan_fwd(d, mask != nullptr, gates != nullptr, al16(Xp) && al16(cond) && (!gates || (al16(gates) && al16(hseq))));
+  if (p.variant) {
     LFI_REQUIRE(!gates || hseq, "lfi_encode_windows_fwd: the gate stash needs the state stash too");
     // (without a gate stash nothing is kept for a backward pass: hseq is not written either)
-    const bool x3 = d->precision == 1;
-    // (decided before the weights are converted: the 64-window kernels on the 16 x 16 x 32 shape want their own fragment order)
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool aligned = al16(Xp) && al16(cond) && (!gates || (al16(gates) && al16(hseq)));
-    const int R2 = 2 * q.R;
-    const int fv = enc_fwd_variant(d, mask != nullptr, gates != nullptr, aligned, &q);
-    const bool take64 = fv >= 3, m16 = fv >= 4, t16 = fv == 5;
-    const size_t lds64 = enc_fwd_r64_lds(q, d->hist, mask != nullptr), ldst = enc_fwd_t16_lds(d->hist, mask != nullptr);
-    if (x3 && m16) hipLaunchKernelGGL(enc_frag_weights16_kernel, dim3(lfi_cdiv(6L * q.Kp * q.Jp, 256)), dim3(256), 0, st, whh, hid, q.Kp,
-                                      q.Jp, reinterpret_cast<__bf16*>(work));
-    else if (x3) hipLaunchKernelGGL(enc_frag_weights_kernel, dim3(lfi_cdiv(6L * q.Kp * q.Jp, 256)), dim3(256), 0, st, whh, hid, q.Kp,
-                                    q.Jp, 1, reinterpret_cast<__bf16*>(work));
-    else hipLaunchKernelGGL(enc_pad_weights_kernel, dim3(lfi_cdiv(3L * q.Kp * q.Jp, 256)), dim3(256), 0, st, whh, hid, q.Kp, q.Jp,
-                            1, work);
-    q.wpad = work;
-    q.wfrag = reinterpret_cast<const uint4*>(work);
-    const size_t lds = (size_t)q.Kp * (q.R + 1) * sizeof(float) + (x3 ? (size_t)2 * q.R * (q.Kp + 8) * sizeof(__bf16) : 0) +
-                       (size_t)3 * q.R * sizeof(unsigned);   // state images + per-row offset tables
-    const dim3 grid(lfi_cdiv(F, q.R));
-    {
-      // row-layout epilogue variant (16-byte accesses): needs 4-float granular rows everywhere it vectorises
-      const size_t ldsw = (size_t)2 * q.R * (q.Kp + 8) * sizeof(__bf16) + (size_t)ENC_NW * 32 * ENC_TP * sizeof(float) +
-                          (size_t)6 * q.Jp * sizeof(float) + (size_t)2 * q.R * sizeof(unsigned) +
-                          (mask ? (size_t)q.R * d->hist * sizeof(float) : 0);
-      // two row tiles per wave, one workgroup per CU (enc_gru_fwd_r64_kernel): half the L2 -> CU weight stream per window; taken
-      // when its workgroups still cover the chip (LFI_ENC_R64=0 keeps the 32-window kernel)
-      if (take64) {
-        const dim3 grid64(lfi_cdiv(F, R2));
-        rc = LFI_OK;
-        switch ((gates && d->stash_f16 ? 4 : 0) | (gates ? 2 : 0) | (mask ? 1 : 0)) {
-#define LFI_ENC_FWD64(ST, MK, H)                                                                                   \
-  if (t16) {                                                                                                       \
-    rc = enc_set_lds(enc_gru_fwd_t16_kernel<ST, MK, H>, ldst);                                                     \
-    if (!rc) hipLaunchKernelGGL((enc_gru_fwd_t16_kernel<ST, MK, H>), grid64, dim3(ENC_NT), ldst, st, a, q);        \
-    break;                                                                                                         \
-  }                                                                                                                \
-  if (m16) {                                                                                                       \
-    rc = enc_set_lds(enc_gru_fwd_r64_kernel<ST, MK, H, true>, lds64);                                              \
-    if (!rc) hipLaunchKernelGGL((enc_gru_fwd_r64_kernel<ST, MK, H, true>), grid64, dim3(ENC_NT), lds64, st, a, q); \
-    break;                                                                                                         \
-  }                                                                                                                \
-  rc = enc_set_lds(enc_gru_fwd_r64_kernel<ST, MK, H>, lds64);                                                      \
-  if (!rc) hipLaunchKernelGGL((enc_gru_fwd_r64_kernel<ST, MK, H>), grid64, dim3(ENC_NT), lds64, st, a, q);        \
-  break
-          case 7: LFI_ENC_FWD64(true, true, true);
-          case 6: LFI_ENC_FWD64(true, false, true);
-          case 3: LFI_ENC_FWD64(true, true, false);
-          case 2: LFI_ENC_FWD64(true, false, false);
-          case 1: LFI_ENC_FWD64(false, true, false);
-          default: LFI_ENC_FWD64(false, false, false);
-#undef LFI_ENC_FWD64
-        }
-        if (rc) return rc;
-        LFI_LAUNCH_CHECK("lfi_encode_windows_fwd (fused, two row tiles per wave)");
-        return LFI_OK;
-      }
-      if (fv == 2) {
-        rc = LFI_OK;
-        switch ((gates && d->stash_f16 ? 4 : 0) | (gates ? 2 : 0) | (mask ? 1 : 0)) {
-#define LFI_ENC_FWDW(ST, MK, H)                                                                                  \
-  rc = enc_set_lds(enc_gru_fwd_wide_kernel<ST, MK, H>, ldsw);                                                    \
-  if (!rc) hipLaunchKernelGGL((enc_gru_fwd_wide_kernel<ST, MK, H>), grid, dim3(ENC_NT), ldsw, st, a, q);        \
-  break
-          case 7: LFI_ENC_FWDW(true, true, true);
-          case 6: LFI_ENC_FWDW(true, false, true);
-          case 3: LFI_ENC_FWDW(true, true, false);
-          case 2: LFI_ENC_FWDW(true, false, false);
-          case 1: LFI_ENC_FWDW(false, true, false);
-          default: LFI_ENC_FWDW(false, false, false);
-#undef LFI_ENC_FWDW
-        }
-        if (rc) return rc;
-        LFI_LAUNCH_CHECK("lfi_encode_windows_fwd (fused, row-layout epilogue)");
-        return LFI_OK;
-      }
-    }
-    LFI_REQUIRE(!(gates && d->stash_f16), "lfi_encode_windows_fwd: an fp16 gate stash (lfi_enc_desc.stash_f16) needs the row-layout "
+    LFI_REQUIRE(p.variant >= 2 || !(gates && d->stash_f16), "lfi_encode_windows_fwd: an fp16 gate stash (lfi_enc_desc.stash_f16) needs the row-layout "
                 "kernel (lfi_encode_windows_stash_f16_ok) and 16-byte aligned buffers");
-    const int variant = (gates ? 4 : 0) | (mask ? 2 : 0) | (x3 ? 1 : 0);
-    rc = LFI_OK;
-    switch (variant) {
-#define LFI_ENC_FWD(ST, MK, X)                                                                                              \
-  rc = enc_set_lds(enc_gru_fwd_fused_kernel<ST, MK, X>, lds);                                                               \
-  if (!rc) hipLaunchKernelGGL((enc_gru_fwd_fused_kernel<ST, MK, X>), grid, dim3(ENC_NT), lds, st, a, q);                    \
-  break
-      case 7: LFI_ENC_FWD(true, true, true);
-      case 6: LFI_ENC_FWD(true, true, false);
-      case 5: LFI_ENC_FWD(true, false, true);
-      case 4: LFI_ENC_FWD(true, false, false);
-      case 3: LFI_ENC_FWD(false, true, true);
-      case 2: LFI_ENC_FWD(false, true, false);
-      case 1: LFI_ENC_FWD(false, false, true);
-      default: LFI_ENC_FWD(false, false, false);
-#undef LFI_ENC_FWD
-    }
-    if (rc) return rc;
-    LFI_LAUNCH_CHECK("lfi_encode_windows_fwd (fused)");
+    enc_build_weights(p.weights, &p.q, whh, hid, 1, work, st);
+    if ((rc = enc_set_lds(p.kernel, p.lds))) return rc;
+    hipLaunchKernelGGL(p.kernel, dim3(p.grid), dim3(ENC_NT), p.lds, st, a, p.q);
+    LFI_LAUNCH_CHECK(p.variant >= 3 ? "lfi_encode_windows_fwd (fused, two row tiles per wave)"
+                     : p.variant == 2 ? "lfi_encode_windows_fwd (fused, row-layout epilogue)" : "lfi_encode_windows_fwd (fused)");
     return LFI_OK;
   }
   LFI_REQUIRE(hseq, "lfi_encode_windows_fwd: hid > 256 needs the state stash hseq");
@@ -2608,13 +2633,6 @@ extern "C" int lfi_encode_windows_fwd(const lfi_enc_desc* d, const float* Xp, co
   return LFI_OK;
 }
 
-extern "C" long lfi_encode_windows_bias_rows(const lfi_enc_desc* d) {
-  EncFused q = {};
-  if (!d || d->lstm || !enc_fused_shape(d->hid, &q)) return 0;
-  const int rows_per_wg = enc_bwd_uses_r64(d, &q) ? 2 * q.R : q.R;
-  return (long)lfi_cdiv((long)d->N * d->B, rows_per_wg) * (ENC_NW / q.ncg);
-}
-
 extern "C" int lfi_encode_windows_bias_grads(const float* bias_part, long rows, int hid, float* db_ih, float* db_hh,
                                              void* stream) {
   LFI_REQUIRE(bias_part && db_ih && db_hh && rows > 0 && hid > 0, "lfi_encode_windows_bias_grads: bad arguments");
@@ -2622,40 +2640,6 @@ extern "C" int lfi_encode_windows_bias_grads(const float* bias_part, long rows, 
                      db_ih, db_hh);
   LFI_LAUNCH_CHECK("lfi_encode_windows_bias_grads");
   return LFI_OK;
-}
-
-// Does lfi_encode_windows_bwd leave dgi / dgh as bf16 arrays (same shapes, half the bytes)? Only the row-layout fused GRU kernel
-// in two-product mode does: its consumers - the dW_hh product (A operand rounded to bf16) and the window scatter - then read
-// bf16 (lfi_gemm_desc.a_bf16; lfi_encode_windows_scatter looks the same answer up itself).
-static bool enc_wide_bwd_shape_ok(const lfi_enc_desc* d, int lddcond, EncFused* q) {
-  if (!d || d->lstm || d->precision != 1 || !enc_fused_shape(d->hid, q)) return false;
-  const char* e = getenv("LFI_ENC_WIDE_BWD");
-  if (e && e[0] == '0') return false;
-  const size_t tab = (size_t)2 * q->R * sizeof(unsigned);
-  const long imgf = (long)q->R * (q->Kp + 8);
-  const size_t ldsw = (size_t)2 * q->R * (q->Kp + 8) * sizeof(__bf16) +
-                      (size_t)(ENC_NW * 32 * ENC_TP > imgf ? ENC_NW * 32 * ENC_TP : imgf) * sizeof(float) + tab;
-  return d->hid % 4 == 0 && lddcond % 4 == 0 && d->col % 4 == 0 && ldsw <= 80 * 1024;
-}
-extern "C" int lfi_encode_windows_grad_stash_bf16(const lfi_enc_desc* d) {
-  EncFused q = {};
-  return (d && d->bwd_two_products && enc_wide_bwd_shape_ok(d, d->ldcond, &q)) ? 1 : 0;
-}
-
-// May the gate stash between lfi_encode_windows_fwd and _bwd be fp16 ([hist][F][hid][4] halves instead of [hist][F][4][hid] floats)?
-// Only the two row-layout fused GRU kernels read / write that form.
-static bool enc_wide_fwd_shape_ok(const lfi_enc_desc* d, EncFused* q, bool mask) {
-  if (!d || d->lstm || d->precision != 1 || !enc_fused_shape(d->hid, q)) return false;
-  const char* e = getenv("LFI_ENC_WIDE");
-  if (e && e[0] == '0') return false;
-  const size_t ldsw = (size_t)2 * q->R * (q->Kp + 8) * sizeof(__bf16) + (size_t)ENC_NW * 32 * ENC_TP * sizeof(float) +
-                      (size_t)6 * q->Jp * sizeof(float) + (size_t)2 * q->R * sizeof(unsigned) +
-                      (mask ? (size_t)q->R * d->hist * sizeof(float) : 0);
-  return d->hid % 4 == 0 && d->ldcond % 4 == 0 && d->col % 4 == 0 && ldsw <= 80 * 1024;
-}
-extern "C" int lfi_encode_windows_stash_f16_ok(const lfi_enc_desc* d) {
-  EncFused q = {};
-  return (enc_wide_fwd_shape_ok(d, &q, true) && enc_wide_bwd_shape_ok(d, d->ldcond, &q)) ? 1 : 0;
 }
 
 extern "C" int lfi_encode_windows_bwd(const lfi_enc_desc* d, const float* dcond, int lddcond, const float* whh,
@@ -2693,69 +2677,16 @@ extern "C" int lfi_encode_windows_bwd(const lfi_enc_desc* d, const float* dcond,
     LFI_LAUNCH_CHECK("lfi_encode_windows_bwd (lstm)");
     return LFI_OK;
   }
-  EncFused q = {};
-  if (enc_fused_shape(hid, &q)) {
-    const size_t tab = (size_t)2 * q.R * sizeof(unsigned);   // per-row offset / liveness tables
-    const size_t ldsf = (size_t)q.Kp * (q.R + 1) * sizeof(float) + tab;
-    static int widebw = -1;
-    if (widebw < 0) {
-      const char* e = getenv("LFI_ENC_WIDE_BWD");
-      widebw = (e && e[0] == '0') ? 0 : 1;
-    }
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const long imgf = (long)q.R * (q.Kp + 8);   // floats of one image pair
-    const size_t ldsw = (size_t)2 * q.R * (q.Kp + 8) * sizeof(__bf16) +
-                        (size_t)(ENC_NW * 32 * ENC_TP > imgf ? ENC_NW * 32 * ENC_TP : imgf) * sizeof(float) + tab;
-    const bool want16 = d->bwd_two_products && lddcond == d->ldcond && lfi_encode_windows_grad_stash_bf16(d);
-    const bool wide_ok = d->precision == 1 && widebw && hid % 4 == 0 && lddcond % 4 == 0 && d->col % 4 == 0 && al16(dcond) && al16(gates) &&
-                         al16(hseq) && al16(dgi) && al16(dgh) && (!bias_part || al16(bias_part)) && ldsw <= 80 * 1024;
-    // bf16x3 recurrence: the row-layout kernels only. What they do not take (LFI_ENC_WIDE_BWD=0, hid not a multiple of 4, unaligned
-    // buffers) runs the exact-f32 accumulator-layout kernel, whatever the engine's GEMM mode (see enc_gru_bwd_fused_kernel)
-    const bool x3 = wide_ok;
-    if (x3) hipLaunchKernelGGL(enc_frag_weights_kernel, dim3(lfi_cdiv(6L * q.Kp * q.Jp, 256)), dim3(256), 0, st, whh, hid, q.Kp,
-                               q.Jp, 0, reinterpret_cast<__bf16*>(work));
-    else hipLaunchKernelGGL(enc_pad_weights_kernel, dim3(lfi_cdiv(3L * q.Kp * q.Jp, 256)), dim3(256), 0, st, whh, hid, q.Kp, q.Jp,
-                            0, work);
-    q.wpad = work;
-    q.wfrag = reinterpret_cast<const uint4*>(work);
-    LFI_REQUIRE(!want16 || wide_ok, "lfi_encode_windows_bwd: lfi_encode_windows_grad_stash_bf16 promised a bf16 gradient stash but the "
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  EncBwdPlan p = enc_plan_bwd(d, lddcond, al16(dcond) && al16(gates) && al16(hseq) && al16(dgi) && al16(dgh) && (!bias_part || al16(bias_part)));
+  if (p.variant) {
+    LFI_REQUIRE(!p.grads_bf16 || p.variant >= 2, "lfi_encode_windows_bwd: lfi_encode_windows_grad_stash_bf16 promised a bf16 gradient stash but the "
                 "buffers are not 16-byte aligned");
-    LFI_REQUIRE(!d->stash_f16 || wide_ok, "lfi_encode_windows_bwd: an fp16 gate stash (lfi_enc_desc.stash_f16) needs the row-layout "
+    LFI_REQUIRE(!d->stash_f16 || p.variant >= 2, "lfi_encode_windows_bwd: an fp16 gate stash (lfi_enc_desc.stash_f16) needs the row-layout "
                 "kernel (lfi_encode_windows_stash_f16_ok) and 16-byte aligned buffers");
-    EncFused q64 = {};
-    if (wide_ok && lddcond == d->ldcond && enc_bwd_uses_r64(d, &q64)) {   // two row tiles per wave, one workgroup per CU
-      const size_t lds64 = enc_bwd_r64_lds(q);
-      const dim3 grid64(lfi_cdiv(F, 2 * q.R));
-      rc = LFI_OK;
-      switch ((want16 ? 2 : 0) | (d->stash_f16 ? 1 : 0)) {
-#define LFI_ENC_BWD64(A2, H)                                                                                   \
-  rc = enc_set_lds(enc_gru_bwd_r64_kernel<A2, H>, lds64);                                                      \
-  if (!rc) hipLaunchKernelGGL((enc_gru_bwd_r64_kernel<A2, H>), grid64, dim3(ENC_NT), lds64, st, a, q);        \
-  break
-        case 3: LFI_ENC_BWD64(true, true);
-        case 2: LFI_ENC_BWD64(true, false);
-        case 1: LFI_ENC_BWD64(false, true);
-        default: LFI_ENC_BWD64(false, false);
-#undef LFI_ENC_BWD64
-      }
-      if (rc) return rc;
-    } else if (wide_ok) {
-      rc = LFI_OK;
-      switch ((want16 ? 2 : 0) | (d->stash_f16 ? 1 : 0)) {
-#define LFI_ENC_BWDW(A2, H)                                                                                             \
-  rc = enc_set_lds(enc_gru_bwd_wide_kernel<A2, H>, ldsw);                                                               \
-  if (!rc) hipLaunchKernelGGL((enc_gru_bwd_wide_kernel<A2, H>), dim3(lfi_cdiv(F, q.R)), dim3(ENC_NT), ldsw, st, a, q);  \
-  break
-        case 3: LFI_ENC_BWDW(true, true);
-        case 2: LFI_ENC_BWDW(true, false);
-        case 1: LFI_ENC_BWDW(false, true);
-        default: LFI_ENC_BWDW(false, false);
-#undef LFI_ENC_BWDW
-      }
-      if (rc) return rc;
-    } else {
-      hipLaunchKernelGGL(enc_gru_bwd_fused_kernel, dim3(lfi_cdiv(F, q.R)), dim3(ENC_NT), ldsf, st, a, q);
-    }
+    enc_build_weights(p.weights, &p.q, whh, hid, 0, work, st);
+    if ((rc = enc_set_lds(p.kernel, p.lds))) return rc;
+    hipLaunchKernelGGL(p.kernel, dim3(p.grid), dim3(ENC_NT), p.lds, st, a, p.q);
     LFI_LAUNCH_CHECK("lfi_encode_windows_bwd (fused)");
     return LFI_OK;
   }
@@ -2779,10 +2710,6 @@ extern "C" int lfi_encode_windows_bwd(const lfi_enc_desc* d, const float* dcond,
   return LFI_OK;
 }
 
-extern "C" int lfi_encode_windows_compact_dgi(const lfi_enc_desc* d) {
-  EncFused q = {};
-  return (d && !d->lstm && enc_fused_shape(d->hid, &q)) ? 1 : 0;
-}
 
 extern "C" int lfi_encode_windows_scatter(const lfi_enc_desc* d, const float* dgi, const float* dgh, const float* mask, float* dXp,
                                           void* stream) {
@@ -2795,10 +2722,9 @@ extern "C" int lfi_encode_windows_scatter(const lfi_enc_desc* d, const float* dg
   a.dgi = (float*)dgi; a.dgh = (float*)dgh; a.mask = mask;
   a.g16 = lfi_encode_windows_grad_stash_bf16(d);
   // bf16 compact stash (the training step's): 16-byte loads, several frame rows per workgroup (LFI_ENC_SCATTER16=0: the kernel above)
-  const char* ev = getenv("LFI_ENC_SCATTER16");
   const int cpr = 3 * d->hid / 8;
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (!(ev && ev[0] == '0') && a.g16 && a.compact && d->hid % 8 == 0 && cpr <= 256 && al16(dgi) && al16(dgh) && al16(dXp)) {
+  if (lfi_env_on("LFI_ENC_SCATTER16") && a.g16 && a.compact && d->hid % 8 == 0 && cpr <= 256 && al16(dgi) && al16(dgh) && al16(dXp)) {
     const int rows = d->B * d->T, rpw = 256 / cpr;
     hipLaunchKernelGGL(enc_scatter16_kernel, dim3(lfi_cdiv(rows, rpw)), dim3(256), 0, (hipStream_t)stream, a, dXp, rows, cpr, rpw);
   } else

@@ -3444,39 +3444,21 @@ void bind_bstash(FlowK* f, float* b) {
 }
 
 // LFI_FLOW_GENERIC=1 keeps the streaming cell kernels (tests cover both paths at sizes where either applies)
-bool flow_force_generic() {
-  const char* e = getenv("LFI_FLOW_GENERIC");
-  return e && e[0] == '1';
-}
+bool flow_force_generic() { return lfi_env_set("LFI_FLOW_GENERIC"); }
 
 // LFI_FLOW_PIPE=0 keeps one launch per anti-diagonal instead of the persistent pipeline (tests cover both)
-bool flow_pipe_enabled() {
-  const char* e = getenv("LFI_FLOW_PIPE");
-  return !(e && e[0] == '0');
-}
+bool flow_pipe_enabled() { return lfi_env_on("LFI_FLOW_PIPE"); }
 // LFI_PIPE_FENCE=1: consumers of a hand-off run an agent-scope acquire and read the tile with plain loads, instead of the
 // fence-free form (every store and load of the tile sc1; MI355X_MICROARCH.md, hand-offs measured without the acquire, row 1)
 // LFI_PIPE_X3=0: keep the exact f32 MFMA for the recurrent products of the persistent walk in bf16x3 mode too
-bool flow_pipe_x3_enabled() {
-  const char* e = getenv("LFI_PIPE_X3");
-  return !(e && e[0] == '0');
-}
+bool flow_pipe_x3_enabled() { return lfi_env_on("LFI_PIPE_X3"); }
 // shapes for which lfi_flow_prep leaves the reverse cell's fp16 fragment images (whole 32-k blocks everywhere: the X3 reverse cell's condition)
 bool flow_x3h_images_ok(const FlowK& f) { return !f.lstm && f.H16 % 32 == 0 && f.Ch16 % 32 == 0 && f.C16 % 32 == 0; }
 // LFI_SAMPLE_WFRAG16=0: the sampler's reverse cells load the f32 images and split them in registers, as before round 5
-bool flow_sample_wfrag16_enabled() {
-  const char* e = getenv("LFI_SAMPLE_WFRAG16");
-  return !(e && e[0] == '0');
-}
+bool flow_sample_wfrag16_enabled() { return lfi_env_on("LFI_SAMPLE_WFRAG16"); }
 // LFI_PIPE_FORCE_ABORT=1 (tests): start the walk with the abort word already set, as if a spin had timed out
-bool flow_pipe_force_abort() {
-  const char* e = getenv("LFI_PIPE_FORCE_ABORT");
-  return e && e[0] == '1';
-}
-int flow_pipe_fence() {
-  const char* e = getenv("LFI_PIPE_FENCE");
-  return (e && e[0] == '1') ? 1 : 0;
-}
+bool flow_pipe_force_abort() { return lfi_env_set("LFI_PIPE_FORCE_ABORT"); }
+int flow_pipe_fence() { return lfi_env_set("LFI_PIPE_FENCE") ? 1 : 0; }
 
 template <typename Kf>
 int set_flow_lds(Kf kernel, size_t bytes, const char* who) {
@@ -3494,6 +3476,79 @@ int set_flow_lds(Kf kernel, size_t bytes, const char* who) {
   return LFI_OK;
 }
 
+// ---- bf16x3 / fp16x3 recurrent products: who takes them. One predicate per consumer; all want bf16x3 GEMM mode (gemm_precision bit 0)
+// and GRU cells. The tails differ on purpose, with what each kernel contracts over (a contraction runs in whole 32-k blocks).
+bool flow_x3_base(const lfi_flow_dims* d) { return (d->gemm_precision & 1) && !d->lstm; }
+// lfi_flow_prep's bf16 hi / lo fragment images of bwh / bwz (flow_prep_x3_kernel), the backward walk's weights: k runs over the hidden
+// units of a gate in both (Ch16 is a column count there). No switch and no size floor: the images are made for every shape that
+// flow_x3_bwd_walk can take, whatever the switches say when the walk runs.
+bool flow_x3_prep_images(const lfi_flow_dims* d, const FlowK& f) { return flow_x3_base(d) && f.H16 % 32 == 0; }
+// forward walk: its products contract over h (H16) and over z1 (Ch16): both 16-k paddings must be whole 32-k blocks
+bool flow_x3_fwd_walk(const lfi_flow_dims* d, const FlowK& f) {
+  return flow_x3_base(d) && f.H16 % 32 == 0 && f.Ch16 % 32 == 0 && flow_pipe_x3_enabled();
+}
+// backward walk: contracts over the hidden units only (the images above: no Ch16 term), and its bf16 operand images, 64 (NG H16 + 8)
+// bytes each, must fit the fp32 regions they replace (NG * H16 >= 128)
+bool flow_x3_bwd_walk(const lfi_flow_dims* d, const FlowK& f) {
+  return flow_x3_base(d) && f.H16 % 32 == 0 && f.NG * f.H16 >= 128 && flow_pipe_x3_enabled();
+}
+// backward planes: the walk above leaves its d(gate) images as the stash's operand planes, so the gate columns must be the stash's
+// own: H itself, not its padding H16, a multiple of 32 (no padding columns), which makes 3 * H the walk's NG * H16
+bool flow_x3_bwd_planes(const lfi_flow_dims* d) {
+  return flow_x3_base(d) && d->H % 32 == 0 && 3 * d->H >= 128 && flow_pipe_x3_enabled();
+}
+// reverse cell (the samplers' chain; three fp16 products - fp32-grade - in both bf16 modes of the per-frame GEMMs): it contracts over
+// z1, h and, for the inverse 1x1 convolution, the channels, so C16 joins the 32-k conditions - the shapes of flow_x3h_images_ok
+bool flow_x3_rev_cell(const lfi_flow_dims* d, const FlowK& f) {
+  return (d->gemm_precision & 1) && flow_x3h_images_ok(f) && flow_pipe_x3_enabled();
+}
+
+// ---- which instantiation runs: one picker per kernel family; set_flow_lds and the launch take the pointer
+typedef void (*FlowDiagKernel)(FlowK, int, int);
+typedef void (*FlowPipeKernel)(FlowK);
+typedef void (*FlowStepKernel)(FlowK, CellIO);
+typedef void (*FlowRevWalkKernel)(FlowK, RevWalk);
+typedef void (*FlowRevChainKernel)(FlowK, RevChain);
+
+FlowDiagKernel flow_diag_fwd_pick(bool fast, bool lstm) {
+  if (!fast) return flow_diag_fwd_kernel;
+  return lstm ? flow_diag_fwd_fast_kernel<4> : flow_diag_fwd_fast_kernel<3>;
+}
+FlowDiagKernel flow_diag_bwd_pick(bool fast, bool lstm) {
+  if (!fast) return flow_diag_bwd_kernel;
+  return lstm ? flow_diag_bwd_fast_kernel<4> : flow_diag_bwd_fast_kernel<3>;
+}
+FlowPipeKernel flow_pipe_fwd_pick(bool lstm, bool x3) {
+  if (lstm) return flow_pipe_fwd_kernel<4, false>;
+  return x3 ? flow_pipe_fwd_kernel<3, true> : flow_pipe_fwd_kernel<3, false>;
+}
+FlowPipeKernel flow_pipe_bwd_pick(bool lstm, bool x3) {
+  if (lstm) return flow_pipe_bwd_kernel<4, false>;
+  return x3 ? flow_pipe_bwd_kernel<3, true> : flow_pipe_bwd_kernel<3, false>;
+}
+FlowStepKernel flow_step_rev_pick(bool fast, bool lstm) {
+  if (!fast) return flow_step_kernel<true>;
+  return lstm ? flow_step_rev_fast_kernel<4> : flow_step_rev_fast_kernel<3>;
+}
+FlowRevWalkKernel flow_rev_walk_pick(bool lstm) { return lstm ? flow_rev_walk_kernel<4> : flow_rev_walk_kernel<3>; }
+template <bool NLL>
+FlowRevChainKernel flow_rev_chain_pick_(bool lstm, bool x3, bool xw) {
+  if (lstm) return flow_rev_chain_kernel<4, false, false, NLL>;
+  if (xw) return flow_rev_chain_kernel<3, true, true, NLL>;
+  return x3 ? flow_rev_chain_kernel<3, true, false, NLL> : flow_rev_chain_kernel<3, false, false, NLL>;
+}
+FlowRevChainKernel flow_rev_chain_pick(bool lstm, bool x3, bool xw, bool nll) {
+  return nll ? flow_rev_chain_pick_<true>(lstm, x3, xw) : flow_rev_chain_pick_<false>(lstm, x3, xw);
+}
+
+// start state of a persistent walk: header and progress words cleared (LFI_PIPE_FORCE_ABORT=1: the abort word already set)
+int flow_pipe_reset(const FlowK& f, hipStream_t st, const char* who) {
+  hipError_t me = hipMemsetAsync(f.pipe, 0, (size_t)pipe_words(f) * sizeof(unsigned), st);
+  LFI_REQUIRE(me == hipSuccess, "%s: hipMemsetAsync: %s", who, hipGetErrorString(me));
+  if (flow_pipe_force_abort()) (void)hipMemsetAsync(f.pipe + 1, 1, sizeof(unsigned), st);
+  return LFI_OK;
+}
+
 }  // namespace
 
 // =================================================================================================== C ABI
@@ -3506,8 +3561,6 @@ extern "C" int lfi_debug_set_stamps(void* device_buffer) {
 
 extern "C" long lfi_flow_prep_floats(const lfi_flow_dims* d) {
   if (!d) return 0;
-  const int Ch = d->C / 2, C2 = d->C - Ch, Cout = d->affine ? 2 * C2 : C2, G = (d->lstm ? 4 : 3) * d->H;
-  (void)Ch; (void)Cout; (void)G;
   // published layout, scratch (per-step log-det parts, fp64 workspace for the inverses), zero-padded cell images
   return prep_scratch_end(d) + prep_padded_floats(d) + 16;
 }
@@ -3540,7 +3593,7 @@ extern "C" int lfi_flow_prep(const lfi_flow_dims* d, const lfi_flow_params* p, f
                        (float*)f.pwh, (float*)f.pwfl, (float*)f.bwfl, (float*)f.bwh, (float*)f.bwz,
                        (with_inverse || p->inv_w) ? (float*)f.pWinv : nullptr);
     LFI_LAUNCH_CHECK("lfi_flow_prep pad");
-    if ((d->gemm_precision & 1) && !f.lstm && f.H16 % 32 == 0) {
+    if (flow_x3_prep_images(d, f)) {
       hipLaunchKernelGGL(flow_prep_x3_kernel, dim3(16, d->Ks, 2), dim3(256), 0, st, f, const_cast<uint4*>(f.xbwh),
                          const_cast<uint4*>(f.xbwz));
       LFI_LAUNCH_CHECK("lfi_flow_prep x3");
@@ -3601,37 +3654,24 @@ extern "C" int lfi_flow_seq_fwd(const lfi_flow_dims* d, const lfi_flow_params* p
   const Carve cv = carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout);
   const CarveF cf = carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout);
   const size_t lds = (size_t)(fast ? cf.total : cv.total) * sizeof(float);
-  rc = fast ? (f.lstm ? set_flow_lds(flow_diag_fwd_fast_kernel<4>, lds, "lfi_flow_seq_fwd")
-                      : set_flow_lds(flow_diag_fwd_fast_kernel<3>, lds, "lfi_flow_seq_fwd"))
-            : set_flow_lds(flow_diag_fwd_kernel, lds, "lfi_flow_seq_fwd");
-  if (rc) return rc;
+  const FlowDiagKernel diag = flow_diag_fwd_pick(fast, f.lstm);
+  if ((rc = set_flow_lds(diag, lds, "lfi_flow_seq_fwd"))) return rc;
   const bool pipe = fast && flow_pipe_enabled();
   if (pipe) {
     long off[8];
     f.pipe = reinterpret_cast<unsigned*>(stash + align4(stash_offsets(f, off)));
     f.pipe_fence = flow_pipe_fence();
     const size_t plds = (size_t)pipe_fwd_lds_floats(f.C, f.C16, f.H16, f.Ch16, f.Cout, f.Co16) * sizeof(float);
-    // bf16 x 3 recurrent products (GRU cells, hidden and z widths whose 16-k padding is a whole number of 32-k blocks)
-    const bool x3 = (d->gemm_precision & 1) && !f.lstm && (f.H16 % 32 == 0) && (f.Ch16 % 32 == 0) && flow_pipe_x3_enabled();
-    rc = f.lstm ? set_flow_lds(flow_pipe_fwd_kernel<4, false>, plds, "lfi_flow_seq_fwd")
-                : (x3 ? set_flow_lds(flow_pipe_fwd_kernel<3, true>, plds, "lfi_flow_seq_fwd")
-                      : set_flow_lds(flow_pipe_fwd_kernel<3, false>, plds, "lfi_flow_seq_fwd"));
-    if (rc) return rc;
-    hipError_t me = hipMemsetAsync(f.pipe, 0, (size_t)pipe_words(f) * sizeof(unsigned), st);
-    LFI_REQUIRE(me == hipSuccess, "lfi_flow_seq_fwd: hipMemsetAsync: %s", hipGetErrorString(me));
-    if (flow_pipe_force_abort()) (void)hipMemsetAsync(f.pipe + 1, 1, sizeof(unsigned), st);
-    const dim3 grid(f.Ks * f.nbt);
-    if (f.lstm) hipLaunchKernelGGL((flow_pipe_fwd_kernel<4, false>), grid, dim3(NT), plds, st, f);
-    else if (x3) hipLaunchKernelGGL((flow_pipe_fwd_kernel<3, true>), grid, dim3(NT), plds, st, f);
-    else hipLaunchKernelGGL((flow_pipe_fwd_kernel<3, false>), grid, dim3(NT), plds, st, f);
+    const FlowPipeKernel walk = flow_pipe_fwd_pick(f.lstm, flow_x3_fwd_walk(d, f));
+    if ((rc = set_flow_lds(walk, plds, "lfi_flow_seq_fwd"))) return rc;
+    if ((rc = flow_pipe_reset(f, st, "lfi_flow_seq_fwd"))) return rc;
+    hipLaunchKernelGGL(walk, dim3(f.Ks * f.nbt), dim3(NT), plds, st, f);
   }
   for (int dg = 0; !pipe && dg < f.N + f.Ks - 1; ++dg) {
     const int klo = dg - (f.N - 1) > 0 ? dg - (f.N - 1) : 0;
     const int khi = dg < f.Ks - 1 ? dg : f.Ks - 1;
     const dim3 grid(f.nbt, khi - klo + 1);
-    if (!fast) hipLaunchKernelGGL(flow_diag_fwd_kernel, grid, dim3(NT), lds, st, f, dg, klo);
-    else if (f.lstm) hipLaunchKernelGGL(flow_diag_fwd_fast_kernel<4>, grid, dim3(NT), lds, st, f, dg, klo);
-    else hipLaunchKernelGGL(flow_diag_fwd_fast_kernel<3>, grid, dim3(NT), lds, st, f, dg, klo);
+    hipLaunchKernelGGL(diag, grid, dim3(NT), lds, st, f, dg, klo);
   }
   LFI_LAUNCH_CHECK("lfi_flow_seq_fwd");
   if (f.C <= NLL_CMAX)
@@ -3646,9 +3686,9 @@ extern "C" int lfi_flow_seq_fwd(const lfi_flow_dims* d, const lfi_flow_params* p
 // (whose d(gate) LDS images are the source), gate columns that are the stash's (H a multiple of 32: no padding columns) and
 // batch tiles that pair up into whole 32-row plane tiles (B a multiple of 32).
 static bool flow_bwd_planes_ok(const lfi_flow_dims* d) {
-  if (!d || d->lstm || !(d->gemm_precision & 1) || d->H % 32 != 0 || d->B % 32 != 0) return false;
+  if (!d || !flow_x3_bwd_planes(d) || d->B % 32 != 0) return false;
   const int Ch = d->C / 2, C2 = d->C - Ch, Cout = d->affine ? 2 * C2 : C2;
-  return flow_fast_ok(d->C, d->H, Cout) && !flow_force_generic() && flow_pipe_enabled() && flow_pipe_x3_enabled() && 3 * d->H >= 128;
+  return flow_fast_ok(d->C, d->H, Cout) && !flow_force_generic() && flow_pipe_enabled();
 }
 extern "C" int lfi_flow_bwd_emits_planes(const lfi_flow_dims* d) { return flow_bwd_planes_ok(d) ? 1 : 0; }
 
@@ -3677,39 +3717,27 @@ extern "C" int lfi_flow_seq_bwd_planes(const lfi_flow_dims* d, const lfi_flow_pa
   const CarveB cv = carve_bwd(f.C, f.H, f.Cout, f.G);
   const CarveFB cf = carve_fast_bwd(f.C16, f.H16, f.Co16, f.Cout, f.NG);
   const size_t lds = (size_t)(fast ? cf.total : cv.total) * sizeof(float);
-  rc = fast ? (f.lstm ? set_flow_lds(flow_diag_bwd_fast_kernel<4>, lds, "lfi_flow_seq_bwd")
-                      : set_flow_lds(flow_diag_bwd_fast_kernel<3>, lds, "lfi_flow_seq_bwd"))
-            : set_flow_lds(flow_diag_bwd_kernel, lds, "lfi_flow_seq_bwd");
-  if (rc) return rc;
+  const FlowDiagKernel diag = flow_diag_bwd_pick(fast, f.lstm);
+  if ((rc = set_flow_lds(diag, lds, "lfi_flow_seq_bwd"))) return rc;
   const bool pipe = fast && flow_pipe_enabled();
   if (pipe) {
     long off[10];
     f.pipe = reinterpret_cast<unsigned*>(bstash + align4(bstash_offsets(f, off)));
     f.pipe_fence = flow_pipe_fence();
-    // (NG * H16 >= 128: the bf16 operand images, 64 (NG H16 + 8) bytes each, must fit the fp32 regions they replace)
-    const bool x3 = (d->gemm_precision & 1) && !f.lstm && (f.H16 % 32 == 0) && f.NG * f.H16 >= 128 && flow_pipe_x3_enabled();
+    const bool x3 = flow_x3_bwd_walk(d, f);
     // + the bf16 hi / lo image of d lin (Q1's bf16 x 3 operand): 2 x MB rows of 32 ceil(Co16 / 32) + 8 bf16
     const size_t plds = x3 ? (((size_t)cf.total + 3) & ~(size_t)3) * sizeof(float) + (size_t)2 * MB * (32 * ((f.Co16 + 31) / 32) + 8) * 2 : lds;
-    rc = f.lstm ? set_flow_lds(flow_pipe_bwd_kernel<4, false>, plds, "lfi_flow_seq_bwd")
-                : (x3 ? set_flow_lds(flow_pipe_bwd_kernel<3, true>, plds, "lfi_flow_seq_bwd")
-                      : set_flow_lds(flow_pipe_bwd_kernel<3, false>, plds, "lfi_flow_seq_bwd"));
-    if (rc) return rc;
-    hipError_t me = hipMemsetAsync(f.pipe, 0, (size_t)pipe_words(f) * sizeof(unsigned), st);
-    LFI_REQUIRE(me == hipSuccess, "lfi_flow_seq_bwd: hipMemsetAsync: %s", hipGetErrorString(me));
-    if (flow_pipe_force_abort()) (void)hipMemsetAsync(f.pipe + 1, 1, sizeof(unsigned), st);
-    const dim3 grid(f.Ks * f.nbt);
-    if (f.lstm) hipLaunchKernelGGL((flow_pipe_bwd_kernel<4, false>), grid, dim3(NT), plds, st, f);
-    else if (x3) hipLaunchKernelGGL((flow_pipe_bwd_kernel<3, true>), grid, dim3(NT), plds, st, f);
-    else hipLaunchKernelGGL((flow_pipe_bwd_kernel<3, false>), grid, dim3(NT), plds, st, f);
+    const FlowPipeKernel walk = flow_pipe_bwd_pick(f.lstm, x3);
+    if ((rc = set_flow_lds(walk, plds, "lfi_flow_seq_bwd"))) return rc;
+    if ((rc = flow_pipe_reset(f, st, "lfi_flow_seq_bwd"))) return rc;
+    hipLaunchKernelGGL(walk, dim3(f.Ks * f.nbt), dim3(NT), plds, st, f);
     hipLaunchKernelGGL(flow_pipe_poison_kernel, dim3(1), dim3(64), 0, st, f);
   }
   for (int dg = f.N + f.Ks - 2; !pipe && dg >= 0; --dg) {
     const int klo = dg - (f.N - 1) > 0 ? dg - (f.N - 1) : 0;
     const int khi = dg < f.Ks - 1 ? dg : f.Ks - 1;
     const dim3 grid(f.nbt, khi - klo + 1);
-    if (!fast) hipLaunchKernelGGL(flow_diag_bwd_kernel, grid, dim3(NT), lds, st, f, dg, klo);
-    else if (f.lstm) hipLaunchKernelGGL(flow_diag_bwd_fast_kernel<4>, grid, dim3(NT), lds, st, f, dg, klo);
-    else hipLaunchKernelGGL(flow_diag_bwd_fast_kernel<3>, grid, dim3(NT), lds, st, f, dg, klo);
+    hipLaunchKernelGGL(diag, grid, dim3(NT), lds, st, f, dg, klo);
   }
   LFI_LAUNCH_CHECK("lfi_flow_seq_bwd");
   return LFI_OK;
@@ -3731,10 +3759,7 @@ extern "C" long lfi_flow_param_grads_work_floats(const lfi_flow_dims* d) {
 }
 
 // LFI_FLOW_WGRAD_FUSED=0: the thin weight-gradient products as four batched split-K launches + a column-sum pass (rounds 2 - 5)
-bool flow_wgrad_fused_enabled() {
-  const char* e = getenv("LFI_FLOW_WGRAD_FUSED");
-  return !(e && e[0] == '0');
-}
+bool flow_wgrad_fused_enabled() { return lfi_env_on("LFI_FLOW_WGRAD_FUSED"); }
 
 extern "C" int lfi_flow_param_grads(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* stash,
                                     const float* bstash, const float* c, long ldc, float gscale, const lfi_flow_grads* g,
@@ -3901,22 +3926,12 @@ extern "C" int lfi_flow_step(const lfi_flow_dims* d, const lfi_flow_params* p, c
   io.k = k; io.rows = rows; io.x_in = x_in; io.ldx = ldx; io.h_prev = h_prev; io.gic = gic_k;
   io.c_prev = d->lstm ? c_prev : nullptr; io.c_out = d->lstm ? c_out : nullptr;
   io.x_out = x_out; io.ldxo = ldxo; io.h_out = h_out; io.l_out = ldc_acc; io.l_accumulate = 1;
-  const Carve cv = carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout);
-  size_t lds = (size_t)cv.total * sizeof(float);
-  if (reverse && flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic()) {
-    lds = (size_t)carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total * sizeof(float);
-    rc = f.lstm ? set_flow_lds(flow_step_rev_fast_kernel<4>, lds, "lfi_flow_step") : set_flow_lds(flow_step_rev_fast_kernel<3>, lds, "lfi_flow_step");
-    if (rc) return rc;
-    if (f.lstm) hipLaunchKernelGGL(flow_step_rev_fast_kernel<4>, dim3(lfi_cdiv(rows, MB)), dim3(NT), lds, (hipStream_t)stream, f, io);
-    else hipLaunchKernelGGL(flow_step_rev_fast_kernel<3>, dim3(lfi_cdiv(rows, MB)), dim3(NT), lds, (hipStream_t)stream, f, io);
-    LFI_LAUNCH_CHECK("lfi_flow_step");
-    return LFI_OK;
-  }
-  rc = reverse ? set_flow_lds(flow_step_kernel<true>, lds, "lfi_flow_step")
-               : set_flow_lds(flow_step_kernel<false>, lds, "lfi_flow_step");
-  if (rc) return rc;
-  if (reverse) hipLaunchKernelGGL(flow_step_kernel<true>, dim3(lfi_cdiv(rows, MB)), dim3(NT), lds, (hipStream_t)stream, f, io);
-  else hipLaunchKernelGGL(flow_step_kernel<false>, dim3(lfi_cdiv(rows, MB)), dim3(NT), lds, (hipStream_t)stream, f, io);
+  const bool fast = reverse && flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();   // (the forward cell has the streaming form only)
+  const size_t lds = (size_t)(fast ? carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total : carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout).total) *
+                     sizeof(float);
+  const FlowStepKernel cell = reverse ? flow_step_rev_pick(fast, f.lstm) : flow_step_kernel<false>;
+  if ((rc = set_flow_lds(cell, lds, "lfi_flow_step"))) return rc;
+  hipLaunchKernelGGL(cell, dim3(lfi_cdiv(rows, MB)), dim3(NT), lds, (hipStream_t)stream, f, io);
   LFI_LAUNCH_CHECK("lfi_flow_step");
   return LFI_OK;
 }
@@ -3925,8 +3940,7 @@ extern "C" int lfi_flow_step(const lfi_flow_dims* d, const lfi_flow_params* p, c
 extern "C" int lfi_flow_seq_rev_ok(const lfi_flow_dims* d) {
   if (!d) return 0;
   const int Cout = d->affine ? 2 * (d->C - d->C / 2) : d->C - d->C / 2;
-  const char* e = getenv("LFI_INVERT_WALK");
-  return (flow_fast_ok(d->C, d->H, Cout) && !flow_force_generic() && !(e && e[0] == '0')) ? 1 : 0;
+  return (flow_fast_ok(d->C, d->H, Cout) && !flow_force_generic() && lfi_env_on("LFI_INVERT_WALK")) ? 1 : 0;
 }
 
 extern "C" long lfi_flow_seq_rev_work_floats(const lfi_flow_dims* d) {
@@ -3959,10 +3973,9 @@ extern "C" int lfi_flow_seq_rev(const lfi_flow_dims* d, const lfi_flow_params* p
   hipError_t me = hipMemsetAsync(rw.pipe, 0, words * sizeof(unsigned), st);
   LFI_REQUIRE(me == hipSuccess, "lfi_flow_seq_rev: hipMemsetAsync: %s", hipGetErrorString(me));
   const size_t lds = (size_t)carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total * sizeof(float);
-  rc = f.lstm ? set_flow_lds(flow_rev_walk_kernel<4>, lds, "lfi_flow_seq_rev") : set_flow_lds(flow_rev_walk_kernel<3>, lds, "lfi_flow_seq_rev");
-  if (rc) return rc;
-  if (f.lstm) hipLaunchKernelGGL(flow_rev_walk_kernel<4>, dim3(f.Ks * f.nbt), dim3(NT), lds, st, f, rw);
-  else hipLaunchKernelGGL(flow_rev_walk_kernel<3>, dim3(f.Ks * f.nbt), dim3(NT), lds, st, f, rw);
+  const FlowRevWalkKernel walk = flow_rev_walk_pick(f.lstm);
+  if ((rc = set_flow_lds(walk, lds, "lfi_flow_seq_rev"))) return rc;
+  hipLaunchKernelGGL(walk, dim3(f.Ks * f.nbt), dim3(NT), lds, st, f, rw);
   LFI_LAUNCH_CHECK("lfi_flow_seq_rev");
   // logdet[n][b] = sum over the flow steps of the coupling log-dets (the constant ActNorm / invconv part is the caller's)
   return lfi_colsum_f32(rw.ldk, F, 0, f.Ks, (int)F, 1, logdet, 0, 1.0f, 0, cws, stream);
@@ -4062,15 +4075,11 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
   const bool fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
   const Carve cv = carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout);
   const size_t lds = (size_t)(fast ? carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total : cv.total) * sizeof(float);
-  rc = !fast ? set_flow_lds(flow_step_kernel<true>, lds, "lfi_flow_sample_seq")
-             : (f.lstm ? set_flow_lds(flow_step_rev_fast_kernel<4>, lds, "lfi_flow_sample_seq")
-                       : set_flow_lds(flow_step_rev_fast_kernel<3>, lds, "lfi_flow_sample_seq"));
-  if (rc) return rc;
+  const FlowStepKernel cell = flow_step_rev_pick(fast, f.lstm);
+  if ((rc = set_flow_lds(cell, lds, "lfi_flow_sample_seq"))) return rc;
   // LFI_SAMPLE_CHAIN=0 keeps one launch per flow step
-  const char* ce = getenv("LFI_SAMPLE_CHAIN");
-  const bool chain = fast && !(ce && ce[0] == '0');
-  // (the reverse cells' recurrent products as three fp16 products - fp32-grade - in both bf16 modes of the per-frame GEMMs)
-  const bool x3 = (d->gemm_precision & 1) && !f.lstm && (f.H16 % 32 == 0) && (f.Ch16 % 32 == 0) && (f.C16 % 32 == 0) && flow_pipe_x3_enabled();
+  const bool chain = fast && lfi_env_on("LFI_SAMPLE_CHAIN");
+  const bool x3 = flow_x3_rev_cell(d, f);
   unsigned* chain_state = reinterpret_cast<unsigned*>((reinterpret_cast<uintptr_t>(xb + (long)B * C) + 15) & ~(uintptr_t)15);
   const size_t chain_words = (size_t)(((long)PIPE_HDR + (long)Ks * f.nbt + 3) & ~3L);
   // raw prev_p1_face windows start (t - hist1) * C floats into a row: 16-byte aligned only on every other frame at C = 50,
@@ -4088,23 +4097,13 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
     if ((rc = lfi_internal_sample_cond_prepare(wct, E, p1col, K1, f.wc, Ks, G, cfrags, stream))) return rc;
   }
   // LFI_SAMPLE_XF_CHAIN=0 keeps the window-fragment kernel in front of every frame's conditioning
-  const char* xce = getenv("LFI_SAMPLE_XF_CHAIN");
-  const bool xf_chain = fused && chain && !(xce && xce[0] == '0');
-  // the reverse cells' weights as the fp16 fragment images lfi_flow_prep left (no split in every workgroup of every frame)
-  const bool xw = x3 && chain && flow_x3h_images_ok(f) && flow_sample_wfrag16_enabled();
-  if (chain && !nll) {
-    rc = f.lstm ? set_flow_lds(flow_rev_chain_kernel<4, false>, lds, "lfi_flow_sample_seq")
-                : (xw ? set_flow_lds(flow_rev_chain_kernel<3, true, true>, lds, "lfi_flow_sample_seq")
-                      : (x3 ? set_flow_lds(flow_rev_chain_kernel<3, true>, lds, "lfi_flow_sample_seq")
-                            : set_flow_lds(flow_rev_chain_kernel<3, false>, lds, "lfi_flow_sample_seq")));
-    if (rc) return rc;
-  } else if (chain) {
-    rc = f.lstm ? set_flow_lds(flow_rev_chain_kernel<4, false, false, true>, lds, "lfi_flow_sample_seq_nll")
-                : (xw ? set_flow_lds(flow_rev_chain_kernel<3, true, true, true>, lds, "lfi_flow_sample_seq_nll")
-                      : (x3 ? set_flow_lds(flow_rev_chain_kernel<3, true, false, true>, lds, "lfi_flow_sample_seq_nll")
-                            : set_flow_lds(flow_rev_chain_kernel<3, false, false, true>, lds, "lfi_flow_sample_seq_nll")));
-    if (rc) return rc;
-  }
+  const bool xf_chain = fused && chain && lfi_env_on("LFI_SAMPLE_XF_CHAIN");
+  // the reverse cells' weights as the fp16 fragment images lfi_flow_prep left (no split in every workgroup of every frame; x3 is true
+  // only for the shapes that have them, flow_x3h_images_ok)
+  const bool xw = x3 && chain && flow_sample_wfrag16_enabled();
+  // one launch for the whole chain of a frame; with nll the cells also pass the rows' running log-density down the chain
+  const FlowRevChainKernel chain_kernel = flow_rev_chain_pick(f.lstm, x3, xw, nll != nullptr);
+  if (chain && (rc = set_flow_lds(chain_kernel, lds, nll ? "lfi_flow_sample_seq_nll" : "lfi_flow_sample_seq"))) return rc;
   for (int n = 0; n < nframes; ++n) {
     const int t = start + n;
     // c = LeakyReLU(pre_static[n] + window @ Wct[:, :hist1*C]^T), IN PLACE: frame n's rows of pre_static are read by this product
@@ -4183,17 +4182,8 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
         hipError_t me = hipMemsetAsync(chain_state, 0, chain_words * sizeof(unsigned), st);
         LFI_REQUIRE(me == hipSuccess, "lfi_flow_sample_seq: hipMemsetAsync: %s", hipGetErrorString(me));
       }
-      if (nll) {   // the same grid; the cells also pass the rows' running log-density down the chain
-        rcn.qa = nll_work; rcn.qb = nll_work + B; rcn.nll = nll + (long)n * B;
-        if (f.lstm) hipLaunchKernelGGL((flow_rev_chain_kernel<4, false, false, true>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
-        else if (xw) hipLaunchKernelGGL((flow_rev_chain_kernel<3, true, true, true>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
-        else if (x3) hipLaunchKernelGGL((flow_rev_chain_kernel<3, true, false, true>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
-        else hipLaunchKernelGGL((flow_rev_chain_kernel<3, false, false, true>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
-      }
-      else if (f.lstm) hipLaunchKernelGGL((flow_rev_chain_kernel<4, false>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
-      else if (xw) hipLaunchKernelGGL((flow_rev_chain_kernel<3, true, true>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
-      else if (x3) hipLaunchKernelGGL((flow_rev_chain_kernel<3, true>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
-      else hipLaunchKernelGGL((flow_rev_chain_kernel<3, false>), dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
+      if (nll) { rcn.qa = nll_work; rcn.qb = nll_work + B; rcn.nll = nll + (long)n * B; }
+      hipLaunchKernelGGL(chain_kernel, dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
       continue;
     }
     const float* xin = noise + (long)n * B * C;
@@ -4208,9 +4198,7 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
       if (k == 0) { io.x_out = faces + (long)t * C; io.ldxo = (long)seq_len * C; }
       else { io.x_out = (k & 1) ? xa : xb; io.ldxo = C; }
       if (nll) { io.l_out = nll_work; io.l_accumulate = k + 1 < Ks; }   // (launch after launch: no two workgroups at one word at a time)
-      if (!fast) hipLaunchKernelGGL(flow_step_kernel<true>, dim3(f.nbt), dim3(NT), lds, st, f, io);
-      else if (f.lstm) hipLaunchKernelGGL(flow_step_rev_fast_kernel<4>, dim3(f.nbt), dim3(NT), lds, st, f, io);
-      else hipLaunchKernelGGL(flow_step_rev_fast_kernel<3>, dim3(f.nbt), dim3(NT), lds, st, f, io);
+      hipLaunchKernelGGL(cell, dim3(f.nbt), dim3(NT), lds, st, f, io);
       xin = io.x_out; ldx = io.ldxo;
     }
     if (nll)

@@ -829,11 +829,7 @@ int kchunk_for(int K, int splitk) {
 // one per CU, ~12 % faster per MFMA on long products).
 struct GemmPlan { int shape, splitk; };
 GemmPlan gemm_plan(int M, int N, int K, int batch, int splitk_req, bool x3) {
-  static int allow256 = -1;
-  if (allow256 < 0) {
-    const char* e = getenv("LFI_GEMM_256");
-    allow256 = (e && e[0] == '0') ? 0 : 1;
-  }
+  const bool allow256 = lfi_env_on("LFI_GEMM_256");
   GemmPlan best = {0, splitk_req > 0 ? splitk_req : 1};
   double best_score = -1.0;
   const int cand[6] = {1, 2, 3, 4, 6, 8};

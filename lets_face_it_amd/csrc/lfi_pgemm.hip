@@ -593,15 +593,13 @@ __global__ __launch_bounds__(256) void planes_from_f32_kernel(const float* __res
 // the three-product 16 x 16 x 32 kernel: whole pairs of k-tiles in every split, the through-LDS or the direct plane epilogue (LFI_PGEMM_16=0:
 // the 32 x 32 x 16 kernel everywhere)
 bool planes16_ok(const GemmArgs& a) {
-  const char* e = getenv("LFI_PGEMM_16");   // (read per call: the tests compare the two kernels)
-  if (e && e[0] == '0') return false;
+  if (!lfi_env_on("LFI_PGEMM_16")) return false;   // (read per call: the tests compare the two kernels)
   return a.vecC && a.skip == 0 && (a.nkt & 1) == 0 && ((a.kchunk >> 4) & 1) == 0;
 }
 
 // the two-product 16 x 16 x 32 kernel: B transposed, A either way, skip bit 0 alone (LFI_PGEMM_16T=0: the 32 x 32 x 16 kernel)
 bool planes16t_ok(const GemmArgs& a) {
-  const char* e = getenv("LFI_PGEMM_16T");
-  if (e && e[0] == '0') return false;
+  if (!lfi_env_on("LFI_PGEMM_16T")) return false;
   return a.vecC && a.skip == 1 && (a.nkt & 1) == 0 && ((a.kchunk >> 4) & 1) == 0;
 }
 
@@ -609,8 +607,7 @@ bool planes16t_ok(const GemmArgs& a) {
 // mask, accumulate, column sums, fp32 rows or split-K partials (LFI_PGEMM_DIRECT=0: always through LDS)
 // -> 0: not covered; 3: planes only
 int planes16_direct_mode(const GemmArgs& a) {
-  const char* e = getenv("LFI_PGEMM_DIRECT");
-  if (e && e[0] == '0') return 0;
+  if (!lfi_env_on("LFI_PGEMM_DIRECT")) return 0;
   if (!(a.vecC && a.act != 2 && a.accumulate == 0 && !a.colpart && (a.N & 3) == 0) || a.splitk > 1) return 0;
   if (a.Cr && !a.storeC) return ((a.strideC & 31) == 0 && (a.colCr & 15) == 0) ? 3 : 0;
   return 0;
@@ -618,8 +615,7 @@ int planes16_direct_mode(const GemmArgs& a) {
 
 // MODE 4 of the direct epilogue: plane outputs only, act 2 with the mask in planes, column sums, 128 x 256 tiles
 bool planes16_direct_mask_ok(const GemmArgs& a) {
-  const char* e = getenv("LFI_PGEMM_DIRECT");
-  if (e && e[0] == '0') return false;
+  if (!lfi_env_on("LFI_PGEMM_DIRECT")) return false;
   return a.vecC && a.act == 2 && a.Gr && !a.G && a.accumulate == 0 && a.colpart && a.splitk == 1 && a.Cr && !a.storeC && !a.bias &&
          (a.N & 3) == 0 && (a.strideC & 31) == 0 && (a.colCr & 15) == 0 && (a.colGr & 15) == 0 && (a.ldpart & 3) == 0;
 }

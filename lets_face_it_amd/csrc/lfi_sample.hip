@@ -399,8 +399,7 @@ __global__ __launch_bounds__(SC_NT) __attribute__((amdgpu_waves_per_eu(RT == 2 ?
 
 // shapes the fused conditioning takes (the caller falls back to its two GEMMs otherwise)
 extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond_ok(int D, int G, int K1) {
-  const char* e = getenv("LFI_SAMPLE_FUSED");
-  if (e && e[0] == '0') return 0;
+  if (!lfi_env_on("LFI_SAMPLE_FUSED")) return 0;
   return (D == SC_D && (G == 384 || G == 512) && K1 >= 1 && K1 <= 512) ? 1 : 0;
 }
 // bytes of fragment storage: [weights of phase 1][weights of phase 2][the frame's window]
@@ -440,8 +439,7 @@ extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond(co
   // inside the conditioning kernel instead (needs 8-byte aligned window rows; bit-identical, tested): one launch less per frame,
   // but 16 workgroups repeat each row tile's split with 8-byte loads - measured 60.0 against 57.0 - 57.4 ms per 1024 x 300 call
   // (profiles/round5_sampler_ab.md): kept as the switch only.
-  const char* xe = getenv("LFI_SAMPLE_XFRAG");
-  const bool inreg = (xe && xe[0] == '0') && ld_faces % 2 == 0 && off % 2 == 0 && (reinterpret_cast<uintptr_t>(faces) & 7) == 0 &&
+  const bool inreg = !lfi_env_on("LFI_SAMPLE_XFRAG") && ld_faces % 2 == 0 && off % 2 == 0 && (reinterpret_cast<uintptr_t>(faces) & 7) == 0 &&
                      faces_floats > 0;
   if (!inreg && !have_xfrag) {   // (have_xfrag: the previous frame's reverse chain left this frame's window fragments - lfi_flow.hip, RevChain.xf)
     const long nx = (long)ntile * NM1 * 2 * 512;
