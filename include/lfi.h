@@ -416,6 +416,22 @@ int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_params* p, co
                             float* faces, int seq_len, int start, int nframes, int first_frame,
                             float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
                             float* nll, float* nll_work, void* stream);
+/* Teacher-forced frames of a sequence whose recurrent state is carried (SampleStream.observe; SeqGlow.forward, glow/models.py:524-561,
+ * one frame at a time): lfi_flow_sample_seq_nll's arguments without `noise`. Per frame n the sampler's conditioning front end (the
+ * window part of cond_transform + gic, every lfi_p1enc kind), then ALL Ks forward flow steps of the OBSERVED frame faces[:, start + n]
+ * in one launch: h / cstate are read and updated in place exactly as the sampler's reverse cells update them (the recurrent cell sees
+ * the pass-through half and the conditioning, the same in both directions), so observed and generated frames alternate freely.
+ * nll (nframes x B): the frame's NLL in bits, -(logdet_fwd + sum_c -0.5 (z_c^2 + log 2 pi)) / ln 2; z (nframes x B x C, NULL = not
+ * wanted): its latent. Arithmetic of the cells by d->gemm_precision: 9 = three fp16 products of two-piece operands (range: the
+ * caller's guard), 5 and 0 = the exact f32 MFMA (no range caveat: the observed frame is caller data; 5 is the range guard's fallback). Shapes outside the register-resident
+ * cells (and LFI_SAMPLE_CHAIN=0): Ks launches of the streaming forward cell + a finish. score_work: lfi_flow_score_work_floats(d)
+ * floats; work / p1work: the sampler's. Allocation-free, capturable; every argument is checked before the first launch. */
+long lfi_flow_score_work_floats(const lfi_flow_dims* d);
+int lfi_flow_score_seq_from(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep,
+                            const float* wct, long E, int hist1, float* pre_static,
+                            float* faces, int seq_len, int start, int nframes, int first_frame,
+                            float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
+                            float* score_work, float* z, float* nll, void* stream);
 /* One frame forward of a streaming sampling session (SeqGlow.open_stream; glow/models.py:567-596 one frame at a time), in ONE launch:
  * every window i (B x hist[i] x dim[i], rows per batch entry) moves up by one frame in place, and its last row receives src[i] (B x
  * dim[i]), or - src[i] == NULL, the prev_p1_face window of the session's own output - keeps the frame the last step generated there;

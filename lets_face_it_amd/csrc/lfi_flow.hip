@@ -2132,6 +2132,335 @@ __global__ __launch_bounds__(NT) void flow_rev_chain_kernel(FlowK f, RevChain rc
   }
 }
 
+// ------------------------------------------------------------------------------------------- forward chain (teacher-forced frame)
+// FlowStep.normal_flow (glow/models.py:311-341) of ONE observed frame with the recurrent state carried in place: the forward twin of
+// rev_fast_cell for a streaming session's observe() step. Same thread maps, same LDS carve, same place of the wait: the weights, gic,
+// h_prev and the h_prev W_hh half of the recurrent product run before it; behind it actnorm, y = a W, the z1 half + the gates,
+// LinearZeros and the coupling. The recurrent cell sees what the reverse cell of the same frame sees - z1 and the conditioning - so
+// the h / c it leaves is the state a sampler continues from. No stash of any kind.
+// X3: every product as three fp16 products of two-piece operands (x3h_*, fp32-grade: 2^-22 relative), the f32 fragment images split
+// in registers before the wait; otherwise the exact f32 MFMA. (The training walks' three bf16 products - 2^-16 pieces - are not used
+// here: the state must match the reverse cell's to the sampler's own tolerance.)
+// q_in: the rows' running coupling log-det from step k - 1 (null: this cell starts it); q_out: where it goes on to step k + 1, sc1
+// stores in front of the publish. nll_out (the last step): the cell adds the prior term of its z, sum_c -0.5 (z_c^2 + log 2 pi), and
+// logdet_const and writes -(logdet + log p(z)) / ln 2 in bits. One writer per word, k ascending: a fixed summation order.
+// io.x_out may be null (the last step of a caller that does not want z).
+template <int NG, bool X3>
+__device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io, int b0, const unsigned* wait_flag, unsigned* abort_w,
+                                               unsigned* pub_flag, int* s_ok, const float* q_in, float* q_out, float* nll_out) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, kq = lane >> 4;
+  const int ri = tid >> 5, cl = tid & 31;
+  const int k = io.k, rows = io.rows;
+  const int C = f.C, H = f.H, Ch = f.Ch, C2 = f.C2, Cout = f.Cout, G = f.G;
+  const int C16 = f.C16, Ch16 = f.Ch16, H16 = f.H16, Co16 = f.Co16;
+  const CarveF cv = carve_fast_fwd(C, C16, H16, Ch16, Cout);
+  float* At = flow_smem + cv.At;
+  float* Ht = flow_smem + cv.Ht;
+  float* Zt = flow_smem + cv.Zt;
+  float* Hn = flow_smem + cv.Hn;
+  float* Yrm = flow_smem + cv.Yrm;
+  float* Orm = flow_smem + cv.Orm;
+  const int ldy = C + 1, ldo = Cout + 1;
+  const int nbC = C16 >> 4, nbZ = Ch16 >> 4, nbH = H16 >> 4;
+  const bool t1 = wave * 16 < C, t2 = wave * 16 < H, t3 = wave * 16 < Cout;
+  const int tcol = wave * 16 + l15;
+  // ---- requests in the order their results are needed: h_prev (its LDS image gates the first barrier), the recurrent weights, then
+  // the weights of the phases behind the wait
+  const int hrow = b0 + ri;
+  float hv[FB_H / 2];
+#pragma unroll
+  for (int q = 0; q < FB_H / 2; ++q) {
+    const int j = cl + 32 * q;
+    hv[q] = (io.h_prev && hrow < rows && j < H) ? io.h_prev[(long)hrow * H + j] : 0.0f;
+  }
+  f32x4 wz[NG][FB_Z], wh[NG][FB_H], w3[FB_H], w1[FB_C];
+  {
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+#pragma unroll
+      for (int b = 0; b < FB_Z; ++b) wz[g][b] = zero4;
+#pragma unroll
+      for (int b = 0; b < FB_H; ++b) wh[g][b] = zero4;
+      load_frag<FB_H>(wh[g], f.pwh + (long)k * H16 * NG * H16, NG * H16, g * H16 + tcol, kq, nbH, t2);
+      load_frag<FB_Z>(wz[g], f.pwz + (long)k * Ch16 * NG * H16, NG * H16, g * H16 + tcol, kq, nbZ, t2);
+    }
+#pragma unroll
+    for (int b = 0; b < FB_H; ++b) w3[b] = zero4;
+#pragma unroll
+    for (int b = 0; b < FB_C; ++b) w1[b] = zero4;
+    // (the LSTM cell's four gate blocks of W_hh fill the register file: its W and LinearZeros fragments are requested once the h-side
+    // product has let those go - still in front of the wait; 24 VGPRs in scratch otherwise)
+    if constexpr (NG != 4) {
+      load_frag<FB_C>(w1, f.pW + (long)k * C16 * C16, C16, tcol, kq, nbC, t1);
+      load_frag<FB_H>(w3, f.pwfl + (long)k * H16 * Co16, Co16, tcol, kq, nbH, t3);
+    }
+  }
+  float gc[4][NG], bh[NG], cprev[4];
+  auto load_gic = [&]() {
+    const float* bhh = f.p.b_hh + (long)k * G;
+    const int jc = tcol < H ? tcol : 0;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) bh[g] = bhh[g * H + jc];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = min(b0 + kq * 4 + r, rows - 1);
+#pragma unroll
+      for (int g = 0; g < NG; ++g) gc[r][g] = io.gic[(long)row * G + g * H + jc];
+      cprev[r] = (NG == 4 && io.c_prev) ? io.c_prev[(long)row * H + jc] : 0.0f;
+    }
+  };
+  if constexpr (NG != 4) load_gic();
+  // per-column constants of the phases behind the wait: ActNorm of this thread's two channels (cl, cl + 32), LinearZeros of its column
+  float an_b[2], an_s[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int c = cl + 32 * q;
+    an_b[q] = c < C ? f.p.an_bias[(long)k * C + c] : 0.0f;
+    an_s[q] = c < C ? expf(f.p.an_logs[(long)k * C + c]) : 0.0f;
+  }
+  const float flb = tcol < Cout ? f.p.b_fl[(long)k * Cout + tcol] : 0.0f;
+  const float fls = tcol < Cout ? expf(3.0f * f.p.l_fl[(long)k * Cout + tcol]) : 0.0f;
+  // ---- before the wait: h_prev and the zero k padding into LDS, the fragment split, the h_prev W_hh half of the recurrent product
+#pragma unroll
+  for (int q = 0; q < FB_H / 2; ++q) {
+    const int j = cl + 32 * q;
+    if (j < H16) {
+      Ht[j * LT + ri] = hv[q];
+      if (j >= H) Hn[j * LT + ri] = 0.0f;
+    }
+  }
+  for (int c = Ch + cl; c < Ch16; c += 32) Zt[c * LT + ri] = 0.0f;
+  X3FragH wzx[X3 ? NG : 1][FB_Z / 2], w3x[X3 ? FB_H / 2 : 1], w1x[X3 ? FB_C / 2 : 1];
+  if constexpr (X3) {   // (instantiated for shapes with whole 32-k blocks everywhere: flow_x3h_images_ok)
+#pragma unroll
+    for (int b = 0; b < FB_H / 2; ++b) w3x[b] = x3h_pack(w3[2 * b], w3[2 * b + 1]);
+#pragma unroll
+    for (int b = 0; b < FB_C / 2; ++b) w1x[b] = x3h_pack(w1[2 * b], w1[2 * b + 1]);
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+      for (int b = 0; b < FB_Z / 2; ++b) wzx[g][b] = x3h_pack(wz[g][2 * b], wz[g][2 * b + 1]);
+  }
+  __syncthreads();
+  f32x4 az[NG], ah[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    az[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    ah[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  if (t2) {
+    const float* hl = Ht + kq * LT + l15;
+    if constexpr (X3) {
+#pragma unroll
+      for (int b = 0; b < FB_H / 2; ++b)
+        if (b < (nbH >> 1)) {
+          const X3FragH a = x3h_a(hl + b * 32 * LT);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) ah[g] = x3h_mma(a, x3h_pack(wh[g][2 * b], wh[g][2 * b + 1]), ah[g]);
+        }
+    } else {
+#pragma unroll
+      for (int b = 0; b < FB_H; ++b)
+        if (b < nbH) {
+          const float* ab = hl + b * 16 * LT;
+          const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
+#pragma unroll
+          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a0, wh[g][b][0], ah[g]);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a1, wh[g][b][1], ah[g]);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a2, wh[g][b][2], ah[g]);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a3, wh[g][b][3], ah[g]);
+        }
+    }
+  }
+  if constexpr (NG == 4) {
+    __builtin_amdgcn_sched_barrier(0);
+    load_frag<FB_C>(w1, f.pW + (long)k * C16 * C16, C16, tcol, kq, nbC, t1);
+    load_frag<FB_H>(w3, f.pwfl + (long)k * H16 * Co16, Co16, tcol, kq, nbH, t3);
+    load_gic();
+  }
+  if (wait_flag && !pipe_acquire(wait_flag, 1u, abort_w, tid, s_ok, false)) return false;
+  // ---- F0: actnorm of the incoming tile (glow/modules.py:45-52), k-major with zero k padding
+  float q = 0.0f;   // lane cl == 0 carries its row's running coupling log-det
+  {
+    const int row = b0 + ri;
+    const bool rok = row < rows;
+    if (q_in && cl == 0 && rok) q = ld_tile(q_in + row, false);   // (in flight under the cell: needed in F4)
+#pragma unroll
+    for (int qq = 0; qq < 2; ++qq) {
+      const int c = cl + 32 * qq;
+      if (c < C16) {
+        const float v = (c < C && rok) ? ld_tile(io.x_in + (long)row * io.ldx + c, wait_flag == nullptr) : 0.0f;
+        At[c * LT + ri] = c < C ? (v + an_b[qq]) * an_s[qq] : 0.0f;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- F1: y = a W   (InvertibleConv1x1.forward, glow/modules.py:186); z1 = y[:, :Ch] is the recurrent cell's input
+  if (t1) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (X3) {
+      const float* al = At + kq * LT + l15;
+#pragma unroll
+      for (int b = 0; b < FB_C / 2; ++b)
+        if (b < (nbC >> 1)) acc = x3h_mma(x3h_a(al + b * 32 * LT), w1x[b], acc);
+    } else {
+      acc = mma16_reg<FB_C>(At + kq * LT + l15, w1, nbC);
+    }
+    if (tcol < C) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = kq * 4 + r;
+        Yrm[i * ldy + tcol] = acc[r];
+        if (tcol < Ch) Zt[tcol * LT + i] = acc[r];
+      }
+    }
+  }
+  __syncthreads();
+  // ---- F2: the z1 half of the recurrent product, then the gate math (h / c updated in place)
+  if (t2) {
+    const float* zl = Zt + kq * LT + l15;
+    if constexpr (X3) {
+#pragma unroll
+      for (int b = 0; b < FB_Z / 2; ++b)
+        if (b < (nbZ >> 1)) {
+          const X3FragH a = x3h_a(zl + b * 32 * LT);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) az[g] = x3h_mma(a, wzx[g][b], az[g]);
+        }
+    } else {
+#pragma unroll
+      for (int b = 0; b < FB_Z; ++b)
+        if (b < nbZ) {
+          const float* ab = zl + b * 16 * LT;
+          const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
+#pragma unroll
+          for (int g = 0; g < NG; ++g) az[g] = mfma16(a0, wz[g][b][0], az[g]);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) az[g] = mfma16(a1, wz[g][b][1], az[g]);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) az[g] = mfma16(a2, wz[g][b][2], az[g]);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) az[g] = mfma16(a3, wz[g][b][3], az[g]);
+        }
+    }
+    fast_cell_p2_gates<NG>(f, Ht, Hn, az, ah, gc, bh, cprev, tcol, kq, b0, rows, io.h_out, io.c_out, nullptr, nullptr);
+  }
+  __syncthreads();
+  // ---- F3: o = (h' Wfl^T + b) exp(3 logs)   (LinearZeros, glow/modules.py:93-95)
+  if (t3) {
+    if constexpr (X3) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      const float* hl = Hn + kq * LT + l15;
+#pragma unroll
+      for (int b = 0; b < FB_H / 2; ++b)
+        if (b < (nbH >> 1)) acc = x3h_mma(x3h_a(hl + b * 32 * LT), w3x[b], acc);
+      if (tcol < Cout) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Orm[(kq * 4 + r) * ldo + tcol] = (acc[r] + flb) * fls;
+      }
+    } else {
+      fast_cell_p3(f, k, Hn, Orm, w3, nbH, tcol, kq, l15, b0, rows, nullptr, 0, flb, fls);
+    }
+  }
+  __syncthreads();
+  // ---- F4: coupling (glow/models.py:330-341), the pass-through half, the row's log-det; the last step: the prior term and the NLL
+  {
+    const int row = b0 + ri;
+    const bool rok = row < rows;
+    float lg = 0.0f, zz = 0.0f;
+    auto put = [&](int c, float v) {
+      if (!io.x_out || !rok) return;
+      if (pub_flag) st_sc1(io.x_out + (long)row * io.ldxo + c, v);
+      else io.x_out[(long)row * io.ldxo + c] = v;
+    };
+    if (cl < C2) {
+      const float z2 = Yrm[ri * ldy + Ch + cl];
+      float z2n;
+      if (f.affine) {
+        const float shift = Orm[ri * ldo + 2 * cl];
+        const float sraw = sigmoidf_(Orm[ri * ldo + 2 * cl + 1] + 2.0f);
+        const float sc = fmaxf(sraw, f.eps);
+        z2n = (z2 + shift) * sc;
+        lg = logf(sc);
+      } else {
+        z2n = z2 + Orm[ri * ldo + cl];
+      }
+      put(Ch + cl, z2n);
+      zz = z2n * z2n;
+    }
+    if (cl < Ch) {
+      const float z1 = Yrm[ri * ldy + cl];
+      put(cl, z1);
+      zz = __builtin_fmaf(z1, z1, zz);
+    }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) lg += __shfl_xor(lg, o, 64);   // the 32 lanes of one row
+    if (nll_out) {
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1) zz += __shfl_xor(zz, o, 64);
+    }
+    if (cl == 0 && rok) {
+      q += lg;
+      if (nll_out) nll_out[row] = -(q + f.ldconst[0] + -0.5f * (zz + (float)C * LOG2PI_F)) / LN2_F;
+      else st_sc1(q_out + row, q);
+    }
+  }
+  if (pub_flag) pipe_publish(pub_flag, 1u, tid, true);
+  return true;
+}
+
+// One OBSERVED frame of a streaming session (SampleStream.observe): all Ks forward flow steps of all batch tiles in ONE launch, the
+// forward twin of flow_rev_chain_kernel. Workgroup (k, tile) - ids by ticket, k ASCENDING, so a workgroup only waits on one that
+// already runs - requests its weights, its part of gic and its recurrent state, then waits for the tile of step k - 1 (the observed
+// frame itself for k = 0), runs the cell and hands its tile and the rows' running log-det to step k + 1; step Ks - 1 writes z (if
+// wanted) and the frame's NLL. Tiles of one sample block chain strictly, so two ping-pong buffers do.
+struct FwdChain {
+  const float* frame; long ld_frame;   // the observed frame's rows in faces (row stride seq_len * C)
+  float *xa, *xb;         // B x C tile buffers: step k writes (k & 1) ? xa : xb
+  const float* gic;       // [Ks][B][G]
+  float *h, *cstate;      // [Ks][B][H] recurrent state, updated in place
+  int has_prev;           // 0 at the first frame of a sequence (zero state)
+  unsigned* pipe;         // ticket, abort, progress words (zeroed before every launch)
+  float *qa, *qb;         // B floats each: step k writes (k & 1) ? qa : qb, as the tiles ping-pong
+  float* z;               // B x C: the frame's latent, or null
+  float* nll;             // B floats: the frame's NLL in bits, written by step Ks - 1
+};
+template <int NG, bool X3>
+__global__ __launch_bounds__(NT) void flow_fwd_chain_kernel(FlowK f, FwdChain fc) {
+  __shared__ int s_id, s_ok;
+  if (threadIdx.x == 0) s_id = (int)atomicAdd(fc.pipe, 1u);
+  __syncthreads();
+  const int nbt = f.nbt;
+  const int k = s_id / nbt, bt = s_id - k * nbt;
+  if (k >= f.Ks) return;
+  const bool last = k == f.Ks - 1;
+  unsigned* prog = fc.pipe + PIPE_HDR;
+  CellIO io = {};
+  io.k = k; io.rows = f.B;
+  if (k == 0) { io.x_in = fc.frame; io.ldx = fc.ld_frame; }
+  else { io.x_in = ((k - 1) & 1) ? fc.xa : fc.xb; io.ldx = f.C; }
+  io.x_out = last ? fc.z : ((k & 1) ? fc.xa : fc.xb); io.ldxo = f.C;
+  io.h_prev = fc.has_prev ? fc.h + (long)k * f.B * f.H : nullptr;
+  io.h_out = fc.h + (long)k * f.B * f.H;
+  if (NG == 4) { io.c_prev = fc.has_prev ? fc.cstate + (long)k * f.B * f.H : nullptr; io.c_out = fc.cstate + (long)k * f.B * f.H; }
+  io.gic = fc.gic + (long)k * f.B * f.G;
+  fwd_chain_cell<NG, X3>(f, io, bt * MB, k > 0 ? prog + (k - 1) * nbt + bt : nullptr, fc.pipe + 1, last ? nullptr : prog + k * nbt + bt,
+                         &s_ok, k > 0 ? (((k - 1) & 1) ? fc.qa : fc.qb) : nullptr, (k & 1) ? fc.qa : fc.qb, last ? fc.nll : nullptr);
+  if (last && ld_agent(fc.pipe + 1) != 0u) {   // an abandoned chain must not pass for a likelihood
+    const int row = bt * MB + (int)(threadIdx.x >> 5);
+    if (row < f.B) {
+      if (fc.z)
+        for (int c = threadIdx.x & 31; c < f.C; c += 32) fc.z[(long)row * f.C + c] = __builtin_nanf("");
+      if ((threadIdx.x & 31) == 0) fc.nll[row] = __builtin_nanf("");   // (the thread that wrote the row's word in F4, if the cell got that far)
+    }
+  }
+}
+
 // SeqGlow.invert (glow/models.py:617-645): the teacher-forced reverse pass over ALL timesteps in ONE launch - the reverse twin of the
 // persistent forward walk. Workgroup (k, tile), ids by ticket with k descending, walks n = 0 .. N-1: it waits for step k + 1's tile
 // of timestep n (the latent z_n for k = Ks - 1), runs the reverse cell with its recurrent state carried in h / cstate (its own
@@ -3509,6 +3838,7 @@ typedef void (*FlowPipeKernel)(FlowK);
 typedef void (*FlowStepKernel)(FlowK, CellIO);
 typedef void (*FlowRevWalkKernel)(FlowK, RevWalk);
 typedef void (*FlowRevChainKernel)(FlowK, RevChain);
+typedef void (*FlowFwdChainKernel)(FlowK, FwdChain);
 
 FlowDiagKernel flow_diag_fwd_pick(bool fast, bool lstm) {
   if (!fast) return flow_diag_fwd_kernel;
@@ -3539,6 +3869,10 @@ FlowRevChainKernel flow_rev_chain_pick_(bool lstm, bool x3, bool xw) {
 }
 FlowRevChainKernel flow_rev_chain_pick(bool lstm, bool x3, bool xw, bool nll) {
   return nll ? flow_rev_chain_pick_<true>(lstm, x3, xw) : flow_rev_chain_pick_<false>(lstm, x3, xw);
+}
+FlowFwdChainKernel flow_fwd_chain_pick(bool lstm, bool x3) {
+  if (lstm) return flow_fwd_chain_kernel<4, false>;
+  return x3 ? flow_fwd_chain_kernel<3, true> : flow_fwd_chain_kernel<3, false>;
 }
 
 // start state of a persistent walk: header and progress words cleared (LFI_PIPE_FORCE_ABORT=1: the abort word already set)
@@ -4028,6 +4362,117 @@ extern "C" int lfi_flow_sample_seq_from(const lfi_flow_dims* d, const lfi_flow_p
                                  p1, p1work, work, nullptr, nullptr, stream);
 }
 
+// The per-frame conditioning front end of the sampler (lfi_flow_sample_seq_nll) and of the teacher-forced scorer
+// (lfi_flow_score_seq_from): the carve of `work`, which form the window part of cond_transform + gic takes, and its launches for one
+// frame. Both callers run the same launches of the same kernels for a frame.
+namespace {
+struct SampleFront {
+  const lfi_flow_dims* d; const lfi_flow_params* p; const FlowK* f;
+  const float* wct; long E; int hist1; float* faces; int seq_len;
+  const lfi_p1enc* p1; float* p1work; int p1kind, p1col;
+  float *gic, *xa, *xb, *wstage;   // [Ks][B][G]; the chain's B x C ping / pong tiles; the aligned copy of the raw window
+  unsigned* chain_state; size_t chain_words;
+  int ldw, K1;
+  bool stage_win, fused, chain;
+  void* cfrags;
+};
+// `chain`: a one-launch chain follows every frame's conditioning (the fused kernel then clears its ticket / progress words)
+int sample_front_setup(SampleFront* s, const lfi_flow_dims* d, const lfi_flow_params* p, const FlowK* f, const float* wct, long E, int hist1,
+                       const float* pre_static, float* faces, int seq_len, const lfi_p1enc* p1, float* p1work, float* work, bool chain,
+                       int nframes, void* stream, const char* who) {
+  s->d = d; s->p = p; s->f = f; s->wct = wct; s->E = E; s->hist1 = hist1; s->faces = faces; s->seq_len = seq_len;
+  s->p1 = p1; s->p1work = p1work; s->chain = chain;
+  s->p1kind = p1 ? p1->kind : 0;
+  LFI_REQUIRE(s->p1kind >= 0 && s->p1kind <= 3, "%s: bad p1_face encoder kind %d", who, s->p1kind);
+  LFI_REQUIRE(s->p1kind == 0 || (p1work && p1->hid > 0), "%s: encoded p1_face window needs p1work", who);
+  s->p1col = p1 ? p1->col : 0;
+  const int B = f->B, C = f->C, D = f->D, Ks = f->Ks, G = f->G;
+  s->gic = work + (long)B * Ks * D;        // [Ks][B][G]   (the first B x Ks*D floats: round 2's copy of c, unused now)
+  s->xa = s->gic + (long)Ks * B * G;       // B x C ping
+  s->xb = s->xa + (long)B * C;             // B x C pong
+  s->chain_state = reinterpret_cast<unsigned*>((reinterpret_cast<uintptr_t>(s->xb + (long)B * C) + 15) & ~(uintptr_t)15);
+  s->chain_words = (size_t)(((long)PIPE_HDR + (long)Ks * f->nbt + 3) & ~3L);
+  // raw prev_p1_face windows start (t - hist1) * C floats into a row: 16-byte aligned only on every other frame at C = 50,
+  // which sent half of the window products to the exact-f32 kernel (91 vs 35 us). A gather into an aligned buffer first.
+  s->wstage = reinterpret_cast<float*>(s->chain_state + s->chain_words);
+  s->ldw = (hist1 * C + 3) & ~3;
+  s->stage_win = s->p1kind == 0 && hist1 <= 64;
+  // raw window + fp16 pieces (precision 9) + final widths: cond_transform's window part and the coupling cell's input projection
+  // as ONE launch per frame, c never written (lfi_sample.hip); the weights' fragments are made here, once per call
+  s->K1 = hist1 * C;
+  s->fused = s->stage_win && (d->gemm_precision & 0xff) == 9 && lfi_internal_sample_cond_ok(D, G, s->K1) &&
+             (reinterpret_cast<uintptr_t>(pre_static) & 15) == 0;
+  s->cfrags = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(s->wstage + (long)B * 64 * ((C + 3) & ~3)) + 255) & ~(uintptr_t)255);
+  if (s->fused && nframes > 0) return lfi_internal_sample_cond_prepare(wct, E, s->p1col, s->K1, f->wc, Ks, G, s->cfrags, stream);
+  return LFI_OK;
+}
+// frame t of the sequence in `faces`: gic of all flow steps from the frame's rows `cfr` of pre_static (B x Ks D, overwritten) and the
+// window faces[:, t - hist1 : t]. have_xfrag: the window's fp16 fragments are already in cfrags (the previous frame's reverse chain)
+int sample_front_frame(const SampleFront& s, int t, float* cfr, int have_xfrag, void* stream) {
+  const lfi_flow_dims* d = s.d;
+  const lfi_p1enc* p1 = s.p1;
+  const int B = s.f->B, C = s.f->C, D = s.f->D, Ks = s.f->Ks, G = s.f->G, hist1 = s.hist1, seq_len = s.seq_len;
+  int rc;
+  // c = LeakyReLU(pre_static[n] + window @ Wct[:, :hist1*C]^T), IN PLACE: frame n's rows of pre_static are read by this product
+  // alone, so they are its pre-activation addend and its output at once (a 32 MB copy per frame into a separate c otherwise)
+  lfi_gemm_desc q = {};
+  q.batch = 1; q.M = B; q.N = Ks * D; q.K = hist1 * C;
+  q.A = s.faces + (long)(t - hist1) * C; q.lda = (long)seq_len * C; q.a_kcontig = 1;
+  q.B = s.wct + s.p1col; q.ldb = s.E; q.b_kcontig = 1;
+  q.C = cfr; q.ldc = (long)Ks * D; q.accumulate = 2; q.act = 1; q.slope = 0.01f; q.precision = d->gemm_precision;
+  if (s.p1kind != 0) {
+    // features of the window first: e (B x hid4), then c = LeakyReLU(pre_static + e Wct[:, col : col + hid]^T)
+    const int hid = p1->hid, hid4 = (hid + 3) & ~3;
+    float* ebuf = s.p1work;                       // B x hid4
+    if (s.p1kind == 1) {
+      lfi_gemm_desc m = {};
+      m.batch = 1; m.M = B; m.N = hid; m.K = hist1 * C;
+      m.A = q.A; m.lda = q.lda; m.a_kcontig = 1;
+      m.B = p1->w1; m.ldb = (long)hist1 * C; m.b_kcontig = 1;
+      m.C = ebuf; m.ldc = hid4; m.bias = p1->b1; m.act = 1; m.slope = 0.01f; m.precision = d->gemm_precision;
+      if ((rc = lfi_gemm_f32(&m, stream))) return rc;
+    } else {
+      // GRU / LSTM over the window: input projections of its hist1 frames (batched over the step), then the recurrence
+      const int ng = s.p1kind == 3 ? 4 : 3;
+      float* xp = ebuf + (long)B * hid4;          // [B][hist1][ng * hid]
+      float* ework = xp + (long)B * hist1 * ng * hid;
+      lfi_gemm_desc m = {};
+      m.batch = hist1; m.M = B; m.N = ng * hid; m.K = C;
+      m.A = q.A; m.lda = q.lda; m.a_kcontig = 1; m.strideA = C;
+      m.B = p1->w_ih; m.ldb = C; m.b_kcontig = 1;
+      m.C = xp; m.ldc = (long)hist1 * ng * hid; m.strideC = ng * hid; m.precision = d->gemm_precision;
+      if ((rc = lfi_gemm_f32(&m, stream))) return rc;
+      lfi_enc_desc ed = {};
+      ed.B = B; ed.T = hist1; ed.N = 1; ed.start = hist1 - 1; ed.hist = hist1; ed.hid = hid;
+      ed.ldcond = hid4; ed.col = 0; ed.precision = d->gemm_precision; ed.dup = 0; ed.lstm = s.p1kind == 3;
+      float* hs = ework + lfi_encode_windows_work_floats(&ed);   // unfused path / LSTM: state sequence
+      float* gst = s.p1kind == 3 ? hs + (long)hist1 * B * hid : nullptr;   // LSTM: gate + cell stash, 5 * hid per (step, row)
+      if ((rc = lfi_encode_windows_fwd(&ed, xp, p1->w_hh, p1->b_ih, p1->b_hh, nullptr, ebuf, gst, hs, ework, stream)))
+        return rc;
+    }
+    q.K = hid; q.A = ebuf; q.lda = hid4;
+  }
+  if (s.fused) {
+    // (its first workgroup also clears the chain's ticket / progress words for the launch that follows: no memset node per frame)
+    return lfi_internal_sample_cond(s.faces, (long)seq_len * C, (long)(t - hist1) * C, s.K1, B, Ks, G, cfr, s.p->b_ih, s.cfrags, s.gic, 0.01f,
+                                    (long)B * seq_len * C, s.chain ? s.chain_state : nullptr, (int)s.chain_words, have_xfrag, stream);
+  }
+  if (s.stage_win) {
+    if ((rc = lfi_gather_windows(s.faces, B, seq_len, C, 1, t, hist1, 0, nullptr, s.wstage, s.ldw, 0, stream))) return rc;
+    q.A = s.wstage; q.lda = s.ldw;
+  }
+  if ((rc = lfi_gemm_f32(&q, stream))) return rc;
+  // gic[k] = c[:, kD:(k+1)D] @ W_ih[k][:, Ch:]^T + b_ih[k]
+  lfi_gemm_desc r = {};
+  r.batch = Ks; r.M = B; r.N = G; r.K = D;
+  r.A = cfr; r.lda = (long)Ks * D; r.a_kcontig = 1; r.strideA = D;
+  r.B = s.f->wc; r.ldb = D; r.b_kcontig = 1; r.strideB = (long)G * D;
+  r.C = s.gic; r.ldc = G; r.strideC = (long)B * G;
+  r.bias = s.p->b_ih; r.strideBias = G; r.precision = d->gemm_precision;
+  return lfi_gemm_f32(&r, stream);
+}
+}  // namespace
+
 // The per-step launches' finish of a frame's NLL (LFI_SAMPLE_CHAIN=0 and the generic cell; the chain kernel does this in its cells):
 // acc[b] = sum over the flow steps of the reverse coupling log-dets, left there by the cells' l_out.
 __global__ __launch_bounds__(256) void sample_nll_finish_kernel(const float* __restrict__ noise, const float* __restrict__ acc,
@@ -4063,14 +4508,7 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
   LFI_REQUIRE((long)hist1 * d->C <= E, "lfi_flow_sample_seq: window wider than the feature vector");
   LFI_REQUIRE(!d->lstm || cstate, "lfi_flow_sample_seq: the LSTM cell needs cstate");
   LFI_REQUIRE(!nll || nll_work, "lfi_flow_sample_seq_nll: nll needs nll_work (lfi_flow_sample_nll_work_floats)");
-  const int p1kind = p1 ? p1->kind : 0;
-  LFI_REQUIRE(p1kind >= 0 && p1kind <= 3, "lfi_flow_sample_seq: bad p1_face encoder kind %d", p1kind);
-  LFI_REQUIRE(p1kind == 0 || (p1work && p1->hid > 0), "lfi_flow_sample_seq: encoded p1_face window needs p1work");
-  const int p1col = p1 ? p1->col : 0;
-  const int B = f.B, C = f.C, H = f.H, D = f.D, Ks = f.Ks, G = f.G;
-  float* gic = work + (long)B * Ks * D;        // [Ks][B][G]   (the first B x Ks*D floats: round 2's copy of c, unused now)
-  float* xa = gic + (long)Ks * B * G;          // B x C ping
-  float* xb = xa + (long)B * C;                // B x C pong
+  const int B = f.B, C = f.C, H = f.H, D = f.D, Ks = f.Ks;
   hipStream_t st = (hipStream_t)stream;
   const bool fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
   const Carve cv = carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout);
@@ -4080,22 +4518,16 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
   // LFI_SAMPLE_CHAIN=0 keeps one launch per flow step
   const bool chain = fast && lfi_env_on("LFI_SAMPLE_CHAIN");
   const bool x3 = flow_x3_rev_cell(d, f);
-  unsigned* chain_state = reinterpret_cast<unsigned*>((reinterpret_cast<uintptr_t>(xb + (long)B * C) + 15) & ~(uintptr_t)15);
-  const size_t chain_words = (size_t)(((long)PIPE_HDR + (long)Ks * f.nbt + 3) & ~3L);
-  // raw prev_p1_face windows start (t - hist1) * C floats into a row: 16-byte aligned only on every other frame at C = 50,
-  // which sent half of the window products to the exact-f32 kernel (91 vs 35 us). A gather into an aligned buffer first.
-  float* wstage = reinterpret_cast<float*>(chain_state + chain_words);
-  const int ldw = (hist1 * C + 3) & ~3;
-  const bool stage_win = p1kind == 0 && hist1 <= 64;
-  // raw window + fp16 pieces (precision 9) + final widths: cond_transform's window part and the coupling cell's input projection
-  // as ONE launch per frame, c never written (lfi_sample.hip); the weights' fragments are made here, once per call
-  const int K1 = hist1 * C;
-  const bool fused = stage_win && (d->gemm_precision & 0xff) == 9 && lfi_internal_sample_cond_ok(D, G, K1) &&
-                     (reinterpret_cast<uintptr_t>(pre_static) & 15) == 0;
-  void* cfrags = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(wstage + (long)B * 64 * ((C + 3) & ~3)) + 255) & ~(uintptr_t)255);
-  if (fused && nframes > 0) {
-    if ((rc = lfi_internal_sample_cond_prepare(wct, E, p1col, K1, f.wc, Ks, G, cfrags, stream))) return rc;
-  }
+  // the per-frame conditioning (sample_front_*): the carve of `work`, the fused kernel's weight fragments once per call
+  SampleFront sf = {};
+  if ((rc = sample_front_setup(&sf, d, p, &f, wct, E, hist1, pre_static, faces, seq_len, p1, p1work, work, chain, nframes, stream,
+                               "lfi_flow_sample_seq"))) return rc;
+  float *gic = sf.gic, *xa = sf.xa, *xb = sf.xb;
+  unsigned* chain_state = sf.chain_state;
+  const size_t chain_words = sf.chain_words;
+  const bool fused = sf.fused;
+  void* cfrags = sf.cfrags;
+  const int K1 = sf.K1, G = f.G;
   // LFI_SAMPLE_XF_CHAIN=0 keeps the window-fragment kernel in front of every frame's conditioning
   const bool xf_chain = fused && chain && lfi_env_on("LFI_SAMPLE_XF_CHAIN");
   // the reverse cells' weights as the fp16 fragment images lfi_flow_prep left (no split in every workgroup of every frame; x3 is true
@@ -4106,68 +4538,8 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
   if (chain && (rc = set_flow_lds(chain_kernel, lds, nll ? "lfi_flow_sample_seq_nll" : "lfi_flow_sample_seq"))) return rc;
   for (int n = 0; n < nframes; ++n) {
     const int t = start + n;
-    // c = LeakyReLU(pre_static[n] + window @ Wct[:, :hist1*C]^T), IN PLACE: frame n's rows of pre_static are read by this product
-    // alone, so they are its pre-activation addend and its output at once (a 32 MB copy per frame into a separate c otherwise)
-    float* cfr = pre_static + (long)n * B * Ks * D;
-    lfi_gemm_desc q = {};
-    q.batch = 1; q.M = B; q.N = Ks * D; q.K = hist1 * C;
-    q.A = faces + (long)(t - hist1) * C; q.lda = (long)seq_len * C; q.a_kcontig = 1;
-    q.B = wct + p1col; q.ldb = E; q.b_kcontig = 1;
-    q.C = cfr; q.ldc = (long)Ks * D; q.accumulate = 2; q.act = 1; q.slope = 0.01f; q.precision = d->gemm_precision;
-    if (p1kind != 0) {
-      // features of the window first: e (B x hid4), then c = LeakyReLU(pre_static + e Wct[:, col : col + hid]^T)
-      const int hid = p1->hid, hid4 = (hid + 3) & ~3;
-      float* ebuf = p1work;                       // B x hid4
-      if (p1kind == 1) {
-        lfi_gemm_desc m = {};
-        m.batch = 1; m.M = B; m.N = hid; m.K = hist1 * C;
-        m.A = q.A; m.lda = q.lda; m.a_kcontig = 1;
-        m.B = p1->w1; m.ldb = (long)hist1 * C; m.b_kcontig = 1;
-        m.C = ebuf; m.ldc = hid4; m.bias = p1->b1; m.act = 1; m.slope = 0.01f; m.precision = d->gemm_precision;
-        if ((rc = lfi_gemm_f32(&m, stream))) return rc;
-      } else {
-        // GRU / LSTM over the window: input projections of its hist1 frames (batched over the step), then the recurrence
-        const int ng = p1kind == 3 ? 4 : 3;
-        float* xp = ebuf + (long)B * hid4;          // [B][hist1][ng * hid]
-        float* ework = xp + (long)B * hist1 * ng * hid;
-        lfi_gemm_desc m = {};
-        m.batch = hist1; m.M = B; m.N = ng * hid; m.K = C;
-        m.A = q.A; m.lda = q.lda; m.a_kcontig = 1; m.strideA = C;
-        m.B = p1->w_ih; m.ldb = C; m.b_kcontig = 1;
-        m.C = xp; m.ldc = (long)hist1 * ng * hid; m.strideC = ng * hid; m.precision = d->gemm_precision;
-        if ((rc = lfi_gemm_f32(&m, stream))) return rc;
-        lfi_enc_desc ed = {};
-        ed.B = B; ed.T = hist1; ed.N = 1; ed.start = hist1 - 1; ed.hist = hist1; ed.hid = hid;
-        ed.ldcond = hid4; ed.col = 0; ed.precision = d->gemm_precision; ed.dup = 0; ed.lstm = p1kind == 3;
-        float* hs = ework + lfi_encode_windows_work_floats(&ed);   // unfused path / LSTM: state sequence
-        float* gst = p1kind == 3 ? hs + (long)hist1 * B * hid : nullptr;   // LSTM: gate + cell stash, 5 * hid per (step, row)
-        if ((rc = lfi_encode_windows_fwd(&ed, xp, p1->w_hh, p1->b_ih, p1->b_hh, nullptr, ebuf, gst, hs, ework, stream)))
-          return rc;
-      }
-      q.K = hid; q.A = ebuf; q.lda = hid4;
-    }
-    if (fused) {
-      // (its first workgroup also clears the reverse chain's ticket / progress words for the launch below: no memset node per frame)
-      // (from the run's second frame on the window's fragments are already there: the previous frame's chain left them)
-      if ((rc = lfi_internal_sample_cond(faces, (long)seq_len * C, (long)(t - hist1) * C, K1, B, Ks, G, cfr, p->b_ih, cfrags, gic, 0.01f,
-                                         (long)B * seq_len * C, chain ? chain_state : nullptr, (int)chain_words,
-                                         (xf_chain && n > 0) ? 1 : 0, stream)))
-        return rc;
-    } else {
-      if (stage_win) {
-        if ((rc = lfi_gather_windows(faces, B, seq_len, C, 1, t, hist1, 0, nullptr, wstage, ldw, 0, stream))) return rc;
-        q.A = wstage; q.lda = ldw;
-      }
-      if ((rc = lfi_gemm_f32(&q, stream))) return rc;
-      // gic[k] = c[:, kD:(k+1)D] @ W_ih[k][:, Ch:]^T + b_ih[k]
-      lfi_gemm_desc r = {};
-      r.batch = Ks; r.M = B; r.N = G; r.K = D;
-      r.A = cfr; r.lda = (long)Ks * D; r.a_kcontig = 1; r.strideA = D;
-      r.B = f.wc; r.ldb = D; r.b_kcontig = 1; r.strideB = (long)G * D;
-      r.C = gic; r.ldc = G; r.strideC = (long)B * G;
-      r.bias = p->b_ih; r.strideBias = G; r.precision = d->gemm_precision;
-      if ((rc = lfi_gemm_f32(&r, stream))) return rc;
-    }
+    // (from the run's second frame on the window's fragments are already there: the previous frame's chain left them)
+    if ((rc = sample_front_frame(sf, t, pre_static + (long)n * B * Ks * D, (xf_chain && n > 0) ? 1 : 0, stream))) return rc;
     // reverse flow: z -> x through steps Ks-1 .. 0
     if (chain) {   // one launch for the whole chain of this frame
       RevChain rcn = {};
@@ -4206,6 +4578,97 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
                          f.ldconst, B, C, nll + (long)n * B);
   }
   LFI_LAUNCH_CHECK("lfi_flow_sample_seq");
+  return LFI_OK;
+}
+
+// ---- teacher-forced frames of a sequence whose state is carried (SampleStream.observe): the sampler's front end, then the FORWARD chain
+// The per-step launches' finish of an observed frame (LFI_SAMPLE_CHAIN=0 and the generic cell; the forward chain does this in its
+// last cell): acc[b] = sum over the flow steps of the forward coupling log-dets (the cells' l_out), zlast = the last step's tile.
+__global__ __launch_bounds__(256) void score_finish_kernel(const float* __restrict__ zlast, const float* __restrict__ acc,
+                                                           const float* __restrict__ ldconst, int B, int C, float* __restrict__ z,
+                                                           float* __restrict__ nll) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  float lp = 0.0f;
+  for (int c = 0; c < C; ++c) {
+    const float v = zlast[(long)b * C + c];
+    lp += -0.5f * (v * v + LOG2PI_F);
+    if (z) z[(long)b * C + c] = v;
+  }
+  nll[b] = -(ldconst[0] + acc[b] + lp) / LN2_F;
+}
+
+extern "C" long lfi_flow_score_work_floats(const lfi_flow_dims* d) {
+  if (!d) return 0;
+  return 2L * d->B + 8;   // the two ping-pong log-det hand-over arrays of the forward chain (the first: the per-step launches' accumulator)
+}
+
+extern "C" int lfi_flow_score_seq_from(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct, long E,
+                                       int hist1, float* pre_static, float* faces, int seq_len, int start, int nframes, int first_frame,
+                                       float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work, float* score_work,
+                                       float* z, float* nll, void* stream) {
+  FlowK f = {};
+  int rc = fill_flow(d, p, prep, &f, "lfi_flow_score_seq_from");
+  if (rc) return rc;
+  LFI_REQUIRE(first_frame >= 0, "lfi_flow_score_seq_from: negative first_frame");
+  LFI_REQUIRE(prep && wct && pre_static && faces && h && work && score_work && nll, "lfi_flow_score_seq_from: null pointer");
+  LFI_REQUIRE(hist1 >= 0 && hist1 <= start && nframes >= 0 && start + nframes <= seq_len, "lfi_flow_score_seq_from: bad frame range");
+  LFI_REQUIRE((long)hist1 * d->C <= E, "lfi_flow_score_seq_from: window wider than the feature vector");
+  LFI_REQUIRE(!d->lstm || cstate, "lfi_flow_score_seq_from: the LSTM cell needs cstate");
+  const int B = f.B, C = f.C, H = f.H, D = f.D, Ks = f.Ks, G = f.G;
+  hipStream_t st = (hipStream_t)stream;
+  // the register-resident chain for the shapes the sampler's chain takes; otherwise (and with LFI_SAMPLE_CHAIN=0) Ks launches of the
+  // streaming forward cell + the finish
+  const bool chain = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic() && lfi_env_on("LFI_SAMPLE_CHAIN");
+  // three fp16 products for per-frame arithmetic 9 only. The reverse cells keep them at 5 as well - their operands are bounded (the
+  // prior draw, h in (-1, 1)) - but this chain's first operand is actnorm of a frame the CALLER supplies: a value beyond fp16's range
+  // would turn into inf - inf = NaN in the split and stay in h / c. 5 is the arithmetic a session falls back to when its range guard
+  // trips and must have no range caveat: it takes the exact-f32 cell (as 0 and the LSTM cell do), which is at least as accurate as
+  // six bf16 products.
+  const bool x3 = flow_x3_rev_cell(d, f) && (d->gemm_precision & 0xff) == 9;
+  const size_t lds = (size_t)(chain ? carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total : carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout).total) *
+                     sizeof(float);
+  const FlowFwdChainKernel chain_kernel = flow_fwd_chain_pick(f.lstm, x3);
+  if ((rc = chain ? set_flow_lds(chain_kernel, lds, "lfi_flow_score_seq_from") : set_flow_lds(flow_step_kernel<false>, lds, "lfi_flow_score_seq_from")))
+    return rc;
+  SampleFront sf = {};
+  if ((rc = sample_front_setup(&sf, d, p, &f, wct, E, hist1, pre_static, faces, seq_len, p1, p1work, work, chain, nframes, stream,
+                               "lfi_flow_score_seq_from"))) return rc;
+  float *qa = score_work, *qb = score_work + B;
+  for (int n = 0; n < nframes; ++n) {
+    const int t = start + n;
+    if ((rc = sample_front_frame(sf, t, pre_static + (long)n * B * Ks * D, 0, stream))) return rc;
+    float* zn = z ? z + (long)n * B * C : nullptr;
+    const int has_prev = first_frame + n > 0 ? 1 : 0;
+    if (chain) {
+      FwdChain fc = {};
+      fc.frame = faces + (long)t * C; fc.ld_frame = (long)seq_len * C;
+      fc.xa = sf.xa; fc.xb = sf.xb; fc.gic = sf.gic; fc.h = h; fc.cstate = cstate; fc.has_prev = has_prev; fc.pipe = sf.chain_state;
+      fc.qa = qa; fc.qb = qb; fc.z = zn; fc.nll = nll + (long)n * B;
+      if (!sf.fused) {   // (the fused conditioning kernel has cleared them)
+        hipError_t me = hipMemsetAsync(sf.chain_state, 0, sf.chain_words * sizeof(unsigned), st);
+        LFI_REQUIRE(me == hipSuccess, "lfi_flow_score_seq_from: hipMemsetAsync: %s", hipGetErrorString(me));
+      }
+      hipLaunchKernelGGL(chain_kernel, dim3(Ks * f.nbt), dim3(NT), lds, st, f, fc);
+      continue;
+    }
+    const float* xin = faces + (long)t * C;
+    long ldx = (long)seq_len * C;
+    for (int k = 0; k < Ks; ++k) {
+      CellIO io = {};
+      io.k = k; io.rows = B; io.x_in = xin; io.ldx = ldx;
+      io.h_prev = has_prev ? h + (long)k * B * H : nullptr;
+      io.gic = sf.gic + (long)k * B * G;
+      io.h_out = h + (long)k * B * H;
+      if (f.lstm) { io.c_prev = has_prev ? cstate + (long)k * B * H : nullptr; io.c_out = cstate + (long)k * B * H; }
+      io.x_out = (k & 1) ? sf.xa : sf.xb; io.ldxo = C;
+      io.l_out = qa; io.l_accumulate = k > 0;   // (launch after launch: no two workgroups at one word at a time)
+      hipLaunchKernelGGL(flow_step_kernel<false>, dim3(f.nbt), dim3(NT), lds, st, f, io);
+      xin = io.x_out; ldx = C;
+    }
+    hipLaunchKernelGGL(score_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, xin, qa, f.ldconst, B, C, zn, nll + (long)n * B);
+  }
+  LFI_LAUNCH_CHECK("lfi_flow_score_seq_from");
   return LFI_OK;
 }
 

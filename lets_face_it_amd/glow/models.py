@@ -561,7 +561,15 @@ class SeqGlow(nn.Module):
         draw the step used, not a density of the tempered sampling distribution. It is an output of a step, not state: the row
         record and reset_rows / save_rows / load_rows are unchanged, and a row reseeded or loaded between steps reports the NLL of
         its own next frame. Best-of-N: load one saved entry into n rows, step, nll.argmin() over them, save_rows([best]) and
-        load_rows it back over the others."""
+        load_rows it back over the others.
+
+        observe(frame, face, return_z=False) is the teacher-forced step: frame t of p1_face is given (face: (B, C) float32 GPU
+        tensor) instead of sampled. -> nll (B,), the frame's NLL in bits as forward() reports it (last_missmatched_nll live, O(1)
+        per frame), or (nll, z). The frame enters the faces window and the coupling cells' h / c move on as a generated frame's do
+        (forward and reverse flow steps feed the recurrent cell the same input), so step() and observe() alternate freely, with
+        return_nll on or off: warm a session up on real history before generating, score faces live, hand over in both directions;
+        warm-up beside a batched server: observe in a small session, save_rows, load_rows into the serving one. `steps` counts
+        both kinds of step."""
         _engine.check_return_nll(return_nll)
         p1 = seed.get("p1_face") if isinstance(seed, dict) else None
         if p1 is None:

@@ -5,6 +5,7 @@ product, the per-frame arithmetic and its range limit, the guard word, the strea
 import collections
 import contextlib
 import ctypes as C
+import functools
 import operator
 import os
 import warnings
@@ -148,7 +149,9 @@ class SampleStream:
         self.precision = eng.precision          # GEMM arithmetic of the static part, fixed at the open
         self.steps = 0                          # frames generated since the open / the last reset()
         self.replays = 0                        # steps that were graph replays
-        self._graph, self._graph_key = None, None
+        self._graph, self._graph_key = None, None                    # step()'s captured graph and what it was captured for
+        self._observe_graphs = {}                                    # observe()'s own, by key
+        self.score_work = self.obs_z = self.obs_nll = None   # observe()'s buffers: allocated at the first observe
         self._stream = None
         self._guard_pending = None
         self._state = {"_ws": {}, "prep": None, "wct_f": torch.zeros_like(eng.wct_f), "_wct_planes": None, "_wc_r": None,
@@ -360,10 +363,10 @@ class SampleStream:
         if self._stream is not None:
             self._stream.synchronize()
         self.closed = True
-        self._graph = None
+        self._graph, self._observe_graphs = None, {}
         self._state = None
         self.faces = self.noise = self.windows = self.cond = self.pre = self.h = self.cs = self.work = self.p1work = self._wins = None
-        self.nll = self.nll_work = None
+        self.nll = self.nll_work = self.score_work = self.obs_z = self.obs_nll = None
 
     def __enter__(self):
         return self
@@ -372,13 +375,8 @@ class SampleStream:
         self.close()
         return False
 
-    @translate_oom
-    def step(self, frame, noise=None):
-        """frame: {modality: (B, dim)} = frame t of every modality with history > 0 (extra keys are ignored). noise: (B, C) prior
-        draw already * eps, or None (drawn with the session's eps). -> generated p1_face frame t, (B, C); a session opened with
-        return_nll=True -> (frame, nll), nll (B,) float32: the frame's NLL in bits (see the class)."""
-        s, eng, B = self.eng.spec, self.eng, self.B
-        self._check_usable()
+    def _check_frame(self, frame):
+        """The conditioning argument of step() / observe(), checked before any launch -> the new frames in the order of self.mods."""
         if not isinstance(frame, dict):
             raise TypeError("frame must be a dict {modality: (B, dim) tensor}")
         srcs = []
@@ -386,72 +384,136 @@ class SampleStream:
             x = frame.get(e.name)
             if x is None:
                 raise KeyError("batch is missing modality %r" % e.name)
-            self._check_matrix(x, e.name, e.in_dim, B)
+            self._check_matrix(x, e.name, e.in_dim, self.B)
             srcs.append(x)
+        return srcs
+
+    @translate_oom
+    def step(self, frame, noise=None):
+        """frame: {modality: (B, dim)} = frame t of every modality with history > 0 (extra keys are ignored). noise: (B, C) prior
+        draw already * eps, or None (drawn with the session's eps). -> generated p1_face frame t, (B, C); a session opened with
+        return_nll=True -> (frame, nll), nll (B,) float32: the frame's NLL in bits (see the class)."""
+        s = self.eng.spec
+        self._check_usable()
+        srcs = self._check_frame(frame)
         if noise is not None:
-            self._check_matrix(noise, "noise", s.C, B)
+            self._check_matrix(noise, "noise", s.C, self.B)
         with self._owned():
             self._check_guard()
             if noise is None:
-                noise = self._noise_fn(B, s.C).contiguous()
-            masks = None
-            drawn = self._masks_fn(B, 1) if self._masks_fn is not None else None
-            eng.precision = self.precision      # (the module's mask draw re-applies its own mode to the engine)
-            if drawn:
-                masks = {}
-                for name, buf in self.mask_bufs.items():
-                    m = drawn.get(name)
-                    if m is None:
-                        continue
-                    if m.dim() != 3 or tuple(m.shape[1:]) != (B, buf.shape[2]):
-                        raise ValueError("mask for %s must be (N, B, hist) = (., %d, %d), got %s" % (name, B, buf.shape[2], tuple(m.shape)))
-                    if m.shape[0] != 1 and self.steps >= m.shape[0]:
-                        raise ValueError("mask for %s holds %d frames; this is frame %d of the stream" % (name, m.shape[0], self.steps))
-                    buf.copy_(m[0 if m.shape[0] == 1 else self.steps].unsqueeze(0))
-                    masks[name] = buf
-            for i, x in enumerate(srcs):
-                self._src_p[i] = x.data_ptr()
-            ev = eng._tic("stream_advance")
-            check(eng.L.lfi_stream_advance(B, len(self._row_win), self._row_win, self._src_p, self._row_hist, self._row_dim,
-                                           noise.data_ptr(), self.noise.data_ptr(), s.C, ptr(self.frame_nb), self.guard.data_ptr(),
-                                           _stream()), "lfi_stream_advance")
-            eng._toc("stream_advance", ev)
-            self._pinned.copy_(self.guard, non_blocking=True)
-            gev = torch.cuda.Event()
-            gev.record()
-            self._guard_pending = gev
-            for x in srcs + [noise]:
-                x.record_stream(torch.cuda.current_stream(self.device))
-            if self.steps == 0 or os.environ.get("LFI_NO_GRAPH") == "1":
-                self._launch(masks, 1 if self.steps > 0 or self._resumed else 0)
-            else:
-                key = (self.frame_precision, masks is not None)
-                if self._graph is None or self._graph_key != key:
-                    timers, eng.timers = eng.timers, None
-                    try:
-                        torch.cuda.synchronize()
-                        g = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(g):
-                            self._launch(masks, 1)
-                    finally:
-                        eng.timers = timers
-                    self._graph, self._graph_key = g, key
-                ev = eng._tic("stream_graph")
-                self._graph.replay()
-                eng._toc("stream_graph", ev)
-                self.replays += 1
+                noise = self._noise_fn(self.B, s.C).contiguous()
+            self._advance(srcs, noise, None)
             out = self.faces[:, self.hist1].clone()
             nll = self.nll.clone() if self.return_nll else None
             self.steps += 1
-        if out.device == self.device and self._stream is not None:
-            out.record_stream(torch.cuda.current_stream(self.device))
-            if nll is not None:
-                nll.record_stream(torch.cuda.current_stream(self.device))
+        self._record_out(out, nll)
         return (out, nll) if self.return_nll else out
 
-    def _launch(self, masks, first_frame):
-        """The static part for the session's B windows, then the reverse chain for one frame: session-owned memory only."""
-        eng, s, B = self.eng, self.eng.spec, self.B
+    @translate_oom
+    def observe(self, frame, face, return_z=False):
+        """A teacher-forced step: frame t of p1_face is GIVEN (recorded, puppeteered, rendered by another system) instead of sampled.
+        frame: as step()'s; face: (B, C) float32 GPU tensor, the observed p1_face frame t. -> nll (B,) float32, the frame's NLL in
+        bits under the model - what forward() reports for it - or (nll, z) with return_z, z (B, C) its latent. The frame enters the
+        session's faces window and the recurrent state h / c moves on exactly as a generated frame's does (the coupling cells see the
+        pass-through half and the conditioning, the same in both directions), so step() and observe() alternate freely: warm a
+        session up on real history, score faces live, hand over in either direction. Works whether return_nll is on or off.
+
+        Per call: lfi_stream_advance with the observed frame as the faces window's source (it passes the range guard there), the
+        static part as a step's, then lfi_flow_score_seq_from for one frame: the sampler's conditioning front end and ALL forward
+        flow steps in one launch. From the second call on, one captured hipGraph of its own, keyed as the step graph is (and on return_z: the latent is
+        written only when asked for). No host wait
+        in steady state. `steps` counts both kinds of step."""
+        s = self.eng.spec
+        self._check_usable()
+        if not isinstance(return_z, bool):
+            raise TypeError("return_z: expected a bool, got %s %r" % (type(return_z).__name__, return_z))
+        srcs = self._check_frame(frame)
+        self._check_matrix(face, "face", s.C, self.B)
+        with self._owned():
+            self._check_guard()
+            if self.obs_nll is None:     # the observe buffers: at the first observe, outside capture
+                eng, dims = self.eng, self.eng._flow_dims(self.B, 1)
+                self.score_work = eng._buf("stream_score_work", eng.L.lfi_flow_score_work_floats(C.byref(dims)))
+                self.obs_z = eng._buf("stream_obs_z", self.B * s.C)[:self.B * s.C].view(self.B, s.C)
+                self.obs_nll = eng._buf("stream_obs_nll", self.B)[:self.B]
+            self._advance(srcs, None, face, return_z)
+            nll = self.obs_nll.clone()
+            z = self.obs_z.clone() if return_z else None
+            self.steps += 1
+        self._record_out(nll, z)
+        return (nll, z) if return_z else nll
+
+    def _record_out(self, *outs):
+        if self._stream is not None:
+            for x in outs:
+                if x is not None and x.device == self.device:
+                    x.record_stream(torch.cuda.current_stream(self.device))
+
+    def _advance(self, srcs, noise, face, want_z=False):
+        """One frame forward, inside _owned(): masks, lfi_stream_advance, the guard's copy, then the launch or the replay. face None: a
+        generating step with the prior draw `noise`; else an observing one - the frame is the faces window's source (and fills the
+        noise slot, which an observing step does not read); want_z: the observing launch also writes the frame's latent."""
+        s, eng, B = self.eng.spec, self.eng, self.B
+        observe = face is not None
+        masks = None
+        drawn = self._masks_fn(B, 1) if self._masks_fn is not None else None
+        eng.precision = self.precision      # (the module's mask draw re-applies its own mode to the engine)
+        if drawn:
+            masks = {}
+            for name, buf in self.mask_bufs.items():
+                m = drawn.get(name)
+                if m is None:
+                    continue
+                if m.dim() != 3 or tuple(m.shape[1:]) != (B, buf.shape[2]):
+                    raise ValueError("mask for %s must be (N, B, hist) = (., %d, %d), got %s" % (name, B, buf.shape[2], tuple(m.shape)))
+                if m.shape[0] != 1 and self.steps >= m.shape[0]:
+                    raise ValueError("mask for %s holds %d frames; this is frame %d of the stream" % (name, m.shape[0], self.steps))
+                buf.copy_(m[0 if m.shape[0] == 1 else self.steps].unsqueeze(0))
+                masks[name] = buf
+        for i, x in enumerate(srcs):
+            self._src_p[i] = x.data_ptr()
+        self._src_p[len(srcs)] = face.data_ptr() if observe else None
+        moved = face if observe else noise
+        ev = eng._tic("stream_advance")
+        check(eng.L.lfi_stream_advance(B, len(self._row_win), self._row_win, self._src_p, self._row_hist, self._row_dim,
+                                       moved.data_ptr(), self.noise.data_ptr(), s.C, ptr(self.frame_nb), self.guard.data_ptr(),
+                                       _stream()), "lfi_stream_advance")
+        eng._toc("stream_advance", ev)
+        self._pinned.copy_(self.guard, non_blocking=True)
+        gev = torch.cuda.Event()
+        gev.record()
+        self._guard_pending = gev
+        for x in srcs + [moved]:
+            x.record_stream(torch.cuda.current_stream(self.device))
+        launch = functools.partial(self._launch_observe, want_z) if observe else self._launch
+        if self.steps == 0 or os.environ.get("LFI_NO_GRAPH") == "1":
+            launch(masks, 1 if self.steps > 0 or self._resumed else 0)
+            return
+        # a captured graph per kind of step, keyed on what its launches depend on. step(): one graph, recaptured when the key changes.
+        # observe(): one per key met (with and without z, per arithmetic) - alternating kinds or return_z recaptures nothing
+        key = (self.frame_precision, masks is not None) + ((want_z,) if observe else ())
+        g = self._observe_graphs.get(key) if observe else (self._graph if self._graph_key == key else None)
+        if g is None:
+            timers, eng.timers = eng.timers, None
+            try:
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    launch(masks, 1)
+            finally:
+                eng.timers = timers
+            if observe:
+                self._observe_graphs[key] = g
+            else:
+                self._graph, self._graph_key = g, key
+        ev = eng._tic("stream_graph")
+        g.replay()
+        eng._toc("stream_graph", ev)
+        self.replays += 1
+
+    def _static(self, masks):
+        """The static part for the session's B windows (window encoders + the static cond_transform columns): session-owned memory."""
+        eng, B = self.eng, self.B
         ev = eng._tic("stream_static")
         data = dict(self.windows)
         if self.frame_nb is not None:
@@ -462,7 +524,12 @@ class SampleStream:
         eng._toc("stream_static", ev)
         dims = eng._flow_dims(B, 1)
         dims.gemm_precision = self.frame_precision
-        p = eng._flow_params()
+        return dims, eng._flow_params()
+
+    def _launch(self, masks, first_frame):
+        """The static part, then the reverse chain for one frame: session-owned memory only."""
+        eng, s = self.eng, self.eng.spec
+        dims, p = self._static(masks)
         ev = eng._tic("stream_chain")
         if self.return_nll:
             check(eng.L.lfi_flow_sample_seq_nll(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
@@ -477,6 +544,19 @@ class SampleStream:
                                              self.hist1, 1, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
                                              self.p1work.data_ptr(), self.work.data_ptr(), _stream()), "lfi_flow_sample_seq_from")
         eng._toc("stream_chain", ev)
+
+    def _launch_observe(self, want_z, masks, first_frame):
+        """The static part, then the forward chain on the observed frame the faces window holds: session-owned memory only. The latent
+        is written only when it is wanted (z = NULL otherwise)."""
+        eng, s = self.eng, self.eng.spec
+        dims, p = self._static(masks)
+        ev = eng._tic("stream_observe_chain")
+        check(eng.L.lfi_flow_score_seq_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
+                                            self.pre.data_ptr(), self.faces.data_ptr(), self.hist1 + 1, self.hist1, 1, first_frame,
+                                            self.h.data_ptr(), ptr(self.cs), C.byref(self._p1), self.p1work.data_ptr(),
+                                            self.work.data_ptr(), self.score_work.data_ptr(), self.obs_z.data_ptr() if want_z else None,
+                                            self.obs_nll.data_ptr(), _stream()), "lfi_flow_score_seq_from")
+        eng._toc("stream_observe_chain", ev)
 
     def _check_guard(self):
         """The range guard of earlier steps (lfi_stream_advance folds max |x| of every value it moves into the session's guard word,

@@ -3,6 +3,7 @@ alternative without a session: re-running SeqGlow.inference over the whole prefi
 
   python tools/stream_latency.py [--batches 1,16,256] [--steps 200] [--warmup 20] [--prefixes 50,150,300] [--out FILE]
                                  [--churn 1,16,64 [--churn-batch 256]] [--migrate 16 [--migrate-batch 256]] [--nll 1,256]
+                                 [--observe 1,16,256]
 
 Per batch size: the wall-clock time from step() to the generated frame on the host (a synchronise after every step: what a live agent
 waits for), its GPU time (HIP events around the step), and a per-kernel breakdown from the engine's enable_timing on an eager session
@@ -21,7 +22,11 @@ and caller as --churn, interleaved step by step in one process: a plain step, sa
 
 --nll b1,b2,..: per batch size two sessions on the same seed, frames and noise, one opened with return_nll=True (every step also
 returns the frame's NLL) and one without, interleaved step by step in one process: what the likelihood costs a step. Then
-inference() over --nll-frames generated frames with and without return_nll, the two alternated call by call."""
+inference() over --nll-frames generated frames with and without return_nll, the two alternated call by call.
+
+--observe b1,b2,..: per batch size a generating session (step()) and a teacher-forced one (observe(), NLL only and with z) on the same
+seed and conditioning, interleaved step by step in one process, which goes first alternating; the observed faces are what an untimed
+generating session produced beforehand."""
 import argparse
 import contextlib
 import os
@@ -46,6 +51,7 @@ def main():
     ap.add_argument("--migrate-batch", type=int, default=256)
     ap.add_argument("--nll", default=None, help="batch sizes of the return_nll leg, e.g. 1,256 (default: no such leg)")
     ap.add_argument("--nll-frames", type=int, default=0, help="with --nll: also inference() over this many generated frames, flag off / on")
+    ap.add_argument("--observe", default=None, help="batch sizes of the observe() leg, e.g. 1,16,256 (default: no such leg)")
     a = ap.parse_args()
     import bench
     helper = bench.start_smi_helper()       # (before the GPU is initialised: see bench.py)
@@ -149,6 +155,9 @@ def main():
     nll = []
     if a.nll:
         nll = nll_leg(m, dev, [int(v) for v in a.nll.split(",")], a.steps, a.warmup, dims, start, C, a.nll_frames)
+    observe = []
+    if a.observe:
+        observe = observe_leg(m, dev, [int(v) for v in a.observe.split(",")], a.steps, a.warmup, dims, start, C)
     bench.stop_smi_helper(helper)
 
     lines += ["## One streaming step", "",
@@ -184,6 +193,11 @@ def main():
         lines += ["", "## Likelihood: a session opened with return_nll=True beside one without, step by step (--nll)", "",
                   "| B | leg | wall ms, median | wall ms, p90 | GPU ms, median (events) | GPU ms, p90 |", "|---|---|---|---|---|---|"]
         for B, leg, med, p90, gmed, gp90 in nll:
+            lines.append("| %d | %s | %.3f | %.3f | %.3f | %.3f |" % (B, leg, med, p90, gmed, gp90))
+    if observe:
+        lines += ["", "## Teacher-forced steps: observe() beside step(), session by session, step by step (--observe)", "",
+                  "| B | leg | wall ms, median | wall ms, p90 | GPU ms, median (events) | GPU ms, p90 |", "|---|---|---|---|---|---|"]
+        for B, leg, med, p90, gmed, gp90 in observe:
             lines.append("| %d | %s | %.3f | %.3f | %.3f | %.3f |" % (B, leg, med, p90, gmed, gp90))
     text = "\n".join(lines) + "\n"
     print(text)
@@ -288,6 +302,47 @@ def nll_leg(m, dev, batches, steps, warmup, dims, start, C, nframes=0):
                 for leg, flag in (list(calls.items()) if i % 2 == 0 else list(calls.items())[::-1]):
                     for j in range(3):
                         timed(lambda: m.inference(t, pd, noise=pn, return_nll=flag), *legs[leg], i >= 2 and j == 2)
+        for leg, (wall, gpu) in legs.items():
+            wall.sort()
+            gpu.sort()
+            out.append((B, leg, statistics.median(wall), wall[int(0.9 * (len(wall) - 1))], statistics.median(gpu),
+                        gpu[int(0.9 * (len(gpu) - 1))]))
+    return out
+
+
+def observe_leg(m, dev, batches, steps, warmup, dims, start, C):
+    """Per batch size: (B, leg, wall median, wall p90, GPU median, GPU p90) of step(), observe() and observe(return_z=True): three
+    sessions on one seed, interleaved step by step, the order rotating. The faces observed are those of an untimed generating
+    session run first with the same noise (so every session sees the same sequence)."""
+    import torch
+    out = []
+    total = warmup + steps
+    for B in batches:
+        gd = torch.Generator().manual_seed(B + 3)
+        data = {k: torch.randn(B, start + total, d, generator=gd).to(dev) for k, d in dims.items()}
+        seed = {k: v[:, :start].contiguous() for k, v in data.items()}
+        frames = [{k: v[:, start + n].contiguous() for k, v in data.items() if k != "p1_face"} for n in range(total)]
+        noise = (torch.randn(total, B, C, generator=gd) * 0.8).to(dev)
+        with m.open_stream(seed) as ref:
+            faces = [ref.step(frames[n], noise[n]) for n in range(total)]
+        with m.open_stream(seed) as gen, m.open_stream(seed) as obs, m.open_stream(seed) as obz:
+            calls = [("step", lambda n: gen.step(frames[n], noise[n])),
+                     ("observe", lambda n: obs.observe(frames[n], faces[n])),
+                     ("observe, return_z", lambda n: obz.observe(frames[n], faces[n], return_z=True))]
+            legs = {name: ([], []) for name, _ in calls}
+            for n in range(total):
+                for name, fn in calls[n % 3:] + calls[:n % 3]:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    e0.record()
+                    fn(n)
+                    e1.record()
+                    e1.synchronize()
+                    t1 = time.perf_counter()
+                    if n >= warmup:
+                        legs[name][0].append((t1 - t0) * 1e3)
+                        legs[name][1].append(e0.elapsed_time(e1))
         for leg, (wall, gpu) in legs.items():
             wall.sort()
             gpu.sort()
