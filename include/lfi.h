@@ -432,6 +432,22 @@ int lfi_flow_score_seq_from(const lfi_flow_dims* d, const lfi_flow_params* p, co
                             float* faces, int seq_len, int start, int nframes, int first_frame,
                             float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
                             float* score_work, float* z, float* nll, void* stream);
+/* ONE frame of a session in which every batch row either observes or generates (SampleStream.step_rows): lfi_flow_sample_seq_nll's
+ * arguments (nframes must be 1; nll, B floats, and nll_work are required), then observed (B ints on the device: != 0 = the row's
+ * frame is GIVEN - it is in faces[:, start] already - and 0 = the row generates from its noise row) and a second work area, rows_work
+ * (lfi_flow_step_rows_work_floats(d) floats). Every row's h / cstate, frame in `faces` and nll are what lfi_flow_score_seq_from
+ * (observing rows) or lfi_flow_sample_seq_nll (generating rows) alone leaves for it; noise rows of observing rows and frame slots of
+ * generating rows are read but never reach anything stored. The conditioning front end once, then both chains in one launch of
+ * 2 Ks ceil(B / 16) workgroups with row-masked stores; a 16-row tile whose rows all have one role costs one chain, not two. Each
+ * direction keeps its own arithmetic rule by d->gemm_precision. Shapes outside the register-resident cells (and LFI_SAMPLE_CHAIN=0):
+ * the two directions' per-step launches and a merge launch. Allocation-free, capturable; every argument is checked before the
+ * first launch. */
+long lfi_flow_step_rows_work_floats(const lfi_flow_dims* d);
+int lfi_flow_step_rows_from(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep,
+                            const float* wct, long E, int hist1, float* pre_static, const float* noise,
+                            float* faces, int seq_len, int start, int nframes, int first_frame,
+                            float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
+                            float* nll, float* nll_work, const int* observed, float* rows_work, void* stream);
 /* One frame forward of a streaming sampling session (SeqGlow.open_stream; glow/models.py:567-596 one frame at a time), in ONE launch:
  * every window i (B x hist[i] x dim[i], rows per batch entry) moves up by one frame in place, and its last row receives src[i] (B x
  * dim[i]), or - src[i] == NULL, the prev_p1_face window of the session's own output - keeps the frame the last step generated there;
@@ -440,6 +456,15 @@ int lfi_flow_score_seq_from(const lfi_flow_dims* d, const lfi_flow_params* p, co
  * Allocation-free, capturable; the host never waits on guard_bits. */
 int lfi_stream_advance(int B, int count, float* const* win, const float* const* src, const int* hist, const int* dim,
                        const float* noise, float* noise_dst, int C, float* frame_nb, unsigned* guard_bits, void* stream);
+/* lfi_stream_advance for a step in which every batch row either observes or generates (SampleStream.step_rows). observed: B bytes on
+ * the device (a bool mask), != 0 = the row observes; role (B ints, the session's own) receives 0 / 1 per row - what
+ * lfi_flow_step_rows_from reads. Window face_win (0 <= face_win < count, src[face_win] required: the observed frames, B x
+ * dim[face_win]) receives its source only in observing rows; generating rows shift only, and the chain writes their newest row.
+ * Into *guard_bits go only values that are used: the windows' (the face only of observing rows) and the noise of generating rows;
+ * the face of a generating row is never read. Everything else as lfi_stream_advance. */
+int lfi_stream_advance_rows(int B, int count, float* const* win, const float* const* src, const int* hist, const int* dim,
+                            int face_win, const float* noise, float* noise_dst, int C, float* frame_nb,
+                            const unsigned char* observed, int* role, unsigned* guard_bits, void* stream);
 /* Reseed listed batch rows of a streaming sampling session (SampleStream.reset_rows; the start of glow/models.py:567-596 for those
  * rows alone) between steps: each session row rows[j] (0 <= rows[j] < B, none twice, nrows >= 1) gets the state open_stream gives
  * a row, from entry j of the caller's seed, and no other row is written. Per window i (count <= 8; the layout of lfi_stream_advance):

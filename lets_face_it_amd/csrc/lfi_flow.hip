@@ -91,11 +91,25 @@ struct CellIO {
   int stamp_base;         // diagnostics (lfi_debug_set_stamps): slot of this cell's first phase stamp + 1, 0 = none (rev_fast_cell)
   int state_l2;           // reverse cell: read h_prev / c_prev with L1-bypassing (sc1) loads - the persistent reverse walk re-reads
                           // the state its own workgroup stored one timestep earlier, with no kernel boundary in between
+  const int* role;        // row-masked cells (flow_rows_chain_kernel) only: one word per batch row, != 0 = the row observes
+  int role_want;          // ... and the role this cell stores for (0: generating rows, 1: observing rows); other rows are never stored
 };
 
 extern __shared__ __attribute__((aligned(16))) float flow_smem[];
 
 __device__ __forceinline__ int rup16(int x) { return (x + 15) & ~15; }
+
+// The rows of the 16-row tile at b0 that a row-masked cell stores: bit i = row b0 + i is inside the batch and has the role `want`.
+// The same for every thread of the workgroup (a uniform read of the tile's 16 role words).
+__device__ __forceinline__ unsigned tile_live_rows(const int* role, int want, int b0, int rows) {
+  unsigned m = 0u;
+#pragma unroll
+  for (int i = 0; i < MB; ++i) {
+    const int row = b0 + i;
+    if (row < rows && (role[row] != 0) == (want != 0)) m |= 1u << i;
+  }
+  return m;
+}
 
 // ---- shared phase: coupling net given z1 (Zt) and h_prev (Ht) in LDS -> new hidden (Hn, LDS) and o (Orm, LDS)
 __device__ __forceinline__ void coupling_net_phase(const FlowK& f, const CellIO& io, int b0, const float* Zt, const float* Ht,
@@ -931,18 +945,20 @@ __device__ __forceinline__ f32x4 x3_mma_gates_img(const __bf16* hi_row, const __
 // h_prev in LDS (k-major), Hn: new state (LDS), h_out / c_out / g_out: row-0 pointers of the (rows x H) / (rows x 4H) outputs
 // (g_out may be null).
 // gate math + stores of P2 on this wave's 16 hidden units, given the two accumulated products (az: z1 side, ah: h side)
-template <int NG>
+// RM (row-masked cells): h_out / c_out are stored for the rows of `live` only (tile_live_rows), not for every row inside the batch.
+template <int NG, bool RM = false>
 __device__ __forceinline__ void fast_cell_p2_gates(const FlowK& f, const float* Ht, float* Hn, const f32x4 (&az)[NG],
                                                    const f32x4 (&ah)[NG], const float (&gc)[4][NG], const float (&bh)[NG],
                                                    const float (&cprev)[4], int j2, int kq, int b0, int rows, float* h_out,
                                                    float* c_out, float* g_out, float* cnew, __bf16* img_hi = nullptr,
-                                                   __bf16* img_lo = nullptr, int img_ld = 0, int img_col = 0) {
+                                                   __bf16* img_lo = nullptr, int img_ld = 0, int img_col = 0, unsigned live = 0u) {
   const int H = f.H;
   if (j2 < H) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = kq * 4 + r;
       const int row = b0 + i;
+      const bool rs = RM ? ((live >> i) & 1u) != 0u : row < rows;   // this row's results go to memory
       float hnew;
       float gs0, gs1, gs2, gs3;
       if (NG == 3) {  // torch.nn.GRUCell, gate order r, z, n
@@ -962,13 +978,13 @@ __device__ __forceinline__ void fast_cell_p2_gates(const FlowK& f, const float* 
         const float oo = sigmoidf_(az[NG - 1][r] + ah[NG - 1][r] + gc[r][NG - 1] + bh[NG - 1]);
         const float c2 = __builtin_fmaf(ff, cprev[r], ii * gg);
         hnew = oo * tanhf_(c2);
-        if (row < rows) c_out[(long)row * H + j2] = c2;
+        if (rs) c_out[(long)row * H + j2] = c2;
         if (cnew) cnew[r] = c2;
         gs0 = ii; gs1 = ff; gs2 = gg; gs3 = oo;
       }
       Hn[j2 * LT + i] = hnew;
       if (img_hi) x3_put(img_hi, img_lo, i * img_ld + img_col + x3_pos(j2), hnew);   // bf16 hi / lo image for the next cell's product
-      if (row < rows) {
+      if (rs) {
         if (h_out) h_out[(long)row * H + j2] = hnew;   // (null: the caller stores the tile's rows itself, 16 bytes at a time)
         if (g_out) {
           // the four stashed gate values of (row, hidden unit) lie together: ONE 16-byte store here and one 16-byte load in the
@@ -1705,7 +1721,10 @@ __global__ __launch_bounds__(NT) void flow_pipe_fwd_kernel(FlowK f) {
 // cell starts it from the prior term of the noise tile it stages); q_out: where this cell leaves it - sc1 stores in front of the
 // publish - or, q_last, the finished -(q + logdet_const) / ln 2 of the frame in bits. One writer per word, k descending: a fixed
 // summation order. Not NLL: none of it is compiled.
-template <int NG, bool X3 = false, bool XW = false, bool NLL = false>
+// RM (flow_rows_chain_kernel): a row-masked cell. Everything it leaves in memory - h_out / c_out, its output tile or the frame row, the
+// hand-over q or the NLL word - is stored only for the tile's rows whose role word (io.role) is io.role_want; the other rows still
+// pass through the products (see that kernel) and are dropped. Not RM: none of it is compiled.
+template <int NG, bool X3 = false, bool XW = false, bool NLL = false, bool RM = false>
 __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, int b0, const unsigned* wait_flag,
                                               unsigned* abort_w, unsigned* pub_flag, int* s_ok, unsigned need = 1u,
                                               unsigned pub_value = 1u, const float* q_in = nullptr, float* q_out = nullptr,
@@ -1727,6 +1746,8 @@ __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, 
   const int nbC = C16 >> 4, nbZ = Ch16 >> 4, nbH = H16 >> 4;
   const bool t1 = wave * 16 < C, t2 = wave * 16 < H, t3 = wave * 16 < Cout;
   const int tcol = wave * 16 + l15;
+  unsigned live = 0u;
+  if constexpr (RM) live = tile_live_rows(io.role, io.role_want, b0, rows);
   // phase stamps of the stamping workgroup (flow step LFI_STAMP_K, tile 0): s_memtime at the phase boundaries (tools/rev_stamps.py)
 #define REV_STAMP(slot)                                                                                                  \
   do {                                                                                                                   \
@@ -1949,7 +1970,8 @@ __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, 
           for (int g = 0; g < NG; ++g) az[g] = mfma16(a3, wz[g][b][3], az[g]);
         }
     }
-    fast_cell_p2_gates<NG>(f, Ht, Hn, az, ah, gc, bh, cprev, tcol, kq, b0, rows, io.h_out, io.c_out, nullptr, nullptr);
+    fast_cell_p2_gates<NG, RM>(f, Ht, Hn, az, ah, gc, bh, cprev, tcol, kq, b0, rows, io.h_out, io.c_out, nullptr, nullptr, nullptr, nullptr,
+                               0, 0, live);
   }
   __syncthreads();
   REV_STAMP(4);
@@ -1973,6 +1995,7 @@ __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, 
   // ---- R3: coupling inverse (glow/models.py:356-365)
   {
     const int row = b0 + ri;
+    const bool rs = RM ? ((live >> ri) & 1u) != 0u : row < rows;
     float lg = 0.0f;
     if (cl < C2) {
       const float z2n = Yrm[ri * ldy + Ch + cl];
@@ -1991,7 +2014,7 @@ __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, 
     }
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) lg += __shfl_xor(lg, o, 64);
-    if (cl == 0 && row < rows && io.l_out) {
+    if (cl == 0 && rs && io.l_out) {
       if (io.l_accumulate) io.l_out[row] += lg; else io.l_out[row] = lg;
     }
     if constexpr (NLL) {
@@ -2000,7 +2023,7 @@ __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, 
         for (int o = 16; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
         q = -0.5f * (q + (float)C * LOG2PI_F);
       }
-      if (cl == 0 && row < rows) {
+      if (cl == 0 && rs) {
         q -= lg;   // forward log-det of this step's coupling = -lg
         if (q_last) q_out[row] = -(q + f.ldconst[0]) / LN2_F;
         else st_sc1(q_out + row, q);
@@ -2026,7 +2049,7 @@ __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = b0 + kq * 4 + r;
-        if (row < rows) {
+        if (RM ? ((live >> (kq * 4 + r)) & 1u) != 0u : row < rows) {
           if (pub_flag) st_sc1(io.x_out + (long)row * io.ldxo + c, acc[r] * es - bb);
           else io.x_out[(long)row * io.ldxo + c] = acc[r] * es - bb;
         }
@@ -2145,7 +2168,9 @@ __global__ __launch_bounds__(NT) void flow_rev_chain_kernel(FlowK f, RevChain rc
 // stores in front of the publish. nll_out (the last step): the cell adds the prior term of its z, sum_c -0.5 (z_c^2 + log 2 pi), and
 // logdet_const and writes -(logdet + log p(z)) / ln 2 in bits. One writer per word, k ascending: a fixed summation order.
 // io.x_out may be null (the last step of a caller that does not want z).
-template <int NG, bool X3>
+// RM (flow_rows_chain_kernel): a row-masked cell, as rev_fast_cell's - h_out / c_out, the output tile, the hand-over q and the NLL word
+// are stored for the rows of role io.role_want only.
+template <int NG, bool X3, bool RM = false>
 __device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io, int b0, const unsigned* wait_flag, unsigned* abort_w,
                                                unsigned* pub_flag, int* s_ok, const float* q_in, float* q_out, float* nll_out) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2165,6 +2190,8 @@ __device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io,
   const int nbC = C16 >> 4, nbZ = Ch16 >> 4, nbH = H16 >> 4;
   const bool t1 = wave * 16 < C, t2 = wave * 16 < H, t3 = wave * 16 < Cout;
   const int tcol = wave * 16 + l15;
+  unsigned live = 0u;
+  if constexpr (RM) live = tile_live_rows(io.role, io.role_want, b0, rows);
   // ---- requests in the order their results are needed: h_prev (its LDS image gates the first barrier), the recurrent weights, then
   // the weights of the phases behind the wait
   const int hrow = b0 + ri;
@@ -2348,7 +2375,8 @@ __device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io,
           for (int g = 0; g < NG; ++g) az[g] = mfma16(a3, wz[g][b][3], az[g]);
         }
     }
-    fast_cell_p2_gates<NG>(f, Ht, Hn, az, ah, gc, bh, cprev, tcol, kq, b0, rows, io.h_out, io.c_out, nullptr, nullptr);
+    fast_cell_p2_gates<NG, RM>(f, Ht, Hn, az, ah, gc, bh, cprev, tcol, kq, b0, rows, io.h_out, io.c_out, nullptr, nullptr, nullptr, nullptr,
+                               0, 0, live);
   }
   __syncthreads();
   // ---- F3: o = (h' Wfl^T + b) exp(3 logs)   (LinearZeros, glow/modules.py:93-95)
@@ -2371,7 +2399,7 @@ __device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io,
   // ---- F4: coupling (glow/models.py:330-341), the pass-through half, the row's log-det; the last step: the prior term and the NLL
   {
     const int row = b0 + ri;
-    const bool rok = row < rows;
+    const bool rok = RM ? ((live >> ri) & 1u) != 0u : row < rows;
     float lg = 0.0f, zz = 0.0f;
     auto put = [&](int c, float v) {
       if (!io.x_out || !rok) return;
@@ -2457,6 +2485,87 @@ __global__ __launch_bounds__(NT) void flow_fwd_chain_kernel(FlowK f, FwdChain fc
       if (fc.z)
         for (int c = threadIdx.x & 31; c < f.C; c += 32) fc.z[(long)row * f.C + c] = __builtin_nanf("");
       if ((threadIdx.x & 31) == 0) fc.nll[row] = __builtin_nanf("");   // (the thread that wrote the row's word in F4, if the cell got that far)
+    }
+  }
+}
+
+// One frame of a streaming session in which every batch row either GENERATES or OBSERVES (SampleStream.step_rows): both chains above in
+// ONE launch of 2 Ks nbt workgroups, ids by ticket. Tickets [0, Ks nbt) are flow_rev_chain_kernel's roles (k descending, the NLL
+// hand-over), tickets [Ks nbt, 2 Ks nbt) flow_fwd_chain_kernel's (k ascending). A workgroup waits only on one of its OWN direction with
+// a lower ticket - there is no wait across the directions - so, as in both chains, it only waits on a workgroup that already runs and
+// any number of resident workgroups makes progress. Each direction has its own ping-pong tiles, log-density hand-over and progress
+// words (the reverse's at pipe[PIPE_HDR ..], the forward's Ks nbt words behind them); the ticket and the abort word are shared.
+//
+// role: one word per batch row, != 0 = the row observes (its frame is in `faces` already), 0 = it generates (from its noise row). Both
+// directions run the cell on whole 16-row tiles with row-masked stores (RM): a tile's rows of the other role still flow through its
+// MFMAs, but row i of the A operand only ever reaches row i of D, every reduction of the cells is along one row, and the elementwise
+// phases are per element - so what such a row holds, NaN included, stays in its row and is never stored. One consequence: a forward
+// workgroup may read h_prev / c_prev or the frame slot of a GENERATING row while the reverse workgroup of that tile writes it (and a
+// reverse workgroup the state of an observing row while the forward one writes it): that value feeds only the row that is dropped.
+// Rows of its own role a workgroup reads are written by nobody else in this launch.
+//
+// A workgroup whose tile has no row of its direction leaves at once, before it requests any weights: all Ks workgroups of that
+// (direction, tile) read the same 16 role words and decide alike, so nobody waits on one that left. A caller that keeps generating and
+// observing rows in separate tiles pays for each tile once.
+struct RowsChain {
+  RevChain rev;       // the generating rows' chain (xf = null: the conditioning makes the next window's fragments itself); rev.pipe: the shared words
+  FwdChain fwd;       // the observing rows' chain (z = null)
+  const int* role;    // B words
+};
+template <int NG, bool X3R, bool XW, bool X3F>
+__global__ __launch_bounds__(NT) void flow_rows_chain_kernel(FlowK f, RowsChain rc) {
+  __shared__ int s_id, s_ok;
+  unsigned* pipe = rc.rev.pipe;
+  if (threadIdx.x == 0) s_id = (int)atomicAdd(pipe, 1u);
+  __syncthreads();
+  const int nbt = f.nbt, per = f.Ks * nbt;
+  const int dir = s_id / per;
+  if (dir >= 2) return;
+  const int id = s_id - dir * per;
+  const int kk = id / nbt, bt = id - kk * nbt;
+  if (tile_live_rows(rc.role, dir, bt * MB, f.B) == 0u) return;   // (uniform: no row of this direction in the tile)
+  unsigned* prog = pipe + PIPE_HDR + dir * per;
+  const int row = bt * MB + (int)(threadIdx.x >> 5);
+  CellIO io = {};
+  io.rows = f.B; io.role = rc.role; io.role_want = dir;
+  if (dir == 0) {
+    const RevChain& r = rc.rev;
+    const int k = f.Ks - 1 - kk;
+    io.k = k;
+    if (k == f.Ks - 1) { io.x_in = r.noise; io.ldx = f.C; }
+    else { io.x_in = ((k + 1) & 1) ? r.xa : r.xb; io.ldx = f.C; }
+    if (k == 0) { io.x_out = r.frame; io.ldxo = r.ld_frame; }
+    else { io.x_out = (k & 1) ? r.xa : r.xb; io.ldxo = f.C; }
+    io.h_prev = r.has_prev ? r.h + (long)k * f.B * f.H : nullptr;
+    io.h_out = r.h + (long)k * f.B * f.H;
+    if (NG == 4) { io.c_prev = r.has_prev ? r.cstate + (long)k * f.B * f.H : nullptr; io.c_out = r.cstate + (long)k * f.B * f.H; }
+    io.gic = r.gic + (long)k * f.B * f.G;
+    rev_fast_cell<NG, X3R, XW, true, true>(f, io, bt * MB, k + 1 < f.Ks ? prog + (k + 1) * nbt + bt : nullptr, pipe + 1,
+                                           k > 0 ? prog + k * nbt + bt : nullptr, &s_ok, 1u, 1u,
+                                           k + 1 < f.Ks ? (((k + 1) & 1) ? r.qa : r.qb) : nullptr,
+                                           k == 0 ? r.nll : ((k & 1) ? r.qa : r.qb), k == 0);
+    if (k == 0 && ld_agent(pipe + 1) != 0u) {   // an abandoned chain must not pass for a frame
+      if (row < f.B && rc.role[row] == 0) {
+        for (int c = threadIdx.x & 31; c < f.C; c += 32) r.frame[(long)row * r.ld_frame + c] = __builtin_nanf("");
+        if ((threadIdx.x & 31) == 0) r.nll[row] = __builtin_nanf("");
+      }
+    }
+  } else {
+    const FwdChain& w = rc.fwd;
+    const int k = kk;
+    const bool last = k == f.Ks - 1;
+    io.k = k;
+    if (k == 0) { io.x_in = w.frame; io.ldx = w.ld_frame; }
+    else { io.x_in = ((k - 1) & 1) ? w.xa : w.xb; io.ldx = f.C; }
+    io.x_out = last ? nullptr : ((k & 1) ? w.xa : w.xb); io.ldxo = f.C;
+    io.h_prev = w.has_prev ? w.h + (long)k * f.B * f.H : nullptr;
+    io.h_out = w.h + (long)k * f.B * f.H;
+    if (NG == 4) { io.c_prev = w.has_prev ? w.cstate + (long)k * f.B * f.H : nullptr; io.c_out = w.cstate + (long)k * f.B * f.H; }
+    io.gic = w.gic + (long)k * f.B * f.G;
+    fwd_chain_cell<NG, X3F, true>(f, io, bt * MB, k > 0 ? prog + (k - 1) * nbt + bt : nullptr, pipe + 1, last ? nullptr : prog + k * nbt + bt,
+                                  &s_ok, k > 0 ? (((k - 1) & 1) ? w.qa : w.qb) : nullptr, (k & 1) ? w.qa : w.qb, last ? w.nll : nullptr);
+    if (last && ld_agent(pipe + 1) != 0u) {   // an abandoned chain must not pass for a likelihood
+      if (row < f.B && rc.role[row] != 0 && (threadIdx.x & 31) == 0) w.nll[row] = __builtin_nanf("");
     }
   }
 }
@@ -3839,6 +3948,7 @@ typedef void (*FlowStepKernel)(FlowK, CellIO);
 typedef void (*FlowRevWalkKernel)(FlowK, RevWalk);
 typedef void (*FlowRevChainKernel)(FlowK, RevChain);
 typedef void (*FlowFwdChainKernel)(FlowK, FwdChain);
+typedef void (*FlowRowsChainKernel)(FlowK, RowsChain);
 
 FlowDiagKernel flow_diag_fwd_pick(bool fast, bool lstm) {
   if (!fast) return flow_diag_fwd_kernel;
@@ -3873,6 +3983,15 @@ FlowRevChainKernel flow_rev_chain_pick(bool lstm, bool x3, bool xw, bool nll) {
 FlowFwdChainKernel flow_fwd_chain_pick(bool lstm, bool x3) {
   if (lstm) return flow_fwd_chain_kernel<4, false>;
   return x3 ? flow_fwd_chain_kernel<3, true> : flow_fwd_chain_kernel<3, false>;
+}
+
+// the two chains' own rules side by side: the reverse cells' form as flow_rev_chain_pick has it (x3: fp16 pieces at precisions 9 and 5,
+// xw: from the fragment images), the forward cells' as flow_fwd_chain_pick has it (x3f: precision 9 only); the LSTM cell exact in both
+FlowRowsChainKernel flow_rows_chain_pick(bool lstm, bool x3, bool xw, bool x3f) {
+  if (lstm) return flow_rows_chain_kernel<4, false, false, false>;
+  if (!x3) return flow_rows_chain_kernel<3, false, false, false>;
+  if (xw) return x3f ? flow_rows_chain_kernel<3, true, true, true> : flow_rows_chain_kernel<3, true, true, false>;
+  return x3f ? flow_rows_chain_kernel<3, true, false, true> : flow_rows_chain_kernel<3, true, false, false>;
 }
 
 // start state of a persistent walk: header and progress words cleared (LFI_PIPE_FORCE_ABORT=1: the abort word already set)
@@ -4377,9 +4496,10 @@ struct SampleFront {
   void* cfrags;
 };
 // `chain`: a one-launch chain follows every frame's conditioning (the fused kernel then clears its ticket / progress words)
+// pipe / pipe_words: those words, when they are not the carve's own
 int sample_front_setup(SampleFront* s, const lfi_flow_dims* d, const lfi_flow_params* p, const FlowK* f, const float* wct, long E, int hist1,
                        const float* pre_static, float* faces, int seq_len, const lfi_p1enc* p1, float* p1work, float* work, bool chain,
-                       int nframes, void* stream, const char* who) {
+                       int nframes, void* stream, const char* who, unsigned* pipe = nullptr, size_t pipe_words = 0) {
   s->d = d; s->p = p; s->f = f; s->wct = wct; s->E = E; s->hist1 = hist1; s->faces = faces; s->seq_len = seq_len;
   s->p1 = p1; s->p1work = p1work; s->chain = chain;
   s->p1kind = p1 ? p1->kind : 0;
@@ -4395,6 +4515,9 @@ int sample_front_setup(SampleFront* s, const lfi_flow_dims* d, const lfi_flow_pa
   // raw prev_p1_face windows start (t - hist1) * C floats into a row: 16-byte aligned only on every other frame at C = 50,
   // which sent half of the window products to the exact-f32 kernel (91 vs 35 us). A gather into an aligned buffer first.
   s->wstage = reinterpret_cast<float*>(s->chain_state + s->chain_words);
+  // pipe: a chain with more hand-off words than one direction's (flow_rows_chain_kernel) brings its own, and the fused conditioning
+  // kernel clears those; everything else of the carve stays where every other caller has it
+  if (pipe) { s->chain_state = pipe; s->chain_words = pipe_words; }
   s->ldw = (hist1 * C + 3) & ~3;
   s->stage_win = s->p1kind == 0 && hist1 <= 64;
   // raw window + fp16 pieces (precision 9) + final widths: cond_transform's window part and the coupling cell's input projection
@@ -4669,6 +4792,180 @@ extern "C" int lfi_flow_score_seq_from(const lfi_flow_dims* d, const lfi_flow_pa
     hipLaunchKernelGGL(score_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, xin, qa, f.ldconst, B, C, zn, nll + (long)n * B);
   }
   LFI_LAUNCH_CHECK("lfi_flow_score_seq_from");
+  return LFI_OK;
+}
+
+// ---- one frame of a session whose rows generate or observe, row by row (SampleStream.step_rows)
+namespace {
+// words of flow_rows_chain_kernel's state: ticket, abort, 2 reserved, then Ks * tiles progress words per direction
+inline long rows_pipe_words(long Ks, long tiles) { return ((long)PIPE_HDR + 2 * Ks * tiles + 3) & ~3L; }
+
+// the carve of lfi_flow_step_rows_from's second work area
+struct RowsWork {
+  unsigned* pipe; long pipe_words;
+  float *xa, *xb;     // the forward direction's B x C ping / pong tiles
+  float *qa, *qb;     // its log-det hand-over (the per-step launches' accumulator)
+  float *hs, *cs;     // per-step launches only: [Ks][B][H] copies of h / cstate the forward direction advances
+  float *gframe;      // ... B x C: the frame the reverse direction generates
+  float *fnll;        // ... B: the forward direction's NLL
+  long total;
+};
+RowsWork rows_work_carve(float* base, long B, long C, long H, long Ks) {
+  RowsWork w = {};
+  const long tiles = (B + MB - 1) / MB;
+  long o = 0;
+  w.pipe = reinterpret_cast<unsigned*>(base); w.pipe_words = rows_pipe_words(Ks, tiles); o += w.pipe_words;
+  w.xa = base + o; o += B * C;
+  w.xb = base + o; o += B * C;
+  w.qa = base + o; o += B;
+  w.qb = base + o; o += B;
+  w.hs = base + o; o += Ks * B * H;
+  w.cs = base + o; o += Ks * B * H;
+  w.gframe = base + o; o += B * C;
+  w.fnll = base + o; o += B;
+  w.total = o + 8;
+  return w;
+}
+
+// The per-step launches' last launch of a mixed frame: the reverse direction has advanced h / cstate of EVERY row and left its frame in
+// gframe and its NLL in nll; the forward direction has advanced the copies hs / cs from the frame in `faces` and left its NLL in fnll.
+// Observing rows take the forward direction's state and NLL (their frame is in place), generating rows their generated frame.
+// Thread (row, element) over Ks * H state elements and C frame elements of every row.
+__global__ __launch_bounds__(256) void rows_merge_kernel(const int* __restrict__ role, int B, int C, int H, int Ks, float* __restrict__ h,
+                                                         float* __restrict__ cstate, const float* __restrict__ hs,
+                                                         const float* __restrict__ cs, float* __restrict__ frame, long ld_frame,
+                                                         const float* __restrict__ gframe, float* __restrict__ nll,
+                                                         const float* __restrict__ fnll) {
+  const int b = blockIdx.x;
+  const bool observes = role[b] != 0;
+  if (observes) {
+    for (int e = threadIdx.x; e < Ks * H; e += 256) {
+      const long o = ((long)(e / H) * B + b) * H + e % H;
+      h[o] = hs[o];
+      if (cstate) cstate[o] = cs[o];
+    }
+    if (threadIdx.x == 0) nll[b] = fnll[b];
+  } else {
+    for (int c = threadIdx.x; c < C; c += 256) frame[(long)b * ld_frame + c] = gframe[(long)b * C + c];
+  }
+}
+}  // namespace
+
+extern "C" long lfi_flow_step_rows_work_floats(const lfi_flow_dims* d) {
+  if (!d) return 0;
+  return rows_work_carve(nullptr, d->B, d->C, d->H, d->Ks).total;
+}
+
+// One frame (nframes = 1) in which row b observes where observed[b] != 0 - its frame is in faces[:, start] already - and generates from
+// noise[b] otherwise: lfi_flow_sample_seq_nll's arguments, the role words and a second work area (lfi_flow_step_rows_work_floats).
+// Every row's h / cstate, frame and nll (B, required) are what lfi_flow_score_seq_from or lfi_flow_sample_seq_nll alone leaves for it.
+// The conditioning front end once, then flow_rows_chain_kernel; shapes and switches outside the chain: the forward direction's
+// per-step launches on copies of h / cstate, the reverse direction's on the state itself with its frame aside, one merge launch.
+extern "C" int lfi_flow_step_rows_from(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct, long E,
+                                       int hist1, float* pre_static, const float* noise, float* faces, int seq_len, int start,
+                                       int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1, float* p1work,
+                                       float* work, float* nll, float* nll_work, const int* observed, float* rows_work, void* stream) {
+  FlowK f = {};
+  int rc = fill_flow(d, p, prep, &f, "lfi_flow_step_rows_from");
+  if (rc) return rc;
+  LFI_REQUIRE(first_frame >= 0, "lfi_flow_step_rows_from: negative first_frame");
+  LFI_REQUIRE(prep && wct && pre_static && noise && faces && h && work && nll && nll_work && observed && rows_work,
+              "lfi_flow_step_rows_from: null pointer");
+  LFI_REQUIRE(nframes == 1, "lfi_flow_step_rows_from: %d frames (one frame per call)", nframes);
+  LFI_REQUIRE(hist1 >= 0 && hist1 <= start && start + nframes <= seq_len, "lfi_flow_step_rows_from: bad frame range");
+  LFI_REQUIRE((long)hist1 * d->C <= E, "lfi_flow_step_rows_from: window wider than the feature vector");
+  LFI_REQUIRE(!d->lstm || cstate, "lfi_flow_step_rows_from: the LSTM cell needs cstate");
+  LFI_REQUIRE((reinterpret_cast<uintptr_t>(rows_work) & 3) == 0, "lfi_flow_step_rows_from: rows_work is not 4-byte aligned");
+  const int B = f.B, C = f.C, H = f.H, Ks = f.Ks, G = f.G;
+  hipStream_t st = (hipStream_t)stream;
+  const bool fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
+  const bool chain = fast && lfi_env_on("LFI_SAMPLE_CHAIN");
+  // each direction's own rule (lfi_flow_sample_seq_nll, lfi_flow_score_seq_from)
+  const bool x3 = flow_x3_rev_cell(d, f);
+  const bool xw = x3 && chain && flow_sample_wfrag16_enabled();
+  const bool x3f = x3 && (d->gemm_precision & 0xff) == 9;
+  const size_t lds_fast = (size_t)carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total * sizeof(float);
+  const size_t lds_gen = (size_t)carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout).total * sizeof(float);
+  const FlowRowsChainKernel chain_kernel = flow_rows_chain_pick(f.lstm, x3, xw, x3f);
+  const FlowStepKernel rev_cell = flow_step_rev_pick(fast, f.lstm);
+  if (chain) {
+    if ((rc = set_flow_lds(chain_kernel, lds_fast, "lfi_flow_step_rows_from"))) return rc;
+  } else {
+    if ((rc = set_flow_lds(rev_cell, fast ? lds_fast : lds_gen, "lfi_flow_step_rows_from"))) return rc;
+    if ((rc = set_flow_lds(flow_step_kernel<false>, lds_gen, "lfi_flow_step_rows_from"))) return rc;
+  }
+  const RowsWork rw = rows_work_carve(rows_work, B, C, H, Ks);
+  SampleFront sf = {};
+  if ((rc = sample_front_setup(&sf, d, p, &f, wct, E, hist1, pre_static, faces, seq_len, p1, p1work, work, chain, nframes, stream,
+                               "lfi_flow_step_rows_from", chain ? rw.pipe : nullptr, (size_t)rw.pipe_words))) return rc;
+  const int t = start;
+  const int has_prev = first_frame > 0 ? 1 : 0;
+  if ((rc = sample_front_frame(sf, t, pre_static, 0, stream))) return rc;
+  float* frame = faces + (long)t * C;
+  const long ld_frame = (long)seq_len * C;
+  if (chain) {
+    RowsChain rcn = {};
+    rcn.role = observed;
+    rcn.rev.noise = noise; rcn.rev.xa = sf.xa; rcn.rev.xb = sf.xb; rcn.rev.frame = frame; rcn.rev.ld_frame = ld_frame;
+    rcn.rev.gic = sf.gic; rcn.rev.h = h; rcn.rev.cstate = cstate; rcn.rev.has_prev = has_prev; rcn.rev.frame_no = first_frame;
+    rcn.rev.pipe = rw.pipe; rcn.rev.qa = nll_work; rcn.rev.qb = nll_work + B; rcn.rev.nll = nll;
+    rcn.fwd.frame = frame; rcn.fwd.ld_frame = ld_frame; rcn.fwd.xa = rw.xa; rcn.fwd.xb = rw.xb; rcn.fwd.gic = sf.gic;
+    rcn.fwd.h = h; rcn.fwd.cstate = cstate; rcn.fwd.has_prev = has_prev; rcn.fwd.pipe = rw.pipe;
+    rcn.fwd.qa = rw.qa; rcn.fwd.qb = rw.qb; rcn.fwd.nll = nll;
+    if (!sf.fused) {   // (the fused conditioning kernel has cleared them)
+      hipError_t me = hipMemsetAsync(rw.pipe, 0, (size_t)rw.pipe_words * sizeof(unsigned), st);
+      LFI_REQUIRE(me == hipSuccess, "lfi_flow_step_rows_from: hipMemsetAsync: %s", hipGetErrorString(me));
+    }
+    hipLaunchKernelGGL(chain_kernel, dim3(2 * Ks * f.nbt), dim3(NT), lds_fast, st, f, rcn);
+    LFI_LAUNCH_CHECK("lfi_flow_step_rows_from");
+    return LFI_OK;
+  }
+  // ---- per-step launches. The forward direction first: it reads the observed frame and the state of the frame before
+  const size_t state_bytes = (size_t)Ks * B * H * sizeof(float);
+  if (has_prev) {
+    hipError_t me = hipMemcpyAsync(rw.hs, h, state_bytes, hipMemcpyDeviceToDevice, st);
+    if (me == hipSuccess && f.lstm) me = hipMemcpyAsync(rw.cs, cstate, state_bytes, hipMemcpyDeviceToDevice, st);
+    LFI_REQUIRE(me == hipSuccess, "lfi_flow_step_rows_from: hipMemcpyAsync: %s", hipGetErrorString(me));
+  }
+  {
+    const float* xin = frame;
+    long ldx = ld_frame;
+    for (int k = 0; k < Ks; ++k) {
+      CellIO io = {};
+      io.k = k; io.rows = B; io.x_in = xin; io.ldx = ldx;
+      io.h_prev = has_prev ? rw.hs + (long)k * B * H : nullptr;
+      io.gic = sf.gic + (long)k * B * G;
+      io.h_out = rw.hs + (long)k * B * H;
+      if (f.lstm) { io.c_prev = has_prev ? rw.cs + (long)k * B * H : nullptr; io.c_out = rw.cs + (long)k * B * H; }
+      io.x_out = (k & 1) ? rw.xa : rw.xb; io.ldxo = C;
+      io.l_out = rw.qa; io.l_accumulate = k > 0;
+      hipLaunchKernelGGL(flow_step_kernel<false>, dim3(f.nbt), dim3(NT), lds_gen, st, f, io);
+      xin = io.x_out; ldx = C;
+    }
+    hipLaunchKernelGGL(score_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, xin, rw.qa, f.ldconst, B, C, (float*)nullptr, rw.fnll);
+  }
+  // ---- the reverse direction on the state itself, its frame aside (the observing rows' frame stays in `faces`)
+  {
+    const float* xin = noise;
+    long ldx = C;
+    for (int k = Ks - 1; k >= 0; --k) {
+      CellIO io = {};
+      io.k = k; io.rows = B; io.x_in = xin; io.ldx = ldx;
+      io.h_prev = has_prev ? h + (long)k * B * H : nullptr;
+      io.gic = sf.gic + (long)k * B * G;
+      io.h_out = h + (long)k * B * H;
+      if (f.lstm) { io.c_prev = has_prev ? cstate + (long)k * B * H : nullptr; io.c_out = cstate + (long)k * B * H; }
+      if (k == 0) { io.x_out = rw.gframe; io.ldxo = C; }
+      else { io.x_out = (k & 1) ? sf.xa : sf.xb; io.ldxo = C; }
+      io.l_out = nll_work; io.l_accumulate = k + 1 < Ks;
+      hipLaunchKernelGGL(rev_cell, dim3(f.nbt), dim3(NT), fast ? lds_fast : lds_gen, st, f, io);
+      xin = io.x_out; ldx = io.ldxo;
+    }
+    hipLaunchKernelGGL(sample_nll_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, noise, nll_work, f.ldconst, B, C, nll);
+  }
+  hipLaunchKernelGGL(rows_merge_kernel, dim3(B), dim3(256), 0, st, observed, B, C, H, Ks, h, cstate, rw.hs, rw.cs, frame, ld_frame,
+                     rw.gframe, nll, rw.fnll);
+  LFI_LAUNCH_CHECK("lfi_flow_step_rows_from");
   return LFI_OK;
 }
 

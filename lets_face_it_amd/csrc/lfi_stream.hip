@@ -71,6 +71,57 @@ __global__ __launch_bounds__(256) void stream_advance_kernel(StreamWins w, const
   if ((threadIdx.x & 63) == 0 && m) atomicMax(guard, m);
 }
 
+// stream_advance_kernel for a step whose rows observe or generate one by one (SampleStream.step_rows): the same workgroup map and chunk
+// order. Window face_win takes its source row only where the row observes (a generating row shifts only: the chain writes its newest
+// row, and its row of the source is never read); the noise row is copied for every row and folded into the guard only where the row
+// generates; workgroup (count, b) also leaves the row's role as one int for the chain.
+__global__ __launch_bounds__(256) void stream_advance_rows_kernel(StreamWins w, int face_win, const float* __restrict__ noise,
+                                                                 float* __restrict__ noise_dst, int C, float* __restrict__ frame_nb,
+                                                                 const unsigned char* __restrict__ observed, int* __restrict__ role,
+                                                                 unsigned* __restrict__ guard) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x;
+  const bool observes = observed[b] != 0;
+  unsigned m = 0u;
+  if (i < w.count) {
+    const int dim = w.dim[i];
+    const long n = (long)w.hist[i] * dim;
+    const long last = n - dim;                     // first element of the newest row
+    float* win = w.win[i] + (long)b * n;
+    const float* src = (i != face_win || observes) ? w.src[i] : nullptr;
+    const long stop = src ? n : last;              // without a source the newest row stays where it is
+    for (long base = 0; base < stop; base += 256) {
+      const long j = base + threadIdx.x;
+      float v = 0.0f;
+      if (j < stop) {
+        v = j < last ? win[j + dim] : src[(long)b * dim + (j - last)];
+        const unsigned a = stream_abs_bits(v);
+        m = a > m ? a : m;
+      }
+      __syncthreads();
+      if (j < stop) win[j] = v;
+    }
+  } else {
+    for (int j = threadIdx.x; j < C; j += 256) {
+      const float v = noise[(long)b * C + j];
+      noise_dst[(long)b * C + j] = v;
+      const unsigned a = observes ? 0u : stream_abs_bits(v);
+      m = a > m ? a : m;
+    }
+    if (threadIdx.x == 0) {
+      role[b] = observes ? 1 : 0;
+      if (frame_nb) frame_nb[b] += 2.0f;
+    }
+  }
+  if (!guard) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
+    m = t > m ? t : m;
+  }
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(guard, m);
+}
+
 // ---- per-row reseed (SampleStream.reset_rows): the state open_stream / reset() give a row, for a listed subset of rows
 //
 // Rows are passed by value in the kernel argument block (StreamReset.rows), at most kResetMaxRows per launch: no staging copy and no
@@ -285,6 +336,28 @@ extern "C" int lfi_stream_advance(int B, int count, float* const* win, const flo
   hipLaunchKernelGGL(stream_advance_kernel, dim3(count + 1, B), dim3(256), 0, (hipStream_t)stream, w, noise, noise_dst, C, frame_nb,
                      guard_bits);
   LFI_LAUNCH_CHECK("lfi_stream_advance");
+  return LFI_OK;
+}
+
+extern "C" int lfi_stream_advance_rows(int B, int count, float* const* win, const float* const* src, const int* hist, const int* dim,
+                                       int face_win, const float* noise, float* noise_dst, int C, float* frame_nb,
+                                       const unsigned char* observed, int* role, unsigned* guard_bits, void* stream) {
+  LFI_REQUIRE(B > 0 && B <= 65535, "lfi_stream_advance_rows: batch %d (1 .. 65535)", B);
+  LFI_REQUIRE(count >= 1 && count <= kStreamMaxWins, "lfi_stream_advance_rows: %d windows (1 .. %d)", count, kStreamMaxWins);
+  LFI_REQUIRE(win && src && hist && dim, "lfi_stream_advance_rows: null window table");
+  LFI_REQUIRE(noise && noise_dst && C > 0, "lfi_stream_advance_rows: null noise / C = %d", C);
+  LFI_REQUIRE(observed && role, "lfi_stream_advance_rows: null observed / role");
+  LFI_REQUIRE(face_win >= 0 && face_win < count && src[face_win], "lfi_stream_advance_rows: face window %d of %d, or its source is null",
+              face_win, count);
+  StreamWins w = {};
+  for (int i = 0; i < count; ++i) {
+    LFI_REQUIRE(win[i] && hist[i] > 0 && dim[i] > 0, "lfi_stream_advance_rows: window %d: hist %d, dim %d", i, hist[i], dim[i]);
+    w.win[i] = win[i]; w.src[i] = src[i]; w.hist[i] = hist[i]; w.dim[i] = dim[i];
+  }
+  w.count = count;
+  hipLaunchKernelGGL(stream_advance_rows_kernel, dim3(count + 1, B), dim3(256), 0, (hipStream_t)stream, w, face_win, noise, noise_dst, C,
+                     frame_nb, observed, role, guard_bits);
+  LFI_LAUNCH_CHECK("lfi_stream_advance_rows");
   return LFI_OK;
 }
 

@@ -151,7 +151,9 @@ class SampleStream:
         self.replays = 0                        # steps that were graph replays
         self._graph, self._graph_key = None, None                    # step()'s captured graph and what it was captured for
         self._observe_graphs = {}                                    # observe()'s own, by key
+        self._rows_graphs = {}                                       # step_rows()'s own, by key
         self.score_work = self.obs_z = self.obs_nll = None   # observe()'s buffers: allocated at the first observe
+        self.role = self.rows_work = self.rows_nll = self.rows_nll_work = None   # step_rows()'s: at the first step_rows
         self._stream = None
         self._guard_pending = None
         self._state = {"_ws": {}, "prep": None, "wct_f": torch.zeros_like(eng.wct_f), "_wct_planes": None, "_wc_r": None,
@@ -363,10 +365,11 @@ class SampleStream:
         if self._stream is not None:
             self._stream.synchronize()
         self.closed = True
-        self._graph, self._observe_graphs = None, {}
+        self._graph, self._observe_graphs, self._rows_graphs = None, {}, {}
         self._state = None
         self.faces = self.noise = self.windows = self.cond = self.pre = self.h = self.cs = self.work = self.p1work = self._wins = None
         self.nll = self.nll_work = self.score_work = self.obs_z = self.obs_nll = None
+        self.role = self.rows_work = self.rows_nll = self.rows_nll_work = None
 
     def __enter__(self):
         return self
@@ -443,18 +446,87 @@ class SampleStream:
         self._record_out(nll, z)
         return (nll, z) if return_z else nll
 
+    def _check_observed(self, observed):
+        """The role mask of step_rows(), checked before any launch -> a (B,) bool tensor, on the session's device or on the host (a
+        host mask is copied in on the step's stream)."""
+        B = self.B
+        if torch.is_tensor(observed):
+            if observed.dtype != torch.bool:
+                raise TypeError("observed: expected a torch.bool tensor or a sequence of bools, got a %s tensor" % observed.dtype)
+            if observed.dim() != 1 or observed.shape[0] != B:
+                raise ValueError("observed: expected %d entries (B,), got %s" % (B, tuple(observed.shape)))
+            if observed.is_cuda and observed.device != self.device:
+                raise ValueError("observed: on %s, the session on %s" % (observed.device, self.device))
+            if not observed.is_cuda and observed.device.type != "cpu":
+                raise ValueError("observed: on %s, the session on %s" % (observed.device, self.device))
+            return observed.contiguous()
+        try:
+            flags = list(observed)
+        except TypeError:
+            raise TypeError("observed: expected a torch.bool tensor or a sequence of bools, got %s" % type(observed).__name__) from None
+        if any(not isinstance(v, bool) for v in flags):
+            raise TypeError("observed: expected a torch.bool tensor or a sequence of bools, got %r" % (observed,))
+        if len(flags) != B:
+            raise ValueError("observed: expected %d entries (B,), got %d" % (B, len(flags)))
+        return torch.tensor(flags, dtype=torch.bool)
+
+    @translate_oom
+    def step_rows(self, frame, face, observed, noise=None):
+        """One frame in which every row either observes or generates: row r takes face[r] as its p1_face frame t where observed[r]
+        is true (observe()'s step for that row) and generates it from noise[r] otherwise (step()'s). frame: as step()'s; face: (B, C)
+        float32 GPU tensor, read only in observing rows (anything, NaN included, elsewhere; not in the range guard there); observed:
+        (B,) torch.bool on the session's device - no host wait, and a mask that changes every call recaptures nothing: the roles are
+        data at a session-owned address - or a host sequence / CPU tensor of B bools, copied in asynchronously; noise: as step()'s
+        (None: B x C values are drawn on every call, whatever the mask), unused in observing rows. -> (out, nll): out (B, C) the frame
+        that entered each row's faces window, generated or given; nll (B,) float32 its NLL in bits, as step(return_nll=True) and
+        observe() report it - both always, whatever return_nll the session was opened with. Each row moves on exactly as the pure
+        call of its role moves it (bit for bit), so step(), observe() and step_rows() alternate freely.
+
+        Per call: lfi_stream_advance_rows (the face enters the faces window in observing rows only; the mask becomes the session's
+        role words), the static part, then lfi_flow_step_rows_from: the conditioning front end once and BOTH chains in one launch
+        with row-masked stores. A 16-row tile whose rows share a role costs one chain, a mixed tile both: keep speaking and
+        listening conversations in separate tiles where possible. From the second call on, one captured hipGraph of its own, keyed
+        as the others are."""
+        s = self.eng.spec
+        self._check_usable()
+        srcs = self._check_frame(frame)
+        observed = self._check_observed(observed)
+        self._check_matrix(face, "face", s.C, self.B)
+        if noise is not None:
+            self._check_matrix(noise, "noise", s.C, self.B)
+        with self._owned():
+            self._check_guard()
+            if self.role is None:        # the step_rows buffers: at the first step_rows, outside capture
+                eng, dims = self.eng, self.eng._flow_dims(self.B, 1)
+                self.rows_work = eng._buf("stream_rows_work", eng.L.lfi_flow_step_rows_work_floats(C.byref(dims)))
+                self.rows_nll = eng._buf("stream_rows_nll", self.B)[:self.B]
+                self.rows_nll_work = eng._buf("stream_rows_nll_work", eng.L.lfi_flow_sample_nll_work_floats(C.byref(dims)))
+                self.role = eng._buf_i32("stream_role", self.B)
+            if noise is None:
+                noise = self._noise_fn(self.B, s.C).contiguous()
+            if not observed.is_cuda:
+                observed = observed.pin_memory().to(self.device, non_blocking=True)
+            self._advance(srcs, noise, face, observed=observed)
+            out = self.faces[:, self.hist1].clone()
+            nll = self.rows_nll.clone()
+            self.steps += 1
+        self._record_out(out, nll)
+        return out, nll
+
     def _record_out(self, *outs):
         if self._stream is not None:
             for x in outs:
                 if x is not None and x.device == self.device:
                     x.record_stream(torch.cuda.current_stream(self.device))
 
-    def _advance(self, srcs, noise, face, want_z=False):
+    def _advance(self, srcs, noise, face, want_z=False, observed=None):
         """One frame forward, inside _owned(): masks, lfi_stream_advance, the guard's copy, then the launch or the replay. face None: a
         generating step with the prior draw `noise`; else an observing one - the frame is the faces window's source (and fills the
-        noise slot, which an observing step does not read); want_z: the observing launch also writes the frame's latent."""
+        noise slot, which an observing step does not read); want_z: the observing launch also writes the frame's latent. observed (a
+        (B,) bool tensor on the device): a step_rows() step - both `noise` and `face`, each used in the rows of its role."""
         s, eng, B = self.eng.spec, self.eng, self.B
-        observe = face is not None
+        rows = observed is not None
+        observe = face is not None and not rows
         masks = None
         drawn = self._masks_fn(B, 1) if self._masks_fn is not None else None
         eng.precision = self.precision      # (the module's mask draw re-applies its own mode to the engine)
@@ -472,27 +544,35 @@ class SampleStream:
                 masks[name] = buf
         for i, x in enumerate(srcs):
             self._src_p[i] = x.data_ptr()
-        self._src_p[len(srcs)] = face.data_ptr() if observe else None
+        self._src_p[len(srcs)] = face.data_ptr() if observe or rows else None
         moved = face if observe else noise
         ev = eng._tic("stream_advance")
-        check(eng.L.lfi_stream_advance(B, len(self._row_win), self._row_win, self._src_p, self._row_hist, self._row_dim,
-                                       moved.data_ptr(), self.noise.data_ptr(), s.C, ptr(self.frame_nb), self.guard.data_ptr(),
-                                       _stream()), "lfi_stream_advance")
+        if rows:
+            check(eng.L.lfi_stream_advance_rows(B, len(self._row_win), self._row_win, self._src_p, self._row_hist, self._row_dim,
+                                                len(srcs), noise.data_ptr(), self.noise.data_ptr(), s.C, ptr(self.frame_nb),
+                                                observed.data_ptr(), self.role.data_ptr(), self.guard.data_ptr(), _stream()),
+                  "lfi_stream_advance_rows")
+        else:
+            check(eng.L.lfi_stream_advance(B, len(self._row_win), self._row_win, self._src_p, self._row_hist, self._row_dim,
+                                           moved.data_ptr(), self.noise.data_ptr(), s.C, ptr(self.frame_nb), self.guard.data_ptr(),
+                                           _stream()), "lfi_stream_advance")
         eng._toc("stream_advance", ev)
         self._pinned.copy_(self.guard, non_blocking=True)
         gev = torch.cuda.Event()
         gev.record()
         self._guard_pending = gev
-        for x in srcs + [moved]:
+        for x in srcs + ([noise, face, observed] if rows else [moved]):
             x.record_stream(torch.cuda.current_stream(self.device))
-        launch = functools.partial(self._launch_observe, want_z) if observe else self._launch
+        launch = self._launch_rows if rows else functools.partial(self._launch_observe, want_z) if observe else self._launch
         if self.steps == 0 or os.environ.get("LFI_NO_GRAPH") == "1":
             launch(masks, 1 if self.steps > 0 or self._resumed else 0)
             return
         # a captured graph per kind of step, keyed on what its launches depend on. step(): one graph, recaptured when the key changes.
         # observe(): one per key met (with and without z, per arithmetic) - alternating kinds or return_z recaptures nothing
+        # step_rows(): one per key met; the role mask is data at a session-owned address (self.role), not part of the key
         key = (self.frame_precision, masks is not None) + ((want_z,) if observe else ())
-        g = self._observe_graphs.get(key) if observe else (self._graph if self._graph_key == key else None)
+        own = self._rows_graphs if rows else self._observe_graphs if observe else None
+        g = own.get(key) if own is not None else (self._graph if self._graph_key == key else None)
         if g is None:
             timers, eng.timers = eng.timers, None
             try:
@@ -502,8 +582,8 @@ class SampleStream:
                     launch(masks, 1)
             finally:
                 eng.timers = timers
-            if observe:
-                self._observe_graphs[key] = g
+            if own is not None:
+                own[key] = g
             else:
                 self._graph, self._graph_key = g, key
         ev = eng._tic("stream_graph")
@@ -557,6 +637,19 @@ class SampleStream:
                                             self.work.data_ptr(), self.score_work.data_ptr(), self.obs_z.data_ptr() if want_z else None,
                                             self.obs_nll.data_ptr(), _stream()), "lfi_flow_score_seq_from")
         eng._toc("stream_observe_chain", ev)
+
+    def _launch_rows(self, masks, first_frame):
+        """The static part, then both chains in one launch, each on the rows of its role (self.role): session-owned memory only."""
+        eng, s = self.eng, self.eng.spec
+        dims, p = self._static(masks)
+        ev = eng._tic("stream_rows_chain")
+        check(eng.L.lfi_flow_step_rows_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
+                                            self.pre.data_ptr(), self.noise.data_ptr(), self.faces.data_ptr(), self.hist1 + 1,
+                                            self.hist1, 1, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
+                                            self.p1work.data_ptr(), self.work.data_ptr(), self.rows_nll.data_ptr(),
+                                            self.rows_nll_work.data_ptr(), self.role.data_ptr(), self.rows_work.data_ptr(), _stream()),
+              "lfi_flow_step_rows_from")
+        eng._toc("stream_rows_chain", ev)
 
     def _check_guard(self):
         """The range guard of earlier steps (lfi_stream_advance folds max |x| of every value it moves into the session's guard word,

@@ -3,7 +3,7 @@ alternative without a session: re-running SeqGlow.inference over the whole prefi
 
   python tools/stream_latency.py [--batches 1,16,256] [--steps 200] [--warmup 20] [--prefixes 50,150,300] [--out FILE]
                                  [--churn 1,16,64 [--churn-batch 256]] [--migrate 16 [--migrate-batch 256]] [--nll 1,256]
-                                 [--observe 1,16,256]
+                                 [--observe 1,16,256] [--rows 1,16,256]
 
 Per batch size: the wall-clock time from step() to the generated frame on the host (a synchronise after every step: what a live agent
 waits for), its GPU time (HIP events around the step), and a per-kernel breakdown from the engine's enable_timing on an eager session
@@ -26,7 +26,13 @@ inference() over --nll-frames generated frames with and without return_nll, the 
 
 --observe b1,b2,..: per batch size a generating session (step()) and a teacher-forced one (observe(), NLL only and with z) on the same
 seed and conditioning, interleaved step by step in one process, which goes first alternating; the observed faces are what an untimed
-generating session produced beforehand."""
+generating session produced beforehand.
+
+--rows b1,b2,..: this leg ALONE (nothing of the above runs), written to --out (default profiles/stream_step_rows.md): per batch size,
+a caller on its own stream, every leg interleaved step by step in one process with the order rotating - (a) step(return_nll=True) and
+observe(); (b) step_rows() with every row generating and with every row observing; (c) step_rows() with the first half of the 16-row
+tiles observing and the rest generating (B >= 32); (d) step_rows() with odd rows observing, even rows generating (B >= 2); (e) what a
+server has without step_rows: step() on one session of B / 2 rows, then observe() on another (B >= 2)."""
 import argparse
 import contextlib
 import os
@@ -52,6 +58,7 @@ def main():
     ap.add_argument("--nll", default=None, help="batch sizes of the return_nll leg, e.g. 1,256 (default: no such leg)")
     ap.add_argument("--nll-frames", type=int, default=0, help="with --nll: also inference() over this many generated frames, flag off / on")
     ap.add_argument("--observe", default=None, help="batch sizes of the observe() leg, e.g. 1,16,256 (default: no such leg)")
+    ap.add_argument("--rows", default=None, help="batch sizes of the step_rows() leg, e.g. 1,16,256: runs this leg alone")
     a = ap.parse_args()
     import bench
     helper = bench.start_smi_helper()       # (before the GPU is initialised: see bench.py)
@@ -79,6 +86,15 @@ def main():
     s = m.spec
     start, C = s.start, s.C
     dims = {"p1_face": C, "p2_face": C, "p1_speech": s.S, "p2_speech": s.S}
+    if a.rows:
+        text = rows_report(m, dev, [int(v) for v in a.rows.split(",")], a.steps, a.warmup, dims, start, C, torch.cuda.get_device_name(dev))
+        bench.stop_smi_helper(helper)
+        print(text)
+        out = a.out or os.path.join(ROOT, "profiles", "stream_step_rows.md")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text)
+        return
     batches = [int(v) for v in a.batches.split(",")]
     prefixes = [int(v) for v in a.prefixes.split(",")]
     total = a.warmup + a.steps
@@ -349,6 +365,111 @@ def observe_leg(m, dev, batches, steps, warmup, dims, start, C):
             out.append((B, leg, statistics.median(wall), wall[int(0.9 * (len(wall) - 1))], statistics.median(gpu),
                         gpu[int(0.9 * (len(gpu) - 1))]))
     return out
+
+
+def rows_leg(m, dev, batches, steps, warmup, dims, start, C):
+    """Per batch size: (B, leg, wall median, wall p90, GPU p10, GPU median, GPU p90) of the legs the module's docstring lists under
+    --rows, on a stream of the caller's own, interleaved step by step with the order rotating. The faces observed are those of an
+    untimed generating session run first with the same noise."""
+    import torch
+    out = []
+    total = warmup + steps
+    own = torch.cuda.Stream(device=dev)
+    for B in batches:
+        gd = torch.Generator().manual_seed(B + 4)
+        data = {k: torch.randn(B, start + total, d, generator=gd).to(dev) for k, d in dims.items()}
+        seed = {k: v[:, :start].contiguous() for k, v in data.items()}
+        frames = [{k: v[:, start + n].contiguous() for k, v in data.items() if k != "p1_face"} for n in range(total)]
+        noise = (torch.randn(total, B, C, generator=gd) * 0.8).to(dev)
+        h = B // 2
+        lo = lambda x: x[:h].contiguous()
+        hi = lambda x: x[h:].contiguous()
+        rows = torch.arange(B, device=dev)
+        masks = {"all generate": rows < 0, "all observe": rows >= 0, "tile-aligned halves": (rows // 16) < (B // 32),
+                 "interleaved in every tile": rows % 2 == 1}
+        own.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(own), contextlib.ExitStack() as stack:
+            opened = lambda sd, **kw: stack.enter_context(m.open_stream(sd, **kw))
+            with m.open_stream(seed) as ref:
+                faces = [ref.step(frames[n], noise[n]) for n in range(total)]
+            gen, obs = opened(seed, return_nll=True), opened(seed)
+            calls = [("(a) step(return_nll=True)", lambda n: gen.step(frames[n], noise[n])),
+                     ("(a) observe()", lambda n: obs.observe(frames[n], faces[n]))]
+
+            def rows_call(tag, mask):
+                st = opened(seed)
+                return (tag, lambda n: st.step_rows(frames[n], faces[n], mask, noise[n]))
+
+            calls += [rows_call("(b) step_rows, all generate", masks["all generate"]),
+                      rows_call("(b) step_rows, all observe", masks["all observe"])]
+            if B >= 32:
+                calls.append(rows_call("(c) step_rows, tile-aligned halves", masks["tile-aligned halves"]))
+            if B >= 2:
+                calls.append(rows_call("(d) step_rows, interleaved in every tile", masks["interleaved in every tile"]))
+                seed_lo, seed_hi = {k: lo(v) for k, v in seed.items()}, {k: hi(v) for k, v in seed.items()}
+                fr_lo = [{k: lo(v) for k, v in f.items()} for f in frames]
+                fr_hi = [{k: hi(v) for k, v in f.items()} for f in frames]
+                nz_lo, fc_hi = [lo(z) for z in noise], [hi(f) for f in faces]
+                two_g, two_o = opened(seed_lo), opened(seed_hi)
+
+                def two(n):
+                    two_g.step(fr_lo[n], nz_lo[n])
+                    two_o.observe(fr_hi[n], fc_hi[n])
+                calls.append(("(e) step() on %d rows, then observe() on %d rows: two sessions" % (h, B - h), two))
+            legs = {name: ([], []) for name, _ in calls}
+            k = len(calls)
+            for n in range(total):
+                for name, fn in calls[n % k:] + calls[:n % k]:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    e0.record()
+                    fn(n)
+                    e1.record()
+                    e1.synchronize()
+                    t1 = time.perf_counter()
+                    if n >= warmup:
+                        legs[name][0].append((t1 - t0) * 1e3)
+                        legs[name][1].append(e0.elapsed_time(e1))
+        torch.cuda.synchronize()
+        for leg, (wall, gpu) in legs.items():
+            wall.sort()
+            gpu.sort()
+            q = lambda v, f: v[int(f * (len(v) - 1))]
+            out.append((B, leg, statistics.median(wall), q(wall, 0.9), q(gpu, 0.1), statistics.median(gpu), q(gpu, 0.9)))
+    return out
+
+
+def rows_report(m, dev, batches, steps, warmup, dims, start, C, device_name):
+    """The --rows report: the table, then the two conditions of the feature read off it."""
+    s = m.spec
+    got = rows_leg(m, dev, batches, steps, warmup, dims, start, C)
+    lines = ["# step_rows(): generating and observing rows in one step (tools/stream_latency.py --rows)", "",
+             "final_model.yaml as shipped (C = %d, S = %d, K = %d, H = %d, D = %d), engine precision %s; caller on its own stream; every "
+             "leg of a batch size interleaved step by step in one process, the order rotating; %d timed steps after %d warm-up steps; "
+             "wall = step to result on the host (a synchronise after every call), GPU = HIP events around the call. Device %s."
+             % (C, s.S, s.Ks, s.H, s.D, m.precision, steps, warmup, device_name), "",
+             "| B | leg | wall ms, median | wall ms, p90 | GPU ms, p10 | GPU ms, median | GPU ms, p90 |", "|---|---|---|---|---|---|---|"]
+    table = {}
+    for B, leg, med, p90, g10, gmed, g90 in got:
+        lines.append("| %d | %s | %.3f | %.3f | %.3f | %.3f | %.3f |" % (B, leg, med, p90, g10, gmed, g90))
+        table[(B, leg[:3])] = table.get((B, leg[:3]), []) + [(leg, med, g10, gmed, g90)]
+    lines += ["", "## The two conditions", ""]
+    for B in batches:
+        a, b = table.get((B, "(a)"), []), table.get((B, "(b)"), [])
+        for (pl, pw, p10, pg, p90), (rl, rw, _, rg, _) in zip(a, b):
+            lines.append("- B = %d: %s %.3f ms GPU (%.3f wall) against %s %.3f (%.3f): %+.3f ms GPU, %+.3f ms wall; the pure leg's own "
+                         "p10 .. p90 spread is %.3f ms GPU." % (B, rl[4:], rg, rw, pl[4:], pg, pw, rg - pg, rw - pw, p90 - p10))
+        c, e = table.get((B, "(c)")), table.get((B, "(e)"))
+        if c and e:
+            lines.append("- B = %d: (c) tile-aligned halves %.3f ms GPU (%.3f wall) against (e) two sessions of %d rows %.3f (%.3f): "
+                         "step_rows %s." % (B, c[0][3], c[0][1], B // 2, e[0][3], e[0][1],
+                                            "is faster" if c[0][1] < e[0][1] and c[0][3] < e[0][3] else "is NOT faster"))
+        d = table.get((B, "(d)"))
+        if c and d:
+            lines.append("- B = %d: (d) roles interleaved inside every tile %.3f ms GPU (%.3f wall): %.2f x the tile-aligned step."
+                         % (B, d[0][3], d[0][1], d[0][3] / c[0][3]))
+    return "\n".join(lines) + "\n"
 
 
 if __name__ == "__main__":
