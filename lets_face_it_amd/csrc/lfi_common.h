@@ -43,7 +43,7 @@ static inline bool lfi_env_set(const char* name) {
   return e && e[0] == '1';
 }
 
-// ---- internal (not part of the C ABI): the sampler's fused per-frame conditioning (lfi_sample.hip), called by lfi_flow.hip
+// ---- internal (not part of the C ABI): the sampler's fused per-frame conditioning (lfi_sample.hip), called by lfi_flow_chain.hip
 extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond_ok(int D, int G, int K1);
 extern "C" __attribute__((visibility("hidden"))) long lfi_internal_sample_cond_bytes(int B, int Ks, int G, int K1);
 extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond_prepare(const float* wct, long ldw, int col0, int K1, const float* wc,

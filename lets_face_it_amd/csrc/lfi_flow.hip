@@ -14,395 +14,13 @@
 // (a W, [z1|h] [Wz|Whh]^T, h' Wfl^T and their transposes in backward) run on v_mfma_f32_16x16x4_f32 with the A
 // operand staged k-major in LDS and the weights streamed from L2 as coalesced row segments; all elementwise math
 // (actnorm, gates, LinearZeros scaling, affine coupling, log-det) is fused around them in fp32.
-#include <math.h>
-#include <stdlib.h>
-
-#include "lfi_common.h"
+//
+// This unit is the TRAINING side: the diagonal and the persistent walks, forward and backward, the NLL, the prep kernels, the invconv
+// backward, the ActNorm init and the parameter gradients. The per-frame side - the samplers' and the streaming sessions' cells and
+// chains and their entry points - is lfi_flow_chain.hip; what both use (the generic cell bodies among it) is lfi_flow_cells.h.
+#include "lfi_flow_cells.h"
 
 namespace {
-
-constexpr int MB = 16;        // samples per workgroup
-constexpr int NT = 512;       // threads per workgroup (8 waves: one 16-wide hidden tile each at H = 128)
-constexpr int NW = NT / 64;
-constexpr int LT = MB + 1;    // k-major LDS leading dimension. (ds_read_b32 / ds_write_b32 bank = dword address mod 32, 32 lanes per LDS cycle:
-                              // with a pitch of 17 a column-of-k store (one row, 32 consecutive k) is conflict-free and the MFMA A-operand read
-                              // of two consecutive k rows x 16 lanes puts ONE lane of the second row on the first row's bank 0 - the extra cycle
-                              // SQ_LDS_BANK_CONFLICT counts on nearly every such read (36 - 40 % of the walks' LDS cycles). Round 4 tried a
-                              // pitch of 16 with 2 floats after every fourth row (reads conflict-free, stores 2 - 4-way): the counter stayed at
-                              // 36 - 40 % - it is not these reads that it counts - and the backward cell's Q3 went from 2.5 k to 5.4 k cycles:
-                              // reverted, profiles/round4_walk_ab.md.)
-constexpr float LOG2PI_F = 1.8378770664093453f;
-constexpr float LN2_F = 0.6931471805599453f;
-
-struct FlowK {
-  // dims
-  int B, N, C, H, D, Ks, affine, lstm;
-  float eps;
-  int Ch, C2, Cout, G, I, F, nbt;
-  int ldc, ldo;   // row strides of the (rows x C) and (rows x Cout) stash arrays: C and Cout rounded up to 4 floats, so that the
-                  // deferred weight-gradient products over them read 16-byte aligned rows (bf16x3 / vector-load paths)
-  // params
-  lfi_flow_params p;
-  // prep
-  const float *W, *Wt, *Winv, *wz_t, *whh_t, *wfl_t, *wc, *ldconst;
-  // prep, zero-padded images for the register-resident cell kernels (k rows padded to 4, columns to 16)
-  const float *pW, *pWt, *pwz, *pwh, *pwfl, *bwfl, *bwh, *bwz, *pWinv;
-  // backward recurrent weights pre-split into bf16 hi / lo 32-k fragments (bf16 x 3 walk): [Ks][NG][H16/32][J][4 lane groups],
-  // one uint4 per entry and plane; the lo plane follows the hi plane of an image
-  const uint4 *xbwh, *xbwz;
-  // reverse (sampling) cell weights pre-split into fp16 hi / lo 32-k fragments (flow_prep_x3h_kernel): images of pwz, pwh, pwfl and
-  // pWinv, entry (32-k block b, lane group kq, column) = x3h_pack of the two f32x4 entries the cell used to load and split itself;
-  // one uint4 per entry and plane, the lo plane follows the hi plane of a flow step's image. Null unless lfi_flow_prep made them.
-  const uint4 *hwz, *hwh, *hwfl, *hWinv;
-  int dgi_hi_only;         // the dgi planes' hi halves only (their consumers take them as a rounded A operand: two products)
-  int g16;                 // backward walk (planes mode): the dgi | dgh ROWS of the backward stash are bf16 arrays of the same shapes -
-                           // their readers, the thin weight-gradient products, round that operand to bf16 anyway (two products):
-                           // lfi_flow_dims.gemm_precision bit 16, honoured by lfi_flow_seq_bwd_planes and lfi_flow_param_grads alike
-  __bf16* bDgiR;           // backward walk (bf16x3): dgi also as operand planes of the (Ks F x G) matrix (lfi_flow_seq_bwd_planes)
-  int C16, Ch16, H16, Co16, NG;
-  // forward stash
-  float *sA, *sY, *sX, *sH, *sG, *sO, *sL, *sC;   // sC: LSTM cell state (lstm only)
-  // backward stash
-  float *bDlin, *bDgi, *bDgh, *bDy, *bDx, *bDh, *bPlfl, *bPan, *bDc;   // bDc: carried d cell state (lstm only)
-  float* bPbias;   // [Ks][nbt][2][G]: per-workgroup sums over timesteps and the tile's rows of dgi | dgh (persistent walk only)
-  // sequence inputs
-  const float* x0; int T, start;
-  const float* gic;
-  float gscale;
-  unsigned long long* stamps;  // diagnostics only (lfi_debug_set_stamps): s_memtime at phase boundaries, else null
-  int stamp_k;                 // flow step whose workgroup (tile 0) stamps (LFI_STAMP_K, default Ks / 2)
-  int pipe_fence;              // 1: consumers run an agent-scope acquire after the poll and read the tile with plain loads
-                               // 0: no fence, every load of a handed-off tile is an sc1 load (L1 bypass)
-  unsigned* pipe;              // persistent-pipeline state (flow_pipe_*_kernel): [0] ticket, [1] abort, [4 + k * nbt + bt] progress
-};
-
-// Everything one forward cell touches, resolved to pointers for its (k, frame block).
-struct CellIO {
-  int k, rows;            // flow step, valid rows in this call (<= B)
-  const float* x_in; long ldx;   // rows x C
-  const float* h_prev;    // rows x H or null (zeros)
-  const float* c_prev;    // LSTM cell state, rows x H or null (zeros); unused for GRU
-  float* c_out;           // LSTM: new cell state (required when lstm)
-  const float* gic;       // rows x G
-  float *a_out, *y_out, *x_out, *h_out, *g_out, *o_out, *l_out;  // nullable stashes; x_out/h_out required
-  long ldxo;              // leading dimension of x_out
-  long ld_c, ld_o;        // leading dimensions of a_out / y_out and of o_out
-  int l_accumulate;       // l_out += instead of =
-  int stamp_base;         // diagnostics (lfi_debug_set_stamps): slot of this cell's first phase stamp + 1, 0 = none (rev_fast_cell)
-  int state_l2;           // reverse cell: read h_prev / c_prev with L1-bypassing (sc1) loads - the persistent reverse walk re-reads
-                          // the state its own workgroup stored one timestep earlier, with no kernel boundary in between
-  const int* role;        // row-masked cells (flow_rows_chain_kernel) only: one word per batch row, != 0 = the row observes
-  int role_want;          // ... and the role this cell stores for (0: generating rows, 1: observing rows); other rows are never stored
-};
-
-extern __shared__ __attribute__((aligned(16))) float flow_smem[];
-
-__device__ __forceinline__ int rup16(int x) { return (x + 15) & ~15; }
-
-// The rows of the 16-row tile at b0 that a row-masked cell stores: bit i = row b0 + i is inside the batch and has the role `want`.
-// The same for every thread of the workgroup (a uniform read of the tile's 16 role words).
-__device__ __forceinline__ unsigned tile_live_rows(const int* role, int want, int b0, int rows) {
-  unsigned m = 0u;
-#pragma unroll
-  for (int i = 0; i < MB; ++i) {
-    const int row = b0 + i;
-    if (row < rows && (role[row] != 0) == (want != 0)) m |= 1u << i;
-  }
-  return m;
-}
-
-// ---- shared phase: coupling net given z1 (Zt) and h_prev (Ht) in LDS -> new hidden (Hn, LDS) and o (Orm, LDS)
-__device__ __forceinline__ void coupling_net_phase(const FlowK& f, const CellIO& io, int b0, const float* Zt, const float* Ht,
-                                                   float* Hn, float* Orm, int tid) {
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, lq = lane >> 4;
-  const int k = io.k, H = f.H, G = f.G, Ch = f.Ch, Cout = f.Cout;
-  const float* wz = f.wz_t + (long)k * Ch * G;
-  const float* wh = f.whh_t + (long)k * H * G;
-  const float* bhh = f.p.b_hh + (long)k * G;
-  const int nht = (H + 15) >> 4;
-  if (f.lstm) {
-    // torch.nn.LSTMCell (gate order i, f, g, o) from zero (h, c) at the first modelled frame (glow/models.py:181-185,
-    // 209-213; the reference's own call crashes there, SURVEY.md finding 2: semantics = zero initial state)
-    for (int t = wave; t < nht; t += NW) {
-      const int j = t * 16 + l15;
-      const bool jok = j < H;
-      f32x4 gz[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-      mma16_pf<4>(gz, Zt, LT, wz + t * 16, G, H, Ch, jok, lane);
-      f32x4 gh[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-      mma16_pf<4>(gh, Ht, LT, wh + t * 16, G, H, H, jok, lane);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = lq * 4 + r;
-        const int row = b0 + i;
-        float hnew = 0.0f;
-        if (row < io.rows && jok) {
-          const float* gc = io.gic + (long)row * G;
-          const float ii = sigmoidf_(gz[0][r] + gh[0][r] + gc[j] + bhh[j]);
-          const float ff = sigmoidf_(gz[1][r] + gh[1][r] + gc[H + j] + bhh[H + j]);
-          const float gg = tanhf_(gz[2][r] + gh[2][r] + gc[2 * H + j] + bhh[2 * H + j]);
-          const float oo = sigmoidf_(gz[3][r] + gh[3][r] + gc[3 * H + j] + bhh[3 * H + j]);
-          const float cp = io.c_prev ? io.c_prev[(long)row * H + j] : 0.0f;
-          const float c2 = ff * cp + ii * gg;
-          hnew = oo * tanhf_(c2);
-          io.h_out[(long)row * H + j] = hnew;
-          io.c_out[(long)row * H + j] = c2;
-          if (io.g_out) {
-            float* gs = io.g_out + (long)row * 4 * H;
-            *reinterpret_cast<f32x4*>(gs + 4 * j) = (f32x4){ii, ff, gg, oo};   // gate-interleaved stash: one 16-byte store
-          }
-        }
-        if (jok) Hn[j * LT + i] = hnew;
-      }
-    }
-  } else
-  for (int t = wave; t < nht; t += NW) {
-    const int j = t * 16 + l15;
-    const bool jok = j < H;
-    // input side (z1 part; the conditioning part was hoisted into gic): r, z, n chains share the A operand
-    f32x4 gz[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    mma16_pf<3>(gz, Zt, LT, wz + t * 16, G, H, Ch, jok, lane);
-    // hidden side
-    f32x4 gh[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    mma16_pf<3>(gh, Ht, LT, wh + t * 16, G, H, H, jok, lane);
-    const f32x4 ar = gz[0] + gh[0], au = gz[1] + gh[1], ain = gz[2], ahn = gh[2];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = lq * 4 + r;
-      const int row = b0 + i;
-      float hnew = 0.0f;
-      if (row < io.rows && jok) {
-        const float* gc = io.gic + (long)row * G;
-        const float rr = sigmoidf_(ar[r] + gc[j] + bhh[j]);
-        const float uu = sigmoidf_(au[r] + gc[H + j] + bhh[H + j]);
-        const float ghn = ahn[r] + bhh[2 * H + j];
-        const float nn = tanhf_(ain[r] + gc[2 * H + j] + rr * ghn);
-        const float hp = Ht[j * LT + i];
-        hnew = (1.0f - uu) * nn + uu * hp;
-        io.h_out[(long)row * H + j] = hnew;
-        if (io.g_out) {
-          float* gs = io.g_out + (long)row * 4 * H;
-          *reinterpret_cast<f32x4*>(gs + 4 * j) = (f32x4){rr, uu, nn, ghn};
-        }
-      }
-      if (jok) Hn[j * LT + i] = hnew;
-    }
-  }
-  __syncthreads();
-  // o = (h' Wfl^T + b) * exp(3 logs)    (LinearZeros, glow/modules.py:93-95)
-  const float* wf = f.wfl_t + (long)k * H * Cout;
-  const float* bfl = f.p.b_fl + (long)k * Cout;
-  const float* lfl = f.p.l_fl + (long)k * Cout;
-  const int not_ = (Cout + 15) >> 4;
-  const int ldo = Cout + 1;
-  for (int t = wave; t < not_; t += NW) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = tile16_lds_glb(acc, Hn, LT, wf + t * 16, Cout, H, min(16, Cout - t * 16), lane);
-    const int col = t * 16 + l15;
-    if (col < Cout) {
-      const float bb = bfl[col], sc = expf(3.0f * lfl[col]);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = lq * 4 + r;
-        const int row = b0 + i;
-        const float o = (acc[r] + bb) * sc;
-        Orm[i * ldo + col] = o;
-        if (io.o_out && row < io.rows) io.o_out[(long)row * io.ld_o + col] = o;
-      }
-    }
-  }
-  __syncthreads();
-}
-
-// LDS carve for the cell kernels (floats). Every k-major block is [dim][LT].
-struct Carve {
-  int At, Ht, Zt, Hn, Yrm, Orm, Lg, total;
-};
-__host__ __device__ inline Carve carve_fwd(int C, int H, int Ch, int C2, int Cout) {
-  Carve c;
-  int o = 0;
-  c.At = o; o += C * LT;
-  c.Ht = o; o += H * LT;
-  c.Zt = o; o += (Ch > 0 ? Ch : 1) * LT;
-  c.Hn = o; o += H * LT;
-  c.Yrm = o; o += MB * (C + 1);
-  c.Orm = o; o += MB * (Cout + 1);
-  c.Lg = o; o += MB * (C2 + 1);
-  c.total = o;
-  return c;
-}
-
-// ------------------------------------------------------------------------------------------- forward cell
-__device__ void cell_forward(const FlowK& f, const CellIO& io, int b0) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, lq = lane >> 4;
-  const int C = f.C, H = f.H, Ch = f.Ch, C2 = f.C2, Cout = f.Cout, k = io.k;
-  const Carve cv = carve_fwd(C, H, Ch, C2, Cout);
-  float* At = flow_smem + cv.At;
-  float* Ht = flow_smem + cv.Ht;
-  float* Zt = flow_smem + cv.Zt;
-  float* Hn = flow_smem + cv.Hn;
-  float* Yrm = flow_smem + cv.Yrm;
-  float* Orm = flow_smem + cv.Orm;
-  float* Lg = flow_smem + cv.Lg;
-  const int ldy = C + 1, ldo = Cout + 1, ldl = C2 + 1;
-
-  // P0: actnorm (glow/modules.py:45-52), stage a and h_prev k-major
-  const float* anb = f.p.an_bias + (long)k * C;
-  const float* anl = f.p.an_logs + (long)k * C;
-  for (int idx = tid; idx < MB * C; idx += NT) {
-    const int i = idx / C, c = idx - i * C;
-    const int row = b0 + i;
-    float a = 0.0f;
-    if (row < io.rows) {
-      a = (io.x_in[(long)row * io.ldx + c] + anb[c]) * expf(anl[c]);
-      if (io.a_out) io.a_out[(long)row * io.ld_c + c] = a;
-    }
-    At[c * LT + i] = a;
-  }
-  for (int idx = tid; idx < MB * H; idx += NT) {
-    const int i = idx / H, j = idx - i * H;
-    const int row = b0 + i;
-    Ht[j * LT + i] = (io.h_prev && row < io.rows) ? io.h_prev[(long)row * H + j] : 0.0f;
-  }
-  __syncthreads();
-
-  // P1: y = a W   (InvertibleConv1x1.forward, glow/modules.py:186; row-vector convention)
-  {
-    const float* W = f.W + (long)k * C * C;
-    const int nt = (C + 15) >> 4;
-    for (int t = wave; t < nt; t += NW) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      acc = tile16_lds_glb(acc, At, LT, W + t * 16, C, C, min(16, C - t * 16), lane);
-      const int c = t * 16 + l15;
-      if (c < C) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = lq * 4 + r;
-          const int row = b0 + i;
-          const float v = acc[r];
-          Yrm[i * ldy + c] = v;
-          if (c < Ch) Zt[c * LT + i] = v;
-          if (io.y_out && row < io.rows) io.y_out[(long)row * io.ld_c + c] = v;
-        }
-      }
-    }
-  }
-  __syncthreads();
-
-  // P2 + P3: coupling net
-  coupling_net_phase(f, io, b0, Zt, Ht, Hn, Orm, tid);
-
-  // P4: coupling (glow/models.py:330-341) and pass-through half
-  for (int idx = tid; idx < MB * C2; idx += NT) {
-    const int i = idx / C2, jj = idx - i * C2;
-    const int row = b0 + i;
-    const float z2 = Yrm[i * ldy + Ch + jj];
-    float z2n, lg = 0.0f;
-    if (f.affine) {
-      const float shift = Orm[i * ldo + 2 * jj];
-      const float sraw = sigmoidf_(Orm[i * ldo + 2 * jj + 1] + 2.0f);
-      const float sc = fmaxf(sraw, f.eps);
-      z2n = (z2 + shift) * sc;
-      lg = logf(sc);
-    } else {
-      z2n = z2 + Orm[i * ldo + jj];
-    }
-    Lg[i * ldl + jj] = lg;
-    if (row < io.rows) io.x_out[(long)row * io.ldxo + Ch + jj] = z2n;
-  }
-  for (int idx = tid; idx < MB * Ch; idx += NT) {
-    const int i = idx / Ch, c = idx - i * Ch;
-    const int row = b0 + i;
-    if (row < io.rows) io.x_out[(long)row * io.ldxo + c] = Yrm[i * ldy + c];
-  }
-  __syncthreads();
-  if (tid < MB && io.l_out) {
-    const int row = b0 + tid;
-    if (row < io.rows) {
-      float s = 0.0f;
-      for (int jj = 0; jj < C2; ++jj) s += Lg[tid * ldl + jj];
-      if (io.l_accumulate) io.l_out[row] += s; else io.l_out[row] = s;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------- reverse cell
-// FlowStep.reverse_flow (glow/models.py:345-373): coupling^-1 -> invconv^-1 -> actnorm^-1.
-__device__ void cell_reverse(const FlowK& f, const CellIO& io, int b0) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, lq = lane >> 4;
-  const int C = f.C, H = f.H, Ch = f.Ch, C2 = f.C2, Cout = f.Cout, k = io.k;
-  const Carve cv = carve_fwd(C, H, Ch, C2, Cout);
-  float* Yt = flow_smem + cv.At;   // y = [z1 | z2] k-major for the W^-1 product
-  float* Ht = flow_smem + cv.Ht;
-  float* Zt = flow_smem + cv.Zt;
-  float* Hn = flow_smem + cv.Hn;
-  float* Yrm = flow_smem + cv.Yrm;
-  float* Orm = flow_smem + cv.Orm;
-  float* Lg = flow_smem + cv.Lg;
-  const int ldy = C + 1, ldo = Cout + 1, ldl = C2 + 1;
-
-  for (int idx = tid; idx < MB * C; idx += NT) {
-    const int i = idx / C, c = idx - i * C;
-    const int row = b0 + i;
-    const float v = row < io.rows ? io.x_in[(long)row * io.ldx + c] : 0.0f;
-    Yrm[i * ldy + c] = v;
-    if (c < Ch) { Zt[c * LT + i] = v; Yt[c * LT + i] = v; }
-  }
-  for (int idx = tid; idx < MB * H; idx += NT) {
-    const int i = idx / H, j = idx - i * H;
-    const int row = b0 + i;
-    Ht[j * LT + i] = (io.h_prev && row < io.rows) ? io.h_prev[(long)row * H + j] : 0.0f;
-  }
-  __syncthreads();
-  coupling_net_phase(f, io, b0, Zt, Ht, Hn, Orm, tid);
-  for (int idx = tid; idx < MB * C2; idx += NT) {
-    const int i = idx / C2, jj = idx - i * C2;
-    const float z2n = Yrm[i * ldy + Ch + jj];
-    float z2, lg = 0.0f;
-    if (f.affine) {
-      const float shift = Orm[i * ldo + 2 * jj];
-      const float sraw = sigmoidf_(Orm[i * ldo + 2 * jj + 1] + 2.0f);
-      const float sc = fmaxf(sraw, f.eps);
-      z2 = z2n / sc;
-      z2 = z2 - shift;
-      lg = -logf(sc);
-    } else {
-      z2 = z2n - Orm[i * ldo + jj];
-    }
-    Lg[i * ldl + jj] = lg;
-    Yt[(Ch + jj) * LT + i] = z2;
-  }
-  __syncthreads();
-  {
-    const float* Wi = f.Winv + (long)k * C * C;
-    const float* anb = f.p.an_bias + (long)k * C;
-    const float* anl = f.p.an_logs + (long)k * C;
-    const int nt = (C + 15) >> 4;
-    for (int t = wave; t < nt; t += NW) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      acc = tile16_lds_glb(acc, Yt, LT, Wi + t * 16, C, C, min(16, C - t * 16), lane);
-      const int c = t * 16 + l15;
-      if (c < C) {
-        const float es = expf(-anl[c]), bb = anb[c];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = b0 + lq * 4 + r;
-          if (row < io.rows) io.x_out[(long)row * io.ldxo + c] = acc[r] * es - bb;  // scale then center (modules.py:76-79)
-        }
-      }
-    }
-  }
-  if (tid < MB && io.l_out) {
-    const int row = b0 + tid;
-    if (row < io.rows) {
-      float s = 0.0f;
-      for (int jj = 0; jj < C2; ++jj) s += Lg[tid * ldl + jj];
-      if (io.l_accumulate) io.l_out[row] += s; else io.l_out[row] = s;
-    }
-  }
-}
 
 __global__ __launch_bounds__(NT) void flow_diag_fwd_kernel(FlowK f, int d, int klo) {
   const int k = klo + blockIdx.y, n = d - k;
@@ -427,17 +45,10 @@ __global__ __launch_bounds__(NT) void flow_diag_fwd_kernel(FlowK f, int d, int k
   cell_forward(f, io, blockIdx.x * MB);
 }
 
-template <bool REVERSE>
-__global__ __launch_bounds__(NT) void flow_step_kernel(FlowK f, CellIO io) {
-  if (REVERSE) cell_reverse(f, io, blockIdx.x * MB);
-  else cell_forward(f, io, blockIdx.x * MB);
-}
-
 // nll[f] = -(logdet + sum_c -0.5 (z^2 + log 2pi)) / ln 2   (SeqGlow.loss, glow/models.py:563-565)
 // 64 frames per workgroup: their z rows (C floats at stride ldc) come in through LDS with coalesced loads (and leave to the
 // caller's z the same way); thread i then sums frame i's row in column order - one thread per frame reading its row straight from
 // memory took 30 us of the step's critical path between the two walks for 3.7 MB. C > NLL_CMAX: that form (STAGED = false).
-constexpr int NLL_FR = 64, NLL_CMAX = 128;
 template <bool STAGED>
 __global__ __launch_bounds__(256) void flow_nll_kernel(FlowK f, float* __restrict__ z, float* __restrict__ nll) {
   extern __shared__ float nll_rows[];   // [NLL_FR][C + 1]
@@ -718,451 +329,6 @@ __global__ __launch_bounds__(NT) void flow_diag_bwd_kernel(FlowK f, int d, int k
   }
 }
 
-// ------------------------------------------------------------------------------------------- register-resident cells
-// Same cells for the common sizes (C <= 64, H <= 128): the generic kernels above stream every weight chunk from L2 inside
-// the dependent MFMA chains (4 phases x ~10 chunk round trips per cell: ~54 % of a wave's life is s_waitcnt, rocprof
-// PMC). Weights do not depend on the data, so here each wave issues the loads of ITS slice of a phase's weights one phase
-// ahead, into registers (<= 136 VGPRs), from zero-padded images made by lfi_flow_prep, and the k loops run MFMA-paced
-// from registers + LDS. Image layout = MFMA B-fragment order in blocks of 16 k: element (k, column) of a K x J operand
-// sits at (((k / 16) * 4 + k % 4) * J16 + column) * 4 + (k / 4) % 4, so the four k-steps of a block are ONE 16-byte load
-// per lane and a wave-load is four 256-byte segments (dword-per-lane loads spent 12k cycles per cell in issue alone,
-// s_memtime stamps). K and J are padded to 16 with zeros: no bounds checks. Elementwise phases use a fixed
-// (row = tid / 32, column = tid % 32 [+ 32]) thread map: no integer divisions, 128-byte row segments.
-#define LFI_STAMP(slot)                                                                                  \
-  do {                                                                                                   \
-    if (f.stamps && tid == 0 && bt == 0) f.stamps[cell * 16 + (slot)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-
-constexpr int FB_C = 4;   // blocks of 16 k over C    <= 64
-constexpr int FB_Z = 2;   //                 over Ch   <= 32
-constexpr int FB_H = 8;   //                 over H    <= 128
-constexpr int FB_O = 4;   //                 over Cout <= 64
-
-__host__ __device__ inline bool flow_fast_ok(int C, int H, int Cout) { return C <= 64 && H <= 128 && Cout <= 64; }
-__host__ __device__ inline long flow_img_index(int k, int col, int J) {
-  return ((long)((k >> 4) * 4 + (k & 3)) * J + col) * 4 + ((k >> 2) & 3);
-}
-
-// Workgroup -> (cell, batch tile). Workgroups are dealt round-robin over the 8 XCDs (block b and b + 8 share one), and every
-// cell of a diagonal needs its own 270 KB of weights: give each XCD a contiguous run of (cell, tile) pairs so that a cell's
-// 16 batch tiles (and the same flow step on the next diagonal) hit the same 4 MB L2 instead of all 8 L2s holding all 16
-// steps' weights (4.3 MB: thrashing). Bijective for any grid size; speed only, never correctness.
-__device__ __forceinline__ void flow_cell_of_block(int nbt, int* cell, int* bt) {
-  const int total = gridDim.x * gridDim.y;
-  int bid = blockIdx.x + gridDim.x * blockIdx.y;
-  const int q = total >> 3, r = total & 7, xcd = bid & 7, idx = bid >> 3;
-  bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  *cell = bid / nbt;
-  *bt = bid - *cell * nbt;
-}
-
-struct CarveF {
-  int At, Ht, Zt, Hn, Yrm, Orm, total;
-};
-__host__ __device__ inline CarveF carve_fast_fwd(int C, int C16, int H16, int Ch16, int Cout) {
-  CarveF c;
-  int o = 0;
-  c.At = o; o += C16 * LT;
-  c.Ht = o; o += H16 * LT;
-  c.Zt = o; o += Ch16 * LT;
-  c.Hn = o; o += H16 * LT;
-  c.Yrm = o; o += MB * (C + 1);
-  c.Orm = o; o += MB * (Cout + 1);
-  c.total = o;
-  return c;
-}
-
-// sum over nb blocks of 16 k: A(16 x 16 nb) from LDS (k-major: a_lane = a_lds + kq * LT + l15, element k at + k * LT) times
-// the register-resident B slice w[b] (components e: k = 16 b + 4 e + kq). Two interleaved chains (40-cycle dependent latency
-// against a 32-cycle issue).
-template <int MAXB>
-__device__ __forceinline__ f32x4 mma16_reg(const float* a_lane, const f32x4 (&w)[MAXB], int nb) {
-  f32x4 e = {0.f, 0.f, 0.f, 0.f}, o = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int b = 0; b < MAXB; ++b)
-    if (b < nb) {
-      const float* ab = a_lane + b * 16 * LT;
-      const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
-      e = mfma16(a0, w[b][0], e);
-      o = mfma16(a1, w[b][1], o);
-      e = mfma16(a2, w[b][2], e);
-      o = mfma16(a3, w[b][3], o);
-    }
-  return e + o;
-}
-
-// this lane's slice of one 16-column tile of an image: nb float4 (k blocks), image row pitch J (columns, multiple of 16)
-template <int MAXB>
-__device__ __forceinline__ void load_frag(f32x4 (&w)[MAXB], const float* __restrict__ img, int J, int col, int kq, int nb,
-                                          bool on) {
-  const f32x4* p = reinterpret_cast<const f32x4*>(img) + (long)kq * J + col;
-#pragma unroll
-  for (int b = 0; b < MAXB; ++b)
-    if (on && b < nb) w[b] = p[(long)b * 4 * J];
-}
-
-// ---- bf16 x 3 form of the recurrent products (persistent walk, engine_precision bf16x3). The f32-input MFMA the cells use
-// everywhere else runs at 1/16 of the bf16 rate, and with flow step k's weights resident the recurrent cell's
-// (z1, h) x (W_ih[:, :Ch], W_hh) product is what a pipeline step waits for (46 % of a forward step, tools/pipe_stamps.py).
-// Same split as the GEMMs: x = hi + lo in bf16, hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_bf16 into fp32 accumulators.
-// No new weight images: two consecutive 16-k blocks of the f32 fragment registers (components e: k = 16 b + 4 e + kq) are
-// split in registers once per launch into one 32-k bf16 fragment, slot i of lane group kq standing for
-// k = 32 B + 16 (i >> 2) + 4 (i & 3) + kq - any bijection does as long as the A operand uses the same one, and this one
-// makes the A side exactly the LDS reads the f32 path already does.
-typedef __bf16 fbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 fbf16x2 __attribute__((ext_vector_type(2)));
-typedef float ffloat2 __attribute__((ext_vector_type(2)));
-struct X3Frag { fbf16x8 hi, lo; };
-__device__ __forceinline__ void x3_split2(float a, float b, unsigned* hi, unsigned* lo) {
-  const fbf16x2 h = __builtin_convertvector((ffloat2){a, b}, fbf16x2);
-  const unsigned hb = __builtin_bit_cast(unsigned, h);
-  const float ha = __builtin_bit_cast(float, hb << 16), hbv = __builtin_bit_cast(float, hb & 0xffff0000u);
-  const fbf16x2 l = __builtin_convertvector((ffloat2){a - ha, b - hbv}, fbf16x2);
-  *hi = hb;
-  *lo = __builtin_bit_cast(unsigned, l);
-}
-__device__ __forceinline__ X3Frag x3_pack(const f32x4& b0, const f32x4& b1) {
-  uint4 h, l;
-  x3_split2(b0[0], b0[1], &h.x, &l.x);
-  x3_split2(b0[2], b0[3], &h.y, &l.y);
-  x3_split2(b1[0], b1[1], &h.z, &l.z);
-  x3_split2(b1[2], b1[3], &h.w, &l.w);
-  X3Frag r;
-  r.hi = __builtin_bit_cast(fbf16x8, h);
-  r.lo = __builtin_bit_cast(fbf16x8, l);
-  return r;
-}
-// A fragment of 32 k from a k-major LDS operand: the eight reads of two f32 blocks
-__device__ __forceinline__ X3Frag x3_a(const float* ab) {
-  f32x4 b0 = {ab[0], ab[4 * LT], ab[8 * LT], ab[12 * LT]};
-  const float* a1 = ab + 16 * LT;
-  f32x4 b1 = {a1[0], a1[4 * LT], a1[8 * LT], a1[12 * LT]};
-  return x3_pack(b0, b1);
-}
-__device__ __forceinline__ f32x4 x3_mma(const X3Frag& a, const X3Frag& w, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo, w.hi, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, w.lo, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, w.hi, acc, 0, 0, 0);
-  return acc;
-}
-
-// ---- the same with fp16 pieces (11 + 11 mantissa bits: 2^-22 relative, fp32-grade) for the SAMPLER's reverse cells. Their
-// operands - h in (-1, 1), flow activations, trained weights - sit far inside fp16's range (a value beyond 65504 turns into
-// inf - inf = NaN: loud, as the exact path is at 3e38; tiny values lose nothing that matters: fp16's subnormal spacing, 6e-8,
-// is the absolute error of an fp32 near 1). Gradients do not qualify (1e-10 underflows), so every backward product and the
-// training walks keep bf16 pieces. Same MFMA rate, same register footprint as bf16 x 3.
-typedef _Float16 fh16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 fh16x2 __attribute__((ext_vector_type(2)));
-struct X3FragH { fh16x8 hi, lo; };
-__device__ __forceinline__ void x3h_split2(float a, float b, unsigned* hi, unsigned* lo) {
-  const fh16x2 h = __builtin_convertvector((ffloat2){a, b}, fh16x2);
-  const ffloat2 hf = __builtin_convertvector(h, ffloat2);
-  const fh16x2 l = __builtin_convertvector((ffloat2){a - hf[0], b - hf[1]}, fh16x2);
-  *hi = __builtin_bit_cast(unsigned, h);
-  *lo = __builtin_bit_cast(unsigned, l);
-}
-__device__ __forceinline__ X3FragH x3h_pack(const f32x4& b0, const f32x4& b1) {
-  uint4 h, l;
-  x3h_split2(b0[0], b0[1], &h.x, &l.x);
-  x3h_split2(b0[2], b0[3], &h.y, &l.y);
-  x3h_split2(b1[0], b1[1], &h.z, &l.z);
-  x3h_split2(b1[2], b1[3], &h.w, &l.w);
-  X3FragH r;
-  r.hi = __builtin_bit_cast(fh16x8, h);
-  r.lo = __builtin_bit_cast(fh16x8, l);
-  return r;
-}
-__device__ __forceinline__ X3FragH x3h_a(const float* ab) {
-  f32x4 b0 = {ab[0], ab[4 * LT], ab[8 * LT], ab[12 * LT]};
-  const float* a1 = ab + 16 * LT;
-  f32x4 b1 = {a1[0], a1[4 * LT], a1[8 * LT], a1[12 * LT]};
-  return x3h_pack(b0, b1);
-}
-__device__ __forceinline__ f32x4 x3h_mma(const X3FragH& a, const X3FragH& w, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.lo, w.hi, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, w.lo, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, w.hi, acc, 0, 0, 0);
-  return acc;
-}
-
-// this lane's fragments of one 16-column tile of a pre-split backward image: nb2 32-k blocks of gate g
-template <int MAXB2>
-__device__ __forceinline__ void x3_load(X3Frag (&w)[MAXB2], const uint4* __restrict__ img, long per, int g, int nB, int J, int col,
-                                        int kq, int nb2, bool on) {
-  const uint4* p = img + (((long)g * nB) * J + col) * 4 + kq;
-#pragma unroll
-  for (int b = 0; b < MAXB2; ++b)
-    if (on && b < nb2) {
-      w[b].hi = __builtin_bit_cast(fbf16x8, p[(long)b * J * 4]);
-      w[b].lo = __builtin_bit_cast(fbf16x8, p[(long)b * J * 4 + per]);
-    }
-}
-// sum over NG gate blocks of nb2 32-k blocks each (A: k-major LDS operand, gate stride blk floats)
-template <int NG, int MAXB2>
-__device__ __forceinline__ f32x4 x3_mma_gates(const float* a_lane, int blk, const X3Frag (&w)[NG][MAXB2], int nb2) {
-  f32x4 e = {0.f, 0.f, 0.f, 0.f}, o = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int g = 0; g < NG; ++g)
-#pragma unroll
-    for (int b = 0; b < MAXB2; ++b)
-      if (b < nb2) {
-        const X3Frag a = x3_a(a_lane + g * blk + b * 32 * LT);
-        if ((g * MAXB2 + b) & 1) o = x3_mma(a, w[g][b], o);
-        else e = x3_mma(a, w[g][b], e);
-      }
-  return e + o;
-}
-
-// The backward cell's MFMA operands d(gate pre-activations) are needed by all eight waves: instead of every wave splitting the
-// same fp32 LDS values again (24 blocks x ~30 VALU per wave and timestep - it bound Q2 once the MFMAs were bf16), the wave
-// that computes a value stores its bf16 hi and lo ONCE, row-major [16 rows][NG * H16 + 8], the column of hidden unit j of
-// gate g at g * H16 + x3_pos(j): within a 32-k block the slot order of x3_a, so a lane's 8 k are one 16-byte read.
-__device__ __forceinline__ int x3_pos(int j) { return (j & ~31) | ((j & 3) << 3) | ((j >> 2) & 7); }
-__device__ __forceinline__ void x3_put(__bf16* hi_img, __bf16* lo_img, int idx, float v) {
-  const __bf16 h = (__bf16)v;
-  hi_img[idx] = h;
-  lo_img[idx] = (__bf16)(v - (float)h);
-}
-template <int NG, int MAXB2>
-__device__ __forceinline__ f32x4 x3_mma_gates_img(const __bf16* hi_row, const __bf16* lo_row, int H16, const X3Frag (&w)[NG][MAXB2],
-                                                  int nb2) {
-  f32x4 e = {0.f, 0.f, 0.f, 0.f}, o = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int g = 0; g < NG; ++g)
-#pragma unroll
-    for (int b = 0; b < MAXB2; ++b)
-      if (b < nb2) {
-        X3Frag a;
-        a.hi = *reinterpret_cast<const fbf16x8*>(hi_row + g * H16 + b * 32);
-        a.lo = *reinterpret_cast<const fbf16x8*>(lo_row + g * H16 + b * 32);
-        if ((g * MAXB2 + b) & 1) o = x3_mma(a, w[g][b], o);
-        else e = x3_mma(a, w[g][b], e);
-      }
-  return e + o;
-}
-
-// P2 of a register-resident cell: the coupling net's recurrent cell on this wave's 16 hidden units. Zt / Ht: z1 and
-// h_prev in LDS (k-major), Hn: new state (LDS), h_out / c_out / g_out: row-0 pointers of the (rows x H) / (rows x 4H) outputs
-// (g_out may be null).
-// gate math + stores of P2 on this wave's 16 hidden units, given the two accumulated products (az: z1 side, ah: h side)
-// RM (row-masked cells): h_out / c_out are stored for the rows of `live` only (tile_live_rows), not for every row inside the batch.
-template <int NG, bool RM = false>
-__device__ __forceinline__ void fast_cell_p2_gates(const FlowK& f, const float* Ht, float* Hn, const f32x4 (&az)[NG],
-                                                   const f32x4 (&ah)[NG], const float (&gc)[4][NG], const float (&bh)[NG],
-                                                   const float (&cprev)[4], int j2, int kq, int b0, int rows, float* h_out,
-                                                   float* c_out, float* g_out, float* cnew, __bf16* img_hi = nullptr,
-                                                   __bf16* img_lo = nullptr, int img_ld = 0, int img_col = 0, unsigned live = 0u) {
-  const int H = f.H;
-  if (j2 < H) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = kq * 4 + r;
-      const int row = b0 + i;
-      const bool rs = RM ? ((live >> i) & 1u) != 0u : row < rows;   // this row's results go to memory
-      float hnew;
-      float gs0, gs1, gs2, gs3;
-      if (NG == 3) {  // torch.nn.GRUCell, gate order r, z, n
-        const float rr = sigmoidf_(az[0][r] + ah[0][r] + gc[r][0] + bh[0]);
-        const float uu = sigmoidf_(az[1][r] + ah[1][r] + gc[r][1] + bh[1]);
-        const float ghn = ah[2][r] + bh[2];
-        // (explicit fused forms: left to -ffp-contract, "(1 - z) n + z h" fuses either product, and which one depended on the
-        // kernel this function was inlined into - the persistent walk and the diagonal walk then differed by an ulp)
-        const float nn = tanhf_(__builtin_fmaf(rr, ghn, az[2][r] + gc[r][2]));
-        const float hp = Ht[j2 * LT + i];
-        hnew = __builtin_fmaf(uu, hp, (1.0f - uu) * nn);
-        gs0 = rr; gs1 = uu; gs2 = nn; gs3 = ghn;
-      } else {        // torch.nn.LSTMCell, gate order i, f, g, o; zero (h, c) at the first modelled frame
-        const float ii = sigmoidf_(az[0][r] + ah[0][r] + gc[r][0] + bh[0]);
-        const float ff = sigmoidf_(az[1][r] + ah[1][r] + gc[r][1] + bh[1]);
-        const float gg = tanhf_(az[2][r] + ah[2][r] + gc[r][2] + bh[2]);
-        const float oo = sigmoidf_(az[NG - 1][r] + ah[NG - 1][r] + gc[r][NG - 1] + bh[NG - 1]);
-        const float c2 = __builtin_fmaf(ff, cprev[r], ii * gg);
-        hnew = oo * tanhf_(c2);
-        if (rs) c_out[(long)row * H + j2] = c2;
-        if (cnew) cnew[r] = c2;
-        gs0 = ii; gs1 = ff; gs2 = gg; gs3 = oo;
-      }
-      Hn[j2 * LT + i] = hnew;
-      if (img_hi) x3_put(img_hi, img_lo, i * img_ld + img_col + x3_pos(j2), hnew);   // bf16 hi / lo image for the next cell's product
-      if (rs) {
-        if (h_out) h_out[(long)row * H + j2] = hnew;   // (null: the caller stores the tile's rows itself, 16 bytes at a time)
-        if (g_out) {
-          // the four stashed gate values of (row, hidden unit) lie together: ONE 16-byte store here and one 16-byte load in the
-          // backward cell instead of four dword accesses each (the walks are bound by vector-memory instruction issue:
-          // without the P2 stash stores the forward walk ran 11 % faster)
-          *reinterpret_cast<f32x4*>(g_out + (long)row * 4 * H + 4 * j2) = (f32x4){gs0, gs1, gs2, gs3};
-        }
-      }
-    }
-  }
-}
-
-template <int NG>
-__device__ __forceinline__ void fast_cell_p2(const FlowK& f, const float* Zt, const float* Ht, float* Hn,
-                                             const f32x4 (&wz)[NG][FB_Z], const f32x4 (&wh)[NG][FB_H], const float (&gc)[4][NG],
-                                             const float (&bh)[NG], const float (&cprev)[4], int nbZ, int nbH, int j2, int kq,
-                                             int l15, int b0, int rows, float* h_out, float* c_out, float* g_out,
-                                             float* cnew = nullptr) {
-  f32x4 az[NG], ah[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    az[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    ah[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-  const float* zl = Zt + kq * LT + l15;
-  const float* hl = Ht + kq * LT + l15;
-#pragma unroll
-  for (int b = 0; b < FB_Z; ++b)
-    if (b < nbZ) {
-      const float* ab = zl + b * 16 * LT;
-      const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
-#pragma unroll
-      for (int g = 0; g < NG; ++g) az[g] = mfma16(a0, wz[g][b][0], az[g]);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) az[g] = mfma16(a1, wz[g][b][1], az[g]);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) az[g] = mfma16(a2, wz[g][b][2], az[g]);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) az[g] = mfma16(a3, wz[g][b][3], az[g]);
-    }
-#pragma unroll
-  for (int b = 0; b < FB_H; ++b)
-    if (b < nbH) {
-      const float* ab = hl + b * 16 * LT;
-      const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
-#pragma unroll
-      for (int g = 0; g < NG; ++g) ah[g] = mfma16(a0, wh[g][b][0], ah[g]);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) ah[g] = mfma16(a1, wh[g][b][1], ah[g]);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) ah[g] = mfma16(a2, wh[g][b][2], ah[g]);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) ah[g] = mfma16(a3, wh[g][b][3], ah[g]);
-    }
-  fast_cell_p2_gates<NG>(f, Ht, Hn, az, ah, gc, bh, cprev, j2, kq, b0, rows, h_out, c_out, g_out, cnew);
-}
-
-// The same cell with its A operand (z1 | h_{t-1}) read from bf16 hi / lo LDS images the PRODUCERS wrote (P1 for z1, the previous
-// timestep's gate epilogue for h: x3_put, slot order x3_pos): one 16-byte read per 32-k block and plane instead of eight
-// 4-byte reads of the k-major fp32 images plus a split redone by all eight waves (stamps: 2.8 k of the 5.8 k cycles of P2).
-template <int NG>
-__device__ __forceinline__ void fast_cell_p2_x3_img(const FlowK& f, const __bf16* ih, const __bf16* il, int ldx, int Ch16,
-                                                    const float* Ht, float* Hn, const X3Frag (&wz)[NG][FB_Z / 2],
-                                                    const X3Frag (&wh)[NG][FB_H / 2], const float (&gc)[4][NG],
-                                                    const float (&bh)[NG], const float (&cprev)[4], int nbZ2, int nbH2, int j2,
-                                                    int kq, int l15, int b0, int rows, float* h_out, float* c_out, float* g_out,
-                                                    float* cnew, __bf16* ihn, __bf16* iln) {
-  f32x4 az[NG], ah[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    az[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    ah[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-  const __bf16* rh = ih + l15 * ldx + 8 * kq;
-  const __bf16* rl = il + l15 * ldx + 8 * kq;
-#pragma unroll
-  for (int b = 0; b < FB_Z / 2; ++b)
-    if (b < nbZ2) {
-      X3Frag a;
-      a.hi = *reinterpret_cast<const fbf16x8*>(rh + b * 32);
-      a.lo = *reinterpret_cast<const fbf16x8*>(rl + b * 32);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) az[g] = x3_mma(a, wz[g][b], az[g]);
-    }
-#pragma unroll
-  for (int b = 0; b < FB_H / 2; ++b)
-    if (b < nbH2) {
-      X3Frag a;
-      a.hi = *reinterpret_cast<const fbf16x8*>(rh + Ch16 + b * 32);
-      a.lo = *reinterpret_cast<const fbf16x8*>(rl + Ch16 + b * 32);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) ah[g] = x3_mma(a, wh[g][b], ah[g]);
-    }
-  fast_cell_p2_gates<NG>(f, Ht, Hn, az, ah, gc, bh, cprev, j2, kq, b0, rows, h_out, c_out, g_out, cnew, ihn, iln, ldx, Ch16);
-}
-
-// bf16 x 3 form: weights as packed 32-k fragments (x3_pack), nbZ2 / nbH2 = number of 32-k blocks
-template <int NG>
-__device__ __forceinline__ void fast_cell_p2_x3(const FlowK& f, const float* Zt, const float* Ht, float* Hn,
-                                                const X3Frag (&wz)[NG][FB_Z / 2], const X3Frag (&wh)[NG][FB_H / 2],
-                                                const float (&gc)[4][NG], const float (&bh)[NG], const float (&cprev)[4], int nbZ2,
-                                                int nbH2, int j2, int kq, int l15, int b0, int rows, float* h_out, float* c_out,
-                                                float* g_out, float* cnew) {
-  f32x4 az[NG], ah[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    az[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    ah[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-  const float* zl = Zt + kq * LT + l15;
-  const float* hl = Ht + kq * LT + l15;
-#pragma unroll
-  for (int b = 0; b < FB_Z / 2; ++b)
-    if (b < nbZ2) {
-      const X3Frag a = x3_a(zl + b * 32 * LT);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) az[g] = x3_mma(a, wz[g][b], az[g]);
-    }
-#pragma unroll
-  for (int b = 0; b < FB_H / 2; ++b)
-    if (b < nbH2) {
-      const X3Frag a = x3_a(hl + b * 32 * LT);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) ah[g] = x3_mma(a, wh[g][b], ah[g]);
-    }
-  fast_cell_p2_gates<NG>(f, Ht, Hn, az, ah, gc, bh, cprev, j2, kq, b0, rows, h_out, c_out, g_out, cnew);
-}
-
-// fp16 x 3 form (x3h_*): the sampler's reverse cells
-template <int NG>
-__device__ __forceinline__ void fast_cell_p2_x3h(const FlowK& f, const float* Zt, const float* Ht, float* Hn,
-                                                 const X3FragH (&wz)[NG][FB_Z / 2], const X3FragH (&wh)[NG][FB_H / 2],
-                                                 const float (&gc)[4][NG], const float (&bh)[NG], const float (&cprev)[4], int nbZ2,
-                                                 int nbH2, int j2, int kq, int l15, int b0, int rows, float* h_out, float* c_out,
-                                                 float* g_out, float* cnew) {
-  f32x4 az[NG], ah[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    az[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    ah[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-  const float* zl = Zt + kq * LT + l15;
-  const float* hl = Ht + kq * LT + l15;
-#pragma unroll
-  for (int b = 0; b < FB_Z / 2; ++b)
-    if (b < nbZ2) {
-      const X3FragH a = x3h_a(zl + b * 32 * LT);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) az[g] = x3h_mma(a, wz[g][b], az[g]);
-    }
-#pragma unroll
-  for (int b = 0; b < FB_H / 2; ++b)
-    if (b < nbH2) {
-      const X3FragH a = x3h_a(hl + b * 32 * LT);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) ah[g] = x3h_mma(a, wh[g][b], ah[g]);
-    }
-  fast_cell_p2_gates<NG>(f, Ht, Hn, az, ah, gc, bh, cprev, j2, kq, b0, rows, h_out, c_out, g_out, cnew);
-}
-
-// P3: o = (h' Wfl^T + b) exp(3 logs) on this wave's 16 outputs   (LinearZeros, glow/modules.py:93-95); o_out may be null
-// (bb, sc: LinearZeros bias and exp(3 logs) of this lane's output column, loaded by the caller OUTSIDE its dependent phases)
-__device__ __forceinline__ void fast_cell_p3(const FlowK& f, int k, const float* Hn, float* Orm, const f32x4 (&w3)[FB_H], int nbH,
-                                             int col, int kq, int l15, int b0, int rows, float* o_out, long ld_out, float bb, float sc) {
-  const int Cout = f.Cout, ldo = Cout + 1;
-  const f32x4 acc = mma16_reg<FB_H>(Hn + kq * LT + l15, w3, nbH);
-  if (col < Cout) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = kq * 4 + r;
-      const int row = b0 + i;
-      const float o = (acc[r] + bb) * sc;
-      Orm[i * ldo + col] = o;
-      if (o_out && row < rows) o_out[(long)row * ld_out + col] = o;
-    }
-  }
-}
-
 template <int NG>
 __global__ __launch_bounds__(NT) void flow_diag_fwd_fast_kernel(FlowK f, int d, int klo) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1306,113 +472,6 @@ __global__ __launch_bounds__(NT) void flow_diag_fwd_fast_kernel(FlowK f, int d, 
   }
   LFI_STAMP(6);
 }
-
-// ------------------------------------------------------------------------------------------- persistent pipeline
-// The diagonal walk above pays one launch + one reload of 270 KB of weights per workgroup for every one of the N + Ks - 1
-// diagonals, although a workgroup's weights never change: cell (n, k) of batch tile bt always needs flow step k's. Here
-// workgroup (k, bt) is PERSISTENT: it loads step k's weights into registers once, then walks n = 0 .. N-1 for its 16
-// samples; the recurrent state h (and the LSTM cell state) never leaves the workgroup (LDS / registers), and the only
-// inter-workgroup traffic is the 16 x C output tile handed from (k, bt) to (k + 1, bt): a systolic pipeline over the flow
-// steps, N + Ks - 1 cell times end to end, one launch. Hand-off (MI355X_MICROARCH.md, inter-workgroup visibility, form R1):
-// the producer stores the tile write-through (sc1), every wave drains its stores, workgroup barrier, ONE lane publishes
-// the progress counter with an agent-scope atomic store; the consumer polls that one word relaxed, ONE agent-scope acquire,
-// barrier, then plain loads. Deadlock-free for ANY grid size and dispatch order: logical (k, bt) ids are dealt by an atomic
-// ticket in arrival order and a workgroup only ever waits on a smaller ticket, i.e. on a workgroup that is already
-// running (more workgroups than CUs simply run as successive groups of flow steps). Every spin is bounded: on timeout
-// the abort word is set, every workgroup leaves its loop, and the host reports LFI_ERR_LAUNCH.
-constexpr unsigned PIPE_HDR = 4;                 // ticket, abort, 2 reserved words
-#ifndef LFI_PIPE_STRIDE
-#define LFI_PIPE_STRIDE 32
-#endif
-constexpr unsigned PIPE_STRIDE = LFI_PIPE_STRIDE;   // words between two progress words of the persistent walks: one 128-byte line each (the polls of 256 workgroups
-                                                    // on eight shared lines queued at one memory channel)
-constexpr unsigned PIPE_WALK_HDR = PIPE_STRIDE > PIPE_HDR ? PIPE_STRIDE : PIPE_HDR;
-constexpr unsigned PIPE_SPIN_LIMIT = 1u << 23;   // polls (each >= ~0.5 us) before giving up
-
-__device__ __forceinline__ unsigned ld_agent(const unsigned* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_agent(unsigned* p, unsigned v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// write-through (sc1) store of one payload element
-__device__ __forceinline__ void st_sc1(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// load of one handed-off payload element: L1-bypassing (sc1) when the consumer did not fence
-__device__ __forceinline__ float ld_tile(const float* p, bool fenced) {
-  return fenced ? *p : __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// ONE lane: wait until *flag >= need. false = aborted (timeout here or in another workgroup).
-__device__ __forceinline__ bool pipe_wait(const unsigned* flag, unsigned need, unsigned* abort_w) {
-  unsigned spins = 0;
-  while (ld_agent(flag) < need) {
-    if ((++spins & 31u) == 0u) {
-      if (ld_agent(abort_w) != 0u) return false;
-      if (spins > PIPE_SPIN_LIMIT) {
-        st_agent(abort_w, 1u);
-        return false;
-      }
-    }
-    __builtin_amdgcn_s_sleep(4);
-  }
-  return true;
-}
-// consumer side of a hand-off, all threads: thread 0 polls + acquires, the rest learn the outcome through LDS
-__device__ __forceinline__ bool pipe_acquire(const unsigned* flag, unsigned need, unsigned* abort_w, int tid, int* s_ok,
-                                             bool fence) {
-  if (tid == 0) {
-    const bool ok = pipe_wait(flag, need, abort_w);
-    if (ok && fence) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    *s_ok = ok ? 1 : 0;
-  }
-  __syncthreads();
-  return *s_ok != 0;
-}
-// producer side, all threads: drain this wave's stores, barrier, one lane publishes
-__device__ __forceinline__ void pipe_publish(unsigned* flag, unsigned value, int tid, bool signal) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (signal && tid == 0) st_agent(flag, value);
-}
-
-// as mma16_reg with the B fragments of this wave in LDS: wl[b * 64] is this lane's float4 of k block b (consecutive lanes
-// read consecutive 16 bytes: conflict-free ds_read_b128)
-__device__ __forceinline__ f32x4 mma16_lds(const float* a_lane, const f32x4* wl, int nb) {
-  f32x4 e = {0.f, 0.f, 0.f, 0.f}, o = {0.f, 0.f, 0.f, 0.f};
-  for (int b = 0; b < nb; ++b) {
-    const float* ab = a_lane + b * 16 * LT;
-    const f32x4 w = wl[b * 64];
-    const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
-    e = mfma16(a0, w[0], e);
-    o = mfma16(a1, w[1], o);
-    e = mfma16(a2, w[2], e);
-    o = mfma16(a3, w[3], o);
-  }
-  return e + o;
-}
-// LDS floats of the pipeline kernel: the cell's operands, then the W fragments of the C16/16 P1 waves and the Wfl fragments
-// of the Co16/16 P3 waves (the recurrent weights W_ih[:, :Ch] and W_hh stay in registers: 120 VGPRs at H = 128)
-__host__ __device__ inline int pipe_fwd_img_offset(int C, int C16, int H16, int Ch16, int Cout, int Co16) {
-  const int base = (carve_fast_fwd(C, C16, H16, Ch16, Cout).total + 3) & ~3;
-  return base + (C16 >> 4) * (C16 >> 4) * 256 + (Co16 >> 4) * (H16 >> 4) * 256;
-}
-// + the bf16 x 3 cell's operand images: two buffers (h of the previous / of this timestep) x {hi, lo} x MB rows of
-// Ch16 + H16 + 8 bf16 (2 MB ldx floats)
-__host__ __device__ inline int pipe_fwd_lds_floats(int C, int C16, int H16, int Ch16, int Cout, int Co16) {
-  return pipe_fwd_img_offset(C, C16, H16, Ch16, Cout, Co16) + 2 * MB * (Ch16 + H16 + 8);
-}
-
-// diagnostics (lfi_debug_set_stamps): s_memtime of workgroup (Ks / 2, tile 0) at the phase boundaries of every timestep, in
-// slots [4096 + 2048 * backward + 16 * n + phase] of the stamp buffer
-#define PIPE_STAMP(dir, slot)                                                                                              \
-  do {                                                                                                                     \
-    if (f.stamps && tid == 0 && bt == 0 && k == f.stamp_k && n < 128)                                                       \
-      f.stamps[4096 + 2048 * (dir) + 16 * n + (slot)] = __builtin_amdgcn_s_memtime();                                      \
-  } while (0)
 
 template <int NG, bool X3>
 __global__ __launch_bounds__(NT) void flow_pipe_fwd_kernel(FlowK f) {
@@ -1705,920 +764,6 @@ __global__ __launch_bounds__(NT) void flow_pipe_fwd_kernel(FlowK f) {
     PIPE_STAMP(0, 7);
     float* t = Ht; Ht = Hn; Hn = t;
     __bf16* ti = ich; ich = inh; inh = ti;
-  }
-}
-
-// FlowStep.reverse_flow (glow/models.py:345-373) with explicit state, register-resident weights: the sampler's and
-// SeqGlow.invert's cell. coupling^-1 -> invconv^-1 (W^-1 image) -> actnorm^-1.
-// wait_flag / pub_flag: hand-off words of the per-frame reverse chain (flow_rev_chain_kernel), or null for a stand-alone launch:
-// the input tile is then read with sc1 loads after the producer's progress word is seen, and the output tile is stored sc1,
-// drained and published (the hand-off of the persistent walks).
-// need / pub_value: the progress value waited for / published (1 for the one-frame chain; timestep + 1 in the persistent reverse
-// walk). false = the wait was abandoned (abort word set): nothing was computed.
-// XW (with X3): the weights come as the fp16 fragment images lfi_flow_prep left (FlowK.hwz ..): no f32 fragments, no split here.
-// NLL (the chain of a sampler that reports its frames' likelihood): the rows' running log-density log p(z) - sum of the reverse
-// coupling log-dets so far travels with the tile. q_in: one float per row from step k + 1, handed over as the tile is (null: this
-// cell starts it from the prior term of the noise tile it stages); q_out: where this cell leaves it - sc1 stores in front of the
-// publish - or, q_last, the finished -(q + logdet_const) / ln 2 of the frame in bits. One writer per word, k descending: a fixed
-// summation order. Not NLL: none of it is compiled.
-// RM (flow_rows_chain_kernel): a row-masked cell. Everything it leaves in memory - h_out / c_out, its output tile or the frame row, the
-// hand-over q or the NLL word - is stored only for the tile's rows whose role word (io.role) is io.role_want; the other rows still
-// pass through the products (see that kernel) and are dropped. Not RM: none of it is compiled.
-template <int NG, bool X3 = false, bool XW = false, bool NLL = false, bool RM = false>
-__device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, int b0, const unsigned* wait_flag,
-                                              unsigned* abort_w, unsigned* pub_flag, int* s_ok, unsigned need = 1u,
-                                              unsigned pub_value = 1u, const float* q_in = nullptr, float* q_out = nullptr,
-                                              bool q_last = false) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, kq = lane >> 4;
-  const int ri = tid >> 5, cl = tid & 31;
-  const int k = io.k, rows = io.rows;
-  const int C = f.C, H = f.H, Ch = f.Ch, C2 = f.C2, Cout = f.Cout, G = f.G;
-  const int C16 = f.C16, Ch16 = f.Ch16, H16 = f.H16, Co16 = f.Co16;
-  const CarveF cv = carve_fast_fwd(C, C16, H16, Ch16, Cout);
-  float* Yt = flow_smem + cv.At;   // y = [z1 | z2] k-major for the W^-1 product
-  float* Ht = flow_smem + cv.Ht;
-  float* Zt = flow_smem + cv.Zt;
-  float* Hn = flow_smem + cv.Hn;
-  float* Yrm = flow_smem + cv.Yrm;
-  float* Orm = flow_smem + cv.Orm;
-  const int ldy = C + 1, ldo = Cout + 1;
-  const int nbC = C16 >> 4, nbZ = Ch16 >> 4, nbH = H16 >> 4;
-  const bool t1 = wave * 16 < C, t2 = wave * 16 < H, t3 = wave * 16 < Cout;
-  const int tcol = wave * 16 + l15;
-  unsigned live = 0u;
-  if constexpr (RM) live = tile_live_rows(io.role, io.role_want, b0, rows);
-  // phase stamps of the stamping workgroup (flow step LFI_STAMP_K, tile 0): s_memtime at the phase boundaries (tools/rev_stamps.py)
-#define REV_STAMP(slot)                                                                                                  \
-  do {                                                                                                                   \
-    if (f.stamps && io.stamp_base > 0 && tid == 0 && b0 == 0 && k == f.stamp_k)                                           \
-      f.stamps[io.stamp_base - 1 + (slot)] = __builtin_amdgcn_s_memtime();                                               \
-  } while (0)
-  REV_STAMP(0);
-  static_assert(!XW || X3, "pre-split weight images are the X3 cell's");
-  f32x4 wz[XW ? 1 : NG][XW ? 1 : FB_Z], wh[XW ? 1 : NG][XW ? 1 : FB_H], w3[XW ? 1 : FB_H];
-  X3FragH wzx[X3 ? NG : 1][FB_Z / 2];            // three fp16 products (fp32-grade, x3h_*): the z1-side fragments
-  X3FragH whx[XW ? NG : 1][XW ? FB_H / 2 : 1];   // XW: the h-side fragments too (otherwise split where they are used)
-  X3FragH w3x[X3 ? FB_H / 2 : 1], w1x[X3 ? FB_C / 2 : 1];
-  // this lane's entries of a pre-split image of flow step k: nb2 32-k blocks of the 16-column tile at `col` (row pitch J entries)
-  auto load_x3h = [&](X3FragH* w, int maxb2, const uint4* img, int K16, int J, int col, int nb2, bool on) {
-    const long per = (long)(K16 >> 5) * 4 * J;
-    const uint4* p = img + (long)k * 2 * per + (long)kq * J + col;
-#pragma unroll
-    for (int b = 0; b < maxb2; ++b)
-      if (on && b < nb2) {
-        w[b].hi = __builtin_bit_cast(fh16x8, p[(long)b * 4 * J]);
-        w[b].lo = __builtin_bit_cast(fh16x8, p[(long)b * 4 * J + per]);
-      } else {
-        w[b].hi = (fh16x8)(_Float16)0.0f;
-        w[b].lo = (fh16x8)(_Float16)0.0f;
-      }
-  };
-  float hv[XW ? FB_H / 2 : 1];   // XW: this thread's elements of h_prev (row ri, columns cl + 32 q), staged to LDS further down
-  if constexpr (XW) {
-    // Vector-memory results come back in issue order: what the work in front of the wait needs first is issued first - h_prev
-    // (its LDS image gates the barrier), then the h-side fragments of the product that runs before the wait; the fragments of the
-    // phases behind the wait follow and arrive under that product.
-    const int row = b0 + ri;
-#pragma unroll
-    for (int q = 0; q < FB_H / 2; ++q) {
-      const int j = cl + 32 * q;
-      hv[q] = (io.h_prev && row < rows && j < H) ? ld_tile(io.h_prev + (long)row * H + j, io.state_l2 == 0) : 0.0f;
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) load_x3h(whx[g], FB_H / 2, f.hwh, H16, NG * H16, g * H16 + tcol, nbH >> 1, t2);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) load_x3h(wzx[g], FB_Z / 2, f.hwz, Ch16, NG * H16, g * H16 + tcol, nbZ >> 1, t2);
-    load_x3h(w3x, FB_H / 2, f.hwfl, H16, Co16, tcol, nbH >> 1, t3);
-  } else {
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-#pragma unroll
-      for (int b = 0; b < FB_Z; ++b) wz[g][b] = zero4;
-#pragma unroll
-      for (int b = 0; b < FB_H; ++b) wh[g][b] = zero4;
-      load_frag<FB_Z>(wz[g], f.pwz + (long)k * Ch16 * NG * H16, NG * H16, g * H16 + tcol, kq, nbZ, t2);
-      load_frag<FB_H>(wh[g], f.pwh + (long)k * H16 * NG * H16, NG * H16, g * H16 + tcol, kq, nbH, t2);
-    }
-    load_frag<FB_H>(w3, f.pwfl + (long)k * H16 * Co16, Co16, tcol, kq, nbH, t3);
-  }
-  float gc[4][NG], bh[NG], cprev[4];
-  {
-    const float* bhh = f.p.b_hh + (long)k * G;
-    const int jc = tcol < H ? tcol : 0;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) bh[g] = bhh[g * H + jc];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = min(b0 + kq * 4 + r, rows - 1);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) gc[r][g] = io.gic[(long)row * G + g * H + jc];
-      cprev[r] = (NG == 4 && io.c_prev) ? ld_tile(io.c_prev + (long)row * H + jc, io.state_l2 == 0) : 0.0f;
-    }
-  }
-  // ---- everything that does not depend on the incoming tile runs BEFORE the wait for it (a chain of Ks dependent cells pays
-  // whatever follows the wait Ks times per frame; stamps of round 4: staging h_prev, splitting the weight fragments into fp16
-  // pieces and the h_prev W_hh half of the recurrent product - 4 of its 5 k-blocks - were 10 k of a cell's 20 k dependent cycles)
-  if constexpr (XW) {
-#pragma unroll
-    for (int q = 0; q < FB_H / 2; ++q) {
-      const int j = cl + 32 * q;
-      if (j < H16) {
-        Ht[j * LT + ri] = hv[q];
-        if (j >= H) Hn[j * LT + ri] = 0.0f;
-      }
-    }
-    for (int c = Ch + cl; c < Ch16; c += 32) Zt[c * LT + ri] = 0.0f;
-  } else {
-    const int row = b0 + ri;
-    const bool rok = row < rows;
-    for (int j = cl; j < H16; j += 32) {
-      Ht[j * LT + ri] = (io.h_prev && rok && j < H) ? ld_tile(io.h_prev + (long)row * H + j, io.state_l2 == 0) : 0.0f;
-      if (j >= H) Hn[j * LT + ri] = 0.0f;
-    }
-    for (int c = Ch + cl; c < Ch16; c += 32) Zt[c * LT + ri] = 0.0f;
-  }
-  // W^-1 slice of this wave's 16 output channels: in flight under the coupling net
-  f32x4 w1[XW ? 1 : FB_C];
-  if constexpr (XW) load_x3h(w1x, FB_C / 2, f.hWinv, C16, C16, tcol, nbC >> 1, t1);
-  else load_frag<FB_C>(w1, f.pWinv + (long)k * C16 * C16, C16, tcol, kq, nbC, t1);
-  // per-column constants of the phases after the wait (LinearZeros bias / scale, ActNorm^-1 scale / bias): loaded here, not between
-  // the barriers of the dependent phases (two L2 round trips per cell each)
-  const float flb = tcol < Cout ? f.p.b_fl[(long)k * Cout + tcol] : 0.0f;
-  const float fls = tcol < Cout ? expf(3.0f * f.p.l_fl[(long)k * Cout + tcol]) : 0.0f;
-  const float an_es = tcol < C ? expf(-f.p.an_logs[(long)k * C + tcol]) : 0.0f;
-  const float an_bb = tcol < C ? f.p.an_bias[(long)k * C + tcol] : 0.0f;
-  // X3: LinearZeros and W^-1 as three fp16 products too (K = H and K = C: 32 and 16 dependent f32-input MFMAs of 32 cycles
-  // otherwise, per cell, after the wait); their weight fragments are split here, before it. Whole pairs of 16-k blocks only.
-  // (X3 is only instantiated for shapes with whole pairs everywhere: the launcher checks H16, Ch16 and C16)
-  if constexpr (X3 && !XW) {
-#pragma unroll
-    for (int b = 0; b < FB_H / 2; ++b)
-      if (b < (nbH >> 1)) w3x[b] = x3h_pack(w3[2 * b], w3[2 * b + 1]);
-#pragma unroll
-    for (int b = 0; b < FB_C / 2; ++b)
-      if (b < (nbC >> 1)) w1x[b] = x3h_pack(w1[2 * b], w1[2 * b + 1]);
-  }
-  __syncthreads();
-  f32x4 az[NG], ah[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    az[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    ah[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-  if (t2) {
-    const float* hl = Ht + kq * LT + l15;
-    if constexpr (XW) {
-#pragma unroll
-      for (int b = 0; b < FB_H / 2; ++b)
-        if (b < ((nbH + 1) >> 1)) {
-          const X3FragH a = x3h_a(hl + b * 32 * LT);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = x3h_mma(a, whx[g][b], ah[g]);
-        }
-    } else if constexpr (X3) {
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int b = 0; b < FB_Z / 2; ++b) wzx[g][b] = x3h_pack(wz[g][2 * b], wz[g][2 * b + 1]);
-#pragma unroll
-      for (int b = 0; b < FB_H / 2; ++b)
-        if (b < ((nbH + 1) >> 1)) {
-          const X3FragH a = x3h_a(hl + b * 32 * LT);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = x3h_mma(a, x3h_pack(wh[g][2 * b], wh[g][2 * b + 1]), ah[g]);
-        }
-    } else {
-#pragma unroll
-      for (int b = 0; b < FB_H; ++b)
-        if (b < nbH) {
-          const float* ab = hl + b * 16 * LT;
-          const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a0, wh[g][b][0], ah[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a1, wh[g][b][1], ah[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a2, wh[g][b][2], ah[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a3, wh[g][b][3], ah[g]);
-        }
-    }
-  }
-  if constexpr (XW) {
-    // the fragments of the phases AFTER the wait are plain loads now: pin them in front of it (the compiler sinks a load towards its
-    // use - behind the wait, where a chain of Ks cells pays its L2 round trip Ks times per frame)
-    auto pin = [](X3FragH& w) { asm volatile("" : "+v"(w.hi), "+v"(w.lo)); };
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-      for (int b = 0; b < FB_Z / 2; ++b) pin(wzx[g][b]);
-#pragma unroll
-    for (int b = 0; b < FB_H / 2; ++b) pin(w3x[b]);
-#pragma unroll
-    for (int b = 0; b < FB_C / 2; ++b) pin(w1x[b]);
-  }
-  REV_STAMP(1);
-  if (wait_flag && !pipe_acquire(wait_flag, need, abort_w, tid, s_ok, false)) return false;
-  REV_STAMP(2);
-  // ---- R0: stage the tile [z1 | z2']
-  float q = 0.0f;   // NLL: lane cl == 0 carries its row's running log-density; the first cell's lanes their parts of sum z^2
-  {
-    const int row = b0 + ri;
-    const bool rok = row < rows;
-    if constexpr (NLL) {
-      if (q_in && cl == 0 && rok) q = ld_tile(q_in + row, false);   // (in flight under the cell: needed in R3)
-    }
-    for (int c = cl; c < C16; c += 32) {
-      const float v = (c < C && rok) ? ld_tile(io.x_in + (long)row * io.ldx + c, wait_flag == nullptr) : 0.0f;
-      if constexpr (NLL) {
-        if (!q_in) q += v * v;
-      }
-      if (c < C) Yrm[ri * ldy + c] = v;
-      if (c < Ch) Zt[c * LT + ri] = v;
-      if (c < Ch || c >= C) Yt[c * LT + ri] = v;   // z1 rows and the zero k padding; z2 rows come from R3
-    }
-  }
-  __syncthreads();
-  REV_STAMP(3);
-  if (t2) {   // the z1 half of the product (one k-block at C <= 64), then the gate math
-    const float* zl = Zt + kq * LT + l15;
-    if constexpr (X3) {
-#pragma unroll
-      for (int b = 0; b < FB_Z / 2; ++b)
-        if (b < ((nbZ + 1) >> 1)) {
-          const X3FragH a = x3h_a(zl + b * 32 * LT);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = x3h_mma(a, wzx[g][b], az[g]);
-        }
-    } else {
-#pragma unroll
-      for (int b = 0; b < FB_Z; ++b)
-        if (b < nbZ) {
-          const float* ab = zl + b * 16 * LT;
-          const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = mfma16(a0, wz[g][b][0], az[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = mfma16(a1, wz[g][b][1], az[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = mfma16(a2, wz[g][b][2], az[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = mfma16(a3, wz[g][b][3], az[g]);
-        }
-    }
-    fast_cell_p2_gates<NG, RM>(f, Ht, Hn, az, ah, gc, bh, cprev, tcol, kq, b0, rows, io.h_out, io.c_out, nullptr, nullptr, nullptr, nullptr,
-                               0, 0, live);
-  }
-  __syncthreads();
-  REV_STAMP(4);
-  if (t3) {
-    if constexpr (X3) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      const float* hl = Hn + kq * LT + l15;
-#pragma unroll
-      for (int b = 0; b < FB_H / 2; ++b)
-        if (b < (nbH >> 1)) acc = x3h_mma(x3h_a(hl + b * 32 * LT), w3x[b], acc);
-      if (tcol < Cout) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Orm[(kq * 4 + r) * ldo + tcol] = (acc[r] + flb) * fls;
-      }
-    } else {
-      fast_cell_p3(f, k, Hn, Orm, w3, nbH, tcol, kq, l15, b0, rows, nullptr, 0, flb, fls);
-    }
-  }
-  __syncthreads();
-  REV_STAMP(5);
-  // ---- R3: coupling inverse (glow/models.py:356-365)
-  {
-    const int row = b0 + ri;
-    const bool rs = RM ? ((live >> ri) & 1u) != 0u : row < rows;
-    float lg = 0.0f;
-    if (cl < C2) {
-      const float z2n = Yrm[ri * ldy + Ch + cl];
-      float z2;
-      if (f.affine) {
-        const float shift = Orm[ri * ldo + 2 * cl];
-        const float sraw = sigmoidf_(Orm[ri * ldo + 2 * cl + 1] + 2.0f);
-        const float sc = fmaxf(sraw, f.eps);
-        z2 = z2n / sc;
-        z2 = z2 - shift;
-        lg = -logf(sc);
-      } else {
-        z2 = z2n - Orm[ri * ldo + cl];
-      }
-      Yt[(Ch + cl) * LT + ri] = z2;
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) lg += __shfl_xor(lg, o, 64);
-    if (cl == 0 && rs && io.l_out) {
-      if (io.l_accumulate) io.l_out[row] += lg; else io.l_out[row] = lg;
-    }
-    if constexpr (NLL) {
-      if (!q_in) {   // log p(z) of the prior draw: sum_c -0.5 (z_c^2 + log 2 pi)
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-        q = -0.5f * (q + (float)C * LOG2PI_F);
-      }
-      if (cl == 0 && rs) {
-        q -= lg;   // forward log-det of this step's coupling = -lg
-        if (q_last) q_out[row] = -(q + f.ldconst[0]) / LN2_F;
-        else st_sc1(q_out + row, q);
-      }
-    }
-  }
-  __syncthreads();
-  REV_STAMP(6);
-  // ---- R4: x = (y W^-1) exp(-logs) - bias   (scale then center, glow/modules.py:76-79)
-  if (t1) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (X3) {
-      const float* yl = Yt + kq * LT + l15;
-#pragma unroll
-      for (int b = 0; b < FB_C / 2; ++b)
-        if (b < (nbC >> 1)) acc = x3h_mma(x3h_a(yl + b * 32 * LT), w1x[b], acc);
-    } else {
-      acc = mma16_reg<FB_C>(Yt + kq * LT + l15, w1, nbC);
-    }
-    const int c = tcol;
-    if (c < C) {
-      const float es = an_es, bb = an_bb;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = b0 + kq * 4 + r;
-        if (RM ? ((live >> (kq * 4 + r)) & 1u) != 0u : row < rows) {
-          if (pub_flag) st_sc1(io.x_out + (long)row * io.ldxo + c, acc[r] * es - bb);
-          else io.x_out[(long)row * io.ldxo + c] = acc[r] * es - bb;
-        }
-      }
-    }
-  }
-  REV_STAMP(7);
-  if (pub_flag) pipe_publish(pub_flag, pub_value, tid, true);
-  REV_STAMP(8);
-#undef REV_STAMP
-  return true;
-}
-
-template <int NG>
-__global__ __launch_bounds__(NT) void flow_step_rev_fast_kernel(FlowK f, CellIO io) {
-  rev_fast_cell<NG>(f, io, blockIdx.x * MB, nullptr, nullptr, nullptr, nullptr);
-}
-
-// One generated frame of the sampler: all Ks reverse flow steps of all batch tiles in ONE launch instead of Ks launches of
-// B / 16 workgroups each (64 of 256 CUs at batch 1024, 270 KB of weights fetched behind every launch boundary). Workgroup
-// (k, tile) - ids by ticket, k descending, so a workgroup only waits on one that already runs - requests its weights, its
-// part of gic and its recurrent state, then waits for the tile of step k + 1 (the prior noise for k = Ks - 1), runs the
-// cell and hands its tile to step k - 1 (step 0 writes the frame). Tiles of one sample block chain strictly, so the two
-// ping-pong tile buffers of the per-step launches still do.
-struct RevChain {
-  const float* noise;     // B x C prior draws of this frame
-  float *xa, *xb;         // B x C tile buffers: step k writes (k & 1) ? xa : xb
-  float* frame; long ld_frame;   // output rows of this frame in faces (row stride seq_len * C)
-  const float* gic;       // [Ks][B][G]
-  float *h, *cstate;      // [Ks][B][H] recurrent state, updated in place
-  int has_prev;           // 0 at the first generated frame (zero state)
-  int frame_no;           // index of the generated frame (diagnostic phase stamps of frames < 128 only)
-  unsigned* pipe;         // ticket, abort, progress words (zeroed before every launch)
-  // round 5: step 0's workgroups also leave the NEXT frame's window as the fp16 fragments the fused conditioning kernel reads
-  // (lfi_sample.hip, sc_xfrag_kernel's format: tile bt, step m, plane: lane l, element e = window[16 bt + (l & 15)][32 m + 8 (l >> 4) + e])
-  // - one launch per generated frame less; null: the conditioning call makes them itself
-  _Float16* xf;
-  const float* faces;     // row 0 of the frames buffer (row pitch ld_frame)
-  long xf_off;            // first window column of the next frame in a row: (t + 1 - hist1) * C
-  int K1, NM1;
-  // NLL instantiations only: the rows' running log-density crosses the chain beside the tile (rev_fast_cell)
-  float *qa, *qb;         // B floats each: step k writes (k & 1) ? qa : qb, as the tiles ping-pong
-  float* nll;             // B floats: this frame's NLL in bits, written by step 0
-};
-template <int NG, bool X3, bool XW = false, bool NLL = false>
-__global__ __launch_bounds__(NT) void flow_rev_chain_kernel(FlowK f, RevChain rc) {
-  __shared__ int s_id, s_ok;
-  if (threadIdx.x == 0) s_id = (int)atomicAdd(rc.pipe, 1u);
-  __syncthreads();
-  const int nbt = f.nbt;
-  const int kk = s_id / nbt, bt = s_id - kk * nbt;
-  if (kk >= f.Ks) return;
-  const int k = f.Ks - 1 - kk;
-  unsigned* prog = rc.pipe + PIPE_HDR;
-  CellIO io = {};
-  io.k = k; io.rows = f.B;
-  if (k == f.Ks - 1) { io.x_in = rc.noise; io.ldx = f.C; }
-  else { io.x_in = ((k + 1) & 1) ? rc.xa : rc.xb; io.ldx = f.C; }
-  if (k == 0) { io.x_out = rc.frame; io.ldxo = rc.ld_frame; }
-  else { io.x_out = (k & 1) ? rc.xa : rc.xb; io.ldxo = f.C; }
-  io.h_prev = rc.has_prev ? rc.h + (long)k * f.B * f.H : nullptr;
-  io.h_out = rc.h + (long)k * f.B * f.H;
-  if (NG == 4) { io.c_prev = rc.has_prev ? rc.cstate + (long)k * f.B * f.H : nullptr; io.c_out = rc.cstate + (long)k * f.B * f.H; }
-  io.gic = rc.gic + (long)k * f.B * f.G;
-  io.stamp_base = rc.frame_no < 128 ? 1024 + 16 * rc.frame_no + 1 : 0;
-  if constexpr (NLL)
-    rev_fast_cell<NG, X3, XW, true>(f, io, bt * MB, k + 1 < f.Ks ? prog + (k + 1) * nbt + bt : nullptr, rc.pipe + 1,
-                                    k > 0 ? prog + k * nbt + bt : nullptr, &s_ok, 1u, 1u,
-                                    k + 1 < f.Ks ? (((k + 1) & 1) ? rc.qa : rc.qb) : nullptr,
-                                    k == 0 ? rc.nll : ((k & 1) ? rc.qa : rc.qb), k == 0);
-  else
-  rev_fast_cell<NG, X3, XW>(f, io, bt * MB, k + 1 < f.Ks ? prog + (k + 1) * nbt + bt : nullptr, rc.pipe + 1,
-                    k > 0 ? prog + k * nbt + bt : nullptr, &s_ok);
-  if (k == 0 && ld_agent(rc.pipe + 1) != 0u) {   // an abandoned chain must not pass for a frame
-    const int row = bt * MB + (int)(threadIdx.x >> 5);
-    if (row < f.B)
-      for (int c = threadIdx.x & 31; c < f.C; c += 32) rc.frame[(long)row * rc.ld_frame + c] = __builtin_nanf("");
-    if constexpr (NLL) {   // (the thread that wrote the row's word in R3, if the cell got that far)
-      if (row < f.B && (threadIdx.x & 31) == 0) rc.nll[row] = __builtin_nanf("");
-    }
-  }
-  if (k == 0 && rc.xf) {
-    // the frame's rows of this tile are on their way to memory: drain, meet, then read the window back past the L1 (agent scope)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    typedef _Float16 xh8 __attribute__((ext_vector_type(8)));
-    for (int it = threadIdx.x; it < rc.NM1 * 64; it += NT) {
-      const int l = it & 63, m = it >> 6;
-      const int row = bt * MB + (l & 15), kk0 = 32 * m + 8 * (l >> 4);
-      xh8 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float v = 0.0f;
-        if (row < f.B && kk0 + e < rc.K1) v = ld_tile(rc.faces + (long)row * rc.ld_frame + rc.xf_off + kk0 + e, false);
-        const _Float16 h = (_Float16)v;
-        hi[e] = h;
-        lo[e] = (_Float16)(v - (float)h);
-      }
-      _Float16* dst = rc.xf + ((long)(bt * rc.NM1 + m) * 2) * 512 + l * 8;
-      *reinterpret_cast<xh8*>(dst) = hi;
-      *reinterpret_cast<xh8*>(dst + 512) = lo;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------- forward chain (teacher-forced frame)
-// FlowStep.normal_flow (glow/models.py:311-341) of ONE observed frame with the recurrent state carried in place: the forward twin of
-// rev_fast_cell for a streaming session's observe() step. Same thread maps, same LDS carve, same place of the wait: the weights, gic,
-// h_prev and the h_prev W_hh half of the recurrent product run before it; behind it actnorm, y = a W, the z1 half + the gates,
-// LinearZeros and the coupling. The recurrent cell sees what the reverse cell of the same frame sees - z1 and the conditioning - so
-// the h / c it leaves is the state a sampler continues from. No stash of any kind.
-// X3: every product as three fp16 products of two-piece operands (x3h_*, fp32-grade: 2^-22 relative), the f32 fragment images split
-// in registers before the wait; otherwise the exact f32 MFMA. (The training walks' three bf16 products - 2^-16 pieces - are not used
-// here: the state must match the reverse cell's to the sampler's own tolerance.)
-// q_in: the rows' running coupling log-det from step k - 1 (null: this cell starts it); q_out: where it goes on to step k + 1, sc1
-// stores in front of the publish. nll_out (the last step): the cell adds the prior term of its z, sum_c -0.5 (z_c^2 + log 2 pi), and
-// logdet_const and writes -(logdet + log p(z)) / ln 2 in bits. One writer per word, k ascending: a fixed summation order.
-// io.x_out may be null (the last step of a caller that does not want z).
-// RM (flow_rows_chain_kernel): a row-masked cell, as rev_fast_cell's - h_out / c_out, the output tile, the hand-over q and the NLL word
-// are stored for the rows of role io.role_want only.
-template <int NG, bool X3, bool RM = false>
-__device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io, int b0, const unsigned* wait_flag, unsigned* abort_w,
-                                               unsigned* pub_flag, int* s_ok, const float* q_in, float* q_out, float* nll_out) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, kq = lane >> 4;
-  const int ri = tid >> 5, cl = tid & 31;
-  const int k = io.k, rows = io.rows;
-  const int C = f.C, H = f.H, Ch = f.Ch, C2 = f.C2, Cout = f.Cout, G = f.G;
-  const int C16 = f.C16, Ch16 = f.Ch16, H16 = f.H16, Co16 = f.Co16;
-  const CarveF cv = carve_fast_fwd(C, C16, H16, Ch16, Cout);
-  float* At = flow_smem + cv.At;
-  float* Ht = flow_smem + cv.Ht;
-  float* Zt = flow_smem + cv.Zt;
-  float* Hn = flow_smem + cv.Hn;
-  float* Yrm = flow_smem + cv.Yrm;
-  float* Orm = flow_smem + cv.Orm;
-  const int ldy = C + 1, ldo = Cout + 1;
-  const int nbC = C16 >> 4, nbZ = Ch16 >> 4, nbH = H16 >> 4;
-  const bool t1 = wave * 16 < C, t2 = wave * 16 < H, t3 = wave * 16 < Cout;
-  const int tcol = wave * 16 + l15;
-  unsigned live = 0u;
-  if constexpr (RM) live = tile_live_rows(io.role, io.role_want, b0, rows);
-  // ---- requests in the order their results are needed: h_prev (its LDS image gates the first barrier), the recurrent weights, then
-  // the weights of the phases behind the wait
-  const int hrow = b0 + ri;
-  float hv[FB_H / 2];
-#pragma unroll
-  for (int q = 0; q < FB_H / 2; ++q) {
-    const int j = cl + 32 * q;
-    hv[q] = (io.h_prev && hrow < rows && j < H) ? io.h_prev[(long)hrow * H + j] : 0.0f;
-  }
-  f32x4 wz[NG][FB_Z], wh[NG][FB_H], w3[FB_H], w1[FB_C];
-  {
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-#pragma unroll
-      for (int b = 0; b < FB_Z; ++b) wz[g][b] = zero4;
-#pragma unroll
-      for (int b = 0; b < FB_H; ++b) wh[g][b] = zero4;
-      load_frag<FB_H>(wh[g], f.pwh + (long)k * H16 * NG * H16, NG * H16, g * H16 + tcol, kq, nbH, t2);
-      load_frag<FB_Z>(wz[g], f.pwz + (long)k * Ch16 * NG * H16, NG * H16, g * H16 + tcol, kq, nbZ, t2);
-    }
-#pragma unroll
-    for (int b = 0; b < FB_H; ++b) w3[b] = zero4;
-#pragma unroll
-    for (int b = 0; b < FB_C; ++b) w1[b] = zero4;
-    // (the LSTM cell's four gate blocks of W_hh fill the register file: its W and LinearZeros fragments are requested once the h-side
-    // product has let those go - still in front of the wait; 24 VGPRs in scratch otherwise)
-    if constexpr (NG != 4) {
-      load_frag<FB_C>(w1, f.pW + (long)k * C16 * C16, C16, tcol, kq, nbC, t1);
-      load_frag<FB_H>(w3, f.pwfl + (long)k * H16 * Co16, Co16, tcol, kq, nbH, t3);
-    }
-  }
-  float gc[4][NG], bh[NG], cprev[4];
-  auto load_gic = [&]() {
-    const float* bhh = f.p.b_hh + (long)k * G;
-    const int jc = tcol < H ? tcol : 0;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) bh[g] = bhh[g * H + jc];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = min(b0 + kq * 4 + r, rows - 1);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) gc[r][g] = io.gic[(long)row * G + g * H + jc];
-      cprev[r] = (NG == 4 && io.c_prev) ? io.c_prev[(long)row * H + jc] : 0.0f;
-    }
-  };
-  if constexpr (NG != 4) load_gic();
-  // per-column constants of the phases behind the wait: ActNorm of this thread's two channels (cl, cl + 32), LinearZeros of its column
-  float an_b[2], an_s[2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int c = cl + 32 * q;
-    an_b[q] = c < C ? f.p.an_bias[(long)k * C + c] : 0.0f;
-    an_s[q] = c < C ? expf(f.p.an_logs[(long)k * C + c]) : 0.0f;
-  }
-  const float flb = tcol < Cout ? f.p.b_fl[(long)k * Cout + tcol] : 0.0f;
-  const float fls = tcol < Cout ? expf(3.0f * f.p.l_fl[(long)k * Cout + tcol]) : 0.0f;
-  // ---- before the wait: h_prev and the zero k padding into LDS, the fragment split, the h_prev W_hh half of the recurrent product
-#pragma unroll
-  for (int q = 0; q < FB_H / 2; ++q) {
-    const int j = cl + 32 * q;
-    if (j < H16) {
-      Ht[j * LT + ri] = hv[q];
-      if (j >= H) Hn[j * LT + ri] = 0.0f;
-    }
-  }
-  for (int c = Ch + cl; c < Ch16; c += 32) Zt[c * LT + ri] = 0.0f;
-  X3FragH wzx[X3 ? NG : 1][FB_Z / 2], w3x[X3 ? FB_H / 2 : 1], w1x[X3 ? FB_C / 2 : 1];
-  if constexpr (X3) {   // (instantiated for shapes with whole 32-k blocks everywhere: flow_x3h_images_ok)
-#pragma unroll
-    for (int b = 0; b < FB_H / 2; ++b) w3x[b] = x3h_pack(w3[2 * b], w3[2 * b + 1]);
-#pragma unroll
-    for (int b = 0; b < FB_C / 2; ++b) w1x[b] = x3h_pack(w1[2 * b], w1[2 * b + 1]);
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-      for (int b = 0; b < FB_Z / 2; ++b) wzx[g][b] = x3h_pack(wz[g][2 * b], wz[g][2 * b + 1]);
-  }
-  __syncthreads();
-  f32x4 az[NG], ah[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    az[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    ah[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-  if (t2) {
-    const float* hl = Ht + kq * LT + l15;
-    if constexpr (X3) {
-#pragma unroll
-      for (int b = 0; b < FB_H / 2; ++b)
-        if (b < (nbH >> 1)) {
-          const X3FragH a = x3h_a(hl + b * 32 * LT);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = x3h_mma(a, x3h_pack(wh[g][2 * b], wh[g][2 * b + 1]), ah[g]);
-        }
-    } else {
-#pragma unroll
-      for (int b = 0; b < FB_H; ++b)
-        if (b < nbH) {
-          const float* ab = hl + b * 16 * LT;
-          const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a0, wh[g][b][0], ah[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a1, wh[g][b][1], ah[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a2, wh[g][b][2], ah[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a3, wh[g][b][3], ah[g]);
-        }
-    }
-  }
-  if constexpr (NG == 4) {
-    __builtin_amdgcn_sched_barrier(0);
-    load_frag<FB_C>(w1, f.pW + (long)k * C16 * C16, C16, tcol, kq, nbC, t1);
-    load_frag<FB_H>(w3, f.pwfl + (long)k * H16 * Co16, Co16, tcol, kq, nbH, t3);
-    load_gic();
-  }
-  if (wait_flag && !pipe_acquire(wait_flag, 1u, abort_w, tid, s_ok, false)) return false;
-  // ---- F0: actnorm of the incoming tile (glow/modules.py:45-52), k-major with zero k padding
-  float q = 0.0f;   // lane cl == 0 carries its row's running coupling log-det
-  {
-    const int row = b0 + ri;
-    const bool rok = row < rows;
-    if (q_in && cl == 0 && rok) q = ld_tile(q_in + row, false);   // (in flight under the cell: needed in F4)
-#pragma unroll
-    for (int qq = 0; qq < 2; ++qq) {
-      const int c = cl + 32 * qq;
-      if (c < C16) {
-        const float v = (c < C && rok) ? ld_tile(io.x_in + (long)row * io.ldx + c, wait_flag == nullptr) : 0.0f;
-        At[c * LT + ri] = c < C ? (v + an_b[qq]) * an_s[qq] : 0.0f;
-      }
-    }
-  }
-  __syncthreads();
-  // ---- F1: y = a W   (InvertibleConv1x1.forward, glow/modules.py:186); z1 = y[:, :Ch] is the recurrent cell's input
-  if (t1) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (X3) {
-      const float* al = At + kq * LT + l15;
-#pragma unroll
-      for (int b = 0; b < FB_C / 2; ++b)
-        if (b < (nbC >> 1)) acc = x3h_mma(x3h_a(al + b * 32 * LT), w1x[b], acc);
-    } else {
-      acc = mma16_reg<FB_C>(At + kq * LT + l15, w1, nbC);
-    }
-    if (tcol < C) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = kq * 4 + r;
-        Yrm[i * ldy + tcol] = acc[r];
-        if (tcol < Ch) Zt[tcol * LT + i] = acc[r];
-      }
-    }
-  }
-  __syncthreads();
-  // ---- F2: the z1 half of the recurrent product, then the gate math (h / c updated in place)
-  if (t2) {
-    const float* zl = Zt + kq * LT + l15;
-    if constexpr (X3) {
-#pragma unroll
-      for (int b = 0; b < FB_Z / 2; ++b)
-        if (b < (nbZ >> 1)) {
-          const X3FragH a = x3h_a(zl + b * 32 * LT);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = x3h_mma(a, wzx[g][b], az[g]);
-        }
-    } else {
-#pragma unroll
-      for (int b = 0; b < FB_Z; ++b)
-        if (b < nbZ) {
-          const float* ab = zl + b * 16 * LT;
-          const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = mfma16(a0, wz[g][b][0], az[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = mfma16(a1, wz[g][b][1], az[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = mfma16(a2, wz[g][b][2], az[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = mfma16(a3, wz[g][b][3], az[g]);
-        }
-    }
-    fast_cell_p2_gates<NG, RM>(f, Ht, Hn, az, ah, gc, bh, cprev, tcol, kq, b0, rows, io.h_out, io.c_out, nullptr, nullptr, nullptr, nullptr,
-                               0, 0, live);
-  }
-  __syncthreads();
-  // ---- F3: o = (h' Wfl^T + b) exp(3 logs)   (LinearZeros, glow/modules.py:93-95)
-  if (t3) {
-    if constexpr (X3) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      const float* hl = Hn + kq * LT + l15;
-#pragma unroll
-      for (int b = 0; b < FB_H / 2; ++b)
-        if (b < (nbH >> 1)) acc = x3h_mma(x3h_a(hl + b * 32 * LT), w3x[b], acc);
-      if (tcol < Cout) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Orm[(kq * 4 + r) * ldo + tcol] = (acc[r] + flb) * fls;
-      }
-    } else {
-      fast_cell_p3(f, k, Hn, Orm, w3, nbH, tcol, kq, l15, b0, rows, nullptr, 0, flb, fls);
-    }
-  }
-  __syncthreads();
-  // ---- F4: coupling (glow/models.py:330-341), the pass-through half, the row's log-det; the last step: the prior term and the NLL
-  {
-    const int row = b0 + ri;
-    const bool rok = RM ? ((live >> ri) & 1u) != 0u : row < rows;
-    float lg = 0.0f, zz = 0.0f;
-    auto put = [&](int c, float v) {
-      if (!io.x_out || !rok) return;
-      if (pub_flag) st_sc1(io.x_out + (long)row * io.ldxo + c, v);
-      else io.x_out[(long)row * io.ldxo + c] = v;
-    };
-    if (cl < C2) {
-      const float z2 = Yrm[ri * ldy + Ch + cl];
-      float z2n;
-      if (f.affine) {
-        const float shift = Orm[ri * ldo + 2 * cl];
-        const float sraw = sigmoidf_(Orm[ri * ldo + 2 * cl + 1] + 2.0f);
-        const float sc = fmaxf(sraw, f.eps);
-        z2n = (z2 + shift) * sc;
-        lg = logf(sc);
-      } else {
-        z2n = z2 + Orm[ri * ldo + cl];
-      }
-      put(Ch + cl, z2n);
-      zz = z2n * z2n;
-    }
-    if (cl < Ch) {
-      const float z1 = Yrm[ri * ldy + cl];
-      put(cl, z1);
-      zz = __builtin_fmaf(z1, z1, zz);
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) lg += __shfl_xor(lg, o, 64);   // the 32 lanes of one row
-    if (nll_out) {
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) zz += __shfl_xor(zz, o, 64);
-    }
-    if (cl == 0 && rok) {
-      q += lg;
-      if (nll_out) nll_out[row] = -(q + f.ldconst[0] + -0.5f * (zz + (float)C * LOG2PI_F)) / LN2_F;
-      else st_sc1(q_out + row, q);
-    }
-  }
-  if (pub_flag) pipe_publish(pub_flag, 1u, tid, true);
-  return true;
-}
-
-// One OBSERVED frame of a streaming session (SampleStream.observe): all Ks forward flow steps of all batch tiles in ONE launch, the
-// forward twin of flow_rev_chain_kernel. Workgroup (k, tile) - ids by ticket, k ASCENDING, so a workgroup only waits on one that
-// already runs - requests its weights, its part of gic and its recurrent state, then waits for the tile of step k - 1 (the observed
-// frame itself for k = 0), runs the cell and hands its tile and the rows' running log-det to step k + 1; step Ks - 1 writes z (if
-// wanted) and the frame's NLL. Tiles of one sample block chain strictly, so two ping-pong buffers do.
-struct FwdChain {
-  const float* frame; long ld_frame;   // the observed frame's rows in faces (row stride seq_len * C)
-  float *xa, *xb;         // B x C tile buffers: step k writes (k & 1) ? xa : xb
-  const float* gic;       // [Ks][B][G]
-  float *h, *cstate;      // [Ks][B][H] recurrent state, updated in place
-  int has_prev;           // 0 at the first frame of a sequence (zero state)
-  unsigned* pipe;         // ticket, abort, progress words (zeroed before every launch)
-  float *qa, *qb;         // B floats each: step k writes (k & 1) ? qa : qb, as the tiles ping-pong
-  float* z;               // B x C: the frame's latent, or null
-  float* nll;             // B floats: the frame's NLL in bits, written by step Ks - 1
-};
-template <int NG, bool X3>
-__global__ __launch_bounds__(NT) void flow_fwd_chain_kernel(FlowK f, FwdChain fc) {
-  __shared__ int s_id, s_ok;
-  if (threadIdx.x == 0) s_id = (int)atomicAdd(fc.pipe, 1u);
-  __syncthreads();
-  const int nbt = f.nbt;
-  const int k = s_id / nbt, bt = s_id - k * nbt;
-  if (k >= f.Ks) return;
-  const bool last = k == f.Ks - 1;
-  unsigned* prog = fc.pipe + PIPE_HDR;
-  CellIO io = {};
-  io.k = k; io.rows = f.B;
-  if (k == 0) { io.x_in = fc.frame; io.ldx = fc.ld_frame; }
-  else { io.x_in = ((k - 1) & 1) ? fc.xa : fc.xb; io.ldx = f.C; }
-  io.x_out = last ? fc.z : ((k & 1) ? fc.xa : fc.xb); io.ldxo = f.C;
-  io.h_prev = fc.has_prev ? fc.h + (long)k * f.B * f.H : nullptr;
-  io.h_out = fc.h + (long)k * f.B * f.H;
-  if (NG == 4) { io.c_prev = fc.has_prev ? fc.cstate + (long)k * f.B * f.H : nullptr; io.c_out = fc.cstate + (long)k * f.B * f.H; }
-  io.gic = fc.gic + (long)k * f.B * f.G;
-  fwd_chain_cell<NG, X3>(f, io, bt * MB, k > 0 ? prog + (k - 1) * nbt + bt : nullptr, fc.pipe + 1, last ? nullptr : prog + k * nbt + bt,
-                         &s_ok, k > 0 ? (((k - 1) & 1) ? fc.qa : fc.qb) : nullptr, (k & 1) ? fc.qa : fc.qb, last ? fc.nll : nullptr);
-  if (last && ld_agent(fc.pipe + 1) != 0u) {   // an abandoned chain must not pass for a likelihood
-    const int row = bt * MB + (int)(threadIdx.x >> 5);
-    if (row < f.B) {
-      if (fc.z)
-        for (int c = threadIdx.x & 31; c < f.C; c += 32) fc.z[(long)row * f.C + c] = __builtin_nanf("");
-      if ((threadIdx.x & 31) == 0) fc.nll[row] = __builtin_nanf("");   // (the thread that wrote the row's word in F4, if the cell got that far)
-    }
-  }
-}
-
-// One frame of a streaming session in which every batch row either GENERATES or OBSERVES (SampleStream.step_rows): both chains above in
-// ONE launch of 2 Ks nbt workgroups, ids by ticket. Tickets [0, Ks nbt) are flow_rev_chain_kernel's roles (k descending, the NLL
-// hand-over), tickets [Ks nbt, 2 Ks nbt) flow_fwd_chain_kernel's (k ascending). A workgroup waits only on one of its OWN direction with
-// a lower ticket - there is no wait across the directions - so, as in both chains, it only waits on a workgroup that already runs and
-// any number of resident workgroups makes progress. Each direction has its own ping-pong tiles, log-density hand-over and progress
-// words (the reverse's at pipe[PIPE_HDR ..], the forward's Ks nbt words behind them); the ticket and the abort word are shared.
-//
-// role: one word per batch row, != 0 = the row observes (its frame is in `faces` already), 0 = it generates (from its noise row). Both
-// directions run the cell on whole 16-row tiles with row-masked stores (RM): a tile's rows of the other role still flow through its
-// MFMAs, but row i of the A operand only ever reaches row i of D, every reduction of the cells is along one row, and the elementwise
-// phases are per element - so what such a row holds, NaN included, stays in its row and is never stored. One consequence: a forward
-// workgroup may read h_prev / c_prev or the frame slot of a GENERATING row while the reverse workgroup of that tile writes it (and a
-// reverse workgroup the state of an observing row while the forward one writes it): that value feeds only the row that is dropped.
-// Rows of its own role a workgroup reads are written by nobody else in this launch.
-//
-// A workgroup whose tile has no row of its direction leaves at once, before it requests any weights: all Ks workgroups of that
-// (direction, tile) read the same 16 role words and decide alike, so nobody waits on one that left. A caller that keeps generating and
-// observing rows in separate tiles pays for each tile once.
-struct RowsChain {
-  RevChain rev;       // the generating rows' chain (xf = null: the conditioning makes the next window's fragments itself); rev.pipe: the shared words
-  FwdChain fwd;       // the observing rows' chain (z = null)
-  const int* role;    // B words
-};
-template <int NG, bool X3R, bool XW, bool X3F>
-__global__ __launch_bounds__(NT) void flow_rows_chain_kernel(FlowK f, RowsChain rc) {
-  __shared__ int s_id, s_ok;
-  unsigned* pipe = rc.rev.pipe;
-  if (threadIdx.x == 0) s_id = (int)atomicAdd(pipe, 1u);
-  __syncthreads();
-  const int nbt = f.nbt, per = f.Ks * nbt;
-  const int dir = s_id / per;
-  if (dir >= 2) return;
-  const int id = s_id - dir * per;
-  const int kk = id / nbt, bt = id - kk * nbt;
-  if (tile_live_rows(rc.role, dir, bt * MB, f.B) == 0u) return;   // (uniform: no row of this direction in the tile)
-  unsigned* prog = pipe + PIPE_HDR + dir * per;
-  const int row = bt * MB + (int)(threadIdx.x >> 5);
-  CellIO io = {};
-  io.rows = f.B; io.role = rc.role; io.role_want = dir;
-  if (dir == 0) {
-    const RevChain& r = rc.rev;
-    const int k = f.Ks - 1 - kk;
-    io.k = k;
-    if (k == f.Ks - 1) { io.x_in = r.noise; io.ldx = f.C; }
-    else { io.x_in = ((k + 1) & 1) ? r.xa : r.xb; io.ldx = f.C; }
-    if (k == 0) { io.x_out = r.frame; io.ldxo = r.ld_frame; }
-    else { io.x_out = (k & 1) ? r.xa : r.xb; io.ldxo = f.C; }
-    io.h_prev = r.has_prev ? r.h + (long)k * f.B * f.H : nullptr;
-    io.h_out = r.h + (long)k * f.B * f.H;
-    if (NG == 4) { io.c_prev = r.has_prev ? r.cstate + (long)k * f.B * f.H : nullptr; io.c_out = r.cstate + (long)k * f.B * f.H; }
-    io.gic = r.gic + (long)k * f.B * f.G;
-    rev_fast_cell<NG, X3R, XW, true, true>(f, io, bt * MB, k + 1 < f.Ks ? prog + (k + 1) * nbt + bt : nullptr, pipe + 1,
-                                           k > 0 ? prog + k * nbt + bt : nullptr, &s_ok, 1u, 1u,
-                                           k + 1 < f.Ks ? (((k + 1) & 1) ? r.qa : r.qb) : nullptr,
-                                           k == 0 ? r.nll : ((k & 1) ? r.qa : r.qb), k == 0);
-    if (k == 0 && ld_agent(pipe + 1) != 0u) {   // an abandoned chain must not pass for a frame
-      if (row < f.B && rc.role[row] == 0) {
-        for (int c = threadIdx.x & 31; c < f.C; c += 32) r.frame[(long)row * r.ld_frame + c] = __builtin_nanf("");
-        if ((threadIdx.x & 31) == 0) r.nll[row] = __builtin_nanf("");
-      }
-    }
-  } else {
-    const FwdChain& w = rc.fwd;
-    const int k = kk;
-    const bool last = k == f.Ks - 1;
-    io.k = k;
-    if (k == 0) { io.x_in = w.frame; io.ldx = w.ld_frame; }
-    else { io.x_in = ((k - 1) & 1) ? w.xa : w.xb; io.ldx = f.C; }
-    io.x_out = last ? nullptr : ((k & 1) ? w.xa : w.xb); io.ldxo = f.C;
-    io.h_prev = w.has_prev ? w.h + (long)k * f.B * f.H : nullptr;
-    io.h_out = w.h + (long)k * f.B * f.H;
-    if (NG == 4) { io.c_prev = w.has_prev ? w.cstate + (long)k * f.B * f.H : nullptr; io.c_out = w.cstate + (long)k * f.B * f.H; }
-    io.gic = w.gic + (long)k * f.B * f.G;
-    fwd_chain_cell<NG, X3F, true>(f, io, bt * MB, k > 0 ? prog + (k - 1) * nbt + bt : nullptr, pipe + 1, last ? nullptr : prog + k * nbt + bt,
-                                  &s_ok, k > 0 ? (((k - 1) & 1) ? w.qa : w.qb) : nullptr, (k & 1) ? w.qa : w.qb, last ? w.nll : nullptr);
-    if (last && ld_agent(pipe + 1) != 0u) {   // an abandoned chain must not pass for a likelihood
-      if (row < f.B && rc.role[row] != 0 && (threadIdx.x & 31) == 0) w.nll[row] = __builtin_nanf("");
-    }
-  }
-}
-
-// SeqGlow.invert (glow/models.py:617-645): the teacher-forced reverse pass over ALL timesteps in ONE launch - the reverse twin of the
-// persistent forward walk. Workgroup (k, tile), ids by ticket with k descending, walks n = 0 .. N-1: it waits for step k + 1's tile
-// of timestep n (the latent z_n for k = Ks - 1), runs the reverse cell with its recurrent state carried in h / cstate (its own
-// rows, updated in place) and hands its tile to step k - 1 (step 0 writes x_n). Every (n, k) tile has its own slot in `tiles`, so a
-// fast producer never overwrites what its consumer has not read and more workgroups than CUs just run as successive groups. The
-// coupling log-det of every (k, n, row) goes to its own word of `ldk` (workgroups on different CUs must not read-modify-write one
-// accumulator between kernel boundaries); the host call sums them over k.
-struct RevWalk {
-  const float* z;       // [N][B][C]
-  float* tiles;         // [Ks][N * B][C]
-  float* out;           // [N][B][C]
-  const float* gic;     // [Ks][N * B][G]
-  float *h, *cstate;    // [Ks][B][H]
-  float* ldk;           // [Ks][N * B]
-  unsigned* pipe;       // ticket, abort, 2 reserved, then one progress word per (k, tile): timesteps published
-};
-template <int NG>
-__global__ __launch_bounds__(NT) void flow_rev_walk_kernel(FlowK f, RevWalk rw) {
-  __shared__ int s_id, s_ok;
-  if (threadIdx.x == 0) s_id = (int)atomicAdd(rw.pipe, 1u);
-  __syncthreads();
-  const int nbt = f.nbt;
-  const int kk = s_id / nbt, bt = s_id - kk * nbt;
-  if (kk >= f.Ks) return;
-  const int k = f.Ks - 1 - kk;
-  unsigned* prog = rw.pipe + PIPE_HDR;
-  const long F = f.F, B = f.B;
-  bool ok = true;
-  for (int n = 0; n < f.N && ok; ++n) {
-    CellIO io = {};
-    io.k = k; io.rows = f.B; io.ldx = f.C; io.ldxo = f.C;
-    io.x_in = (k == f.Ks - 1) ? rw.z + (long)n * B * f.C : rw.tiles + ((long)(k + 1) * F + (long)n * B) * f.C;
-    io.x_out = (k == 0) ? rw.out + (long)n * B * f.C : rw.tiles + ((long)k * F + (long)n * B) * f.C;
-    io.h_prev = n > 0 ? rw.h + (long)k * B * f.H : nullptr;
-    io.h_out = rw.h + (long)k * B * f.H;
-    if (NG == 4) { io.c_prev = n > 0 ? rw.cstate + (long)k * B * f.H : nullptr; io.c_out = rw.cstate + (long)k * B * f.H; }
-    io.gic = rw.gic + ((long)k * F + (long)n * B) * f.G;
-    io.l_out = rw.ldk + (long)k * F + (long)n * B; io.l_accumulate = 0;
-    io.state_l2 = 1;
-    io.stamp_base = n < 128 ? 1024 + 16 * n + 1 : 0;
-    ok = rev_fast_cell<NG, false>(f, io, bt * MB, k + 1 < f.Ks ? prog + (k + 1) * nbt + bt : nullptr, rw.pipe + 1,
-                                  k > 0 ? prog + k * nbt + bt : nullptr, &s_ok, (unsigned)n + 1u, (unsigned)n + 1u);
-    __syncthreads();   // the cell's last reads of the LDS operands are done before the next timestep stages its own
-  }
-  if (k == 0 && ld_agent(rw.pipe + 1) != 0u) {   // an abandoned walk must not pass for a reconstruction
-    const int row = bt * MB + (int)(threadIdx.x >> 5);
-    if (row < f.B)
-      for (int n = 0; n < f.N; ++n)
-        for (int c = threadIdx.x & 31; c < f.C; c += 32) rw.out[((long)n * B + row) * f.C + c] = __builtin_nanf("");
   }
 }
 
@@ -3765,76 +1910,6 @@ __global__ __launch_bounds__(256) void actnorm_apply_kernel(const double* __rest
 }
 
 // ------------------------------------------------------------------------------------------- host helpers
-// floats of the prep buffer up to the end of the scratch area (published layout + log-det parts + fp64 workspace)
-long prep_scratch_end(const lfi_flow_dims* d) {
-  const int Ch = d->C / 2, C2 = d->C - Ch, Cout = d->affine ? 2 * C2 : C2, G = (d->lstm ? 4 : 3) * d->H;
-  const long cc = (long)d->Ks * d->C * d->C;
-  long n = 3 * cc + (long)d->Ks * Ch * G + (long)d->Ks * d->H * G + (long)d->Ks * d->H * Cout + (long)d->Ks * G * d->D + 4;
-  n += d->Ks + 4;
-  n += 2 * ((long)d->Ks * 2 * d->C * d->C + (long)d->Ks * d->C) + 8;  // doubles, counted as 2 floats each
-  return (n + 3) & ~3L;  // 16-byte aligned: the images behind it are read with dwordx4 loads
-}
-long prep_padded_floats(const lfi_flow_dims* d) {
-  const int Ch = d->C / 2, C2 = d->C - Ch, Cout = d->affine ? 2 * C2 : C2, NG = d->lstm ? 4 : 3;
-  auto r16 = [](int x) { return (long)((x + 15) & ~15); };
-  const long C16 = r16(d->C), Ch16 = Ch ? r16(Ch) : 16, H16 = r16(d->H), Co16 = r16(Cout);
-  return d->Ks * (3 * C16 * C16 + Ch16 * NG * H16 + H16 * NG * H16 + 2 * H16 * Co16 + NG * H16 * H16 + NG * H16 * Ch16)
-         + d->Ks * (NG * H16 * H16 + NG * H16 * Ch16) + 8    // + the bf16 hi/lo fragment images of bwh / bwz (same byte counts)
-         + d->Ks * (Ch16 * NG * H16 + H16 * NG * H16 + H16 * Co16 + C16 * C16) + 8;   // + the fp16 hi/lo images of pwz / pwh / pwfl / pWinv
-}
-
-int fill_flow(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, FlowK* f, const char* who) {
-  LFI_REQUIRE(d && p, "%s: null dims/params", who);
-  LFI_REQUIRE(d->B > 0 && d->N > 0 && d->C >= 2 && d->H > 0 && d->D > 0 && d->Ks > 0, "%s: bad dims", who);
-  f->B = d->B; f->N = d->N; f->C = d->C; f->H = d->H; f->D = d->D; f->Ks = d->Ks;
-  f->affine = d->affine; f->lstm = d->lstm; f->eps = d->scale_eps;
-  f->Ch = d->C / 2; f->C2 = d->C - f->Ch; f->Cout = d->affine ? 2 * f->C2 : f->C2;
-  f->G = (d->lstm ? 4 : 3) * d->H; f->I = f->Ch + d->D; f->F = d->N * d->B; f->nbt = lfi_cdiv(d->B, MB);
-  f->p = *p;
-  f->stamps = g_lfi_stamps;
-  {
-    const char* e = getenv("LFI_STAMP_K");
-    f->stamp_k = e ? atoi(e) : f->Ks / 2;
-  }
-  f->NG = d->lstm ? 4 : 3;
-  f->ldc = (f->C + 3) & ~3; f->ldo = (f->Cout + 3) & ~3;
-  f->C16 = (f->C + 15) & ~15; f->Ch16 = (f->Ch + 15) & ~15; f->H16 = (f->H + 15) & ~15; f->Co16 = (f->Cout + 15) & ~15;
-  if (f->Ch16 == 0) f->Ch16 = 16;
-  if (prep) {
-    const long cc = (long)d->Ks * d->C * d->C;
-    const float* q = prep;
-    f->W = q; q += cc;
-    f->Wt = q; q += cc;
-    f->Winv = q; q += cc;
-    f->wz_t = q; q += (long)d->Ks * f->Ch * f->G;
-    f->whh_t = q; q += (long)d->Ks * d->H * f->G;
-    f->wfl_t = q; q += (long)d->Ks * d->H * f->Cout;
-    f->wc = q; q += (long)d->Ks * f->G * d->D;
-    f->ldconst = q;
-    // scratch (log-det parts, fp64 inverse workspace), then the zero-padded images of the register-resident cells
-    q = prep + prep_scratch_end(d);
-    const long Ks = d->Ks;
-    f->pW = q; q += Ks * f->C16 * f->C16;
-    f->pWt = q; q += Ks * f->C16 * f->C16;
-    f->pwz = q; q += Ks * f->Ch16 * f->NG * f->H16;
-    f->pwh = q; q += Ks * f->H16 * f->NG * f->H16;
-    f->pwfl = q; q += Ks * f->H16 * f->Co16;
-    f->bwfl = q; q += Ks * f->Co16 * f->H16;
-    f->bwh = q; q += Ks * f->NG * f->H16 * f->H16;
-    f->bwz = q; q += Ks * f->NG * f->H16 * f->Ch16;
-    f->pWinv = q; q += Ks * f->C16 * f->C16;
-    q = reinterpret_cast<const float*>((reinterpret_cast<uintptr_t>(q) + 15) & ~(uintptr_t)15);
-    f->xbwh = reinterpret_cast<const uint4*>(q); q += Ks * f->NG * f->H16 * f->H16;
-    f->xbwz = reinterpret_cast<const uint4*>(q); q += Ks * f->NG * f->H16 * f->Ch16;
-    q = reinterpret_cast<const float*>((reinterpret_cast<uintptr_t>(q) + 15) & ~(uintptr_t)15);
-    f->hwz = reinterpret_cast<const uint4*>(q); q += Ks * f->Ch16 * f->NG * f->H16;
-    f->hwh = reinterpret_cast<const uint4*>(q); q += Ks * f->H16 * f->NG * f->H16;
-    f->hwfl = reinterpret_cast<const uint4*>(q); q += Ks * f->H16 * f->Co16;
-    f->hWinv = reinterpret_cast<const uint4*>(q); q += Ks * f->C16 * f->C16;
-  }
-  return LFI_OK;
-}
-
 long stash_offsets(const FlowK& f, long* off) {
   const long KF = (long)f.Ks * f.F;
   long o = 0;
@@ -3881,74 +1956,9 @@ void bind_bstash(FlowK* f, float* b) {
   f->bPbias = b + off[9];
 }
 
-// LFI_FLOW_GENERIC=1 keeps the streaming cell kernels (tests cover both paths at sizes where either applies)
-bool flow_force_generic() { return lfi_env_set("LFI_FLOW_GENERIC"); }
-
-// LFI_FLOW_PIPE=0 keeps one launch per anti-diagonal instead of the persistent pipeline (tests cover both)
-bool flow_pipe_enabled() { return lfi_env_on("LFI_FLOW_PIPE"); }
-// LFI_PIPE_FENCE=1: consumers of a hand-off run an agent-scope acquire and read the tile with plain loads, instead of the
-// fence-free form (every store and load of the tile sc1; MI355X_MICROARCH.md, hand-offs measured without the acquire, row 1)
-// LFI_PIPE_X3=0: keep the exact f32 MFMA for the recurrent products of the persistent walk in bf16x3 mode too
-bool flow_pipe_x3_enabled() { return lfi_env_on("LFI_PIPE_X3"); }
-// shapes for which lfi_flow_prep leaves the reverse cell's fp16 fragment images (whole 32-k blocks everywhere: the X3 reverse cell's condition)
-bool flow_x3h_images_ok(const FlowK& f) { return !f.lstm && f.H16 % 32 == 0 && f.Ch16 % 32 == 0 && f.C16 % 32 == 0; }
-// LFI_SAMPLE_WFRAG16=0: the sampler's reverse cells load the f32 images and split them in registers, as before round 5
-bool flow_sample_wfrag16_enabled() { return lfi_env_on("LFI_SAMPLE_WFRAG16"); }
-// LFI_PIPE_FORCE_ABORT=1 (tests): start the walk with the abort word already set, as if a spin had timed out
-bool flow_pipe_force_abort() { return lfi_env_set("LFI_PIPE_FORCE_ABORT"); }
-int flow_pipe_fence() { return lfi_env_set("LFI_PIPE_FENCE") ? 1 : 0; }
-
-template <typename Kf>
-int set_flow_lds(Kf kernel, size_t bytes, const char* who) {
-  if (bytes > 160 * 1024) {
-    lfi_set_error("%s: needs %zu bytes of LDS (C/H too large)", who, bytes);
-    return LFI_ERR_UNSUPPORTED;
-  }
-  if (bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) {
-      lfi_set_error("%s: hipFuncSetAttribute(%zu): %s", who, bytes, hipGetErrorString(e));
-      return LFI_ERR_LAUNCH;
-    }
-  }
-  return LFI_OK;
-}
-
-// ---- bf16x3 / fp16x3 recurrent products: who takes them. One predicate per consumer; all want bf16x3 GEMM mode (gemm_precision bit 0)
-// and GRU cells. The tails differ on purpose, with what each kernel contracts over (a contraction runs in whole 32-k blocks).
-bool flow_x3_base(const lfi_flow_dims* d) { return (d->gemm_precision & 1) && !d->lstm; }
-// lfi_flow_prep's bf16 hi / lo fragment images of bwh / bwz (flow_prep_x3_kernel), the backward walk's weights: k runs over the hidden
-// units of a gate in both (Ch16 is a column count there). No switch and no size floor: the images are made for every shape that
-// flow_x3_bwd_walk can take, whatever the switches say when the walk runs.
-bool flow_x3_prep_images(const lfi_flow_dims* d, const FlowK& f) { return flow_x3_base(d) && f.H16 % 32 == 0; }
-// forward walk: its products contract over h (H16) and over z1 (Ch16): both 16-k paddings must be whole 32-k blocks
-bool flow_x3_fwd_walk(const lfi_flow_dims* d, const FlowK& f) {
-  return flow_x3_base(d) && f.H16 % 32 == 0 && f.Ch16 % 32 == 0 && flow_pipe_x3_enabled();
-}
-// backward walk: contracts over the hidden units only (the images above: no Ch16 term), and its bf16 operand images, 64 (NG H16 + 8)
-// bytes each, must fit the fp32 regions they replace (NG * H16 >= 128)
-bool flow_x3_bwd_walk(const lfi_flow_dims* d, const FlowK& f) {
-  return flow_x3_base(d) && f.H16 % 32 == 0 && f.NG * f.H16 >= 128 && flow_pipe_x3_enabled();
-}
-// backward planes: the walk above leaves its d(gate) images as the stash's operand planes, so the gate columns must be the stash's
-// own: H itself, not its padding H16, a multiple of 32 (no padding columns), which makes 3 * H the walk's NG * H16
-bool flow_x3_bwd_planes(const lfi_flow_dims* d) {
-  return flow_x3_base(d) && d->H % 32 == 0 && 3 * d->H >= 128 && flow_pipe_x3_enabled();
-}
-// reverse cell (the samplers' chain; three fp16 products - fp32-grade - in both bf16 modes of the per-frame GEMMs): it contracts over
-// z1, h and, for the inverse 1x1 convolution, the channels, so C16 joins the 32-k conditions - the shapes of flow_x3h_images_ok
-bool flow_x3_rev_cell(const lfi_flow_dims* d, const FlowK& f) {
-  return (d->gemm_precision & 1) && flow_x3h_images_ok(f) && flow_pipe_x3_enabled();
-}
-
 // ---- which instantiation runs: one picker per kernel family; set_flow_lds and the launch take the pointer
 typedef void (*FlowDiagKernel)(FlowK, int, int);
 typedef void (*FlowPipeKernel)(FlowK);
-typedef void (*FlowStepKernel)(FlowK, CellIO);
-typedef void (*FlowRevWalkKernel)(FlowK, RevWalk);
-typedef void (*FlowRevChainKernel)(FlowK, RevChain);
-typedef void (*FlowFwdChainKernel)(FlowK, FwdChain);
-typedef void (*FlowRowsChainKernel)(FlowK, RowsChain);
 
 FlowDiagKernel flow_diag_fwd_pick(bool fast, bool lstm) {
   if (!fast) return flow_diag_fwd_kernel;
@@ -3965,33 +1975,6 @@ FlowPipeKernel flow_pipe_fwd_pick(bool lstm, bool x3) {
 FlowPipeKernel flow_pipe_bwd_pick(bool lstm, bool x3) {
   if (lstm) return flow_pipe_bwd_kernel<4, false>;
   return x3 ? flow_pipe_bwd_kernel<3, true> : flow_pipe_bwd_kernel<3, false>;
-}
-FlowStepKernel flow_step_rev_pick(bool fast, bool lstm) {
-  if (!fast) return flow_step_kernel<true>;
-  return lstm ? flow_step_rev_fast_kernel<4> : flow_step_rev_fast_kernel<3>;
-}
-FlowRevWalkKernel flow_rev_walk_pick(bool lstm) { return lstm ? flow_rev_walk_kernel<4> : flow_rev_walk_kernel<3>; }
-template <bool NLL>
-FlowRevChainKernel flow_rev_chain_pick_(bool lstm, bool x3, bool xw) {
-  if (lstm) return flow_rev_chain_kernel<4, false, false, NLL>;
-  if (xw) return flow_rev_chain_kernel<3, true, true, NLL>;
-  return x3 ? flow_rev_chain_kernel<3, true, false, NLL> : flow_rev_chain_kernel<3, false, false, NLL>;
-}
-FlowRevChainKernel flow_rev_chain_pick(bool lstm, bool x3, bool xw, bool nll) {
-  return nll ? flow_rev_chain_pick_<true>(lstm, x3, xw) : flow_rev_chain_pick_<false>(lstm, x3, xw);
-}
-FlowFwdChainKernel flow_fwd_chain_pick(bool lstm, bool x3) {
-  if (lstm) return flow_fwd_chain_kernel<4, false>;
-  return x3 ? flow_fwd_chain_kernel<3, true> : flow_fwd_chain_kernel<3, false>;
-}
-
-// the two chains' own rules side by side: the reverse cells' form as flow_rev_chain_pick has it (x3: fp16 pieces at precisions 9 and 5,
-// xw: from the fragment images), the forward cells' as flow_fwd_chain_pick has it (x3f: precision 9 only); the LSTM cell exact in both
-FlowRowsChainKernel flow_rows_chain_pick(bool lstm, bool x3, bool xw, bool x3f) {
-  if (lstm) return flow_rows_chain_kernel<4, false, false, false>;
-  if (!x3) return flow_rows_chain_kernel<3, false, false, false>;
-  if (xw) return x3f ? flow_rows_chain_kernel<3, true, true, true> : flow_rows_chain_kernel<3, true, true, false>;
-  return x3f ? flow_rows_chain_kernel<3, true, false, true> : flow_rows_chain_kernel<3, true, false, false>;
 }
 
 // start state of a persistent walk: header and progress words cleared (LFI_PIPE_FORCE_ABORT=1: the abort word already set)
@@ -4363,609 +2346,6 @@ extern "C" int lfi_actnorm_init_apply(const double* sums, double count, int C, f
   LFI_REQUIRE(sums && bias && logs && count > 0 && C > 0, "lfi_actnorm_init_apply: bad arguments");
   hipLaunchKernelGGL(actnorm_apply_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sums, count, C, scale, bias, logs);
   LFI_LAUNCH_CHECK("lfi_actnorm_init_apply");
-  return LFI_OK;
-}
-
-extern "C" int lfi_flow_step(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, int k, int rows,
-                             const float* x_in, long ldx, const float* h_prev, const float* c_prev, const float* gic_k,
-                             float* x_out, long ldxo, float* h_out, float* c_out, float* ldc_acc, int reverse, void* stream) {
-  FlowK f = {};
-  int rc = fill_flow(d, p, prep, &f, "lfi_flow_step");
-  if (rc) return rc;
-  LFI_REQUIRE(prep && x_in && gic_k && x_out && h_out, "lfi_flow_step: null pointer");
-  LFI_REQUIRE(k >= 0 && k < d->Ks && rows > 0, "lfi_flow_step: bad k/rows");
-  LFI_REQUIRE(!d->lstm || c_out, "lfi_flow_step: the LSTM cell needs c_out");
-  CellIO io = {};
-  io.k = k; io.rows = rows; io.x_in = x_in; io.ldx = ldx; io.h_prev = h_prev; io.gic = gic_k;
-  io.c_prev = d->lstm ? c_prev : nullptr; io.c_out = d->lstm ? c_out : nullptr;
-  io.x_out = x_out; io.ldxo = ldxo; io.h_out = h_out; io.l_out = ldc_acc; io.l_accumulate = 1;
-  const bool fast = reverse && flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();   // (the forward cell has the streaming form only)
-  const size_t lds = (size_t)(fast ? carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total : carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout).total) *
-                     sizeof(float);
-  const FlowStepKernel cell = reverse ? flow_step_rev_pick(fast, f.lstm) : flow_step_kernel<false>;
-  if ((rc = set_flow_lds(cell, lds, "lfi_flow_step"))) return rc;
-  hipLaunchKernelGGL(cell, dim3(lfi_cdiv(rows, MB)), dim3(NT), lds, (hipStream_t)stream, f, io);
-  LFI_LAUNCH_CHECK("lfi_flow_step");
-  return LFI_OK;
-}
-
-// SeqGlow.invert (glow/models.py:617-645) as ONE persistent launch (flow_rev_walk_kernel) + the sum of the per-step log-dets.
-extern "C" int lfi_flow_seq_rev_ok(const lfi_flow_dims* d) {
-  if (!d) return 0;
-  const int Cout = d->affine ? 2 * (d->C - d->C / 2) : d->C - d->C / 2;
-  return (flow_fast_ok(d->C, d->H, Cout) && !flow_force_generic() && lfi_env_on("LFI_INVERT_WALK")) ? 1 : 0;
-}
-
-extern "C" long lfi_flow_seq_rev_work_floats(const lfi_flow_dims* d) {
-  if (!d) return 0;
-  const long F = (long)d->N * d->B, tiles = (d->B + MB - 1) / MB;
-  return (long)d->Ks * F * d->C + (long)d->Ks * F + lfi_colsum_work_floats(d->Ks, (int)F, 1) +
-         (((long)PIPE_HDR + d->Ks * tiles + 3) & ~3L) + 16;
-}
-
-extern "C" int lfi_flow_seq_rev(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* z,
-                                const float* gic, float* x_out, float* logdet, float* h, float* cstate, float* work,
-                                void* stream) {
-  FlowK f = {};
-  int rc = fill_flow(d, p, prep, &f, "lfi_flow_seq_rev");
-  if (rc) return rc;
-  LFI_REQUIRE(prep && z && gic && x_out && logdet && h && work, "lfi_flow_seq_rev: null pointer");
-  LFI_REQUIRE(!d->lstm || cstate, "lfi_flow_seq_rev: the LSTM cell needs cstate");
-  LFI_REQUIRE(lfi_flow_seq_rev_ok(d), "lfi_flow_seq_rev: C <= 64, hidden_channels <= 128 only (lfi_flow_seq_rev_ok); wider flows "
-              "walk cell by cell with lfi_flow_step");
-  LFI_REQUIRE((long)f.N * f.B < (1L << 31), "lfi_flow_seq_rev: too many frames");
-  hipStream_t st = (hipStream_t)stream;
-  const long F = f.F;
-  RevWalk rw = {};
-  rw.z = z; rw.gic = gic; rw.out = x_out; rw.h = h; rw.cstate = cstate;
-  rw.tiles = work;
-  rw.ldk = rw.tiles + (long)f.Ks * F * f.C;
-  float* cws = rw.ldk + (long)f.Ks * F;
-  rw.pipe = reinterpret_cast<unsigned*>((reinterpret_cast<uintptr_t>(cws + lfi_colsum_work_floats(f.Ks, (int)F, 1)) + 15) & ~(uintptr_t)15);
-  const size_t words = (size_t)(((long)PIPE_HDR + (long)f.Ks * f.nbt + 3) & ~3L);
-  hipError_t me = hipMemsetAsync(rw.pipe, 0, words * sizeof(unsigned), st);
-  LFI_REQUIRE(me == hipSuccess, "lfi_flow_seq_rev: hipMemsetAsync: %s", hipGetErrorString(me));
-  const size_t lds = (size_t)carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total * sizeof(float);
-  const FlowRevWalkKernel walk = flow_rev_walk_pick(f.lstm);
-  if ((rc = set_flow_lds(walk, lds, "lfi_flow_seq_rev"))) return rc;
-  hipLaunchKernelGGL(walk, dim3(f.Ks * f.nbt), dim3(NT), lds, st, f, rw);
-  LFI_LAUNCH_CHECK("lfi_flow_seq_rev");
-  // logdet[n][b] = sum over the flow steps of the coupling log-dets (the constant ActNorm / invconv part is the caller's)
-  return lfi_colsum_f32(rw.ldk, F, 0, f.Ks, (int)F, 1, logdet, 0, 1.0f, 0, cws, stream);
-}
-
-// SeqGlow.inference (glow/models.py:567-596): everything that does not depend on generated frames was hoisted by the
-// caller into pre_static; per frame two small GEMMs (window part of cond_transform, then W_ih[:, Ch:] c) and Ks
-// reverse cells. The growing torch.cat history of the reference (:591, O(T^2) copies) is a preallocated buffer here.
-extern "C" long lfi_flow_sample_p1_work_floats(const lfi_flow_dims* d, const lfi_p1enc* e, int hist1) {
-  if (!d || !e || e->kind == 0) return 0;
-  const long hid4 = (e->hid + 3) & ~3;
-  long n = (long)d->B * hid4 + 16;
-  if (e->kind == 2 || e->kind == 3) {
-    const int ng = e->kind == 3 ? 4 : 3;
-    lfi_enc_desc ed = {};
-    ed.B = d->B; ed.T = hist1; ed.N = 1; ed.start = hist1 - 1; ed.hist = hist1; ed.hid = e->hid; ed.lstm = e->kind == 3;
-    n += (long)d->B * hist1 * ng * e->hid + lfi_encode_windows_work_floats(&ed) + (long)hist1 * d->B * e->hid;
-    if (e->kind == 3) n += (long)hist1 * d->B * 5 * e->hid;   // the LSTM encoder keeps its cell state in the gate stash
-  }
-  return n;
-}
-
-extern "C" long lfi_flow_sample_work_floats(const lfi_flow_dims* d) {
-  if (!d) return 0;
-  const int G = (d->lstm ? 4 : 3) * d->H;
-  const long tiles = (d->B + MB - 1) / MB;
-  return (long)d->B * d->Ks * d->D + (long)d->Ks * d->B * G + 2L * d->B * d->C + 16
-         + (((long)PIPE_HDR + d->Ks * tiles + 3) & ~3L) + 4    // + the hand-off words of the per-frame reverse chain
-         + (long)d->B * 64 * ((d->C + 3) & ~3) + 4             // + the aligned copy of the raw prev_p1_face window (hist1 <= 64)
-         + lfi_internal_sample_cond_bytes(d->B, d->Ks, G, 512) / 4 + 64;   // + the fused conditioning's fragments (window <= 512 floats)
-}
-
-extern "C" int lfi_flow_sample_seq(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct,
-                                   long E, int hist1, float* pre_static, const float* noise, float* faces, int seq_len,
-                                   int start, int nframes, float* h, float* cstate, const lfi_p1enc* p1, float* p1work,
-                                   float* work, void* stream) {
-  return lfi_flow_sample_seq_from(d, p, prep, wct, E, hist1, pre_static, noise, faces, seq_len, start, nframes, 0, h, cstate, p1,
-                                  p1work, work, stream);
-}
-
-// A run of `nframes` generated frames that is NOT the first of its sequence: first_frame = how many frames of the sequence earlier
-// calls generated (> 0: the recurrent state in h / cstate is theirs and carries on; pre_static / noise / start are this run's own).
-// The engine samples a long sequence as a few such runs so that the static part of run i + 1 (window encoders, the
-// non-autoregressive cond_transform columns) can be computed on a second stream under the latency-bound chain of run i.
-extern "C" int lfi_flow_sample_seq_from(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct,
-                                        long E, int hist1, float* pre_static, const float* noise, float* faces, int seq_len,
-                                        int start, int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1,
-                                        float* p1work, float* work, void* stream) {
-  return lfi_flow_sample_seq_nll(d, p, prep, wct, E, hist1, pre_static, noise, faces, seq_len, start, nframes, first_frame, h, cstate,
-                                 p1, p1work, work, nullptr, nullptr, stream);
-}
-
-// The per-frame conditioning front end of the sampler (lfi_flow_sample_seq_nll) and of the teacher-forced scorer
-// (lfi_flow_score_seq_from): the carve of `work`, which form the window part of cond_transform + gic takes, and its launches for one
-// frame. Both callers run the same launches of the same kernels for a frame.
-namespace {
-struct SampleFront {
-  const lfi_flow_dims* d; const lfi_flow_params* p; const FlowK* f;
-  const float* wct; long E; int hist1; float* faces; int seq_len;
-  const lfi_p1enc* p1; float* p1work; int p1kind, p1col;
-  float *gic, *xa, *xb, *wstage;   // [Ks][B][G]; the chain's B x C ping / pong tiles; the aligned copy of the raw window
-  unsigned* chain_state; size_t chain_words;
-  int ldw, K1;
-  bool stage_win, fused, chain;
-  void* cfrags;
-};
-// `chain`: a one-launch chain follows every frame's conditioning (the fused kernel then clears its ticket / progress words)
-// pipe / pipe_words: those words, when they are not the carve's own
-int sample_front_setup(SampleFront* s, const lfi_flow_dims* d, const lfi_flow_params* p, const FlowK* f, const float* wct, long E, int hist1,
-                       const float* pre_static, float* faces, int seq_len, const lfi_p1enc* p1, float* p1work, float* work, bool chain,
-                       int nframes, void* stream, const char* who, unsigned* pipe = nullptr, size_t pipe_words = 0) {
-  s->d = d; s->p = p; s->f = f; s->wct = wct; s->E = E; s->hist1 = hist1; s->faces = faces; s->seq_len = seq_len;
-  s->p1 = p1; s->p1work = p1work; s->chain = chain;
-  s->p1kind = p1 ? p1->kind : 0;
-  LFI_REQUIRE(s->p1kind >= 0 && s->p1kind <= 3, "%s: bad p1_face encoder kind %d", who, s->p1kind);
-  LFI_REQUIRE(s->p1kind == 0 || (p1work && p1->hid > 0), "%s: encoded p1_face window needs p1work", who);
-  s->p1col = p1 ? p1->col : 0;
-  const int B = f->B, C = f->C, D = f->D, Ks = f->Ks, G = f->G;
-  s->gic = work + (long)B * Ks * D;        // [Ks][B][G]   (the first B x Ks*D floats: round 2's copy of c, unused now)
-  s->xa = s->gic + (long)Ks * B * G;       // B x C ping
-  s->xb = s->xa + (long)B * C;             // B x C pong
-  s->chain_state = reinterpret_cast<unsigned*>((reinterpret_cast<uintptr_t>(s->xb + (long)B * C) + 15) & ~(uintptr_t)15);
-  s->chain_words = (size_t)(((long)PIPE_HDR + (long)Ks * f->nbt + 3) & ~3L);
-  // raw prev_p1_face windows start (t - hist1) * C floats into a row: 16-byte aligned only on every other frame at C = 50,
-  // which sent half of the window products to the exact-f32 kernel (91 vs 35 us). A gather into an aligned buffer first.
-  s->wstage = reinterpret_cast<float*>(s->chain_state + s->chain_words);
-  // pipe: a chain with more hand-off words than one direction's (flow_rows_chain_kernel) brings its own, and the fused conditioning
-  // kernel clears those; everything else of the carve stays where every other caller has it
-  if (pipe) { s->chain_state = pipe; s->chain_words = pipe_words; }
-  s->ldw = (hist1 * C + 3) & ~3;
-  s->stage_win = s->p1kind == 0 && hist1 <= 64;
-  // raw window + fp16 pieces (precision 9) + final widths: cond_transform's window part and the coupling cell's input projection
-  // as ONE launch per frame, c never written (lfi_sample.hip); the weights' fragments are made here, once per call
-  s->K1 = hist1 * C;
-  s->fused = s->stage_win && (d->gemm_precision & 0xff) == 9 && lfi_internal_sample_cond_ok(D, G, s->K1) &&
-             (reinterpret_cast<uintptr_t>(pre_static) & 15) == 0;
-  s->cfrags = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(s->wstage + (long)B * 64 * ((C + 3) & ~3)) + 255) & ~(uintptr_t)255);
-  if (s->fused && nframes > 0) return lfi_internal_sample_cond_prepare(wct, E, s->p1col, s->K1, f->wc, Ks, G, s->cfrags, stream);
-  return LFI_OK;
-}
-// frame t of the sequence in `faces`: gic of all flow steps from the frame's rows `cfr` of pre_static (B x Ks D, overwritten) and the
-// window faces[:, t - hist1 : t]. have_xfrag: the window's fp16 fragments are already in cfrags (the previous frame's reverse chain)
-int sample_front_frame(const SampleFront& s, int t, float* cfr, int have_xfrag, void* stream) {
-  const lfi_flow_dims* d = s.d;
-  const lfi_p1enc* p1 = s.p1;
-  const int B = s.f->B, C = s.f->C, D = s.f->D, Ks = s.f->Ks, G = s.f->G, hist1 = s.hist1, seq_len = s.seq_len;
-  int rc;
-  // c = LeakyReLU(pre_static[n] + window @ Wct[:, :hist1*C]^T), IN PLACE: frame n's rows of pre_static are read by this product
-  // alone, so they are its pre-activation addend and its output at once (a 32 MB copy per frame into a separate c otherwise)
-  lfi_gemm_desc q = {};
-  q.batch = 1; q.M = B; q.N = Ks * D; q.K = hist1 * C;
-  q.A = s.faces + (long)(t - hist1) * C; q.lda = (long)seq_len * C; q.a_kcontig = 1;
-  q.B = s.wct + s.p1col; q.ldb = s.E; q.b_kcontig = 1;
-  q.C = cfr; q.ldc = (long)Ks * D; q.accumulate = 2; q.act = 1; q.slope = 0.01f; q.precision = d->gemm_precision;
-  if (s.p1kind != 0) {
-    // features of the window first: e (B x hid4), then c = LeakyReLU(pre_static + e Wct[:, col : col + hid]^T)
-    const int hid = p1->hid, hid4 = (hid + 3) & ~3;
-    float* ebuf = s.p1work;                       // B x hid4
-    if (s.p1kind == 1) {
-      lfi_gemm_desc m = {};
-      m.batch = 1; m.M = B; m.N = hid; m.K = hist1 * C;
-      m.A = q.A; m.lda = q.lda; m.a_kcontig = 1;
-      m.B = p1->w1; m.ldb = (long)hist1 * C; m.b_kcontig = 1;
-      m.C = ebuf; m.ldc = hid4; m.bias = p1->b1; m.act = 1; m.slope = 0.01f; m.precision = d->gemm_precision;
-      if ((rc = lfi_gemm_f32(&m, stream))) return rc;
-    } else {
-      // GRU / LSTM over the window: input projections of its hist1 frames (batched over the step), then the recurrence
-      const int ng = s.p1kind == 3 ? 4 : 3;
-      float* xp = ebuf + (long)B * hid4;          // [B][hist1][ng * hid]
-      float* ework = xp + (long)B * hist1 * ng * hid;
-      lfi_gemm_desc m = {};
-      m.batch = hist1; m.M = B; m.N = ng * hid; m.K = C;
-      m.A = q.A; m.lda = q.lda; m.a_kcontig = 1; m.strideA = C;
-      m.B = p1->w_ih; m.ldb = C; m.b_kcontig = 1;
-      m.C = xp; m.ldc = (long)hist1 * ng * hid; m.strideC = ng * hid; m.precision = d->gemm_precision;
-      if ((rc = lfi_gemm_f32(&m, stream))) return rc;
-      lfi_enc_desc ed = {};
-      ed.B = B; ed.T = hist1; ed.N = 1; ed.start = hist1 - 1; ed.hist = hist1; ed.hid = hid;
-      ed.ldcond = hid4; ed.col = 0; ed.precision = d->gemm_precision; ed.dup = 0; ed.lstm = s.p1kind == 3;
-      float* hs = ework + lfi_encode_windows_work_floats(&ed);   // unfused path / LSTM: state sequence
-      float* gst = s.p1kind == 3 ? hs + (long)hist1 * B * hid : nullptr;   // LSTM: gate + cell stash, 5 * hid per (step, row)
-      if ((rc = lfi_encode_windows_fwd(&ed, xp, p1->w_hh, p1->b_ih, p1->b_hh, nullptr, ebuf, gst, hs, ework, stream)))
-        return rc;
-    }
-    q.K = hid; q.A = ebuf; q.lda = hid4;
-  }
-  if (s.fused) {
-    // (its first workgroup also clears the chain's ticket / progress words for the launch that follows: no memset node per frame)
-    return lfi_internal_sample_cond(s.faces, (long)seq_len * C, (long)(t - hist1) * C, s.K1, B, Ks, G, cfr, s.p->b_ih, s.cfrags, s.gic, 0.01f,
-                                    (long)B * seq_len * C, s.chain ? s.chain_state : nullptr, (int)s.chain_words, have_xfrag, stream);
-  }
-  if (s.stage_win) {
-    if ((rc = lfi_gather_windows(s.faces, B, seq_len, C, 1, t, hist1, 0, nullptr, s.wstage, s.ldw, 0, stream))) return rc;
-    q.A = s.wstage; q.lda = s.ldw;
-  }
-  if ((rc = lfi_gemm_f32(&q, stream))) return rc;
-  // gic[k] = c[:, kD:(k+1)D] @ W_ih[k][:, Ch:]^T + b_ih[k]
-  lfi_gemm_desc r = {};
-  r.batch = Ks; r.M = B; r.N = G; r.K = D;
-  r.A = cfr; r.lda = (long)Ks * D; r.a_kcontig = 1; r.strideA = D;
-  r.B = s.f->wc; r.ldb = D; r.b_kcontig = 1; r.strideB = (long)G * D;
-  r.C = s.gic; r.ldc = G; r.strideC = (long)B * G;
-  r.bias = s.p->b_ih; r.strideBias = G; r.precision = d->gemm_precision;
-  return lfi_gemm_f32(&r, stream);
-}
-}  // namespace
-
-// The per-step launches' finish of a frame's NLL (LFI_SAMPLE_CHAIN=0 and the generic cell; the chain kernel does this in its cells):
-// acc[b] = sum over the flow steps of the reverse coupling log-dets, left there by the cells' l_out.
-__global__ __launch_bounds__(256) void sample_nll_finish_kernel(const float* __restrict__ noise, const float* __restrict__ acc,
-                                                                const float* __restrict__ ldconst, int B, int C,
-                                                                float* __restrict__ nll) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= B) return;
-  float lp = 0.0f;
-  for (int c = 0; c < C; ++c) {
-    const float v = noise[(long)b * C + c];
-    lp += -0.5f * (v * v + LOG2PI_F);
-  }
-  nll[b] = -(ldconst[0] - acc[b] + lp) / LN2_F;
-}
-
-extern "C" long lfi_flow_sample_nll_work_floats(const lfi_flow_dims* d) {
-  if (!d) return 0;
-  return 2L * d->B + 8;   // the two ping-pong hand-over arrays of the chain (the first is the per-step launches' accumulator)
-}
-
-// lfi_flow_sample_seq_from that also leaves the per-frame NLL (bits) of every frame it generates in nll (nframes x B); nll == NULL:
-// lfi_flow_sample_seq_from itself - the same launches of the same kernels.
-extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct,
-                                       long E, int hist1, float* pre_static, const float* noise, float* faces, int seq_len,
-                                       int start, int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1,
-                                       float* p1work, float* work, float* nll, float* nll_work, void* stream) {
-  FlowK f = {};
-  int rc = fill_flow(d, p, prep, &f, "lfi_flow_sample_seq");
-  if (rc) return rc;
-  LFI_REQUIRE(first_frame >= 0, "lfi_flow_sample_seq_from: negative first_frame");
-  LFI_REQUIRE(prep && wct && pre_static && noise && faces && h && work, "lfi_flow_sample_seq: null pointer");
-  LFI_REQUIRE(hist1 >= 0 && hist1 <= start && start + nframes <= seq_len, "lfi_flow_sample_seq: bad frame range");
-  LFI_REQUIRE((long)hist1 * d->C <= E, "lfi_flow_sample_seq: window wider than the feature vector");
-  LFI_REQUIRE(!d->lstm || cstate, "lfi_flow_sample_seq: the LSTM cell needs cstate");
-  LFI_REQUIRE(!nll || nll_work, "lfi_flow_sample_seq_nll: nll needs nll_work (lfi_flow_sample_nll_work_floats)");
-  const int B = f.B, C = f.C, H = f.H, D = f.D, Ks = f.Ks;
-  hipStream_t st = (hipStream_t)stream;
-  const bool fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
-  const Carve cv = carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout);
-  const size_t lds = (size_t)(fast ? carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total : cv.total) * sizeof(float);
-  const FlowStepKernel cell = flow_step_rev_pick(fast, f.lstm);
-  if ((rc = set_flow_lds(cell, lds, "lfi_flow_sample_seq"))) return rc;
-  // LFI_SAMPLE_CHAIN=0 keeps one launch per flow step
-  const bool chain = fast && lfi_env_on("LFI_SAMPLE_CHAIN");
-  const bool x3 = flow_x3_rev_cell(d, f);
-  // the per-frame conditioning (sample_front_*): the carve of `work`, the fused kernel's weight fragments once per call
-  SampleFront sf = {};
-  if ((rc = sample_front_setup(&sf, d, p, &f, wct, E, hist1, pre_static, faces, seq_len, p1, p1work, work, chain, nframes, stream,
-                               "lfi_flow_sample_seq"))) return rc;
-  float *gic = sf.gic, *xa = sf.xa, *xb = sf.xb;
-  unsigned* chain_state = sf.chain_state;
-  const size_t chain_words = sf.chain_words;
-  const bool fused = sf.fused;
-  void* cfrags = sf.cfrags;
-  const int K1 = sf.K1, G = f.G;
-  // LFI_SAMPLE_XF_CHAIN=0 keeps the window-fragment kernel in front of every frame's conditioning
-  const bool xf_chain = fused && chain && lfi_env_on("LFI_SAMPLE_XF_CHAIN");
-  // the reverse cells' weights as the fp16 fragment images lfi_flow_prep left (no split in every workgroup of every frame; x3 is true
-  // only for the shapes that have them, flow_x3h_images_ok)
-  const bool xw = x3 && chain && flow_sample_wfrag16_enabled();
-  // one launch for the whole chain of a frame; with nll the cells also pass the rows' running log-density down the chain
-  const FlowRevChainKernel chain_kernel = flow_rev_chain_pick(f.lstm, x3, xw, nll != nullptr);
-  if (chain && (rc = set_flow_lds(chain_kernel, lds, nll ? "lfi_flow_sample_seq_nll" : "lfi_flow_sample_seq"))) return rc;
-  for (int n = 0; n < nframes; ++n) {
-    const int t = start + n;
-    // (from the run's second frame on the window's fragments are already there: the previous frame's chain left them)
-    if ((rc = sample_front_frame(sf, t, pre_static + (long)n * B * Ks * D, (xf_chain && n > 0) ? 1 : 0, stream))) return rc;
-    // reverse flow: z -> x through steps Ks-1 .. 0
-    if (chain) {   // one launch for the whole chain of this frame
-      RevChain rcn = {};
-      rcn.noise = noise + (long)n * B * C; rcn.xa = xa; rcn.xb = xb;
-      rcn.frame = faces + (long)t * C; rcn.ld_frame = (long)seq_len * C;
-      rcn.gic = gic; rcn.h = h; rcn.cstate = cstate; rcn.has_prev = first_frame + n > 0 ? 1 : 0; rcn.frame_no = first_frame + n; rcn.pipe = chain_state;
-      if (xf_chain && n + 1 < nframes) {
-        rcn.xf = reinterpret_cast<_Float16*>(lfi_internal_sample_cond_xfrag_ptr(cfrags, Ks, G, K1));
-        rcn.faces = faces; rcn.xf_off = (long)(t + 1 - hist1) * C; rcn.K1 = K1; rcn.NM1 = (K1 + 31) / 32;
-      }
-      if (!fused) {   // (the fused conditioning kernel has cleared them)
-        hipError_t me = hipMemsetAsync(chain_state, 0, chain_words * sizeof(unsigned), st);
-        LFI_REQUIRE(me == hipSuccess, "lfi_flow_sample_seq: hipMemsetAsync: %s", hipGetErrorString(me));
-      }
-      if (nll) { rcn.qa = nll_work; rcn.qb = nll_work + B; rcn.nll = nll + (long)n * B; }
-      hipLaunchKernelGGL(chain_kernel, dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
-      continue;
-    }
-    const float* xin = noise + (long)n * B * C;
-    long ldx = C;
-    for (int k = Ks - 1; k >= 0; --k) {
-      CellIO io = {};
-      io.k = k; io.rows = B; io.x_in = xin; io.ldx = ldx;
-      io.h_prev = first_frame + n > 0 ? h + (long)k * B * H : nullptr;
-      io.gic = gic + (long)k * B * G;
-      io.h_out = h + (long)k * B * H;
-      if (f.lstm) { io.c_prev = first_frame + n > 0 ? cstate + (long)k * B * H : nullptr; io.c_out = cstate + (long)k * B * H; }
-      if (k == 0) { io.x_out = faces + (long)t * C; io.ldxo = (long)seq_len * C; }
-      else { io.x_out = (k & 1) ? xa : xb; io.ldxo = C; }
-      if (nll) { io.l_out = nll_work; io.l_accumulate = k + 1 < Ks; }   // (launch after launch: no two workgroups at one word at a time)
-      hipLaunchKernelGGL(cell, dim3(f.nbt), dim3(NT), lds, st, f, io);
-      xin = io.x_out; ldx = io.ldxo;
-    }
-    if (nll)
-      hipLaunchKernelGGL(sample_nll_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, noise + (long)n * B * C, nll_work,
-                         f.ldconst, B, C, nll + (long)n * B);
-  }
-  LFI_LAUNCH_CHECK("lfi_flow_sample_seq");
-  return LFI_OK;
-}
-
-// ---- teacher-forced frames of a sequence whose state is carried (SampleStream.observe): the sampler's front end, then the FORWARD chain
-// The per-step launches' finish of an observed frame (LFI_SAMPLE_CHAIN=0 and the generic cell; the forward chain does this in its
-// last cell): acc[b] = sum over the flow steps of the forward coupling log-dets (the cells' l_out), zlast = the last step's tile.
-__global__ __launch_bounds__(256) void score_finish_kernel(const float* __restrict__ zlast, const float* __restrict__ acc,
-                                                           const float* __restrict__ ldconst, int B, int C, float* __restrict__ z,
-                                                           float* __restrict__ nll) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= B) return;
-  float lp = 0.0f;
-  for (int c = 0; c < C; ++c) {
-    const float v = zlast[(long)b * C + c];
-    lp += -0.5f * (v * v + LOG2PI_F);
-    if (z) z[(long)b * C + c] = v;
-  }
-  nll[b] = -(ldconst[0] + acc[b] + lp) / LN2_F;
-}
-
-extern "C" long lfi_flow_score_work_floats(const lfi_flow_dims* d) {
-  if (!d) return 0;
-  return 2L * d->B + 8;   // the two ping-pong log-det hand-over arrays of the forward chain (the first: the per-step launches' accumulator)
-}
-
-extern "C" int lfi_flow_score_seq_from(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct, long E,
-                                       int hist1, float* pre_static, float* faces, int seq_len, int start, int nframes, int first_frame,
-                                       float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work, float* score_work,
-                                       float* z, float* nll, void* stream) {
-  FlowK f = {};
-  int rc = fill_flow(d, p, prep, &f, "lfi_flow_score_seq_from");
-  if (rc) return rc;
-  LFI_REQUIRE(first_frame >= 0, "lfi_flow_score_seq_from: negative first_frame");
-  LFI_REQUIRE(prep && wct && pre_static && faces && h && work && score_work && nll, "lfi_flow_score_seq_from: null pointer");
-  LFI_REQUIRE(hist1 >= 0 && hist1 <= start && nframes >= 0 && start + nframes <= seq_len, "lfi_flow_score_seq_from: bad frame range");
-  LFI_REQUIRE((long)hist1 * d->C <= E, "lfi_flow_score_seq_from: window wider than the feature vector");
-  LFI_REQUIRE(!d->lstm || cstate, "lfi_flow_score_seq_from: the LSTM cell needs cstate");
-  const int B = f.B, C = f.C, H = f.H, D = f.D, Ks = f.Ks, G = f.G;
-  hipStream_t st = (hipStream_t)stream;
-  // the register-resident chain for the shapes the sampler's chain takes; otherwise (and with LFI_SAMPLE_CHAIN=0) Ks launches of the
-  // streaming forward cell + the finish
-  const bool chain = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic() && lfi_env_on("LFI_SAMPLE_CHAIN");
-  // three fp16 products for per-frame arithmetic 9 only. The reverse cells keep them at 5 as well - their operands are bounded (the
-  // prior draw, h in (-1, 1)) - but this chain's first operand is actnorm of a frame the CALLER supplies: a value beyond fp16's range
-  // would turn into inf - inf = NaN in the split and stay in h / c. 5 is the arithmetic a session falls back to when its range guard
-  // trips and must have no range caveat: it takes the exact-f32 cell (as 0 and the LSTM cell do), which is at least as accurate as
-  // six bf16 products.
-  const bool x3 = flow_x3_rev_cell(d, f) && (d->gemm_precision & 0xff) == 9;
-  const size_t lds = (size_t)(chain ? carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total : carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout).total) *
-                     sizeof(float);
-  const FlowFwdChainKernel chain_kernel = flow_fwd_chain_pick(f.lstm, x3);
-  if ((rc = chain ? set_flow_lds(chain_kernel, lds, "lfi_flow_score_seq_from") : set_flow_lds(flow_step_kernel<false>, lds, "lfi_flow_score_seq_from")))
-    return rc;
-  SampleFront sf = {};
-  if ((rc = sample_front_setup(&sf, d, p, &f, wct, E, hist1, pre_static, faces, seq_len, p1, p1work, work, chain, nframes, stream,
-                               "lfi_flow_score_seq_from"))) return rc;
-  float *qa = score_work, *qb = score_work + B;
-  for (int n = 0; n < nframes; ++n) {
-    const int t = start + n;
-    if ((rc = sample_front_frame(sf, t, pre_static + (long)n * B * Ks * D, 0, stream))) return rc;
-    float* zn = z ? z + (long)n * B * C : nullptr;
-    const int has_prev = first_frame + n > 0 ? 1 : 0;
-    if (chain) {
-      FwdChain fc = {};
-      fc.frame = faces + (long)t * C; fc.ld_frame = (long)seq_len * C;
-      fc.xa = sf.xa; fc.xb = sf.xb; fc.gic = sf.gic; fc.h = h; fc.cstate = cstate; fc.has_prev = has_prev; fc.pipe = sf.chain_state;
-      fc.qa = qa; fc.qb = qb; fc.z = zn; fc.nll = nll + (long)n * B;
-      if (!sf.fused) {   // (the fused conditioning kernel has cleared them)
-        hipError_t me = hipMemsetAsync(sf.chain_state, 0, sf.chain_words * sizeof(unsigned), st);
-        LFI_REQUIRE(me == hipSuccess, "lfi_flow_score_seq_from: hipMemsetAsync: %s", hipGetErrorString(me));
-      }
-      hipLaunchKernelGGL(chain_kernel, dim3(Ks * f.nbt), dim3(NT), lds, st, f, fc);
-      continue;
-    }
-    const float* xin = faces + (long)t * C;
-    long ldx = (long)seq_len * C;
-    for (int k = 0; k < Ks; ++k) {
-      CellIO io = {};
-      io.k = k; io.rows = B; io.x_in = xin; io.ldx = ldx;
-      io.h_prev = has_prev ? h + (long)k * B * H : nullptr;
-      io.gic = sf.gic + (long)k * B * G;
-      io.h_out = h + (long)k * B * H;
-      if (f.lstm) { io.c_prev = has_prev ? cstate + (long)k * B * H : nullptr; io.c_out = cstate + (long)k * B * H; }
-      io.x_out = (k & 1) ? sf.xa : sf.xb; io.ldxo = C;
-      io.l_out = qa; io.l_accumulate = k > 0;   // (launch after launch: no two workgroups at one word at a time)
-      hipLaunchKernelGGL(flow_step_kernel<false>, dim3(f.nbt), dim3(NT), lds, st, f, io);
-      xin = io.x_out; ldx = C;
-    }
-    hipLaunchKernelGGL(score_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, xin, qa, f.ldconst, B, C, zn, nll + (long)n * B);
-  }
-  LFI_LAUNCH_CHECK("lfi_flow_score_seq_from");
-  return LFI_OK;
-}
-
-// ---- one frame of a session whose rows generate or observe, row by row (SampleStream.step_rows)
-namespace {
-// words of flow_rows_chain_kernel's state: ticket, abort, 2 reserved, then Ks * tiles progress words per direction
-inline long rows_pipe_words(long Ks, long tiles) { return ((long)PIPE_HDR + 2 * Ks * tiles + 3) & ~3L; }
-
-// the carve of lfi_flow_step_rows_from's second work area
-struct RowsWork {
-  unsigned* pipe; long pipe_words;
-  float *xa, *xb;     // the forward direction's B x C ping / pong tiles
-  float *qa, *qb;     // its log-det hand-over (the per-step launches' accumulator)
-  float *hs, *cs;     // per-step launches only: [Ks][B][H] copies of h / cstate the forward direction advances
-  float *gframe;      // ... B x C: the frame the reverse direction generates
-  float *fnll;        // ... B: the forward direction's NLL
-  long total;
-};
-RowsWork rows_work_carve(float* base, long B, long C, long H, long Ks) {
-  RowsWork w = {};
-  const long tiles = (B + MB - 1) / MB;
-  long o = 0;
-  w.pipe = reinterpret_cast<unsigned*>(base); w.pipe_words = rows_pipe_words(Ks, tiles); o += w.pipe_words;
-  w.xa = base + o; o += B * C;
-  w.xb = base + o; o += B * C;
-  w.qa = base + o; o += B;
-  w.qb = base + o; o += B;
-  w.hs = base + o; o += Ks * B * H;
-  w.cs = base + o; o += Ks * B * H;
-  w.gframe = base + o; o += B * C;
-  w.fnll = base + o; o += B;
-  w.total = o + 8;
-  return w;
-}
-
-// The per-step launches' last launch of a mixed frame: the reverse direction has advanced h / cstate of EVERY row and left its frame in
-// gframe and its NLL in nll; the forward direction has advanced the copies hs / cs from the frame in `faces` and left its NLL in fnll.
-// Observing rows take the forward direction's state and NLL (their frame is in place), generating rows their generated frame.
-// Thread (row, element) over Ks * H state elements and C frame elements of every row.
-__global__ __launch_bounds__(256) void rows_merge_kernel(const int* __restrict__ role, int B, int C, int H, int Ks, float* __restrict__ h,
-                                                         float* __restrict__ cstate, const float* __restrict__ hs,
-                                                         const float* __restrict__ cs, float* __restrict__ frame, long ld_frame,
-                                                         const float* __restrict__ gframe, float* __restrict__ nll,
-                                                         const float* __restrict__ fnll) {
-  const int b = blockIdx.x;
-  const bool observes = role[b] != 0;
-  if (observes) {
-    for (int e = threadIdx.x; e < Ks * H; e += 256) {
-      const long o = ((long)(e / H) * B + b) * H + e % H;
-      h[o] = hs[o];
-      if (cstate) cstate[o] = cs[o];
-    }
-    if (threadIdx.x == 0) nll[b] = fnll[b];
-  } else {
-    for (int c = threadIdx.x; c < C; c += 256) frame[(long)b * ld_frame + c] = gframe[(long)b * C + c];
-  }
-}
-}  // namespace
-
-extern "C" long lfi_flow_step_rows_work_floats(const lfi_flow_dims* d) {
-  if (!d) return 0;
-  return rows_work_carve(nullptr, d->B, d->C, d->H, d->Ks).total;
-}
-
-// One frame (nframes = 1) in which row b observes where observed[b] != 0 - its frame is in faces[:, start] already - and generates from
-// noise[b] otherwise: lfi_flow_sample_seq_nll's arguments, the role words and a second work area (lfi_flow_step_rows_work_floats).
-// Every row's h / cstate, frame and nll (B, required) are what lfi_flow_score_seq_from or lfi_flow_sample_seq_nll alone leaves for it.
-// The conditioning front end once, then flow_rows_chain_kernel; shapes and switches outside the chain: the forward direction's
-// per-step launches on copies of h / cstate, the reverse direction's on the state itself with its frame aside, one merge launch.
-extern "C" int lfi_flow_step_rows_from(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct, long E,
-                                       int hist1, float* pre_static, const float* noise, float* faces, int seq_len, int start,
-                                       int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1, float* p1work,
-                                       float* work, float* nll, float* nll_work, const int* observed, float* rows_work, void* stream) {
-  FlowK f = {};
-  int rc = fill_flow(d, p, prep, &f, "lfi_flow_step_rows_from");
-  if (rc) return rc;
-  LFI_REQUIRE(first_frame >= 0, "lfi_flow_step_rows_from: negative first_frame");
-  LFI_REQUIRE(prep && wct && pre_static && noise && faces && h && work && nll && nll_work && observed && rows_work,
-              "lfi_flow_step_rows_from: null pointer");
-  LFI_REQUIRE(nframes == 1, "lfi_flow_step_rows_from: %d frames (one frame per call)", nframes);
-  LFI_REQUIRE(hist1 >= 0 && hist1 <= start && start + nframes <= seq_len, "lfi_flow_step_rows_from: bad frame range");
-  LFI_REQUIRE((long)hist1 * d->C <= E, "lfi_flow_step_rows_from: window wider than the feature vector");
-  LFI_REQUIRE(!d->lstm || cstate, "lfi_flow_step_rows_from: the LSTM cell needs cstate");
-  LFI_REQUIRE((reinterpret_cast<uintptr_t>(rows_work) & 3) == 0, "lfi_flow_step_rows_from: rows_work is not 4-byte aligned");
-  const int B = f.B, C = f.C, H = f.H, Ks = f.Ks, G = f.G;
-  hipStream_t st = (hipStream_t)stream;
-  const bool fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
-  const bool chain = fast && lfi_env_on("LFI_SAMPLE_CHAIN");
-  // each direction's own rule (lfi_flow_sample_seq_nll, lfi_flow_score_seq_from)
-  const bool x3 = flow_x3_rev_cell(d, f);
-  const bool xw = x3 && chain && flow_sample_wfrag16_enabled();
-  const bool x3f = x3 && (d->gemm_precision & 0xff) == 9;
-  const size_t lds_fast = (size_t)carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total * sizeof(float);
-  const size_t lds_gen = (size_t)carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout).total * sizeof(float);
-  const FlowRowsChainKernel chain_kernel = flow_rows_chain_pick(f.lstm, x3, xw, x3f);
-  const FlowStepKernel rev_cell = flow_step_rev_pick(fast, f.lstm);
-  if (chain) {
-    if ((rc = set_flow_lds(chain_kernel, lds_fast, "lfi_flow_step_rows_from"))) return rc;
-  } else {
-    if ((rc = set_flow_lds(rev_cell, fast ? lds_fast : lds_gen, "lfi_flow_step_rows_from"))) return rc;
-    if ((rc = set_flow_lds(flow_step_kernel<false>, lds_gen, "lfi_flow_step_rows_from"))) return rc;
-  }
-  const RowsWork rw = rows_work_carve(rows_work, B, C, H, Ks);
-  SampleFront sf = {};
-  if ((rc = sample_front_setup(&sf, d, p, &f, wct, E, hist1, pre_static, faces, seq_len, p1, p1work, work, chain, nframes, stream,
-                               "lfi_flow_step_rows_from", chain ? rw.pipe : nullptr, (size_t)rw.pipe_words))) return rc;
-  const int t = start;
-  const int has_prev = first_frame > 0 ? 1 : 0;
-  if ((rc = sample_front_frame(sf, t, pre_static, 0, stream))) return rc;
-  float* frame = faces + (long)t * C;
-  const long ld_frame = (long)seq_len * C;
-  if (chain) {
-    RowsChain rcn = {};
-    rcn.role = observed;
-    rcn.rev.noise = noise; rcn.rev.xa = sf.xa; rcn.rev.xb = sf.xb; rcn.rev.frame = frame; rcn.rev.ld_frame = ld_frame;
-    rcn.rev.gic = sf.gic; rcn.rev.h = h; rcn.rev.cstate = cstate; rcn.rev.has_prev = has_prev; rcn.rev.frame_no = first_frame;
-    rcn.rev.pipe = rw.pipe; rcn.rev.qa = nll_work; rcn.rev.qb = nll_work + B; rcn.rev.nll = nll;
-    rcn.fwd.frame = frame; rcn.fwd.ld_frame = ld_frame; rcn.fwd.xa = rw.xa; rcn.fwd.xb = rw.xb; rcn.fwd.gic = sf.gic;
-    rcn.fwd.h = h; rcn.fwd.cstate = cstate; rcn.fwd.has_prev = has_prev; rcn.fwd.pipe = rw.pipe;
-    rcn.fwd.qa = rw.qa; rcn.fwd.qb = rw.qb; rcn.fwd.nll = nll;
-    if (!sf.fused) {   // (the fused conditioning kernel has cleared them)
-      hipError_t me = hipMemsetAsync(rw.pipe, 0, (size_t)rw.pipe_words * sizeof(unsigned), st);
-      LFI_REQUIRE(me == hipSuccess, "lfi_flow_step_rows_from: hipMemsetAsync: %s", hipGetErrorString(me));
-    }
-    hipLaunchKernelGGL(chain_kernel, dim3(2 * Ks * f.nbt), dim3(NT), lds_fast, st, f, rcn);
-    LFI_LAUNCH_CHECK("lfi_flow_step_rows_from");
-    return LFI_OK;
-  }
-  // ---- per-step launches. The forward direction first: it reads the observed frame and the state of the frame before
-  const size_t state_bytes = (size_t)Ks * B * H * sizeof(float);
-  if (has_prev) {
-    hipError_t me = hipMemcpyAsync(rw.hs, h, state_bytes, hipMemcpyDeviceToDevice, st);
-    if (me == hipSuccess && f.lstm) me = hipMemcpyAsync(rw.cs, cstate, state_bytes, hipMemcpyDeviceToDevice, st);
-    LFI_REQUIRE(me == hipSuccess, "lfi_flow_step_rows_from: hipMemcpyAsync: %s", hipGetErrorString(me));
-  }
-  {
-    const float* xin = frame;
-    long ldx = ld_frame;
-    for (int k = 0; k < Ks; ++k) {
-      CellIO io = {};
-      io.k = k; io.rows = B; io.x_in = xin; io.ldx = ldx;
-      io.h_prev = has_prev ? rw.hs + (long)k * B * H : nullptr;
-      io.gic = sf.gic + (long)k * B * G;
-      io.h_out = rw.hs + (long)k * B * H;
-      if (f.lstm) { io.c_prev = has_prev ? rw.cs + (long)k * B * H : nullptr; io.c_out = rw.cs + (long)k * B * H; }
-      io.x_out = (k & 1) ? rw.xa : rw.xb; io.ldxo = C;
-      io.l_out = rw.qa; io.l_accumulate = k > 0;
-      hipLaunchKernelGGL(flow_step_kernel<false>, dim3(f.nbt), dim3(NT), lds_gen, st, f, io);
-      xin = io.x_out; ldx = C;
-    }
-    hipLaunchKernelGGL(score_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, xin, rw.qa, f.ldconst, B, C, (float*)nullptr, rw.fnll);
-  }
-  // ---- the reverse direction on the state itself, its frame aside (the observing rows' frame stays in `faces`)
-  {
-    const float* xin = noise;
-    long ldx = C;
-    for (int k = Ks - 1; k >= 0; --k) {
-      CellIO io = {};
-      io.k = k; io.rows = B; io.x_in = xin; io.ldx = ldx;
-      io.h_prev = has_prev ? h + (long)k * B * H : nullptr;
-      io.gic = sf.gic + (long)k * B * G;
-      io.h_out = h + (long)k * B * H;
-      if (f.lstm) { io.c_prev = has_prev ? cstate + (long)k * B * H : nullptr; io.c_out = cstate + (long)k * B * H; }
-      if (k == 0) { io.x_out = rw.gframe; io.ldxo = C; }
-      else { io.x_out = (k & 1) ? sf.xa : sf.xb; io.ldxo = C; }
-      io.l_out = nll_work; io.l_accumulate = k + 1 < Ks;
-      hipLaunchKernelGGL(rev_cell, dim3(f.nbt), dim3(NT), fast ? lds_fast : lds_gen, st, f, io);
-      xin = io.x_out; ldx = io.ldxo;
-    }
-    hipLaunchKernelGGL(sample_nll_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, noise, nll_work, f.ldconst, B, C, nll);
-  }
-  hipLaunchKernelGGL(rows_merge_kernel, dim3(B), dim3(256), 0, st, observed, B, C, H, Ks, h, cstate, rw.hs, rw.cs, frame, ld_frame,
-                     rw.gframe, nll, rw.fnll);
-  LFI_LAUNCH_CHECK("lfi_flow_step_rows_from");
   return LFI_OK;
 }
 

@@ -441,7 +441,7 @@ extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond(co
   // (profiles/round5_sampler_ab.md): kept as the switch only.
   const bool inreg = !lfi_env_on("LFI_SAMPLE_XFRAG") && ld_faces % 2 == 0 && off % 2 == 0 && (reinterpret_cast<uintptr_t>(faces) & 7) == 0 &&
                      faces_floats > 0;
-  if (!inreg && !have_xfrag) {   // (have_xfrag: the previous frame's reverse chain left this frame's window fragments - lfi_flow.hip, RevChain.xf)
+  if (!inreg && !have_xfrag) {   // (have_xfrag: the previous frame's reverse chain left this frame's window fragments - lfi_flow_chain.hip, RevChain.xf)
     const long nx = (long)ntile * NM1 * 2 * 512;
     hipLaunchKernelGGL(sc_xfrag_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, (hipStream_t)stream, faces, ld_faces, off, K1, B, NM1, ntile,
                        fx);

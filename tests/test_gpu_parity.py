@@ -634,7 +634,7 @@ def test_pipeline_walk_matches_diagonal_walk(gpu_device, monkeypatch, case):
     outs = []
     monkeypatch.setenv("LFI_PIPE_X3", "0")   # same arithmetic in both walks: the recurrent products on the exact f32 MFMA
     # The bf16x3 form of the walk's recurrent products exists for GRU cells with hidden_channels and C // 2 padded to multiples of
-    # 32 only (lfi_flow.hip: H16 % 32 == 0 && Ch16 % 32 == 0 && !lstm): the fixture cases - "mid" H = 44, "tiny_lstm" an LSTM - have
+    # 32 only (lfi_flow_cells.h: H16 % 32 == 0 && Ch16 % 32 == 0 && !lstm): the fixture cases - "mid" H = 44, "tiny_lstm" an LSTM - have
     # no such kernel in ANY engine mode (VERDICT r3 weak #1c: their third leg printed 0.00e+00, vacuously; measured again in round
     # 4 with the leg moved to the bf16x3 engine mode: still bit-identical). They run the two bitwise legs; the bf16x3-recurrence leg
     # runs where the kernel exists, at final widths.

@@ -13,7 +13,7 @@ for SRC in ${SRCS//,/ }; do
   hipcc $FLAGS "$@" -c $ROOT/lets_face_it_amd/csrc/$SRC -o $ROOT/build/var/${NAME}_${SRC%.hip}.o
 done
 OBJS=""
-for f in lfi_core lfi_gemm lfi_pgemm lfi_encoder lfi_flow lfi_data lfi_sample lfi_wgrad; do
+for f in lfi_core lfi_gemm lfi_pgemm lfi_encoder lfi_flow lfi_flow_chain lfi_data lfi_sample lfi_wgrad; do
   case ",$SRCS," in
     *",$f.hip,"*) OBJS="$OBJS $ROOT/build/var/${NAME}_$f.o" ;;
     *) OBJS="$OBJS $ROOT/build/csrc/$f.o" ;;
