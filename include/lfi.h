@@ -125,9 +125,31 @@ typedef struct {
                                                     as its A operand with skip bit 0 (two products, A rounded to bf16), which never
                                                     fetches A's lo planes */
   int tile;                                      /* 0: the library picks 128 x 256 or 256 x 128 tiles by N; 1 / 2 pin them (tests) */
+  /* Sign words of the Cr matrix (format below; lfi_planes_sign_words(M, 16 cr_nkt) words, indexed like Cr: cr_col0, strideC).
+   * sign_out: the product also writes them, bit = (hi plane value > 0). sign_in: act == 2 takes its mask from them instead of G / Gr
+   * (the in-place masked product: Cr is then also where the mask's matrix lay). Only where lfi_gemm_planes_signs_ok says so;
+   * lfi_gemm_planes rejects them anywhere else. NULL: off. */
+  void* sign_out; const void* sign_in;
 } lfi_pgemm_desc;
 long lfi_gemm_planes_work_floats(const lfi_pgemm_desc* d);
 long lfi_gemm_planes_colpart_rows(const lfi_pgemm_desc* d);
+/* ---- sign words of a planes matrix: ONE BIT per element, (the hi plane's bf16 value, as a float, > 0) - all that the act == 2 mask of
+ * a later product uses of it. Defined in element coordinates of the rows x cols matrix (rows and cols padded to 64), whoever writes
+ * them; element (row, col):
+ *   64 x 64 patch (row >> 6, col >> 6), patches row-major, 64 words of 64 bits per patch;
+ *   word = lane (row & 15) + 16 * ((col >> 2) & 3) of the patch;
+ *   bit  = 16 * ((row >> 4) & 3) + 4 * ((col >> 4) & 3) + (col & 3) of that word.
+ * (What one lane of a wave holds of its 64 x 64 patch in the kernels' direct plane epilogue: a wave moves one contiguous 512-byte run
+ * per patch.) Bits of elements outside the matrix inside an existing patch are 0. Buffer: lfi_planes_sign_words(rows, cols) 8-byte
+ * words, 8-byte aligned.
+ * lfi_gemm_planes_signs_ok(d): 1 when the product d describes (sign_out and / or sign_in set to the buffer it would get) takes the sign
+ * path - the direct plane epilogue is chosen on 128 x 256 tiles, cr_nkt is a multiple of 4, cr_col0 and (batch > 1) strideC are multiples of 64,
+ * splitk <= 1 - and 0 otherwise, or with LFI_PGEMM_SIGNS=0 (read per call). */
+long lfi_planes_sign_words(long rows, long cols);
+int lfi_gemm_planes_signs_ok(const lfi_pgemm_desc* d);
+/* Workgroups of the persistent launch the product d describes gets (the in-place masked product with LFI_PGEMM_PERSIST=1:
+ * min(tiles x batch, 2 x CUs), capped by the test hook LFI_PGEMM_PERSIST_WGS), 0 when it is launched one workgroup per tile. Read per call. */
+long lfi_gemm_planes_persist_grid(const lfi_pgemm_desc* d);
 int lfi_gemm_planes(const lfi_pgemm_desc* d, void* stream);
 
 /* out[c] (+)= scale * sum_r X[r*ldx + c]  for r < rows, c < cols; batched. Deterministic two-stage reduction.

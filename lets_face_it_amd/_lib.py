@@ -47,6 +47,7 @@ class PGemmDesc(C.Structure):
         ("Gr", C.c_void_p), ("gr_nkt", C.c_int), ("gr_col0", C.c_long),
         ("colsum_part", C.c_void_p), ("ld_part", C.c_long),
         ("out_hi_only", C.c_int), ("tile", C.c_int),
+        ("sign_out", C.c_void_p), ("sign_in", C.c_void_p),
     ]
 
 
@@ -115,6 +116,9 @@ def lib():
         "lfi_encode_windows_fwd_variant": (i, [P(EncDesc), i, i]),
         "lfi_gemm_planes_work_floats": (l, [P(PGemmDesc)]),
         "lfi_gemm_planes_colpart_rows": (l, [P(PGemmDesc)]),
+        "lfi_planes_sign_words": (l, [l, l]),
+        "lfi_gemm_planes_signs_ok": (i, [P(PGemmDesc)]),
+        "lfi_gemm_planes_persist_grid": (l, [P(PGemmDesc)]),
         "lfi_colsum_work_floats": (l, [i, i, i]),
         "lfi_colsum_f32": (i, [vp, l, l, i, i, i, vp, l, f, i, vp, vp]),
         "lfi_cols_fold": (i, [vp, l, l, vp, vp, i, vp, l, vp]),
@@ -196,7 +200,7 @@ def lib():
 
 EXPORTS = [
     "lfi_last_error", "lfi_version", "lfi_gemm_work_floats", "lfi_gemm_f32", "lfi_gemm_colpart_rows", "lfi_planes_elems", "lfi_planes_from_f32",
-    "lfi_gemm_planes", "lfi_gemm_planes_work_floats", "lfi_gemm_planes_colpart_rows",
+    "lfi_gemm_planes", "lfi_gemm_planes_work_floats", "lfi_gemm_planes_colpart_rows", "lfi_planes_sign_words", "lfi_gemm_planes_signs_ok", "lfi_gemm_planes_persist_grid",
     "lfi_flow_bwd_emits_planes", "lfi_flow_seq_bwd_planes", "lfi_encode_windows_grad_stash_bf16", "lfi_encode_windows_stash_f16_ok", "lfi_encode_windows_fwd_variant", "lfi_colsum_work_floats",
     "lfi_colsum_f32", "lfi_cols_fold", "lfi_encode_windows_work_floats", "lfi_encode_windows_fwd", "lfi_encode_windows_bwd",
     "lfi_encode_windows_bias_rows", "lfi_encode_windows_bias_grads",

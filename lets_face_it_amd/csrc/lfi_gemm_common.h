@@ -52,6 +52,13 @@ struct GemmArgs {
   __bf16* Cr; int nktCr; long colCr;        // planes of the result: rows = C rows, columns = colCr + batch * strideC + C column
   const __bf16* Gr; int nktGr; long colGr;  // act == 2: row planes of G (hi plane read) instead of g.G
   int hiOnly;                               // plane outputs: the hi planes only (their consumer takes them as a rounded A operand)
+  // sign words (include/lfi.h, "sign words of a planes matrix"): one bit per element of the Cr matrix, (hi plane value > 0). So: the
+  // direct epilogue (MODE 3) also writes them; Si: the MODE 4 epilogue takes its act-2 mask from them instead of Gr's hi plane.
+  // Both are indexed like Cr (colCr, strideC); npcS = 64-column patches per patch row = nktCr / 4.
+  unsigned long long* So; const unsigned long long* Si; int npcS;
+  // gemm_planes16t_kernel<false, true, 2, 4, 5> only: > 0: persistent launch - the grid is 1-D, smaller than the number of tiles,
+  // and workgroup b walks work items b, b + gridDim.x, .. of pbatch batch entries (gemm_tile_of_linear); 0: one workgroup per tile
+  int pbatch;
 };
 
 __device__ __forceinline__ float apply_act(float v, int act, float slope, const float* G, long gidx) {
@@ -337,9 +344,31 @@ __device__ __forceinline__ void gemm_epilogue_wide(const GemmArgs& g, const ACC&
 // (the through-LDS epilogue of a 128 x 256 tile measured about half as long as the tile's whole main loop at K = 896)
 typedef unsigned gu32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned gu32x2 __attribute__((ext_vector_type(2)));
-template <int MODE>
-__device__ __forceinline__ void gemm_epilogue_direct16(const GemmArgs& g, const f32x4 (&acc)[4][4], int m0, int n0, int wm, int wn, int lane,
-                                                       int batch, int split) {
+// This lane's sign word of the wave's 64 x 64 patch at (r0, c0) of the Cr matrix (bit 16 i + 4 j + r = accumulator (i, j) register r):
+// its byte offset in the sign buffer / whether the patch exists
+// (GA: GemmArgs, or GemmArgsK - the same descriptor read where it lies in the kernel-argument segment, see gemm_planes16t_kernel)
+typedef const __attribute__((address_space(4))) GemmArgs GemmArgsK;
+template <typename GA>
+__device__ __forceinline__ long gemm_sign_patch_offset(const GA& g, int r0, int c0, int batch) {
+  const long gcol0 = g.colCr + (long)batch * g.strideC + c0;   // multiple of 64 (the host checks colCr, strideC)
+  return ((long)(r0 >> 6) * g.npcS + (gcol0 >> 6)) * 512;
+}
+template <typename GA>
+__device__ __forceinline__ gu32x2 gemm_sign_word_load(const GA& g, int m0, int n0, int wm, int wn, int lane, int batch) {
+  const int r0 = m0 + wm * 64, c0 = n0 + wn * 64;
+  gu32x2 sw = {0u, 0u};
+  if (g.Si && r0 < g.M && c0 < g.N) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char*>(reinterpret_cast<const char*>(g.Si)) + gemm_sign_patch_offset(g, r0, c0, batch), 0, 0x7fffffff, 0x00020000);
+    sw = __builtin_amdgcn_raw_buffer_load_b64(rs, (unsigned)lane * 8u, 0, 0);
+  }
+  return sw;
+}
+// sw: MODE 4 with g.Si set: the patch's sign word of this lane (gemm_sign_word_load), fetched by the caller ahead of its main loop
+// SIGNW: MODE 3 may write sign words (compiled in for the 128 x 256 tile only: the 256 x 128 kernel has no registers to spare for it)
+template <int MODE, typename GA = GemmArgs, bool SIGNW = true>
+__device__ __forceinline__ void gemm_epilogue_direct16(const GA& g, const f32x4 (&acc)[4][4], int m0, int n0, int wm, int wn, int lane,
+                                                       int batch, int split, gu32x2 sw = (gu32x2){0u, 0u}) {
   const int l15 = lane & 15, g4 = lane >> 4;
   const int r0 = m0 + wm * 64, c0 = n0 + wn * 64;             // this wave's patch (wave-uniform)
   const float* bias = g.bias ? g.bias + batch * g.strideBias : nullptr;
@@ -357,6 +386,11 @@ __device__ __forceinline__ void gemm_epilogue_direct16(const GemmArgs& g, const 
   f32x4 csum[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) csum[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  // sign words. MODE 3 with g.So: bit = (the hi bf16 value about to be stored, as a float, > 0) - the predicate MODE 4 applies to the
+  // hi plane below, on the same half-words; one 8-byte store per lane and patch. MODE 4 with g.Si: the mask comes from sw, and the
+  // sixteen loads on Gr's planes are not issued.
+  const bool wsign = SIGNW && MODE == 3 && g.So != nullptr, rsign = MODE == 4 && g.Si != nullptr;
+  unsigned sb[2] = {0u, 0u};
   {
     const long gcol0 = g.colCr + (long)batch * g.strideC + c0;      // multiple of 16 (colCr, strideC, c0 are)
 #pragma unroll
@@ -378,12 +412,18 @@ __device__ __forceinline__ void gemm_epilogue_direct16(const GemmArgs& g, const 
         const int col = c0 + 16 * j + 4 * g4;
         f32x4 v = acc[i][j] + bv[j];
         if constexpr (MODE == 4) {
-          gu32x2 m2 = {0u, 0u};
-          if (blk && c0 + 16 * j < g.N) m2 = __builtin_amdgcn_raw_buffer_load_b64(rg, voff, 2048 * j, 0);
-          const float o0 = __builtin_bit_cast(float, m2[0] << 16), o1 = __builtin_bit_cast(float, m2[0] & 0xffff0000u);
-          const float o2 = __builtin_bit_cast(float, m2[1] << 16), o3 = __builtin_bit_cast(float, m2[1] & 0xffff0000u);
-          v[0] = o0 > 0.0f ? v[0] : v[0] * g.slope; v[1] = o1 > 0.0f ? v[1] : v[1] * g.slope;
-          v[2] = o2 > 0.0f ? v[2] : v[2] * g.slope; v[3] = o3 > 0.0f ? v[3] : v[3] * g.slope;
+          bool p0, p1, p2, p3;
+          if (rsign) {
+            const unsigned m4 = sw[i >> 1] >> (16 * (i & 1) + 4 * j);
+            p0 = (m4 & 1u) != 0; p1 = (m4 & 2u) != 0; p2 = (m4 & 4u) != 0; p3 = (m4 & 8u) != 0;
+          } else {
+            gu32x2 m2 = {0u, 0u};
+            if (blk && c0 + 16 * j < g.N) m2 = __builtin_amdgcn_raw_buffer_load_b64(rg, voff, 2048 * j, 0);
+            p0 = __builtin_bit_cast(float, m2[0] << 16) > 0.0f; p1 = __builtin_bit_cast(float, m2[0] & 0xffff0000u) > 0.0f;
+            p2 = __builtin_bit_cast(float, m2[1] << 16) > 0.0f; p3 = __builtin_bit_cast(float, m2[1] & 0xffff0000u) > 0.0f;
+          }
+          v[0] = p0 ? v[0] : v[0] * g.slope; v[1] = p1 ? v[1] : v[1] * g.slope;
+          v[2] = p2 ? v[2] : v[2] * g.slope; v[3] = p3 ? v[3] : v[3] * g.slope;
         } else if (g.act == 1) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.0f ? v[r] : v[r] * g.slope;
@@ -393,12 +433,22 @@ __device__ __forceinline__ void gemm_epilogue_direct16(const GemmArgs& g, const 
         uint2 h, l;
         split2(v[0], v[1], &h.x, &l.x);
         split2(v[2], v[3], &h.y, &l.y);
+        if (wsign) {
+          const unsigned m4 = (__builtin_bit_cast(float, h.x << 16) > 0.0f ? 1u : 0u) | (__builtin_bit_cast(float, h.x & 0xffff0000u) > 0.0f ? 2u : 0u) |
+                              (__builtin_bit_cast(float, h.y << 16) > 0.0f ? 4u : 0u) | (__builtin_bit_cast(float, h.y & 0xffff0000u) > 0.0f ? 8u : 0u);
+          sb[i >> 1] |= m4 << (16 * (i & 1) + 4 * j);
+        }
         if (blk && c0 + 16 * j < g.N) {
           __builtin_amdgcn_raw_buffer_store_b64((gu32x2){h.x, h.y}, rs, voff, 2048 * j, 2);
           if (!g.hiOnly) __builtin_amdgcn_raw_buffer_store_b64((gu32x2){l.x, l.y}, rs, voff, 2048 * j + 1024, 2);
         }
       }
     }
+  }
+  if (wsign && r0 < g.M && c0 < g.N) {
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(g.So) + gemm_sign_patch_offset(g, r0, c0, batch), 0,
+                                                                       0x7fffffff, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b64((gu32x2){sb[0], sb[1]}, rw, (unsigned)lane * 8u, 0, 2);
   }
   if constexpr (MODE == 4) {
     if (g.colpart) {
@@ -424,10 +474,14 @@ __device__ __forceinline__ void gemm_epilogue_direct16(const GemmArgs& g, const 
 // of fetching them from HBM once per XCD (the long-K weight-gradient products have 12 tiles per split: spread over the
 // XCDs their B panel was fetched up to 6 times). Inside a batch entry tiles are walked in groups of GM tile-rows column by
 // column so the ~100 tiles an XCD has in flight form a compact GM x 12 patch.
-__device__ __forceinline__ void gemm_tile_of_block(const GemmArgs& g, int* tm, int* tn, int* batch, int* split) {
+// (lin, total, nbatch): the work item of linear index lin out of total = tiles x nbatch x splits - the launched grid's own block
+// index (gemm_tile_of_block) or a virtual one (the persistent dpre product: workgroup b walks b, b + gridDim.x, ..; with a stride that
+// is a multiple of 8 - the uncapped grid of 2 x CUs is - lin & 7 is still the XCD the workgroup runs on, and every XCD keeps the
+// contiguous run it has with one workgroup per item. A grid capped by the test hook LFI_PGEMM_PERSIST_WGS to something that is no
+// multiple of 8 loses that locality and nothing else: every item is still walked exactly once).
+template <typename GA>
+__device__ __forceinline__ void gemm_tile_of_linear(const GA& g, long lin, long total, int nbatch, int* tm, int* tn, int* batch, int* split) {
   const int ntile = g.tiles_m * g.tiles_n;
-  const long total = (long)gridDim.x * gridDim.y * gridDim.z;
-  long lin = blockIdx.x + (long)gridDim.x * (blockIdx.y + (long)gridDim.y * blockIdx.z);
   {
     const long q = total >> 3, idx = lin >> 3;
     const int r = (int)(total & 7), xcd = (int)(lin & 7);
@@ -435,14 +489,19 @@ __device__ __forceinline__ void gemm_tile_of_block(const GemmArgs& g, int* tm, i
   }
   int bid = (int)(lin % ntile);
   const long rest = lin / ntile;
-  *batch = (int)(rest % gridDim.y);
-  *split = (int)(rest / gridDim.y);
+  *batch = (int)(rest % nbatch);
+  *split = (int)(rest / nbatch);
   const int GM = g.gm > 0 ? g.gm : 8;
   const int per_group = GM * g.tiles_n;
   const int grp = bid / per_group, in_grp = bid - grp * per_group;
   const int rows_here = min(GM, g.tiles_m - grp * GM);
   *tm = grp * GM + in_grp % rows_here;
   *tn = in_grp / rows_here;
+}
+__device__ __forceinline__ void gemm_tile_of_block(const GemmArgs& g, int* tm, int* tn, int* batch, int* split) {
+  const long total = (long)gridDim.x * gridDim.y * gridDim.z;
+  const long lin = blockIdx.x + (long)gridDim.x * (blockIdx.y + (long)gridDim.y * blockIdx.z);
+  gemm_tile_of_linear(g, lin, total, (int)gridDim.y, tm, tn, batch, split);
 }
 
 #ifndef LFI_EPI_ROWS

@@ -388,7 +388,7 @@ __global__ __launch_bounds__(512, 4) void gemm_planes16_kernel(GemmArgs g) {
     // (laundered: otherwise the epilogue's address arithmetic is hoisted above the main loop and lives through it in registers)
     int lanez = lane, m0z = m0, n0z = n0;
     asm volatile("" : "+v"(lanez), "+s"(m0z), "+s"(n0z));
-    gemm_epilogue_direct16<TRP>(g, acc, m0z, n0z, wm, wn, lanez, batch, split);
+    gemm_epilogue_direct16<TRP, GemmArgs, WMT == 2>(g, acc, m0z, n0z, wm, wn, lanez, batch, split);
   } else {
     __syncthreads();
     gemm_epilogue_wide<64 * WNT, 512, 2, COLP, true, true>(g, acc, reinterpret_cast<float*>(xsmem), WNT == 4 ? 64 : 128, m0, n0, wm, wn,
@@ -416,9 +416,20 @@ __global__ __launch_bounds__(512, 4) void gemm_planes16t_kernel(GemmArgs g) {
   static_assert(WMT * WNT == 8 && NA + 4 * WNT == 24, "eight waves, 24 blocks per slot");
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // TRP == 4: the in-place dpre product (gemm_epilogue_direct16<4>; its epilogue uses no LDS). TRP == 5: the same product launched
+  // PERSISTENT (g.pbatch > 0, a 1-D grid): fewer workgroups than work items, workgroup b walks items b, b + gridDim.x, .., and the
+  // next item's ring fill and sign word are issued ahead of this item's epilogue (below). Everything else: one item per workgroup,
+  // the loop below runs once and PERS-only code is not compiled in.
+  constexpr bool PERS = TRP == 5;
+  constexpr int EMODE = TRP == 5 ? 4 : TRP;   // the direct epilogue's MODE
+  const long total = PERS ? (long)g.tiles_m * g.tiles_n * g.pbatch : (long)gridDim.x * gridDim.y * gridDim.z;
+  const long lstep = PERS ? (long)gridDim.x : total;
+  const int nbat = PERS ? g.pbatch : (int)gridDim.y;
+  long lin = blockIdx.x + (long)gridDim.x * (blockIdx.y + (long)gridDim.y * blockIdx.z);
   int tm, tn, batch, split;
-  gemm_tile_of_block(g, &tm, &tn, &batch, &split);
-  const int m0 = tm * 64 * WMT, n0 = tn * 64 * WNT;
+  if constexpr (PERS) gemm_tile_of_linear(g, lin, total, nbat, &tm, &tn, &batch, &split);
+  else gemm_tile_of_block(g, &tm, &tn, &batch, &split);
+  int m0 = tm * 64 * WMT, n0 = tn * 64 * WNT;
   const int ktc = g.kchunk >> 4;
   const int kt0 = split * ktc;
   const int npair = max(min(g.nkt - kt0, ktc), 0) >> 1;
@@ -429,9 +440,26 @@ __global__ __launch_bounds__(512, 4) void gemm_planes16t_kernel(GemmArgs g) {
   const char* baseA = reinterpret_cast<const char*>(g.Ap + batch * g.pstrideA) +
                       (AT ? (long)(tm * 2 * WMT) * 4096 + (long)(kt0 >> 1) * rowA : (long)(tm * 2 * WMT) * rowA + (long)kt0 * 2048);
   const char* baseB = reinterpret_cast<const char*>(g.Bp + batch * g.pstrideB) + (long)(tn * 2 * WNT) * 4096 + (long)(kt0 >> 1) * rowB;
+  // (persistent walk: the next work item's tile and panel bases; splits do not occur there, kt0 stays)
+  // Everything the walk does between two main loops - the next item's tile, its sign word, the epilogue - reads the descriptor
+  // through gk: the kernel-argument segment itself (this kernel's only argument lies at its start), behind a pointer the compiler
+  // cannot see through. Those fields are then scalar loads at the place of use, once per item, as they are with one item per
+  // workgroup; read from `g` they would all be hoisted in front of the item loop and live through the main loop in scalar
+  // registers, which this kernel does not have (measured at build time: 85 of them spilled into vector registers and from there
+  // to scratch).
+  // (PERS only: with one item per workgroup nothing reads gk, and the descriptor is the by-value argument as everywhere else)
+  [[maybe_unused]] GemmArgsK* gk = PERS ? (GemmArgsK*)__builtin_amdgcn_kernarg_segment_ptr() : nullptr;
+  [[maybe_unused]] auto next_item = [&]() {
+    gemm_tile_of_linear(*gk, lin, total, nbat, &tm, &tn, &batch, &split);
+    m0 = tm * 64 * WMT; n0 = tn * 64 * WNT;
+    baseA = reinterpret_cast<const char*>(gk->Ap + batch * gk->pstrideA) +
+            (AT ? (long)(tm * 2 * WMT) * 4096 + (long)(kt0 >> 1) * rowA : (long)(tm * 2 * WMT) * rowA + (long)kt0 * 2048);
+    baseB = reinterpret_cast<const char*>(gk->Bp + batch * gk->pstrideB) + (long)(tn * 2 * WNT) * 4096 + (long)(kt0 >> 1) * rowB;
+  };
   // per-lane source offset inside a block: as it lies (row use), or with the row swap of the header (transposed use)
+  // (PERS: worked out again per work item by lane_offsets below)
   const int prow = lane >> 1, srow = prow ^ ((prow & 16) ? 4 : 0);
-  const int laneR = lane * 16, laneT = srow * 32 + (lane & 1) * 16;
+  int laneR = lane * 16, laneT = srow * 32 + (lane & 1) * 16;
   // this wave's pieces: piece i = block 8 i + wave, so that which operand a piece belongs to is a compile-time fact. Sub-slot 2 p:
   // [A (NA)][B hi (4 WNT)]; sub-slot 2 p + 1: B lo, NY pieces, in B's place
   int sofX[3], doffX[3], sofY[2], doffY[2];   // (NY <= 2 used; a template-dependent bound here breaks the host pass of this hipcc)
@@ -472,12 +500,26 @@ __global__ __launch_bounds__(512, 4) void gemm_planes16t_kernel(GemmArgs g) {
   };
 #undef PG_RSRC
   const int wm = wave / WNT, wn = wave % WNT;
-  const int g4 = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
   // row use: one ds_read_b128 (16-row tile 1 of a block pair: + 512). Transposed use: two ds_read_b64_tr_b16 on ONE block (16 mn
   // columns x the pair's 32 k rows), the second at toff ^ 128 (k rows + 4)
-  const int fo = (g4 & 1) * 1024 + lfi_u_plane_offset(lane & 15, g4 >> 1);
+  const int g4 = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
+  int fo = (g4 & 1) * 1024 + lfi_u_plane_offset(lane & 15, g4 >> 1);
   const int kr = 16 * (g4 & 1) + 8 * (g4 >> 1) + tq;
-  const int toff = (kr ^ ((kr & 16) ? 4 : 0)) * 32 + (((tp >> 1) ^ ((kr >> 3) & 1)) << 4) + (tp & 1) * 8;
+  int toff = (kr ^ ((kr & 16) ? 4 : 0)) * 32 + (((tp >> 1) ^ ((kr >> 3) & 1)) << 4) + (tp & 1) * 8;
+  // The persistent walk (PERS) works these per-lane offsets of the DMA and of the fragment reads out again for every work item (a
+  // few VALU instructions) from a laundered lane number: they then do not live through the epilogue, which has the registers to
+  // itself as it has with one item per workgroup. Everything else computes them once, above, where it always did (moving them costs
+  // the 256 x 128 instantiations registers: measured with tools/kernel_resources.py).
+  int lanev = lane;
+  [[maybe_unused]] auto lane_offsets = [&]() {
+    asm volatile("" : "+v"(lanev));
+    const int prow = lanev >> 1, srow = prow ^ ((prow & 16) ? 4 : 0);
+    laneR = lanev * 16; laneT = srow * 32 + (lanev & 1) * 16;
+    const int g4 = lanev >> 4, tq = (lanev >> 2) & 3, tp = lanev & 3;
+    fo = (g4 & 1) * 1024 + lfi_u_plane_offset(lanev & 15, g4 >> 1);
+    const int kr = 16 * (g4 & 1) + 8 * (g4 >> 1) + tq;
+    toff = (kr ^ ((kr & 16) ? 4 : 0)) * 32 + (((tp >> 1) ^ ((kr >> 3) & 1)) << 4) + (tp & 1) * 8;
+  };
   const char* ldsA = lds + (wm * 4) * 1024;
   const char* ldsB = lds + NA * 1024 + (wn * 4) * 1024;
   auto fragA = [&](int slot, int i) -> bf16x8 {
@@ -487,6 +529,10 @@ __global__ __launch_bounds__(512, 4) void gemm_planes16t_kernel(GemmArgs g) {
   auto fragB = [&](int slot, int i) -> bf16x8 { return pg_frag<true>(ldsB + slot * QSLOT + i * 1024, 0, toff); };
 
   f32x4 acc[4][4];
+  gu32x2 sw = {0u, 0u};   // TRP >= 4 with sign words: this lane's word of the wave's patch (the act-2 mask), fetched ahead of the main loop
+  bool filled = false;    // the ring fill of this item was issued ahead of the previous item's epilogue
+  if constexpr (PERS) lane_offsets();
+  for (;;) {
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -494,9 +540,20 @@ __global__ __launch_bounds__(512, 4) void gemm_planes16t_kernel(GemmArgs g) {
 
   if (npair > 0) {
     bf16x8 ah[4], bh[4];
-    dmaX(0, 0); dmaY(0, 1); dmaX(1, 2);
-    if (NY == 2) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    if (!filled) {
+      // (the sign word first: it is the OLDEST load in flight, so every counted wait below that covers a DMA piece covers it too)
+      if constexpr (TRP >= 4) sw = gemm_sign_word_load(g, m0, n0, wm, wn, lanev, batch);
+      dmaX(0, 0); dmaY(0, 1); dmaX(1, 2);
+      if (NY == 2) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    } else {
+      // Prefetched fill: in issue order this wave has in flight [sign word][dmaX(0, 0): 3][dmaY(0, 1): NY][dmaX(1, 2): 3] and then the
+      // previous item's epilogue stores (up to 32 plane stores and 4 column-sum stores, how many depends on the tile's edges). Loads
+      // and stores share vmcnt in issue order, so a count that lets dmaX(0, 0) through would have to skip NY + 3 + that variable
+      // number of stores: the only count that is right for every tile is 0. Nothing older is then left, and the counts inside the
+      // loop (which only ever skip what the loop itself issued) hold as they are.
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int i = 0; i < 4; ++i) { ah[i] = fragA(0, i); bh[i] = fragB(0, i); }
@@ -551,13 +608,38 @@ __global__ __launch_bounds__(512, 4) void gemm_planes16t_kernel(GemmArgs g) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   if constexpr (TRP != 0) {
-    int lanez = lane, m0z = m0, n0z = n0;
+    int lanez = lanev, m0z = m0, n0z = n0;
+    const int batchz = batch;
+    const gu32x2 swz = sw;
+    bool more = false;
+    if constexpr (PERS) {
+      asm volatile("" : "+s"(gk));
+      // The last pair's closing barrier is behind every wave: all fragment reads of the ring are done, and this wave's own pieces
+      // (each block of a slot is written by one wave only) have landed (vmcnt(0) above). The epilogue needs no LDS: the next item's
+      // fill - the three groups the top of the loop issues otherwise - and its sign word go out now and travel under the epilogue.
+      lin += lstep;
+      more = lin < total;
+      filled = false;
+      if (more) {
+        next_item();
+        if (npair > 0) {
+          sw = gemm_sign_word_load(*gk, m0, n0, wm, wn, lanev, batch);
+          dmaX(0, 0); dmaY(0, 1); dmaX(1, 2);
+          filled = true;
+        }
+      }
+    }
     asm volatile("" : "+v"(lanez), "+s"(m0z), "+s"(n0z));
-    gemm_epilogue_direct16<TRP>(g, acc, m0z, n0z, wm, wn, lanez, batch, split);
+    if constexpr (PERS) gemm_epilogue_direct16<EMODE>(*gk, acc, m0z, n0z, wm, wn, lanez, batchz, split, swz);
+    else gemm_epilogue_direct16<EMODE>(g, acc, m0z, n0z, wm, wn, lanez, batchz, split, swz);
+    if (!more) break;
+    if constexpr (PERS) lane_offsets();
   } else {
     __syncthreads();
     gemm_epilogue_wide<64 * WNT, 512, 2, COLP, true, true>(g, acc, reinterpret_cast<float*>(xsmem), WNT == 4 ? 64 : 128, m0, n0, wm, wn,
                                                            lane & 31, lane >> 5, batch, split, 64 * WMT);
+    break;
+  }
   }
 }
 
@@ -616,8 +698,49 @@ int planes16_direct_mode(const GemmArgs& a) {
 // MODE 4 of the direct epilogue: plane outputs only, act 2 with the mask in planes, column sums, 128 x 256 tiles
 bool planes16_direct_mask_ok(const GemmArgs& a) {
   if (!lfi_env_on("LFI_PGEMM_DIRECT")) return false;
-  return a.vecC && a.act == 2 && a.Gr && !a.G && a.accumulate == 0 && a.colpart && a.splitk == 1 && a.Cr && !a.storeC && !a.bias &&
+  return a.vecC && a.act == 2 && (a.Gr || a.Si) && !a.G && a.accumulate == 0 && a.colpart && a.splitk == 1 && a.Cr && !a.storeC && !a.bias &&
          (a.N & 3) == 0 && (a.strideC & 31) == 0 && (a.colCr & 15) == 0 && (a.colGr & 15) == 0 && (a.ldpart & 3) == 0;
+}
+
+// sign words address whole 64 x 64 patches of the Cr matrix: its columns, the first column and the batch pitch in 64s
+bool planes_sign_geometry_ok(const GemmArgs& a, int batch) {
+  return a.Cr && (a.nktCr & 3) == 0 && (a.colCr & 63) == 0 && (batch == 1 || (a.strideC & 63) == 0) && a.splitk == 1;
+}
+
+// which kernel a product takes (launch_planes below asks the same questions in the same order)
+bool planes_takes_direct3(const GemmArgs& a, int at, int bt, bool tall) {   // gemm_epilogue_direct16<3> on 128 x 256 tiles: the sign-word writer
+  if (tall || (bt && planes16t_ok(a))) return false;
+  return !at && !bt && planes16_ok(a) && !a.colpart && planes16_direct_mode(a) == 3;
+}
+bool planes_takes_direct4(const GemmArgs& a, int at, int bt, bool tall) {   // gemm_epilogue_direct16<4>: the sign-word reader
+  return bt && planes16t_ok(a) && a.colpart && !tall && !at && planes16_direct_mask_ok(a);
+}
+
+// workgroups of the persistent dpre launch: min(work items, 2 x CUs) (two workgroups of this kernel are resident per CU), capped by the
+// TEST HOOK LFI_PGEMM_PERSIST_WGS=n (read per launch: small shapes then put many tiles on one workgroup; a cap that is no multiple
+// of 8 gives up the XCD locality of gemm_tile_of_linear, results are the same). 0: not persistent.
+// LFI_PGEMM_PERSIST=1 switches the persistent launch ON; it is OFF by default: measured, the step is slower with it
+// (profiles/dpre_sign_words.md), so one workgroup per tile stays the default.
+// The CU count is asked of the CURRENT device once per device and kept. A device whose properties cannot be read gets 0 - one
+// workgroup per tile, which is a complete launch of the same product, not a fall-back to other arithmetic.
+long planes_persist_wgs(long items) {
+  if (!lfi_env_set("LFI_PGEMM_PERSIST")) return 0;
+  constexpr int MAXDEV = 64;
+  static int cus_of[MAXDEV] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return 0;
+  if (cus_of[dev] == 0) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount <= 0) return 0;
+    cus_of[dev] = prop.multiProcessorCount;
+  }
+  const int cus = cus_of[dev];
+  long wgs = min(items, 2L * cus);
+  if (const char* e = getenv("LFI_PGEMM_PERSIST_WGS")) {
+    const long cap = atol(e);
+    if (cap > 0) wgs = min(wgs, cap);
+  }
+  return wgs;
 }
 
 template <bool COLP, int WMT, int WNT>
@@ -648,13 +771,20 @@ int launch_planes(const GemmArgs& a, int at, int bt, dim3 grid, size_t lds, hipS
     if (COLP && WMT == 2 && !at && planes16_direct_mask_ok(a)) {   // the in-place dpre product: planes + mask from planes + column sums
       static bool attr4 = false;
       if (!attr4) {
-        if (hipFuncSetAttribute((const void*)gemm_planes16t_kernel<false, true, 2, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        if (hipFuncSetAttribute((const void*)gemm_planes16t_kernel<false, true, 2, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+            hipFuncSetAttribute((const void*)gemm_planes16t_kernel<false, true, 2, 4, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
           lfi_set_error("lfi_gemm_planes: cannot reserve %zu bytes of LDS", lds);
           return LFI_ERR_LAUNCH;
         }
         attr4 = true;
       }
-      hipLaunchKernelGGL((gemm_planes16t_kernel<false, true, 2, 4, 4>), grid, dim3(512), lds, st, a);
+      // persistent (TRP 5): fewer workgroups than work items, each walks several (the kernel's item loop); otherwise one per item
+      const long items = (long)grid.x * grid.y, wgs = planes_persist_wgs(items);
+      if (wgs > 0 && grid.z == 1) {
+        GemmArgs ap = a;
+        ap.pbatch = (int)grid.y;
+        hipLaunchKernelGGL((gemm_planes16t_kernel<false, true, 2, 4, 5>), dim3((unsigned)wgs), dim3(512), lds, st, ap);
+      } else hipLaunchKernelGGL((gemm_planes16t_kernel<false, true, 2, 4, 4>), grid, dim3(512), lds, st, a);
     } else if (at) hipLaunchKernelGGL((gemm_planes16t_kernel<true, COLP, WMT, WNT>), grid, dim3(512), lds, st, a);
     else hipLaunchKernelGGL((gemm_planes16t_kernel<false, COLP, WMT, WNT>), grid, dim3(512), lds, st, a);
   } else if (!at && !bt && planes16_ok(a) && !COLP && planes16_direct_mode(a)) {
@@ -707,6 +837,11 @@ extern "C" long lfi_planes_elems(long rows, int cols) {
   return ((rows + 255) / 256 * 256) * (long)((cols + 15) / 16 * 16) * 2;
 }
 
+extern "C" long lfi_planes_sign_words(long rows, long cols) {
+  if (rows <= 0 || cols <= 0) return 0;
+  return ((rows + 63) / 64) * ((cols + 63) / 64) * 64;
+}
+
 extern "C" int lfi_planes_from_f32(const float* X, long ldx, long rows, int cols, void* planes, void* stream) {
   LFI_REQUIRE(rows >= 0 && cols >= 0, "lfi_planes_from_f32: bad dims %ld x %d", rows, cols);
   if (rows == 0 || cols == 0) return LFI_OK;
@@ -736,36 +871,21 @@ extern "C" long lfi_gemm_planes_colpart_rows(const lfi_pgemm_desc* d) {
   return planes_tall_tile(d) ? (long)lfi_cdiv(d->M, 256) * 2 : (long)lfi_cdiv(d->M, 128) * 2;   // two passes per tile either way
 }
 
-extern "C" int lfi_gemm_planes(const lfi_pgemm_desc* d, void* stream) {
-  LFI_REQUIRE(d, "lfi_gemm_planes: null descriptor");
-  LFI_REQUIRE(d->M >= 0 && d->N >= 0 && d->K >= 0 && d->batch >= 1 && d->batch <= 65535, "lfi_gemm_planes: bad dims M=%d N=%d K=%d batch=%d",
-              d->M, d->N, d->K, d->batch);
-  if (d->M == 0 || d->N == 0) return LFI_OK;
-  const bool store = d->store_f32 != 0;
-  LFI_REQUIRE(d->Ap && d->Bp && (d->C || !store), "lfi_gemm_planes: null operand");
-  LFI_REQUIRE(store || d->Cr, "lfi_gemm_planes: store_f32 = 0 and no plane output: the result would go nowhere");
-  LFI_REQUIRE(d->K > 0, "lfi_gemm_planes: K = 0");
-  LFI_REQUIRE(d->act >= 0 && d->act <= 2 && (d->act != 2 || d->G || d->Gr), "lfi_gemm_planes: bad act %d", d->act);
+namespace {
+
+int planes_clamped_splitk(const lfi_pgemm_desc* d) {
   const int nkt = (d->K + 15) / 16;
-  // (row use: the buffer's column tiles are the product's k-tiles; transposed use: they are its mn tiles, two per 32-wide mn tile)
-  LFI_REQUIRE((d->a_fmt ? 2L * d->a_nkt >= (d->M + 15) / 16 : d->a_nkt >= nkt) && (d->b_fmt ? 2L * d->b_nkt >= (d->N + 15) / 16 : d->b_nkt >= nkt),
-              "lfi_gemm_planes: plane buffers hold %ld / %ld column tiles per row tile: too few for this product", (long)d->a_nkt, (long)d->b_nkt);
-  LFI_REQUIRE(d->a_nkt > 0 && d->b_nkt > 0, "lfi_gemm_planes: a_nkt / b_nkt = column tiles per row tile of the plane buffers");
-  LFI_REQUIRE((reinterpret_cast<uintptr_t>(d->Ap) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->Bp) & 15) == 0 &&
-              (d->a_stride & 7) == 0 && (d->b_stride & 7) == 0, "lfi_gemm_planes: planes must be 16-byte aligned");
-  int splitk = d->splitk < 1 ? 1 : d->splitk;
-  if (splitk > nkt) splitk = nkt;
-  LFI_REQUIRE(splitk == 1 || d->work, "lfi_gemm_planes: splitk needs a workspace");
-  LFI_REQUIRE(splitk == 1 || (!d->Cr && !d->colsum_part && store), "lfi_gemm_planes: plane outputs / column sums need splitk = 1");
-  const bool planes_io = d->Cr || d->Gr;
-  if (planes_io) {
-    LFI_REQUIRE(d->batch == 1 || (d->strideC > 0 && d->strideC * d->batch <= (d->C ? d->ldc : d->strideC * d->batch) && d->strideC % 32 == 0),
-                "lfi_gemm_planes: plane outputs need batch entries side by side in C's columns, 32-column granular");
-    LFI_REQUIRE(d->cr_col0 % 16 == 0 && d->gr_col0 % 16 == 0, "lfi_gemm_planes: plane outputs must start on block boundaries");
-    LFI_REQUIRE((!d->Cr || (reinterpret_cast<uintptr_t>(d->Cr) & 15) == 0) && (!d->Gr || (reinterpret_cast<uintptr_t>(d->Gr) & 15) == 0),
-                "lfi_gemm_planes: planes must be 16-byte aligned");
-  }
-  GemmArgs a = {};
+  const int splitk = d->splitk < 1 ? 1 : d->splitk;
+  return splitk > nkt ? nkt : splitk;
+}
+
+// the launch descriptor of a (validated) product: shared by lfi_gemm_planes and the host queries about what it will do.
+// The sign-word fields are left to the caller.
+void planes_args(const lfi_pgemm_desc* d, GemmArgs& a, bool& tall) {
+  const int nkt = (d->K + 15) / 16;
+  const int splitk = planes_clamped_splitk(d);
+  const bool store = d->store_f32 != 0;
+  a = GemmArgs{};
   a.M = d->M; a.N = d->N; a.K = d->K;
   a.C = d->C; a.ldc = d->ldc; a.bias = d->bias; a.G = d->G; a.ldg = d->ldg;
   a.strideC = d->strideC; a.strideBias = d->strideBias; a.strideG = d->strideG;
@@ -790,12 +910,11 @@ extern "C" int lfi_gemm_planes(const lfi_pgemm_desc* d, void* stream) {
     const bool partial = splitk > 1;
     const bool c_ok = partial ? (((long)d->M * d->N) % 4 == 0 && d->N % 4 == 0 && (reinterpret_cast<uintptr_t>(d->work) & 15) == 0)
                               : (!store || ((reinterpret_cast<uintptr_t>(d->C) & 15) == 0 && d->ldc % 4 == 0 && d->strideC % 4 == 0));
-    const bool g_ok = d->act != 2 || d->Gr || ((reinterpret_cast<uintptr_t>(d->G) & 15) == 0 && d->ldg % 4 == 0 && d->strideG % 4 == 0);
+    const bool g_ok = d->act != 2 || d->Gr || d->sign_in || ((reinterpret_cast<uintptr_t>(d->G) & 15) == 0 && d->ldg % 4 == 0 && d->strideG % 4 == 0);
     a.vecC = (c_ok && g_ok && !(d->act == 2 && d->accumulate != 0)) ? 1 : 0;
-    LFI_REQUIRE(a.vecC || !(planes_io || d->colsum_part), "lfi_gemm_planes: plane outputs / column sums need 16-byte granular C rows");
   }
   a.hiOnly = d->out_hi_only ? 1 : 0;
-  const bool tall = planes_tall_tile(d);
+  tall = planes_tall_tile(d);
   a.tiles_m = lfi_cdiv(d->M, tall ? 256 : 128);
   a.tiles_n = lfi_cdiv(d->N, tall ? 128 : 256);
   {
@@ -809,6 +928,86 @@ extern "C" int lfi_gemm_planes(const lfi_pgemm_desc* d, void* stream) {
       gm_env = e ? atoi(e) : 0;
     }
     a.gm = gm_env > 0 ? gm_env : 8;
+  }
+}
+
+// The product as lfi_gemm_planes would launch it can honour sign words: out = as their writer (direct plane epilogue), otherwise as
+// their reader (the in-place masked product's direct epilogue); whole 64 x 64 patches of the Cr matrix either way.
+bool planes_signs_path(const GemmArgs& a, const lfi_pgemm_desc* d, bool tall, bool out) {
+  if (!lfi_env_on("LFI_PGEMM_SIGNS")) return false;
+  if (!planes_sign_geometry_ok(a, d->batch)) return false;
+  return out ? planes_takes_direct3(a, d->a_fmt, d->b_fmt, tall) : planes_takes_direct4(a, d->a_fmt, d->b_fmt, tall);
+}
+
+}  // namespace
+
+extern "C" int lfi_gemm_planes_signs_ok(const lfi_pgemm_desc* d) {
+  if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch < 1 || !d->Ap || !d->Bp) return 0;
+  if (!d->sign_out && !d->sign_in) return 0;
+  GemmArgs a;
+  bool tall;
+  planes_args(d, a, tall);
+  if (d->sign_in) a.Si = reinterpret_cast<const unsigned long long*>(d->sign_in);
+  if (d->sign_out && !planes_signs_path(a, d, tall, true)) return 0;
+  if (d->sign_in && !planes_signs_path(a, d, tall, false)) return 0;
+  return 1;
+}
+
+extern "C" long lfi_gemm_planes_persist_grid(const lfi_pgemm_desc* d) {
+  if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch < 1 || !d->Ap || !d->Bp) return 0;
+  GemmArgs a;
+  bool tall;
+  planes_args(d, a, tall);
+  if (d->sign_in) a.Si = reinterpret_cast<const unsigned long long*>(d->sign_in);
+  if (!planes_takes_direct4(a, d->a_fmt, d->b_fmt, tall) || a.splitk != 1) return 0;
+  return planes_persist_wgs((long)a.tiles_m * a.tiles_n * d->batch);
+}
+
+extern "C" int lfi_gemm_planes(const lfi_pgemm_desc* d, void* stream) {
+  LFI_REQUIRE(d, "lfi_gemm_planes: null descriptor");
+  LFI_REQUIRE(d->M >= 0 && d->N >= 0 && d->K >= 0 && d->batch >= 1 && d->batch <= 65535, "lfi_gemm_planes: bad dims M=%d N=%d K=%d batch=%d",
+              d->M, d->N, d->K, d->batch);
+  if (d->M == 0 || d->N == 0) return LFI_OK;
+  const bool store = d->store_f32 != 0;
+  LFI_REQUIRE(d->Ap && d->Bp && (d->C || !store), "lfi_gemm_planes: null operand");
+  LFI_REQUIRE(store || d->Cr, "lfi_gemm_planes: store_f32 = 0 and no plane output: the result would go nowhere");
+  LFI_REQUIRE(d->K > 0, "lfi_gemm_planes: K = 0");
+  LFI_REQUIRE(d->act >= 0 && d->act <= 2 && (d->act != 2 || d->G || d->Gr || d->sign_in), "lfi_gemm_planes: bad act %d", d->act);
+  const int nkt = (d->K + 15) / 16;
+  // (row use: the buffer's column tiles are the product's k-tiles; transposed use: they are its mn tiles, two per 32-wide mn tile)
+  LFI_REQUIRE((d->a_fmt ? 2L * d->a_nkt >= (d->M + 15) / 16 : d->a_nkt >= nkt) && (d->b_fmt ? 2L * d->b_nkt >= (d->N + 15) / 16 : d->b_nkt >= nkt),
+              "lfi_gemm_planes: plane buffers hold %ld / %ld column tiles per row tile: too few for this product", (long)d->a_nkt, (long)d->b_nkt);
+  LFI_REQUIRE(d->a_nkt > 0 && d->b_nkt > 0, "lfi_gemm_planes: a_nkt / b_nkt = column tiles per row tile of the plane buffers");
+  LFI_REQUIRE((reinterpret_cast<uintptr_t>(d->Ap) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->Bp) & 15) == 0 &&
+              (d->a_stride & 7) == 0 && (d->b_stride & 7) == 0, "lfi_gemm_planes: planes must be 16-byte aligned");
+  const int splitk = planes_clamped_splitk(d);
+  LFI_REQUIRE(splitk == 1 || d->work, "lfi_gemm_planes: splitk needs a workspace");
+  LFI_REQUIRE(splitk == 1 || (!d->Cr && !d->colsum_part && store), "lfi_gemm_planes: plane outputs / column sums need splitk = 1");
+  const bool planes_io = d->Cr || d->Gr;
+  if (planes_io) {
+    LFI_REQUIRE(d->batch == 1 || (d->strideC > 0 && d->strideC * d->batch <= (d->C ? d->ldc : d->strideC * d->batch) && d->strideC % 32 == 0),
+                "lfi_gemm_planes: plane outputs need batch entries side by side in C's columns, 32-column granular");
+    LFI_REQUIRE(d->cr_col0 % 16 == 0 && d->gr_col0 % 16 == 0, "lfi_gemm_planes: plane outputs must start on block boundaries");
+    LFI_REQUIRE((!d->Cr || (reinterpret_cast<uintptr_t>(d->Cr) & 15) == 0) && (!d->Gr || (reinterpret_cast<uintptr_t>(d->Gr) & 15) == 0),
+                "lfi_gemm_planes: planes must be 16-byte aligned");
+  }
+  GemmArgs a;
+  bool tall;
+  planes_args(d, a, tall);
+  LFI_REQUIRE(a.vecC || !(planes_io || d->colsum_part), "lfi_gemm_planes: plane outputs / column sums need 16-byte granular C rows");
+  if (d->sign_out || d->sign_in) {
+    // sign words (include/lfi.h): only on the products whose epilogue writes / reads them - an error otherwise, never a silent no-op
+    LFI_REQUIRE(lfi_env_on("LFI_PGEMM_SIGNS"), "lfi_gemm_planes: sign words passed with LFI_PGEMM_SIGNS=0");
+    LFI_REQUIRE(!(d->sign_out && d->sign_in), "lfi_gemm_planes: a product writes sign words or reads them, not both");
+    LFI_REQUIRE(((reinterpret_cast<uintptr_t>(d->sign_out) | reinterpret_cast<uintptr_t>(d->sign_in)) & 7) == 0,
+                "lfi_gemm_planes: sign words must be 8-byte aligned");
+    LFI_REQUIRE(!d->sign_in || (d->act == 2 && !d->Gr && !d->G), "lfi_gemm_planes: sign_in is the act-2 mask: act = 2, and neither G nor Gr");
+    if (d->sign_in) a.Si = reinterpret_cast<const unsigned long long*>(d->sign_in);
+    LFI_REQUIRE(planes_signs_path(a, d, tall, d->sign_out != nullptr),
+                "lfi_gemm_planes: this product cannot take sign words (lfi_gemm_planes_signs_ok: direct plane epilogue, 128 x 256 tiles, Cr columns / "
+                "cr_col0 / strideC in 64s, splitk 1)");
+    if (d->sign_out) a.So = reinterpret_cast<unsigned long long*>(d->sign_out);
+    a.npcS = d->cr_nkt / 4;
   }
   const size_t lds = (size_t)QRING * QSLOT;   // 72 KB: two workgroups per CU; the epilogue's 64 x 260 floats fit inside
   dim3 grid(a.tiles_m * a.tiles_n, d->batch, splitk);

@@ -264,6 +264,7 @@ class GlowEngine:
         # the threshold. hparams `engine_backward_products` / LFI_BWD_PRODUCTS override.
         self.backward_products = self.check_backward_products(os.environ.get("LFI_BWD_PRODUCTS", "auto"))
         self._bwd_skip = 0   # skip bits of the backward classes for the backward pass in progress (set by backward())
+        self._signs_ok = {}  # _project: (F, backward products, the switches the queries read) -> c's sign words are written and read
         self.tile_pin = {k.strip(): int(v) for k, v in (it.split("=") for it in os.environ.get("LFI_TILE_PIN", "").split(",") if it)}
         self.pass_skip = {}
         env = os.environ.get("LFI_PASS_SKIP", "")
@@ -547,12 +548,15 @@ class GlowEngine:
     def gemm_planes(self, M, N, K, Ap, a_nkt, Bp, b_nkt, Cm, ldc, bias=None, act=0, slope=0.01, G=None, ldg=0, batch=1,
                     a_stride=0, b_stride=0, sC=0, sBias=0, sG=0, accumulate=0, c_off=0, bias_off=0, tag=None, cls=None,
                     a_fmt=0, b_fmt=0, a_off=0, b_off=0, splitk=1, ws="scratch.pgemm_splitk", store=True,
-                    Cr=None, cr_nkt=0, cr_col0=0, Gr=None, gr_nkt=0, gr_col0=0, colsum_into=None, hi_only=False, tile=0):
+                    Cr=None, cr_nkt=0, cr_col0=0, Gr=None, gr_nkt=0, gr_col0=0, colsum_into=None, hi_only=False, tile=0,
+                    sign_out=None, sign_in=None, signs_query=False, persist_query=False):
         """lfi_gemm_planes. a_fmt / b_fmt: 0 = row use of the operand's planes (k = the matrix' columns), 1 = transposed use (k = its
         rows). a_nkt / b_nkt: column tiles per row tile of the plane buffers. a_off / b_off: bf16 elements into the plane buffers (a
         column-tile offset: ct * 1024; a row-tile offset: rt * nkt * 1024). Cr: bf16 tensor that receives the result as planes; Gr:
-        planes whose hi plane's sign stands in for G (act 2). colsum_into: as gemm(). Returns True when the column sums were taken in
-        the epilogue."""
+        planes whose hi plane's sign stands in for G (act 2). colsum_into: as gemm(). sign_out / sign_in: sign words of the Cr matrix
+        (include/lfi.h) to write / to take the act-2 mask from; signs_query: launch nothing, return whether the product as described
+        takes the sign path (lfi_gemm_planes_signs_ok); persist_query: likewise, return the workgroups of its persistent launch
+        (lfi_gemm_planes_persist_grid; 0: one workgroup per tile). Returns True when the column sums were taken in the epilogue."""
         g = PGemmDesc()
         g.skip = self._skip_bits(cls)
         g.M, g.N, g.K = M, N, K
@@ -571,12 +575,17 @@ class GlowEngine:
         g.Cr, g.cr_nkt, g.cr_col0 = ptr(Cr), cr_nkt, cr_col0
         g.Gr, g.gr_nkt, g.gr_col0 = ptr(Gr), gr_nkt, gr_col0
         g.out_hi_only, g.tile = (1 if hi_only else 0), tile
+        g.sign_out, g.sign_in = ptr(sign_out), ptr(sign_in)
         part, prow = None, 0
         if colsum_into is not None and os.environ.get("LFI_NO_COLPART") != "1":
             prow = int(self.L.lfi_gemm_planes_colpart_rows(C.byref(g)))
             if prow > 0:
                 part = self._buf("scratch.colpart", prow * ldc)
                 g.colsum_part, g.ld_part = part.data_ptr(), ldc
+        if signs_query:
+            return bool(self.L.lfi_gemm_planes_signs_ok(C.byref(g)))
+        if persist_query:
+            return int(self.L.lfi_gemm_planes_persist_grid(C.byref(g)))
         ev = self._tic(tag)
         check(self.L.lfi_gemm_planes(C.byref(g), _stream()), "lfi_gemm_planes")
         self._toc(tag, ev)
@@ -816,8 +825,31 @@ class GlowEngine:
             wp, nkw = self._wct_planes
             nkKD = KD // 16
             c_r = self.plane_buf("c_r", self.L.lfi_planes_elems(F, KD) + 256 * KD * 2)
-            self.gemm_planes(F, KD, s.ldf, cp, nkc, wp, nkw, None, KD, bias=self.fview("bct"), act=1, slope=0.01, store=False,
-                             Cr=c_r, cr_nkt=nkKD, tag="gemm_cond_fwd", cls="cond_fwd")
+            fwd = dict(bias=self.fview("bct"), act=1, slope=0.01, store=False, Cr=c_r, cr_nkt=nkKD, tag="gemm_cond_fwd", cls="cond_fwd")
+            # sign words of c (one bit per element: all that the backward mask uses of it): written here when a backward pass follows
+            # and both this product and the dpre product take them (LFI_PGEMM_SIGNS=0, or either on another kernel: nobody does)
+            signs = None
+            if with_stash:
+                # (the answer depends on the shapes, the backward pass's product count and the switches the two host queries read:
+                # asked once. The queries launch nothing and only look whether a sign buffer is named: c_r stands in for it.)
+                env = os.environ.get
+                key = (F, self.backward_product_count(F), env("LFI_PGEMM_SIGNS"), env("LFI_PGEMM_DIRECT"), env("LFI_PGEMM_16"),
+                       env("LFI_PGEMM_16T"), env("LFI_NO_COLPART"),
+                       tuple(sorted(self.pass_skip.items())) if self.pass_skip else (), tuple(sorted(self.tile_pin.items())) if self.tile_pin else ())
+                ok = self._signs_ok.get(key)
+                if ok is None:
+                    saved = self._bwd_skip   # (the dpre product is asked about as backward() will run it: its product count)
+                    self._bwd_skip = 1 if key[1] == 2 else 0
+                    try:
+                        ok = (self.gemm_planes(F, KD, s.ldf, cp, nkc, wp, nkw, None, KD, sign_out=c_r, signs_query=True, **fwd)
+                              and self._dpre_product(c_r, F, c_r, signs_query=True))
+                    finally:
+                        self._bwd_skip = saved
+                    self._signs_ok[key] = ok
+                if ok:
+                    signs = self._buf("c_signs", 2 * self.L.lfi_planes_sign_words(F, KD))
+            self._c_signs = signs
+            self.gemm_planes(F, KD, s.ldf, cp, nkc, wp, nkw, None, KD, sign_out=signs, **fwd)
             gic = self._buf("gic", s.Ks * F * s.G)
             wr, nkwr = self._wc_r
             self.gemm_planes(F, s.G, s.D, c_r, nkKD, wr, nkwr, gic, s.G, bias=self.fview("b_ih"), batch=s.Ks,
@@ -876,6 +908,7 @@ class GlowEngine:
         ctx.batch, ctx.masks, ctx.B, ctx.T, ctx.N, ctx.F = batch, masks, B, T, N, F
         ctx.cond, ctx.cbuf, ctx.gic, ctx.stash, ctx.dims, ctx.with_stash, ctx.chain = cond, cbuf, gic, stash, dims, with_stash, chain
         ctx.enc_stash_f16 = dict(self._enc_stash_f16)
+        ctx.signs = self._c_signs if (chain and with_stash) else None
         self._last = ctx
         return z, nll
 
@@ -985,9 +1018,8 @@ class GlowEngine:
         nkKD, nkG, nkD = KD // 16, G // 16, D // 16
         dgi_p = self.plane_buf("dgi_planes", self.L.lfi_planes_elems(Ks * F, G) + 256 * G * 2)
         # with two products in their consumers (A rounded to bf16) the lo planes of dgi and of d pre-activation are never
-        # fetched: the walk / the dpre epilogue then write the hi planes only (half the plane traffic)
+        # fetched: the walk / the dpre epilogue (_dpre_product) then write the hi planes only (half the plane traffic)
         dgi_hi = all(self._skip_bits(c) & 1 for c in ("dpre", "flow_pgrads"))
-        dpre_hi = all(self._skip_bits(c) & 1 for c in ("cond_wgrad", "cond_dgrad"))
         # two-product thin weight-gradient products round dgi | dgh to bf16 on arrival: the walk then leaves those ROWS as bf16 (half the
         # bytes written by the walk and read by the products; gemm_precision bit 16, same bit in both calls; LFI_FLOW_G16=0: fp32 rows)
         pg_skip = self._skip_bits("flow_pgrads")
@@ -1017,11 +1049,8 @@ class GlowEngine:
         # d pre-activation of cond_transform = (dgi[k] W_c[k]) * leaky'(c), written as planes IN PLACE of c's (same blocks, read
         # for the mask and rewritten by the same workgroup; dW_c above was c's last reader); W_c's planes in transposed use (the sum
         # runs over its G gate rows); the epilogue also leaves per-pass column sums: the cond_transform bias gradient
-        wr, nkwr = self._wc_r
-        bct_done = self.gemm_planes(F, D, G, dgi_p, nkG, wr, nkwr, None, KD, act=2, slope=0.01, batch=Ks, b_fmt=1,
-                                    a_stride=(F // 32) * nkG * 1024, b_stride=(G // 32) * nkwr * 1024, sC=D, store=False,
-                                    Gr=c_r, gr_nkt=nkKD, Cr=c_r, cr_nkt=nkKD, hi_only=dpre_hi,
-                                    colsum_into=self.fview("bct", self.grads), tag="gemm_dpre", cls="dpre")
+        # (the mask from c's sign words where the forward product left them, from the hi plane of c's planes otherwise)
+        bct_done = self._dpre_product(c_r, F, ctx.signs)
         if not bct_done:
             raise _lib.LfiError("the dpre product on planes did not take the column-sum epilogue")
         dpre_p = c_r
@@ -1048,6 +1077,20 @@ class GlowEngine:
             self.gemm_planes(F, W, KD, dpre_p, nkKD, wp, nkw, dcond, ldd, b_fmt=1, b_off=(col0 // 16) * 1024,
                              splitk=self._planes_splitk(F, W, KD), tag="gemm_cond_dgrad", cls="cond_dgrad")
             self._encoders_backward(rnn, ctx, dcond, ldd, col0)
+
+    def _dpre_product(self, c_r, F, signs, signs_query=False):
+        """The in-place dpre product of _backward_chain (or, signs_query: whether it would take its mask from the sign words)."""
+        s = self.spec
+        KD, G, D, Ks = s.Ks * s.D, s.G, s.D, s.Ks
+        nkKD, nkG = KD // 16, G // 16
+        dgi_p = self.plane_buf("dgi_planes", self.L.lfi_planes_elems(Ks * F, G) + 256 * G * 2)
+        dpre_hi = all(self._skip_bits(c) & 1 for c in ("cond_wgrad", "cond_dgrad"))
+        wr, nkwr = self._wc_r
+        return self.gemm_planes(F, D, G, dgi_p, nkG, wr, nkwr, None, KD, act=2, slope=0.01, batch=Ks, b_fmt=1,
+                                a_stride=(F // 32) * nkG * 1024, b_stride=(G // 32) * nkwr * 1024, sC=D, store=False,
+                                Gr=(None if signs is not None else c_r), gr_nkt=nkKD, Cr=c_r, cr_nkt=nkKD, hi_only=dpre_hi,
+                                sign_in=signs, signs_query=signs_query,
+                                colsum_into=self.fview("bct", self.grads), tag="gemm_dpre", cls="dpre")
 
     def _encoders_backward(self, rnn, ctx, dcond, ldd, col0):
         """BPTT of every trainable window encoder. Largest recurrence first on the main stream (each one's window scatter + dW_ih on
