@@ -454,6 +454,28 @@ int lfi_flow_score_seq_from(const lfi_flow_dims* d, const lfi_flow_params* p, co
                             float* faces, int seq_len, int start, int nframes, int first_frame,
                             float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
                             float* score_work, float* z, float* nll, void* stream);
+/* lfi_flow_score_seq_from for a CHUNK of frames known up front (SampleStream.observe_many): the same arguments with a chunk work area
+ * where that has score_work, and the same contract - it leaves in h / cstate, z and nll what lfi_flow_score_seq_from leaves for
+ * them. The front end runs ONCE for all nframes (the prev_p1_face windows gathered, the encoded kinds over nframes * B windows,
+ * c = LeakyReLU(pre_static + window part) in place, gic as [Ks][nframes * B][G]) at d->gemm_precision, and the chain is ONE launch of
+ * Ks ceil(B / 16) workgroups: workgroup (k, tile) loops over the frames with its recurrent state on chip, waits for frame n of
+ * (k - 1, tile) and hands its own on through a slot per (step boundary, frame) - nframes + Ks - 1 cell times end to end where one
+ * launch per frame takes nframes * Ks. A workgroup waits only on a lower ticket and no slot is reused inside a launch, so any number
+ * of resident workgroups makes progress; spins are bounded, and an abandoned launch leaves NaN in every nll / z it did not finish.
+ * The cells' arithmetic by d->gemm_precision as lfi_flow_score_seq_from's. chunk_work: lfi_flow_score_chunk_work_floats(d, p1, hist1)
+ * floats, d->N = the frames per call (the caller bounds it by splitting a long chunk: state carries through h / cstate and
+ * first_frame); p1work / work are not used. lfi_flow_score_chunk_ok: 1 where this chain runs (C, Cout <= 64, H <= 128,
+ * LFI_SAMPLE_CHAIN not 0, LFI_FLOW_GENERIC not 1); elsewhere call lfi_flow_score_seq_from. hist1 >= 1 is required (a window of no
+ * frames has no front end to batch: lfi_flow_score_seq_from takes that case too). LFI_CHUNK_ONLY=front / chain, for
+ * tools/stream_latency.py alone: only that part of the call is launched, to be timed; the results are not meaningful.
+ * Allocation-free; every argument is checked before the first launch. */
+long lfi_flow_score_chunk_work_floats(const lfi_flow_dims* d, const lfi_p1enc* p1, int hist1);
+int lfi_flow_score_chunk_ok(const lfi_flow_dims* d);
+int lfi_flow_score_seq_chunk(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep,
+                             const float* wct, long E, int hist1, float* pre_static,
+                             float* faces, int seq_len, int start, int nframes, int first_frame,
+                             float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
+                             float* chunk_work, float* z, float* nll, void* stream);
 /* ONE frame of a session in which every batch row either observes or generates (SampleStream.step_rows): lfi_flow_sample_seq_nll's
  * arguments (nframes must be 1; nll, B floats, and nll_work are required), then observed (B ints on the device: != 0 = the row's
  * frame is GIVEN - it is in faces[:, start] already - and 0 = the row generates from its noise row) and a second work area, rows_work
@@ -487,6 +509,21 @@ int lfi_stream_advance(int B, int count, float* const* win, const float* const* 
 int lfi_stream_advance_rows(int B, int count, float* const* win, const float* const* src, const int* hist, const int* dim,
                             int face_win, const float* noise, float* noise_dst, int C, float* frame_nb,
                             const unsigned char* observed, int* role, unsigned* guard_bits, void* stream);
+/* A chunk of n >= 1 observed frames of a streaming session per call (SampleStream.observe_many), two launches around the chunk's static
+ * part and chain. The window tables are lfi_stream_reset_rows' (count <= 8, the prev_p1_face window last with lead[i] = 1: its hist[i]
+ * counts the leading row). seq[i]: the session's sequence buffer of window i, B x (start + n) x dim[i], the shape the sequence mode
+ * of the feature builder and lfi_flow_score_seq_chunk take; hist[i] - lead[i] <= start.
+ * in: the window's live frames go to frames start - (hist[i] - lead[i]) .. start - 1 of seq[i], src[i] (B x n x dim[i], the
+ * caller's frames t .. t + n - 1; the observed faces for the prev_p1_face window) to frames start .. start + n - 1. Frames in front
+ * of a window are neither read nor written (zero them once). max |v| of every NEW value is folded into *guard_bits as
+ * lfi_stream_advance does (NULL = no guard).
+ * out: every window takes the last hist[i] frames of seq[i] - right for n below, at and above hist[i] (the prev_p1_face window's
+ * leading row so holds what n one-frame advances leave in it); frame_nb (B floats, NULL = no counter) += 2 n.
+ * Allocation-free; every argument is checked before the launch. */
+int lfi_stream_chunk_in(int B, int n, int start, int count, float* const* win, const float* const* src, float* const* seq,
+                        const int* hist, const int* dim, const int* lead, unsigned* guard_bits, void* stream);
+int lfi_stream_chunk_out(int B, int n, int start, int count, float* const* win, float* const* seq, const int* hist,
+                         const int* dim, const int* lead, float* frame_nb, void* stream);
 /* Reseed listed batch rows of a streaming sampling session (SampleStream.reset_rows; the start of glow/models.py:567-596 for those
  * rows alone) between steps: each session row rows[j] (0 <= rows[j] < B, none twice, nrows >= 1) gets the state open_stream gives
  * a row, from entry j of the caller's seed, and no other row is written. Per window i (count <= 8; the layout of lfi_stream_advance):

@@ -54,6 +54,12 @@ extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond(co
                                                                               int have_xfrag, void* stream);
 extern "C" __attribute__((visibility("hidden"))) void* lfi_internal_sample_cond_xfrag_ptr(void* frags, int Ks, int G, int K1);
 
+// ---- internal: the sampler's front end for M rows of prev_p1_face windows (lfi_flow_chain.hip), called by lfi_flow_chunk.hip too
+extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_front_rows(const lfi_flow_dims* d, const lfi_flow_params* p,
+                                                                                    const lfi_p1enc* p1, const float* wct, long E, int hist1,
+                                                                                    const float* wc, int M, const float* win, long ldwin,
+                                                                                    float* cfr, float* gic, float* p1work, void* stream);
+
 // ---- internal: the flow's thin weight-gradient products in one pass over the backward stash (lfi_wgrad.hip), called by
 // lfi_flow_param_grads (lfi_flow.hip)
 extern "C" __attribute__((visibility("hidden"))) int lfi_internal_flow_wgrad_ok(int B, int N, int C, int Ch, int Cout, int H, int G, int ldc,

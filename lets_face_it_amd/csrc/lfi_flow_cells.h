@@ -625,7 +625,8 @@ __device__ __forceinline__ f32x4 x3_mma_gates_img(const __bf16* hi_row, const __
 // (g_out may be null).
 // gate math + stores of P2 on this wave's 16 hidden units, given the two accumulated products (az: z1 side, ah: h side)
 // RM (row-masked cells): h_out / c_out are stored for the rows of `live` only (tile_live_rows), not for every row inside the batch.
-template <int NG, bool RM = false>
+// CST = false (the frame loop of fwd_chain_cell): c_out is not stored here - the caller keeps the cell state in cnew and stores it itself.
+template <int NG, bool RM = false, bool CST = true>
 __device__ __forceinline__ void fast_cell_p2_gates(const FlowK& f, const float* Ht, float* Hn, const f32x4 (&az)[NG],
                                                    const f32x4 (&ah)[NG], const float (&gc)[4][NG], const float (&bh)[NG],
                                                    const float (&cprev)[4], int j2, int kq, int b0, int rows, float* h_out,
@@ -657,7 +658,7 @@ __device__ __forceinline__ void fast_cell_p2_gates(const FlowK& f, const float* 
         const float oo = sigmoidf_(az[NG - 1][r] + ah[NG - 1][r] + gc[r][NG - 1] + bh[NG - 1]);
         const float c2 = __builtin_fmaf(ff, cprev[r], ii * gg);
         hnew = oo * tanhf_(c2);
-        if (rs) c_out[(long)row * H + j2] = c2;
+        if (CST && rs) c_out[(long)row * H + j2] = c2;
         if (cnew) cnew[r] = c2;
         gs0 = ii; gs1 = ff; gs2 = gg; gs3 = oo;
       }
@@ -1079,5 +1080,427 @@ inline bool flow_x3_bwd_planes(const lfi_flow_dims* d) {
 inline bool flow_x3_rev_cell(const lfi_flow_dims* d, const FlowK& f) {
   return (d->gemm_precision & 1) && flow_x3h_images_ok(f) && flow_pipe_x3_enabled();
 }
+
+// What lfi_flow_sample_seq_nll, lfi_flow_score_seq_from and lfi_flow_step_rows_from (and lfi_flow_score_seq_chunk, lfi_flow_chunk.hip) ask of the arguments they share, in one order.
+// who_from: the name first_frame is reported under (the sampler's is its _from entry point); ptrs_ok: the caller's own list of
+// pointers that must not be null. A rule on the frame count itself is the caller's and follows this check.
+inline int frame_args_check(const char* who, const char* who_from, const lfi_flow_dims* d, bool ptrs_ok, long E, int hist1, int start,
+                     int nframes, int seq_len, const float* cstate, int first_frame) {
+  LFI_REQUIRE(first_frame >= 0, "%s: negative first_frame", who_from);
+  LFI_REQUIRE(ptrs_ok, "%s: null pointer", who);
+  LFI_REQUIRE(hist1 >= 0 && hist1 <= start && start + nframes <= seq_len, "%s: bad frame range", who);
+  LFI_REQUIRE((long)hist1 * d->C <= E, "%s: window wider than the feature vector", who);
+  LFI_REQUIRE(!d->lstm || cstate, "%s: the LSTM cell needs cstate", who);
+  return LFI_OK;
+}
+
+
+// ---- the forward chain's cell (lfi_flow_chain.hip: one frame per launch; lfi_flow_chunk.hip: the frames of a chunk in one launch)
+// FlowStep.normal_flow (glow/models.py:311-341) of ONE observed frame with the recurrent state carried in place: the forward twin of
+// rev_fast_cell for a streaming session's observe() step. Same thread maps, same LDS carve, same place of the wait: the weights, gic,
+// h_prev and the h_prev W_hh half of the recurrent product run before it; behind it actnorm, y = a W, the z1 half + the gates,
+// LinearZeros and the coupling. The recurrent cell sees what the reverse cell of the same frame sees - z1 and the conditioning - so
+// the h / c it leaves is the state a sampler continues from. No stash of any kind.
+// X3: every product as three fp16 products of two-piece operands (x3h_*, fp32-grade: 2^-22 relative), the f32 fragment images split
+// in registers before the wait; otherwise the exact f32 MFMA. (The training walks' three bf16 products - 2^-16 pieces - are not used
+// here: the state must match the reverse cell's to the sampler's own tolerance.)
+// q_in: the rows' running coupling log-det from step k - 1 (null: this cell starts it); q_out: where it goes on to step k + 1, sc1
+// stores in front of the publish. nll_out (the last step): the cell adds the prior term of its z, sum_c -0.5 (z_c^2 + log 2 pi), and
+// logdet_const and writes -(logdet + log p(z)) / ln 2 in bits. One writer per word, k ascending: a fixed summation order.
+// io.x_out may be null (the last step of a caller that does not want z).
+// RM (flow_rows_chain_kernel): a row-masked cell, as rev_fast_cell's - h_out / c_out, the output tile, the hand-over q and the NLL word
+// are stored for the rows of role io.role_want only.
+// SEQ (flow_fwd_seq_chain_kernel): the cell runs the sq->frames frames of a launch one after another. What does not depend on the frame
+// is requested once where the register file allows - the GRU cell's W_hh and W_ih[:, :Ch], the per-column constants, h_prev / c_prev
+// of the first frame; W and LinearZeros (and, for the LSTM cell, whose four gate blocks of W_hh alone are 128 VGPRs, every weight)
+// are asked for again in every frame, from the L2 and in front of where they are needed. The recurrent state stays
+// on chip: Hn of frame n is Ht of frame n + 1 (the two LDS images swap), the LSTM cell state crosses in registers; h_out and c_out are stored at
+// the last frame only. Per frame: gic, the wait for frame n of step k - 1 (progress word >= n + 1), the cell, the hand-over slot of
+// (k, n), progress word = n + 1. io / q_in / q_out / nll_out point at frame 0; sq holds the strides. A wait that gives up leaves NaN in
+// the nll / z of the frames the last step has not finished.
+struct FwdSeq {
+  int frames;
+  long x_in_step, x_out_step;   // floats between two frames' rows of x_in / x_out
+  long gic_step, row_step;      // B * G; B (q_in, q_out, nll_out)
+};
+template <int NG, bool X3, bool RM = false, bool SEQ = false>
+__device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io, int b0, const unsigned* wait_flag, unsigned* abort_w,
+                                               unsigned* pub_flag, int* s_ok, const float* q_in, float* q_out, float* nll_out,
+                                               const FwdSeq* sq = nullptr) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int l15 = lane & 15, kq = lane >> 4;   // (not const: SEQ, at the head of the frame loop)
+  int ri = tid >> 5, cl = tid & 31;
+  const int k = io.k, rows = io.rows;
+  const int C = f.C, H = f.H, Ch = f.Ch, C2 = f.C2, Cout = f.Cout, G = f.G;
+  const int C16 = f.C16, Ch16 = f.Ch16, H16 = f.H16, Co16 = f.Co16;
+  const CarveF cv = carve_fast_fwd(C, C16, H16, Ch16, Cout);
+  float* At = flow_smem + cv.At;
+  float* Ht = flow_smem + cv.Ht;
+  float* Zt = flow_smem + cv.Zt;
+  float* Hn = flow_smem + cv.Hn;
+  float* Yrm = flow_smem + cv.Yrm;
+  float* Orm = flow_smem + cv.Orm;
+  const int ldy = C + 1, ldo = Cout + 1;
+  const int nbC = C16 >> 4, nbZ = Ch16 >> 4, nbH = H16 >> 4;
+  const bool t1 = wave * 16 < C, t2 = wave * 16 < H, t3 = wave * 16 < Cout;
+  int tcol = wave * 16 + l15;
+  unsigned live = 0u;
+  if constexpr (RM) live = tile_live_rows(io.role, io.role_want, b0, rows);
+  // ---- requests in the order their results are needed: h_prev (its LDS image gates the first barrier), the recurrent weights, then
+  // the weights of the phases behind the wait
+  const int hrow = b0 + ri;
+  float hv[FB_H / 2];
+#pragma unroll
+  for (int q = 0; q < FB_H / 2; ++q) {
+    const int j = cl + 32 * q;
+    hv[q] = (io.h_prev && hrow < rows && j < H) ? io.h_prev[(long)hrow * H + j] : 0.0f;
+  }
+  f32x4 wz[NG][FB_Z], wh[NG][FB_H], w3[FB_H], w1[FB_C];
+  // SEQ: what a frame asks for again, whole (zero padding included, so that nothing of it lives across the frames): W behind the
+  // h-side product and LinearZeros behind F1; for the LSTM cell also W_hh in front of the h-side product and W_ih[:, :Ch] behind it.
+  // W_hh and W_ih[:, :Ch] of the GRU cell (120 VGPRs at H = 128) are what the register file holds across the frames beside the
+  // cell's own values. (The image pointer goes through an empty asm statement in every frame: the compiler would otherwise hoist
+  // these loop-invariant loads out of the frame loop and keep their 48 - 208 VGPRs alive across it - in scratch.)
+  constexpr bool WH_PER_FRAME = SEQ && NG == 4;
+  auto per_frame = [](const float* img) {
+    asm volatile("" : "+s"(img));
+    return img;
+  };
+  [[maybe_unused]] auto load_wh = [&](const float* img) {
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+#pragma unroll
+      for (int b = 0; b < FB_H; ++b) wh[g][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      load_frag<FB_H>(wh[g], img + (long)k * H16 * NG * H16, NG * H16, g * H16 + tcol, kq, nbH, t2);
+    }
+  };
+  [[maybe_unused]] auto load_w1 = [&]() {
+#pragma unroll
+    for (int b = 0; b < FB_C; ++b) w1[b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    load_frag<FB_C>(w1, per_frame(f.pW) + (long)k * C16 * C16, C16, tcol, kq, nbC, t1);
+  };
+  [[maybe_unused]] auto load_w3 = [&]() {
+#pragma unroll
+    for (int b = 0; b < FB_H; ++b) w3[b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    load_frag<FB_H>(w3, per_frame(f.pwfl) + (long)k * H16 * Co16, Co16, tcol, kq, nbH, t3);
+  };
+  [[maybe_unused]] auto load_wz = [&](const float* img) {
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+#pragma unroll
+      for (int b = 0; b < FB_Z; ++b) wz[g][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      load_frag<FB_Z>(wz[g], img + (long)k * Ch16 * NG * H16, NG * H16, g * H16 + tcol, kq, nbZ, t2);
+    }
+  };
+  if constexpr (SEQ) {
+    if constexpr (!WH_PER_FRAME) {
+      load_wh(f.pwh);
+      load_wz(f.pwz);
+    }
+  } else {
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+#pragma unroll
+      for (int b = 0; b < FB_Z; ++b) wz[g][b] = zero4;
+#pragma unroll
+      for (int b = 0; b < FB_H; ++b) wh[g][b] = zero4;
+      load_frag<FB_H>(wh[g], f.pwh + (long)k * H16 * NG * H16, NG * H16, g * H16 + tcol, kq, nbH, t2);
+      load_frag<FB_Z>(wz[g], f.pwz + (long)k * Ch16 * NG * H16, NG * H16, g * H16 + tcol, kq, nbZ, t2);
+    }
+#pragma unroll
+    for (int b = 0; b < FB_H; ++b) w3[b] = zero4;
+#pragma unroll
+    for (int b = 0; b < FB_C; ++b) w1[b] = zero4;
+    // (the LSTM cell's four gate blocks of W_hh fill the register file: its W and LinearZeros fragments are requested once the h-side
+    // product has let those go - still in front of the wait; 24 VGPRs in scratch otherwise)
+    if constexpr (NG != 4) {
+      load_frag<FB_C>(w1, f.pW + (long)k * C16 * C16, C16, tcol, kq, nbC, t1);
+      load_frag<FB_H>(w3, f.pwfl + (long)k * H16 * Co16, Co16, tcol, kq, nbH, t3);
+    }
+  }
+  float gc[4][NG], bh[NG], cprev[4];
+  [[maybe_unused]] float cnew[4];
+  auto load_gic = [&](const float* gic, bool first) {   // first: + the constants and the state that arrive once
+    const float* bhh = f.p.b_hh + (long)k * G;
+    const int jc = tcol < H ? tcol : 0;
+    if (first) {
+#pragma unroll
+      for (int g = 0; g < NG; ++g) bh[g] = bhh[g * H + jc];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = min(b0 + kq * 4 + r, rows - 1);
+#pragma unroll
+      for (int g = 0; g < NG; ++g) gc[r][g] = gic[(long)row * G + g * H + jc];
+      if (first) cprev[r] = (NG == 4 && io.c_prev) ? io.c_prev[(long)row * H + jc] : 0.0f;
+    }
+  };
+  if constexpr (NG != 4) load_gic(io.gic, true);
+  // per-column constants of the phases behind the wait: ActNorm of this thread's two channels (cl, cl + 32), LinearZeros of its column
+  float an_b[2], an_s[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int c = cl + 32 * q;
+    an_b[q] = c < C ? f.p.an_bias[(long)k * C + c] : 0.0f;
+    an_s[q] = c < C ? expf(f.p.an_logs[(long)k * C + c]) : 0.0f;
+  }
+  const float flb = tcol < Cout ? f.p.b_fl[(long)k * Cout + tcol] : 0.0f;
+  const float fls = tcol < Cout ? expf(3.0f * f.p.l_fl[(long)k * Cout + tcol]) : 0.0f;
+  // ---- before the wait: h_prev and the zero k padding into LDS, the fragment split, the h_prev W_hh half of the recurrent product
+#pragma unroll
+  for (int q = 0; q < FB_H / 2; ++q) {
+    const int j = cl + 32 * q;
+    if (j < H16) {
+      Ht[j * LT + ri] = hv[q];
+      if (j >= H) Hn[j * LT + ri] = 0.0f;
+    }
+  }
+  for (int c = Ch + cl; c < Ch16; c += 32) Zt[c * LT + ri] = 0.0f;
+  X3FragH wzx[X3 ? NG : 1][FB_Z / 2], w3x[X3 ? FB_H / 2 : 1], w1x[X3 ? FB_C / 2 : 1];
+  if constexpr (X3) {   // (instantiated for shapes with whole 32-k blocks everywhere: flow_x3h_images_ok)
+    if constexpr (!SEQ) {
+#pragma unroll
+    for (int b = 0; b < FB_H / 2; ++b) w3x[b] = x3h_pack(w3[2 * b], w3[2 * b + 1]);
+#pragma unroll
+    for (int b = 0; b < FB_C / 2; ++b) w1x[b] = x3h_pack(w1[2 * b], w1[2 * b + 1]);
+    }
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+      for (int b = 0; b < FB_Z / 2; ++b) wzx[g][b] = WH_PER_FRAME ? X3FragH{} : x3h_pack(wz[g][2 * b], wz[g][2 * b + 1]);
+  }
+  __syncthreads();
+  const int frames = SEQ ? sq->frames : 1;
+  for (int n = 0; n < frames; ++n) {
+  if constexpr (SEQ) {
+    // (the thread's coordinates pass through an empty asm statement: everything addressed from them is then worked out again in
+    // every frame - a few VALU instructions - instead of being hoisted out of the loop, where some twenty such addresses and
+    // predicates sat in registers across all phases and pushed the kernel into scratch)
+    asm volatile("" : "+v"(l15), "+v"(kq), "+v"(ri), "+v"(cl), "+v"(tcol));
+    if constexpr (WH_PER_FRAME) load_wh(per_frame(f.pwh));
+    if (NG != 4 && n > 0) load_gic(io.gic + n * sq->gic_step, false);
+  }
+  f32x4 az[NG], ah[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    az[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    ah[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  if (t2) {
+    const float* hl = Ht + kq * LT + l15;
+    if constexpr (X3) {
+#pragma unroll
+      for (int b = 0; b < FB_H / 2; ++b)
+        if (b < (nbH >> 1)) {
+          const X3FragH a = x3h_a(hl + b * 32 * LT);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) ah[g] = x3h_mma(a, x3h_pack(wh[g][2 * b], wh[g][2 * b + 1]), ah[g]);
+        }
+    } else {
+#pragma unroll
+      for (int b = 0; b < FB_H; ++b)
+        if (b < nbH) {
+          const float* ab = hl + b * 16 * LT;
+          const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
+#pragma unroll
+          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a0, wh[g][b][0], ah[g]);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a1, wh[g][b][1], ah[g]);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a2, wh[g][b][2], ah[g]);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a3, wh[g][b][3], ah[g]);
+        }
+    }
+  }
+  if constexpr (SEQ) {
+    __builtin_amdgcn_sched_barrier(0);
+    load_w1();   // (W now, LinearZeros once F1 has let W go: in flight under the recurrent product of F2)
+    if constexpr (WH_PER_FRAME) load_wz(per_frame(f.pwz));
+    if constexpr (NG == 4) load_gic(io.gic + n * sq->gic_step, n == 0);
+    if constexpr (X3) {
+#pragma unroll
+      for (int b = 0; b < FB_C / 2; ++b) w1x[b] = x3h_pack(w1[2 * b], w1[2 * b + 1]);
+    }
+  } else if constexpr (NG == 4) {
+    __builtin_amdgcn_sched_barrier(0);
+    load_frag<FB_C>(w1, f.pW + (long)k * C16 * C16, C16, tcol, kq, nbC, t1);
+    load_frag<FB_H>(w3, f.pwfl + (long)k * H16 * Co16, Co16, tcol, kq, nbH, t3);
+    load_gic(io.gic, true);
+  }
+  if (wait_flag && !pipe_acquire(wait_flag, SEQ ? (unsigned)(n + 1) : 1u, abort_w, tid, s_ok, false)) {
+    if constexpr (SEQ) {
+      const int row = b0 + ri;
+      if (nll_out && row < rows)
+        for (int m = n; m < frames; ++m) {
+          if (io.x_out)
+            for (int c = cl; c < C; c += 32) io.x_out[m * sq->x_out_step + (long)row * io.ldxo + c] = __builtin_nanf("");
+          if (cl == 0) nll_out[m * sq->row_step + row] = __builtin_nanf("");
+        }
+    }
+    return false;
+  }
+  const float* x_in = SEQ ? io.x_in + n * sq->x_in_step : io.x_in;
+  float* x_out = (SEQ && io.x_out) ? io.x_out + n * sq->x_out_step : io.x_out;
+  const long rstep = SEQ ? n * sq->row_step : 0;
+  // ---- F0: actnorm of the incoming tile (glow/modules.py:45-52), k-major with zero k padding
+  float q = 0.0f;   // lane cl == 0 carries its row's running coupling log-det
+  {
+    const int row = b0 + ri;
+    const bool rok = row < rows;
+    if (q_in && cl == 0 && rok) q = ld_tile(q_in + rstep + row, false);   // (in flight under the cell: needed in F4)
+#pragma unroll
+    for (int qq = 0; qq < 2; ++qq) {
+      const int c = cl + 32 * qq;
+      if (c < C16) {
+        const float v = (c < C && rok) ? ld_tile(x_in + (long)row * io.ldx + c, wait_flag == nullptr) : 0.0f;
+        At[c * LT + ri] = c < C ? (v + an_b[qq]) * an_s[qq] : 0.0f;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- F1: y = a W   (InvertibleConv1x1.forward, glow/modules.py:186); z1 = y[:, :Ch] is the recurrent cell's input
+  if (t1) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (X3) {
+      const float* al = At + kq * LT + l15;
+#pragma unroll
+      for (int b = 0; b < FB_C / 2; ++b)
+        if (b < (nbC >> 1)) acc = x3h_mma(x3h_a(al + b * 32 * LT), w1x[b], acc);
+    } else {
+      acc = mma16_reg<FB_C>(At + kq * LT + l15, w1, nbC);
+    }
+    if (tcol < C) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = kq * 4 + r;
+        Yrm[i * ldy + tcol] = acc[r];
+        if (tcol < Ch) Zt[tcol * LT + i] = acc[r];
+      }
+    }
+  }
+  if constexpr (SEQ) {
+    __builtin_amdgcn_sched_barrier(0);
+    load_w3();
+  }
+  __syncthreads();
+  // ---- F2: the z1 half of the recurrent product, then the gate math (h / c updated in place)
+  if (t2) {
+    const float* zl = Zt + kq * LT + l15;
+    if constexpr (X3) {
+#pragma unroll
+      for (int b = 0; b < FB_Z / 2; ++b)
+        if (b < (nbZ >> 1)) {
+          const X3FragH a = x3h_a(zl + b * 32 * LT);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) az[g] = x3h_mma(a, wzx[g][b], az[g]);
+        }
+    } else {
+#pragma unroll
+      for (int b = 0; b < FB_Z; ++b)
+        if (b < nbZ) {
+          const float* ab = zl + b * 16 * LT;
+          const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
+#pragma unroll
+          for (int g = 0; g < NG; ++g) az[g] = mfma16(a0, wz[g][b][0], az[g]);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) az[g] = mfma16(a1, wz[g][b][1], az[g]);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) az[g] = mfma16(a2, wz[g][b][2], az[g]);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) az[g] = mfma16(a3, wz[g][b][3], az[g]);
+        }
+    }
+    if constexpr (SEQ) {
+      fast_cell_p2_gates<NG, RM, false>(f, Ht, Hn, az, ah, gc, bh, cprev, tcol, kq, b0, rows, n == frames - 1 ? io.h_out : nullptr, nullptr,
+                                        nullptr, NG == 4 ? cnew : nullptr, nullptr, nullptr, 0, 0, live);
+      if (NG == 4 && n == frames - 1 && tcol < H) {   // the cell state crossed the frames in registers: stored once, as h
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = b0 + kq * 4 + r;
+          if (row < rows) io.c_out[(long)row * H + tcol] = cnew[r];
+        }
+      }
+    } else
+    fast_cell_p2_gates<NG, RM>(f, Ht, Hn, az, ah, gc, bh, cprev, tcol, kq, b0, rows, io.h_out, io.c_out, nullptr, nullptr, nullptr, nullptr,
+                               0, 0, live);
+  }
+  __syncthreads();
+  // ---- F3: o = (h' Wfl^T + b) exp(3 logs)   (LinearZeros, glow/modules.py:93-95)
+  if constexpr (SEQ && X3) {
+#pragma unroll
+    for (int b = 0; b < FB_H / 2; ++b) w3x[b] = x3h_pack(w3[2 * b], w3[2 * b + 1]);
+  }
+  if (t3) {
+    if constexpr (X3) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      const float* hl = Hn + kq * LT + l15;
+#pragma unroll
+      for (int b = 0; b < FB_H / 2; ++b)
+        if (b < (nbH >> 1)) acc = x3h_mma(x3h_a(hl + b * 32 * LT), w3x[b], acc);
+      if (tcol < Cout) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Orm[(kq * 4 + r) * ldo + tcol] = (acc[r] + flb) * fls;
+      }
+    } else {
+      fast_cell_p3(f, k, Hn, Orm, w3, nbH, tcol, kq, l15, b0, rows, nullptr, 0, flb, fls);
+    }
+  }
+  __syncthreads();
+  // ---- F4: coupling (glow/models.py:330-341), the pass-through half, the row's log-det; the last step: the prior term and the NLL
+  {
+    const int row = b0 + ri;
+    const bool rok = RM ? ((live >> ri) & 1u) != 0u : row < rows;
+    float lg = 0.0f, zz = 0.0f;
+    auto put = [&](int c, float v) {
+      if (!x_out || !rok) return;
+      if (pub_flag) st_sc1(x_out + (long)row * io.ldxo + c, v);
+      else x_out[(long)row * io.ldxo + c] = v;
+    };
+    if (cl < C2) {
+      const float z2 = Yrm[ri * ldy + Ch + cl];
+      float z2n;
+      if (f.affine) {
+        const float shift = Orm[ri * ldo + 2 * cl];
+        const float sraw = sigmoidf_(Orm[ri * ldo + 2 * cl + 1] + 2.0f);
+        const float sc = fmaxf(sraw, f.eps);
+        z2n = (z2 + shift) * sc;
+        lg = logf(sc);
+      } else {
+        z2n = z2 + Orm[ri * ldo + cl];
+      }
+      put(Ch + cl, z2n);
+      zz = z2n * z2n;
+    }
+    if (cl < Ch) {
+      const float z1 = Yrm[ri * ldy + cl];
+      put(cl, z1);
+      zz = __builtin_fmaf(z1, z1, zz);
+    }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) lg += __shfl_xor(lg, o, 64);   // the 32 lanes of one row
+    if (nll_out) {
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1) zz += __shfl_xor(zz, o, 64);
+    }
+    if (cl == 0 && rok) {
+      q += lg;
+      if (nll_out) nll_out[rstep + row] = -(q + f.ldconst[0] + -0.5f * (zz + (float)C * LOG2PI_F)) / LN2_F;
+      else st_sc1(q_out + rstep + row, q);
+    }
+  }
+  if (pub_flag) pipe_publish(pub_flag, SEQ ? (unsigned)(n + 1) : 1u, tid, true);
+  if constexpr (SEQ) {   // this frame's new state is the next frame's previous one
+    float* t = Ht; Ht = Hn; Hn = t;
+    if constexpr (NG == 4) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) cprev[r] = cnew[r];
+    }
+  }
+  }
+  return true;
+}
+
 
 }  // namespace

@@ -462,292 +462,7 @@ __global__ __launch_bounds__(NT) void flow_rev_chain_kernel(FlowK f, RevChain rc
 }
 
 // ------------------------------------------------------------------------------------------- forward chain (teacher-forced frame)
-// FlowStep.normal_flow (glow/models.py:311-341) of ONE observed frame with the recurrent state carried in place: the forward twin of
-// rev_fast_cell for a streaming session's observe() step. Same thread maps, same LDS carve, same place of the wait: the weights, gic,
-// h_prev and the h_prev W_hh half of the recurrent product run before it; behind it actnorm, y = a W, the z1 half + the gates,
-// LinearZeros and the coupling. The recurrent cell sees what the reverse cell of the same frame sees - z1 and the conditioning - so
-// the h / c it leaves is the state a sampler continues from. No stash of any kind.
-// X3: every product as three fp16 products of two-piece operands (x3h_*, fp32-grade: 2^-22 relative), the f32 fragment images split
-// in registers before the wait; otherwise the exact f32 MFMA. (The training walks' three bf16 products - 2^-16 pieces - are not used
-// here: the state must match the reverse cell's to the sampler's own tolerance.)
-// q_in: the rows' running coupling log-det from step k - 1 (null: this cell starts it); q_out: where it goes on to step k + 1, sc1
-// stores in front of the publish. nll_out (the last step): the cell adds the prior term of its z, sum_c -0.5 (z_c^2 + log 2 pi), and
-// logdet_const and writes -(logdet + log p(z)) / ln 2 in bits. One writer per word, k ascending: a fixed summation order.
-// io.x_out may be null (the last step of a caller that does not want z).
-// RM (flow_rows_chain_kernel): a row-masked cell, as rev_fast_cell's - h_out / c_out, the output tile, the hand-over q and the NLL word
-// are stored for the rows of role io.role_want only.
-template <int NG, bool X3, bool RM = false>
-__device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io, int b0, const unsigned* wait_flag, unsigned* abort_w,
-                                               unsigned* pub_flag, int* s_ok, const float* q_in, float* q_out, float* nll_out) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, kq = lane >> 4;
-  const int ri = tid >> 5, cl = tid & 31;
-  const int k = io.k, rows = io.rows;
-  const int C = f.C, H = f.H, Ch = f.Ch, C2 = f.C2, Cout = f.Cout, G = f.G;
-  const int C16 = f.C16, Ch16 = f.Ch16, H16 = f.H16, Co16 = f.Co16;
-  const CarveF cv = carve_fast_fwd(C, C16, H16, Ch16, Cout);
-  float* At = flow_smem + cv.At;
-  float* Ht = flow_smem + cv.Ht;
-  float* Zt = flow_smem + cv.Zt;
-  float* Hn = flow_smem + cv.Hn;
-  float* Yrm = flow_smem + cv.Yrm;
-  float* Orm = flow_smem + cv.Orm;
-  const int ldy = C + 1, ldo = Cout + 1;
-  const int nbC = C16 >> 4, nbZ = Ch16 >> 4, nbH = H16 >> 4;
-  const bool t1 = wave * 16 < C, t2 = wave * 16 < H, t3 = wave * 16 < Cout;
-  const int tcol = wave * 16 + l15;
-  unsigned live = 0u;
-  if constexpr (RM) live = tile_live_rows(io.role, io.role_want, b0, rows);
-  // ---- requests in the order their results are needed: h_prev (its LDS image gates the first barrier), the recurrent weights, then
-  // the weights of the phases behind the wait
-  const int hrow = b0 + ri;
-  float hv[FB_H / 2];
-#pragma unroll
-  for (int q = 0; q < FB_H / 2; ++q) {
-    const int j = cl + 32 * q;
-    hv[q] = (io.h_prev && hrow < rows && j < H) ? io.h_prev[(long)hrow * H + j] : 0.0f;
-  }
-  f32x4 wz[NG][FB_Z], wh[NG][FB_H], w3[FB_H], w1[FB_C];
-  {
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-#pragma unroll
-      for (int b = 0; b < FB_Z; ++b) wz[g][b] = zero4;
-#pragma unroll
-      for (int b = 0; b < FB_H; ++b) wh[g][b] = zero4;
-      load_frag<FB_H>(wh[g], f.pwh + (long)k * H16 * NG * H16, NG * H16, g * H16 + tcol, kq, nbH, t2);
-      load_frag<FB_Z>(wz[g], f.pwz + (long)k * Ch16 * NG * H16, NG * H16, g * H16 + tcol, kq, nbZ, t2);
-    }
-#pragma unroll
-    for (int b = 0; b < FB_H; ++b) w3[b] = zero4;
-#pragma unroll
-    for (int b = 0; b < FB_C; ++b) w1[b] = zero4;
-    // (the LSTM cell's four gate blocks of W_hh fill the register file: its W and LinearZeros fragments are requested once the h-side
-    // product has let those go - still in front of the wait; 24 VGPRs in scratch otherwise)
-    if constexpr (NG != 4) {
-      load_frag<FB_C>(w1, f.pW + (long)k * C16 * C16, C16, tcol, kq, nbC, t1);
-      load_frag<FB_H>(w3, f.pwfl + (long)k * H16 * Co16, Co16, tcol, kq, nbH, t3);
-    }
-  }
-  float gc[4][NG], bh[NG], cprev[4];
-  auto load_gic = [&]() {
-    const float* bhh = f.p.b_hh + (long)k * G;
-    const int jc = tcol < H ? tcol : 0;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) bh[g] = bhh[g * H + jc];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = min(b0 + kq * 4 + r, rows - 1);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) gc[r][g] = io.gic[(long)row * G + g * H + jc];
-      cprev[r] = (NG == 4 && io.c_prev) ? io.c_prev[(long)row * H + jc] : 0.0f;
-    }
-  };
-  if constexpr (NG != 4) load_gic();
-  // per-column constants of the phases behind the wait: ActNorm of this thread's two channels (cl, cl + 32), LinearZeros of its column
-  float an_b[2], an_s[2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int c = cl + 32 * q;
-    an_b[q] = c < C ? f.p.an_bias[(long)k * C + c] : 0.0f;
-    an_s[q] = c < C ? expf(f.p.an_logs[(long)k * C + c]) : 0.0f;
-  }
-  const float flb = tcol < Cout ? f.p.b_fl[(long)k * Cout + tcol] : 0.0f;
-  const float fls = tcol < Cout ? expf(3.0f * f.p.l_fl[(long)k * Cout + tcol]) : 0.0f;
-  // ---- before the wait: h_prev and the zero k padding into LDS, the fragment split, the h_prev W_hh half of the recurrent product
-#pragma unroll
-  for (int q = 0; q < FB_H / 2; ++q) {
-    const int j = cl + 32 * q;
-    if (j < H16) {
-      Ht[j * LT + ri] = hv[q];
-      if (j >= H) Hn[j * LT + ri] = 0.0f;
-    }
-  }
-  for (int c = Ch + cl; c < Ch16; c += 32) Zt[c * LT + ri] = 0.0f;
-  X3FragH wzx[X3 ? NG : 1][FB_Z / 2], w3x[X3 ? FB_H / 2 : 1], w1x[X3 ? FB_C / 2 : 1];
-  if constexpr (X3) {   // (instantiated for shapes with whole 32-k blocks everywhere: flow_x3h_images_ok)
-#pragma unroll
-    for (int b = 0; b < FB_H / 2; ++b) w3x[b] = x3h_pack(w3[2 * b], w3[2 * b + 1]);
-#pragma unroll
-    for (int b = 0; b < FB_C / 2; ++b) w1x[b] = x3h_pack(w1[2 * b], w1[2 * b + 1]);
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-      for (int b = 0; b < FB_Z / 2; ++b) wzx[g][b] = x3h_pack(wz[g][2 * b], wz[g][2 * b + 1]);
-  }
-  __syncthreads();
-  f32x4 az[NG], ah[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    az[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    ah[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-  if (t2) {
-    const float* hl = Ht + kq * LT + l15;
-    if constexpr (X3) {
-#pragma unroll
-      for (int b = 0; b < FB_H / 2; ++b)
-        if (b < (nbH >> 1)) {
-          const X3FragH a = x3h_a(hl + b * 32 * LT);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = x3h_mma(a, x3h_pack(wh[g][2 * b], wh[g][2 * b + 1]), ah[g]);
-        }
-    } else {
-#pragma unroll
-      for (int b = 0; b < FB_H; ++b)
-        if (b < nbH) {
-          const float* ab = hl + b * 16 * LT;
-          const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a0, wh[g][b][0], ah[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a1, wh[g][b][1], ah[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a2, wh[g][b][2], ah[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) ah[g] = mfma16(a3, wh[g][b][3], ah[g]);
-        }
-    }
-  }
-  if constexpr (NG == 4) {
-    __builtin_amdgcn_sched_barrier(0);
-    load_frag<FB_C>(w1, f.pW + (long)k * C16 * C16, C16, tcol, kq, nbC, t1);
-    load_frag<FB_H>(w3, f.pwfl + (long)k * H16 * Co16, Co16, tcol, kq, nbH, t3);
-    load_gic();
-  }
-  if (wait_flag && !pipe_acquire(wait_flag, 1u, abort_w, tid, s_ok, false)) return false;
-  // ---- F0: actnorm of the incoming tile (glow/modules.py:45-52), k-major with zero k padding
-  float q = 0.0f;   // lane cl == 0 carries its row's running coupling log-det
-  {
-    const int row = b0 + ri;
-    const bool rok = row < rows;
-    if (q_in && cl == 0 && rok) q = ld_tile(q_in + row, false);   // (in flight under the cell: needed in F4)
-#pragma unroll
-    for (int qq = 0; qq < 2; ++qq) {
-      const int c = cl + 32 * qq;
-      if (c < C16) {
-        const float v = (c < C && rok) ? ld_tile(io.x_in + (long)row * io.ldx + c, wait_flag == nullptr) : 0.0f;
-        At[c * LT + ri] = c < C ? (v + an_b[qq]) * an_s[qq] : 0.0f;
-      }
-    }
-  }
-  __syncthreads();
-  // ---- F1: y = a W   (InvertibleConv1x1.forward, glow/modules.py:186); z1 = y[:, :Ch] is the recurrent cell's input
-  if (t1) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (X3) {
-      const float* al = At + kq * LT + l15;
-#pragma unroll
-      for (int b = 0; b < FB_C / 2; ++b)
-        if (b < (nbC >> 1)) acc = x3h_mma(x3h_a(al + b * 32 * LT), w1x[b], acc);
-    } else {
-      acc = mma16_reg<FB_C>(At + kq * LT + l15, w1, nbC);
-    }
-    if (tcol < C) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = kq * 4 + r;
-        Yrm[i * ldy + tcol] = acc[r];
-        if (tcol < Ch) Zt[tcol * LT + i] = acc[r];
-      }
-    }
-  }
-  __syncthreads();
-  // ---- F2: the z1 half of the recurrent product, then the gate math (h / c updated in place)
-  if (t2) {
-    const float* zl = Zt + kq * LT + l15;
-    if constexpr (X3) {
-#pragma unroll
-      for (int b = 0; b < FB_Z / 2; ++b)
-        if (b < (nbZ >> 1)) {
-          const X3FragH a = x3h_a(zl + b * 32 * LT);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = x3h_mma(a, wzx[g][b], az[g]);
-        }
-    } else {
-#pragma unroll
-      for (int b = 0; b < FB_Z; ++b)
-        if (b < nbZ) {
-          const float* ab = zl + b * 16 * LT;
-          const float a0 = ab[0], a1 = ab[4 * LT], a2 = ab[8 * LT], a3 = ab[12 * LT];
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = mfma16(a0, wz[g][b][0], az[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = mfma16(a1, wz[g][b][1], az[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = mfma16(a2, wz[g][b][2], az[g]);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) az[g] = mfma16(a3, wz[g][b][3], az[g]);
-        }
-    }
-    fast_cell_p2_gates<NG, RM>(f, Ht, Hn, az, ah, gc, bh, cprev, tcol, kq, b0, rows, io.h_out, io.c_out, nullptr, nullptr, nullptr, nullptr,
-                               0, 0, live);
-  }
-  __syncthreads();
-  // ---- F3: o = (h' Wfl^T + b) exp(3 logs)   (LinearZeros, glow/modules.py:93-95)
-  if (t3) {
-    if constexpr (X3) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      const float* hl = Hn + kq * LT + l15;
-#pragma unroll
-      for (int b = 0; b < FB_H / 2; ++b)
-        if (b < (nbH >> 1)) acc = x3h_mma(x3h_a(hl + b * 32 * LT), w3x[b], acc);
-      if (tcol < Cout) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Orm[(kq * 4 + r) * ldo + tcol] = (acc[r] + flb) * fls;
-      }
-    } else {
-      fast_cell_p3(f, k, Hn, Orm, w3, nbH, tcol, kq, l15, b0, rows, nullptr, 0, flb, fls);
-    }
-  }
-  __syncthreads();
-  // ---- F4: coupling (glow/models.py:330-341), the pass-through half, the row's log-det; the last step: the prior term and the NLL
-  {
-    const int row = b0 + ri;
-    const bool rok = RM ? ((live >> ri) & 1u) != 0u : row < rows;
-    float lg = 0.0f, zz = 0.0f;
-    auto put = [&](int c, float v) {
-      if (!io.x_out || !rok) return;
-      if (pub_flag) st_sc1(io.x_out + (long)row * io.ldxo + c, v);
-      else io.x_out[(long)row * io.ldxo + c] = v;
-    };
-    if (cl < C2) {
-      const float z2 = Yrm[ri * ldy + Ch + cl];
-      float z2n;
-      if (f.affine) {
-        const float shift = Orm[ri * ldo + 2 * cl];
-        const float sraw = sigmoidf_(Orm[ri * ldo + 2 * cl + 1] + 2.0f);
-        const float sc = fmaxf(sraw, f.eps);
-        z2n = (z2 + shift) * sc;
-        lg = logf(sc);
-      } else {
-        z2n = z2 + Orm[ri * ldo + cl];
-      }
-      put(Ch + cl, z2n);
-      zz = z2n * z2n;
-    }
-    if (cl < Ch) {
-      const float z1 = Yrm[ri * ldy + cl];
-      put(cl, z1);
-      zz = __builtin_fmaf(z1, z1, zz);
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) lg += __shfl_xor(lg, o, 64);   // the 32 lanes of one row
-    if (nll_out) {
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) zz += __shfl_xor(zz, o, 64);
-    }
-    if (cl == 0 && rok) {
-      q += lg;
-      if (nll_out) nll_out[row] = -(q + f.ldconst[0] + -0.5f * (zz + (float)C * LOG2PI_F)) / LN2_F;
-      else st_sc1(q_out + row, q);
-    }
-  }
-  if (pub_flag) pipe_publish(pub_flag, 1u, tid, true);
-  return true;
-}
-
+// (the cell itself, fwd_chain_cell, is in lfi_flow_cells.h: lfi_flow_chunk.hip runs it too)
 // One OBSERVED frame of a streaming session (SampleStream.observe): all Ks forward flow steps of all batch tiles in ONE launch, the
 // forward twin of flow_rev_chain_kernel. Workgroup (k, tile) - ids by ticket, k ASCENDING, so a workgroup only waits on one that
 // already runs - requests its weights, its part of gic and its recurrent state, then waits for the tile of step k - 1 (the observed
@@ -953,7 +668,6 @@ FlowFwdChainKernel flow_fwd_chain_pick(bool lstm, bool x3) {
   if (lstm) return flow_fwd_chain_kernel<4, false>;
   return x3 ? flow_fwd_chain_kernel<3, true> : flow_fwd_chain_kernel<3, false>;
 }
-
 // the two chains' own rules side by side: the reverse cells' form as flow_rev_chain_pick has it (x3: fp16 pieces at precisions 9 and 5,
 // xw: from the fragment images), the forward cells' as flow_fwd_chain_pick has it (x3f: precision 9 only); the LSTM cell exact in both
 FlowRowsChainKernel flow_rows_chain_pick(bool lstm, bool x3, bool xw, bool x3f) {
@@ -1129,89 +843,90 @@ int sample_front_setup(SampleFront* s, const lfi_flow_dims* d, const lfi_flow_pa
   if (s->fused && nframes > 0) return lfi_internal_sample_cond_prepare(wct, E, s->p1col, s->K1, f->wc, Ks, G, s->cfrags, stream);
   return LFI_OK;
 }
-// frame t of the sequence in `faces`: gic of all flow steps from the frame's rows `cfr` of pre_static (B x Ks D, overwritten) and the
-// window faces[:, t - hist1 : t]. have_xfrag: the window's fp16 fragments are already in cfrags (the previous frame's reverse chain)
-int sample_front_frame(const SampleFront& s, int t, float* cfr, int have_xfrag, void* stream) {
-  const lfi_flow_dims* d = s.d;
-  const lfi_p1enc* p1 = s.p1;
-  const int B = s.f->B, C = s.f->C, D = s.f->D, Ks = s.f->Ks, G = s.f->G, hist1 = s.hist1, seq_len = s.seq_len;
+// The front end's products for M rows of windows - M = B: one frame; M = nframes * B, frame-major: a chunk of frames known up front.
+// win: row m's raw prev_p1_face window (hist1 * C floats, row pitch ldwin); cfr: the rows' pre_static (M x Ks D, overwritten with c);
+// gic: [Ks][M][G]; p1work: lfi_flow_sample_p1_work_floats for M rows (encoded kinds).
+// d, p, p1, wct, E, hist1: the sampler's; wc: the coupling cells' W_ih[:, Ch:] of all steps (FlowK.wc).
+}  // namespace
+extern "C" int lfi_internal_sample_front_rows(const lfi_flow_dims* d, const lfi_flow_params* p, const lfi_p1enc* p1, const float* wct, long E,
+                                              int hist1, const float* wc, int M, const float* win, long ldwin, float* cfr, float* gic,
+                                              float* p1work, void* stream) {
+  const int C = d->C, D = d->D, Ks = d->Ks, G = (d->lstm ? 4 : 3) * d->H;
+  const int p1kind = p1 ? p1->kind : 0, p1col = p1 ? p1->col : 0;
   int rc;
   // c = LeakyReLU(pre_static[n] + window @ Wct[:, :hist1*C]^T), IN PLACE: frame n's rows of pre_static are read by this product
   // alone, so they are its pre-activation addend and its output at once (a 32 MB copy per frame into a separate c otherwise)
   lfi_gemm_desc q = {};
-  q.batch = 1; q.M = B; q.N = Ks * D; q.K = hist1 * C;
-  q.A = s.faces + (long)(t - hist1) * C; q.lda = (long)seq_len * C; q.a_kcontig = 1;
-  q.B = s.wct + s.p1col; q.ldb = s.E; q.b_kcontig = 1;
+  q.batch = 1; q.M = M; q.N = Ks * D; q.K = hist1 * C;
+  q.A = win; q.lda = ldwin; q.a_kcontig = 1;
+  q.B = wct + p1col; q.ldb = E; q.b_kcontig = 1;
   q.C = cfr; q.ldc = (long)Ks * D; q.accumulate = 2; q.act = 1; q.slope = 0.01f; q.precision = d->gemm_precision;
-  if (s.p1kind != 0) {
-    // features of the window first: e (B x hid4), then c = LeakyReLU(pre_static + e Wct[:, col : col + hid]^T)
+  if (p1kind != 0) {
+    // features of the window first: e (M x hid4), then c = LeakyReLU(pre_static + e Wct[:, col : col + hid]^T)
     const int hid = p1->hid, hid4 = (hid + 3) & ~3;
-    float* ebuf = s.p1work;                       // B x hid4
-    if (s.p1kind == 1) {
+    float* ebuf = p1work;                         // M x hid4
+    if (p1kind == 1) {
       lfi_gemm_desc m = {};
-      m.batch = 1; m.M = B; m.N = hid; m.K = hist1 * C;
+      m.batch = 1; m.M = M; m.N = hid; m.K = hist1 * C;
       m.A = q.A; m.lda = q.lda; m.a_kcontig = 1;
       m.B = p1->w1; m.ldb = (long)hist1 * C; m.b_kcontig = 1;
       m.C = ebuf; m.ldc = hid4; m.bias = p1->b1; m.act = 1; m.slope = 0.01f; m.precision = d->gemm_precision;
       if ((rc = lfi_gemm_f32(&m, stream))) return rc;
     } else {
       // GRU / LSTM over the window: input projections of its hist1 frames (batched over the step), then the recurrence
-      const int ng = s.p1kind == 3 ? 4 : 3;
-      float* xp = ebuf + (long)B * hid4;          // [B][hist1][ng * hid]
-      float* ework = xp + (long)B * hist1 * ng * hid;
+      const int ng = p1kind == 3 ? 4 : 3;
+      float* xp = ebuf + (long)M * hid4;          // [M][hist1][ng * hid]
+      float* ework = xp + (long)M * hist1 * ng * hid;
       lfi_gemm_desc m = {};
-      m.batch = hist1; m.M = B; m.N = ng * hid; m.K = C;
+      m.batch = hist1; m.M = M; m.N = ng * hid; m.K = C;
       m.A = q.A; m.lda = q.lda; m.a_kcontig = 1; m.strideA = C;
       m.B = p1->w_ih; m.ldb = C; m.b_kcontig = 1;
       m.C = xp; m.ldc = (long)hist1 * ng * hid; m.strideC = ng * hid; m.precision = d->gemm_precision;
       if ((rc = lfi_gemm_f32(&m, stream))) return rc;
       lfi_enc_desc ed = {};
-      ed.B = B; ed.T = hist1; ed.N = 1; ed.start = hist1 - 1; ed.hist = hist1; ed.hid = hid;
-      ed.ldcond = hid4; ed.col = 0; ed.precision = d->gemm_precision; ed.dup = 0; ed.lstm = s.p1kind == 3;
+      ed.B = M; ed.T = hist1; ed.N = 1; ed.start = hist1 - 1; ed.hist = hist1; ed.hid = hid;
+      ed.ldcond = hid4; ed.col = 0; ed.precision = d->gemm_precision; ed.dup = 0; ed.lstm = p1kind == 3;
       float* hs = ework + lfi_encode_windows_work_floats(&ed);   // unfused path / LSTM: state sequence
-      float* gst = s.p1kind == 3 ? hs + (long)hist1 * B * hid : nullptr;   // LSTM: gate + cell stash, 5 * hid per (step, row)
+      float* gst = p1kind == 3 ? hs + (long)hist1 * M * hid : nullptr;   // LSTM: gate + cell stash, 5 * hid per (step, row)
       if ((rc = lfi_encode_windows_fwd(&ed, xp, p1->w_hh, p1->b_ih, p1->b_hh, nullptr, ebuf, gst, hs, ework, stream)))
         return rc;
     }
     q.K = hid; q.A = ebuf; q.lda = hid4;
   }
+  if ((rc = lfi_gemm_f32(&q, stream))) return rc;
+  // gic[k] = c[:, kD:(k+1)D] @ W_ih[k][:, Ch:]^T + b_ih[k]
+  lfi_gemm_desc r = {};
+  r.batch = Ks; r.M = M; r.N = G; r.K = D;
+  r.A = cfr; r.lda = (long)Ks * D; r.a_kcontig = 1; r.strideA = D;
+  r.B = wc; r.ldb = D; r.b_kcontig = 1; r.strideB = (long)G * D;
+  r.C = gic; r.ldc = G; r.strideC = (long)M * G;
+  r.bias = p->b_ih; r.strideBias = G; r.precision = d->gemm_precision;
+  return lfi_gemm_f32(&r, stream);
+}
+namespace {
+// frame t of the sequence in `faces`: gic of all flow steps from the frame's rows `cfr` of pre_static (B x Ks D, overwritten) and the
+// window faces[:, t - hist1 : t]. have_xfrag: the window's fp16 fragments are already in cfrags (the previous frame's reverse chain)
+int sample_front_frame(const SampleFront& s, int t, float* cfr, int have_xfrag, void* stream) {
+  const int B = s.f->B, C = s.f->C, Ks = s.f->Ks, G = s.f->G, hist1 = s.hist1, seq_len = s.seq_len;
   if (s.fused) {
     // (its first workgroup also clears the chain's ticket / progress words for the launch that follows: no memset node per frame)
     return lfi_internal_sample_cond(s.faces, (long)seq_len * C, (long)(t - hist1) * C, s.K1, B, Ks, G, cfr, s.p->b_ih, s.cfrags, s.gic, 0.01f,
                                     (long)B * seq_len * C, s.chain ? s.chain_state : nullptr, (int)s.chain_words, have_xfrag, stream);
   }
+  const float* win = s.faces + (long)(t - hist1) * C;
+  long ldwin = (long)seq_len * C;
   if (s.stage_win) {
+    int rc;
     if ((rc = lfi_gather_windows(s.faces, B, seq_len, C, 1, t, hist1, 0, nullptr, s.wstage, s.ldw, 0, stream))) return rc;
-    q.A = s.wstage; q.lda = s.ldw;
+    win = s.wstage; ldwin = s.ldw;
   }
-  if ((rc = lfi_gemm_f32(&q, stream))) return rc;
-  // gic[k] = c[:, kD:(k+1)D] @ W_ih[k][:, Ch:]^T + b_ih[k]
-  lfi_gemm_desc r = {};
-  r.batch = Ks; r.M = B; r.N = G; r.K = D;
-  r.A = cfr; r.lda = (long)Ks * D; r.a_kcontig = 1; r.strideA = D;
-  r.B = s.f->wc; r.ldb = D; r.b_kcontig = 1; r.strideB = (long)G * D;
-  r.C = s.gic; r.ldc = G; r.strideC = (long)B * G;
-  r.bias = s.p->b_ih; r.strideBias = G; r.precision = d->gemm_precision;
-  return lfi_gemm_f32(&r, stream);
+  return lfi_internal_sample_front_rows(s.d, s.p, s.p1, s.wct, s.E, hist1, s.f->wc, B, win, ldwin, cfr, s.gic, s.p1work, stream);
 }
 // the chain's ticket / progress words before a frame's launch, unless the fused conditioning kernel has cleared them
 int sample_front_clear_chain(const SampleFront& s, hipStream_t st, const char* who) {
   if (s.fused) return LFI_OK;
   hipError_t me = hipMemsetAsync(s.chain_state, 0, s.chain_words * sizeof(unsigned), st);
   LFI_REQUIRE(me == hipSuccess, "%s: hipMemsetAsync: %s", who, hipGetErrorString(me));
-  return LFI_OK;
-}
-
-// What lfi_flow_sample_seq_nll, lfi_flow_score_seq_from and lfi_flow_step_rows_from ask of the arguments they share, in one order.
-// who_from: the name first_frame is reported under (the sampler's is its _from entry point); ptrs_ok: the caller's own list of
-// pointers that must not be null. A rule on the frame count itself is the caller's and follows this check.
-int frame_args_check(const char* who, const char* who_from, const lfi_flow_dims* d, bool ptrs_ok, long E, int hist1, int start,
-                     int nframes, int seq_len, const float* cstate, int first_frame) {
-  LFI_REQUIRE(first_frame >= 0, "%s: negative first_frame", who_from);
-  LFI_REQUIRE(ptrs_ok, "%s: null pointer", who);
-  LFI_REQUIRE(hist1 >= 0 && hist1 <= start && start + nframes <= seq_len, "%s: bad frame range", who);
-  LFI_REQUIRE((long)hist1 * d->C <= E, "%s: window wider than the feature vector", who);
-  LFI_REQUIRE(!d->lstm || cstate, "%s: the LSTM cell needs cstate", who);
   return LFI_OK;
 }
 

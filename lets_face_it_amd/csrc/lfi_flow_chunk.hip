@@ -1,0 +1,147 @@
+// A chunk of teacher-forced frames of a streaming session per call (SampleStream.observe_many): the forward chain's cell
+// (fwd_chain_cell, lfi_flow_cells.h) with the loop over the frames inside the chain, and its entry points. A unit of its own: the
+// reverse chains and the reverse walk of lfi_flow_chain.hip compile to the instructions they had without it (in one unit with
+// them, these kernels changed the inliner's choices inside the LSTM cells there).
+#include "lfi_flow_cells.h"
+
+namespace {
+
+// A CHUNK of observed frames of a streaming session (SampleStream.observe_many): flow_fwd_chain_kernel with the loop over the frames
+// INSIDE the chain - the systolic schedule of the training walk (nframes + Ks - 1 cell times end to end, where one launch per frame
+// runs nframes * Ks) on the streaming cell, from a carried state and with no stash. Workgroup (k, tile), ids by ticket, k ascending,
+// runs fwd_chain_cell<.., SEQ> over all frames of its tile. It waits only on (k - 1, tile), a lower ticket, and the hand-over slots
+// are per (step boundary, frame), never reused inside a launch: there is no back-pressure, so no wait on a higher ticket, and any
+// number of resident workgroups makes progress. The caller bounds the slots by the frames it gives one launch.
+struct FwdSeqChain {
+  const float* frame0; long ld_frame;   // the chunk's first frame in the faces sequence (row stride seq_len * C); frame n: + n * C
+  int nframes;
+  float* tiles;           // [Ks - 1][nframes][B][C]: what step k hands to step k + 1
+  float* q;               // [Ks - 1][nframes][B]: the rows' running log-det beside it
+  const float* gic;       // [Ks][nframes][B][G]
+  float *h, *cstate;      // [Ks][B][H] recurrent state: read at the first frame, written at the last
+  int has_prev;           // 0: the chunk starts a sequence (zero state)
+  unsigned* pipe;         // ticket, abort, progress words (frames published per (k, tile)); zeroed before the launch
+  float* z;               // [nframes][B][C] or null
+  float* nll;             // [nframes][B]
+};
+template <int NG, bool X3>
+__global__ __launch_bounds__(NT) void flow_fwd_seq_chain_kernel(FlowK f, FwdSeqChain sc) {
+  __shared__ int s_id, s_ok;
+  if (threadIdx.x == 0) s_id = (int)atomicAdd(sc.pipe, 1u);
+  __syncthreads();
+  const int nbt = f.nbt;
+  const int k = s_id / nbt, bt = s_id - k * nbt;
+  if (k >= f.Ks) return;
+  const bool last = k == f.Ks - 1;
+  const long FB = (long)sc.nframes * f.B;
+  unsigned* prog = sc.pipe + PIPE_HDR;
+  CellIO io = {};
+  FwdSeq sq = {};
+  sq.frames = sc.nframes; sq.gic_step = (long)f.B * f.G; sq.row_step = f.B; sq.x_out_step = (long)f.B * f.C;
+  io.k = k; io.rows = f.B;
+  if (k == 0) { io.x_in = sc.frame0; io.ldx = sc.ld_frame; sq.x_in_step = f.C; }
+  else { io.x_in = sc.tiles + (long)(k - 1) * FB * f.C; io.ldx = f.C; sq.x_in_step = (long)f.B * f.C; }
+  io.x_out = last ? sc.z : sc.tiles + (long)k * FB * f.C; io.ldxo = f.C;
+  io.h_prev = sc.has_prev ? sc.h + (long)k * f.B * f.H : nullptr;
+  io.h_out = sc.h + (long)k * f.B * f.H;
+  if (NG == 4) { io.c_prev = sc.has_prev ? sc.cstate + (long)k * f.B * f.H : nullptr; io.c_out = sc.cstate + (long)k * f.B * f.H; }
+  io.gic = sc.gic + (long)k * FB * f.G;
+  fwd_chain_cell<NG, X3, false, true>(f, io, bt * MB, k > 0 ? prog + (k - 1) * nbt + bt : nullptr, sc.pipe + 1,
+                                      last ? nullptr : prog + k * nbt + bt, &s_ok, k > 0 ? sc.q + (long)(k - 1) * FB : nullptr,
+                                      last ? nullptr : sc.q + (long)k * FB, last ? sc.nll : nullptr, &sq);
+}
+
+typedef void (*FlowFwdSeqChainKernel)(FlowK, FwdSeqChain);
+FlowFwdSeqChainKernel flow_fwd_seq_chain_pick(bool lstm, bool x3) {
+  if (lstm) return flow_fwd_seq_chain_kernel<4, false>;
+  return x3 ? flow_fwd_seq_chain_kernel<3, true> : flow_fwd_seq_chain_kernel<3, false>;
+}
+
+}  // namespace
+
+// ---- a chunk of teacher-forced frames known up front (SampleStream.observe_many): the front end once, the chain as ONE launch
+namespace {
+// the carve of a chunk work area for F = nframes * B rows, in floats from its 16-byte aligned start
+struct ChunkCarve {
+  long p1work, wstage, gic, tiles, q, pipe, pipe_words, total;
+  int ldw;
+};
+ChunkCarve chunk_carve(const lfi_flow_dims* d, const lfi_p1enc* p1, int hist1, int nframes) {
+  const long F = (long)nframes * d->B, G = (long)(d->lstm ? 4 : 3) * d->H, nbt = (d->B + MB - 1) / MB;
+  auto up4 = [](long v) { return (v + 3) & ~3L; };
+  lfi_flow_dims dm = *d;
+  dm.B = (int)F;
+  ChunkCarve c = {};
+  c.ldw = (int)up4((long)hist1 * d->C);
+  long o = 0;
+  c.p1work = o; o += up4(lfi_flow_sample_p1_work_floats(&dm, p1, hist1));
+  c.wstage = o; o += F * c.ldw;
+  c.gic = o; o += up4((long)d->Ks * F * G);
+  c.tiles = o; o += up4((long)(d->Ks - 1) * F * d->C);
+  c.q = o; o += up4((long)(d->Ks - 1) * F);
+  c.pipe = o; c.pipe_words = up4((long)PIPE_HDR + (long)d->Ks * nbt); o += c.pipe_words;
+  c.total = o;
+  return c;
+}
+}  // namespace
+
+extern "C" int lfi_flow_score_chunk_ok(const lfi_flow_dims* d) {
+  if (!d) return 0;
+  const int Cout = d->affine ? 2 * (d->C - d->C / 2) : d->C - d->C / 2;
+  return (flow_fast_ok(d->C, d->H, Cout) && !flow_force_generic() && lfi_env_on("LFI_SAMPLE_CHAIN")) ? 1 : 0;
+}
+
+extern "C" long lfi_flow_score_chunk_work_floats(const lfi_flow_dims* d, const lfi_p1enc* p1, int hist1) {
+  if (!d || d->B <= 0 || d->N <= 0 || d->Ks <= 0 || hist1 < 0) return 0;
+  return chunk_carve(d, p1, hist1, d->N).total + 4;   // (+ the slack of the 16-byte alignment)
+}
+
+extern "C" int lfi_flow_score_seq_chunk(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct, long E,
+                                        int hist1, float* pre_static, float* faces, int seq_len, int start, int nframes, int first_frame,
+                                        float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work, float* chunk_work,
+                                        float* z, float* nll, void* stream) {
+  FlowK f = {};
+  const char* who = "lfi_flow_score_seq_chunk";
+  int rc = fill_flow(d, p, prep, &f, who);
+  if (rc) return rc;
+  if ((rc = frame_args_check(who, who, d, prep && wct && pre_static && faces && h && chunk_work && nll, E, hist1, start, nframes, seq_len,
+                             cstate, first_frame))) return rc;
+  LFI_REQUIRE(nframes >= 1 && nframes <= d->N, "%s: %d frames, the work area holds d->N = %d", who, nframes, d->N);
+  LFI_REQUIRE(hist1 >= 1, "%s: bad frame range (hist1 %d)", who, hist1);
+  LFI_REQUIRE((long)nframes * f.B < (1L << 24), "%s: %d frames x batch %d: too many rows for one launch", who, nframes, f.B);
+  LFI_REQUIRE(lfi_flow_score_chunk_ok(d), "%s: C, Cout <= 64 and hidden_channels <= 128 only, LFI_SAMPLE_CHAIN not 0 "
+              "(lfi_flow_score_chunk_ok); otherwise lfi_flow_score_seq_from", who);
+  const int B = f.B, C = f.C, Ks = f.Ks;
+  const long F = (long)nframes * B;
+  hipStream_t st = (hipStream_t)stream;
+  const int p1kind = p1 ? p1->kind : 0;
+  LFI_REQUIRE(p1kind >= 0 && p1kind <= 3, "%s: bad p1_face encoder kind %d", who, p1kind);
+  LFI_REQUIRE(p1kind == 0 || p1->hid > 0, "%s: encoded p1_face window with hid %d", who, p1->hid);
+  const ChunkCarve cv = chunk_carve(d, p1, hist1, nframes);
+  float* base = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(chunk_work) + 15) & ~(uintptr_t)15);
+  unsigned* pipe = reinterpret_cast<unsigned*>(base + cv.pipe);
+  const bool x3 = flow_x3_rev_cell(d, f) && (d->gemm_precision & 0xff) == 9;   // lfi_flow_score_seq_from's rule
+  const size_t lds = (size_t)carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total * sizeof(float);
+  const FlowFwdSeqChainKernel chain_kernel = flow_fwd_seq_chain_pick(f.lstm, x3);
+  if ((rc = set_flow_lds(chain_kernel, lds, who))) return rc;
+  // front end, once: the windows of all frames (row n * B + b: frames [start + n - hist1, start + n) of sample b), then the products
+  // (diagnostics, tools/stream_latency.py: LFI_CHUNK_ONLY=front / chain launches one of the two parts alone, so that events around the
+  // call time it - the chain then reads the gic an earlier whole call left in the work area. Results are not meaningful.)
+  const char* only = getenv("LFI_CHUNK_ONLY");
+  const bool run_front = !(only && only[0] == 'c'), run_chain = !(only && only[0] == 'f');
+  if (run_front) {
+    if ((rc = lfi_gather_windows(faces, B, seq_len, C, nframes, start, hist1, 0, nullptr, base + cv.wstage, cv.ldw, 0, stream))) return rc;
+    if ((rc = lfi_internal_sample_front_rows(d, p, p1, wct, E, hist1, f.wc, (int)F, base + cv.wstage, cv.ldw, pre_static, base + cv.gic,
+                                             base + cv.p1work, stream))) return rc;
+  }
+  if (!run_chain) return LFI_OK;
+  hipError_t me = hipMemsetAsync(pipe, 0, (size_t)cv.pipe_words * sizeof(unsigned), st);
+  LFI_REQUIRE(me == hipSuccess, "%s: hipMemsetAsync: %s", who, hipGetErrorString(me));
+  FwdSeqChain sc = {};
+  sc.frame0 = faces + (long)start * C; sc.ld_frame = (long)seq_len * C; sc.nframes = nframes;
+  sc.tiles = base + cv.tiles; sc.q = base + cv.q; sc.gic = base + cv.gic;
+  sc.h = h; sc.cstate = cstate; sc.has_prev = first_frame > 0 ? 1 : 0; sc.pipe = pipe; sc.z = z; sc.nll = nll;
+  hipLaunchKernelGGL(chain_kernel, dim3(Ks * f.nbt), dim3(NT), lds, st, f, sc);
+  LFI_LAUNCH_CHECK(who);
+  return LFI_OK;
+}

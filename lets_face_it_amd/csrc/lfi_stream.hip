@@ -122,6 +122,63 @@ __global__ __launch_bounds__(256) void stream_advance_rows_kernel(StreamWins w, 
   if ((threadIdx.x & 63) == 0 && m) atomicMax(guard, m);
 }
 
+// ---- a chunk of n observed frames per call (SampleStream.observe_many): the windows as sequences, and back
+//
+// In: workgroup (i, b) lays window i of batch row b out as the sequence the sequence mode of the feature builder and the chain take,
+// seq[i] (B x (start + n) x dim): the window's live frames (all hist of a conditioning window; rows 1 .. hist - 1 of the prev_p1_face
+// window, lead = 1) end at frame start - 1, the caller's n new frames follow from frame `start`. Frames in front of the window are
+// never read by anybody and never written here. max |v| of the NEW values goes into the guard word, as stream_advance_kernel's.
+struct StreamChunk {
+  float* win[kStreamMaxWins];        // B x hist x dim, row b at b * hist * dim
+  const float* src[kStreamMaxWins];  // B x n x dim: the chunk's frames (chunk_in only)
+  float* seq[kStreamMaxWins];        // B x (start + n) x dim
+  int hist[kStreamMaxWins];
+  int dim[kStreamMaxWins];
+  int lead[kStreamMaxWins];
+  int count;
+};
+
+__global__ __launch_bounds__(256) void stream_chunk_in_kernel(StreamChunk w, int n, int start, unsigned* __restrict__ guard) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x;
+  const int dim = w.dim[i];
+  const long live = (long)(w.hist[i] - w.lead[i]) * dim, fresh = (long)n * dim;
+  const float* win = w.win[i] + ((long)b * w.hist[i] + w.lead[i]) * dim;
+  const float* src = w.src[i] + (long)b * fresh;
+  float* seq = w.seq[i] + (long)b * (start + n) * dim + (long)start * dim;
+  for (long j = threadIdx.x; j < live; j += 256) seq[j - live] = win[j];
+  unsigned m = 0u;
+  for (long j = threadIdx.x; j < fresh; j += 256) {
+    const float v = src[j];
+    seq[j] = v;
+    const unsigned a = stream_abs_bits(v);
+    m = a > m ? a : m;
+  }
+  if (!guard) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
+    m = t > m ? t : m;
+  }
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(guard, m);
+}
+
+// Out: workgroup (i, b) takes the last hist frames of seq[i] back into window i of batch row b - right for n below, at and above hist.
+// The prev_p1_face window's hist counts its leading row, which so receives the frame in front of the last hist - 1: what n one-frame
+// advances leave there. Workgroup (count, b): the row's frame counter += 2 n.
+__global__ __launch_bounds__(256) void stream_chunk_out_kernel(StreamChunk w, int n, int start, float* __restrict__ frame_nb) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x;
+  if (i == w.count) {
+    if (frame_nb && threadIdx.x == 0) frame_nb[b] += 2.0f * (float)n;
+    return;
+  }
+  const long tot = (long)w.hist[i] * w.dim[i];
+  float* win = w.win[i] + (long)b * tot;
+  const float* seq = w.seq[i] + ((long)(b + 1) * (start + n)) * w.dim[i] - tot;
+  for (long j = threadIdx.x; j < tot; j += 256) win[j] = seq[j];
+}
+
 // ---- per-row reseed (SampleStream.reset_rows): the state open_stream / reset() give a row, for a listed subset of rows
 //
 // Rows are passed by value in the kernel argument block (StreamReset.rows), at most kResetMaxRows per launch: no staging copy and no
@@ -451,5 +508,49 @@ extern "C" int lfi_stream_load_rows(int B, int nrows, const int* rows, const int
                        const_cast<float*>(in), ld_in, guard_bits);
     LFI_LAUNCH_CHECK("lfi_stream_load_rows");
   }
+  return LFI_OK;
+}
+
+namespace {
+int stream_chunk_args(const char* what, int B, int n, int start, int count, float* const* win, float* const* seq, const int* hist,
+                      const int* dim, const int* lead, StreamChunk* w) {
+  LFI_REQUIRE(B > 0 && B <= 65535, "%s: batch %d (1 .. 65535)", what, B);
+  LFI_REQUIRE(n >= 1 && start >= 0 && (long)start + n < (1L << 30), "%s: %d frames from frame %d", what, n, start);
+  LFI_REQUIRE(count >= 1 && count <= kStreamMaxWins, "%s: %d windows (1 .. %d)", what, count, kStreamMaxWins);
+  LFI_REQUIRE(win && seq && hist && dim && lead, "%s: null pointer (window table)", what);
+  for (int i = 0; i < count; ++i) {
+    LFI_REQUIRE(win[i] && seq[i], "%s: null pointer (window %d)", what, i);
+    LFI_REQUIRE(hist[i] > 0 && dim[i] > 0 && (lead[i] == 0 || lead[i] == 1) && hist[i] - lead[i] <= start,
+                "%s: window %d: hist %d, dim %d, lead %d, start %d", what, i, hist[i], dim[i], lead[i], start);
+    w->win[i] = win[i]; w->seq[i] = seq[i]; w->hist[i] = hist[i]; w->dim[i] = dim[i]; w->lead[i] = lead[i];
+  }
+  w->count = count;
+  return LFI_OK;
+}
+}  // namespace
+
+extern "C" int lfi_stream_chunk_in(int B, int n, int start, int count, float* const* win, const float* const* src, float* const* seq,
+                                   const int* hist, const int* dim, const int* lead, unsigned* guard_bits, void* stream) {
+  StreamChunk w = {};
+  const int rc = stream_chunk_args("lfi_stream_chunk_in", B, n, start, count, win, seq, hist, dim, lead, &w);
+  if (rc != LFI_OK) return rc;
+  LFI_REQUIRE(src, "lfi_stream_chunk_in: null pointer (source table)");
+  for (int i = 0; i < count; ++i) {
+    LFI_REQUIRE(src[i], "lfi_stream_chunk_in: null pointer (source %d)", i);
+    w.src[i] = src[i];
+  }
+  hipLaunchKernelGGL(stream_chunk_in_kernel, dim3(count, B), dim3(256), 0, (hipStream_t)stream, w, n, start, guard_bits);
+  LFI_LAUNCH_CHECK("lfi_stream_chunk_in");
+  return LFI_OK;
+}
+
+extern "C" int lfi_stream_chunk_out(int B, int n, int start, int count, float* const* win, float* const* seq, const int* hist,
+                                    const int* dim, const int* lead, float* frame_nb, void* stream) {
+  StreamChunk w = {};
+  const int rc = stream_chunk_args("lfi_stream_chunk_out", B, n, start, count, win, seq, hist, dim, lead, &w);
+  if (rc != LFI_OK) return rc;
+  // (hist - lead <= start and n >= 1: the last hist frames of a sequence lie inside what chunk_in wrote)
+  hipLaunchKernelGGL(stream_chunk_out_kernel, dim3(count + 1, B), dim3(256), 0, (hipStream_t)stream, w, n, start, frame_nb);
+  LFI_LAUNCH_CHECK("lfi_stream_chunk_out");
   return LFI_OK;
 }

@@ -703,11 +703,13 @@ class GlowEngine:
                              % (name, B, Tmin, dim, tuple(x.shape), x.dtype, x.device))
 
     def build_features(self, data, faces, B, T, masks, cond, with_stash, skip_p1=False, sampling=False, windows=False, frame0=0,
-                       side=None):
+                       side=None, frame_nb_offset=None):
         """FeatureEncoder.forward for every timestep at once (models.py:127-145): fills cond (F x ldf, folded layout).
 
         windows=True: `data` holds ONE conditioning window per modality, (B, hist, dim) each, as create_conditioning
-        cuts them (models.py:598-615), and `data["frame_nb"]` the counter itself: one timestep, N = 1."""
+        cuts them (models.py:598-615), and `data["frame_nb"]` the counter itself: one timestep, N = 1.
+        frame_nb_offset (not sampling): what is added to `data["frame_nb"]` for the first timestep instead of 2 * start - a streaming
+        session's chunk of frames counts on from its own per-row counter (SampleStream.observe_many: 2)."""
         s = self.spec
         N = 1 if windows else T - s.start
         F = N * B
@@ -724,9 +726,11 @@ class GlowEngine:
         gather_side = side is not None and os.environ.get("LFI_ENC_GATHER_ON_SIDE", "1") != "0"
         for e in s.encoders:
             with (self._on(side) if (e is small or (gather_side and e.enc == "none")) else contextlib.nullcontext()):
-                self._build_feature(e, data, faces, B, T, N, F, masks, cond, with_stash, skip_p1, sampling, windows, frame0)
+                self._build_feature(e, data, faces, B, T, N, F, masks, cond, with_stash, skip_p1, sampling, windows, frame0,
+                                    frame_nb_offset)
 
-    def _build_feature(self, e, data, faces, B, T, N, F, masks, cond, with_stash, skip_p1, sampling, windows, frame0):
+    def _build_feature(self, e, data, faces, B, T, N, F, masks, cond, with_stash, skip_p1, sampling, windows, frame0,
+                       frame_nb_offset=None):
         s = self.spec
         st = _stream()
         p1 = e.name == "p1_face"
@@ -745,8 +749,10 @@ class GlowEngine:
                                      % (tuple(base.shape), base.dtype, base.device))
                 base = base.contiguous()
             # (frame0: a run of sampled frames that starts frame0 frames into its sequence, see sample())
-            check(self.L.lfi_fill_frame_nb(ptr(base), 2.0 * frame0 if sampling else (0.0 if windows else 2.0 * s.start), B, N,
-                                           cond.data_ptr(), s.ldf, e.fcol, st), "lfi_fill_frame_nb")
+            offset = 2.0 * frame0 if sampling else (0.0 if windows else 2.0 * s.start)
+            if frame_nb_offset is not None and not sampling:
+                offset = float(frame_nb_offset)
+            check(self.L.lfi_fill_frame_nb(ptr(base), offset, B, N, cond.data_ptr(), s.ldf, e.fcol, st), "lfi_fill_frame_nb")
             return
         # prev_p1_face is the window [t - hist, t) of the model's own output (models.py:601-603); every other modality
         # (t - hist, t] of its input stream (:607-610): same kernels, window end shifted by one frame

@@ -569,7 +569,12 @@ class SeqGlow(nn.Module):
         (forward and reverse flow steps feed the recurrent cell the same input), so step() and observe() alternate freely, with
         return_nll on or off: warm a session up on real history before generating, score faces live, hand over in both directions;
         warm-up beside a batched server: observe in a small session, save_rows, load_rows into the serving one. `steps` counts
-        both kinds of step."""
+        both kinds of step.
+
+        observe_many(frames, faces, return_z=False) is n observe() steps in one call for frames known up front (recorded history,
+        a clip to score): frames {modality: (B, n, dim)}, faces (B, n, C) -> nll (n, B), or (nll, z) with z (n, B, C). It leaves
+        the session where n observe() calls leave it (steps += n), with the conditioning front end run once for the chunk and the
+        flow steps as one launch that loops over the frames; eager launches, no graph."""
         _engine.check_return_nll(return_nll)
         p1 = seed.get("p1_face") if isinstance(seed, dict) else None
         if p1 is None:

@@ -154,6 +154,7 @@ class SampleStream:
         self._rows_graphs = {}                                       # step_rows()'s own, by key
         self.score_work = self.obs_z = self.obs_nll = None   # observe()'s buffers: allocated at the first observe
         self.role = self.rows_work = self.rows_nll = self.rows_nll_work = None   # step_rows()'s: at the first step_rows
+        self._chunk_ws = {}                     # observe_many()'s workspaces, sized by the chunk (the graphs never address them)
         self._stream = None
         self._guard_pending = None
         self._state = {"_ws": {}, "prep": None, "wct_f": torch.zeros_like(eng.wct_f), "_wct_planes": None, "_wc_r": None,
@@ -366,7 +367,7 @@ class SampleStream:
             self._stream.synchronize()
         self.closed = True
         self._graph, self._observe_graphs, self._rows_graphs = None, {}, {}
-        self._state = None
+        self._state = self._chunk_ws = None
         self.faces = self.noise = self.windows = self.cond = self.pre = self.h = self.cs = self.work = self.p1work = self._wins = None
         self.nll = self.nll_work = self.score_work = self.obs_z = self.obs_nll = None
         self.role = self.rows_work = self.rows_nll = self.rows_nll_work = None
@@ -445,6 +446,162 @@ class SampleStream:
             self.steps += 1
         self._record_out(nll, z)
         return (nll, z) if return_z else nll
+
+    def _check_chunk(self, x, name, cols, n=None):
+        """A chunk's frames of one modality, (B, n, cols) with n >= 1 (None: whatever it has) -> n. The wording of _check_matrix."""
+        ok = (torch.is_tensor(x) and x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.is_contiguous()
+              and x.dim() == 3 and x.shape[0] == self.B and x.shape[1] >= 1 and x.shape[2] == cols)
+        if not ok or (n is not None and x.shape[1] != n):
+            raise ValueError("%s: expected contiguous float32 GPU tensor (B=%d, %s, %d) on %s, got %s %s on %s"
+                             % (name, self.B, "n>=1" if n is None else "n=%d" % n, cols, self.device,
+                                tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x)), getattr(x, "device", None)))
+        return int(x.shape[1])
+
+    def _chunk_cap(self):
+        """Frames one launch of the chunk chain takes: its hand-over slots are per frame and never reused inside a launch, and the
+        front end's operands (pre-activations, gic, features) grow with the frames too, so a long chunk runs as several calls with
+        the state carried. As many as fit 64 Mi floats of them, between 8 and 256; LFI_OBSERVE_CHUNK_FRAMES overrides (tests: 3)."""
+        env = os.environ.get("LFI_OBSERVE_CHUNK_FRAMES")
+        if env:
+            cap = int(env)
+            if cap < 1:
+                raise ValueError("LFI_OBSERVE_CHUNK_FRAMES: %r is not a frame count" % env)
+            return cap
+        s = self.eng.spec
+        G = (4 if s.rnn_type == "lstm" else 3) * s.H
+        per_frame = self.B * (s.Ks * (s.D + G + s.C + 1) + s.ldf)
+        return max(8, min(256, (64 << 20) // per_frame))
+
+    @translate_oom
+    def observe_many(self, frames, faces, return_z=False):
+        """n teacher-forced steps in one call, for frames known up front (recorded history a conversation joins with, a clip to
+        score): exactly what n successive observe(frame_i, face_i) calls do to the session - the conditioning windows, the faces
+        window, h / c, the frame counter, `steps` += n - so step(), observe(), step_rows() and observe_many() alternate freely and
+        save_rows / load_rows / reset_rows work as before. frames: {modality: (B, n, dim)} contiguous float32 on the session's
+        device, frames t .. t + n - 1 of every modality with history > 0 (extra keys are ignored); faces: (B, n, C) likewise, the
+        observed p1_face frames; n >= 1, the same in every tensor. -> nll (n, B) float32, every frame's NLL in bits as observe()
+        reports it, or (nll, z) with return_z, z (n, B, C) the latents: frame-major, as forward() and inference(return_nll=True).
+
+        Per call: lfi_stream_chunk_in (the windows as sequences, the chunk behind them; the new values pass the range guard), the
+        static part in sequence mode for all n frames, lfi_flow_score_seq_chunk - the conditioning front end ONCE for n B windows and
+        ONE chain launch that loops over the frames inside (n + Ks - 1 cell times end to end where n observe() calls take n Ks) -
+        and lfi_stream_chunk_out. A chunk beyond the frames one launch takes (_chunk_cap) runs as several such rounds. Eager
+        launches, amortised over the chunk: no graph is captured, `replays` does not count them, and the graphs of the per-frame calls
+        stay valid (they address the same session buffers). Shapes outside the register-resident cells, LFI_SAMPLE_CHAIN=0 and
+        LFI_FLOW_GENERIC=1: lfi_flow_score_seq_from with nframes = n, the per-frame kernels. Everything is checked before the first
+        launch: a refused call leaves the session as it was."""
+        s = self.eng.spec
+        self._check_usable()
+        if not isinstance(return_z, bool):
+            raise TypeError("return_z: expected a bool, got %s %r" % (type(return_z).__name__, return_z))
+        if not isinstance(frames, dict):
+            raise TypeError("frames must be a dict {modality: (B, n, dim) tensor}")
+        n = self._check_chunk(faces, "faces", s.C)
+        srcs = []
+        for e in self.mods:
+            x = frames.get(e.name)
+            if x is None:
+                raise KeyError("batch is missing modality %r" % e.name)
+            self._check_chunk(x, e.name, e.in_dim, n)
+            srcs.append(x)
+        srcs.append(faces)
+        cap = self._chunk_cap()
+        with self._owned():
+            self._check_guard()
+            eng, B = self.eng, self.B
+            masks = self._chunk_masks(n)
+            nll = torch.empty(n, B, dtype=torch.float32, device=self.device)
+            z = torch.empty(n, B, s.C, dtype=torch.float32, device=self.device) if return_z else None
+            keep, eng._ws = eng._ws, self._chunk_ws      # (the session's own workspaces keep the addresses its graphs hold)
+            try:
+                for o in range(0, n, cap):
+                    m = min(cap, n - o)
+                    mk = None if masks is None else {k: v[o:o + m].contiguous() for k, v in masks.items()}
+                    self._chunk_round([x[:, o:o + m] for x in srcs], m, mk, nll[o:o + m], None if z is None else z[o:o + m])
+            finally:
+                self._chunk_ws, eng._ws = eng._ws, keep
+            self._pinned.copy_(self.guard, non_blocking=True)
+            gev = torch.cuda.Event()
+            gev.record()
+            self._guard_pending = gev
+            for x in srcs:
+                x.record_stream(torch.cuda.current_stream(self.device))
+        self._record_out(nll, z)
+        return (nll, z) if return_z else nll
+
+    def _chunk_masks(self, n):
+        """Injected masks (masks_fn, tests only) for frames steps .. steps + n - 1 -> {name: (n, B, hist)} or None; a one-frame mask
+        repeats, as in _advance."""
+        drawn = self._masks_fn(self.B, n) if self._masks_fn is not None else None
+        self.eng.precision = self.precision      # (the module's mask draw re-applies its own mode to the engine)
+        if not drawn:
+            return None
+        masks = {}
+        for name, buf in self.mask_bufs.items():
+            m = drawn.get(name)
+            if m is None:
+                continue
+            if m.dim() != 3 or tuple(m.shape[1:]) != (self.B, buf.shape[2]):
+                raise ValueError("mask for %s must be (N, B, hist) = (., %d, %d), got %s" % (name, self.B, buf.shape[2], tuple(m.shape)))
+            if m.shape[0] != 1 and self.steps + n > m.shape[0]:
+                raise ValueError("mask for %s holds %d frames; this is frame %d of the stream" % (name, m.shape[0], self.steps + n - 1))
+            m = m.expand(n, -1, -1) if m.shape[0] == 1 else m[self.steps:self.steps + n]
+            masks[name] = m.to(device=self.device, dtype=torch.float32).contiguous()
+        return masks or None
+
+    def _chunk_round(self, srcs, m, masks, nll, z):
+        """m frames of a chunk, inside _owned() with the chunk's workspaces as the engine's: windows in, static part, chain, windows
+        out. srcs: the frames of self._wins' windows in their order (strided views of the caller's tensors); nll (m, B) / z (m, B, C)
+        or None: contiguous slices of the call's outputs."""
+        s, eng, B = self.eng.spec, self.eng, self.B
+        T = s.start + m
+        k = len(self._wins)
+        seq_p, src_p = (C.c_void_p * k)(), (C.c_void_p * k)()
+        seqs = {}
+        for i, ((name, _, _, d, _), x) in enumerate(zip(self._wins, srcs)):
+            x = x if x.is_contiguous() else x.contiguous()
+            srcs[i] = x                                   # (kept alive until the launches that read it are queued)
+            seqs[name] = eng._buf("chunk_seq." + name, B * T * d)[:B * T * d].view(B, T, d)
+            seq_p[i], src_p[i] = seqs[name].data_ptr(), x.data_ptr()
+        ev = eng._tic("stream_chunk_in")
+        check(eng.L.lfi_stream_chunk_in(B, m, s.start, k, self._row_win, src_p, seq_p, self._row_hist, self._row_dim, self._lead,
+                                        self.guard.data_ptr(), _stream()), "lfi_stream_chunk_in")
+        eng._toc("stream_chunk_in", ev)
+        # the static part as _sample's static() makes it for a run of frames, from the session's sequences and its per-row counter
+        ev = eng._tic("stream_chunk_static")
+        KD = s.Ks * s.D
+        cond = eng._buf("chunk_cond", m * B * s.ldf)
+        pre = eng._buf("chunk_pre", m * B * KD)
+        data = {name: t for name, t in seqs.items() if name != "p1_face"}
+        if self.frame_nb is not None:
+            data["frame_nb"] = self.frame_nb
+        eng.build_features(data, None, B, T, masks, cond, with_stash=False, skip_p1=True, sampling=False, frame_nb_offset=2.0)
+        eng._static_pre(cond, pre, m * B, self.c1, self._wp)
+        eng._toc("stream_chunk_static", ev)
+        dims, p = eng._flow_dims(B, m), eng._flow_params()
+        dims.gemm_precision = self.frame_precision
+        first = 1 if self.steps > 0 or self._resumed else 0
+        faces = seqs["p1_face"]
+        ev = eng._tic("stream_chunk_chain")
+        if self.hist1 >= 1 and eng.L.lfi_flow_score_chunk_ok(C.byref(dims)):     # (the chunk chain wants a faces window)
+            work = eng._buf("chunk_work", eng.L.lfi_flow_score_chunk_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
+            check(eng.L.lfi_flow_score_seq_chunk(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
+                                                 pre.data_ptr(), faces.data_ptr(), T, s.start, m, first, self.h.data_ptr(), ptr(self.cs),
+                                                 C.byref(self._p1), None, None, work.data_ptr(), ptr(z), nll.data_ptr(), _stream()),
+                  "lfi_flow_score_seq_chunk")
+        else:
+            # the per-frame kernels on the same sequences: m front ends and m chains (or Ks cells each), one frame's work areas
+            work = eng._buf("chunk_frame_work", eng.L.lfi_flow_sample_work_floats(C.byref(dims)))
+            p1work = eng._buf("chunk_frame_p1work", eng.L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
+            score = eng._buf("chunk_frame_score", eng.L.lfi_flow_score_work_floats(C.byref(dims)))
+            check(eng.L.lfi_flow_score_seq_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
+                                                pre.data_ptr(), faces.data_ptr(), T, s.start, m, first, self.h.data_ptr(), ptr(self.cs),
+                                                C.byref(self._p1), p1work.data_ptr(), work.data_ptr(), score.data_ptr(), ptr(z),
+                                                nll.data_ptr(), _stream()), "lfi_flow_score_seq_from")
+        eng._toc("stream_chunk_chain", ev)
+        check(eng.L.lfi_stream_chunk_out(B, m, s.start, k, self._row_win, seq_p, self._row_hist, self._row_dim, self._lead,
+                                         ptr(self.frame_nb), _stream()), "lfi_stream_chunk_out")
+        self.steps += m
 
     def _check_observed(self, observed):
         """The role mask of step_rows(), checked before any launch -> a (B,) bool tensor, on the session's device or on the host (a
