@@ -524,6 +524,26 @@ int lfi_stream_chunk_in(int B, int n, int start, int count, float* const* win, c
                         const int* hist, const int* dim, const int* lead, unsigned* guard_bits, void* stream);
 int lfi_stream_chunk_out(int B, int n, int start, int count, float* const* win, float* const* seq, const int* hist,
                          const int* dim, const int* lead, float* frame_nb, void* stream);
+/* The two window launches for a chunk of n >= 1 GENERATED frames per call (SampleStream.step_many), around the chunk's static part
+ * and lfi_flow_sample_seq_nll with nframes = n on seq[gen_win]: lfi_stream_chunk_in / lfi_stream_chunk_out with the same tables,
+ * for a session whose prev_p1_face window gen_win (0 <= gen_win < count, dim[gen_win] == C) has no source - the chain writes its
+ * frames start .. start + n - 1.
+ * gen_in: every window but gen_win as lfi_stream_chunk_in. Of gen_win only the live frames go into seq[gen_win]; src[gen_win] is not
+ * read and may be NULL (the table itself may not); its frames start .. start + n - 1 are left alone. noise (n x B x C, frame-major,
+ * already * eps: lfi_flow_sample_seq_nll's) is read once and folded into *guard_bits beside the new conditioning values; it is not
+ * copied - the chain reads the caller's tensor in place.
+ * gen_out: lfi_stream_chunk_out, and the n generated frames of every batch row b go from seq[gen_win] to out + b * ld_out (n x C
+ * each; ld_out >= n * C floats, so a (B, N, C) result takes a run of its frames in place) and are folded into *guard_bits: a
+ * generated value beyond the fp16 pieces' range reaches the guard as it does through the lfi_stream_advance after a one-frame step.
+ * guard_bits NULL = no guard. One launch each, allocation-free; every argument is checked before the launch. */
+int lfi_stream_chunk_gen_in(int B, int n, int start, int count, float* const* win, const float* const* src, float* const* seq,
+                            const int* hist, const int* dim, const int* lead, int gen_win,
+                            const float* noise /* n x B x C, frame-major, already * eps */, int C,
+                            unsigned* guard_bits, void* stream);
+int lfi_stream_chunk_gen_out(int B, int n, int start, int count, float* const* win, float* const* seq,
+                             const int* hist, const int* dim, const int* lead, int gen_win,
+                             float* out /* B x n x C, row pitch ld_out floats */, long ld_out,
+                             float* frame_nb, unsigned* guard_bits, void* stream);
 /* Reseed listed batch rows of a streaming sampling session (SampleStream.reset_rows; the start of glow/models.py:567-596 for those
  * rows alone) between steps: each session row rows[j] (0 <= rows[j] < B, none twice, nrows >= 1) gets the state open_stream gives
  * a row, from entry j of the caller's seed, and no other row is written. Per window i (count <= 8; the layout of lfi_stream_advance):

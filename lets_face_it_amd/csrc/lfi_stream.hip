@@ -179,6 +179,81 @@ __global__ __launch_bounds__(256) void stream_chunk_out_kernel(StreamChunk w, in
   for (long j = threadIdx.x; j < tot; j += 256) win[j] = seq[j];
 }
 
+// The guard fold the chunk kernels end with: the workgroup's waves each put their max into the word.
+__device__ __forceinline__ void stream_guard_fold(unsigned m, unsigned* __restrict__ guard) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
+    m = t > m ? t : m;
+  }
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(guard, m);
+}
+
+// ---- a chunk of n GENERATED frames per call (SampleStream.step_many): stream_chunk_in_kernel / stream_chunk_out_kernel around the
+// reverse chain, which writes frames start .. start + n - 1 of seq[gen_win] itself.
+//
+// In: every window but gen_win as stream_chunk_in_kernel. Workgroup (gen_win, b) lays out the live frames only - it has no source -
+// and folds row b of the n noise frames (n x B x C, frame-major, read where the caller keeps them) into the guard word instead.
+__global__ __launch_bounds__(256) void stream_chunk_gen_in_kernel(StreamChunk w, int n, int start, int gen_win, int B,
+                                                                 const float* __restrict__ noise, unsigned* __restrict__ guard) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x;
+  const int dim = w.dim[i];
+  const long live = (long)(w.hist[i] - w.lead[i]) * dim, fresh = (long)n * dim;
+  const float* win = w.win[i] + ((long)b * w.hist[i] + w.lead[i]) * dim;
+  float* seq = w.seq[i] + (long)b * (start + n) * dim + (long)start * dim;
+  for (long j = threadIdx.x; j < live; j += 256) seq[j - live] = win[j];
+  unsigned m = 0u;
+  if (i != gen_win) {
+    const float* src = w.src[i] + (long)b * fresh;
+    for (long j = threadIdx.x; j < fresh; j += 256) {
+      const float v = src[j];
+      seq[j] = v;
+      const unsigned a = stream_abs_bits(v);
+      m = a > m ? a : m;
+    }
+  } else {
+    for (int f = 0; f < n; ++f) {
+      const float* row = noise + ((long)f * B + b) * dim;      // (dim[gen_win] == C)
+      for (int j = threadIdx.x; j < dim; j += 256) {
+        const unsigned a = stream_abs_bits(row[j]);
+        m = a > m ? a : m;
+      }
+    }
+  }
+  if (guard) stream_guard_fold(m, guard);
+}
+
+// Out: stream_chunk_out_kernel, and workgroup (gen_win, b) also hands the n generated frames of row b to the caller (out + b * ld_out,
+// n x C) and folds them into the guard word: what the next one-frame advance does with a frame step() generated.
+__global__ __launch_bounds__(256) void stream_chunk_gen_out_kernel(StreamChunk w, int n, int start, int gen_win, float* __restrict__ out,
+                                                                  long ld_out, float* __restrict__ frame_nb,
+                                                                  unsigned* __restrict__ guard) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x;
+  if (i == w.count) {
+    if (frame_nb && threadIdx.x == 0) frame_nb[b] += 2.0f * (float)n;
+    return;
+  }
+  const int dim = w.dim[i];
+  const long tot = (long)w.hist[i] * dim;
+  float* win = w.win[i] + (long)b * tot;
+  const float* end = w.seq[i] + ((long)(b + 1) * (start + n)) * dim;      // one past row b's last frame
+  for (long j = threadIdx.x; j < tot; j += 256) win[j] = (end - tot)[j];
+  if (i != gen_win) return;
+  const long fresh = (long)n * dim;
+  const float* gen = end - fresh;
+  float* dst = out + (long)b * ld_out;
+  unsigned m = 0u;
+  for (long j = threadIdx.x; j < fresh; j += 256) {
+    const float v = gen[j];
+    dst[j] = v;
+    const unsigned a = stream_abs_bits(v);
+    m = a > m ? a : m;
+  }
+  if (guard) stream_guard_fold(m, guard);
+}
+
 // ---- per-row reseed (SampleStream.reset_rows): the state open_stream / reset() give a row, for a listed subset of rows
 //
 // Rows are passed by value in the kernel argument block (StreamReset.rows), at most kResetMaxRows per launch: no staging copy and no
@@ -552,5 +627,42 @@ extern "C" int lfi_stream_chunk_out(int B, int n, int start, int count, float* c
   // (hist - lead <= start and n >= 1: the last hist frames of a sequence lie inside what chunk_in wrote)
   hipLaunchKernelGGL(stream_chunk_out_kernel, dim3(count + 1, B), dim3(256), 0, (hipStream_t)stream, w, n, start, frame_nb);
   LFI_LAUNCH_CHECK("lfi_stream_chunk_out");
+  return LFI_OK;
+}
+
+extern "C" int lfi_stream_chunk_gen_in(int B, int n, int start, int count, float* const* win, const float* const* src, float* const* seq,
+                                       const int* hist, const int* dim, const int* lead, int gen_win, const float* noise, int C,
+                                       unsigned* guard_bits, void* stream) {
+  StreamChunk w = {};
+  const int rc = stream_chunk_args("lfi_stream_chunk_gen_in", B, n, start, count, win, seq, hist, dim, lead, &w);
+  if (rc != LFI_OK) return rc;
+  LFI_REQUIRE(src && noise, "lfi_stream_chunk_gen_in: null pointer (source table / noise)");
+  LFI_REQUIRE(gen_win >= 0 && gen_win < count, "lfi_stream_chunk_gen_in: generated window %d of %d", gen_win, count);
+  LFI_REQUIRE(C > 0 && dim[gen_win] == C, "lfi_stream_chunk_gen_in: generated window %d has dim %d, the noise C = %d", gen_win,
+              dim[gen_win], C);
+  for (int i = 0; i < count; ++i) {
+    LFI_REQUIRE(i == gen_win || src[i], "lfi_stream_chunk_gen_in: null pointer (source %d)", i);
+    w.src[i] = i == gen_win ? nullptr : src[i];
+  }
+  hipLaunchKernelGGL(stream_chunk_gen_in_kernel, dim3(count, B), dim3(256), 0, (hipStream_t)stream, w, n, start, gen_win, B, noise,
+                     guard_bits);
+  LFI_LAUNCH_CHECK("lfi_stream_chunk_gen_in");
+  return LFI_OK;
+}
+
+extern "C" int lfi_stream_chunk_gen_out(int B, int n, int start, int count, float* const* win, float* const* seq, const int* hist,
+                                        const int* dim, const int* lead, int gen_win, float* out, long ld_out, float* frame_nb,
+                                        unsigned* guard_bits, void* stream) {
+  StreamChunk w = {};
+  const int rc = stream_chunk_args("lfi_stream_chunk_gen_out", B, n, start, count, win, seq, hist, dim, lead, &w);
+  if (rc != LFI_OK) return rc;
+  LFI_REQUIRE(out, "lfi_stream_chunk_gen_out: null pointer (out)");
+  LFI_REQUIRE(gen_win >= 0 && gen_win < count, "lfi_stream_chunk_gen_out: generated window %d of %d", gen_win, count);
+  LFI_REQUIRE(ld_out >= (long)n * dim[gen_win], "lfi_stream_chunk_gen_out: out row pitch %ld below the %d frames' %ld floats", ld_out, n,
+              (long)n * dim[gen_win]);
+  // (hist - lead <= start and n >= 1: the last hist frames of a sequence lie inside what chunk_gen_in and the chain wrote)
+  hipLaunchKernelGGL(stream_chunk_gen_out_kernel, dim3(count + 1, B), dim3(256), 0, (hipStream_t)stream, w, n, start, gen_win, out, ld_out,
+                     frame_nb, guard_bits);
+  LFI_LAUNCH_CHECK("lfi_stream_chunk_gen_out");
   return LFI_OK;
 }

@@ -574,7 +574,12 @@ class SeqGlow(nn.Module):
         observe_many(frames, faces, return_z=False) is n observe() steps in one call for frames known up front (recorded history,
         a clip to score): frames {modality: (B, n, dim)}, faces (B, n, C) -> nll (n, B), or (nll, z) with z (n, B, C). It leaves
         the session where n observe() calls leave it (steps += n), with the conditioning front end run once for the chunk and the
-        flow steps as one launch that loops over the frames; eager launches, no graph."""
+        flow steps as one launch that loops over the frames; eager launches, no graph.
+
+        step_many(frames, noise=None) is n step() calls in one for conditioning known ahead (a look-ahead buffer, a rollout between
+        save_rows and load_rows, finishing a clip): frames {modality: (B, n, dim)}, noise (n, B, C) as inference()'s or None (n draws
+        of the session's own) -> out (B, n, C), or (out, nll) with nll (n, B) under return_nll=True. It leaves the session where n
+        step() calls leave it (steps += n), with the static part run once for the chunk; eager launches, no graph."""
         _engine.check_return_nll(return_nll)
         p1 = seed.get("p1_face") if isinstance(seed, dict) else None
         if p1 is None:

@@ -154,7 +154,7 @@ class SampleStream:
         self._rows_graphs = {}                                       # step_rows()'s own, by key
         self.score_work = self.obs_z = self.obs_nll = None   # observe()'s buffers: allocated at the first observe
         self.role = self.rows_work = self.rows_nll = self.rows_nll_work = None   # step_rows()'s: at the first step_rows
-        self._chunk_ws = {}                     # observe_many()'s workspaces, sized by the chunk (the graphs never address them)
+        self._chunk_ws = {}                     # observe_many()'s / step_many()'s workspaces, sized by the chunk (the graphs never address them)
         self._stream = None
         self._guard_pending = None
         self._state = {"_ws": {}, "prep": None, "wct_f": torch.zeros_like(eng.wct_f), "_wct_planes": None, "_wc_r": None,
@@ -529,6 +529,78 @@ class SampleStream:
         self._record_out(nll, z)
         return (nll, z) if return_z else nll
 
+    @translate_oom
+    def step_many(self, frames, noise=None):
+        """n generated frames in one call, for conditioning known ahead (a look-ahead buffer over synthesised speech, a rollout under
+        hypothesised conditioning, finishing a clip): exactly what n successive step(frame_i, noise_i) calls do to the session - the
+        conditioning windows, the faces window, h / c, the frame counter, `steps` += n - so all five kinds of call alternate freely
+        and save_rows / load_rows / reset_rows work as before. frames: {modality: (B, n, dim)} contiguous float32 on the session's
+        device, frames t .. t + n - 1 of every modality with history > 0 (extra keys are ignored), n >= 1 the same in every tensor;
+        noise: (n, B, C) contiguous float32 on the session's device, the prior draws already * eps, frame-major as inference()'s
+        noise and observe_many()'s z, or None: n draws of the session's own, stacked - the random numbers n step() calls consume.
+        -> out (B, n, C), the generated p1_face frames as inference() returns them; a session opened with return_nll=True ->
+        (out, nll), nll (n, B) float32, every frame's NLL in bits as step() reports it.
+
+        Per call: lfi_stream_chunk_gen_in (the windows as sequences, the conditioning behind them; the new values and the noise pass
+        the range guard, the noise is read where the caller keeps it), the static part in sequence mode ONCE for all n frames - n
+        step() calls run the window encoders n times over windows that overlap in all but one frame - then lfi_flow_sample_seq_nll
+        with nframes = n on the faces sequence from the session's live h / c, and lfi_stream_chunk_gen_out (the windows back, the
+        generated frames into `out` and through the range guard). A chunk beyond the frames one round takes (_chunk_cap) runs as
+        several such rounds. Eager launches: no graph is captured, `replays` does not count them, and the graphs of the per-frame
+        calls stay valid. The sampler entry point picks its kernels as it does for inference(): every shape and switch it handles
+        works here. Train mode without injected masks: the masks of the n frames are drawn in one call, before the noise.
+        Everything is checked before the first launch: a refused call leaves the session as it was."""
+        s = self.eng.spec
+        self._check_usable()
+        if not isinstance(frames, dict):
+            raise TypeError("frames must be a dict {modality: (B, n, dim) tensor}")
+        srcs, n = [], None
+        for e in self.mods:
+            x = frames.get(e.name)
+            if x is None:
+                raise KeyError("batch is missing modality %r" % e.name)
+            n = self._check_chunk(x, e.name, e.in_dim, n)
+            srcs.append(x)
+        if noise is None and n is None:
+            raise ValueError("noise: a model without conditioning windows takes its frame count from the noise, (n, B=%d, %d)"
+                             % (self.B, s.C))
+        if noise is not None:
+            ok = (torch.is_tensor(noise) and noise.is_cuda and noise.device == self.device and noise.dtype == torch.float32
+                  and noise.is_contiguous() and noise.dim() == 3 and noise.shape[0] >= 1 and tuple(noise.shape[1:]) == (self.B, s.C))
+            if not ok or (n is not None and noise.shape[0] != n):
+                raise ValueError("noise: expected contiguous float32 GPU tensor (%s, B=%d, %d) on %s, frame-major, got %s %s on %s"
+                                 % ("n>=1" if n is None else "n=%d" % n, self.B, s.C, self.device,
+                                    tuple(getattr(noise, "shape", ())), getattr(noise, "dtype", type(noise)),
+                                    getattr(noise, "device", None)))
+            n = int(noise.shape[0])
+        srcs.append(None)                       # (the faces window has no source: the chain writes its frames)
+        cap = self._chunk_cap()
+        with self._owned():
+            self._check_guard()
+            eng, B = self.eng, self.B
+            masks = self._chunk_masks(n)
+            if noise is None:
+                noise = torch.stack([self._noise_fn(B, s.C) for _ in range(n)]).contiguous()
+            out = torch.empty(B, n, s.C, dtype=torch.float32, device=self.device)
+            nll = torch.empty(n, B, dtype=torch.float32, device=self.device) if self.return_nll else None
+            keep, eng._ws = eng._ws, self._chunk_ws      # (the session's own workspaces keep the addresses its graphs hold)
+            try:
+                for o in range(0, n, cap):
+                    m = min(cap, n - o)
+                    mk = None if masks is None else {k: v[o:o + m].contiguous() for k, v in masks.items()}
+                    self._gen_round([x if x is None else x[:, o:o + m] for x in srcs], m, mk, noise[o:o + m], out, o,
+                                    None if nll is None else nll[o:o + m])
+            finally:
+                self._chunk_ws, eng._ws = eng._ws, keep
+            self._pinned.copy_(self.guard, non_blocking=True)
+            gev = torch.cuda.Event()
+            gev.record()
+            self._guard_pending = gev
+            for x in srcs[:-1] + [noise]:
+                x.record_stream(torch.cuda.current_stream(self.device))
+        self._record_out(out, nll)
+        return (out, nll) if self.return_nll else out
+
     def _chunk_masks(self, n):
         """Injected masks (masks_fn, tests only) for frames steps .. steps + n - 1 -> {name: (n, B, hist)} or None; a one-frame mask
         repeats, as in _advance."""
@@ -549,6 +621,39 @@ class SampleStream:
             masks[name] = m.to(device=self.device, dtype=torch.float32).contiguous()
         return masks or None
 
+    def _chunk_seqs(self, srcs, m):
+        """The sequence buffers of a round of m frames (B x (start + m) x dim per window of self._wins, in the chunk's workspaces) and
+        the pointer tables the window launches take. srcs: the round's frames per window, in self._wins' order, None where a window
+        has no source (step_many's faces); a strided view is made contiguous in place in the list, which keeps it alive until the
+        launches that read it are queued. -> (seqs by name, seq_p, src_p)."""
+        s, eng, B = self.eng.spec, self.eng, self.B
+        T = s.start + m
+        k = len(self._wins)
+        seq_p, src_p = (C.c_void_p * k)(), (C.c_void_p * k)()
+        seqs = {}
+        for i, ((name, _, _, d, _), x) in enumerate(zip(self._wins, srcs)):
+            if x is not None:
+                x = x if x.is_contiguous() else x.contiguous()
+                srcs[i] = x
+            seqs[name] = eng._buf("chunk_seq." + name, B * T * d)[:B * T * d].view(B, T, d)
+            seq_p[i], src_p[i] = seqs[name].data_ptr(), None if x is None else x.data_ptr()
+        return seqs, seq_p, src_p
+
+    def _chunk_static(self, seqs, m, masks):
+        """The static part as _sample's static() makes it for a run of m frames, from the session's sequences and its per-row
+        counter -> pre (m * B rows of Ks * D), what the chains consume."""
+        s, eng, B = self.eng.spec, self.eng, self.B
+        ev = eng._tic("stream_chunk_static")
+        cond = eng._buf("chunk_cond", m * B * s.ldf)
+        pre = eng._buf("chunk_pre", m * B * s.Ks * s.D)
+        data = {name: t for name, t in seqs.items() if name != "p1_face"}
+        if self.frame_nb is not None:
+            data["frame_nb"] = self.frame_nb
+        eng.build_features(data, None, B, s.start + m, masks, cond, with_stash=False, skip_p1=True, sampling=False, frame_nb_offset=2.0)
+        eng._static_pre(cond, pre, m * B, self.c1, self._wp)
+        eng._toc("stream_chunk_static", ev)
+        return pre
+
     def _chunk_round(self, srcs, m, masks, nll, z):
         """m frames of a chunk, inside _owned() with the chunk's workspaces as the engine's: windows in, static part, chain, windows
         out. srcs: the frames of self._wins' windows in their order (strided views of the caller's tensors); nll (m, B) / z (m, B, C)
@@ -556,28 +661,12 @@ class SampleStream:
         s, eng, B = self.eng.spec, self.eng, self.B
         T = s.start + m
         k = len(self._wins)
-        seq_p, src_p = (C.c_void_p * k)(), (C.c_void_p * k)()
-        seqs = {}
-        for i, ((name, _, _, d, _), x) in enumerate(zip(self._wins, srcs)):
-            x = x if x.is_contiguous() else x.contiguous()
-            srcs[i] = x                                   # (kept alive until the launches that read it are queued)
-            seqs[name] = eng._buf("chunk_seq." + name, B * T * d)[:B * T * d].view(B, T, d)
-            seq_p[i], src_p[i] = seqs[name].data_ptr(), x.data_ptr()
+        seqs, seq_p, src_p = self._chunk_seqs(srcs, m)
         ev = eng._tic("stream_chunk_in")
         check(eng.L.lfi_stream_chunk_in(B, m, s.start, k, self._row_win, src_p, seq_p, self._row_hist, self._row_dim, self._lead,
                                         self.guard.data_ptr(), _stream()), "lfi_stream_chunk_in")
         eng._toc("stream_chunk_in", ev)
-        # the static part as _sample's static() makes it for a run of frames, from the session's sequences and its per-row counter
-        ev = eng._tic("stream_chunk_static")
-        KD = s.Ks * s.D
-        cond = eng._buf("chunk_cond", m * B * s.ldf)
-        pre = eng._buf("chunk_pre", m * B * KD)
-        data = {name: t for name, t in seqs.items() if name != "p1_face"}
-        if self.frame_nb is not None:
-            data["frame_nb"] = self.frame_nb
-        eng.build_features(data, None, B, T, masks, cond, with_stash=False, skip_p1=True, sampling=False, frame_nb_offset=2.0)
-        eng._static_pre(cond, pre, m * B, self.c1, self._wp)
-        eng._toc("stream_chunk_static", ev)
+        pre = self._chunk_static(seqs, m, masks)
         dims, p = eng._flow_dims(B, m), eng._flow_params()
         dims.gemm_precision = self.frame_precision
         first = 1 if self.steps > 0 or self._resumed else 0
@@ -601,6 +690,37 @@ class SampleStream:
         eng._toc("stream_chunk_chain", ev)
         check(eng.L.lfi_stream_chunk_out(B, m, s.start, k, self._row_win, seq_p, self._row_hist, self._row_dim, self._lead,
                                          ptr(self.frame_nb), _stream()), "lfi_stream_chunk_out")
+        self.steps += m
+
+    def _gen_round(self, srcs, m, masks, noise, out, o, nll):
+        """m generated frames of a step_many() call, inside _owned() with the chunk's workspaces as the engine's: windows in, static
+        part, the reverse chain from the session's live state, windows and frames out. srcs: as _chunk_round's, None for the faces
+        window; noise (m, B, C) / nll (m, B) or None: contiguous slices of the call's; the frames go to out[:, o:o + m]."""
+        s, eng, B = self.eng.spec, self.eng, self.B
+        T = s.start + m
+        k = len(self._wins)
+        gen = k - 1                             # the prev_p1_face window: the last of self._wins
+        seqs, seq_p, src_p = self._chunk_seqs(srcs, m)
+        ev = eng._tic("stream_chunk_in")
+        check(eng.L.lfi_stream_chunk_gen_in(B, m, s.start, k, self._row_win, src_p, seq_p, self._row_hist, self._row_dim, self._lead,
+                                            gen, noise.data_ptr(), s.C, self.guard.data_ptr(), _stream()), "lfi_stream_chunk_gen_in")
+        eng._toc("stream_chunk_in", ev)
+        pre = self._chunk_static(seqs, m, masks)
+        dims, p = eng._flow_dims(B, m), eng._flow_params()
+        dims.gemm_precision = self.frame_precision
+        first = 1 if self.steps > 0 or self._resumed else 0
+        work = eng._buf("chunk_gen_work", eng.L.lfi_flow_sample_work_floats(C.byref(dims)))
+        p1work = eng._buf("chunk_gen_p1work", eng.L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
+        nll_work = eng._buf("chunk_gen_nll_work", eng.L.lfi_flow_sample_nll_work_floats(C.byref(dims))) if nll is not None else None
+        ev = eng._tic("stream_chunk_gen_chain")
+        check(eng.L.lfi_flow_sample_seq_nll(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
+                                            pre.data_ptr(), noise.data_ptr(), seqs["p1_face"].data_ptr(), T, s.start, m, first,
+                                            self.h.data_ptr(), ptr(self.cs), C.byref(self._p1), p1work.data_ptr(), work.data_ptr(),
+                                            ptr(nll), ptr(nll_work), _stream()), "lfi_flow_sample_seq_nll")
+        eng._toc("stream_chunk_gen_chain", ev)
+        check(eng.L.lfi_stream_chunk_gen_out(B, m, s.start, k, self._row_win, seq_p, self._row_hist, self._row_dim, self._lead, gen,
+                                             out.data_ptr() + 4 * o * s.C, out.shape[1] * s.C, ptr(self.frame_nb),
+                                             self.guard.data_ptr(), _stream()), "lfi_stream_chunk_gen_out")
         self.steps += m
 
     def _check_observed(self, observed):

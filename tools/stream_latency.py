@@ -4,6 +4,7 @@ alternative without a session: re-running SeqGlow.inference over the whole prefi
   python tools/stream_latency.py [--batches 1,16,256] [--steps 200] [--warmup 20] [--prefixes 50,150,300] [--out FILE]
                                  [--churn 1,16,64 [--churn-batch 256]] [--migrate 16 [--migrate-batch 256]] [--nll 1,256]
                                  [--observe 1,16,256] [--rows 1,16,256] [--observe-many 16,64,250]
+                                 [--step-many 4,16,64]
 
 Per batch size: the wall-clock time from step() to the generated frame on the host (a synchronise after every step: what a live agent
 waits for), its GPU time (HIP events around the step), and a per-kernel breakdown from the engine's enable_timing on an eager session
@@ -38,7 +39,13 @@ server has without step_rows: step() on one session of B / 2 rows, then observe(
 chunk length n, two sessions on one seed, both one observed frame into their sequence: n observe() calls in a Python loop on the one,
 one observe_many(n) on the other, alternating which goes first, --reps times after two untimed rounds (sessions are reset(seed) in
 between, graphs kept). Per frame: wall clock (a synchronise after the whole loop / call) and GPU time (HIP events around it). Then the
-front end / chain split of one observe_many per n from the engine's enable_timing."""
+front end / chain split of one observe_many per n from the engine's enable_timing.
+
+--step-many n1,n2,..: this leg ALONE, written to --out (default profiles/stream_step_many.md): per batch size of --batches and per n, two
+sessions on one seed, both one generated frame into their sequence: n step() calls in a Python loop on the one, one step_many(n) on
+the other, the same conditioning and noise, alternating which goes first, --reps times after two untimed rounds (sessions are
+reset(seed) in between, graphs kept). Per frame: wall clock and GPU time as --observe-many. Then where one step_many call's GPU time
+goes (windows in, static part, the sampler's n front ends and chains) from the engine's enable_timing."""
 import argparse
 import contextlib
 import os
@@ -66,7 +73,8 @@ def main():
     ap.add_argument("--observe", default=None, help="batch sizes of the observe() leg, e.g. 1,16,256 (default: no such leg)")
     ap.add_argument("--rows", default=None, help="batch sizes of the step_rows() leg, e.g. 1,16,256: runs this leg alone")
     ap.add_argument("--observe-many", default=None, help="chunk lengths of the observe_many() leg, e.g. 16,64,250: runs this leg alone")
-    ap.add_argument("--reps", type=int, default=7, help="with --observe-many: timed rounds per (batch size, chunk length)")
+    ap.add_argument("--step-many", default=None, help="frames per call of the step_many() leg, e.g. 4,16,64: runs this leg alone")
+    ap.add_argument("--reps", type=int, default=7, help="with --observe-many / --step-many: timed rounds per (batch size, chunk length)")
     a = ap.parse_args()
     import bench
     helper = bench.start_smi_helper()       # (before the GPU is initialised: see bench.py)
@@ -109,6 +117,16 @@ def main():
         bench.stop_smi_helper(helper)
         print(text)
         out = a.out or os.path.join(ROOT, "profiles", "stream_observe_many.md")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text)
+        return
+    if a.step_many:
+        text = step_many_report(m, dev, [int(v) for v in a.batches.split(",")], [int(v) for v in a.step_many.split(",")], a.reps,
+                                dims, start, C, torch.cuda.get_device_name(dev))
+        bench.stop_smi_helper(helper)
+        print(text)
+        out = a.out or os.path.join(ROOT, "profiles", "stream_step_many.md")
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as f:
             f.write(text)
@@ -566,6 +584,72 @@ def observe_many_report(m, dev, batches, ns, reps, dims, start, C, device_name):
         a, b, c = (t.get("stream_chunk_" + k, 0.0) for k in ("in", "static", "chain"))
         lines.append("| %d | %d | %.3f | %.3f | %.3f | %.3f | %.3f | %.0f %% |"
                      % (B, n, a, b, c, t["front"], t["chain"], 100.0 * t["chain"] / max(a + b + c, 1e-9)))
+    return "\n".join(lines) + "\n"
+
+
+def step_many_report(m, dev, batches, ns, reps, dims, start, C, device_name):
+    """The --step-many report: per (B, n) the per-frame time of the step() loop and of step_many(n), then where a step_many call's GPU
+    time goes."""
+    import torch
+    s = m.spec
+    eng = m._ensure_engine(dev)
+    top = max(ns)
+    lines = ["# step_many(): several generated frames per call (tools/stream_latency.py --step-many)", "",
+             "final_model.yaml as shipped (C = %d, S = %d, K = %d, H = %d, D = %d), engine precision %s; both legs of a (B, n) in one "
+             "process on the same conditioning and noise, alternating which goes first; %d timed rounds after 2 untimed ones; per "
+             "FRAME: wall = call to result on the host (one synchronise after the n calls / the one call) / n, GPU = HIP events around "
+             "them / n. Device %s." % (C, s.S, s.Ks, s.H, s.D, m.precision, reps, device_name), "",
+             "| B | n | step() loop: wall ms / frame | GPU ms / frame | step_many: wall ms / frame | GPU ms / frame | loop / call, wall | "
+             "loop / call, GPU | frames per round |", "|---|---|---|---|---|---|---|---|---|"]
+    split, slower = [], []
+    for B in batches:
+        gd = torch.Generator().manual_seed(B + 7)
+        data = {k: torch.randn(B, start + top + 1, d, generator=gd).to(dev) for k, d in dims.items()}
+        seed = {k: v[:, :start].contiguous() for k, v in data.items()}
+        frames = [{k: v[:, start + i].contiguous() for k, v in data.items() if k != "p1_face"} for i in range(top + 1)]
+        noise = (torch.randn(top + 1, B, C, generator=gd) * 0.8).to(dev)
+        with m.open_stream(seed) as loop, m.open_stream(seed) as many:
+            for n in ns:
+                chunk = {k: v[:, start + 1:start + 1 + n].contiguous() for k, v in data.items() if k != "p1_face"}
+                cnoise = noise[1:1 + n]
+                calls = [("loop", loop, lambda: [loop.step(frames[i], noise[i]) for i in range(1, n + 1)]),
+                         ("many", many, lambda: many.step_many(chunk, cnoise))]
+                legs = {"loop": ([], []), "many": ([], [])}
+                for r in range(reps + 2):
+                    for name, st, fn in (calls if r % 2 == 0 else calls[::-1]):
+                        st.reset(seed)
+                        st.step(frames[0], noise[0])
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        e0.record()
+                        fn()
+                        e1.record()
+                        e1.synchronize()
+                        t1 = time.perf_counter()
+                        if r >= 2:
+                            legs[name][0].append((t1 - t0) * 1e3 / n)
+                            legs[name][1].append(e0.elapsed_time(e1) / n)
+                lw, lg, mw, mg = (statistics.median(v) for v in legs["loop"] + legs["many"])
+                lines.append("| %d | %d | %.4f | %.4f | %.4f | %.4f | %.2f x | %.2f x | %d |"
+                             % (B, n, lw, lg, mw, mg, lw / mw, lg / mg, min(n, many._chunk_cap())))
+                if n == 16 and not (mw < lw and mg < lg):
+                    slower.append(B)
+                many.reset(seed)
+                many.step(frames[0], noise[0])
+                eng.enable_timing(True)
+                many.step_many(chunk, cnoise)
+                summary = eng.timing_summary()
+                eng.enable_timing(False)
+                split.append((B, n, {t: v[0] * v[1] for t, v in summary.items() if t.startswith("stream_chunk")}))
+    lines += ["", "Per-frame time of step_many(16) below the same run's step() loop at every batch size: %s."
+              % ("yes" if not slower else "NO, not at B = %s" % slower), "",
+              "## Where a step_many call's GPU time goes (enable_timing, HIP events; ms per call, all its launches of a kind summed)", "",
+              "| B | n | windows in | static part (window encoders + static cond_transform columns) | sampler: n front ends + n chains | "
+              "sampler per frame | sampler share of the call |", "|---|---|---|---|---|---|---|"]
+    for B, n, t in split:
+        a, b, c = (t.get("stream_chunk_" + k, 0.0) for k in ("in", "static", "gen_chain"))
+        lines.append("| %d | %d | %.3f | %.3f | %.3f | %.4f | %.0f %% |" % (B, n, a, b, c, c / n, 100.0 * c / max(a + b + c, 1e-9)))
     return "\n".join(lines) + "\n"
 
 
