@@ -476,6 +476,18 @@ int lfi_flow_score_seq_chunk(const lfi_flow_dims* d, const lfi_flow_params* p, c
                              float* faces, int seq_len, int start, int nframes, int first_frame,
                              float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
                              float* chunk_work, float* z, float* nll, void* stream);
+/* lfi_flow_score_seq_chunk for a RAGGED chunk (SampleStream.observe_many with lengths): lengths, B ints on the device - batch row b
+ * takes the first lengths[b] of the nframes frames (values outside 0 .. nframes are clamped by the kernel). h / cstate of row b are
+ * what lfi_flow_score_seq_chunk leaves after lengths[b] frames (a row of length 0 is not written at all), z and nll are written for
+ * frames n < lengths[b] only - the caller zeroes them first - and with the dense call's arithmetic, instruction for instruction. The
+ * front end stays dense over nframes * B windows (behind a row's length `faces` and pre_static must hold finite values; their results
+ * reach nothing stored); in the chain a 16-row tile loops to its longest row, and a tile of length 0 leaves at once. The work area,
+ * lfi_flow_score_chunk_ok, LFI_CHUNK_ONLY and every other rule are lfi_flow_score_seq_chunk's. */
+int lfi_flow_score_seq_chunk_rows(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep,
+                             const float* wct, long E, int hist1, float* pre_static,
+                             float* faces, int seq_len, int start, int nframes, int first_frame,
+                             float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
+                             float* chunk_work, float* z, float* nll, const int* lengths, void* stream);
 /* ONE frame of a session in which every batch row either observes or generates (SampleStream.step_rows): lfi_flow_sample_seq_nll's
  * arguments (nframes must be 1; nll, B floats, and nll_work are required), then observed (B ints on the device: != 0 = the row's
  * frame is GIVEN - it is in faces[:, start] already - and 0 = the row generates from its noise row) and a second work area, rows_work
@@ -524,6 +536,17 @@ int lfi_stream_chunk_in(int B, int n, int start, int count, float* const* win, c
                         const int* hist, const int* dim, const int* lead, unsigned* guard_bits, void* stream);
 int lfi_stream_chunk_out(int B, int n, int start, int count, float* const* win, float* const* seq, const int* hist,
                          const int* dim, const int* lead, float* frame_nb, void* stream);
+/* The two window launches around a RAGGED chunk (SampleStream.observe_many with lengths; lfi_flow_score_seq_chunk_rows): the dense
+ * ones' arguments and lengths, B ints on the device (values outside 0 .. n are clamped), required.
+ * in_rows: the window's live frames as lfi_stream_chunk_in, then the first lengths[b] frames of row b's source, then zeros up to
+ * frame start + n - 1. What a source holds behind a row's length is not read: it reaches neither seq[i] nor *guard_bits.
+ * out_rows: row b takes the hist[i] frames of seq[i] that end at frame start + lengths[b], and frame_nb[b] += 2 lengths[b]; a row
+ * of length 0 is skipped entirely (its windows and counter are not written).
+ * Allocation-free; every argument is checked before the launch. */
+int lfi_stream_chunk_in_rows(int B, int n, int start, int count, float* const* win, const float* const* src, float* const* seq,
+                        const int* hist, const int* dim, const int* lead, unsigned* guard_bits, const int* lengths, void* stream);
+int lfi_stream_chunk_out_rows(int B, int n, int start, int count, float* const* win, float* const* seq, const int* hist,
+                         const int* dim, const int* lead, float* frame_nb, const int* lengths, void* stream);
 /* The two window launches for a chunk of n >= 1 GENERATED frames per call (SampleStream.step_many), around the chunk's static part
  * and lfi_flow_sample_seq_nll with nframes = n on seq[gen_win]: lfi_stream_chunk_in / lfi_stream_chunk_out with the same tables,
  * for a session whose prev_p1_face window gen_win (0 <= gen_win < count, dim[gen_win] == C) has no source - the chain writes its

@@ -1118,12 +1118,49 @@ inline int frame_args_check(const char* who, const char* who_from, const lfi_flo
 // the last frame only. Per frame: gic, the wait for frame n of step k - 1 (progress word >= n + 1), the cell, the hand-over slot of
 // (k, n), progress word = n + 1. io / q_in / q_out / nll_out point at frame 0; sq holds the strides. A wait that gives up leaves NaN in
 // the nll / z of the frames the last step has not finished.
+// RAG (flow_fwd_seq_rows_chain_kernel, lfi_flow_chunk_rows.hip; with SEQ): a ragged chunk - batch row r takes the first sq->lengths[r]
+// frames only. sq->frames is the TILE's longest row (the same in every step k of the tile, so the progress words agree); per frame
+// two uniform masks of the tile's 16 rows (tile_row_lengths once, tile_row_frames per frame: scalar registers): h_out / c_out are
+// stored for the rows whose last frame this is - the masked stores of the RM cells - and the output tile, the hand-over q and the
+// NLL word for the rows that have the frame. A row behind its length goes on through the arithmetic (rows never mix inside a cell)
+// and reaches nothing stored.
 struct FwdSeq {
   int frames;
   long x_in_step, x_out_step;   // floats between two frames' rows of x_in / x_out
   long gic_step, row_step;      // B * G; B (q_in, q_out, nll_out)
+  const int* lengths;           // RAG only: one word per batch row
 };
-template <int NG, bool X3, bool RM = false, bool SEQ = false>
+// RAG: the lengths of the tile's 16 rows, read once in front of the frame loop, clamped from above to `frames`; 0 for a row outside the
+// batch. A length below 0 acts as 0. (Uniform values, and through readfirstlane the compiler knows it: behind the kernel's first
+// stores it reads them with vector loads, and sixteen VGPRs across the frame loop are more than the SEQ cell has to spare.)
+__device__ __forceinline__ void tile_row_lengths(const int* lengths, int b0, int rows, int frames, int (&len)[MB]) {
+#pragma unroll
+  for (int i = 0; i < MB; ++i) {
+    const int row = b0 + i;
+    len[i] = row < rows ? min(__builtin_amdgcn_readfirstlane(lengths[row]), frames) : 0;
+  }
+}
+// RAG: the tile's rows at frame n - bit i of *has: row b0 + i has the frame (length > n), of *ends: it is the row's last (length == n + 1)
+__device__ __forceinline__ void tile_row_frames(const int (&len)[MB], int n, unsigned* has, unsigned* ends) {
+  unsigned a = 0u, e = 0u;
+#pragma unroll
+  for (int i = 0; i < MB; ++i) {
+    if (len[i] > n) a |= 1u << i;
+    if (len[i] == n + 1) e |= 1u << i;
+  }
+  *has = a; *ends = e;
+}
+// RAG: the longest row of the tile at b0, lengths clamped to [0, nframes] (0: the tile has nothing to do)
+__device__ __forceinline__ int tile_max_frames(const int* lengths, int b0, int rows, int nframes) {
+  int m = 0;
+#pragma unroll
+  for (int i = 0; i < MB; ++i) {
+    const int row = b0 + i;
+    if (row < rows) m = max(m, min(lengths[row], nframes));
+  }
+  return m;
+}
+template <int NG, bool X3, bool RM = false, bool SEQ = false, bool RAG = false>
 __device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io, int b0, const unsigned* wait_flag, unsigned* abort_w,
                                                unsigned* pub_flag, int* s_ok, const float* q_in, float* q_out, float* nll_out,
                                                const FwdSeq* sq = nullptr) {
@@ -1272,7 +1309,11 @@ __device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io,
   }
   __syncthreads();
   const int frames = SEQ ? sq->frames : 1;
+  [[maybe_unused]] unsigned rag_has = 0u, rag_ends = 0u;
+  [[maybe_unused]] int rag_len[RAG ? MB : 1];
+  if constexpr (RAG) tile_row_lengths(sq->lengths, b0, rows, frames, rag_len);
   for (int n = 0; n < frames; ++n) {
+  if constexpr (RAG) tile_row_frames(rag_len, n, &rag_has, &rag_ends);
   if constexpr (SEQ) {
     // (the thread's coordinates pass through an empty asm statement: everything addressed from them is then worked out again in
     // every frame - a few VALU instructions - instead of being hoisted out of the loop, where some twenty such addresses and
@@ -1332,8 +1373,10 @@ __device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io,
   if (wait_flag && !pipe_acquire(wait_flag, SEQ ? (unsigned)(n + 1) : 1u, abort_w, tid, s_ok, false)) {
     if constexpr (SEQ) {
       const int row = b0 + ri;
+      int mend = frames;
+      if constexpr (RAG) mend = row < rows ? min(sq->lengths[row], frames) : 0;   // (the row's own frames only)
       if (nll_out && row < rows)
-        for (int m = n; m < frames; ++m) {
+        for (int m = n; m < mend; ++m) {
           if (io.x_out)
             for (int c = cl; c < C; c += 32) io.x_out[m * sq->x_out_step + (long)row * io.ldxo + c] = __builtin_nanf("");
           if (cl == 0) nll_out[m * sq->row_step + row] = __builtin_nanf("");
@@ -1412,7 +1455,17 @@ __device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io,
           for (int g = 0; g < NG; ++g) az[g] = mfma16(a3, wz[g][b][3], az[g]);
         }
     }
-    if constexpr (SEQ) {
+    if constexpr (RAG) {   // the state leaves at each row's own last frame
+      fast_cell_p2_gates<NG, true, false>(f, Ht, Hn, az, ah, gc, bh, cprev, tcol, kq, b0, rows, io.h_out, nullptr, nullptr,
+                                          NG == 4 ? cnew : nullptr, nullptr, nullptr, 0, 0, rag_ends);
+      if (NG == 4 && tcol < H) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = kq * 4 + r;
+          if ((rag_ends >> i) & 1u) io.c_out[(long)(b0 + i) * H + tcol] = cnew[r];
+        }
+      }
+    } else if constexpr (SEQ) {
       fast_cell_p2_gates<NG, RM, false>(f, Ht, Hn, az, ah, gc, bh, cprev, tcol, kq, b0, rows, n == frames - 1 ? io.h_out : nullptr, nullptr,
                                         nullptr, NG == 4 ? cnew : nullptr, nullptr, nullptr, 0, 0, live);
       if (NG == 4 && n == frames - 1 && tcol < H) {   // the cell state crossed the frames in registers: stored once, as h
@@ -1451,7 +1504,8 @@ __device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io,
   // ---- F4: coupling (glow/models.py:330-341), the pass-through half, the row's log-det; the last step: the prior term and the NLL
   {
     const int row = b0 + ri;
-    const bool rok = RM ? ((live >> ri) & 1u) != 0u : row < rows;
+    bool rok = RM ? ((live >> ri) & 1u) != 0u : row < rows;
+    if constexpr (RAG) rok = ((rag_has >> ri) & 1u) != 0u;
     float lg = 0.0f, zz = 0.0f;
     auto put = [&](int c, float v) {
       if (!x_out || !rok) return;
@@ -1502,5 +1556,28 @@ __device__ __forceinline__ bool fwd_chain_cell(const FlowK& f, const CellIO& io,
   return true;
 }
 
+// ---- the carve of a chunk work area (lfi_flow_score_seq_chunk and its ragged form) for F = nframes * B rows, in floats from its
+// 16-byte aligned start
+struct ChunkCarve {
+  long p1work, wstage, gic, tiles, q, pipe, pipe_words, total;
+  int ldw;
+};
+inline ChunkCarve chunk_carve(const lfi_flow_dims* d, const lfi_p1enc* p1, int hist1, int nframes) {
+  const long F = (long)nframes * d->B, G = (long)(d->lstm ? 4 : 3) * d->H, nbt = (d->B + MB - 1) / MB;
+  auto up4 = [](long v) { return (v + 3) & ~3L; };
+  lfi_flow_dims dm = *d;
+  dm.B = (int)F;
+  ChunkCarve c = {};
+  c.ldw = (int)up4((long)hist1 * d->C);
+  long o = 0;
+  c.p1work = o; o += up4(lfi_flow_sample_p1_work_floats(&dm, p1, hist1));
+  c.wstage = o; o += F * c.ldw;
+  c.gic = o; o += up4((long)d->Ks * F * G);
+  c.tiles = o; o += up4((long)(d->Ks - 1) * F * d->C);
+  c.q = o; o += up4((long)(d->Ks - 1) * F);
+  c.pipe = o; c.pipe_words = up4((long)PIPE_HDR + (long)d->Ks * nbt); o += c.pipe_words;
+  c.total = o;
+  return c;
+}
 
 }  // namespace

@@ -60,30 +60,7 @@ FlowFwdSeqChainKernel flow_fwd_seq_chain_pick(bool lstm, bool x3) {
 }  // namespace
 
 // ---- a chunk of teacher-forced frames known up front (SampleStream.observe_many): the front end once, the chain as ONE launch
-namespace {
-// the carve of a chunk work area for F = nframes * B rows, in floats from its 16-byte aligned start
-struct ChunkCarve {
-  long p1work, wstage, gic, tiles, q, pipe, pipe_words, total;
-  int ldw;
-};
-ChunkCarve chunk_carve(const lfi_flow_dims* d, const lfi_p1enc* p1, int hist1, int nframes) {
-  const long F = (long)nframes * d->B, G = (long)(d->lstm ? 4 : 3) * d->H, nbt = (d->B + MB - 1) / MB;
-  auto up4 = [](long v) { return (v + 3) & ~3L; };
-  lfi_flow_dims dm = *d;
-  dm.B = (int)F;
-  ChunkCarve c = {};
-  c.ldw = (int)up4((long)hist1 * d->C);
-  long o = 0;
-  c.p1work = o; o += up4(lfi_flow_sample_p1_work_floats(&dm, p1, hist1));
-  c.wstage = o; o += F * c.ldw;
-  c.gic = o; o += up4((long)d->Ks * F * G);
-  c.tiles = o; o += up4((long)(d->Ks - 1) * F * d->C);
-  c.q = o; o += up4((long)(d->Ks - 1) * F);
-  c.pipe = o; c.pipe_words = up4((long)PIPE_HDR + (long)d->Ks * nbt); o += c.pipe_words;
-  c.total = o;
-  return c;
-}
-}  // namespace
+// (the carve of the chunk work area: chunk_carve, lfi_flow_cells.h - shared with the ragged chunk of lfi_flow_chunk_rows.hip)
 
 extern "C" int lfi_flow_score_chunk_ok(const lfi_flow_dims* d) {
   if (!d) return 0;

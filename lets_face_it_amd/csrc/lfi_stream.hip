@@ -189,6 +189,51 @@ __device__ __forceinline__ void stream_guard_fold(unsigned m, unsigned* __restri
   if ((threadIdx.x & 63) == 0 && m) atomicMax(guard, m);
 }
 
+// ---- a RAGGED chunk (SampleStream.observe_many with lengths): batch row b takes the first lengths[b] of the chunk's n frames.
+//
+// In: stream_chunk_in_kernel, but behind the row's length the sequence gets zeros and the source is not read - what lies there never
+// reaches the sequence or the guard word. (A row of length 0 still gets its live frames: the dense front end reads every row.)
+__global__ __launch_bounds__(256) void stream_chunk_in_rows_kernel(StreamChunk w, int n, int start, const int* __restrict__ lengths,
+                                                                   unsigned* __restrict__ guard) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x;
+  const int dim = w.dim[i];
+  const int len = min(max(lengths[b], 0), n);
+  const long live = (long)(w.hist[i] - w.lead[i]) * dim, fresh = (long)n * dim, mine = (long)len * dim;
+  const float* win = w.win[i] + ((long)b * w.hist[i] + w.lead[i]) * dim;
+  const float* src = w.src[i] + (long)b * fresh;
+  float* seq = w.seq[i] + (long)b * (start + n) * dim + (long)start * dim;
+  for (long j = threadIdx.x; j < live; j += 256) seq[j - live] = win[j];
+  unsigned m = 0u;
+  for (long j = threadIdx.x; j < mine; j += 256) {
+    const float v = src[j];
+    seq[j] = v;
+    const unsigned a = stream_abs_bits(v);
+    m = a > m ? a : m;
+  }
+  for (long j = mine + threadIdx.x; j < fresh; j += 256) seq[j] = 0.0f;
+  if (guard) stream_guard_fold(m, guard);
+}
+
+// Out: stream_chunk_out_kernel with the row's own end: the hist frames that end at frame start + lengths[b], the counter += 2
+// lengths[b]. A row of length 0 is not touched at all (its window is what it was; with hist - lead == start the leading row would be
+// read from in front of the sequence).
+__global__ __launch_bounds__(256) void stream_chunk_out_rows_kernel(StreamChunk w, int n, int start, const int* __restrict__ lengths,
+                                                                    float* __restrict__ frame_nb) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x;
+  const int len = min(max(lengths[b], 0), n);
+  if (len == 0) return;
+  if (i == w.count) {
+    if (frame_nb && threadIdx.x == 0) frame_nb[b] += 2.0f * (float)len;
+    return;
+  }
+  const long tot = (long)w.hist[i] * w.dim[i];
+  float* win = w.win[i] + (long)b * tot;
+  const float* seq = w.seq[i] + ((long)b * (start + n) + start + len) * w.dim[i] - tot;
+  for (long j = threadIdx.x; j < tot; j += 256) win[j] = seq[j];
+}
+
 // ---- a chunk of n GENERATED frames per call (SampleStream.step_many): stream_chunk_in_kernel / stream_chunk_out_kernel around the
 // reverse chain, which writes frames start .. start + n - 1 of seq[gen_win] itself.
 //
@@ -627,6 +672,35 @@ extern "C" int lfi_stream_chunk_out(int B, int n, int start, int count, float* c
   // (hist - lead <= start and n >= 1: the last hist frames of a sequence lie inside what chunk_in wrote)
   hipLaunchKernelGGL(stream_chunk_out_kernel, dim3(count + 1, B), dim3(256), 0, (hipStream_t)stream, w, n, start, frame_nb);
   LFI_LAUNCH_CHECK("lfi_stream_chunk_out");
+  return LFI_OK;
+}
+
+extern "C" int lfi_stream_chunk_in_rows(int B, int n, int start, int count, float* const* win, const float* const* src, float* const* seq,
+                                        const int* hist, const int* dim, const int* lead, unsigned* guard_bits, const int* lengths,
+                                        void* stream) {
+  StreamChunk w = {};
+  const int rc = stream_chunk_args("lfi_stream_chunk_in_rows", B, n, start, count, win, seq, hist, dim, lead, &w);
+  if (rc != LFI_OK) return rc;
+  LFI_REQUIRE(src, "lfi_stream_chunk_in_rows: null pointer (source table)");
+  LFI_REQUIRE(lengths, "lfi_stream_chunk_in_rows: null pointer (lengths)");
+  for (int i = 0; i < count; ++i) {
+    LFI_REQUIRE(src[i], "lfi_stream_chunk_in_rows: null pointer (source %d)", i);
+    w.src[i] = src[i];
+  }
+  hipLaunchKernelGGL(stream_chunk_in_rows_kernel, dim3(count, B), dim3(256), 0, (hipStream_t)stream, w, n, start, lengths, guard_bits);
+  LFI_LAUNCH_CHECK("lfi_stream_chunk_in_rows");
+  return LFI_OK;
+}
+
+extern "C" int lfi_stream_chunk_out_rows(int B, int n, int start, int count, float* const* win, float* const* seq, const int* hist,
+                                         const int* dim, const int* lead, float* frame_nb, const int* lengths, void* stream) {
+  StreamChunk w = {};
+  const int rc = stream_chunk_args("lfi_stream_chunk_out_rows", B, n, start, count, win, seq, hist, dim, lead, &w);
+  if (rc != LFI_OK) return rc;
+  LFI_REQUIRE(lengths, "lfi_stream_chunk_out_rows: null pointer (lengths)");
+  // (hist - lead <= start and lengths[b] >= 1 where a row is written: its last hist frames lie inside what chunk_in_rows wrote)
+  hipLaunchKernelGGL(stream_chunk_out_rows_kernel, dim3(count + 1, B), dim3(256), 0, (hipStream_t)stream, w, n, start, lengths, frame_nb);
+  LFI_LAUNCH_CHECK("lfi_stream_chunk_out_rows");
   return LFI_OK;
 }
 

@@ -575,6 +575,9 @@ class SeqGlow(nn.Module):
         a clip to score): frames {modality: (B, n, dim)}, faces (B, n, C) -> nll (n, B), or (nll, z) with z (n, B, C). It leaves
         the session where n observe() calls leave it (steps += n), with the conditioning front end run once for the chunk and the
         flow steps as one launch that loops over the frames; eager launches, no graph.
+        observe_many(frames, faces, return_z=False, lengths=[40, 250, 7, 0]) is the ragged form: row r takes its first lengths[r]
+        frames (host ints, 0 .. n) and is left where a dense call of that many frames leaves it, a row of length 0 untouched; nll
+        and z are exact zeros behind a row's length, and what the tensors hold there is never read.
 
         step_many(frames, noise=None) is n step() calls in one for conditioning known ahead (a look-ahead buffer, a rollout between
         save_rows and load_rows, finishing a clip): frames {modality: (B, n, dim)}, noise (n, B, C) as inference()'s or None (n draws

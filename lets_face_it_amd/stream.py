@@ -457,6 +457,30 @@ class SampleStream:
                                 tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x)), getattr(x, "device", None)))
         return int(x.shape[1])
 
+    def _check_lengths(self, lengths, n):
+        """The lengths argument of observe_many(): a sequence of B ints or a 1-D CPU integer tensor of B entries, each in [0, n] -> a
+        list of ints. Host data, as reset_rows' rows; the wording of _index_list."""
+        wrong = "lengths: expected a sequence of ints or a 1-D CPU integer tensor, got %s"
+        if torch.is_tensor(lengths):
+            if (lengths.is_cuda or lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool
+                    or lengths.dim() != 1):
+                raise ValueError(wrong % ("%s %s on %s" % (tuple(lengths.shape), lengths.dtype, lengths.device)))
+            vals = lengths.tolist()
+        else:
+            try:
+                vals = list(lengths)
+                if any(isinstance(v, bool) for v in vals):
+                    raise TypeError
+                vals = [operator.index(v) for v in vals]
+            except TypeError:
+                raise ValueError(wrong % repr(lengths)) from None
+        if len(vals) != self.B:
+            raise ValueError("lengths: %d listed for %d rows" % (len(vals), self.B))
+        bad = [v for v in vals if not 0 <= v <= n]
+        if bad:
+            raise ValueError("lengths: %s outside the chunk's frames (0 .. %d)" % (bad, n))
+        return vals
+
     def _chunk_cap(self):
         """Frames one launch of the chunk chain takes: its hand-over slots are per frame and never reused inside a launch, and the
         front end's operands (pre-activations, gic, features) grow with the frames too, so a long chunk runs as several calls with
@@ -473,7 +497,7 @@ class SampleStream:
         return max(8, min(256, (64 << 20) // per_frame))
 
     @translate_oom
-    def observe_many(self, frames, faces, return_z=False):
+    def observe_many(self, frames, faces, return_z=False, lengths=None):
         """n teacher-forced steps in one call, for frames known up front (recorded history a conversation joins with, a clip to
         score): exactly what n successive observe(frame_i, face_i) calls do to the session - the conditioning windows, the faces
         window, h / c, the frame counter, `steps` += n - so step(), observe(), step_rows() and observe_many() alternate freely and
@@ -489,7 +513,21 @@ class SampleStream:
         launches, amortised over the chunk: no graph is captured, `replays` does not count them, and the graphs of the per-frame calls
         stay valid (they address the same session buffers). Shapes outside the register-resident cells, LFI_SAMPLE_CHAIN=0 and
         LFI_FLOW_GENERIC=1: lfi_flow_score_seq_from with nframes = n, the per-frame kernels. Everything is checked before the first
-        launch: a refused call leaves the session as it was."""
+        launch: a refused call leaves the session as it was.
+
+        lengths (a ragged chunk: conversations that join with histories of different lengths, clips of different lengths to score):
+        None, or a sequence of B ints / a 1-D CPU integer tensor of B entries with 0 <= lengths[r] <= n - host data, as reset_rows'
+        rows. Row r takes its first lengths[r] frames and is left exactly where a dense observe_many of those lengths[r] frames
+        leaves it: windows, h / c and the frame counter (+= 2 lengths[r]), bit for bit; a row of length 0 is not written at all, so
+        joiners warm up in place while the other rows stay where they are. nll[i, r] and z[i, r] for i < lengths[r] are the dense
+        call's; behind a row's length both are exact zeros (nll.sum(0) is each clip's total). What frames / faces hold behind a
+        row's length is never read - anything, NaN included, and it does not reach the range guard. `steps` += n whatever the
+        lengths (injected masks: mask frame steps + i belongs to chunk frame i in every row). Into a session that has not stepped
+        yet, h / c are zeroed first and the call runs as a continuing one, as load_rows does. Launches: lfi_stream_chunk_in_rows,
+        the static part and the front end dense over n B windows, lfi_flow_score_seq_chunk_rows - a 16-row tile loops to its
+        longest row, a tile of length 0 leaves at once: keep rows of similar length in one tile where possible -
+        lfi_stream_chunk_out_rows; a round in which every row has length 0 is skipped. Where the dense call falls back to the
+        per-frame kernels this one does too, in segments between the distinct lengths."""
         s = self.eng.spec
         self._check_usable()
         if not isinstance(return_z, bool):
@@ -497,6 +535,7 @@ class SampleStream:
         if not isinstance(frames, dict):
             raise TypeError("frames must be a dict {modality: (B, n, dim) tensor}")
         n = self._check_chunk(faces, "faces", s.C)
+        lens = None if lengths is None else self._check_lengths(lengths, n)
         srcs = []
         for e in self.mods:
             x = frames.get(e.name)
@@ -510,14 +549,24 @@ class SampleStream:
             self._check_guard()
             eng, B = self.eng, self.B
             masks = self._chunk_masks(n)
-            nll = torch.empty(n, B, dtype=torch.float32, device=self.device)
-            z = torch.empty(n, B, s.C, dtype=torch.float32, device=self.device) if return_z else None
+            new = torch.empty if lens is None else torch.zeros     # (a ragged chunk's launches write live entries only)
+            nll = new(n, B, dtype=torch.float32, device=self.device)
+            z = new(n, B, s.C, dtype=torch.float32, device=self.device) if return_z else None
+            if lens is not None and self.steps == 0 and not self._resumed:
+                self.h.zero_()          # (as load_rows: a zeroed row is a first frame's state, and rows of length 0 keep it)
+                if self.cs is not None:
+                    self.cs.zero_()
+                self._resumed = True
             keep, eng._ws = eng._ws, self._chunk_ws      # (the session's own workspaces keep the addresses its graphs hold)
             try:
                 for o in range(0, n, cap):
                     m = min(cap, n - o)
+                    rl = None if lens is None else [min(max(v - o, 0), m) for v in lens]
+                    if rl is not None and not any(rl):
+                        self.steps += m         # (nothing to run in this round)
+                        continue
                     mk = None if masks is None else {k: v[o:o + m].contiguous() for k, v in masks.items()}
-                    self._chunk_round([x[:, o:o + m] for x in srcs], m, mk, nll[o:o + m], None if z is None else z[o:o + m])
+                    self._chunk_round([x[:, o:o + m] for x in srcs], m, mk, nll[o:o + m], None if z is None else z[o:o + m], rl)
             finally:
                 self._chunk_ws, eng._ws = eng._ws, keep
             self._pinned.copy_(self.guard, non_blocking=True)
@@ -654,17 +703,26 @@ class SampleStream:
         eng._toc("stream_chunk_static", ev)
         return pre
 
-    def _chunk_round(self, srcs, m, masks, nll, z):
+    def _chunk_round(self, srcs, m, masks, nll, z, lens=None):
         """m frames of a chunk, inside _owned() with the chunk's workspaces as the engine's: windows in, static part, chain, windows
         out. srcs: the frames of self._wins' windows in their order (strided views of the caller's tensors); nll (m, B) / z (m, B, C)
-        or None: contiguous slices of the call's outputs."""
+        or None: contiguous slices of the call's outputs. lens (a ragged chunk): the B rows' frame counts in this round, each in
+        [0, m] and not all 0 - the _rows forms of the three entry points, nll / z zeroed by the caller."""
         s, eng, B = self.eng.spec, self.eng, self.B
         T = s.start + m
         k = len(self._wins)
         seqs, seq_p, src_p = self._chunk_seqs(srcs, m)
         ev = eng._tic("stream_chunk_in")
-        check(eng.L.lfi_stream_chunk_in(B, m, s.start, k, self._row_win, src_p, seq_p, self._row_hist, self._row_dim, self._lead,
-                                        self.guard.data_ptr(), _stream()), "lfi_stream_chunk_in")
+        if lens is not None:
+            # the round's lengths: pinned host memory of their own (the copy is asynchronous), one session-owned device buffer
+            len_dev = eng._buf_i32("chunk_lengths", B)
+            len_dev[:B].copy_(torch.tensor(lens, dtype=torch.int32).pin_memory(), non_blocking=True)
+            check(eng.L.lfi_stream_chunk_in_rows(B, m, s.start, k, self._row_win, src_p, seq_p, self._row_hist, self._row_dim,
+                                                 self._lead, self.guard.data_ptr(), len_dev.data_ptr(), _stream()),
+                  "lfi_stream_chunk_in_rows")
+        else:
+            check(eng.L.lfi_stream_chunk_in(B, m, s.start, k, self._row_win, src_p, seq_p, self._row_hist, self._row_dim, self._lead,
+                                            self.guard.data_ptr(), _stream()), "lfi_stream_chunk_in")
         eng._toc("stream_chunk_in", ev)
         pre = self._chunk_static(seqs, m, masks)
         dims, p = eng._flow_dims(B, m), eng._flow_params()
@@ -674,23 +732,69 @@ class SampleStream:
         ev = eng._tic("stream_chunk_chain")
         if self.hist1 >= 1 and eng.L.lfi_flow_score_chunk_ok(C.byref(dims)):     # (the chunk chain wants a faces window)
             work = eng._buf("chunk_work", eng.L.lfi_flow_score_chunk_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
-            check(eng.L.lfi_flow_score_seq_chunk(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
-                                                 pre.data_ptr(), faces.data_ptr(), T, s.start, m, first, self.h.data_ptr(), ptr(self.cs),
-                                                 C.byref(self._p1), None, None, work.data_ptr(), ptr(z), nll.data_ptr(), _stream()),
-                  "lfi_flow_score_seq_chunk")
+            if lens is not None:
+                check(eng.L.lfi_flow_score_seq_chunk_rows(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf,
+                                                          self.hist1, pre.data_ptr(), faces.data_ptr(), T, s.start, m, first,
+                                                          self.h.data_ptr(), ptr(self.cs), C.byref(self._p1), None, None, work.data_ptr(),
+                                                          ptr(z), nll.data_ptr(), len_dev.data_ptr(), _stream()),
+                      "lfi_flow_score_seq_chunk_rows")
+            else:
+                check(eng.L.lfi_flow_score_seq_chunk(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf,
+                                                     self.hist1, pre.data_ptr(), faces.data_ptr(), T, s.start, m, first,
+                                                     self.h.data_ptr(), ptr(self.cs), C.byref(self._p1), None, None, work.data_ptr(),
+                                                     ptr(z), nll.data_ptr(), _stream()), "lfi_flow_score_seq_chunk")
         else:
             # the per-frame kernels on the same sequences: m front ends and m chains (or Ks cells each), one frame's work areas
             work = eng._buf("chunk_frame_work", eng.L.lfi_flow_sample_work_floats(C.byref(dims)))
             p1work = eng._buf("chunk_frame_p1work", eng.L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
             score = eng._buf("chunk_frame_score", eng.L.lfi_flow_score_work_floats(C.byref(dims)))
-            check(eng.L.lfi_flow_score_seq_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
-                                                pre.data_ptr(), faces.data_ptr(), T, s.start, m, first, self.h.data_ptr(), ptr(self.cs),
-                                                C.byref(self._p1), p1work.data_ptr(), work.data_ptr(), score.data_ptr(), ptr(z),
-                                                nll.data_ptr(), _stream()), "lfi_flow_score_seq_from")
+
+            def run(o, cnt, first_frame):       # frames o .. o + cnt - 1 of the round, every row
+                check(eng.L.lfi_flow_score_seq_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf,
+                                                    self.hist1, pre.data_ptr() + 4 * o * B * s.Ks * s.D, faces.data_ptr(), T,
+                                                    s.start + o, cnt, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
+                                                    p1work.data_ptr(), work.data_ptr(), score.data_ptr(),
+                                                    None if z is None else z.data_ptr() + 4 * o * B * s.C,
+                                                    nll.data_ptr() + 4 * o * B, _stream()), "lfi_flow_score_seq_from")
+            if lens is None:
+                run(0, m, first)
+            else:
+                self._ragged_frames(run, lens, m, first, nll, z)
         eng._toc("stream_chunk_chain", ev)
-        check(eng.L.lfi_stream_chunk_out(B, m, s.start, k, self._row_win, seq_p, self._row_hist, self._row_dim, self._lead,
-                                         ptr(self.frame_nb), _stream()), "lfi_stream_chunk_out")
+        if lens is not None:
+            check(eng.L.lfi_stream_chunk_out_rows(B, m, s.start, k, self._row_win, seq_p, self._row_hist, self._row_dim, self._lead,
+                                                  ptr(self.frame_nb), len_dev.data_ptr(), _stream()), "lfi_stream_chunk_out_rows")
+        else:
+            check(eng.L.lfi_stream_chunk_out(B, m, s.start, k, self._row_win, seq_p, self._row_hist, self._row_dim, self._lead,
+                                             ptr(self.frame_nb), _stream()), "lfi_stream_chunk_out")
         self.steps += m
+
+    def _ragged_frames(self, run, lens, m, first, nll, z):
+        """A ragged round on the per-frame kernels, which know no lengths: the frames in segments between the sorted distinct
+        lengths, every row in every segment (a row behind its length runs on the zeros lfi_stream_chunk_in_rows left in the
+        sequences). After a segment the h / c rows of the rows that end there are put aside; at the end they go back, with the
+        rows of length 0 as they were before the round, and the outputs behind each length are zeroed."""
+        s, B = self.eng.spec, self.B
+        states = [t[:s.Ks * B * s.H].view(s.Ks, B, s.H) for t in (self.h, self.cs) if t is not None]
+        rows_at = collections.defaultdict(list)
+        for r, v in enumerate(lens):
+            rows_at[v].append(r)
+        index = {v: torch.tensor(rows, dtype=torch.long, device=self.device) for v, rows in rows_at.items()}
+        kept = [(index[0], [t.index_select(1, index[0]) for t in states])] if 0 in index else []
+        done = 0
+        for cut in sorted(v for v in index if v > 0):
+            run(done, cut - done, first if done == 0 else 1)
+            if cut < max(lens):                 # (the longest rows' state is where it belongs already)
+                kept.append((index[cut], [t.index_select(1, index[cut]) for t in states]))
+            done = cut
+        for idx, saved in kept:
+            for t, v in zip(states, saved):
+                t.index_copy_(1, idx, v)
+        behind = torch.arange(m).unsqueeze(1) >= torch.tensor(lens).unsqueeze(0)     # (m, B), built on the host
+        behind = behind.to(self.device)
+        nll.masked_fill_(behind, 0.0)
+        if z is not None:
+            z.masked_fill_(behind.unsqueeze(2), 0.0)
 
     def _gen_round(self, srcs, m, masks, noise, out, o, nll):
         """m generated frames of a step_many() call, inside _owned() with the chunk's workspaces as the engine's: windows in, static

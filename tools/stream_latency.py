@@ -4,7 +4,7 @@ alternative without a session: re-running SeqGlow.inference over the whole prefi
   python tools/stream_latency.py [--batches 1,16,256] [--steps 200] [--warmup 20] [--prefixes 50,150,300] [--out FILE]
                                  [--churn 1,16,64 [--churn-batch 256]] [--migrate 16 [--migrate-batch 256]] [--nll 1,256]
                                  [--observe 1,16,256] [--rows 1,16,256] [--observe-many 16,64,250]
-                                 [--step-many 4,16,64]
+                                 [--step-many 4,16,64] [--observe-ragged 16,64,250]
 
 Per batch size: the wall-clock time from step() to the generated frame on the host (a synchronise after every step: what a live agent
 waits for), its GPU time (HIP events around the step), and a per-kernel breakdown from the engine's enable_timing on an eager session
@@ -45,7 +45,15 @@ front end / chain split of one observe_many per n from the engine's enable_timin
 sessions on one seed, both one generated frame into their sequence: n step() calls in a Python loop on the one, one step_many(n) on
 the other, the same conditioning and noise, alternating which goes first, --reps times after two untimed rounds (sessions are
 reset(seed) in between, graphs kept). Per frame: wall clock and GPU time as --observe-many. Then where one step_many call's GPU time
-goes (windows in, static part, the sampler's n front ends and chains) from the engine's enable_timing."""
+goes (windows in, static part, the sampler's n front ends and chains) from the engine's enable_timing.
+
+--observe-ragged n1,n2,..: this leg ALONE, written to --out (default profiles/stream_observe_ragged.md): per batch size of --batches and
+per n, observe_many(n) with per-row lengths beside the dense call, every arm of a (B, n) on a session of its own one observed frame
+into its sequence, the order rotating, --reps times after two untimed rounds: (a) dense against lengths all n, with the dense arm's
+own rep-to-rep spread; (b) (B > 16) the first 16-row tile at length n and every other row at 0 - joiners warmed up in place - with
+its front end / chain split (LFI_CHUNK_ONLY) and, beside it, the side-session recipe: open_stream for 16 rows, observe_many, save_rows,
+load_rows into the big session; (c) lengths spread evenly over 0 .. n. Then the register figures of the dense and the ragged chain
+kernels from tools/kernel_resources.py (compiled for gfx950 while the GPU is still untouched)."""
 import argparse
 import contextlib
 import os
@@ -74,8 +82,10 @@ def main():
     ap.add_argument("--rows", default=None, help="batch sizes of the step_rows() leg, e.g. 1,16,256: runs this leg alone")
     ap.add_argument("--observe-many", default=None, help="chunk lengths of the observe_many() leg, e.g. 16,64,250: runs this leg alone")
     ap.add_argument("--step-many", default=None, help="frames per call of the step_many() leg, e.g. 4,16,64: runs this leg alone")
-    ap.add_argument("--reps", type=int, default=7, help="with --observe-many / --step-many: timed rounds per (batch size, chunk length)")
+    ap.add_argument("--observe-ragged", default=None, help="chunk lengths of the ragged observe_many() leg: runs this leg alone")
+    ap.add_argument("--reps", type=int, default=7, help="with --observe-many / --step-many / --observe-ragged: timed rounds per (batch size, chunk length)")
     a = ap.parse_args()
+    resources = chain_kernel_resources() if a.observe_ragged else None     # (compiles; before the GPU is initialised)
     import bench
     helper = bench.start_smi_helper()       # (before the GPU is initialised: see bench.py)
     import copy
@@ -127,6 +137,16 @@ def main():
         bench.stop_smi_helper(helper)
         print(text)
         out = a.out or os.path.join(ROOT, "profiles", "stream_step_many.md")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text)
+        return
+    if a.observe_ragged:
+        text = observe_ragged_report(m, dev, [int(v) for v in a.batches.split(",")], [int(v) for v in a.observe_ragged.split(",")],
+                                     a.reps, dims, start, C, torch.cuda.get_device_name(dev), resources)
+        bench.stop_smi_helper(helper)
+        print(text)
+        out = a.out or os.path.join(ROOT, "profiles", "stream_observe_ragged.md")
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as f:
             f.write(text)
@@ -650,6 +670,124 @@ def step_many_report(m, dev, batches, ns, reps, dims, start, C, device_name):
     for B, n, t in split:
         a, b, c = (t.get("stream_chunk_" + k, 0.0) for k in ("in", "static", "gen_chain"))
         lines.append("| %d | %d | %.3f | %.3f | %.3f | %.4f | %.0f %% |" % (B, n, a, b, c, c / n, 100.0 * c / max(a + b + c, 1e-9)))
+    return "\n".join(lines) + "\n"
+
+
+def chain_kernel_resources():
+    """tools/kernel_resources.py on the two chunk units, side by side -> the chain kernels' lines."""
+    import subprocess
+    units = (("lfi_flow_chunk.hip", "flow_fwd_seq_chain_kernel"), ("lfi_flow_chunk_rows.hip", "flow_fwd_seq_rows_chain_kernel"))
+    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"),
+                               os.path.join(ROOT, "lets_face_it_amd", "csrc", unit), name], stdout=subprocess.PIPE, text=True)
+             for unit, name in units]
+    return [line for p in procs for line in p.communicate()[0].splitlines() if "chain_kernel" in line]
+
+
+def observe_ragged_report(m, dev, batches, ns, reps, dims, start, C, device_name, resources):
+    """The --observe-ragged report: per (B, n) the GPU and wall time per call of the arms the module's docstring lists."""
+    import torch
+    s = m.spec
+    eng = m._ensure_engine(dev)
+    top = max(ns)
+    lines = ["# observe_many(lengths=...): ragged chunks (tools/stream_latency.py --observe-ragged)", "",
+             "final_model.yaml as shipped (C = %d, S = %d, K = %d, H = %d, D = %d), engine precision %s; every arm of a (B, n) on a "
+             "session of its own in one process, the order rotating; %d timed rounds after 2 untimed ones; per CALL: wall = call to "
+             "result on the host (one synchronise after it), GPU = HIP events around it; median (min .. max). Device %s."
+             % (C, s.S, s.Ks, s.H, s.D, m.precision, reps, device_name), "",
+             "| B | n | arm | wall ms | GPU ms | GPU ms / live frame-row x 1e3 |", "|---|---|---|---|---|---|"]
+    notes, split = [], []
+    for B in batches:
+        gd = torch.Generator().manual_seed(B + 9)
+        data = {k: torch.randn(B, start + top + 1, d, generator=gd).to(dev) for k, d in dims.items()}
+        seed = {k: v[:, :start].contiguous() for k, v in data.items()}
+        frames = [{k: v[:, start + i].contiguous() for k, v in data.items() if k != "p1_face"} for i in range(top + 1)]
+        noise = (torch.randn(top + 1, B, C, generator=gd) * 0.8).to(dev)
+        with m.open_stream(seed) as ref:
+            faces = [ref.step(frames[i], noise[i]) for i in range(top + 1)]
+        clip = torch.stack(faces, 1)
+        seed16 = {k: v[:16].contiguous() for k, v in seed.items()}
+        with contextlib.ExitStack() as stack:
+            for n in ns:
+                chunk = {k: v[:, start + 1:start + 1 + n].contiguous() for k, v in data.items() if k != "p1_face"}
+                cfaces = clip[:, 1:1 + n].contiguous()
+                chunk16, cfaces16 = {k: v[:16].contiguous() for k, v in chunk.items()}, cfaces[:16].contiguous()
+                arms = [("(a) dense", None), ("(a) lengths all n", [n] * B)]
+                if B > 16:
+                    arms.append(("(b) rows 0 .. 15 at n, %d rows at 0" % (B - 16), [n] * 16 + [0] * (B - 16)))
+                    arms.append(("(b) side session: open_stream(16 rows), observe_many, save_rows, load_rows", "side"))
+                arms.append(("(c) lengths spread evenly over 0 .. n", [round(r * n / (B - 1)) if B > 1 else n // 2 for r in range(B)]))
+                sessions = {name: stack.enter_context(m.open_stream(seed)) for name, _ in arms}
+                legs = {name: ([], []) for name, _ in arms}
+
+                def call(st, lens):
+                    if lens == "side":
+                        with m.open_stream(seed16) as side:
+                            side.observe(frames16[0], faces16[0])
+                            side.observe_many(chunk16, cfaces16)
+                            st.load_rows(list(range(16)), side.save_rows(list(range(16))))
+                    else:
+                        st.observe_many(chunk, cfaces, lengths=lens)
+                frames16, faces16 = [{k: v[:16].contiguous() for k, v in frames[0].items()}], [faces[0][:16].contiguous()]
+                k = len(arms)
+                for r in range(reps + 2):
+                    for name, lens in arms[r % k:] + arms[:r % k]:
+                        st = sessions[name]
+                        st.reset(seed)
+                        st.observe(frames[0], faces[0])
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        e0.record()
+                        call(st, lens)
+                        e1.record()
+                        e1.synchronize()
+                        t1 = time.perf_counter()
+                        if r >= 2:
+                            legs[name][0].append((t1 - t0) * 1e3)
+                            legs[name][1].append(e0.elapsed_time(e1))
+                fmt = lambda v: "%.3f (%.3f .. %.3f)" % (statistics.median(v), min(v), max(v))
+                for name, lens in arms:
+                    live = n * B if lens is None else 16 * n if lens == "side" else sum(lens)
+                    lines.append("| %d | %d | %s | %s | %s | %.3f |" % (B, n, name, fmt(legs[name][0]), fmt(legs[name][1]),
+                                                                      1e3 * statistics.median(legs[name][1]) / max(live, 1)))
+                dense, full = legs["(a) dense"][1], legs["(a) lengths all n"][1]
+                diff, spread = statistics.median(full) - statistics.median(dense), max(dense) - min(dense)
+                notes.append("- B = %d, n = %d: lengths all n %+.3f ms GPU against dense; the dense arm's own spread over its %d rounds is "
+                             "%.3f ms: %s." % (B, n, diff, reps, spread, "inside it" if abs(diff) <= spread else "BEYOND it"))
+                if B > 16:
+                    # the front end / chain split of arm (b): each part alone (LFI_CHUNK_ONLY, honoured by the ragged entry point as by
+                    # the dense one), the chain on the gic a whole call left in the work area
+                    name, lens = arms[2]
+                    st = sessions[name]
+                    st.reset(seed)
+                    st.observe(frames[0], faces[0])
+                    st.observe_many(chunk, cfaces, lengths=lens)
+                    parts = {}
+                    for part in ("chain", "front"):
+                        os.environ["LFI_CHUNK_ONLY"] = part
+                        try:
+                            eng.enable_timing(True)
+                            st.observe_many(chunk, cfaces, lengths=lens)
+                            summary = eng.timing_summary()
+                        finally:
+                            eng.enable_timing(False)
+                            del os.environ["LFI_CHUNK_ONLY"]
+                        got = summary.get("stream_chunk_chain")
+                        parts[part] = got[0] * got[1] if got else 0.0
+                        if part == "front":
+                            for t in ("stream_chunk_in", "stream_chunk_static"):
+                                parts[t] = summary[t][0] * summary[t][1] if t in summary else 0.0
+                    split.append((B, n, parts))
+                for st in sessions.values():
+                    st.close()
+    lines += ["", "## (a) Dense against lengths all n", ""] + notes
+    if split:
+        lines += ["", "## (b) Where the GPU time of the one-live-tile call goes (enable_timing, HIP events; ms per call)", "",
+                  "The front end stays dense over n * B windows whatever the lengths; the chain runs one tile.", "",
+                  "| B | n | windows in | static part | front end alone | chain alone (one launch, one live tile) |", "|---|---|---|---|---|---|"]
+        for B, n, t in split:
+            lines.append("| %d | %d | %.3f | %.3f | %.3f | %.3f |" % (B, n, t["stream_chunk_in"], t["stream_chunk_static"], t["front"], t["chain"]))
+    lines += ["", "## Register figures of the two chain kernels (tools/kernel_resources.py, gfx950)", "", "```"] + (resources or []) + ["```"]
     return "\n".join(lines) + "\n"
 
 
