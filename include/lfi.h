@@ -504,6 +504,22 @@ int lfi_flow_step_rows_from(const lfi_flow_dims* d, const lfi_flow_params* p, co
                             float* faces, int seq_len, int start, int nframes, int first_frame,
                             float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
                             float* nll, float* nll_work, const int* observed, float* rows_work, void* stream);
+/* A run of nframes >= 1 frames of a chunk in which every batch row takes its role FRAME BY FRAME (SampleStream.step_rows_many): it
+ * replaces a host loop of nframes lfi_flow_step_rows_from calls - the same launches, from one call with one argument check, one kernel
+ * pick and one preparation of the fused conditioning kernel's weight fragments. lfi_flow_step_rows_from's arguments, frame-major:
+ * pre_static has nframes * B rows, noise is nframes x B x C, nll nframes x B, observed nframes x B ints (!= 0 = row b's frame n is
+ * GIVEN, in faces[:, start + n] already). Per frame n: the conditioning front end at t = start + n on that frame's rows of pre_static,
+ * the chain-state clear, one flow_rows_chain_kernel launch with that frame's role, noise and nll rows, has_prev = first_frame + n > 0
+ * and frame_no = first_frame + n; LFI_SAMPLE_CHAIN=0 and the generic cell: the per-step launches and the merge launch, per frame.
+ * The work areas are ONE frame's (lfi_flow_step_rows_work_floats, lfi_flow_sample_nll_work_floats, lfi_flow_sample_work_floats),
+ * reused from frame to frame; the stream orders them. The window-fragment hand-over of the reverse chain is not used (a frame may
+ * have been observed). lfi_flow_step_rows_from is the nframes = 1 call of the same body. Allocation-free; every argument is checked
+ * before the first launch. */
+int lfi_flow_step_rows_seq(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep,
+                            const float* wct, long E, int hist1, float* pre_static, const float* noise,
+                            float* faces, int seq_len, int start, int nframes, int first_frame,
+                            float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
+                            float* nll, float* nll_work, const int* observed, float* rows_work, void* stream);
 /* One frame forward of a streaming sampling session (SeqGlow.open_stream; glow/models.py:567-596 one frame at a time), in ONE launch:
  * every window i (B x hist[i] x dim[i], rows per batch entry) moves up by one frame in place, and its last row receives src[i] (B x
  * dim[i]), or - src[i] == NULL, the prev_p1_face window of the session's own output - keeps the frame the last step generated there;
@@ -567,6 +583,19 @@ int lfi_stream_chunk_gen_out(int B, int n, int start, int count, float* const* w
                              const int* hist, const int* dim, const int* lead, int gen_win,
                              float* out /* B x n x C, row pitch ld_out floats */, long ld_out,
                              float* frame_nb, unsigned* guard_bits, void* stream);
+/* The window launch INTO a chunk of n >= 1 frames whose rows observe or generate frame by frame (SampleStream.step_rows_many): it
+ * replaces n lfi_stream_advance_rows launches. lfi_stream_chunk_gen_in's arguments and roles (n x B ints on the device, frame-major,
+ * != 0 = the row observes that frame), required; unlike gen_in, src[gen_win] (the given faces, B x n x C) is required too. Every
+ * conditioning window is laid out as in gen_in. Of gen_win the live frames go into seq[gen_win]; then, frame by frame: where
+ * roles[f * B + b] != 0 the given frame goes to frame start + f of the sequence and is folded into *guard_bits; elsewhere the slot is
+ * left alone - lfi_flow_step_rows_seq writes it - the given frame is not read, and the row's noise of that frame is folded instead.
+ * Only values that are used reach the guard word. The way out is lfi_stream_chunk_gen_out as it is (all n frames of the faces
+ * sequence go to `out` and are folded; a given frame folded twice changes nothing in a maximum). One launch, allocation-free; every
+ * argument is checked before the launch. */
+int lfi_stream_chunk_roles_in(int B, int n, int start, int count, float* const* win, const float* const* src, float* const* seq,
+                            const int* hist, const int* dim, const int* lead, int gen_win,
+                            const float* noise /* n x B x C, frame-major, already * eps */, int C,
+                            const int* roles, unsigned* guard_bits, void* stream);
 /* Reseed listed batch rows of a streaming sampling session (SampleStream.reset_rows; the start of glow/models.py:567-596 for those
  * rows alone) between steps: each session row rows[j] (0 <= rows[j] < B, none twice, nrows >= 1) gets the state open_stream gives
  * a row, from entry j of the caller's seed, and no other row is written. Per window i (count <= 8; the layout of lfi_stream_advance):

@@ -1192,24 +1192,26 @@ extern "C" long lfi_flow_step_rows_work_floats(const lfi_flow_dims* d) {
   return rows_work_carve(nullptr, d->B, d->C, d->H, d->Ks).total;
 }
 
-// One frame (nframes = 1) in which row b observes where observed[b] != 0 - its frame is in faces[:, start] already - and generates from
-// noise[b] otherwise: lfi_flow_sample_seq_nll's arguments, the role words and a second work area (lfi_flow_step_rows_work_floats).
-// Every row's h / cstate, frame and nll (B, required) are what lfi_flow_score_seq_from or lfi_flow_sample_seq_nll alone leaves for it.
-// The conditioning front end once, then flow_rows_chain_kernel; shapes and switches outside the chain: the forward direction's
-// per-step launches on copies of h / cstate, the reverse direction's on the state itself with its frame aside, one merge launch.
-extern "C" int lfi_flow_step_rows_from(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct, long E,
-                                       int hist1, float* pre_static, const float* noise, float* faces, int seq_len, int start,
-                                       int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1, float* p1work,
-                                       float* work, float* nll, float* nll_work, const int* observed, float* rows_work, void* stream) {
+// nframes >= 1 frames in which row b observes frame n where observed[n * B + b] != 0 - that frame is in faces[:, start + n] already - and
+// generates it from noise[n][b] otherwise: the one body of lfi_flow_step_rows_from (nframes = 1) and lfi_flow_step_rows_seq. Per frame:
+// the conditioning front end, the chain-state clear, then flow_rows_chain_kernel with that frame's role, noise and nll rows; shapes and
+// switches outside the chain: the forward direction's per-step launches on copies of h / cstate, the reverse direction's on the state
+// itself with its frame aside, one merge launch. The work areas are one frame's, reused from frame to frame: the stream orders them,
+// as in lfi_flow_sample_seq_nll's loop. have_xfrag stays 0: the reverse chain's window-fragment hand-over has no forward-direction
+// counterpart, and a frame a row observed never passes through the chain that would leave its fragments.
+namespace {
+int step_rows_frames(const char* who, const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct, long E,
+                     int hist1, float* pre_static, const float* noise, float* faces, int seq_len, int start, int nframes,
+                     int first_frame, float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work, float* nll,
+                     float* nll_work, const int* observed, float* rows_work, void* stream) {
   FlowK f = {};
-  int rc = fill_flow(d, p, prep, &f, "lfi_flow_step_rows_from");
+  int rc = fill_flow(d, p, prep, &f, who);
   if (rc) return rc;
-  const char* who = "lfi_flow_step_rows_from";
   if ((rc = frame_args_check(who, who, d, prep && wct && pre_static && noise && faces && h && work && nll && nll_work && observed && rows_work,
                              E, hist1, start, nframes, seq_len, cstate, first_frame))) return rc;
-  LFI_REQUIRE(nframes == 1, "%s: %d frames (one frame per call)", who, nframes);
+  LFI_REQUIRE(nframes >= 1, "%s: %d frames (at least one)", who, nframes);
   LFI_REQUIRE((reinterpret_cast<uintptr_t>(rows_work) & 3) == 0, "%s: rows_work is not 4-byte aligned", who);
-  const int B = f.B, C = f.C, H = f.H, Ks = f.Ks;
+  const int B = f.B, C = f.C, D = f.D, H = f.H, Ks = f.Ks;
   hipStream_t st = (hipStream_t)stream;
   const bool fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
   const bool chain = fast && lfi_env_on("LFI_SAMPLE_CHAIN");
@@ -1222,48 +1224,80 @@ extern "C" int lfi_flow_step_rows_from(const lfi_flow_dims* d, const lfi_flow_pa
   const FlowRowsChainKernel chain_kernel = flow_rows_chain_pick(f.lstm, x3, xw, x3f);
   const FlowStepKernel rev_cell = flow_step_rev_pick(fast, f.lstm);
   if (chain) {
-    if ((rc = set_flow_lds(chain_kernel, lds_fast, "lfi_flow_step_rows_from"))) return rc;
+    if ((rc = set_flow_lds(chain_kernel, lds_fast, who))) return rc;
   } else {
-    if ((rc = set_flow_lds(rev_cell, fast ? lds_fast : lds_gen, "lfi_flow_step_rows_from"))) return rc;
-    if ((rc = set_flow_lds(flow_step_kernel<false>, lds_gen, "lfi_flow_step_rows_from"))) return rc;
+    if ((rc = set_flow_lds(rev_cell, fast ? lds_fast : lds_gen, who))) return rc;
+    if ((rc = set_flow_lds(flow_step_kernel<false>, lds_gen, who))) return rc;
   }
   const RowsWork rw = rows_work_carve(rows_work, B, C, H, Ks);
   SampleFront sf = {};
   if ((rc = sample_front_setup(&sf, d, p, &f, wct, E, hist1, pre_static, faces, seq_len, p1, p1work, work, chain, nframes, stream,
-                               "lfi_flow_step_rows_from", chain ? rw.pipe : nullptr, (size_t)rw.pipe_words))) return rc;
-  const int t = start;
-  const int has_prev = first_frame > 0 ? 1 : 0;
-  if ((rc = sample_front_frame(sf, t, pre_static, 0, stream))) return rc;
-  float* frame = faces + (long)t * C;
+                               who, chain ? rw.pipe : nullptr, (size_t)rw.pipe_words))) return rc;
   const long ld_frame = (long)seq_len * C;
-  if (chain) {
-    RowsChain rcn = {};
-    rcn.role = observed;
-    rcn.rev.noise = noise; rcn.rev.xa = sf.xa; rcn.rev.xb = sf.xb; rcn.rev.frame = frame; rcn.rev.ld_frame = ld_frame;
-    rcn.rev.gic = sf.gic; rcn.rev.h = h; rcn.rev.cstate = cstate; rcn.rev.has_prev = has_prev; rcn.rev.frame_no = first_frame;
-    rcn.rev.pipe = rw.pipe; rcn.rev.qa = nll_work; rcn.rev.qb = nll_work + B; rcn.rev.nll = nll;
-    rcn.fwd.frame = frame; rcn.fwd.ld_frame = ld_frame; rcn.fwd.xa = rw.xa; rcn.fwd.xb = rw.xb; rcn.fwd.gic = sf.gic;
-    rcn.fwd.h = h; rcn.fwd.cstate = cstate; rcn.fwd.has_prev = has_prev; rcn.fwd.pipe = rw.pipe;
-    rcn.fwd.qa = rw.qa; rcn.fwd.qb = rw.qb; rcn.fwd.nll = nll;
-    if ((rc = sample_front_clear_chain(sf, st, who))) return rc;   // (sf's chain words are rw.pipe here)
-    hipLaunchKernelGGL(chain_kernel, dim3(2 * Ks * f.nbt), dim3(NT), lds_fast, st, f, rcn);
-    LFI_LAUNCH_CHECK("lfi_flow_step_rows_from");
-    return LFI_OK;
-  }
-  // ---- per-step launches. The forward direction first: it reads the observed frame and the state of the frame before
   const size_t state_bytes = (size_t)Ks * B * H * sizeof(float);
-  if (has_prev) {
-    hipError_t me = hipMemcpyAsync(rw.hs, h, state_bytes, hipMemcpyDeviceToDevice, st);
-    if (me == hipSuccess && f.lstm) me = hipMemcpyAsync(rw.cs, cstate, state_bytes, hipMemcpyDeviceToDevice, st);
-    LFI_REQUIRE(me == hipSuccess, "lfi_flow_step_rows_from: hipMemcpyAsync: %s", hipGetErrorString(me));
+  for (int n = 0; n < nframes; ++n) {
+    const int t = start + n;
+    const int has_prev = first_frame + n > 0 ? 1 : 0;
+    const int* role = observed + (long)n * B;
+    const float* noise_n = noise + (long)n * B * C;
+    float* nll_n = nll + (long)n * B;
+    if ((rc = sample_front_frame(sf, t, pre_static + (long)n * B * Ks * D, 0, stream))) return rc;
+    float* frame = faces + (long)t * C;
+    if (chain) {
+      RowsChain rcn = {};
+      rcn.role = role;
+      rcn.rev.noise = noise_n; rcn.rev.xa = sf.xa; rcn.rev.xb = sf.xb; rcn.rev.frame = frame; rcn.rev.ld_frame = ld_frame;
+      rcn.rev.gic = sf.gic; rcn.rev.h = h; rcn.rev.cstate = cstate; rcn.rev.has_prev = has_prev; rcn.rev.frame_no = first_frame + n;
+      rcn.rev.pipe = rw.pipe; rcn.rev.qa = nll_work; rcn.rev.qb = nll_work + B; rcn.rev.nll = nll_n;
+      rcn.fwd.frame = frame; rcn.fwd.ld_frame = ld_frame; rcn.fwd.xa = rw.xa; rcn.fwd.xb = rw.xb; rcn.fwd.gic = sf.gic;
+      rcn.fwd.h = h; rcn.fwd.cstate = cstate; rcn.fwd.has_prev = has_prev; rcn.fwd.pipe = rw.pipe;
+      rcn.fwd.qa = rw.qa; rcn.fwd.qb = rw.qb; rcn.fwd.nll = nll_n;
+      if ((rc = sample_front_clear_chain(sf, st, who))) return rc;   // (sf's chain words are rw.pipe here)
+      hipLaunchKernelGGL(chain_kernel, dim3(2 * Ks * f.nbt), dim3(NT), lds_fast, st, f, rcn);
+      continue;
+    }
+    // ---- per-step launches. The forward direction first: it reads the observed frame and the state of the frame before
+    if (has_prev) {
+      hipError_t me = hipMemcpyAsync(rw.hs, h, state_bytes, hipMemcpyDeviceToDevice, st);
+      if (me == hipSuccess && f.lstm) me = hipMemcpyAsync(rw.cs, cstate, state_bytes, hipMemcpyDeviceToDevice, st);
+      LFI_REQUIRE(me == hipSuccess, "%s: hipMemcpyAsync: %s", who, hipGetErrorString(me));
+    }
+    const float* zlast = launch_fwd_steps(f, flow_step_kernel<false>, lds_gen, st, sf.gic, rw.hs, rw.cs, has_prev, rw.xa, rw.xb, frame, ld_frame, rw.qa);
+    hipLaunchKernelGGL(score_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, zlast, rw.qa, f.ldconst, B, C, (float*)nullptr, rw.fnll);
+    // ---- the reverse direction on the state itself, its frame aside (the observing rows' frame stays in `faces`)
+    launch_rev_steps(f, rev_cell, fast ? lds_fast : lds_gen, st, sf.gic, h, cstate, has_prev, sf.xa, sf.xb, noise_n, C, rw.gframe, C, nll_work);
+    hipLaunchKernelGGL(sample_nll_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, noise_n, nll_work, f.ldconst, B, C, nll_n);
+    hipLaunchKernelGGL(rows_merge_kernel, dim3(B), dim3(256), 0, st, role, B, C, H, Ks, h, cstate, rw.hs, rw.cs, frame, ld_frame,
+                       rw.gframe, nll_n, rw.fnll);
   }
-  const float* zlast = launch_fwd_steps(f, flow_step_kernel<false>, lds_gen, st, sf.gic, rw.hs, rw.cs, has_prev, rw.xa, rw.xb, frame, ld_frame, rw.qa);
-  hipLaunchKernelGGL(score_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, zlast, rw.qa, f.ldconst, B, C, (float*)nullptr, rw.fnll);
-  // ---- the reverse direction on the state itself, its frame aside (the observing rows' frame stays in `faces`)
-  launch_rev_steps(f, rev_cell, fast ? lds_fast : lds_gen, st, sf.gic, h, cstate, has_prev, sf.xa, sf.xb, noise, C, rw.gframe, C, nll_work);
-  hipLaunchKernelGGL(sample_nll_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, noise, nll_work, f.ldconst, B, C, nll);
-  hipLaunchKernelGGL(rows_merge_kernel, dim3(B), dim3(256), 0, st, observed, B, C, H, Ks, h, cstate, rw.hs, rw.cs, frame, ld_frame,
-                     rw.gframe, nll, rw.fnll);
-  LFI_LAUNCH_CHECK("lfi_flow_step_rows_from");
+  LFI_LAUNCH_CHECK(who);
   return LFI_OK;
+}
+}  // namespace
+
+// One frame (nframes = 1) in which row b observes where observed[b] != 0 - its frame is in faces[:, start] already - and generates from
+// noise[b] otherwise: lfi_flow_sample_seq_nll's arguments, the role words and a second work area (lfi_flow_step_rows_work_floats).
+// Every row's h / cstate, frame and nll (B, required) are what lfi_flow_score_seq_from or lfi_flow_sample_seq_nll alone leaves for it.
+// The one-frame call of step_rows_frames: the conditioning front end once, then flow_rows_chain_kernel (or the per-step launches).
+extern "C" int lfi_flow_step_rows_from(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct, long E,
+                                       int hist1, float* pre_static, const float* noise, float* faces, int seq_len, int start,
+                                       int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1, float* p1work,
+                                       float* work, float* nll, float* nll_work, const int* observed, float* rows_work, void* stream) {
+  const char* who = "lfi_flow_step_rows_from";
+  LFI_REQUIRE(nframes == 1, "%s: %d frames (one frame per call)", who, nframes);
+  return step_rows_frames(who, d, p, prep, wct, E, hist1, pre_static, noise, faces, seq_len, start, nframes, first_frame, h, cstate, p1,
+                          p1work, work, nll, nll_work, observed, rows_work, stream);
+}
+
+// A run of nframes >= 1 frames of a chunk whose rows take their roles frame by frame (SampleStream.step_rows_many): what a host loop
+// of nframes lfi_flow_step_rows_from calls launches, in one call with one argument check, one kernel pick and - for the fused
+// conditioning kernel - one preparation of the weight fragments. lfi_flow_step_rows_from's arguments; pre_static has nframes * B rows,
+// noise is nframes x B x C, nll nframes x B and observed nframes x B ints, all frame-major. Frame n runs at t = start + n with
+// has_prev = first_frame + n > 0 and frame_no = first_frame + n; the work areas are one frame's.
+extern "C" int lfi_flow_step_rows_seq(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct, long E,
+                                      int hist1, float* pre_static, const float* noise, float* faces, int seq_len, int start,
+                                      int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1, float* p1work,
+                                      float* work, float* nll, float* nll_work, const int* observed, float* rows_work, void* stream) {
+  return step_rows_frames("lfi_flow_step_rows_seq", d, p, prep, wct, E, hist1, pre_static, noise, faces, seq_len, start, nframes,
+                          first_frame, h, cstate, p1, p1work, work, nll, nll_work, observed, rows_work, stream);
 }

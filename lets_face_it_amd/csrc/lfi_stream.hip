@@ -269,6 +269,46 @@ __global__ __launch_bounds__(256) void stream_chunk_gen_in_kernel(StreamChunk w,
   if (guard) stream_guard_fold(m, guard);
 }
 
+// ---- a chunk of n frames in which every row observes or generates FRAME BY FRAME (SampleStream.step_rows_many): what n
+// stream_advance_rows_kernel launches move, in one. Every window but gen_win as stream_chunk_in_kernel. Workgroup (gen_win, b) lays out
+// the live frames, then goes through the chunk: where roles[f * B + b] != 0 (n x B ints, frame-major) the row's given frame f (src, B x
+// n x dim) goes into the sequence and into the guard word; elsewhere the slot is left alone - the rows chain writes it - the given
+// frame is not read, and the row's noise of that frame (n x B x C, read in place) is folded instead. Only values that are used reach
+// the guard word.
+__global__ __launch_bounds__(256) void stream_chunk_roles_in_kernel(StreamChunk w, int n, int start, int gen_win, int B,
+                                                                   const float* __restrict__ noise, const int* __restrict__ roles,
+                                                                   unsigned* __restrict__ guard) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x;
+  const int dim = w.dim[i];
+  const long live = (long)(w.hist[i] - w.lead[i]) * dim, fresh = (long)n * dim;
+  const float* win = w.win[i] + ((long)b * w.hist[i] + w.lead[i]) * dim;
+  const float* src = w.src[i] + (long)b * fresh;
+  float* seq = w.seq[i] + (long)b * (start + n) * dim + (long)start * dim;
+  for (long j = threadIdx.x; j < live; j += 256) seq[j - live] = win[j];
+  unsigned m = 0u;
+  if (i != gen_win) {
+    for (long j = threadIdx.x; j < fresh; j += 256) {
+      const float v = src[j];
+      seq[j] = v;
+      const unsigned a = stream_abs_bits(v);
+      m = a > m ? a : m;
+    }
+  } else {
+    for (int f = 0; f < n; ++f) {
+      const bool observes = roles[(long)f * B + b] != 0;      // (uniform over the workgroup)
+      const float* row = observes ? src + (long)f * dim : noise + ((long)f * B + b) * dim;      // (dim[gen_win] == C)
+      for (int j = threadIdx.x; j < dim; j += 256) {
+        const float v = row[j];
+        if (observes) seq[(long)f * dim + j] = v;
+        const unsigned a = stream_abs_bits(v);
+        m = a > m ? a : m;
+      }
+    }
+  }
+  if (guard) stream_guard_fold(m, guard);
+}
+
 // Out: stream_chunk_out_kernel, and workgroup (gen_win, b) also hands the n generated frames of row b to the caller (out + b * ld_out,
 // n x C) and folds them into the guard word: what the next one-frame advance does with a frame step() generated.
 __global__ __launch_bounds__(256) void stream_chunk_gen_out_kernel(StreamChunk w, int n, int start, int gen_win, float* __restrict__ out,
@@ -721,6 +761,28 @@ extern "C" int lfi_stream_chunk_gen_in(int B, int n, int start, int count, float
   hipLaunchKernelGGL(stream_chunk_gen_in_kernel, dim3(count, B), dim3(256), 0, (hipStream_t)stream, w, n, start, gen_win, B, noise,
                      guard_bits);
   LFI_LAUNCH_CHECK("lfi_stream_chunk_gen_in");
+  return LFI_OK;
+}
+
+extern "C" int lfi_stream_chunk_roles_in(int B, int n, int start, int count, float* const* win, const float* const* src, float* const* seq,
+                                         const int* hist, const int* dim, const int* lead, int gen_win, const float* noise, int C,
+                                         const int* roles, unsigned* guard_bits, void* stream) {
+  StreamChunk w = {};
+  const int rc = stream_chunk_args("lfi_stream_chunk_roles_in", B, n, start, count, win, seq, hist, dim, lead, &w);
+  if (rc != LFI_OK) return rc;
+  LFI_REQUIRE(src && noise, "lfi_stream_chunk_roles_in: null pointer (source table / noise)");
+  LFI_REQUIRE(roles, "lfi_stream_chunk_roles_in: null pointer (roles)");
+  LFI_REQUIRE(gen_win >= 0 && gen_win < count, "lfi_stream_chunk_roles_in: generated window %d of %d", gen_win, count);
+  LFI_REQUIRE(C > 0 && dim[gen_win] == C, "lfi_stream_chunk_roles_in: generated window %d has dim %d, the noise C = %d", gen_win,
+              dim[gen_win], C);
+  for (int i = 0; i < count; ++i) {
+    // (the generated window's source is required here: the given frames of the rows that observe)
+    LFI_REQUIRE(src[i], "lfi_stream_chunk_roles_in: null pointer (source %d)", i);
+    w.src[i] = src[i];
+  }
+  hipLaunchKernelGGL(stream_chunk_roles_in_kernel, dim3(count, B), dim3(256), 0, (hipStream_t)stream, w, n, start, gen_win, B, noise,
+                     roles, guard_bits);
+  LFI_LAUNCH_CHECK("lfi_stream_chunk_roles_in");
   return LFI_OK;
 }
 

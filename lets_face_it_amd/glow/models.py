@@ -582,7 +582,17 @@ class SeqGlow(nn.Module):
         step_many(frames, noise=None) is n step() calls in one for conditioning known ahead (a look-ahead buffer, a rollout between
         save_rows and load_rows, finishing a clip): frames {modality: (B, n, dim)}, noise (n, B, C) as inference()'s or None (n draws
         of the session's own) -> out (B, n, C), or (out, nll) with nll (n, B) under return_nll=True. It leaves the session where n
-        step() calls leave it (steps += n), with the static part run once for the chunk; eager launches, no graph."""
+        step() calls leave it (steps += n), with the static part run once for the chunk; eager launches, no graph.
+
+        step_rows(frame, face, observed, noise=None) is one frame in which every row observes (observed[r] true: row r takes face[r])
+        or generates (from noise[r]) -> (out, nll), both always. step_rows_many(frames, faces, observed, noise=None) is n such
+        steps in one call for frames known ahead: frames {modality: (B, n, dim)}, faces (B, n, C), noise (n, B, C) or None,
+        observed HOST data - an (n, B) CPU torch.bool tensor or n sequences of B bools, frame-major, True = the row observes that
+        frame; prompt then continue with a prompt length per row is observed = torch.arange(n)[:, None] < lengths[None, :] ->
+        (out, nll), out (B, n, C) the frames that entered the faces window, given or generated, nll (n, B). It leaves the session
+        where n step_rows() calls leave it (steps += n): the static part once per chunk, runs of frames every row observes on the
+        chunk forward chain, everything else on the rows chain frame by frame (st.last_plan shows the split); eager launches, no
+        graph. All six kinds of call alternate freely."""
         _engine.check_return_nll(return_nll)
         p1 = seed.get("p1_face") if isinstance(seed, dict) else None
         if p1 is None:

@@ -59,6 +59,26 @@ def _index_list(name, idx, bound, where, count=None, distinct=True):
     return idx
 
 
+def plan_rows_many(all_observe, min_run):
+    """The plan of a step_rows_many() round, a pure function of the mask (no device): all_observe[i] is true where EVERY row observes
+    frame i. Maximal runs of at least min_run such frames go to the chunk forward chain (n + Ks - 1 cell times and one front end for
+    n frames), everything else to the rows chain (n Ks cell times, n front ends); min_run 0 never uses the chunk chain. ->
+    [(kind, first, count), ...] with kind "observe" or "rows", in frame order, covering every frame once."""
+    flags = [bool(v) for v in all_observe]
+    plan, i, n = [], 0, len(flags)
+    while i < n:
+        j = i + 1
+        while j < n and flags[j] == flags[i]:
+            j += 1
+        kind = "observe" if flags[i] and min_run > 0 and j - i >= min_run else "rows"
+        if plan and kind == "rows" and plan[-1][0] == "rows":
+            plan[-1] = ("rows", plan[-1][1], plan[-1][2] + j - i)
+        else:
+            plan.append((kind, i, j - i))
+        i = j
+    return plan
+
+
 class StreamRows:
     """The live state of n conversations taken out of a streaming session (SampleStream.save_rows): `data`, one contiguous float32
     (n, R) tensor of records, and `signature`, the record layout (C, H, Ks, rnn_type, use_frame_nb, ((name, hist, dim), ...), hist1,
@@ -155,6 +175,7 @@ class SampleStream:
         self.score_work = self.obs_z = self.obs_nll = None   # observe()'s buffers: allocated at the first observe
         self.role = self.rows_work = self.rows_nll = self.rows_nll_work = None   # step_rows()'s: at the first step_rows
         self._chunk_ws = {}                     # observe_many()'s / step_many()'s workspaces, sized by the chunk (the graphs never address them)
+        self.last_plan = None                   # diagnostic: the last step_rows_many() call's plan (plan_rows_many), offsets in the call
         self._stream = None
         self._guard_pending = None
         self._state = {"_ws": {}, "prep": None, "wct_f": torch.zeros_like(eng.wct_f), "_wct_planes": None, "_wc_r": None,
@@ -649,6 +670,183 @@ class SampleStream:
                 x.record_stream(torch.cuda.current_stream(self.device))
         self._record_out(out, nll)
         return (out, nll) if self.return_nll else out
+
+    def _check_observed_many(self, observed, n):
+        """The role mask of step_rows_many(), checked before any launch: host data, an (n, B) CPU torch.bool tensor or a sequence of n
+        sequences of B bools, frame-major -> an (n, B) CPU bool tensor."""
+        B = self.B
+        kind = "observed: expected an (n, B) CPU torch.bool tensor or a sequence of n sequences of B bools, frame-major, got %s"
+        if torch.is_tensor(observed):
+            if observed.is_cuda:
+                raise ValueError("observed: on %s - step_rows_many() takes its role mask as host data (it plans the chunk's launches "
+                                 "from it), as observe_many() takes lengths; step_rows() is the call for device-resident masks"
+                                 % observed.device)
+            if observed.dtype != torch.bool:
+                raise TypeError(kind % ("a %s tensor" % observed.dtype))
+            if observed.device.type != "cpu":
+                raise ValueError("observed: on %s, expected host data" % observed.device)
+            if tuple(observed.shape) != (n, B):
+                raise ValueError("observed: expected (n, B) = (%d, %d), frame-major, got %s" % (n, B, tuple(observed.shape)))
+            return observed.contiguous()
+        try:
+            rows = [list(r) for r in observed]
+        except TypeError:
+            raise TypeError(kind % type(observed).__name__) from None
+        if len(rows) != n or any(len(r) != B for r in rows):
+            raise ValueError("observed: expected (n, B) = (%d, %d), frame-major, got rows of %s entries"
+                             % (n, B, [len(r) for r in rows]))
+        if any(not isinstance(v, bool) for r in rows for v in r):
+            raise TypeError(kind % repr(observed))
+        return torch.tensor(rows, dtype=torch.bool).view(n, B)
+
+    @staticmethod
+    def _rows_many_min_run():
+        """The shortest run of all-observe frames step_rows_many() gives to the chunk forward chain: 2, the smallest run for which n +
+        Ks - 1 cell times and one front end beat n Ks and n; LFI_ROWS_MANY_OBSERVE_RUN overrides, 0 never uses the chunk chain."""
+        env = os.environ.get("LFI_ROWS_MANY_OBSERVE_RUN")
+        if not env:
+            return 2
+        run = int(env)
+        if run < 0:
+            raise ValueError("LFI_ROWS_MANY_OBSERVE_RUN: %r is not a frame count" % env)
+        return run
+
+    @translate_oom
+    def step_rows_many(self, frames, faces, observed, noise=None):
+        """n frames in one call in which every row takes its own role FRAME BY FRAME, for frames known ahead (a look-ahead buffer over
+        a batch in which some conversations speak while others listen; prompt then continue: each row observes its own recorded
+        history, of its own length, and generates the rest): exactly what n successive step_rows(frame_i, face_i, observed[i],
+        noise_i) calls do to the session - the conditioning windows, the faces window, h / c, the frame counter (+= 2 n), `steps`
+        += n - so all six kinds of call alternate freely and save_rows / load_rows / reset_rows work as before. frames: as
+        step_many()'s, {modality: (B, n, dim)}; faces: as observe_many()'s, (B, n, C), read only where a row observes; noise: as
+        step_many()'s, (n, B, C) or None (n draws of the session's own, stacked, whatever the mask says - as step_rows draws on
+        every call), read only where a row generates; observed: HOST data, as lengths and rows are - an (n, B) CPU torch.bool tensor
+        or a sequence of n sequences of B bools, frame-major like nll, True = the row observes that frame (a CUDA tensor is
+        refused: step_rows() takes device-resident masks). The prompt-then-continue mask of per-row prompt lengths is
+            observed = torch.arange(n)[:, None] < lengths[None, :]
+        -> (out, nll), always both whatever return_nll the session was opened with, as step_rows: out (B, n, C) the frame that
+        entered each row's faces window, given (a copy of `faces` there) or generated; nll (n, B) every frame's NLL in bits. `faces`
+        at generating slots and `noise` at observing slots are never read into anything stored and do not reach the range guard:
+        anything, NaN included.
+
+        Per round of at most _chunk_cap() frames: the role words to a session-owned buffer (pinned host memory, asynchronously),
+        lfi_stream_chunk_roles_in (the windows as sequences; given frames enter the faces sequence where their row observes), the
+        static part in sequence mode ONCE for the round, then the round's plan (plan_rows_many; kept, rounds concatenated and with
+        offsets in the call, in `last_plan` - a diagnostic): maximal runs of at least 2 frames that EVERY row observes go to
+        lfi_flow_score_seq_chunk (LFI_ROWS_MANY_OBSERVE_RUN overrides the 2, 0 = never; never where that chain does not run),
+        everything else - all-generate runs included: step_many() is for callers who know that nobody observes - to
+        lfi_flow_step_rows_seq, the rows chain frame by frame; then lfi_stream_chunk_gen_out. Eager launches: no graph is captured,
+        `replays` does not count them, and the graphs of the per-frame calls stay valid. With a fixed plan a row's values do not
+        depend on the other rows' roles or inputs (rows never mix in a cell, and the dense static part runs the same shapes);
+        across plans, and against the per-frame calls, values agree to the session's gates, not bit for bit (the batched front end
+        and the sequence-mode static part sum in another order, as for step_many / observe_many). Everything is checked before the
+        first launch: a refused call leaves the session as it was."""
+        s = self.eng.spec
+        self._check_usable()
+        if not isinstance(frames, dict):
+            raise TypeError("frames must be a dict {modality: (B, n, dim) tensor}")
+        n = self._check_chunk(faces, "faces", s.C)
+        srcs = []
+        for e in self.mods:
+            x = frames.get(e.name)
+            if x is None:
+                raise KeyError("batch is missing modality %r" % e.name)
+            self._check_chunk(x, e.name, e.in_dim, n)
+            srcs.append(x)
+        if noise is not None:
+            ok = (torch.is_tensor(noise) and noise.is_cuda and noise.device == self.device and noise.dtype == torch.float32
+                  and noise.is_contiguous() and noise.dim() == 3 and tuple(noise.shape) == (n, self.B, s.C))
+            if not ok:
+                raise ValueError("noise: expected contiguous float32 GPU tensor (n=%d, B=%d, %d) on %s, frame-major, got %s %s on %s"
+                                 % (n, self.B, s.C, self.device, tuple(getattr(noise, "shape", ())),
+                                    getattr(noise, "dtype", type(noise)), getattr(noise, "device", None)))
+        roles = self._check_observed_many(observed, n)
+        srcs.append(faces)
+        min_run = self._rows_many_min_run()
+        cap = self._chunk_cap()
+        with self._owned():
+            self._check_guard()
+            eng, B = self.eng, self.B
+            masks = self._chunk_masks(n)
+            if noise is None:
+                noise = torch.stack([self._noise_fn(B, s.C) for _ in range(n)]).contiguous()
+            out = torch.empty(B, n, s.C, dtype=torch.float32, device=self.device)
+            nll = torch.empty(n, B, dtype=torch.float32, device=self.device)
+            plan = []
+            keep, eng._ws = eng._ws, self._chunk_ws      # (the session's own workspaces keep the addresses its graphs hold)
+            try:
+                for o in range(0, n, cap):
+                    m = min(cap, n - o)
+                    mk = None if masks is None else {k: v[o:o + m].contiguous() for k, v in masks.items()}
+                    plan += [(kind, o + f0, cnt) for kind, f0, cnt in
+                             self._roles_round([x[:, o:o + m] for x in srcs], m, mk, noise[o:o + m], out, o, nll[o:o + m],
+                                               roles[o:o + m], min_run)]
+            finally:
+                self._chunk_ws, eng._ws = eng._ws, keep
+            self.last_plan = plan
+            self._pinned.copy_(self.guard, non_blocking=True)
+            gev = torch.cuda.Event()
+            gev.record()
+            self._guard_pending = gev
+            for x in srcs + [noise]:
+                x.record_stream(torch.cuda.current_stream(self.device))
+        self._record_out(out, nll)
+        return out, nll
+
+    def _roles_round(self, srcs, m, masks, noise, out, o, nll, roles, min_run):
+        """m frames of a step_rows_many() call, inside _owned() with the chunk's workspaces as the engine's: role words and windows
+        in, static part, the plan's runs from the session's live state, windows and frames out. srcs: as _chunk_round's (the faces
+        last); noise (m, B, C) / nll (m, B): contiguous slices of the call's; roles: (m, B) CPU bool; the frames go to
+        out[:, o:o + m]. -> the round's plan [(kind, first, count), ...], offsets in the round."""
+        s, eng, B = self.eng.spec, self.eng, self.B
+        T = s.start + m
+        k = len(self._wins)
+        gen = k - 1                             # the prev_p1_face window: the last of self._wins
+        seqs, seq_p, src_p = self._chunk_seqs(srcs, m)
+        ev = eng._tic("stream_chunk_in")
+        # the round's role words: pinned host memory of their own (the copy is asynchronous), one session-owned device buffer
+        role_dev = eng._buf_i32("chunk_roles", m * B)
+        role_dev[:m * B].copy_(roles.to(torch.int32).reshape(-1).pin_memory(), non_blocking=True)
+        check(eng.L.lfi_stream_chunk_roles_in(B, m, s.start, k, self._row_win, src_p, seq_p, self._row_hist, self._row_dim, self._lead,
+                                              gen, noise.data_ptr(), s.C, role_dev.data_ptr(), self.guard.data_ptr(), _stream()),
+              "lfi_stream_chunk_roles_in")
+        eng._toc("stream_chunk_in", ev)
+        pre = self._chunk_static(seqs, m, masks)
+        dims, p = eng._flow_dims(B, m), eng._flow_params()
+        dims.gemm_precision = self.frame_precision
+        first = 1 if self.steps > 0 or self._resumed else 0
+        faces = seqs["p1_face"]
+        # chunk-chain runs only where that chain runs (it wants a faces window and the register-resident cells)
+        chunk_ok = self.hist1 >= 1 and bool(eng.L.lfi_flow_score_chunk_ok(C.byref(dims)))
+        plan = plan_rows_many(roles.all(1).tolist(), min_run if chunk_ok else 0)
+        pre_row = 4 * B * s.Ks * s.D            # bytes of one frame's rows of pre
+        ev = eng._tic("stream_chunk_rows_chain")
+        for kind, f0, cnt in plan:
+            ff = first if f0 == 0 else 1
+            if kind == "observe":
+                work = eng._buf("chunk_work", eng.L.lfi_flow_score_chunk_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
+                check(eng.L.lfi_flow_score_seq_chunk(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf,
+                                                     self.hist1, pre.data_ptr() + f0 * pre_row, faces.data_ptr(), T, s.start + f0, cnt,
+                                                     ff, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1), None, None,
+                                                     work.data_ptr(), None, nll.data_ptr() + 4 * f0 * B, _stream()),
+                      "lfi_flow_score_seq_chunk")
+                continue
+            work = eng._buf("chunk_gen_work", eng.L.lfi_flow_sample_work_floats(C.byref(dims)))
+            p1work = eng._buf("chunk_gen_p1work", eng.L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
+            nll_work = eng._buf("chunk_gen_nll_work", eng.L.lfi_flow_sample_nll_work_floats(C.byref(dims)))
+            rows_work = eng._buf("chunk_rows_work", eng.L.lfi_flow_step_rows_work_floats(C.byref(dims)))
+            check(eng.L.lfi_flow_step_rows_seq(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
+                                               pre.data_ptr() + f0 * pre_row, noise.data_ptr() + 4 * f0 * B * s.C, faces.data_ptr(), T,
+                                               s.start + f0, cnt, ff, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
+                                               p1work.data_ptr(), work.data_ptr(), nll.data_ptr() + 4 * f0 * B, nll_work.data_ptr(),
+                                               role_dev.data_ptr() + 4 * f0 * B, rows_work.data_ptr(), _stream()),
+                  "lfi_flow_step_rows_seq")
+        eng._toc("stream_chunk_rows_chain", ev)
+        check(eng.L.lfi_stream_chunk_gen_out(B, m, s.start, k, self._row_win, seq_p, self._row_hist, self._row_dim, self._lead, gen,
+                                             out.data_ptr() + 4 * o * s.C, out.shape[1] * s.C, ptr(self.frame_nb),
+                                             self.guard.data_ptr(), _stream()), "lfi_stream_chunk_gen_out")
+        self.steps += m
+        return plan
 
     def _chunk_masks(self, n):
         """Injected masks (masks_fn, tests only) for frames steps .. steps + n - 1 -> {name: (n, B, hist)} or None; a one-frame mask

@@ -4,7 +4,7 @@ alternative without a session: re-running SeqGlow.inference over the whole prefi
   python tools/stream_latency.py [--batches 1,16,256] [--steps 200] [--warmup 20] [--prefixes 50,150,300] [--out FILE]
                                  [--churn 1,16,64 [--churn-batch 256]] [--migrate 16 [--migrate-batch 256]] [--nll 1,256]
                                  [--observe 1,16,256] [--rows 1,16,256] [--observe-many 16,64,250]
-                                 [--step-many 4,16,64] [--observe-ragged 16,64,250]
+                                 [--step-many 4,16,64] [--observe-ragged 16,64,250] [--rows-many 4,16,64]
 
 Per batch size: the wall-clock time from step() to the generated frame on the host (a synchronise after every step: what a live agent
 waits for), its GPU time (HIP events around the step), and a per-kernel breakdown from the engine's enable_timing on an eager session
@@ -53,7 +53,16 @@ into its sequence, the order rotating, --reps times after two untimed rounds: (a
 own rep-to-rep spread; (b) (B > 16) the first 16-row tile at length n and every other row at 0 - joiners warmed up in place - with
 its front end / chain split (LFI_CHUNK_ONLY) and, beside it, the side-session recipe: open_stream for 16 rows, observe_many, save_rows,
 load_rows into the big session; (c) lengths spread evenly over 0 .. n. Then the register figures of the dense and the ragged chain
-kernels from tools/kernel_resources.py (compiled for gfx950 while the GPU is still untouched)."""
+kernels from tools/kernel_resources.py (compiled for gfx950 while the GPU is still untouched).
+
+--rows-many n1,n2,..: this leg ALONE, written to --out (default profiles/stream_step_rows_many.md): per batch size of --batches and per
+n, every arm on a session of its own one generated frame into its sequence, the same conditioning, faces and noise, the order
+rotating, --reps times after two untimed rounds: (a) n step_rows() calls in a Python loop (host masks, as the chunk call takes them);
+(b) step_rows_many(n) with the first half of the 16-row tiles observing and the rest generating (B >= 32; the loop runs this mask
+there); (c) step_rows_many(n) with odd rows observing and even rows generating - every tile mixed (B >= 2; at B = 1 the one row
+alternates frame by frame; below B = 32 the loop runs this mask); (d) step_rows_many(n) with a prompt-then-continue mask, prompt
+lengths spread over n / 4 .. 3 n / 4, with the plan on and (e) with LFI_ROWS_MANY_OBSERVE_RUN=0. Per frame: wall clock and GPU time
+as --step-many. Then where the GPU time of arms (d) and (e) goes, from the engine's enable_timing."""
 import argparse
 import contextlib
 import os
@@ -83,6 +92,7 @@ def main():
     ap.add_argument("--observe-many", default=None, help="chunk lengths of the observe_many() leg, e.g. 16,64,250: runs this leg alone")
     ap.add_argument("--step-many", default=None, help="frames per call of the step_many() leg, e.g. 4,16,64: runs this leg alone")
     ap.add_argument("--observe-ragged", default=None, help="chunk lengths of the ragged observe_many() leg: runs this leg alone")
+    ap.add_argument("--rows-many", default=None, help="frames per call of the step_rows_many() leg, e.g. 4,16,64: runs this leg alone")
     ap.add_argument("--reps", type=int, default=7, help="with --observe-many / --step-many / --observe-ragged: timed rounds per (batch size, chunk length)")
     a = ap.parse_args()
     resources = chain_kernel_resources() if a.observe_ragged else None     # (compiles; before the GPU is initialised)
@@ -137,6 +147,16 @@ def main():
         bench.stop_smi_helper(helper)
         print(text)
         out = a.out or os.path.join(ROOT, "profiles", "stream_step_many.md")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text)
+        return
+    if a.rows_many:
+        text = rows_many_report(m, dev, [int(v) for v in a.batches.split(",")], [int(v) for v in a.rows_many.split(",")], a.reps,
+                                dims, start, C, torch.cuda.get_device_name(dev))
+        bench.stop_smi_helper(helper)
+        print(text)
+        out = a.out or os.path.join(ROOT, "profiles", "stream_step_rows_many.md")
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as f:
             f.write(text)
@@ -670,6 +690,121 @@ def step_many_report(m, dev, batches, ns, reps, dims, start, C, device_name):
     for B, n, t in split:
         a, b, c = (t.get("stream_chunk_" + k, 0.0) for k in ("in", "static", "gen_chain"))
         lines.append("| %d | %d | %.3f | %.3f | %.3f | %.4f | %.0f %% |" % (B, n, a, b, c, c / n, 100.0 * c / max(a + b + c, 1e-9)))
+    return "\n".join(lines) + "\n"
+
+
+def rows_many_report(m, dev, batches, ns, reps, dims, start, C, device_name):
+    """The --rows-many report: per (B, n) the per-frame time of the step_rows() loop and of step_rows_many(n) under the masks the
+    module's docstring lists, then where the prompt-then-continue call's GPU time goes with the plan on and off."""
+    import torch
+    s = m.spec
+    eng = m._ensure_engine(dev)
+    top = max(ns)
+    switch = "LFI_ROWS_MANY_OBSERVE_RUN"
+    arms = ("loop", "halves", "mixed", "prompt", "prompt, plan off")
+    lines = ["# step_rows_many(): per-row roles over a chunk of frames (tools/stream_latency.py --rows-many)", "",
+             "final_model.yaml as shipped (C = %d, S = %d, K = %d, H = %d, D = %d), engine precision %s; every arm of a (B, n) in one "
+             "process on a session of its own, the same conditioning, faces and noise, the order rotating; %d timed rounds after 2 "
+             "untimed ones; per FRAME: wall = call to result on the host (one synchronise after the n calls / the one call) / n, GPU = "
+             "HIP events around them / n; wall / GPU in every cell. Device %s." % (C, s.S, s.Ks, s.H, s.D, m.precision, reps, device_name),
+             "", "Masks: halves = the first half of the 16-row tiles observes, the rest generates (B >= 32); mixed = odd rows observe, "
+             "even rows generate, every tile mixed (B = 1: the row alternates frame by frame); prompt = row b observes its first "
+             "lengths[b] frames and generates the rest, lengths spread over n / 4 .. 3 n / 4, with the plan on (runs every row observes "
+             "go to the chunk forward chain) and with %s=0 (everything on the rows chain). The step_rows() loop runs the halves mask "
+             "where there is one (its cheaper case: one chain per tile), the mixed mask below B = 32." % switch, "",
+             "| B | n | step_rows() loop, ms / frame | step_rows_many: halves | mixed | prompt | prompt, plan off | loop / halves, GPU | "
+             "loop / mixed, GPU | plan off / on, GPU | plan of the prompt call |", "|---|---|---|---|---|---|---|---|---|---|---|"]
+    split, slower, plan_slower = [], [], []
+    for B in batches:
+        gd = torch.Generator().manual_seed(B + 11)
+        data = {k: torch.randn(B, start + top + 1, d, generator=gd).to(dev) for k, d in dims.items()}
+        seed = {k: v[:, :start].contiguous() for k, v in data.items()}
+        frames = [{k: v[:, start + i].contiguous() for k, v in data.items() if k != "p1_face"} for i in range(top + 1)]
+        noise = (torch.randn(top + 1, B, C, generator=gd) * 0.8).to(dev)
+        given = (torch.randn(B, top + 1, C, generator=gd) * 0.5).to(dev)
+        face = [given[:, i].contiguous() for i in range(top + 1)]
+        tiles = (B + 15) // 16
+        sessions = {name: m.open_stream(seed) for name in arms}
+        try:
+            for n in ns:
+                chunk = {k: v[:, start + 1:start + 1 + n].contiguous() for k, v in data.items() if k != "p1_face"}
+                cnoise, cfaces = noise[1:1 + n], given[:, 1:1 + n].contiguous()
+                halves = (torch.arange(B) // 16 < tiles // 2).expand(n, B).contiguous() if B >= 32 else None
+                mixed = ((torch.arange(B) % 2 == 1).expand(n, B) if B >= 2 else (torch.arange(n) % 2 == 1)[:, None]).contiguous()
+                lengths = torch.tensor([n // 4 + (b * (n // 2)) // max(B - 1, 1) for b in range(B)]) if B > 1 else torch.tensor([n // 2])
+                prompt = torch.arange(n)[:, None] < lengths[None, :]
+                loop_mask = (halves if halves is not None else mixed).tolist()
+
+                def many(name, mask, off=False):
+                    def call():
+                        if off:
+                            os.environ[switch] = "0"
+                        try:
+                            return sessions[name].step_rows_many(chunk, cfaces, mask, cnoise)
+                        finally:
+                            os.environ.pop(switch, None)
+                    return call
+
+                def loop():
+                    st = sessions["loop"]
+                    return [st.step_rows(frames[i], face[i], loop_mask[i - 1], noise[i]) for i in range(1, n + 1)]
+
+                calls = [("loop", loop), ("mixed", many("mixed", mixed)), ("prompt", many("prompt", prompt)),
+                         ("prompt, plan off", many("prompt, plan off", prompt, True))]
+                if halves is not None:
+                    calls.insert(1, ("halves", many("halves", halves)))
+                legs = {name: ([], []) for name, _ in calls}
+                for r in range(reps + 2):
+                    k = r % len(calls)
+                    for name, fn in calls[k:] + calls[:k]:
+                        st = sessions[name]
+                        st.reset(seed)
+                        st.step(frames[0], noise[0])
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        e0.record()
+                        fn()
+                        e1.record()
+                        e1.synchronize()
+                        t1 = time.perf_counter()
+                        if r >= 2:
+                            legs[name][0].append((t1 - t0) * 1e3 / n)
+                            legs[name][1].append(e0.elapsed_time(e1) / n)
+                med = {name: (statistics.median(w), statistics.median(g)) for name, (w, g) in legs.items()}
+                cell = lambda name: "%.4f / %.4f" % med[name] if name in med else "-"
+                ratio = lambda a, b: "%.2f x" % (med[a][1] / med[b][1]) if a in med and b in med else "-"
+                plan = sessions["prompt"].last_plan
+                lines.append("| %d | %d | %s | %s | %s | %s | %s | %s | %s | %s | %s |"
+                             % (B, n, cell("loop"), cell("halves"), cell("mixed"), cell("prompt"), cell("prompt, plan off"),
+                                ratio("loop", "halves"), ratio("loop", "mixed"), ratio("prompt, plan off", "prompt"),
+                                " ".join("%s %d+%d" % run for run in plan)))
+                if n == 16 and not all(med[name][0] < med["loop"][0] and med[name][1] < med["loop"][1] for name in med if name != "loop"):
+                    slower.append(B)
+                if med["prompt"][1] > med["prompt, plan off"][1]:
+                    plan_slower.append((B, n))
+                for name, off in (("prompt", False), ("prompt, plan off", True)):
+                    st = sessions[name]
+                    st.reset(seed)
+                    st.step(frames[0], noise[0])
+                    eng.enable_timing(True)
+                    many(name, prompt, off)()
+                    summary = eng.timing_summary()
+                    eng.enable_timing(False)
+                    split.append((B, n, name, {t: v[0] * v[1] for t, v in summary.items() if t.startswith("stream_chunk")}))
+        finally:
+            for st in sessions.values():
+                st.close()
+    lines += ["", "Per-frame time of step_rows_many(16), every mask, below the same run's step_rows() loop at every batch size (wall "
+              "and GPU): %s." % ("yes" if not slower else "NO, not at B = %s" % slower),
+              "The prompt mask with the plan on not slower than with it off (GPU, medians): %s."
+              % ("yes, at every (B, n)" if not plan_slower else "NO, slower at (B, n) = %s" % plan_slower), "",
+              "## Where a prompt-then-continue call's GPU time goes (enable_timing, HIP events; ms per call, all its launches of a kind summed)",
+              "", "| B | n | arm | role words + windows in | static part (window encoders + static cond_transform columns) | the plan's runs: "
+              "front ends + chains | runs per frame |", "|---|---|---|---|---|---|---|"]
+    for B, n, name, t in split:
+        a, b, c = (t.get("stream_chunk_" + k, 0.0) for k in ("in", "static", "rows_chain"))
+        lines.append("| %d | %d | %s | %.3f | %.3f | %.3f | %.4f |" % (B, n, name, a, b, c, c / n))
     return "\n".join(lines) + "\n"
 
 
