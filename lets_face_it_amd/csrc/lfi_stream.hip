@@ -1,4 +1,4 @@
-// Streaming (frame-by-frame) sampling: the per-step state update of a sampling session (engine.py SampleStream).
+// Streaming (frame-by-frame) sampling: the per-step state update of a sampling session (stream.py SampleStream).
 //
 // A session keeps, per conditioning modality with history > 0, the last `hist` frames of every batch row (B x hist x dim), the
 // prev_p1_face window of its own output (B x (hist1 + 1) x C), the prior noise of the step and the frame counter. One launch moves
@@ -25,6 +25,38 @@ struct StreamWins {
 };
 
 __device__ __forceinline__ unsigned stream_abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+
+// The guard folds, one of which every kernel here ends with: max |v| (as bits) of what a thread moved goes into the session's guard
+// word (NULL = no guard), which only grows between the session's clears. Per wave: one atomic from every wave that saw a value.
+__device__ __forceinline__ void stream_guard_fold(unsigned m, unsigned* __restrict__ guard) {
+  if (!guard) return;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
+    m = t > m ? t : m;
+  }
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(guard, m);
+}
+
+// Per workgroup of 256 (every thread calls it): one atomic, and none when the word already holds as much - the clears are
+// stream-ordered before the launch, so a read of at least m means the result is at least m. Atomics on the one word serialise (~10 ns
+// each on this chip): one per wave was most of a 64-row reset launch.
+__device__ __forceinline__ void stream_guard_fold_block(unsigned m, unsigned* __restrict__ guard) {
+  if (!guard) return;
+  __shared__ unsigned wmax[4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
+    m = t > m ? t : m;
+  }
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = wmax[0];
+    for (int w = 1; w < 4; ++w) m = wmax[w] > m ? wmax[w] : m;
+    if (m > __atomic_load_n(guard, __ATOMIC_RELAXED)) atomicMax(guard, m);
+  }
+}
 
 // Workgroup (i, b): window i of batch row b, or (i = count) the noise row and the frame counter of batch row b. A window is read and
 // written by its own workgroup only: every 256-element chunk is read into registers, a barrier, then written. Chunk k reads elements
@@ -62,13 +94,7 @@ __global__ __launch_bounds__(256) void stream_advance_kernel(StreamWins w, const
     }
     if (frame_nb && threadIdx.x == 0) frame_nb[b] += 2.0f;   // SeqGlow.inference: ones, + 2 per frame (glow/models.py:572-575)
   }
-  if (!guard) return;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
-    m = t > m ? t : m;
-  }
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(guard, m);
+  stream_guard_fold(m, guard);
 }
 
 // stream_advance_kernel for a step whose rows observe or generate one by one (SampleStream.step_rows): the same workgroup map and chunk
@@ -113,24 +139,15 @@ __global__ __launch_bounds__(256) void stream_advance_rows_kernel(StreamWins w, 
       if (frame_nb) frame_nb[b] += 2.0f;
     }
   }
-  if (!guard) return;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
-    m = t > m ? t : m;
-  }
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(guard, m);
+  stream_guard_fold(m, guard);
 }
 
-// ---- a chunk of n observed frames per call (SampleStream.observe_many): the windows as sequences, and back
-//
-// In: workgroup (i, b) lays window i of batch row b out as the sequence the sequence mode of the feature builder and the chain take,
-// seq[i] (B x (start + n) x dim): the window's live frames (all hist of a conditioning window; rows 1 .. hist - 1 of the prev_p1_face
-// window, lead = 1) end at frame start - 1, the caller's n new frames follow from frame `start`. Frames in front of the window are
-// never read by anybody and never written here. max |v| of the NEW values goes into the guard word, as stream_advance_kernel's.
+// ---- a chunk of n frames per call (SampleStream.observe_many / step_many / step_rows_many): the windows as sequences, and back.
+// One kernel each way; what the calls differ in are nullable arguments (gen_win: -1 = none), and every branch on them is uniform over
+// a workgroup.
 struct StreamChunk {
   float* win[kStreamMaxWins];        // B x hist x dim, row b at b * hist * dim
-  const float* src[kStreamMaxWins];  // B x n x dim: the chunk's frames (chunk_in only)
+  const float* src[kStreamMaxWins];  // B x n x dim: the chunk's frames (in only; NULL for a gen_win without roles)
   float* seq[kStreamMaxWins];        // B x (start + n) x dim
   int hist[kStreamMaxWins];
   int dim[kStreamMaxWins];
@@ -138,109 +155,21 @@ struct StreamChunk {
   int count;
 };
 
-__global__ __launch_bounds__(256) void stream_chunk_in_kernel(StreamChunk w, int n, int start, unsigned* __restrict__ guard) {
-  const int b = blockIdx.y;
-  const int i = blockIdx.x;
-  const int dim = w.dim[i];
-  const long live = (long)(w.hist[i] - w.lead[i]) * dim, fresh = (long)n * dim;
-  const float* win = w.win[i] + ((long)b * w.hist[i] + w.lead[i]) * dim;
-  const float* src = w.src[i] + (long)b * fresh;
-  float* seq = w.seq[i] + (long)b * (start + n) * dim + (long)start * dim;
-  for (long j = threadIdx.x; j < live; j += 256) seq[j - live] = win[j];
-  unsigned m = 0u;
-  for (long j = threadIdx.x; j < fresh; j += 256) {
-    const float v = src[j];
-    seq[j] = v;
-    const unsigned a = stream_abs_bits(v);
-    m = a > m ? a : m;
-  }
-  if (!guard) return;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
-    m = t > m ? t : m;
-  }
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(guard, m);
-}
-
-// Out: workgroup (i, b) takes the last hist frames of seq[i] back into window i of batch row b - right for n below, at and above hist.
-// The prev_p1_face window's hist counts its leading row, which so receives the frame in front of the last hist - 1: what n one-frame
-// advances leave there. Workgroup (count, b): the row's frame counter += 2 n.
-__global__ __launch_bounds__(256) void stream_chunk_out_kernel(StreamChunk w, int n, int start, float* __restrict__ frame_nb) {
-  const int b = blockIdx.y;
-  const int i = blockIdx.x;
-  if (i == w.count) {
-    if (frame_nb && threadIdx.x == 0) frame_nb[b] += 2.0f * (float)n;
-    return;
-  }
-  const long tot = (long)w.hist[i] * w.dim[i];
-  float* win = w.win[i] + (long)b * tot;
-  const float* seq = w.seq[i] + ((long)(b + 1) * (start + n)) * w.dim[i] - tot;
-  for (long j = threadIdx.x; j < tot; j += 256) win[j] = seq[j];
-}
-
-// The guard fold the chunk kernels end with: the workgroup's waves each put their max into the word.
-__device__ __forceinline__ void stream_guard_fold(unsigned m, unsigned* __restrict__ guard) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
-    m = t > m ? t : m;
-  }
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(guard, m);
-}
-
-// ---- a RAGGED chunk (SampleStream.observe_many with lengths): batch row b takes the first lengths[b] of the chunk's n frames.
-//
-// In: stream_chunk_in_kernel, but behind the row's length the sequence gets zeros and the source is not read - what lies there never
-// reaches the sequence or the guard word. (A row of length 0 still gets its live frames: the dense front end reads every row.)
-__global__ __launch_bounds__(256) void stream_chunk_in_rows_kernel(StreamChunk w, int n, int start, const int* __restrict__ lengths,
-                                                                   unsigned* __restrict__ guard) {
-  const int b = blockIdx.y;
-  const int i = blockIdx.x;
-  const int dim = w.dim[i];
-  const int len = min(max(lengths[b], 0), n);
-  const long live = (long)(w.hist[i] - w.lead[i]) * dim, fresh = (long)n * dim, mine = (long)len * dim;
-  const float* win = w.win[i] + ((long)b * w.hist[i] + w.lead[i]) * dim;
-  const float* src = w.src[i] + (long)b * fresh;
-  float* seq = w.seq[i] + (long)b * (start + n) * dim + (long)start * dim;
-  for (long j = threadIdx.x; j < live; j += 256) seq[j - live] = win[j];
-  unsigned m = 0u;
-  for (long j = threadIdx.x; j < mine; j += 256) {
-    const float v = src[j];
-    seq[j] = v;
-    const unsigned a = stream_abs_bits(v);
-    m = a > m ? a : m;
-  }
-  for (long j = mine + threadIdx.x; j < fresh; j += 256) seq[j] = 0.0f;
-  if (guard) stream_guard_fold(m, guard);
-}
-
-// Out: stream_chunk_out_kernel with the row's own end: the hist frames that end at frame start + lengths[b], the counter += 2
-// lengths[b]. A row of length 0 is not touched at all (its window is what it was; with hist - lead == start the leading row would be
-// read from in front of the sequence).
-__global__ __launch_bounds__(256) void stream_chunk_out_rows_kernel(StreamChunk w, int n, int start, const int* __restrict__ lengths,
-                                                                    float* __restrict__ frame_nb) {
-  const int b = blockIdx.y;
-  const int i = blockIdx.x;
-  const int len = min(max(lengths[b], 0), n);
-  if (len == 0) return;
-  if (i == w.count) {
-    if (frame_nb && threadIdx.x == 0) frame_nb[b] += 2.0f * (float)len;
-    return;
-  }
-  const long tot = (long)w.hist[i] * w.dim[i];
-  float* win = w.win[i] + (long)b * tot;
-  const float* seq = w.seq[i] + ((long)b * (start + n) + start + len) * w.dim[i] - tot;
-  for (long j = threadIdx.x; j < tot; j += 256) win[j] = seq[j];
-}
-
-// ---- a chunk of n GENERATED frames per call (SampleStream.step_many): stream_chunk_in_kernel / stream_chunk_out_kernel around the
-// reverse chain, which writes frames start .. start + n - 1 of seq[gen_win] itself.
-//
-// In: every window but gen_win as stream_chunk_in_kernel. Workgroup (gen_win, b) lays out the live frames only - it has no source -
-// and folds row b of the n noise frames (n x B x C, frame-major, read where the caller keeps them) into the guard word instead.
-__global__ __launch_bounds__(256) void stream_chunk_gen_in_kernel(StreamChunk w, int n, int start, int gen_win, int B,
-                                                                 const float* __restrict__ noise, unsigned* __restrict__ guard) {
+// In: workgroup (i, b) lays window i of batch row b out as the sequence the sequence mode of the feature builder and the chains take,
+// seq[i] (B x (start + n) x dim): the window's live frames (all hist of a conditioning window; rows 1 .. hist - 1 of the prev_p1_face
+// window, lead = 1) end at frame start - 1, the chunk's n frames follow from frame `start`. Frames in front of the window are never
+// read by anybody and never written here. max |v| of the NEW values that are used goes into the guard word, as
+// stream_advance_kernel's.
+//   i != gen_win: the row's first len frames of src, len = n or (lengths, a ragged chunk) the clamped lengths[b]; zeros behind len,
+//     where the source is not read. (A row of length 0 still gets its live frames: the dense front end reads every row.)
+//   i == gen_win (dim == C), the window a chain writes: the live frames only, and row b of the n noise frames (n x B x C, frame-major,
+//     read where the caller keeps them) is folded into the guard word instead. With roles (n x B ints, frame-major; what n
+//     stream_advance_rows_kernel launches move, in one): where roles[f * B + b] != 0 the row's given frame f of src enters the
+//     sequence and the guard word, elsewhere the slot is left alone - the rows chain writes it - the given frame is not read and the
+//     row's noise of that frame is folded.
+__global__ __launch_bounds__(256) void stream_chunk_in_kernel(StreamChunk w, int n, int start, const int* __restrict__ lengths,
+                                                              int gen_win, int B, const float* __restrict__ noise,
+                                                              const int* __restrict__ roles, unsigned* __restrict__ guard) {
   const int b = blockIdx.y;
   const int i = blockIdx.x;
   const int dim = w.dim[i];
@@ -251,53 +180,18 @@ __global__ __launch_bounds__(256) void stream_chunk_gen_in_kernel(StreamChunk w,
   unsigned m = 0u;
   if (i != gen_win) {
     const float* src = w.src[i] + (long)b * fresh;
-    for (long j = threadIdx.x; j < fresh; j += 256) {
+    const long mine = lengths ? (long)min(max(lengths[b], 0), n) * dim : fresh;
+    for (long j = threadIdx.x; j < mine; j += 256) {
       const float v = src[j];
       seq[j] = v;
       const unsigned a = stream_abs_bits(v);
       m = a > m ? a : m;
     }
+    for (long j = mine + threadIdx.x; j < fresh; j += 256) seq[j] = 0.0f;
   } else {
     for (int f = 0; f < n; ++f) {
-      const float* row = noise + ((long)f * B + b) * dim;      // (dim[gen_win] == C)
-      for (int j = threadIdx.x; j < dim; j += 256) {
-        const unsigned a = stream_abs_bits(row[j]);
-        m = a > m ? a : m;
-      }
-    }
-  }
-  if (guard) stream_guard_fold(m, guard);
-}
-
-// ---- a chunk of n frames in which every row observes or generates FRAME BY FRAME (SampleStream.step_rows_many): what n
-// stream_advance_rows_kernel launches move, in one. Every window but gen_win as stream_chunk_in_kernel. Workgroup (gen_win, b) lays out
-// the live frames, then goes through the chunk: where roles[f * B + b] != 0 (n x B ints, frame-major) the row's given frame f (src, B x
-// n x dim) goes into the sequence and into the guard word; elsewhere the slot is left alone - the rows chain writes it - the given
-// frame is not read, and the row's noise of that frame (n x B x C, read in place) is folded instead. Only values that are used reach
-// the guard word.
-__global__ __launch_bounds__(256) void stream_chunk_roles_in_kernel(StreamChunk w, int n, int start, int gen_win, int B,
-                                                                   const float* __restrict__ noise, const int* __restrict__ roles,
-                                                                   unsigned* __restrict__ guard) {
-  const int b = blockIdx.y;
-  const int i = blockIdx.x;
-  const int dim = w.dim[i];
-  const long live = (long)(w.hist[i] - w.lead[i]) * dim, fresh = (long)n * dim;
-  const float* win = w.win[i] + ((long)b * w.hist[i] + w.lead[i]) * dim;
-  const float* src = w.src[i] + (long)b * fresh;
-  float* seq = w.seq[i] + (long)b * (start + n) * dim + (long)start * dim;
-  for (long j = threadIdx.x; j < live; j += 256) seq[j - live] = win[j];
-  unsigned m = 0u;
-  if (i != gen_win) {
-    for (long j = threadIdx.x; j < fresh; j += 256) {
-      const float v = src[j];
-      seq[j] = v;
-      const unsigned a = stream_abs_bits(v);
-      m = a > m ? a : m;
-    }
-  } else {
-    for (int f = 0; f < n; ++f) {
-      const bool observes = roles[(long)f * B + b] != 0;      // (uniform over the workgroup)
-      const float* row = observes ? src + (long)f * dim : noise + ((long)f * B + b) * dim;      // (dim[gen_win] == C)
+      const bool observes = roles && roles[(long)f * B + b] != 0;
+      const float* row = observes ? w.src[i] + (long)b * fresh + (long)f * dim : noise + ((long)f * B + b) * dim;
       for (int j = threadIdx.x; j < dim; j += 256) {
         const float v = row[j];
         if (observes) seq[(long)f * dim + j] = v;
@@ -306,28 +200,34 @@ __global__ __launch_bounds__(256) void stream_chunk_roles_in_kernel(StreamChunk 
       }
     }
   }
-  if (guard) stream_guard_fold(m, guard);
+  stream_guard_fold(m, guard);
 }
 
-// Out: stream_chunk_out_kernel, and workgroup (gen_win, b) also hands the n generated frames of row b to the caller (out + b * ld_out,
-// n x C) and folds them into the guard word: what the next one-frame advance does with a frame step() generated.
-__global__ __launch_bounds__(256) void stream_chunk_gen_out_kernel(StreamChunk w, int n, int start, int gen_win, float* __restrict__ out,
-                                                                  long ld_out, float* __restrict__ frame_nb,
-                                                                  unsigned* __restrict__ guard) {
+// Out: workgroup (i, b) takes the last hist frames that end at frame start + len of seq[i] back into window i of batch row b - right
+// for len below, at and above hist; len as above. The prev_p1_face window's hist counts its leading row, which so receives the frame
+// in front of the last hist - 1: what len one-frame advances leave there. A ragged row of length 0 is not touched at all (its window
+// is what it was; with hist - lead == start the leading row would be read from in front of the sequence). Workgroup (count, b): the
+// row's frame counter += 2 len. With out, workgroup (gen_win, b) also hands the n fresh frames of row b to the caller (out + b *
+// ld_out, n x C) and folds them into the guard word: what the next one-frame advance does with a frame step() generated.
+__global__ __launch_bounds__(256) void stream_chunk_out_kernel(StreamChunk w, int n, int start, const int* __restrict__ lengths,
+                                                               int gen_win, float* __restrict__ out, long ld_out,
+                                                               float* __restrict__ frame_nb, unsigned* __restrict__ guard) {
   const int b = blockIdx.y;
   const int i = blockIdx.x;
+  const int len = lengths ? min(max(lengths[b], 0), n) : n;
+  if (len == 0) return;
   if (i == w.count) {
-    if (frame_nb && threadIdx.x == 0) frame_nb[b] += 2.0f * (float)n;
+    if (frame_nb && threadIdx.x == 0) frame_nb[b] += 2.0f * (float)len;
     return;
   }
   const int dim = w.dim[i];
   const long tot = (long)w.hist[i] * dim;
   float* win = w.win[i] + (long)b * tot;
-  const float* end = w.seq[i] + ((long)(b + 1) * (start + n)) * dim;      // one past row b's last frame
-  for (long j = threadIdx.x; j < tot; j += 256) win[j] = (end - tot)[j];
-  if (i != gen_win) return;
+  const float* gen = w.seq[i] + ((long)b * (start + n) + start) * dim;      // the row's first fresh frame
+  const float* seq = gen + (long)len * dim - tot;
+  for (long j = threadIdx.x; j < tot; j += 256) win[j] = seq[j];
+  if (i != gen_win || !out) return;
   const long fresh = (long)n * dim;
-  const float* gen = end - fresh;
   float* dst = out + (long)b * ld_out;
   unsigned m = 0u;
   for (long j = threadIdx.x; j < fresh; j += 256) {
@@ -336,7 +236,7 @@ __global__ __launch_bounds__(256) void stream_chunk_gen_out_kernel(StreamChunk w
     const unsigned a = stream_abs_bits(v);
     m = a > m ? a : m;
   }
-  if (guard) stream_guard_fold(m, guard);
+  stream_guard_fold(m, guard);
 }
 
 // ---- per-row reseed (SampleStream.reset_rows): the state open_stream / reset() give a row, for a listed subset of rows
@@ -390,23 +290,7 @@ __global__ __launch_bounds__(256) void stream_reset_rows_kernel(StreamReset r, f
     }
     if (frame_nb && threadIdx.x == 0) frame_nb[b] = -1.0f;   // the next advance's + 2 makes it inference's 1
   }
-  if (!guard) return;
-  // One atomic per workgroup, and none when the word already holds as much: it only grows between the session's clears (which are
-  // stream-ordered before this launch), so a read at least m means the result is at least m. Atomics on the one word serialise
-  // (~10 ns each on this chip): one per wave was most of a 64-row launch.
-  __shared__ unsigned wmax[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
-    m = t > m ? t : m;
-  }
-  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    m = wmax[0];
-    for (int w = 1; w < 4; ++w) m = wmax[w] > m ? wmax[w] : m;
-    if (m > __atomic_load_n(guard, __ATOMIC_RELAXED)) atomicMax(guard, m);
-  }
+  stream_guard_fold_block(m, guard);
 }
 
 // ---- live rows out of and into a session (SampleStream.save_rows / load_rows): a conversation's whole state as one record
@@ -495,21 +379,7 @@ __global__ __launch_bounds__(256) void stream_move_rows_kernel(StreamMove r, flo
       else rec[r.rec.nb] = frame_nb[b];
     }
   }
-  if (!LOAD || !guard) return;
-  // (one atomic per workgroup, none when the word already holds as much: see stream_reset_rows_kernel)
-  __shared__ unsigned wmax[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
-    m = t > m ? t : m;
-  }
-  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    m = wmax[0];
-    for (int w = 1; w < 4; ++w) m = wmax[w] > m ? wmax[w] : m;
-    if (m > __atomic_load_n(guard, __ATOMIC_RELAXED)) atomicMax(guard, m);
-  }
+  if (LOAD) stream_guard_fold_block(m, guard);
 }
 
 // The argument checks save and load share (everything but the record side); fills r and the layout table.
@@ -533,6 +403,74 @@ int stream_move_args(const char* what, int B, int nrows, const int* rows, int co
     LFI_REQUIRE(!seen[rows[j]], "%s: row %d is listed twice", what, rows[j]);
     seen[rows[j]] = 1;
   }
+  return LFI_OK;
+}
+
+// What a chunk window launch takes beyond the window tables. An entry point names what it has (`kind`: those pointers are required)
+// and leaves the rest as it is here, which the kernels take as "not there".
+enum : unsigned { kChunkIn = 1u, kChunkRagged = 2u, kChunkGen = 4u, kChunkRoles = 8u };
+
+struct StreamChunkOpts {
+  const float* const* src = nullptr;   // kChunkIn: the chunk's frames per window
+  const int* lengths = nullptr;        // kChunkRagged
+  int gen_win = -1;                    // kChunkGen ...
+  const float* noise = nullptr;        // ... in
+  int C = 0;
+  float* out = nullptr;                // ... out
+  long ld_out = 0;
+  const int* roles = nullptr;          // kChunkRoles (in, with kChunkGen): the generated window's source is then required too
+};
+
+// The argument checks of the seven chunk entry points, before any launch; fills w.
+int stream_chunk_args(const char* what, unsigned kind, int B, int n, int start, int count, float* const* win, float* const* seq,
+                      const int* hist, const int* dim, const int* lead, const StreamChunkOpts& o, StreamChunk* w) {
+  const bool in = kind & kChunkIn, gen = kind & kChunkGen, roles = kind & kChunkRoles;
+  LFI_REQUIRE(B > 0 && B <= 65535, "%s: batch %d (1 .. 65535)", what, B);
+  LFI_REQUIRE(n >= 1 && start >= 0 && (long)start + n < (1L << 30), "%s: %d frames from frame %d", what, n, start);
+  LFI_REQUIRE(count >= 1 && count <= kStreamMaxWins, "%s: %d windows (1 .. %d)", what, count, kStreamMaxWins);
+  LFI_REQUIRE(win && seq && hist && dim && lead, "%s: null pointer (window table)", what);
+  // (hist - lead <= start and a written row's len >= 1: the last hist frames of a sequence lie inside what in and the chain wrote)
+  for (int i = 0; i < count; ++i) {
+    LFI_REQUIRE(win[i] && seq[i], "%s: null pointer (window %d)", what, i);
+    LFI_REQUIRE(hist[i] > 0 && dim[i] > 0 && (lead[i] == 0 || lead[i] == 1) && hist[i] - lead[i] <= start,
+                "%s: window %d: hist %d, dim %d, lead %d, start %d", what, i, hist[i], dim[i], lead[i], start);
+    w->win[i] = win[i]; w->seq[i] = seq[i]; w->hist[i] = hist[i]; w->dim[i] = dim[i]; w->lead[i] = lead[i];
+  }
+  w->count = count;
+  if (in) LFI_REQUIRE(o.src && (!gen || o.noise), "%s: null pointer (source table%s)", what, gen ? " / noise" : "");
+  if (kind & kChunkRagged) LFI_REQUIRE(o.lengths, "%s: null pointer (lengths)", what);
+  if (roles) LFI_REQUIRE(o.roles, "%s: null pointer (roles)", what);
+  if (gen && !in) LFI_REQUIRE(o.out, "%s: null pointer (out)", what);
+  if (gen) LFI_REQUIRE(o.gen_win >= 0 && o.gen_win < count, "%s: generated window %d of %d", what, o.gen_win, count);
+  if (gen && in)
+    LFI_REQUIRE(o.C > 0 && dim[o.gen_win] == o.C, "%s: generated window %d has dim %d, the noise C = %d", what, o.gen_win,
+                dim[o.gen_win], o.C);
+  if (gen && !in)
+    LFI_REQUIRE(o.ld_out >= (long)n * dim[o.gen_win], "%s: out row pitch %ld below the %d frames' %ld floats", what, o.ld_out, n,
+                (long)n * dim[o.gen_win]);
+  for (int i = 0; in && i < count; ++i) {
+    // (the generated window has no source - the chain writes its frames - but with roles: the given frames of the rows that observe)
+    const bool none = gen && !roles && i == o.gen_win;
+    LFI_REQUIRE(none || o.src[i], "%s: null pointer (source %d)", what, i);
+    w->src[i] = none ? nullptr : o.src[i];
+  }
+  return LFI_OK;
+}
+
+// The checks and the launch of a chunk entry point: windows in (kChunkIn) or out.
+int stream_chunk_launch(const char* what, unsigned kind, int B, int n, int start, int count, float* const* win, float* const* seq,
+                        const int* hist, const int* dim, const int* lead, const StreamChunkOpts& o, float* frame_nb, unsigned* guard,
+                        void* stream) {
+  StreamChunk w = {};
+  const int rc = stream_chunk_args(what, kind, B, n, start, count, win, seq, hist, dim, lead, o, &w);
+  if (rc != LFI_OK) return rc;
+  if (kind & kChunkIn)
+    hipLaunchKernelGGL(stream_chunk_in_kernel, dim3(count, B), dim3(256), 0, (hipStream_t)stream, w, n, start, o.lengths, o.gen_win, B,
+                       o.noise, o.roles, guard);
+  else
+    hipLaunchKernelGGL(stream_chunk_out_kernel, dim3(count + 1, B), dim3(256), 0, (hipStream_t)stream, w, n, start, o.lengths, o.gen_win,
+                       o.out, o.ld_out, frame_nb, guard);
+  LFI_LAUNCH_CHECK(what);
   return LFI_OK;
 }
 
@@ -671,134 +609,59 @@ extern "C" int lfi_stream_load_rows(int B, int nrows, const int* rows, const int
   return LFI_OK;
 }
 
-namespace {
-int stream_chunk_args(const char* what, int B, int n, int start, int count, float* const* win, float* const* seq, const int* hist,
-                      const int* dim, const int* lead, StreamChunk* w) {
-  LFI_REQUIRE(B > 0 && B <= 65535, "%s: batch %d (1 .. 65535)", what, B);
-  LFI_REQUIRE(n >= 1 && start >= 0 && (long)start + n < (1L << 30), "%s: %d frames from frame %d", what, n, start);
-  LFI_REQUIRE(count >= 1 && count <= kStreamMaxWins, "%s: %d windows (1 .. %d)", what, count, kStreamMaxWins);
-  LFI_REQUIRE(win && seq && hist && dim && lead, "%s: null pointer (window table)", what);
-  for (int i = 0; i < count; ++i) {
-    LFI_REQUIRE(win[i] && seq[i], "%s: null pointer (window %d)", what, i);
-    LFI_REQUIRE(hist[i] > 0 && dim[i] > 0 && (lead[i] == 0 || lead[i] == 1) && hist[i] - lead[i] <= start,
-                "%s: window %d: hist %d, dim %d, lead %d, start %d", what, i, hist[i], dim[i], lead[i], start);
-    w->win[i] = win[i]; w->seq[i] = seq[i]; w->hist[i] = hist[i]; w->dim[i] = dim[i]; w->lead[i] = lead[i];
-  }
-  w->count = count;
-  return LFI_OK;
-}
-}  // namespace
-
 extern "C" int lfi_stream_chunk_in(int B, int n, int start, int count, float* const* win, const float* const* src, float* const* seq,
                                    const int* hist, const int* dim, const int* lead, unsigned* guard_bits, void* stream) {
-  StreamChunk w = {};
-  const int rc = stream_chunk_args("lfi_stream_chunk_in", B, n, start, count, win, seq, hist, dim, lead, &w);
-  if (rc != LFI_OK) return rc;
-  LFI_REQUIRE(src, "lfi_stream_chunk_in: null pointer (source table)");
-  for (int i = 0; i < count; ++i) {
-    LFI_REQUIRE(src[i], "lfi_stream_chunk_in: null pointer (source %d)", i);
-    w.src[i] = src[i];
-  }
-  hipLaunchKernelGGL(stream_chunk_in_kernel, dim3(count, B), dim3(256), 0, (hipStream_t)stream, w, n, start, guard_bits);
-  LFI_LAUNCH_CHECK("lfi_stream_chunk_in");
-  return LFI_OK;
+  StreamChunkOpts o;
+  o.src = src;
+  return stream_chunk_launch("lfi_stream_chunk_in", kChunkIn, B, n, start, count, win, seq, hist, dim, lead, o, nullptr, guard_bits, stream);
 }
 
 extern "C" int lfi_stream_chunk_out(int B, int n, int start, int count, float* const* win, float* const* seq, const int* hist,
                                     const int* dim, const int* lead, float* frame_nb, void* stream) {
-  StreamChunk w = {};
-  const int rc = stream_chunk_args("lfi_stream_chunk_out", B, n, start, count, win, seq, hist, dim, lead, &w);
-  if (rc != LFI_OK) return rc;
-  // (hist - lead <= start and n >= 1: the last hist frames of a sequence lie inside what chunk_in wrote)
-  hipLaunchKernelGGL(stream_chunk_out_kernel, dim3(count + 1, B), dim3(256), 0, (hipStream_t)stream, w, n, start, frame_nb);
-  LFI_LAUNCH_CHECK("lfi_stream_chunk_out");
-  return LFI_OK;
+  return stream_chunk_launch("lfi_stream_chunk_out", 0u, B, n, start, count, win, seq, hist, dim, lead, StreamChunkOpts(), frame_nb, nullptr,
+                             stream);
 }
 
 extern "C" int lfi_stream_chunk_in_rows(int B, int n, int start, int count, float* const* win, const float* const* src, float* const* seq,
                                         const int* hist, const int* dim, const int* lead, unsigned* guard_bits, const int* lengths,
                                         void* stream) {
-  StreamChunk w = {};
-  const int rc = stream_chunk_args("lfi_stream_chunk_in_rows", B, n, start, count, win, seq, hist, dim, lead, &w);
-  if (rc != LFI_OK) return rc;
-  LFI_REQUIRE(src, "lfi_stream_chunk_in_rows: null pointer (source table)");
-  LFI_REQUIRE(lengths, "lfi_stream_chunk_in_rows: null pointer (lengths)");
-  for (int i = 0; i < count; ++i) {
-    LFI_REQUIRE(src[i], "lfi_stream_chunk_in_rows: null pointer (source %d)", i);
-    w.src[i] = src[i];
-  }
-  hipLaunchKernelGGL(stream_chunk_in_rows_kernel, dim3(count, B), dim3(256), 0, (hipStream_t)stream, w, n, start, lengths, guard_bits);
-  LFI_LAUNCH_CHECK("lfi_stream_chunk_in_rows");
-  return LFI_OK;
+  StreamChunkOpts o;
+  o.src = src; o.lengths = lengths;
+  return stream_chunk_launch("lfi_stream_chunk_in_rows", kChunkIn | kChunkRagged, B, n, start, count, win, seq, hist, dim, lead, o, nullptr,
+                             guard_bits, stream);
 }
 
 extern "C" int lfi_stream_chunk_out_rows(int B, int n, int start, int count, float* const* win, float* const* seq, const int* hist,
                                          const int* dim, const int* lead, float* frame_nb, const int* lengths, void* stream) {
-  StreamChunk w = {};
-  const int rc = stream_chunk_args("lfi_stream_chunk_out_rows", B, n, start, count, win, seq, hist, dim, lead, &w);
-  if (rc != LFI_OK) return rc;
-  LFI_REQUIRE(lengths, "lfi_stream_chunk_out_rows: null pointer (lengths)");
-  // (hist - lead <= start and lengths[b] >= 1 where a row is written: its last hist frames lie inside what chunk_in_rows wrote)
-  hipLaunchKernelGGL(stream_chunk_out_rows_kernel, dim3(count + 1, B), dim3(256), 0, (hipStream_t)stream, w, n, start, lengths, frame_nb);
-  LFI_LAUNCH_CHECK("lfi_stream_chunk_out_rows");
-  return LFI_OK;
+  StreamChunkOpts o;
+  o.lengths = lengths;
+  return stream_chunk_launch("lfi_stream_chunk_out_rows", kChunkRagged, B, n, start, count, win, seq, hist, dim, lead, o, frame_nb, nullptr,
+                             stream);
 }
 
 extern "C" int lfi_stream_chunk_gen_in(int B, int n, int start, int count, float* const* win, const float* const* src, float* const* seq,
                                        const int* hist, const int* dim, const int* lead, int gen_win, const float* noise, int C,
                                        unsigned* guard_bits, void* stream) {
-  StreamChunk w = {};
-  const int rc = stream_chunk_args("lfi_stream_chunk_gen_in", B, n, start, count, win, seq, hist, dim, lead, &w);
-  if (rc != LFI_OK) return rc;
-  LFI_REQUIRE(src && noise, "lfi_stream_chunk_gen_in: null pointer (source table / noise)");
-  LFI_REQUIRE(gen_win >= 0 && gen_win < count, "lfi_stream_chunk_gen_in: generated window %d of %d", gen_win, count);
-  LFI_REQUIRE(C > 0 && dim[gen_win] == C, "lfi_stream_chunk_gen_in: generated window %d has dim %d, the noise C = %d", gen_win,
-              dim[gen_win], C);
-  for (int i = 0; i < count; ++i) {
-    LFI_REQUIRE(i == gen_win || src[i], "lfi_stream_chunk_gen_in: null pointer (source %d)", i);
-    w.src[i] = i == gen_win ? nullptr : src[i];
-  }
-  hipLaunchKernelGGL(stream_chunk_gen_in_kernel, dim3(count, B), dim3(256), 0, (hipStream_t)stream, w, n, start, gen_win, B, noise,
-                     guard_bits);
-  LFI_LAUNCH_CHECK("lfi_stream_chunk_gen_in");
-  return LFI_OK;
+  StreamChunkOpts o;
+  o.src = src; o.gen_win = gen_win; o.noise = noise; o.C = C;
+  return stream_chunk_launch("lfi_stream_chunk_gen_in", kChunkIn | kChunkGen, B, n, start, count, win, seq, hist, dim, lead, o, nullptr,
+                             guard_bits, stream);
 }
 
 extern "C" int lfi_stream_chunk_roles_in(int B, int n, int start, int count, float* const* win, const float* const* src, float* const* seq,
                                          const int* hist, const int* dim, const int* lead, int gen_win, const float* noise, int C,
                                          const int* roles, unsigned* guard_bits, void* stream) {
-  StreamChunk w = {};
-  const int rc = stream_chunk_args("lfi_stream_chunk_roles_in", B, n, start, count, win, seq, hist, dim, lead, &w);
-  if (rc != LFI_OK) return rc;
-  LFI_REQUIRE(src && noise, "lfi_stream_chunk_roles_in: null pointer (source table / noise)");
-  LFI_REQUIRE(roles, "lfi_stream_chunk_roles_in: null pointer (roles)");
-  LFI_REQUIRE(gen_win >= 0 && gen_win < count, "lfi_stream_chunk_roles_in: generated window %d of %d", gen_win, count);
-  LFI_REQUIRE(C > 0 && dim[gen_win] == C, "lfi_stream_chunk_roles_in: generated window %d has dim %d, the noise C = %d", gen_win,
-              dim[gen_win], C);
-  for (int i = 0; i < count; ++i) {
-    // (the generated window's source is required here: the given frames of the rows that observe)
-    LFI_REQUIRE(src[i], "lfi_stream_chunk_roles_in: null pointer (source %d)", i);
-    w.src[i] = src[i];
-  }
-  hipLaunchKernelGGL(stream_chunk_roles_in_kernel, dim3(count, B), dim3(256), 0, (hipStream_t)stream, w, n, start, gen_win, B, noise,
-                     roles, guard_bits);
-  LFI_LAUNCH_CHECK("lfi_stream_chunk_roles_in");
-  return LFI_OK;
+  StreamChunkOpts o;
+  o.src = src; o.gen_win = gen_win; o.noise = noise; o.C = C; o.roles = roles;
+  return stream_chunk_launch("lfi_stream_chunk_roles_in", kChunkIn | kChunkGen | kChunkRoles, B, n, start, count, win, seq, hist, dim, lead,
+                             o, nullptr, guard_bits, stream);
 }
 
 extern "C" int lfi_stream_chunk_gen_out(int B, int n, int start, int count, float* const* win, float* const* seq, const int* hist,
                                         const int* dim, const int* lead, int gen_win, float* out, long ld_out, float* frame_nb,
                                         unsigned* guard_bits, void* stream) {
-  StreamChunk w = {};
-  const int rc = stream_chunk_args("lfi_stream_chunk_gen_out", B, n, start, count, win, seq, hist, dim, lead, &w);
-  if (rc != LFI_OK) return rc;
-  LFI_REQUIRE(out, "lfi_stream_chunk_gen_out: null pointer (out)");
-  LFI_REQUIRE(gen_win >= 0 && gen_win < count, "lfi_stream_chunk_gen_out: generated window %d of %d", gen_win, count);
-  LFI_REQUIRE(ld_out >= (long)n * dim[gen_win], "lfi_stream_chunk_gen_out: out row pitch %ld below the %d frames' %ld floats", ld_out, n,
-              (long)n * dim[gen_win]);
-  // (hist - lead <= start and n >= 1: the last hist frames of a sequence lie inside what chunk_gen_in and the chain wrote)
-  hipLaunchKernelGGL(stream_chunk_gen_out_kernel, dim3(count + 1, B), dim3(256), 0, (hipStream_t)stream, w, n, start, gen_win, out, ld_out,
-                     frame_nb, guard_bits);
-  LFI_LAUNCH_CHECK("lfi_stream_chunk_gen_out");
-  return LFI_OK;
+  StreamChunkOpts o;
+  o.gen_win = gen_win; o.out = out; o.ld_out = ld_out;
+  return stream_chunk_launch("lfi_stream_chunk_gen_out", kChunkGen, B, n, start, count, win, seq, hist, dim, lead, o, frame_nb, guard_bits,
+                             stream);
 }

@@ -8,6 +8,7 @@ import ctypes as C
 import functools
 import operator
 import os
+import types
 import warnings
 import weakref
 
@@ -21,6 +22,7 @@ _SESSION_ATTRS = ("_ws", "prep", "wct_f", "_wct_planes", "_wc_r", "_cond_planes"
 _PARAMS_CHANGED = ("SampleStream: the model's parameters changed since open_stream (optimiser step, parameter load or "
                    "ActNorm init): a session samples with the weights of its open; open a new one")
 _ROW_FIELDS = ("C", "H", "Ks", "rnn_type", "use_frame_nb", "windows", "hist1", "R")
+_ABSENT = object()       # (an argument a call does not take, where None is a value to refuse)
 
 
 def _stream():
@@ -33,20 +35,28 @@ def check_return_nll(value):
         raise TypeError("return_nll: expected a bool, got %s %r" % (type(value).__name__, value))
 
 
+def _host_ints(name, x, strict=False):
+    """The host-data argument `name`: a sequence of ints or a CPU integer tensor -> a list of ints. A tensor may be 1-D or (not
+    strict) a scalar, never torch.bool; strict also refuses bools in a sequence."""
+    wrong = "%s: expected a sequence of ints or a 1-D CPU integer tensor, got %s"
+    if torch.is_tensor(x):
+        if x.is_cuda or x.is_floating_point() or x.is_complex() or x.dtype == torch.bool or x.dim() > 1 or (strict and x.dim() != 1):
+            raise ValueError(wrong % (name, "%s %s on %s" % (tuple(x.shape), x.dtype, x.device)))
+        return x.reshape(-1).tolist()
+    try:
+        vals = list(x)
+        if strict and any(isinstance(v, bool) for v in vals):
+            raise TypeError
+        return [operator.index(v) for v in vals]
+    except TypeError:
+        raise ValueError(wrong % (name, repr(x))) from None
+
+
 def _index_list(name, idx, bound, where, count=None, distinct=True):
     """The index-list argument `name` of reset_rows / save_rows / load_rows: a sequence of ints or a 1-D CPU integer tensor -> a list
     of ints in [0, bound); `where` words what lies beyond. count: as many as that are wanted (None: any number but none at all);
     distinct: none may be listed twice."""
-    wrong = "%s: expected a sequence of ints or a 1-D CPU integer tensor, got %s"
-    if torch.is_tensor(idx):
-        if idx.is_cuda or idx.is_floating_point() or idx.is_complex() or idx.dtype == torch.bool or idx.dim() > 1:
-            raise ValueError(wrong % (name, "%s %s on %s" % (tuple(idx.shape), idx.dtype, idx.device)))
-        idx = idx.reshape(-1).tolist()
-    else:
-        try:
-            idx = [operator.index(i) for i in idx]
-        except TypeError:
-            raise ValueError(wrong % (name, repr(idx))) from None
+    idx = _host_ints(name, idx)
     if count is None and not idx:
         raise ValueError("%s: empty list" % name)
     if count is not None and len(idx) != count:
@@ -325,7 +335,7 @@ class SampleStream:
             out = torch.empty(n, R, dtype=torch.float32, device=self.device)
             check(eng.L.lfi_stream_save_rows(self.B, n, row_a, len(self._row_win), self._row_win, self._row_hist, self._row_dim,
                                              self.h.data_ptr(), ptr(self.cs), s.Ks, s.H, ptr(self.frame_nb),
-                                             int(self.steps == 0 and not self._resumed), out.data_ptr(), R, _stream()),
+                                             1 - self._first_frame, out.data_ptr(), R, _stream()),
                   "lfi_stream_save_rows")
         if self._stream is not None:
             out.record_stream(torch.cuda.current_stream(self.device))
@@ -355,10 +365,7 @@ class SampleStream:
             raise RuntimeError(_PARAMS_CHANGED)
         row_a, ent_a = (C.c_int * n)(*rows), (C.c_int * n)(*entries)
         with self._owned():
-            if self.steps == 0 and not self._resumed:
-                self.h.zero_()          # (stale after a reset(); the first launch would have ignored them)
-                if self.cs is not None:
-                    self.cs.zero_()
+            self._zero_state_if_fresh(resumed=False)        # (marked below, after the launch)
             check(eng.L.lfi_stream_load_rows(self.B, n, row_a, ent_a, len(saved), len(self._row_win), self._row_win, self._row_hist,
                                              self._row_dim, self.h.data_ptr(), ptr(self.cs), s.Ks, s.H, ptr(self.frame_nb),
                                              x.data_ptr(), R, self.guard.data_ptr(), _stream()), "lfi_stream_load_rows")
@@ -366,6 +373,24 @@ class SampleStream:
                 self._resumed = True    # the session's first _launch then keeps h / c (first_frame = 1)
             if self._stream is not None and torch.cuda.current_stream(self.device) == self._stream:
                 x.record_stream(self._stream)
+
+    @property
+    def _first_frame(self):
+        """The first_frame argument of the chains: 0 = the launch ignores what h / c hold (nothing stepped or loaded since the open /
+        reset()), 1 = it carries them on."""
+        return 1 if self.steps > 0 or self._resumed else 0
+
+    def _zero_state_if_fresh(self, resumed=True):
+        """Before rows are put into a session that has not stepped yet: h / c of every row zeroed (stale after a reset(); the first
+        launch would have ignored them - a zeroed row is a first frame's state), so that the first launch can run as a continuing
+        one; resumed: mark it so now."""
+        if self._first_frame:
+            return
+        self.h.zero_()
+        if self.cs is not None:
+            self.cs.zero_()
+        if resumed:
+            self._resumed = True
 
     def _fill(self, seed):
         s, h1 = self.eng.spec, self.hist1
@@ -481,26 +506,41 @@ class SampleStream:
     def _check_lengths(self, lengths, n):
         """The lengths argument of observe_many(): a sequence of B ints or a 1-D CPU integer tensor of B entries, each in [0, n] -> a
         list of ints. Host data, as reset_rows' rows; the wording of _index_list."""
-        wrong = "lengths: expected a sequence of ints or a 1-D CPU integer tensor, got %s"
-        if torch.is_tensor(lengths):
-            if (lengths.is_cuda or lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool
-                    or lengths.dim() != 1):
-                raise ValueError(wrong % ("%s %s on %s" % (tuple(lengths.shape), lengths.dtype, lengths.device)))
-            vals = lengths.tolist()
-        else:
-            try:
-                vals = list(lengths)
-                if any(isinstance(v, bool) for v in vals):
-                    raise TypeError
-                vals = [operator.index(v) for v in vals]
-            except TypeError:
-                raise ValueError(wrong % repr(lengths)) from None
+        vals = _host_ints("lengths", lengths, strict=True)
         if len(vals) != self.B:
             raise ValueError("lengths: %d listed for %d rows" % (len(vals), self.B))
         bad = [v for v in vals if not 0 <= v <= n]
         if bad:
             raise ValueError("lengths: %s outside the chunk's frames (0 .. %d)" % (bad, n))
         return vals
+
+    def _check_frames(self, frames, faces=_ABSENT, lengths=None):
+        """The tensor arguments of a chunk call in the order they are checked, before any launch: frames, {modality: (B, n, dim)};
+        faces, (B, n, C), where the call takes them; lengths, where given. n is the first tensor's, the same in all the others. ->
+        (the frames in the order of self.mods, n - None when no tensor has said it yet -, lengths as a list or None)."""
+        if not isinstance(frames, dict):
+            raise TypeError("frames must be a dict {modality: (B, n, dim) tensor}")
+        n = None if faces is _ABSENT else self._check_chunk(faces, "faces", self.eng.spec.C)
+        lens = None if lengths is None else self._check_lengths(lengths, n)
+        srcs = []
+        for e in self.mods:
+            x = frames.get(e.name)
+            if x is None:
+                raise KeyError("batch is missing modality %r" % e.name)
+            n = self._check_chunk(x, e.name, e.in_dim, n)
+            srcs.append(x)
+        return srcs, n, lens
+
+    def _check_noise_many(self, noise, n):
+        """The prior draws of a chunk call, (n, B, C) frame-major with n >= 1 (None: whatever it has) -> n."""
+        B, C_ = self.B, self.eng.spec.C
+        ok = (torch.is_tensor(noise) and noise.is_cuda and noise.device == self.device and noise.dtype == torch.float32
+              and noise.is_contiguous() and noise.dim() == 3 and noise.shape[0] >= 1 and tuple(noise.shape[1:]) == (B, C_))
+        if not ok or (n is not None and noise.shape[0] != n):
+            raise ValueError("noise: expected contiguous float32 GPU tensor (%s, B=%d, %d) on %s, frame-major, got %s %s on %s"
+                             % ("n>=1" if n is None else "n=%d" % n, B, C_, self.device, tuple(getattr(noise, "shape", ())),
+                                getattr(noise, "dtype", type(noise)), getattr(noise, "device", None)))
+        return int(noise.shape[0])
 
     def _chunk_cap(self):
         """Frames one launch of the chunk chain takes: its hand-over slots are per frame and never reused inside a launch, and the
@@ -553,49 +593,21 @@ class SampleStream:
         self._check_usable()
         if not isinstance(return_z, bool):
             raise TypeError("return_z: expected a bool, got %s %r" % (type(return_z).__name__, return_z))
-        if not isinstance(frames, dict):
-            raise TypeError("frames must be a dict {modality: (B, n, dim) tensor}")
-        n = self._check_chunk(faces, "faces", s.C)
-        lens = None if lengths is None else self._check_lengths(lengths, n)
-        srcs = []
-        for e in self.mods:
-            x = frames.get(e.name)
-            if x is None:
-                raise KeyError("batch is missing modality %r" % e.name)
-            self._check_chunk(x, e.name, e.in_dim, n)
-            srcs.append(x)
+        srcs, n, lens = self._check_frames(frames, faces, lengths)
         srcs.append(faces)
-        cap = self._chunk_cap()
-        with self._owned():
-            self._check_guard()
-            eng, B = self.eng, self.B
-            masks = self._chunk_masks(n)
+        with self._chunk_call(n, srcs) as rounds:
             new = torch.empty if lens is None else torch.zeros     # (a ragged chunk's launches write live entries only)
-            nll = new(n, B, dtype=torch.float32, device=self.device)
-            z = new(n, B, s.C, dtype=torch.float32, device=self.device) if return_z else None
-            if lens is not None and self.steps == 0 and not self._resumed:
-                self.h.zero_()          # (as load_rows: a zeroed row is a first frame's state, and rows of length 0 keep it)
-                if self.cs is not None:
-                    self.cs.zero_()
-                self._resumed = True
-            keep, eng._ws = eng._ws, self._chunk_ws      # (the session's own workspaces keep the addresses its graphs hold)
-            try:
-                for o in range(0, n, cap):
-                    m = min(cap, n - o)
-                    rl = None if lens is None else [min(max(v - o, 0), m) for v in lens]
-                    if rl is not None and not any(rl):
-                        self.steps += m         # (nothing to run in this round)
-                        continue
-                    mk = None if masks is None else {k: v[o:o + m].contiguous() for k, v in masks.items()}
-                    self._chunk_round([x[:, o:o + m] for x in srcs], m, mk, nll[o:o + m], None if z is None else z[o:o + m], rl)
-            finally:
-                self._chunk_ws, eng._ws = eng._ws, keep
-            self._pinned.copy_(self.guard, non_blocking=True)
-            gev = torch.cuda.Event()
-            gev.record()
-            self._guard_pending = gev
-            for x in srcs:
-                x.record_stream(torch.cuda.current_stream(self.device))
+            nll = new(n, self.B, dtype=torch.float32, device=self.device)
+            z = new(n, self.B, s.C, dtype=torch.float32, device=self.device) if return_z else None
+            if lens is not None:
+                self._zero_state_if_fresh()     # (as load_rows; rows of length 0 keep the zeroed state)
+            for o, m, mk in rounds:
+                rl = None if lens is None else [min(max(v - o, 0), m) for v in lens]
+                if rl is not None and not any(rl):
+                    self.steps += m             # (nothing to run in this round)
+                    continue
+                chain = functools.partial(self._forward_chain, nll=nll[o:o + m], z=None if z is None else z[o:o + m])
+                self._round([x[:, o:o + m] for x in srcs], m, mk, chain, lens=rl)
         self._record_out(nll, z)
         return (nll, z) if return_z else nll
 
@@ -615,59 +627,29 @@ class SampleStream:
         the range guard, the noise is read where the caller keeps it), the static part in sequence mode ONCE for all n frames - n
         step() calls run the window encoders n times over windows that overlap in all but one frame - then lfi_flow_sample_seq_nll
         with nframes = n on the faces sequence from the session's live h / c, and lfi_stream_chunk_gen_out (the windows back, the
-        generated frames into `out` and through the range guard). A chunk beyond the frames one round takes (_chunk_cap) runs as
-        several such rounds. Eager launches: no graph is captured, `replays` does not count them, and the graphs of the per-frame
-        calls stay valid. The sampler entry point picks its kernels as it does for inference(): every shape and switch it handles
-        works here. Train mode without injected masks: the masks of the n frames are drawn in one call, before the noise.
-        Everything is checked before the first launch: a refused call leaves the session as it was."""
+        generated frames into `out` and through the range guard). Rounds, eager launches and graphs as observe_many()'s. The
+        sampler entry point picks its kernels as it does for inference(): every shape and switch it handles works here. Train mode
+        without injected masks: the masks of the n frames are drawn in one call, before the noise. Everything is checked before the
+        first launch: a refused call leaves the session as it was."""
         s = self.eng.spec
         self._check_usable()
-        if not isinstance(frames, dict):
-            raise TypeError("frames must be a dict {modality: (B, n, dim) tensor}")
-        srcs, n = [], None
-        for e in self.mods:
-            x = frames.get(e.name)
-            if x is None:
-                raise KeyError("batch is missing modality %r" % e.name)
-            n = self._check_chunk(x, e.name, e.in_dim, n)
-            srcs.append(x)
+        srcs, n, _ = self._check_frames(frames)
         if noise is None and n is None:
             raise ValueError("noise: a model without conditioning windows takes its frame count from the noise, (n, B=%d, %d)"
                              % (self.B, s.C))
         if noise is not None:
-            ok = (torch.is_tensor(noise) and noise.is_cuda and noise.device == self.device and noise.dtype == torch.float32
-                  and noise.is_contiguous() and noise.dim() == 3 and noise.shape[0] >= 1 and tuple(noise.shape[1:]) == (self.B, s.C))
-            if not ok or (n is not None and noise.shape[0] != n):
-                raise ValueError("noise: expected contiguous float32 GPU tensor (%s, B=%d, %d) on %s, frame-major, got %s %s on %s"
-                                 % ("n>=1" if n is None else "n=%d" % n, self.B, s.C, self.device,
-                                    tuple(getattr(noise, "shape", ())), getattr(noise, "dtype", type(noise)),
-                                    getattr(noise, "device", None)))
-            n = int(noise.shape[0])
+            n = self._check_noise_many(noise, n)
+        used = list(srcs)
         srcs.append(None)                       # (the faces window has no source: the chain writes its frames)
-        cap = self._chunk_cap()
-        with self._owned():
-            self._check_guard()
-            eng, B = self.eng, self.B
-            masks = self._chunk_masks(n)
+        with self._chunk_call(n, used) as rounds:
             if noise is None:
-                noise = torch.stack([self._noise_fn(B, s.C) for _ in range(n)]).contiguous()
-            out = torch.empty(B, n, s.C, dtype=torch.float32, device=self.device)
-            nll = torch.empty(n, B, dtype=torch.float32, device=self.device) if self.return_nll else None
-            keep, eng._ws = eng._ws, self._chunk_ws      # (the session's own workspaces keep the addresses its graphs hold)
-            try:
-                for o in range(0, n, cap):
-                    m = min(cap, n - o)
-                    mk = None if masks is None else {k: v[o:o + m].contiguous() for k, v in masks.items()}
-                    self._gen_round([x if x is None else x[:, o:o + m] for x in srcs], m, mk, noise[o:o + m], out, o,
-                                    None if nll is None else nll[o:o + m])
-            finally:
-                self._chunk_ws, eng._ws = eng._ws, keep
-            self._pinned.copy_(self.guard, non_blocking=True)
-            gev = torch.cuda.Event()
-            gev.record()
-            self._guard_pending = gev
-            for x in srcs[:-1] + [noise]:
-                x.record_stream(torch.cuda.current_stream(self.device))
+                noise = self._draw_noise(n)
+            used.append(noise)
+            out = torch.empty(self.B, n, s.C, dtype=torch.float32, device=self.device)
+            nll = torch.empty(n, self.B, dtype=torch.float32, device=self.device) if self.return_nll else None
+            for o, m, mk in rounds:
+                chain = functools.partial(self._reverse_chain, nll=None if nll is None else nll[o:o + m])
+                self._round([x if x is None else x[:, o:o + m] for x in srcs], m, mk, chain, noise=noise[o:o + m], out=out, o=o)
         self._record_out(out, nll)
         return (out, nll) if self.return_nll else out
 
@@ -735,122 +717,192 @@ class SampleStream:
         offsets in the call, in `last_plan` - a diagnostic): maximal runs of at least 2 frames that EVERY row observes go to
         lfi_flow_score_seq_chunk (LFI_ROWS_MANY_OBSERVE_RUN overrides the 2, 0 = never; never where that chain does not run),
         everything else - all-generate runs included: step_many() is for callers who know that nobody observes - to
-        lfi_flow_step_rows_seq, the rows chain frame by frame; then lfi_stream_chunk_gen_out. Eager launches: no graph is captured,
-        `replays` does not count them, and the graphs of the per-frame calls stay valid. With a fixed plan a row's values do not
+        lfi_flow_step_rows_seq, the rows chain frame by frame; then lfi_stream_chunk_gen_out. Eager launches and graphs as
+        observe_many()'s. With a fixed plan a row's values do not
         depend on the other rows' roles or inputs (rows never mix in a cell, and the dense static part runs the same shapes);
         across plans, and against the per-frame calls, values agree to the session's gates, not bit for bit (the batched front end
         and the sequence-mode static part sum in another order, as for step_many / observe_many). Everything is checked before the
         first launch: a refused call leaves the session as it was."""
         s = self.eng.spec
         self._check_usable()
-        if not isinstance(frames, dict):
-            raise TypeError("frames must be a dict {modality: (B, n, dim) tensor}")
-        n = self._check_chunk(faces, "faces", s.C)
-        srcs = []
-        for e in self.mods:
-            x = frames.get(e.name)
-            if x is None:
-                raise KeyError("batch is missing modality %r" % e.name)
-            self._check_chunk(x, e.name, e.in_dim, n)
-            srcs.append(x)
+        srcs, n, _ = self._check_frames(frames, faces)
         if noise is not None:
-            ok = (torch.is_tensor(noise) and noise.is_cuda and noise.device == self.device and noise.dtype == torch.float32
-                  and noise.is_contiguous() and noise.dim() == 3 and tuple(noise.shape) == (n, self.B, s.C))
-            if not ok:
-                raise ValueError("noise: expected contiguous float32 GPU tensor (n=%d, B=%d, %d) on %s, frame-major, got %s %s on %s"
-                                 % (n, self.B, s.C, self.device, tuple(getattr(noise, "shape", ())),
-                                    getattr(noise, "dtype", type(noise)), getattr(noise, "device", None)))
+            self._check_noise_many(noise, n)
         roles = self._check_observed_many(observed, n)
         srcs.append(faces)
         min_run = self._rows_many_min_run()
-        cap = self._chunk_cap()
-        with self._owned():
-            self._check_guard()
-            eng, B = self.eng, self.B
-            masks = self._chunk_masks(n)
+        used = list(srcs)
+        with self._chunk_call(n, used) as rounds:
             if noise is None:
-                noise = torch.stack([self._noise_fn(B, s.C) for _ in range(n)]).contiguous()
-            out = torch.empty(B, n, s.C, dtype=torch.float32, device=self.device)
-            nll = torch.empty(n, B, dtype=torch.float32, device=self.device)
+                noise = self._draw_noise(n)
+            used.append(noise)
+            out = torch.empty(self.B, n, s.C, dtype=torch.float32, device=self.device)
+            nll = torch.empty(n, self.B, dtype=torch.float32, device=self.device)
             plan = []
-            keep, eng._ws = eng._ws, self._chunk_ws      # (the session's own workspaces keep the addresses its graphs hold)
-            try:
-                for o in range(0, n, cap):
-                    m = min(cap, n - o)
-                    mk = None if masks is None else {k: v[o:o + m].contiguous() for k, v in masks.items()}
-                    plan += [(kind, o + f0, cnt) for kind, f0, cnt in
-                             self._roles_round([x[:, o:o + m] for x in srcs], m, mk, noise[o:o + m], out, o, nll[o:o + m],
-                                               roles[o:o + m], min_run)]
-            finally:
-                self._chunk_ws, eng._ws = eng._ws, keep
+            for o, m, mk in rounds:
+                chain = functools.partial(self._planned_chain, nll=nll[o:o + m], min_run=min_run)
+                plan += [(kind, o + f0, cnt) for kind, f0, cnt in
+                         self._round([x[:, o:o + m] for x in srcs], m, mk, chain, noise=noise[o:o + m], roles=roles[o:o + m],
+                                     out=out, o=o)]
             self.last_plan = plan
-            self._pinned.copy_(self.guard, non_blocking=True)
-            gev = torch.cuda.Event()
-            gev.record()
-            self._guard_pending = gev
-            for x in srcs + [noise]:
-                x.record_stream(torch.cuda.current_stream(self.device))
         self._record_out(out, nll)
         return out, nll
 
-    def _roles_round(self, srcs, m, masks, noise, out, o, nll, roles, min_run):
-        """m frames of a step_rows_many() call, inside _owned() with the chunk's workspaces as the engine's: role words and windows
-        in, static part, the plan's runs from the session's live state, windows and frames out. srcs: as _chunk_round's (the faces
-        last); noise (m, B, C) / nll (m, B): contiguous slices of the call's; roles: (m, B) CPU bool; the frames go to
-        out[:, o:o + m]. -> the round's plan [(kind, first, count), ...], offsets in the round."""
+    @contextlib.contextmanager
+    def _chunk_call(self, n, used):
+        """The driver of a chunk call of n frames, once its arguments are checked: the session's engine state (_owned), the range guard
+        of earlier calls and the mask draw - before anything the body draws; then the body, with the chunk's workspaces as the
+        engine's (the session's own keep the addresses its graphs hold); behind it the guard's copy and record_stream of `used`, the
+        caller's tensors the launches read (the body may add to the list). Yields the rounds, at most _chunk_cap() frames each:
+        [(first frame, frames, the round's masks or None), ...]. A body that raises leaves the workspaces as they were."""
+        cap = self._chunk_cap()
+        with self._owned():
+            self._check_guard()
+            eng = self.eng
+            masks = self._chunk_masks(n)
+            keep, eng._ws = eng._ws, self._chunk_ws
+            try:
+                yield [(o, min(cap, n - o), None if masks is None else {k: v[o:o + cap].contiguous() for k, v in masks.items()})
+                       for o in range(0, n, cap)]
+            finally:
+                self._chunk_ws, eng._ws = eng._ws, keep
+            self._publish_guard()
+            for x in used:
+                x.record_stream(torch.cuda.current_stream(self.device))
+
+    def _draw_noise(self, n):
+        """n prior draws of the session's own, stacked (n, B, C): the random numbers n one-frame calls consume."""
+        return torch.stack([self._noise_fn(self.B, self.eng.spec.C) for _ in range(n)]).contiguous()
+
+    def _round(self, srcs, m, masks, chain, lens=None, noise=None, roles=None, out=None, o=0):
+        """m frames of a chunk call, inside _chunk_call(): windows in, static part, chain, windows out, `steps` += m. srcs: the
+        round's frames of self._wins' windows in their order (strided views of the caller's tensors; None for a window without a
+        source). The options say what the call is and pick the window launches. lens (a ragged observe_many round): the B rows'
+        frame counts, each in [0, m] and not all 0 - the _rows pair. noise (step_many, step_rows_many): (m, B, C), a contiguous
+        slice of the call's - the faces window is the generated one (gen_in / gen_out), and its m frames go to out[:, o:o + m].
+        roles (step_rows_many): (m, B) CPU bool - roles_in. chain(r) launches the middle from the session's live state, given the
+        round r: dims, p, pre, faces (the faces sequence), m, noise, lens, roles and words, the round's lengths or role words on the
+        device. -> what chain returns."""
         s, eng, B = self.eng.spec, self.eng, self.B
-        T = s.start + m
         k = len(self._wins)
         gen = k - 1                             # the prev_p1_face window: the last of self._wins
         seqs, seq_p, src_p = self._chunk_seqs(srcs, m)
+        head, tabs = (B, m, s.start, k, self._row_win), (self._row_hist, self._row_dim, self._lead)
         ev = eng._tic("stream_chunk_in")
-        # the round's role words: pinned host memory of their own (the copy is asynchronous), one session-owned device buffer
-        role_dev = eng._buf_i32("chunk_roles", m * B)
-        role_dev[:m * B].copy_(roles.to(torch.int32).reshape(-1).pin_memory(), non_blocking=True)
-        check(eng.L.lfi_stream_chunk_roles_in(B, m, s.start, k, self._row_win, src_p, seq_p, self._row_hist, self._row_dim, self._lead,
-                                              gen, noise.data_ptr(), s.C, role_dev.data_ptr(), self.guard.data_ptr(), _stream()),
-              "lfi_stream_chunk_roles_in")
+        words = None
+        if lens is not None or roles is not None:
+            # pinned host memory of their own (the copy is asynchronous), one session-owned device buffer
+            host = torch.tensor(lens, dtype=torch.int32) if roles is None else roles.to(torch.int32).reshape(-1)
+            words = eng._buf_i32("chunk_lengths" if roles is None else "chunk_roles", host.numel())
+            words[:host.numel()].copy_(host.pin_memory(), non_blocking=True)
+        if noise is None:
+            name = "lfi_stream_chunk_in" if lens is None else "lfi_stream_chunk_in_rows"
+            more = (self.guard.data_ptr(),) + (() if lens is None else (words.data_ptr(),))
+        else:
+            name = "lfi_stream_chunk_gen_in" if roles is None else "lfi_stream_chunk_roles_in"
+            more = (gen, noise.data_ptr(), s.C) + (() if roles is None else (words.data_ptr(),)) + (self.guard.data_ptr(),)
+        check(getattr(eng.L, name)(*head, src_p, seq_p, *tabs, *more, _stream()), name)
         eng._toc("stream_chunk_in", ev)
         pre = self._chunk_static(seqs, m, masks)
         dims, p = eng._flow_dims(B, m), eng._flow_params()
         dims.gemm_precision = self.frame_precision
-        first = 1 if self.steps > 0 or self._resumed else 0
-        faces = seqs["p1_face"]
+        done = chain(types.SimpleNamespace(dims=dims, p=p, pre=pre, faces=seqs["p1_face"], m=m, noise=noise, lens=lens, roles=roles,
+                                           words=words))
+        if noise is None:
+            name = "lfi_stream_chunk_out" if lens is None else "lfi_stream_chunk_out_rows"
+            more = (ptr(self.frame_nb),) + (() if lens is None else (words.data_ptr(),))
+        else:
+            name = "lfi_stream_chunk_gen_out"
+            more = (gen, out.data_ptr() + 4 * o * s.C, out.shape[1] * s.C, ptr(self.frame_nb), self.guard.data_ptr())
+        check(getattr(eng.L, name)(*head, seq_p, *tabs, *more, _stream()), name)
+        self.steps += m
+        return done
+
+    def _chain_args(self, r, f0=0, cnt=None, noise=False):
+        """What every sequence chain's argument list starts with, for frames f0 .. f0 + cnt - 1 (default: to the end) of round r, from
+        the session's live h / c: only the round's first frame can be the session's first. noise: the chain takes the prior draws."""
+        s, eng, B = self.eng.spec, self.eng, self.B
+        args = (C.byref(r.dims), C.byref(r.p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
+                r.pre.data_ptr() + 4 * f0 * B * s.Ks * s.D)
+        if noise:
+            args += (r.noise.data_ptr() + 4 * f0 * B * s.C,)
+        return args + (r.faces.data_ptr(), s.start + r.m, s.start + f0, r.m - f0 if cnt is None else cnt,
+                       self._first_frame if f0 == 0 else 1, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1))
+
+    def _chunk_work(self, dims):
+        eng = self.eng
+        return eng._buf("chunk_work", eng.L.lfi_flow_score_chunk_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
+
+    def _gen_work(self, dims, nll=True):
+        """The work areas of the chains that generate (reverse, rows) -> (work, p1work, nll_work or None)."""
+        eng, L = self.eng, self.eng.L
+        return (eng._buf("chunk_gen_work", L.lfi_flow_sample_work_floats(C.byref(dims))),
+                eng._buf("chunk_gen_p1work", L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(self._p1), self.hist1)),
+                eng._buf("chunk_gen_nll_work", L.lfi_flow_sample_nll_work_floats(C.byref(dims))) if nll else None)
+
+    def _forward_chain(self, r, nll, z):
+        """observe_many's chain: the chunk forward chain (its _rows form for a ragged round), or the per-frame kernels on the same
+        sequences where it does not run. nll (m, B) / z (m, B, C) or None: contiguous slices of the call's outputs, zeroed by the
+        caller for a ragged round."""
+        s, eng, L, B = self.eng.spec, self.eng, self.eng.L, self.B
+        ev = eng._tic("stream_chunk_chain")
+        if self.hist1 >= 1 and L.lfi_flow_score_chunk_ok(C.byref(r.dims)):     # (the chunk chain wants a faces window)
+            outs = (None, None, self._chunk_work(r.dims).data_ptr(), ptr(z), nll.data_ptr())
+            if r.lens is not None:
+                check(L.lfi_flow_score_seq_chunk_rows(*self._chain_args(r), *outs, r.words.data_ptr(), _stream()),
+                      "lfi_flow_score_seq_chunk_rows")
+            else:
+                check(L.lfi_flow_score_seq_chunk(*self._chain_args(r), *outs, _stream()), "lfi_flow_score_seq_chunk")
+        else:
+            # m front ends and m chains (or Ks cells each), one frame's work areas
+            work = eng._buf("chunk_frame_work", L.lfi_flow_sample_work_floats(C.byref(r.dims)))
+            p1work = eng._buf("chunk_frame_p1work", L.lfi_flow_sample_p1_work_floats(C.byref(r.dims), C.byref(self._p1), self.hist1))
+            score = eng._buf("chunk_frame_score", L.lfi_flow_score_work_floats(C.byref(r.dims)))
+
+            def run(f0, cnt):                   # frames f0 .. f0 + cnt - 1 of the round, every row
+                check(L.lfi_flow_score_seq_from(*self._chain_args(r, f0, cnt), p1work.data_ptr(), work.data_ptr(), score.data_ptr(),
+                                                None if z is None else z.data_ptr() + 4 * f0 * B * s.C, nll.data_ptr() + 4 * f0 * B,
+                                                _stream()), "lfi_flow_score_seq_from")
+            if r.lens is None:
+                run(0, r.m)
+            else:
+                self._ragged_frames(run, r.lens, r.m, nll, z)
+        eng._toc("stream_chunk_chain", ev)
+
+    def _reverse_chain(self, r, nll):
+        """step_many's chain: the sampler's, which writes the round's frames into the faces sequence. nll (m, B) or None."""
+        eng = self.eng
+        work, p1work, nll_work = self._gen_work(r.dims, nll is not None)
+        ev = eng._tic("stream_chunk_gen_chain")
+        check(eng.L.lfi_flow_sample_seq_nll(*self._chain_args(r, noise=True), p1work.data_ptr(), work.data_ptr(), ptr(nll), ptr(nll_work),
+                                            _stream()), "lfi_flow_sample_seq_nll")
+        eng._toc("stream_chunk_gen_chain", ev)
+
+    def _planned_chain(self, r, nll, min_run):
+        """step_rows_many's mix: the runs of the round's plan, chunk forward chain or rows chain, in frame order on the same
+        sequences and the same pre. -> the plan [(kind, first, count), ...], offsets in the round."""
+        eng, L, B = self.eng, self.eng.L, self.B
         # chunk-chain runs only where that chain runs (it wants a faces window and the register-resident cells)
-        chunk_ok = self.hist1 >= 1 and bool(eng.L.lfi_flow_score_chunk_ok(C.byref(dims)))
-        plan = plan_rows_many(roles.all(1).tolist(), min_run if chunk_ok else 0)
-        pre_row = 4 * B * s.Ks * s.D            # bytes of one frame's rows of pre
+        chunk_ok = self.hist1 >= 1 and bool(L.lfi_flow_score_chunk_ok(C.byref(r.dims)))
+        plan = plan_rows_many(r.roles.all(1).tolist(), min_run if chunk_ok else 0)
         ev = eng._tic("stream_chunk_rows_chain")
         for kind, f0, cnt in plan:
-            ff = first if f0 == 0 else 1
+            at = nll.data_ptr() + 4 * f0 * B
             if kind == "observe":
-                work = eng._buf("chunk_work", eng.L.lfi_flow_score_chunk_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
-                check(eng.L.lfi_flow_score_seq_chunk(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf,
-                                                     self.hist1, pre.data_ptr() + f0 * pre_row, faces.data_ptr(), T, s.start + f0, cnt,
-                                                     ff, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1), None, None,
-                                                     work.data_ptr(), None, nll.data_ptr() + 4 * f0 * B, _stream()),
-                      "lfi_flow_score_seq_chunk")
+                check(L.lfi_flow_score_seq_chunk(*self._chain_args(r, f0, cnt), None, None, self._chunk_work(r.dims).data_ptr(), None, at,
+                                                 _stream()), "lfi_flow_score_seq_chunk")
                 continue
-            work = eng._buf("chunk_gen_work", eng.L.lfi_flow_sample_work_floats(C.byref(dims)))
-            p1work = eng._buf("chunk_gen_p1work", eng.L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
-            nll_work = eng._buf("chunk_gen_nll_work", eng.L.lfi_flow_sample_nll_work_floats(C.byref(dims)))
-            rows_work = eng._buf("chunk_rows_work", eng.L.lfi_flow_step_rows_work_floats(C.byref(dims)))
-            check(eng.L.lfi_flow_step_rows_seq(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
-                                               pre.data_ptr() + f0 * pre_row, noise.data_ptr() + 4 * f0 * B * s.C, faces.data_ptr(), T,
-                                               s.start + f0, cnt, ff, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
-                                               p1work.data_ptr(), work.data_ptr(), nll.data_ptr() + 4 * f0 * B, nll_work.data_ptr(),
-                                               role_dev.data_ptr() + 4 * f0 * B, rows_work.data_ptr(), _stream()),
+            work, p1work, nll_work = self._gen_work(r.dims)
+            rows_work = eng._buf("chunk_rows_work", L.lfi_flow_step_rows_work_floats(C.byref(r.dims)))
+            check(L.lfi_flow_step_rows_seq(*self._chain_args(r, f0, cnt, noise=True), p1work.data_ptr(), work.data_ptr(), at,
+                                           nll_work.data_ptr(), r.words.data_ptr() + 4 * f0 * B, rows_work.data_ptr(), _stream()),
                   "lfi_flow_step_rows_seq")
         eng._toc("stream_chunk_rows_chain", ev)
-        check(eng.L.lfi_stream_chunk_gen_out(B, m, s.start, k, self._row_win, seq_p, self._row_hist, self._row_dim, self._lead, gen,
-                                             out.data_ptr() + 4 * o * s.C, out.shape[1] * s.C, ptr(self.frame_nb),
-                                             self.guard.data_ptr(), _stream()), "lfi_stream_chunk_gen_out")
-        self.steps += m
         return plan
 
-    def _chunk_masks(self, n):
-        """Injected masks (masks_fn, tests only) for frames steps .. steps + n - 1 -> {name: (n, B, hist)} or None; a one-frame mask
-        repeats, as in _advance."""
+    def _drawn_masks(self, n):
+        """Injected masks (masks_fn, tests only) for frames steps .. steps + n - 1, validated -> {name: (n, B, hist)}, views of what
+        was drawn, or None without any; a one-frame mask repeats."""
         drawn = self._masks_fn(self.B, n) if self._masks_fn is not None else None
         self.eng.precision = self.precision      # (the module's mask draw re-applies its own mode to the engine)
         if not drawn:
@@ -864,9 +916,15 @@ class SampleStream:
                 raise ValueError("mask for %s must be (N, B, hist) = (., %d, %d), got %s" % (name, self.B, buf.shape[2], tuple(m.shape)))
             if m.shape[0] != 1 and self.steps + n > m.shape[0]:
                 raise ValueError("mask for %s holds %d frames; this is frame %d of the stream" % (name, m.shape[0], self.steps + n - 1))
-            m = m.expand(n, -1, -1) if m.shape[0] == 1 else m[self.steps:self.steps + n]
-            masks[name] = m.to(device=self.device, dtype=torch.float32).contiguous()
-        return masks or None
+            masks[name] = m.expand(n, -1, -1) if m.shape[0] == 1 else m[self.steps:self.steps + n]
+        return masks
+
+    def _chunk_masks(self, n):
+        """The injected masks of a chunk's n frames on the session's device, or None."""
+        drawn = self._drawn_masks(n)
+        if not drawn:
+            return None
+        return {name: m.to(device=self.device, dtype=torch.float32).contiguous() for name, m in drawn.items()}
 
     def _chunk_seqs(self, srcs, m):
         """The sequence buffers of a round of m frames (B x (start + m) x dim per window of self._wins, in the chunk's workspaces) and
@@ -901,73 +959,7 @@ class SampleStream:
         eng._toc("stream_chunk_static", ev)
         return pre
 
-    def _chunk_round(self, srcs, m, masks, nll, z, lens=None):
-        """m frames of a chunk, inside _owned() with the chunk's workspaces as the engine's: windows in, static part, chain, windows
-        out. srcs: the frames of self._wins' windows in their order (strided views of the caller's tensors); nll (m, B) / z (m, B, C)
-        or None: contiguous slices of the call's outputs. lens (a ragged chunk): the B rows' frame counts in this round, each in
-        [0, m] and not all 0 - the _rows forms of the three entry points, nll / z zeroed by the caller."""
-        s, eng, B = self.eng.spec, self.eng, self.B
-        T = s.start + m
-        k = len(self._wins)
-        seqs, seq_p, src_p = self._chunk_seqs(srcs, m)
-        ev = eng._tic("stream_chunk_in")
-        if lens is not None:
-            # the round's lengths: pinned host memory of their own (the copy is asynchronous), one session-owned device buffer
-            len_dev = eng._buf_i32("chunk_lengths", B)
-            len_dev[:B].copy_(torch.tensor(lens, dtype=torch.int32).pin_memory(), non_blocking=True)
-            check(eng.L.lfi_stream_chunk_in_rows(B, m, s.start, k, self._row_win, src_p, seq_p, self._row_hist, self._row_dim,
-                                                 self._lead, self.guard.data_ptr(), len_dev.data_ptr(), _stream()),
-                  "lfi_stream_chunk_in_rows")
-        else:
-            check(eng.L.lfi_stream_chunk_in(B, m, s.start, k, self._row_win, src_p, seq_p, self._row_hist, self._row_dim, self._lead,
-                                            self.guard.data_ptr(), _stream()), "lfi_stream_chunk_in")
-        eng._toc("stream_chunk_in", ev)
-        pre = self._chunk_static(seqs, m, masks)
-        dims, p = eng._flow_dims(B, m), eng._flow_params()
-        dims.gemm_precision = self.frame_precision
-        first = 1 if self.steps > 0 or self._resumed else 0
-        faces = seqs["p1_face"]
-        ev = eng._tic("stream_chunk_chain")
-        if self.hist1 >= 1 and eng.L.lfi_flow_score_chunk_ok(C.byref(dims)):     # (the chunk chain wants a faces window)
-            work = eng._buf("chunk_work", eng.L.lfi_flow_score_chunk_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
-            if lens is not None:
-                check(eng.L.lfi_flow_score_seq_chunk_rows(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf,
-                                                          self.hist1, pre.data_ptr(), faces.data_ptr(), T, s.start, m, first,
-                                                          self.h.data_ptr(), ptr(self.cs), C.byref(self._p1), None, None, work.data_ptr(),
-                                                          ptr(z), nll.data_ptr(), len_dev.data_ptr(), _stream()),
-                      "lfi_flow_score_seq_chunk_rows")
-            else:
-                check(eng.L.lfi_flow_score_seq_chunk(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf,
-                                                     self.hist1, pre.data_ptr(), faces.data_ptr(), T, s.start, m, first,
-                                                     self.h.data_ptr(), ptr(self.cs), C.byref(self._p1), None, None, work.data_ptr(),
-                                                     ptr(z), nll.data_ptr(), _stream()), "lfi_flow_score_seq_chunk")
-        else:
-            # the per-frame kernels on the same sequences: m front ends and m chains (or Ks cells each), one frame's work areas
-            work = eng._buf("chunk_frame_work", eng.L.lfi_flow_sample_work_floats(C.byref(dims)))
-            p1work = eng._buf("chunk_frame_p1work", eng.L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
-            score = eng._buf("chunk_frame_score", eng.L.lfi_flow_score_work_floats(C.byref(dims)))
-
-            def run(o, cnt, first_frame):       # frames o .. o + cnt - 1 of the round, every row
-                check(eng.L.lfi_flow_score_seq_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf,
-                                                    self.hist1, pre.data_ptr() + 4 * o * B * s.Ks * s.D, faces.data_ptr(), T,
-                                                    s.start + o, cnt, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
-                                                    p1work.data_ptr(), work.data_ptr(), score.data_ptr(),
-                                                    None if z is None else z.data_ptr() + 4 * o * B * s.C,
-                                                    nll.data_ptr() + 4 * o * B, _stream()), "lfi_flow_score_seq_from")
-            if lens is None:
-                run(0, m, first)
-            else:
-                self._ragged_frames(run, lens, m, first, nll, z)
-        eng._toc("stream_chunk_chain", ev)
-        if lens is not None:
-            check(eng.L.lfi_stream_chunk_out_rows(B, m, s.start, k, self._row_win, seq_p, self._row_hist, self._row_dim, self._lead,
-                                                  ptr(self.frame_nb), len_dev.data_ptr(), _stream()), "lfi_stream_chunk_out_rows")
-        else:
-            check(eng.L.lfi_stream_chunk_out(B, m, s.start, k, self._row_win, seq_p, self._row_hist, self._row_dim, self._lead,
-                                             ptr(self.frame_nb), _stream()), "lfi_stream_chunk_out")
-        self.steps += m
-
-    def _ragged_frames(self, run, lens, m, first, nll, z):
+    def _ragged_frames(self, run, lens, m, nll, z):
         """A ragged round on the per-frame kernels, which know no lengths: the frames in segments between the sorted distinct
         lengths, every row in every segment (a row behind its length runs on the zeros lfi_stream_chunk_in_rows left in the
         sequences). After a segment the h / c rows of the rows that end there are put aside; at the end they go back, with the
@@ -981,7 +973,7 @@ class SampleStream:
         kept = [(index[0], [t.index_select(1, index[0]) for t in states])] if 0 in index else []
         done = 0
         for cut in sorted(v for v in index if v > 0):
-            run(done, cut - done, first if done == 0 else 1)
+            run(done, cut - done)
             if cut < max(lens):                 # (the longest rows' state is where it belongs already)
                 kept.append((index[cut], [t.index_select(1, index[cut]) for t in states]))
             done = cut
@@ -993,37 +985,6 @@ class SampleStream:
         nll.masked_fill_(behind, 0.0)
         if z is not None:
             z.masked_fill_(behind.unsqueeze(2), 0.0)
-
-    def _gen_round(self, srcs, m, masks, noise, out, o, nll):
-        """m generated frames of a step_many() call, inside _owned() with the chunk's workspaces as the engine's: windows in, static
-        part, the reverse chain from the session's live state, windows and frames out. srcs: as _chunk_round's, None for the faces
-        window; noise (m, B, C) / nll (m, B) or None: contiguous slices of the call's; the frames go to out[:, o:o + m]."""
-        s, eng, B = self.eng.spec, self.eng, self.B
-        T = s.start + m
-        k = len(self._wins)
-        gen = k - 1                             # the prev_p1_face window: the last of self._wins
-        seqs, seq_p, src_p = self._chunk_seqs(srcs, m)
-        ev = eng._tic("stream_chunk_in")
-        check(eng.L.lfi_stream_chunk_gen_in(B, m, s.start, k, self._row_win, src_p, seq_p, self._row_hist, self._row_dim, self._lead,
-                                            gen, noise.data_ptr(), s.C, self.guard.data_ptr(), _stream()), "lfi_stream_chunk_gen_in")
-        eng._toc("stream_chunk_in", ev)
-        pre = self._chunk_static(seqs, m, masks)
-        dims, p = eng._flow_dims(B, m), eng._flow_params()
-        dims.gemm_precision = self.frame_precision
-        first = 1 if self.steps > 0 or self._resumed else 0
-        work = eng._buf("chunk_gen_work", eng.L.lfi_flow_sample_work_floats(C.byref(dims)))
-        p1work = eng._buf("chunk_gen_p1work", eng.L.lfi_flow_sample_p1_work_floats(C.byref(dims), C.byref(self._p1), self.hist1))
-        nll_work = eng._buf("chunk_gen_nll_work", eng.L.lfi_flow_sample_nll_work_floats(C.byref(dims))) if nll is not None else None
-        ev = eng._tic("stream_chunk_gen_chain")
-        check(eng.L.lfi_flow_sample_seq_nll(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
-                                            pre.data_ptr(), noise.data_ptr(), seqs["p1_face"].data_ptr(), T, s.start, m, first,
-                                            self.h.data_ptr(), ptr(self.cs), C.byref(self._p1), p1work.data_ptr(), work.data_ptr(),
-                                            ptr(nll), ptr(nll_work), _stream()), "lfi_flow_sample_seq_nll")
-        eng._toc("stream_chunk_gen_chain", ev)
-        check(eng.L.lfi_stream_chunk_gen_out(B, m, s.start, k, self._row_win, seq_p, self._row_hist, self._row_dim, self._lead, gen,
-                                             out.data_ptr() + 4 * o * s.C, out.shape[1] * s.C, ptr(self.frame_nb),
-                                             self.guard.data_ptr(), _stream()), "lfi_stream_chunk_gen_out")
-        self.steps += m
 
     def _check_observed(self, observed):
         """The role mask of step_rows(), checked before any launch -> a (B,) bool tensor, on the session's device or on the host (a
@@ -1106,21 +1067,9 @@ class SampleStream:
         s, eng, B = self.eng.spec, self.eng, self.B
         rows = observed is not None
         observe = face is not None and not rows
-        masks = None
-        drawn = self._masks_fn(B, 1) if self._masks_fn is not None else None
-        eng.precision = self.precision      # (the module's mask draw re-applies its own mode to the engine)
-        if drawn:
-            masks = {}
-            for name, buf in self.mask_bufs.items():
-                m = drawn.get(name)
-                if m is None:
-                    continue
-                if m.dim() != 3 or tuple(m.shape[1:]) != (B, buf.shape[2]):
-                    raise ValueError("mask for %s must be (N, B, hist) = (., %d, %d), got %s" % (name, B, buf.shape[2], tuple(m.shape)))
-                if m.shape[0] != 1 and self.steps >= m.shape[0]:
-                    raise ValueError("mask for %s holds %d frames; this is frame %d of the stream" % (name, m.shape[0], self.steps))
-                buf.copy_(m[0 if m.shape[0] == 1 else self.steps].unsqueeze(0))
-                masks[name] = buf
+        masks = self._drawn_masks(1)
+        if masks is not None:
+            masks = {name: self.mask_bufs[name].copy_(m) for name, m in masks.items()}
         for i, x in enumerate(srcs):
             self._src_p[i] = x.data_ptr()
         self._src_p[len(srcs)] = face.data_ptr() if observe or rows else None
@@ -1136,15 +1085,12 @@ class SampleStream:
                                            moved.data_ptr(), self.noise.data_ptr(), s.C, ptr(self.frame_nb), self.guard.data_ptr(),
                                            _stream()), "lfi_stream_advance")
         eng._toc("stream_advance", ev)
-        self._pinned.copy_(self.guard, non_blocking=True)
-        gev = torch.cuda.Event()
-        gev.record()
-        self._guard_pending = gev
+        self._publish_guard()
         for x in srcs + ([noise, face, observed] if rows else [moved]):
             x.record_stream(torch.cuda.current_stream(self.device))
         launch = self._launch_rows if rows else functools.partial(self._launch_observe, want_z) if observe else self._launch
         if self.steps == 0 or os.environ.get("LFI_NO_GRAPH") == "1":
-            launch(masks, 1 if self.steps > 0 or self._resumed else 0)
+            launch(masks, self._first_frame)
             return
         # a captured graph per kind of step, keyed on what its launches depend on. step(): one graph, recaptured when the key changes.
         # observe(): one per key met (with and without z, per arithmetic) - alternating kinds or return_z recaptures nothing
@@ -1229,6 +1175,13 @@ class SampleStream:
                                             self.rows_nll_work.data_ptr(), self.role.data_ptr(), self.rows_work.data_ptr(), _stream()),
               "lfi_flow_step_rows_from")
         eng._toc("stream_rows_chain", ev)
+
+    def _publish_guard(self):
+        """The guard word's copy to pinned memory behind the launches that folded into it, and the event _check_guard waits on."""
+        self._pinned.copy_(self.guard, non_blocking=True)
+        gev = torch.cuda.Event()
+        gev.record()
+        self._guard_pending = gev
 
     def _check_guard(self):
         """The range guard of earlier steps (lfi_stream_advance folds max |x| of every value it moves into the session's guard word,
