@@ -62,6 +62,17 @@ def max_rel(a, b, floor=1e-3):
     return ((a - b).abs() / b.abs().clamp(min=floor)).max().item()
 
 
+def rel_l2(a, b):
+    """||a - b|| / ||b|| in fp64 (on a's device), with no max(1, .) floor. A reference whose norm is exactly 0 asks for exact
+    equality: 0.0 when a is all zeros, inf otherwise."""
+    a = torch.as_tensor(a).to(torch.float64)
+    b = torch.as_tensor(b).to(torch.float64).to(a.device)
+    nb = float(torch.linalg.vector_norm(b))
+    if nb == 0.0:
+        return 0.0 if bool((a == 0).all()) else float("inf")
+    return float(torch.linalg.vector_norm(a - b)) / nb
+
+
 def report(line):
     """Print a measured-error line and, when LFI_PARITY_REPORT names a file, append it there: the GPU run's numbers end up in
     profiles/parity_report_*.txt instead of being swallowed by `pytest -q`."""
