@@ -504,6 +504,24 @@ int lfi_flow_step_rows_from(const lfi_flow_dims* d, const lfi_flow_params* p, co
                             float* faces, int seq_len, int start, int nframes, int first_frame,
                             float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
                             float* nll, float* nll_work, const int* observed, float* rows_work, void* stream);
+/* N CANDIDATES of ONE frame per batch row (SampleStream.step_candidates, best-of-N): lfi_flow_sample_seq_nll's arguments (nframes must
+ * be 1; nll and nll_work are not used and may be NULL), then ncand >= 1, the candidates' outputs and a work area, cand_work
+ * (lfi_flow_sample_cand_work_floats(d, ncand) floats). noise is B x ncand x C (already * eps): virtual row v = b * ncand + j is
+ * candidate j of batch row b. The conditioning front end runs once for the B rows; the reverse chain runs over V = B * ncand virtual
+ * rows that read gic and the incoming h / cstate of their PARENT row in place - one launch of Ks ceil(V / 16) workgroups, nothing of
+ * the session copied V-fold. faces, h and cstate are READ ONLY here: candidate v's frame goes to cand_frames (V x C), its NLL in bits
+ * to cand_nll (V), its new state to cand_h / cand_c ([Ks][V][H]; cand_c NULL for GRU), each what lfi_flow_sample_seq_nll leaves for
+ * a row with that state, conditioning and prior draw - bit for bit on the one-launch chain. lfi_stream_commit_cand installs the
+ * chosen candidates. Shapes outside the register-resident cells, LFI_SAMPLE_CHAIN=0, LFI_FLOW_GENERIC=1: a gather launch broadcasts
+ * gic / h / c to V rows, then the per-step launches and the NLL finish over V rows. Allocation-free, capturable; every argument is
+ * checked before the first launch. */
+long lfi_flow_sample_cand_work_floats(const lfi_flow_dims* d, int ncand);
+int lfi_flow_sample_cand_from(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep,
+                            const float* wct, long E, int hist1, float* pre_static, const float* noise,
+                            float* faces, int seq_len, int start, int nframes, int first_frame,
+                            float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
+                            float* nll, float* nll_work, int ncand, float* cand_frames, float* cand_nll, float* cand_h,
+                            float* cand_c, float* cand_work, void* stream);
 /* A run of nframes >= 1 frames of a chunk in which every batch row takes its role FRAME BY FRAME (SampleStream.step_rows_many): it
  * replaces a host loop of nframes lfi_flow_step_rows_from calls - the same launches, from one call with one argument check, one kernel
  * pick and one preparation of the fused conditioning kernel's weight fragments. lfi_flow_step_rows_from's arguments, frame-major:
@@ -632,6 +650,16 @@ int lfi_stream_save_rows(int B, int nrows, const int* rows, int count, const flo
 int lfi_stream_load_rows(int B, int nrows, const int* rows, const int* entries, int nentries, int count, float* const* win,
                          const int* hist, const int* dim, float* h, float* cstate, int Ks, int H, float* frame_nb, const float* in,
                          long ld_in, unsigned* guard_bits, void* stream);
+/* One of every row's candidates becomes the row's frame (SampleStream.commit), in ONE launch: for session row r, j = choice[r]
+ * (B ints on the device, clamped into 0 .. ncand - 1 by the kernel) or - choice == NULL - the arg-min of cand_nll[r, :] (ties to the
+ * lowest index; NaN counts as larger than any number; all NaN: 0). cand_frames[r, j] (lfi_flow_sample_cand_from's outputs) goes into
+ * the newest slot of the row's faces window (face_win, B x hist x C) and to out_frame (B x C); cand_h[k][r * ncand + j] to h[k][r]
+ * for every flow step k, and cand_c to cstate likewise when cstate is non-NULL; cand_nll[r, j] to out_nll[r], j to out_choice[r].
+ * The frame is folded into *guard_bits as a window value (NULL = no guard). Allocation-free, no host wait, capturable. */
+int lfi_stream_commit_cand(int B, int ncand, int C, int Ks, int H, const int* choice, const float* cand_frames,
+                           const float* cand_nll, const float* cand_h, const float* cand_c, float* face_win, int hist,
+                           float* h, float* cstate, float* out_frame, float* out_nll, int* out_choice,
+                           unsigned* guard_bits, void* stream);
 
 /* ---------------------------------------------------------------- optimiser (configure_optimizers, glow/lets_face_it_glow.py:61-72)
  * Flat-buffer Adam with global-norm gradient clipping (Trainer gradient_clip_val, hparams/final_model.yaml:126):

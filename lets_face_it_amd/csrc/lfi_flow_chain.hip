@@ -1,6 +1,6 @@
 // The per-frame side of the flow: one frame's Ks cells with the recurrent state carried by the caller. The reverse cell of the
 // samplers and of SeqGlow.invert (rev_fast_cell), the forward cell of a teacher-forced frame (fwd_chain_cell), the one-launch chains
-// over them (reverse, forward, and both at once row by row), the persistent reverse walk, and every entry point a sampler or a
+// over them (reverse, forward, both at once row by row, and the reverse chain over N candidates per row), the persistent reverse walk, and every entry point a sampler or a
 // streaming session calls. Nothing here is reached by the training step: that side is lfi_flow.hip, and what the two share - the
 // cell's structs and carves, the generic cell bodies, the register-resident cell's phases, the hand-off primitives, fill_flow and
 // the switch readers - is lfi_flow_cells.h.
@@ -30,11 +30,15 @@ __global__ __launch_bounds__(NT) void flow_step_kernel(FlowK f, CellIO io) {
 // RM (flow_rows_chain_kernel): a row-masked cell. Everything it leaves in memory - h_out / c_out, its output tile or the frame row, the
 // hand-over q or the NLL word - is stored only for the tile's rows whose role word (io.role) is io.role_want; the other rows still
 // pass through the products (see that kernel) and are dropped. Not RM: none of it is compiled.
-template <int NG, bool X3 = false, bool XW = false, bool NLL = false, bool RM = false>
+// CD (flow_cand_chain_kernel): a candidate cell. io.rows counts VIRTUAL rows, `ncand` per session row; virtual row v reads h_prev,
+// c_prev and gic from row v / ncand of the session's arrays (io.h_prev / io.c_prev / io.gic are the parents') and stores everything
+// at row v of its own. The division is made once per thread where those loads are requested, in front of the wait. Not CD: none of
+// it is compiled.
+template <int NG, bool X3 = false, bool XW = false, bool NLL = false, bool RM = false, bool CD = false>
 __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, int b0, const unsigned* wait_flag,
                                               unsigned* abort_w, unsigned* pub_flag, int* s_ok, unsigned need = 1u,
                                               unsigned pub_value = 1u, const float* q_in = nullptr, float* q_out = nullptr,
-                                              bool q_last = false) {
+                                              bool q_last = false, int ncand = 1) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, kq = lane >> 4;
   const int ri = tid >> 5, cl = tid & 31;
@@ -86,10 +90,11 @@ __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, 
     // (its LDS image gates the barrier), then the h-side fragments of the product that runs before the wait; the fragments of the
     // phases behind the wait follow and arrive under that product.
     const int row = b0 + ri;
+    const int hrow = CD ? row / ncand : row;
 #pragma unroll
     for (int q = 0; q < FB_H / 2; ++q) {
       const int j = cl + 32 * q;
-      hv[q] = (io.h_prev && row < rows && j < H) ? ld_tile(io.h_prev + (long)row * H + j, io.state_l2 == 0) : 0.0f;
+      hv[q] = (io.h_prev && row < rows && j < H) ? ld_tile(io.h_prev + (long)hrow * H + j, io.state_l2 == 0) : 0.0f;
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -119,7 +124,8 @@ __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, 
     for (int g = 0; g < NG; ++g) bh[g] = bhh[g * H + jc];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int row = min(b0 + kq * 4 + r, rows - 1);
+      const int vrow = min(b0 + kq * 4 + r, rows - 1);
+      const int row = CD ? vrow / ncand : vrow;
 #pragma unroll
       for (int g = 0; g < NG; ++g) gc[r][g] = io.gic[(long)row * G + g * H + jc];
       cprev[r] = (NG == 4 && io.c_prev) ? ld_tile(io.c_prev + (long)row * H + jc, io.state_l2 == 0) : 0.0f;
@@ -140,9 +146,10 @@ __device__ __forceinline__ bool rev_fast_cell(const FlowK& f, const CellIO& io, 
     for (int c = Ch + cl; c < Ch16; c += 32) Zt[c * LT + ri] = 0.0f;
   } else {
     const int row = b0 + ri;
+    const int hrow = CD ? row / ncand : row;
     const bool rok = row < rows;
     for (int j = cl; j < H16; j += 32) {
-      Ht[j * LT + ri] = (io.h_prev && rok && j < H) ? ld_tile(io.h_prev + (long)row * H + j, io.state_l2 == 0) : 0.0f;
+      Ht[j * LT + ri] = (io.h_prev && rok && j < H) ? ld_tile(io.h_prev + (long)hrow * H + j, io.state_l2 == 0) : 0.0f;
       if (j >= H) Hn[j * LT + ri] = 0.0f;
     }
     for (int c = Ch + cl; c < Ch16; c += 32) Zt[c * LT + ri] = 0.0f;
@@ -461,6 +468,76 @@ __global__ __launch_bounds__(NT) void flow_rev_chain_kernel(FlowK f, RevChain rc
   }
 }
 
+// N CANDIDATES of one generated frame per session row (SampleStream.step_candidates): flow_rev_chain_kernel over V = B * ncand virtual
+// rows, always with the NLL hand-over. Virtual row v is candidate v % ncand of session row v / ncand: it takes its own prior draw
+// (noise, V x C) and reads gic and the incoming h / c of its PARENT row in place (the CD cell) - within one frame the candidates of a
+// row share their conditioning and their recurrent state, so nothing of the session's is copied V-fold and nothing of it is written.
+// What a candidate leaves goes to areas of its own: its frame to `frames` (V x C), its NLL word to nll[v], its new state to
+// ch / cc ([Ks][V][H]); lfi_stream_commit_cand installs the chosen one. Ks * ceil(V / 16) workgroups, ids by ticket, k descending; the
+// ticket and progress words are sized for V. Rows of one tile may belong to different parents - rows never mix inside a cell.
+struct CandChain {
+  const float* noise;     // V x C prior draws
+  float *xa, *xb;         // V x C tile buffers: step k writes (k & 1) ? xa : xb
+  float* frames;          // V x C: the candidates' frames
+  const float* gic;       // [Ks][B][G], the parents'
+  const float *h, *cstate;   // [Ks][B][H], the parents' state: read only
+  float *ch, *cc;         // [Ks][V][H]: the candidates' new state
+  int has_prev;           // 0 at the first frame of a session (zero state: h / cstate are not read)
+  int V, ncand, nbt;      // nbt = ceil(V / 16)
+  unsigned* pipe;         // ticket, abort, progress words (zeroed before every launch)
+  float *qa, *qb;         // V floats each: the log-density hand-over
+  float* nll;             // V floats
+};
+template <int NG, bool X3, bool XW>
+__global__ __launch_bounds__(NT) void flow_cand_chain_kernel(FlowK f, CandChain rc) {
+  __shared__ int s_id, s_ok;
+  if (threadIdx.x == 0) s_id = (int)atomicAdd(rc.pipe, 1u);
+  __syncthreads();
+  const int nbt = rc.nbt, V = rc.V;
+  const int kk = s_id / nbt, bt = s_id - kk * nbt;
+  if (kk >= f.Ks) return;
+  const int k = f.Ks - 1 - kk;
+  unsigned* prog = rc.pipe + PIPE_HDR;
+  CellIO io = {};
+  io.k = k; io.rows = V; io.ldx = f.C; io.ldxo = f.C;
+  io.x_in = (k == f.Ks - 1) ? rc.noise : (((k + 1) & 1) ? rc.xa : rc.xb);
+  io.x_out = (k == 0) ? rc.frames : ((k & 1) ? rc.xa : rc.xb);
+  io.h_prev = rc.has_prev ? rc.h + (long)k * f.B * f.H : nullptr;
+  io.h_out = rc.ch + (long)k * V * f.H;
+  if (NG == 4) { io.c_prev = rc.has_prev ? rc.cstate + (long)k * f.B * f.H : nullptr; io.c_out = rc.cc + (long)k * V * f.H; }
+  io.gic = rc.gic + (long)k * f.B * f.G;
+  rev_fast_cell<NG, X3, XW, true, false, true>(f, io, bt * MB, k + 1 < f.Ks ? prog + (k + 1) * nbt + bt : nullptr, rc.pipe + 1,
+                                               k > 0 ? prog + k * nbt + bt : nullptr, &s_ok, 1u, 1u,
+                                               k + 1 < f.Ks ? (((k + 1) & 1) ? rc.qa : rc.qb) : nullptr,
+                                               k == 0 ? rc.nll : ((k & 1) ? rc.qa : rc.qb), k == 0, rc.ncand);
+  if (k == 0 && ld_agent(rc.pipe + 1) != 0u) {   // an abandoned chain must not pass for candidates
+    const int row = bt * MB + (int)(threadIdx.x >> 5);
+    if (row < V) {
+      for (int c = threadIdx.x & 31; c < f.C; c += 32) rc.frames[(long)row * f.C + c] = __builtin_nanf("");
+      if ((threadIdx.x & 31) == 0) rc.nll[row] = __builtin_nanf("");
+    }
+  }
+}
+
+// The candidates on the per-step launches (shapes outside the register-resident cells, LFI_SAMPLE_CHAIN=0, LFI_FLOW_GENERIC=1): the
+// parents' gic and incoming state broadcast to V rows, which the existing cells then advance in place. Workgroup (v, k).
+__global__ __launch_bounds__(256) void cand_gather_kernel(const float* __restrict__ gic, const float* __restrict__ h,
+                                                          const float* __restrict__ cstate, int B, int V, int ncand, int G, int H,
+                                                          int has_prev, float* __restrict__ gicv, float* __restrict__ ch,
+                                                          float* __restrict__ cc) {
+  const int v = blockIdx.x, k = blockIdx.y;
+  const long b = v / ncand;
+  const float* g = gic + ((long)k * B + b) * G;
+  float* gv = gicv + ((long)k * V + v) * G;
+  for (int j = threadIdx.x; j < G; j += 256) gv[j] = g[j];
+  if (!has_prev) return;
+  const long src = ((long)k * B + b) * H, dst = ((long)k * V + v) * H;
+  for (int j = threadIdx.x; j < H; j += 256) {
+    ch[dst + j] = h[src + j];
+    if (cstate) cc[dst + j] = cstate[src + j];
+  }
+}
+
 // ------------------------------------------------------------------------------------------- forward chain (teacher-forced frame)
 // (the cell itself, fwd_chain_cell, is in lfi_flow_cells.h: lfi_flow_chunk.hip runs it too)
 // One OBSERVED frame of a streaming session (SampleStream.observe): all Ks forward flow steps of all batch tiles in ONE launch, the
@@ -649,6 +726,7 @@ typedef void (*FlowRevWalkKernel)(FlowK, RevWalk);
 typedef void (*FlowRevChainKernel)(FlowK, RevChain);
 typedef void (*FlowFwdChainKernel)(FlowK, FwdChain);
 typedef void (*FlowRowsChainKernel)(FlowK, RowsChain);
+typedef void (*FlowCandChainKernel)(FlowK, CandChain);
 
 FlowStepKernel flow_step_rev_pick(bool fast, bool lstm) {
   if (!fast) return flow_step_kernel<true>;
@@ -663,6 +741,12 @@ FlowRevChainKernel flow_rev_chain_pick_(bool lstm, bool x3, bool xw) {
 }
 FlowRevChainKernel flow_rev_chain_pick(bool lstm, bool x3, bool xw, bool nll) {
   return nll ? flow_rev_chain_pick_<true>(lstm, x3, xw) : flow_rev_chain_pick_<false>(lstm, x3, xw);
+}
+// the candidate chain: flow_rev_chain_pick's rule
+FlowCandChainKernel flow_cand_chain_pick(bool lstm, bool x3, bool xw) {
+  if (lstm) return flow_cand_chain_kernel<4, false, false>;
+  if (xw) return flow_cand_chain_kernel<3, true, true>;
+  return x3 ? flow_cand_chain_kernel<3, true, false> : flow_cand_chain_kernel<3, false, false>;
 }
 FlowFwdChainKernel flow_fwd_chain_pick(bool lstm, bool x3) {
   if (lstm) return flow_fwd_chain_kernel<4, false>;
@@ -1053,6 +1137,92 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
                          f.ldconst, B, C, nll + (long)n * B);
   }
   LFI_LAUNCH_CHECK("lfi_flow_sample_seq");
+  return LFI_OK;
+}
+
+// ---- N candidates of one frame per session row (SampleStream.step_candidates)
+namespace {
+// the carve of lfi_flow_sample_cand_from's candidate work area
+struct CandWork {
+  unsigned* pipe; long pipe_words;
+  float *xa, *xb;     // V x C ping / pong tiles
+  float *qa, *qb;     // V floats each: the log-density hand-over (qa: the per-step launches' accumulator)
+  float* gicv;        // per-step launches only: [Ks][V][G], the parents' gic broadcast
+  long total;
+};
+CandWork cand_work_carve(float* base, long V, long C, long G, long Ks) {
+  CandWork w = {};
+  const long tiles = (V + MB - 1) / MB;
+  long o = 0;
+  w.pipe = reinterpret_cast<unsigned*>(base); w.pipe_words = ((long)PIPE_HDR + Ks * tiles + 3) & ~3L; o += w.pipe_words;
+  w.xa = base + o; o += V * C;
+  w.xb = base + o; o += V * C;
+  w.qa = base + o; o += V;
+  w.qb = base + o; o += V;
+  w.gicv = base + o; o += Ks * V * G;
+  w.total = o + 8;
+  return w;
+}
+constexpr long kCandMaxRows = 1L << 22;   // virtual rows of one call
+}  // namespace
+
+extern "C" long lfi_flow_sample_cand_work_floats(const lfi_flow_dims* d, int ncand) {
+  if (!d || ncand < 1 || d->B < 1 || (long)d->B * ncand > kCandMaxRows) return 0;
+  return cand_work_carve(nullptr, (long)d->B * ncand, d->C, (long)(d->lstm ? 4 : 3) * d->H, d->Ks).total;
+}
+
+extern "C" int lfi_flow_sample_cand_from(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct,
+                                         long E, int hist1, float* pre_static, const float* noise, float* faces, int seq_len,
+                                         int start, int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1,
+                                         float* p1work, float* work, float* nll, float* nll_work, int ncand, float* cand_frames,
+                                         float* cand_nll, float* cand_h, float* cand_c, float* cand_work, void* stream) {
+  const char* who = "lfi_flow_sample_cand_from";
+  (void)nll; (void)nll_work;
+  FlowK f = {};
+  int rc = fill_flow(d, p, prep, &f, who);
+  if (rc) return rc;
+  if ((rc = frame_args_check(who, who, d, prep && wct && pre_static && noise && faces && h && work && cand_frames && cand_nll && cand_h && cand_work,
+                             E, hist1, start, nframes, seq_len, cstate, first_frame))) return rc;
+  LFI_REQUIRE(nframes == 1, "%s: %d frames (one frame per call)", who, nframes);
+  LFI_REQUIRE(ncand >= 1 && (long)d->B * ncand <= kCandMaxRows, "%s: %d candidates per row (1 .. %ld at batch %d)", who, ncand,
+              kCandMaxRows / d->B, d->B);
+  LFI_REQUIRE(!d->lstm || cand_c, "%s: the LSTM cell needs cand_c", who);
+  LFI_REQUIRE((reinterpret_cast<uintptr_t>(cand_work) & 3) == 0, "%s: cand_work is not 4-byte aligned", who);
+  const int B = f.B, C = f.C, H = f.H, Ks = f.Ks, G = f.G;
+  const int V = B * ncand, nbtv = lfi_cdiv(V, MB);
+  hipStream_t st = (hipStream_t)stream;
+  const bool fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
+  const bool chain = fast && lfi_env_on("LFI_SAMPLE_CHAIN");
+  const bool x3 = flow_x3_rev_cell(d, f);
+  const bool xw = x3 && chain && flow_sample_wfrag16_enabled();
+  const size_t lds = (size_t)(fast ? carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total : carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout).total) *
+                     sizeof(float);
+  const FlowCandChainKernel chain_kernel = flow_cand_chain_pick(f.lstm, x3, xw);
+  const FlowStepKernel cell = flow_step_rev_pick(fast, f.lstm);
+  if ((rc = chain ? set_flow_lds(chain_kernel, lds, who) : set_flow_lds(cell, lds, who))) return rc;
+  const CandWork cw = cand_work_carve(cand_work, V, C, G, Ks);
+  // the front end for the session's B rows, unchanged; the chain's words are the candidate area's (sized for V)
+  SampleFront sf = {};
+  if ((rc = sample_front_setup(&sf, d, p, &f, wct, E, hist1, pre_static, faces, seq_len, p1, p1work, work, chain, 1, stream, who,
+                               chain ? cw.pipe : nullptr, (size_t)cw.pipe_words))) return rc;
+  if ((rc = sample_front_frame(sf, start, pre_static, 0, stream))) return rc;
+  const int has_prev = first_frame > 0 ? 1 : 0;
+  if (chain) {
+    CandChain cc = {};
+    cc.noise = noise; cc.xa = cw.xa; cc.xb = cw.xb; cc.frames = cand_frames; cc.gic = sf.gic; cc.h = h; cc.cstate = cstate;
+    cc.ch = cand_h; cc.cc = cand_c; cc.has_prev = has_prev; cc.V = V; cc.ncand = ncand; cc.nbt = nbtv; cc.pipe = cw.pipe;
+    cc.qa = cw.qa; cc.qb = cw.qb; cc.nll = cand_nll;
+    if ((rc = sample_front_clear_chain(sf, st, who))) return rc;   // (sf's chain words are cw.pipe here)
+    hipLaunchKernelGGL(chain_kernel, dim3(Ks * nbtv), dim3(NT), lds, st, f, cc);
+  } else {
+    hipLaunchKernelGGL(cand_gather_kernel, dim3(V, Ks), dim3(256), 0, st, sf.gic, h, f.lstm ? cstate : nullptr, B, V, ncand, G, H, has_prev,
+                       cw.gicv, cand_h, cand_c);
+    FlowK fv = f;   // the cells over V rows
+    fv.B = V; fv.F = V; fv.nbt = nbtv;
+    launch_rev_steps(fv, cell, lds, st, cw.gicv, cand_h, cand_c, has_prev, cw.xa, cw.xb, noise, C, cand_frames, C, cw.qa);
+    hipLaunchKernelGGL(sample_nll_finish_kernel, dim3(lfi_cdiv(V, 256)), dim3(256), 0, st, noise, cw.qa, f.ldconst, V, C, cand_nll);
+  }
+  LFI_LAUNCH_CHECK(who);
   return LFI_OK;
 }
 

@@ -7,7 +7,8 @@
 // frame at a time. A second entry point puts listed batch rows back to the state of the open (SampleStream.reset_rows), between
 // steps, leaving the other rows alone: conversations join and leave one batched session independently. Two more copy listed rows'
 // live state out of a session into plain fp32 records and back into any session of the same model (SampleStream.save_rows /
-// load_rows): conversations move between sessions, pause on the host, branch and roll back.
+// load_rows): conversations move between sessions, pause on the host, branch and roll back. One more installs the chosen one of every
+// row's candidates for a frame (SampleStream.commit, after step_candidates).
 #include "lfi_common.h"
 
 #include <vector>
@@ -457,6 +458,56 @@ int stream_chunk_args(const char* what, unsigned kind, int B, int n, int start, 
   return LFI_OK;
 }
 
+// ---- best-of-N (SampleStream.step_candidates / commit): one of a row's candidates becomes the row's frame
+//
+// Workgroup r: session row r. Thread 0 picks j - the clamped choice[r], or (choice == NULL) the arg-min of the row's ncand NLL words:
+// ties go to the lowest index, NaN counts as larger than any number, all NaN picks 0 - then the workgroup copies candidate (r, j): its
+// frame into the newest slot of the row's faces window and into out_frame, its h / c of every flow step into the session's, its NLL
+// word and j into out_nll / out_choice. Every word has one writer; the frame is folded into the guard word as a window value is.
+__global__ __launch_bounds__(256) void stream_commit_cand_kernel(int B, int ncand, int C, int Ks, int H, const int* __restrict__ choice,
+                                                                const float* __restrict__ cand_frames,
+                                                                const float* __restrict__ cand_nll, const float* __restrict__ cand_h,
+                                                                const float* __restrict__ cand_c, float* __restrict__ face_win,
+                                                                int hist, float* __restrict__ h, float* __restrict__ cstate,
+                                                                float* __restrict__ out_frame, float* __restrict__ out_nll,
+                                                                int* __restrict__ out_choice, unsigned* __restrict__ guard) {
+  __shared__ int s_j;
+  const long r = blockIdx.x;
+  if (threadIdx.x == 0) {
+    int j = 0;
+    if (choice) {
+      j = min(max(choice[r], 0), ncand - 1);
+    } else {
+      float best = cand_nll[r * ncand];
+      for (int i = 1; i < ncand; ++i) {
+        const float v = cand_nll[r * ncand + i];
+        if (v < best || (best != best && v == v)) { best = v; j = i; }
+      }
+    }
+    s_j = j;
+    out_choice[r] = j;
+    out_nll[r] = cand_nll[r * ncand + j];
+  }
+  __syncthreads();
+  const long v = r * ncand + s_j, V = (long)B * ncand;
+  unsigned m = 0u;
+  float* slot = face_win + (r * hist + (hist - 1)) * C;
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const float x = cand_frames[v * C + c];
+    slot[c] = x;
+    out_frame[r * C + c] = x;
+    const unsigned a = stream_abs_bits(x);
+    m = a > m ? a : m;
+  }
+  for (int e = threadIdx.x; e < Ks * H; e += 256) {
+    const int k = e / H, c = e - k * H;
+    const long src = ((long)k * V + v) * H + c, dst = ((long)k * B + r) * H + c;
+    h[dst] = cand_h[src];
+    if (cstate) cstate[dst] = cand_c[src];
+  }
+  stream_guard_fold_block(m, guard);
+}
+
 // The checks and the launch of a chunk entry point: windows in (kChunkIn) or out.
 int stream_chunk_launch(const char* what, unsigned kind, int B, int n, int start, int count, float* const* win, float* const* seq,
                         const int* hist, const int* dim, const int* lead, const StreamChunkOpts& o, float* frame_nb, unsigned* guard,
@@ -664,4 +715,20 @@ extern "C" int lfi_stream_chunk_gen_out(int B, int n, int start, int count, floa
   o.gen_win = gen_win; o.out = out; o.ld_out = ld_out;
   return stream_chunk_launch("lfi_stream_chunk_gen_out", kChunkGen, B, n, start, count, win, seq, hist, dim, lead, o, frame_nb, guard_bits,
                              stream);
+}
+
+extern "C" int lfi_stream_commit_cand(int B, int ncand, int C, int Ks, int H, const int* choice, const float* cand_frames,
+                                      const float* cand_nll, const float* cand_h, const float* cand_c, float* face_win, int hist,
+                                      float* h, float* cstate, float* out_frame, float* out_nll, int* out_choice,
+                                      unsigned* guard_bits, void* stream) {
+  LFI_REQUIRE(B > 0 && B <= 65535, "lfi_stream_commit_cand: batch %d (1 .. 65535)", B);
+  LFI_REQUIRE(ncand >= 1 && (long)B * ncand <= (1L << 22), "lfi_stream_commit_cand: %d candidates per row at batch %d", ncand, B);
+  LFI_REQUIRE(C > 0 && Ks > 0 && H > 0 && hist >= 1, "lfi_stream_commit_cand: C = %d, Ks = %d, H = %d, hist = %d", C, Ks, H, hist);
+  LFI_REQUIRE(cand_frames && cand_nll && cand_h && face_win && h && out_frame && out_nll && out_choice,
+              "lfi_stream_commit_cand: null pointer");
+  LFI_REQUIRE(!cstate || cand_c, "lfi_stream_commit_cand: cstate without cand_c");
+  hipLaunchKernelGGL(stream_commit_cand_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, B, ncand, C, Ks, H, choice, cand_frames, cand_nll,
+                     cand_h, cand_c, face_win, hist, h, cstate, out_frame, out_nll, out_choice, guard_bits);
+  LFI_LAUNCH_CHECK("lfi_stream_commit_cand");
+  return LFI_OK;
 }

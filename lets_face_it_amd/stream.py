@@ -23,6 +23,9 @@ _PARAMS_CHANGED = ("SampleStream: the model's parameters changed since open_stre
                    "ActNorm init): a session samples with the weights of its open; open a new one")
 _ROW_FIELDS = ("C", "H", "Ks", "rnn_type", "use_frame_nb", "windows", "hist1", "R")
 _ABSENT = object()       # (an argument a call does not take, where None is a value to refuse)
+_MAX_CANDIDATES = 256    # candidates per row of one step_candidates() call
+_PENDING = ("SampleStream: %d candidates per row are pending (step_candidates): commit() one of them, or reset(), before any other "
+            "call of the session")
 
 
 def _stream():
@@ -160,6 +163,8 @@ class SampleStream:
     step runs), so training, inference() and other sessions can run between steps. Weights are frozen: a parameter change after the
     open (GlowEngine.param_version) makes step() raise."""
 
+    _pending = None          # ncand of the candidates step_candidates() left and commit() has not installed yet
+
     def __init__(self, eng, seed, noise_fn, masks_fn=None, bound=None, return_nll=False):
         check_return_nll(return_nll)
         self.return_nll = return_nll            # fixed for the session: part of what the captured graph launches
@@ -184,6 +189,7 @@ class SampleStream:
         self._rows_graphs = {}                                       # step_rows()'s own, by key
         self.score_work = self.obs_z = self.obs_nll = None   # observe()'s buffers: allocated at the first observe
         self.role = self.rows_work = self.rows_nll = self.rows_nll_work = None   # step_rows()'s: at the first step_rows
+        self._cand, self._cand_graphs = {}, {}  # step_candidates()'s buffers, per ncand (a graph holds their addresses), and its graphs
         self._chunk_ws = {}                     # observe_many()'s / step_many()'s workspaces, sized by the chunk (the graphs never address them)
         self.last_plan = None                   # diagnostic: the last step_rows_many() call's plan (plan_rows_many), offsets in the call
         self._stream = None
@@ -262,11 +268,13 @@ class SampleStream:
                              % (name, "n>=1, R=%d" % cols if rows is None else "B=%d, %d" % (rows, cols), self.device,
                                 tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x)), getattr(x, "device", None)))
 
-    def _check_usable(self):
+    def _check_usable(self, pending_ok=False):
         if self.closed:
             raise RuntimeError("SampleStream: the session is closed")
         if self.eng.param_version != self.param_version or (self._bound is not None and not self._bound()):
             raise RuntimeError(_PARAMS_CHANGED)
+        if self._pending is not None and not pending_ok:
+            raise RuntimeError(_PENDING % self._pending)
 
     # ---- session-owned engine state, on a stream that is not the legacy default one (the session's private stream for a caller on it)
     @contextlib.contextmanager
@@ -286,8 +294,8 @@ class SampleStream:
 
     # ---- public surface
     def reset(self, seed):
-        """Start a new sequence from `seed` (same batch size); the captured graph is kept."""
-        self._check_usable()
+        """Start a new sequence from `seed` (same batch size); the captured graph is kept. Pending candidates are dropped."""
+        self._check_usable(pending_ok=True)
         self._check_seed(seed)
         with self._owned():
             self._fill(seed)
@@ -404,6 +412,7 @@ class SampleStream:
         self.steps = 0
         self._resumed = False           # load_rows into a session that has not stepped sets it: the first launch keeps h / c
         self._guard_pending = None
+        self._pending = None
 
     def close(self):
         """Releases the session's buffers and graph; step() raises afterwards."""
@@ -413,6 +422,7 @@ class SampleStream:
             self._stream.synchronize()
         self.closed = True
         self._graph, self._observe_graphs, self._rows_graphs = None, {}, {}
+        self._cand, self._cand_graphs, self._pending = None, {}, None
         self._state = self._chunk_ws = None
         self.faces = self.noise = self.windows = self.cond = self.pre = self.h = self.cs = self.work = self.p1work = self._wins = None
         self.nll = self.nll_work = self.score_work = self.obs_z = self.obs_nll = None
@@ -492,6 +502,135 @@ class SampleStream:
             self.steps += 1
         self._record_out(nll, z)
         return (nll, z) if return_z else nll
+
+    @staticmethod
+    def _check_ncand(ncand):
+        """The ncand argument of step_candidates() / step_best_of(): an int in 1 .. 256, checked before any launch."""
+        if isinstance(ncand, bool) or not isinstance(ncand, int):
+            raise TypeError("ncand: expected an int, got %s %r" % (type(ncand).__name__, ncand))
+        if not 1 <= ncand <= _MAX_CANDIDATES:
+            raise ValueError("ncand: %d outside 1 .. %d" % (ncand, _MAX_CANDIDATES))
+        return ncand
+
+    def _check_cand_noise(self, noise, ncand):
+        """The candidates' prior draws, (B, ncand, C). The wording of _check_matrix."""
+        B, C_ = self.B, self.eng.spec.C
+        if not (torch.is_tensor(noise) and noise.is_cuda and noise.device == self.device and noise.dtype == torch.float32
+                and noise.is_contiguous() and tuple(noise.shape) == (B, ncand, C_)):
+            raise ValueError("noise: expected contiguous float32 GPU tensor (B=%d, ncand=%d, %d) on %s, got %s %s on %s"
+                             % (B, ncand, C_, self.device, tuple(getattr(noise, "shape", ())), getattr(noise, "dtype", type(noise)),
+                                getattr(noise, "device", None)))
+
+    def _cand_buffers(self, ncand):
+        """The buffers of step_candidates() for `ncand` candidates per row: at the first use of that ncand, outside capture, and kept -
+        the graph of an ncand holds their addresses."""
+        c = self._cand.get(ncand)
+        if c is None:
+            s, eng, B = self.eng.spec, self.eng, self.B
+            V, tag = B * ncand, ".%d" % ncand
+            dims = eng._flow_dims(B, 1)
+            floats = eng.L.lfi_flow_sample_cand_work_floats(C.byref(dims), ncand)
+            if floats <= 0:
+                raise ValueError("ncand: %d candidates for each of %d rows are more than one call takes" % (ncand, B))
+            c = self._cand[ncand] = types.SimpleNamespace(
+                noise=eng._buf("stream_cand_noise" + tag, V * s.C)[:V * s.C].view(B, ncand, s.C),
+                frames=eng._buf("stream_cand_frames" + tag, V * s.C)[:V * s.C].view(B, ncand, s.C),
+                nll=eng._buf("stream_cand_nll" + tag, V)[:V].view(B, ncand),
+                h=eng._buf("stream_cand_h" + tag, s.Ks * V * s.H),
+                c=eng._buf("stream_cand_c" + tag, s.Ks * V * s.H) if self.cs is not None else None,
+                work=eng._buf("stream_cand_work" + tag, floats),
+                choice=eng._buf_i32("stream_cand_choice" + tag, B)[:B])
+        return c
+
+    @translate_oom
+    def step_candidates(self, frame, ncand, noise=None):
+        """ncand CANDIDATES for frame t of every row (best-of-N on a live conversation), from which commit() installs one. frame: as
+        step()'s; ncand: an int in 1 .. 256; noise: (B, ncand, C) contiguous float32 on the session's device, the candidates' prior
+        draws already * eps - a temperature per candidate is the caller's choice - or None: ncand draws of the session's own, stacked
+        on dim 1. -> (faces, nll): faces (B, ncand, C), nll (B, ncand) float32 in bits - both always, whatever return_nll the
+        session was opened with. Candidate j of row r is what step(frame, noise[:, j]) generates and reports for row r, bit for bit
+        on the one-launch chain (rows never mix inside a cell); where the per-step launches run instead - wide flows,
+        LFI_SAMPLE_CHAIN=0, LFI_FLOW_GENERIC=1 - to the session's gates.
+
+        Within one frame the candidates of a row share their conditioning windows, their faces window and their incoming h / c. Per
+        call: lfi_stream_advance exactly as a step's (the windows and the frame counter move on; the candidates' noise goes to a
+        session-owned buffer and passes the range guard), the static part for B windows, then lfi_flow_sample_cand_from: the
+        conditioning front end for B rows and the reverse chain over B * ncand virtual rows that read their parent row's gic and
+        state in place. In train mode the candidates share their row's dropout masks. From the second frame on, one captured
+        hipGraph of its own per (per-frame arithmetic, masks injected, ncand), replayed; no host wait in steady state.
+
+        The call leaves the session PENDING: the newest slot of the faces window and h / c are not written yet and `steps` has not
+        moved. Until commit() - or reset(), which drops the candidates - every other call of the session raises RuntimeError."""
+        s = self.eng.spec
+        self._check_usable()
+        ncand = self._check_ncand(ncand)
+        srcs = self._check_frame(frame)
+        if noise is not None:
+            self._check_cand_noise(noise, ncand)
+        with self._owned():
+            self._check_guard()
+            cand = self._cand_buffers(ncand)
+            if noise is None:
+                noise = torch.stack([self._noise_fn(self.B, s.C) for _ in range(ncand)], 1).contiguous()
+            self._advance(srcs, noise, None, ncand=ncand)
+            faces, nll = cand.frames.clone(), cand.nll.clone()
+            self._pending = ncand
+        self._record_out(faces, nll)
+        return faces, nll
+
+    def _check_choice(self, choice, ncand):
+        """commit()'s choice, checked before any launch -> (a (B,) integer tensor on the session's device, which the kernel clamps,
+        or None; host data as a validated list of B ints in 0 .. ncand - 1, or None)."""
+        if choice is None:
+            return None, None
+        if torch.is_tensor(choice) and choice.is_cuda:
+            if choice.device != self.device:
+                raise ValueError("choice: on %s, the session on %s" % (choice.device, self.device))
+            if choice.dtype not in (torch.int32, torch.int64) or tuple(choice.shape) != (self.B,):
+                raise ValueError("choice: expected %d entries (B,) of int32 / int64, got %s %s" % (self.B, tuple(choice.shape), choice.dtype))
+            return choice, None
+        return None, _index_list("choice", choice, ncand, "the row's candidates", count=self.B, distinct=False)
+
+    @translate_oom
+    def commit(self, choice=None):
+        """Install one of the pending candidates of every row (step_candidates) as the row's frame t. choice: None - each row's
+        candidate of least NLL, picked on the device (ties to the lowest index; a NaN never wins unless all are NaN, then 0) - or a
+        (B,) int32 / int64 tensor on the session's device, clamped into 0 .. ncand - 1 by the kernel, or a host sequence / CPU
+        integer tensor of B ints in that range, copied in asynchronously. -> (frame (B, C), nll (B,), choice (B,) int32): the
+        installed candidates. One launch (lfi_stream_commit_cand), no host wait: the frame enters the newest slot of the faces window,
+        the candidate's h / c become the row's, `steps` += 1 - the session is exactly where step(frame, noise[r, choice[r]]) per row
+        would have left it, and no longer pending."""
+        s, eng, B = self.eng.spec, self.eng, self.B
+        self._check_usable(pending_ok=True)
+        ncand = self._pending
+        if ncand is None:
+            raise RuntimeError("SampleStream: commit() without pending candidates (step_candidates comes first)")
+        dev, host = self._check_choice(choice, ncand)
+        with self._owned():
+            cand = self._cand[ncand]
+            if dev is not None:
+                cand.choice.copy_(dev)
+                dev.record_stream(torch.cuda.current_stream(self.device))
+            elif host is not None:
+                cand.choice.copy_(torch.tensor(host, dtype=torch.int32).pin_memory(), non_blocking=True)
+            out = torch.empty(B, s.C, dtype=torch.float32, device=self.device)
+            nll = torch.empty(B, dtype=torch.float32, device=self.device)
+            picked = torch.empty(B, dtype=torch.int32, device=self.device)
+            check(eng.L.lfi_stream_commit_cand(B, ncand, s.C, s.Ks, s.H, None if choice is None else cand.choice.data_ptr(),
+                                               cand.frames.data_ptr(), cand.nll.data_ptr(), cand.h.data_ptr(), ptr(cand.c),
+                                               self.faces.data_ptr(), self.hist1 + 1, self.h.data_ptr(), ptr(self.cs), out.data_ptr(),
+                                               nll.data_ptr(), picked.data_ptr(), self.guard.data_ptr(), _stream()),
+                  "lfi_stream_commit_cand")
+            self._pending = None
+            self.steps += 1
+        self._record_out(out, nll, picked)
+        return out, nll, picked
+
+    def step_best_of(self, frame, ncand, noise=None):
+        """step_candidates(frame, ncand, noise) followed by commit(): every row's candidate of least NLL becomes its frame t. ->
+        commit()'s (frame, nll, choice)."""
+        self.step_candidates(frame, ncand, noise)
+        return self.commit()
 
     def _check_chunk(self, x, name, cols, n=None):
         """A chunk's frames of one modality, (B, n, cols) with n >= 1 (None: whatever it has) -> n. The wording of _check_matrix."""
@@ -1059,11 +1198,12 @@ class SampleStream:
                 if x is not None and x.device == self.device:
                     x.record_stream(torch.cuda.current_stream(self.device))
 
-    def _advance(self, srcs, noise, face, want_z=False, observed=None):
+    def _advance(self, srcs, noise, face, want_z=False, observed=None, ncand=None):
         """One frame forward, inside _owned(): masks, lfi_stream_advance, the guard's copy, then the launch or the replay. face None: a
         generating step with the prior draw `noise`; else an observing one - the frame is the faces window's source (and fills the
         noise slot, which an observing step does not read); want_z: the observing launch also writes the frame's latent. observed (a
-        (B,) bool tensor on the device): a step_rows() step - both `noise` and `face`, each used in the rows of its role."""
+        (B,) bool tensor on the device): a step_rows() step - both `noise` and `face`, each used in the rows of its role. ncand: a
+        step_candidates() step - `noise` is (B, ncand, C) and moves into that ncand's own buffer, a row of ncand * C values."""
         s, eng, B = self.eng.spec, self.eng, self.B
         rows = observed is not None
         observe = face is not None and not rows
@@ -1081,22 +1221,26 @@ class SampleStream:
                                                 observed.data_ptr(), self.role.data_ptr(), self.guard.data_ptr(), _stream()),
                   "lfi_stream_advance_rows")
         else:
+            slot, width = (self.noise, s.C) if ncand is None else (self._cand[ncand].noise, ncand * s.C)
             check(eng.L.lfi_stream_advance(B, len(self._row_win), self._row_win, self._src_p, self._row_hist, self._row_dim,
-                                           moved.data_ptr(), self.noise.data_ptr(), s.C, ptr(self.frame_nb), self.guard.data_ptr(),
+                                           moved.data_ptr(), slot.data_ptr(), width, ptr(self.frame_nb), self.guard.data_ptr(),
                                            _stream()), "lfi_stream_advance")
         eng._toc("stream_advance", ev)
         self._publish_guard()
         for x in srcs + ([noise, face, observed] if rows else [moved]):
             x.record_stream(torch.cuda.current_stream(self.device))
         launch = self._launch_rows if rows else functools.partial(self._launch_observe, want_z) if observe else self._launch
+        if ncand is not None:
+            launch = functools.partial(self._launch_cand, ncand)
         if self.steps == 0 or os.environ.get("LFI_NO_GRAPH") == "1":
             launch(masks, self._first_frame)
             return
         # a captured graph per kind of step, keyed on what its launches depend on. step(): one graph, recaptured when the key changes.
         # observe(): one per key met (with and without z, per arithmetic) - alternating kinds or return_z recaptures nothing
         # step_rows(): one per key met; the role mask is data at a session-owned address (self.role), not part of the key
-        key = (self.frame_precision, masks is not None) + ((want_z,) if observe else ())
-        own = self._rows_graphs if rows else self._observe_graphs if observe else None
+        # step_candidates(): one per key met, ncand among it (the launch's grid and the buffers it addresses)
+        key = (self.frame_precision, masks is not None) + ((want_z,) if observe else ()) + ((ncand,) if ncand is not None else ())
+        own = self._rows_graphs if rows else self._observe_graphs if observe else self._cand_graphs if ncand is not None else None
         g = own.get(key) if own is not None else (self._graph if self._graph_key == key else None)
         if g is None:
             timers, eng.timers = eng.timers, None
@@ -1175,6 +1319,21 @@ class SampleStream:
                                             self.rows_nll_work.data_ptr(), self.role.data_ptr(), self.rows_work.data_ptr(), _stream()),
               "lfi_flow_step_rows_from")
         eng._toc("stream_rows_chain", ev)
+
+    def _launch_cand(self, ncand, masks, first_frame):
+        """The static part for B windows, then the front end for B rows and the candidate chain over B * ncand virtual rows: the
+        session's faces window and h / c are read only, what the candidates leave goes to that ncand's buffers."""
+        eng, s = self.eng, self.eng.spec
+        cand = self._cand[ncand]
+        dims, p = self._static(masks)
+        ev = eng._tic("stream_chain")
+        check(eng.L.lfi_flow_sample_cand_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
+                                              self.pre.data_ptr(), cand.noise.data_ptr(), self.faces.data_ptr(), self.hist1 + 1,
+                                              self.hist1, 1, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
+                                              self.p1work.data_ptr(), self.work.data_ptr(), None, None, ncand, cand.frames.data_ptr(),
+                                              cand.nll.data_ptr(), cand.h.data_ptr(), ptr(cand.c), cand.work.data_ptr(), _stream()),
+              "lfi_flow_sample_cand_from")
+        eng._toc("stream_chain", ev)
 
     def _publish_guard(self):
         """The guard word's copy to pinned memory behind the launches that folded into it, and the event _check_guard waits on."""

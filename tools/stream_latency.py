@@ -5,6 +5,7 @@ alternative without a session: re-running SeqGlow.inference over the whole prefi
                                  [--churn 1,16,64 [--churn-batch 256]] [--migrate 16 [--migrate-batch 256]] [--nll 1,256]
                                  [--observe 1,16,256] [--rows 1,16,256] [--observe-many 16,64,250]
                                  [--step-many 4,16,64] [--observe-ragged 16,64,250] [--rows-many 4,16,64]
+                                 [--candidates 16,8 [--passes 5]]
 
 Per batch size: the wall-clock time from step() to the generated frame on the host (a synchronise after every step: what a live agent
 waits for), its GPU time (HIP events around the step), and a per-kernel breakdown from the engine's enable_timing on an eager session
@@ -62,7 +63,17 @@ rotating, --reps times after two untimed rounds: (a) n step_rows() calls in a Py
 there); (c) step_rows_many(n) with odd rows observing and even rows generating - every tile mixed (B >= 2; at B = 1 the one row
 alternates frame by frame; below B = 32 the loop runs this mask); (d) step_rows_many(n) with a prompt-then-continue mask, prompt
 lengths spread over n / 4 .. 3 n / 4, with the plan on and (e) with LFI_ROWS_MANY_OBSERVE_RUN=0. Per frame: wall clock and GPU time
-as --step-many. Then where the GPU time of arms (d) and (e) goes, from the engine's enable_timing."""
+as --step-many. Then where the GPU time of arms (d) and (e) goes, from the engine's enable_timing.
+
+--candidates B,ncand: this leg ALONE, written to --out (default: printed only): best-of-N per frame for B conversations, two arms
+alternated as whole passes, --passes of each (the recipe first) of --steps timed frames after --warmup untimed ones, a caller on the
+legacy default stream. (new) step_candidates(frame, ncand, noise) + commit() on a session of B rows. (recipe) what INTEGRATION.md
+prescribed before those calls existed, on a session of B * ncand rows opened with return_nll=True, conversation r at home in row
+r * ncand: save_rows(home rows), load_rows(every row, entries = row // ncand), step() with every row's conditioning repeated ncand
+times (the repeats are made before the clock starts), the arg-min per conversation read on the host, save_rows(the winners'
+rows), load_rows(home rows). Per pass: the median frame's wall clock (a synchronise after the frame) and GPU time (HIP events). Then
+the stream_advance / stream_static / stream_chain timers of both arms from the engine's enable_timing on eager sessions
+(LFI_NO_GRAPH=1), and the shader clock under the new arm's load."""
 import argparse
 import contextlib
 import os
@@ -93,6 +104,8 @@ def main():
     ap.add_argument("--step-many", default=None, help="frames per call of the step_many() leg, e.g. 4,16,64: runs this leg alone")
     ap.add_argument("--observe-ragged", default=None, help="chunk lengths of the ragged observe_many() leg: runs this leg alone")
     ap.add_argument("--rows-many", default=None, help="frames per call of the step_rows_many() leg, e.g. 4,16,64: runs this leg alone")
+    ap.add_argument("--candidates", default=None, help="B,ncand of the best-of-N leg, e.g. 16,8: runs this leg alone")
+    ap.add_argument("--passes", type=int, default=5, help="with --candidates: whole passes per arm, alternated")
     ap.add_argument("--reps", type=int, default=7, help="with --observe-many / --step-many / --observe-ragged: timed rounds per (batch size, chunk length)")
     a = ap.parse_args()
     resources = chain_kernel_resources() if a.observe_ragged else None     # (compiles; before the GPU is initialised)
@@ -122,6 +135,16 @@ def main():
     s = m.spec
     start, C = s.start, s.C
     dims = {"p1_face": C, "p2_face": C, "p1_speech": s.S, "p2_speech": s.S}
+    if a.candidates:
+        B, ncand = (int(v) for v in a.candidates.split(","))
+        text = candidates_report(m, dev, B, ncand, a.passes, a.steps, a.warmup, dims, start, C, torch.cuda.get_device_name(dev), bench, helper)
+        bench.stop_smi_helper(helper)
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text)
+        return
     if a.rows:
         text = rows_report(m, dev, [int(v) for v in a.rows.split(",")], a.steps, a.warmup, dims, start, C, torch.cuda.get_device_name(dev))
         bench.stop_smi_helper(helper)
@@ -805,6 +828,104 @@ def rows_many_report(m, dev, batches, ns, reps, dims, start, C, device_name):
     for B, n, name, t in split:
         a, b, c = (t.get("stream_chunk_" + k, 0.0) for k in ("in", "static", "rows_chain"))
         lines.append("| %d | %d | %s | %.3f | %.3f | %.3f | %.4f |" % (B, n, name, a, b, c, c / n))
+    return "\n".join(lines) + "\n"
+
+
+def candidates_report(m, dev, B, ncand, passes, steps, warmup, dims, start, C, device_name, bench, helper):
+    """The --candidates report: per pass the median frame of step_candidates + commit() and of the save / load / step / save / load
+    recipe, alternated as whole passes; then the timer split of both arms on eager sessions."""
+    import torch
+    s = m.spec
+    eng = m._ensure_engine(dev)
+    V, total = B * ncand, warmup + steps
+    gd = torch.Generator().manual_seed(B * 1000 + ncand)
+    data = {k: torch.randn(B, start + total, d, generator=gd).to(dev) for k, d in dims.items()}
+    seed = {k: v[:, :start].contiguous() for k, v in data.items()}
+    frames = [{k: v[:, start + n].contiguous() for k, v in data.items() if k != "p1_face"} for n in range(total)]
+    noise = (torch.randn(total, B, ncand, C, generator=gd) * 0.8).to(dev)
+    # the recipe's session: every conversation's seed, conditioning and noise in ncand neighbouring rows
+    seed_v = {k: v.repeat_interleave(ncand, 0).contiguous() for k, v in seed.items()}
+    frames_v = [{k: v.repeat_interleave(ncand, 0).contiguous() for k, v in f.items()} for f in frames]
+    noise_v = noise.view(total, V, C)
+    home, every, parent = [r * ncand for r in range(B)], list(range(V)), [v // ncand for v in range(V)]
+    base = torch.tensor(home, device=dev)
+
+    def new_frame(st, n):
+        st.step_candidates(frames[n], ncand, noise[n])
+        return st.commit()[0]
+
+    def recipe_frame(st, n):
+        st.load_rows(every, st.save_rows(home), parent)
+        out, nll = st.step(frames_v[n], noise_v[n])
+        win = (base + nll.view(B, ncand).argmin(1)).tolist()        # (the arg-min on the host side: the row lists are host data)
+        st.load_rows(home, st.save_rows(win))
+        return out[win]
+
+    def run(st, frame_fn, timed=True):
+        wall, gpu = [], []
+        for n in range(total):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e0.record()
+            frame_fn(st, n)
+            e1.record()
+            e1.synchronize()
+            t1 = time.perf_counter()
+            if n >= warmup:
+                wall.append((t1 - t0) * 1e3)
+                gpu.append(e0.elapsed_time(e1))
+        return statistics.median(wall), statistics.median(gpu)
+
+    series = {"recipe": [], "new": []}
+    with m.open_stream(seed) as st_new, m.open_stream(seed_v, return_nll=True) as st_old:
+        arms = (("recipe", st_old, seed_v, recipe_frame), ("new", st_new, seed, new_frame))
+        for p in range(passes):
+            for name, st, sd, fn in arms:
+                st.reset(sd)
+                series[name].append(run(st, fn))
+        st_new.reset(seed)
+        clk = bench.gpu_state_under_load(lambda i: new_frame(st_new, i % total), dev, helper)
+    # the timer split: eager sessions, the engine's events on
+    os.environ["LFI_NO_GRAPH"] = "1"
+    split = {}
+    for name, sd, fn, nll in (("recipe", seed_v, recipe_frame, True), ("new", seed, new_frame, False)):
+        with m.open_stream(sd, return_nll=nll) as st:
+            for n in range(warmup):
+                fn(st, n)
+            eng.enable_timing(True)
+            for n in range(warmup, total):
+                fn(st, n)
+            split[name] = eng.timing_summary()
+            eng.enable_timing(False)
+    del os.environ["LFI_NO_GRAPH"]
+    lines = ["# Best-of-N per frame: step_candidates + commit() against the save / load recipe (tools/stream_latency.py --candidates %d,%d)"
+             % (B, ncand), "",
+             "final_model.yaml as shipped (C = %d, S = %d, K = %d, H = %d, D = %d), engine precision %s; B = %d conversations, ncand = %d "
+             "candidates per frame (the recipe's session has %d rows); %d whole passes per arm, alternated, the recipe first; a pass is "
+             "the median of %d timed frames after %d untimed ones. wall = call to result on the host (a synchronise after the frame), "
+             "GPU = HIP events around the frame. Device %s." % (C, s.S, s.Ks, s.H, s.D, m.precision, B, ncand, V, passes, steps, warmup,
+                                                                 device_name), "",
+             "| pass | recipe: wall ms / frame | recipe: GPU ms / frame | new: wall ms / frame | new: GPU ms / frame |", "|---|---|---|---|---|"]
+    for p in range(passes):
+        (rw, rg), (nw, ng) = series["recipe"][p], series["new"][p]
+        lines.append("| %d | %.4f | %.4f | %.4f | %.4f |" % (p + 1, rw, rg, nw, ng))
+    for i, what in ((0, "wall"), (1, "GPU")):
+        new_med = statistics.median(v[i] for v in series["new"])
+        low = min(v[i] for v in series["recipe"])
+        lines += ["", "%s: the new calls' median over the passes %.4f ms, the recipe's lowest pass %.4f ms (%.2f x): %s."
+                  % (what, new_med, low, low / new_med, "below it" if new_med < low else "NOT below it")]
+    lines += ["", "## Timer split of an eager frame (LFI_NO_GRAPH=1, HIP events; mean ms per launch x launches per frame)", "",
+              "| tag | recipe | new |", "|---|---|---|"]
+    for t in sorted(set(split["recipe"]) | set(split["new"])):
+        if t.startswith("stream_"):
+            lines.append("| %s | " % t + " | ".join("%.4f x %.0f" % (split[k][t][1], split[k][t][0] / steps) if t in split[k] else "-"
+                                                    for k in ("recipe", "new")) + " |")
+    lines += ["", "`stream_static`: window encoders + static cond_transform columns (%d windows in the recipe, %d in the new calls); "
+              "`stream_chain`: front end + reverse chain (lfi_flow_sample_seq_nll over %d rows; lfi_flow_sample_cand_from: front end for %d "
+              "rows, chain over %d virtual rows). The save / load launches of the recipe and the commit launch carry no timer: they are "
+              "the rest of the frame's GPU time." % (V, B, V, B, V), "",
+              "GPU state under the new calls' load: %s" % (clk if clk else "not read (no rocm-smi helper)")]
     return "\n".join(lines) + "\n"
 
 
