@@ -522,6 +522,30 @@ int lfi_flow_sample_cand_from(const lfi_flow_dims* d, const lfi_flow_params* p, 
                             float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
                             float* nll, float* nll_work, int ncand, float* cand_frames, float* cand_nll, float* cand_h,
                             float* cand_c, float* cand_work, void* stream);
+/* N candidate ROLLOUTS of nframes >= 1 frames per batch row (SampleStream.rollout_candidates): lfi_flow_sample_seq_nll's arguments with
+ * d->B = V = B * ncand VIRTUAL rows, then ncand >= 1 (it must divide d->B; V <= 2^22). Virtual row v = b * ncand + j is candidate j
+ * of batch row b. From the second frame on the candidates of a row differ in their faces windows and their h / c, so faces
+ * (V x seq_len x C), noise (nframes x V x C), nll (nframes x V), h / cstate ([Ks][V][H]), p1work and nll_work are the candidates'
+ * own, sized for V rows and updated in place exactly as lfi_flow_sample_seq_nll updates them for V rows. What they share is the static
+ * conditioning: pre_static has the PARENTS' rows only, nframes * (V / ncand) of them, frame-major, and virtual row v of frame i reads
+ * row i * (V / ncand) + v / ncand. Where the fused front end runs (lfi_flow_sample_seq_nll's rule) it reads the parent's row in place -
+ * a compile-time parent mode of the same kernel, the row index of its one pre_static load divided by ncand - and pre_static is not
+ * written: a parent's Ks * D floats come out of L2 ncand times and are never copied V-fold. Every other front end overwrites the rows
+ * it reads, so there a small launch per frame first copies the frame's parent rows to V rows of a ONE-frame scratch inside `work`,
+ * which the front end then consumes in place (pre_static itself stays as it was). work: lfi_flow_sample_cand_seq_work_floats(d, ncand)
+ * floats, 16-byte aligned, where d is the PARENTS' dims (d->B = V / ncand): lfi_flow_sample_work_floats for V rows and that scratch;
+ * 0 for a NULL d, ncand < 1 or V beyond the limit. The reverse chain, the step-0 window-fragment hand-over and the NLL hand-over are
+ * lfi_flow_sample_seq_nll's for V rows, kernel for kernel: rows never mix in the fused kernel or in a cell, so on that path candidate
+ * (b, j) is bit for bit the row a B-row call generates from the same state, conditioning and draws; ncand = 1 runs the same launches
+ * on the same shapes on every path (the copy aside). LFI_CHUNK_ONLY=front, for tools/stream_latency.py alone: every frame's front
+ * end and no chain is launched, to be timed; the results are not meaningful. Allocation-free; every argument is checked before the
+ * first launch. */
+long lfi_flow_sample_cand_seq_work_floats(const lfi_flow_dims* d, int ncand);
+int lfi_flow_sample_cand_seq(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep,
+                            const float* wct, long E, int hist1, float* pre_static, const float* noise,
+                            float* faces, int seq_len, int start, int nframes, int first_frame,
+                            float* h, float* cstate, const lfi_p1enc* p1, float* p1work, float* work,
+                            float* nll, float* nll_work, int ncand, void* stream);
 /* A run of nframes >= 1 frames of a chunk in which every batch row takes its role FRAME BY FRAME (SampleStream.step_rows_many): it
  * replaces a host loop of nframes lfi_flow_step_rows_from calls - the same launches, from one call with one argument check, one kernel
  * pick and one preparation of the fused conditioning kernel's weight fragments. lfi_flow_step_rows_from's arguments, frame-major:
@@ -660,6 +684,28 @@ int lfi_stream_commit_cand(int B, int ncand, int C, int Ks, int H, const int* ch
                            const float* cand_nll, const float* cand_h, const float* cand_c, float* face_win, int hist,
                            float* h, float* cstate, float* out_frame, float* out_nll, int* out_choice,
                            unsigned* guard_bits, void* stream);
+/* The two launches around lfi_flow_sample_cand_seq (SampleStream.rollout_candidates / commit), V = B * ncand virtual rows, row
+ * v = b * ncand + j. Neither writes a conditioning window; the session's own state is written by the commit alone.
+ * cand_seq_in, after lfi_stream_chunk_gen_in has laid the windows out as sequences: the first `start` frames of batch row b's faces
+ * sequence (parent_seq, B x (start + n) x C) go to every candidate's own sequence (cand_seq, V x (start + n) x C), whose frames
+ * start .. start + n - 1 are the chain's to write; with first_frame > 0 the row's h / cstate ([Ks][B][H]) go to the candidates'
+ * ([Ks][V][H]; first_frame = 0: the chain ignores what they hold); the candidates' noise (n x V x C, frame-major, already * eps) is
+ * read once and folded into *guard_bits (NULL = no guard) - it is not copied. ncand = 1: a copy.
+ * commit_cand_seq: for session row r, j = choice[r] (B ints on the device, clamped into 0 .. ncand - 1 by the kernel) or - choice ==
+ * NULL - the candidate of least summed NLL: sum over f = 0 .. n - 1 in that order, in fp32, of cand_nll[f, r, j] (n x V); ties to the
+ * lowest index; a NaN sum counts as larger than any number; all NaN: 0. Of candidate (r, j): frames start .. start + n - 1 of its
+ * sequence go to out (B x n x C) and are folded into *guard_bits; the last hist frames of its sequence (1 <= hist <= start + n; they
+ * end at frame start + n, so a short rollout keeps old frames) become the row's faces window (face_win, B x hist x C); cand_h / cand_c
+ * of every flow step become h / cstate of the row (cstate NULL = GRU); its NLL words go to out_nll (n x B), j to out_choice[r], and
+ * frame_nb[r] += 2 n (NULL = no counter). The conditioning windows come back with lfi_stream_chunk_out over those windows alone.
+ * One launch each, allocation-free, no host wait; every argument is checked before the launch. */
+int lfi_stream_cand_seq_in(int B, int ncand, int n, int start, int C, int Ks, int H, const float* parent_seq, float* cand_seq,
+                           const float* h, const float* cstate, float* cand_h, float* cand_c, int first_frame,
+                           const float* noise, unsigned* guard_bits, void* stream);
+int lfi_stream_commit_cand_seq(int B, int ncand, int n, int start, int C, int Ks, int H, const int* choice,
+                               const float* cand_seq, const float* cand_nll, const float* cand_h, const float* cand_c,
+                               float* face_win, int hist, float* h, float* cstate, float* frame_nb, float* out, float* out_nll,
+                               int* out_choice, unsigned* guard_bits, void* stream);
 
 /* ---------------------------------------------------------------- optimiser (configure_optimizers, glow/lets_face_it_glow.py:61-72)
  * Flat-buffer Adam with global-norm gradient clipping (Trainer gradient_clip_val, hparams/final_model.yaml:126):

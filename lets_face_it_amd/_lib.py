@@ -180,6 +180,11 @@ def lib():
         "lfi_flow_sample_cand_from": (i, [P(FlowDims), P(FlowParams), vp, vp, l, i, vp, vp, vp, i, i, i, i, vp, vp, P(P1Enc), vp, vp,
                                           vp, vp, i, vp, vp, vp, vp, vp, vp]),
         "lfi_stream_commit_cand": (i, [i, i, i, i, i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp]),
+        "lfi_flow_sample_cand_seq_work_floats": (l, [P(FlowDims), i]),
+        "lfi_flow_sample_cand_seq": (i, [P(FlowDims), P(FlowParams), vp, vp, l, i, vp, vp, vp, i, i, i, i, vp, vp, P(P1Enc), vp, vp,
+                                         vp, vp, i, vp]),
+        "lfi_stream_cand_seq_in": (i, [i, i, i, i, i, i, i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp]),
+        "lfi_stream_commit_cand_seq": (i, [i, i, i, i, i, i, i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp]),
         "lfi_absmax_f32": (i, [i, P(vp), P(l), vp, vp]),
         "lfi_stream_advance": (i, [i, i, P(vp), P(vp), P(i), P(i), vp, vp, i, vp, vp, vp]),
         "lfi_stream_advance_rows": (i, [i, i, P(vp), P(vp), P(i), P(i), i, vp, vp, i, vp, vp, vp, vp, vp]),
@@ -234,6 +239,7 @@ EXPORTS = [
     "lfi_flow_score_seq_chunk_rows", "lfi_stream_chunk_in_rows", "lfi_stream_chunk_out_rows",
     "lfi_flow_step_rows_seq", "lfi_stream_chunk_roles_in",
     "lfi_flow_sample_cand_work_floats", "lfi_flow_sample_cand_from", "lfi_stream_commit_cand",
+    "lfi_flow_sample_cand_seq_work_floats", "lfi_flow_sample_cand_seq", "lfi_stream_cand_seq_in", "lfi_stream_commit_cand_seq",
     "lfi_flow_step_rows_work_floats", "lfi_flow_step_rows_from", "lfi_absmax_f32", "lfi_stream_advance", "lfi_stream_advance_rows", "lfi_stream_reset_rows", "lfi_stream_row_floats",
     "lfi_stream_save_rows", "lfi_stream_load_rows", "lfi_stream_create_partial", "lfi_stream_destroy", "lfi_grad_sumsq", "lfi_adam_clip_step", "lfi_adam_clip_step_ex",
     "lfi_sgd_clip_step", "lfi_rmsprop_clip_step", "lfi_set_step_params", "lfi_dropout_masks_dev", "lfi_adam_clip_step_dev", "lfi_selftest_mfma", "lfi_debug_set_stamps",

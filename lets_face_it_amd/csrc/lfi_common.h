@@ -51,7 +51,7 @@ extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond_pr
 extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond(const float* faces, long ld_faces, long off, int K1, int B, int Ks, int G,
                                                                               const float* pre, const float* b_ih, void* frags, float* gic,
                                                                               float slope, long faces_floats, unsigned* reset, int reset_words,
-                                                                              int have_xfrag, void* stream);
+                                                                              int have_xfrag, int ncand, void* stream);
 extern "C" __attribute__((visibility("hidden"))) void* lfi_internal_sample_cond_xfrag_ptr(void* frags, int Ks, int G, int K1);
 
 // ---- internal: the sampler's front end for M rows of prev_p1_face windows (lfi_flow_chain.hip), called by lfi_flow_chunk.hip too

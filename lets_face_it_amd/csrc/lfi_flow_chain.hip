@@ -990,12 +990,13 @@ extern "C" int lfi_internal_sample_front_rows(const lfi_flow_dims* d, const lfi_
 namespace {
 // frame t of the sequence in `faces`: gic of all flow steps from the frame's rows `cfr` of pre_static (B x Ks D, overwritten) and the
 // window faces[:, t - hist1 : t]. have_xfrag: the window's fp16 fragments are already in cfrags (the previous frame's reverse chain)
-int sample_front_frame(const SampleFront& s, int t, float* cfr, int have_xfrag, void* stream) {
+// ncand >= 2 (lfi_flow_sample_cand_seq, the fused kernel only): cfr holds B / ncand parent rows, row r reads row r / ncand of it
+int sample_front_frame(const SampleFront& s, int t, float* cfr, int have_xfrag, void* stream, int ncand = 0) {
   const int B = s.f->B, C = s.f->C, Ks = s.f->Ks, G = s.f->G, hist1 = s.hist1, seq_len = s.seq_len;
   if (s.fused) {
     // (its first workgroup also clears the chain's ticket / progress words for the launch that follows: no memset node per frame)
     return lfi_internal_sample_cond(s.faces, (long)seq_len * C, (long)(t - hist1) * C, s.K1, B, Ks, G, cfr, s.p->b_ih, s.cfrags, s.gic, 0.01f,
-                                    (long)B * seq_len * C, s.chain ? s.chain_state : nullptr, (int)s.chain_words, have_xfrag, stream);
+                                    (long)B * seq_len * C, s.chain ? s.chain_state : nullptr, (int)s.chain_words, have_xfrag, ncand, stream);
   }
   const float* win = s.faces + (long)(t - hist1) * C;
   long ldwin = (long)seq_len * C;
@@ -1076,19 +1077,46 @@ extern "C" long lfi_flow_sample_nll_work_floats(const lfi_flow_dims* d) {
   return 2L * d->B + 8;   // the two ping-pong hand-over arrays of the chain (the first is the per-step launches' accumulator)
 }
 
-// lfi_flow_sample_seq_from that also leaves the per-frame NLL (bits) of every frame it generates in nll (nframes x B); nll == NULL:
-// lfi_flow_sample_seq_from itself - the same launches of the same kernels.
-extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct,
-                                       long E, int hist1, float* pre_static, const float* noise, float* faces, int seq_len,
-                                       int start, int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1,
-                                       float* p1work, float* work, float* nll, float* nll_work, void* stream) {
+// A frame's rows of pre_static for the candidates of lfi_flow_sample_cand_seq, where the front end overwrites what it reads (every
+// path but the fused kernel): workgroup v copies parent row v / ncand (KD floats) to row v of a one-frame scratch. 16-byte words
+// where both sides allow it.
+__global__ __launch_bounds__(256) void cand_pre_bcast_kernel(const float* __restrict__ src, float* __restrict__ dst, int ncand, long KD,
+                                                            int vec) {
+  const long v = blockIdx.x;
+  const float* from = src + (v / ncand) * KD;
+  float* to = dst + v * KD;
+  if (vec) {
+    for (long j = threadIdx.x; j < KD / 4; j += 256) reinterpret_cast<float4*>(to)[j] = reinterpret_cast<const float4*>(from)[j];
+  } else {
+    for (long j = threadIdx.x; j < KD; j += 256) to[j] = from[j];
+  }
+}
+
+namespace {
+constexpr long kCandSeqMaxRows = 1L << 22;   // virtual rows of one lfi_flow_sample_cand_seq call (lfi_flow_sample_cand_from's limit)
+// where the one-frame scratch of lfi_flow_sample_cand_seq lies in its work area: behind the sampler's own carve, 16-byte aligned
+inline long cand_seq_scratch_offset(const lfi_flow_dims* dv) { return (lfi_flow_sample_work_floats(dv) + 3) & ~3L; }
+
+// The body of lfi_flow_sample_seq_nll (ncand = 0, names as they always were) and of lfi_flow_sample_cand_seq (ncand >= 1: the d->B
+// rows are ncand candidates of each of d->B / ncand parent rows; pre_static has the PARENTS' rows, nframes * (d->B / ncand), and
+// virtual row v of frame n reads row n * (d->B / ncand) + v / ncand). Everything else is per row in both.
+int sample_seq_run(const char* who, const char* who_from, const char* who_nll, const lfi_flow_dims* d, const lfi_flow_params* p,
+                   const float* prep, const float* wct, long E, int hist1, float* pre_static, const float* noise, float* faces,
+                   int seq_len, int start, int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1, float* p1work,
+                   float* work, float* nll, float* nll_work, void* stream, int ncand) {
   FlowK f = {};
-  int rc = fill_flow(d, p, prep, &f, "lfi_flow_sample_seq");
+  int rc = fill_flow(d, p, prep, &f, who);
   if (rc) return rc;
-  if ((rc = frame_args_check("lfi_flow_sample_seq", "lfi_flow_sample_seq_from", d, prep && wct && pre_static && noise && faces && h && work,
+  if ((rc = frame_args_check(who, who_from, d, prep && wct && pre_static && noise && faces && h && work,
                              E, hist1, start, nframes, seq_len, cstate, first_frame))) return rc;
-  LFI_REQUIRE(!nll || nll_work, "lfi_flow_sample_seq_nll: nll needs nll_work (lfi_flow_sample_nll_work_floats)");
+  LFI_REQUIRE(!nll || nll_work, "%s: nll needs nll_work (lfi_flow_sample_nll_work_floats)", who_nll);
+  if (ncand) {
+    LFI_REQUIRE(ncand >= 1 && d->B % ncand == 0 && (long)d->B <= kCandSeqMaxRows,
+                "%s: %d candidates per row do not divide the %d virtual rows (at most %ld)", who, ncand, d->B, kCandSeqMaxRows);
+    LFI_REQUIRE((reinterpret_cast<uintptr_t>(work) & 15) == 0, "%s: work is not 16-byte aligned", who);
+  }
   const int B = f.B, C = f.C, D = f.D, Ks = f.Ks;
+  const int Bp = ncand ? B / ncand : B;          // rows of pre_static per frame
   hipStream_t st = (hipStream_t)stream;
   const bool fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
   const Carve cv = carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout);
@@ -1101,8 +1129,17 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
   // the per-frame conditioning (sample_front_*): the carve of `work`, the fused kernel's weight fragments once per call
   SampleFront sf = {};
   if ((rc = sample_front_setup(&sf, d, p, &f, wct, E, hist1, pre_static, faces, seq_len, p1, p1work, work, chain, nframes, stream,
-                               "lfi_flow_sample_seq"))) return rc;
+                               who))) return rc;
   const int K1 = sf.K1;
+  // candidates: the fused kernel reads the parents' rows in place (it never writes them); every other front end overwrites its rows
+  // of pre_static with c, so each frame's parent rows are first copied to B rows of a one-frame scratch behind the sampler's carve
+  // (ncand = 1: a plain copy, then the same launches on the same shapes)
+  float* scratch = (ncand && !sf.fused) ? work + cand_seq_scratch_offset(d) : nullptr;
+  const long KD = (long)Ks * D;
+  // (diagnostics, tools/stream_latency.py, the candidates' entry point only: LFI_CHUNK_ONLY=front launches every frame's front end and
+  // no chain, so that events around the call time the front end alone. Results are not meaningful.)
+  const char* only = ncand ? getenv("LFI_CHUNK_ONLY") : nullptr;
+  const bool run_chain = !(only && only[0] == 'f');
   // LFI_SAMPLE_XF_CHAIN=0 keeps the window-fragment kernel in front of every frame's conditioning
   const bool xf_chain = sf.fused && chain && lfi_env_on("LFI_SAMPLE_XF_CHAIN");
   // the reverse cells' weights as the fp16 fragment images lfi_flow_prep left (no split in every workgroup of every frame; x3 is true
@@ -1110,11 +1147,18 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
   const bool xw = x3 && chain && flow_sample_wfrag16_enabled();
   // one launch for the whole chain of a frame; with nll the cells also pass the rows' running log-density down the chain
   const FlowRevChainKernel chain_kernel = flow_rev_chain_pick(f.lstm, x3, xw, nll != nullptr);
-  if (chain && (rc = set_flow_lds(chain_kernel, lds, nll ? "lfi_flow_sample_seq_nll" : "lfi_flow_sample_seq"))) return rc;
+  if (chain && (rc = set_flow_lds(chain_kernel, lds, nll ? who_nll : who))) return rc;
   for (int n = 0; n < nframes; ++n) {
     const int t = start + n;
+    float* cfr = pre_static + (long)n * Bp * KD;
+    if (scratch) {
+      const int vec = KD % 4 == 0 && (reinterpret_cast<uintptr_t>(cfr) & 15) == 0 ? 1 : 0;
+      hipLaunchKernelGGL(cand_pre_bcast_kernel, dim3(B), dim3(256), 0, st, cfr, scratch, ncand, KD, vec);
+      cfr = scratch;
+    }
     // (from the run's second frame on the window's fragments are already there: the previous frame's chain left them)
-    if ((rc = sample_front_frame(sf, t, pre_static + (long)n * B * Ks * D, (xf_chain && n > 0) ? 1 : 0, stream))) return rc;
+    if ((rc = sample_front_frame(sf, t, cfr, (xf_chain && n > 0) ? 1 : 0, stream, scratch ? 0 : ncand))) return rc;
+    if (!run_chain) continue;
     // reverse flow: z -> x through steps Ks-1 .. 0
     if (chain) {   // one launch for the whole chain of this frame
       RevChain rcn = {};
@@ -1125,7 +1169,7 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
         rcn.xf = reinterpret_cast<_Float16*>(lfi_internal_sample_cond_xfrag_ptr(sf.cfrags, Ks, f.G, K1));
         rcn.faces = faces; rcn.xf_off = (long)(t + 1 - hist1) * C; rcn.K1 = K1; rcn.NM1 = (K1 + 31) / 32;
       }
-      if ((rc = sample_front_clear_chain(sf, st, "lfi_flow_sample_seq"))) return rc;
+      if ((rc = sample_front_clear_chain(sf, st, who))) return rc;
       if (nll) { rcn.qa = nll_work; rcn.qb = nll_work + B; rcn.nll = nll + (long)n * B; }
       hipLaunchKernelGGL(chain_kernel, dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
       continue;
@@ -1136,8 +1180,39 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
       hipLaunchKernelGGL(sample_nll_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, noise + (long)n * B * C, nll_work,
                          f.ldconst, B, C, nll + (long)n * B);
   }
-  LFI_LAUNCH_CHECK("lfi_flow_sample_seq");
+  LFI_LAUNCH_CHECK(who);
   return LFI_OK;
+}
+}  // namespace
+
+// lfi_flow_sample_seq_from that also leaves the per-frame NLL (bits) of every frame it generates in nll (nframes x B); nll == NULL:
+// lfi_flow_sample_seq_from itself - the same launches of the same kernels.
+extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct,
+                                       long E, int hist1, float* pre_static, const float* noise, float* faces, int seq_len,
+                                       int start, int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1,
+                                       float* p1work, float* work, float* nll, float* nll_work, void* stream) {
+  return sample_seq_run("lfi_flow_sample_seq", "lfi_flow_sample_seq_from", "lfi_flow_sample_seq_nll", d, p, prep, wct, E, hist1, pre_static,
+                        noise, faces, seq_len, start, nframes, first_frame, h, cstate, p1, p1work, work, nll, nll_work, stream, 0);
+}
+
+// ---- N candidate ROLLOUTS of nframes frames per session row (SampleStream.rollout_candidates): the sampler over V = B * ncand virtual
+// rows whose static conditioning is their parent row's, read in place
+extern "C" long lfi_flow_sample_cand_seq_work_floats(const lfi_flow_dims* d, int ncand) {
+  if (!d || ncand < 1 || d->B < 1 || (long)d->B * ncand > kCandSeqMaxRows) return 0;
+  lfi_flow_dims dv = *d;
+  dv.B = d->B * ncand;
+  return cand_seq_scratch_offset(&dv) + (long)dv.B * dv.Ks * dv.D + 8;
+}
+
+extern "C" int lfi_flow_sample_cand_seq(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* wct,
+                                        long E, int hist1, float* pre_static, const float* noise, float* faces, int seq_len,
+                                        int start, int nframes, int first_frame, float* h, float* cstate, const lfi_p1enc* p1,
+                                        float* p1work, float* work, float* nll, float* nll_work, int ncand, void* stream) {
+  const char* who = "lfi_flow_sample_cand_seq";
+  LFI_REQUIRE(d && p, "%s: null pointer (dims / params)", who);
+  LFI_REQUIRE(ncand >= 1, "%s: %d candidates per row (at least 1)", who, ncand);
+  return sample_seq_run(who, who, who, d, p, prep, wct, E, hist1, pre_static, noise, faces, seq_len, start, nframes, first_frame, h, cstate,
+                        p1, p1work, work, nll, nll_work, stream, ncand);
 }
 
 // ---- N candidates of one frame per session row (SampleStream.step_candidates)

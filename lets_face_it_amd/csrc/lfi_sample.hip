@@ -119,6 +119,7 @@ struct ScArgs {
   float* gic;            // Ks x B x G
   int B, Ks, G, NM1;
   float slope;
+  int ncand;             // PAR instantiations: row r reads row r / ncand of pre (the rows are candidates of B / ncand parent rows)
 };
 
 // grid (Ks, row tiles of 16 RT); 512 threads = 8 waves: wave w owns c columns [64 w, 64 w + 64) in phase 1 and gic columns
@@ -127,7 +128,10 @@ struct ScArgs {
 // site). Same arithmetic per output element either way: bit-identical (tested).
 // XF = false (round 5): the window's fp16 pieces are made in registers from the fp32 frames - 16 workgroups repeat the split of
 // a row tile, 256 values per lane, instead of a launch of its own per generated frame (12.6 us + its boundary)
-template <int NGT, bool XF, int RT>
+// PAR (lfi_flow_sample_cand_seq): the B rows are ncand candidates of each of B / ncand parent rows, which share their parent's row of
+// pre_static - the one load of pre indexes row / ncand, and a parent's 32 KB are read ncand times out of L2 instead of being copied
+// B-fold. Everything else - the window, gic, the arithmetic per output element and its order - is per row, as without PAR.
+template <int NGT, bool XF, int RT, bool PAR = false>
 __global__ __launch_bounds__(SC_NT) __attribute__((amdgpu_waves_per_eu(RT == 2 ? 4 : 2, RT == 2 ? 4 : 2))) void sc_cond_kernel(ScArgs a) {
   constexpr int SC_ROWS = 16 * RT;
   constexpr int SC_PLANE = SC_ROWS * SC_PITCH;
@@ -301,7 +305,8 @@ __global__ __launch_bounds__(SC_NT) __attribute__((amdgpu_waves_per_eu(RT == 2 ?
   f32x4 ps[RT][4];
 #pragma unroll
   for (int ri = 0; ri < RT; ++ri) {
-    const long row = min((long)rt * SC_ROWS + 16 * ri + l15, (long)a.B - 1);   // (rows past B: values never stored)
+    long row = min((long)rt * SC_ROWS + 16 * ri + l15, (long)a.B - 1);   // (rows past B: values never stored)
+    if (PAR) row = (long)((unsigned)row / (unsigned)a.ncand);                // (B < 2^31: a 32-bit division)
 #pragma unroll
     for (int ci = 0; ci < 4; ++ci)
       ps[ri][ci] = *reinterpret_cast<const f32x4*>(a.pre + row * KD + (long)k * SC_D + 64 * wave + 16 * ci + 4 * g4);
@@ -425,11 +430,12 @@ extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond_pr
   return LFI_OK;
 }
 // faces_floats: floats from `faces` to the end of its buffer (the window loads are bounds-checked against it); reset / reset_words: the
-// reverse chain's state words to clear for the launch that follows (or null: the caller memsets them)
+// reverse chain's state words to clear for the launch that follows (or null: the caller memsets them); ncand >= 2: `pre` holds
+// B / ncand parent rows and row r reads row r / ncand of it (the PAR instantiations), ncand <= 1: B rows of its own
 extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond(const float* faces, long ld_faces, long off, int K1, int B, int Ks, int G,
                                                                               const float* pre, const float* b_ih, void* frags, float* gic,
                                                                               float slope, long faces_floats, unsigned* reset, int reset_words,
-                                                                              int have_xfrag, void* stream) {
+                                                                              int have_xfrag, int ncand, void* stream) {
   const int NM1 = (K1 + 31) / 32, NGT = G / 128;
   const int ntile = (B + 63) / 64 * 4;
   _Float16* f1 = reinterpret_cast<_Float16*>(frags);
@@ -451,6 +457,8 @@ extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond(co
   a.faces = faces; a.ld_faces = ld_faces; a.off = off; a.faces_bytes = faces_floats * 4; a.K1 = K1;
   a.reset = reset; a.reset_words = reset_words;
   a.pre = pre; a.b_ih = b_ih; a.gic = gic; a.B = B; a.Ks = Ks; a.G = G; a.NM1 = NM1; a.slope = slope;
+  const bool par = ncand >= 2;
+  a.ncand = par ? ncand : 1;
   // samples per workgroup: 64 (one workgroup per CU). LFI_SAMPLE_COND_ROWS=32: the two-per-CU tile VERDICT r5 asked for (67 KB of LDS,
   // 126 VGPRs, no spills) - built, bit-identical, and SLOWER: 44.3 against 40.6 ms of per-frame graphs per 1024 x 300 call, 48.96 against
   // 45.13 ms per call, same box, alternating (profiles/round6_sampler_ab.md): every workgroup streams its flow step's 1.3 MB of weight
@@ -459,7 +467,7 @@ extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond(co
   // (the in-register window split, LFI_SAMPLE_XFRAG=0, and the LSTM cell's four gate blocks - 82 spilled VGPRs at the 128-register
   // cap - keep the 64-sample tile)
   const char* re = getenv("LFI_SAMPLE_COND_ROWS");
-  const int RT = ((re && re[0] == '3') && !inreg && NGT == 3) ? 2 : 4;
+  const int RT = ((re && re[0] == '3') && !inreg && NGT == 3 && !par) ? 2 : 4;   // (the parent mode has the 64-sample tile only)
   const size_t lds = (size_t)2 * 16 * RT * SC_PITCH;
   static bool attr = false;
   if (!attr) {
@@ -469,6 +477,11 @@ extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond(co
   ok = ok && hipFuncSetAttribute((const void*)sc_cond_kernel<N, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l4) == hipSuccess &&  \
        hipFuncSetAttribute((const void*)sc_cond_kernel<N, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l4) == hipSuccess
     SC_ATTR(3); SC_ATTR(4);
+#define SC_ATTR_PAR(N)                                                                                                                               \
+  ok = ok && hipFuncSetAttribute((const void*)sc_cond_kernel<N, true, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l4) == hipSuccess &&  \
+       hipFuncSetAttribute((const void*)sc_cond_kernel<N, false, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l4) == hipSuccess
+    SC_ATTR_PAR(3); SC_ATTR_PAR(4);
+#undef SC_ATTR_PAR
     ok = ok && hipFuncSetAttribute((const void*)sc_cond_kernel<3, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2) == hipSuccess;
 #undef SC_ATTR
     if (!ok) {
@@ -483,10 +496,18 @@ extern "C" __attribute__((visibility("hidden"))) int lfi_internal_sample_cond(co
     if (inreg) hipLaunchKernelGGL((sc_cond_kernel<N, false, 4>), grid, dim3(SC_NT), lds, (hipStream_t)stream, a);   \
     else hipLaunchKernelGGL((sc_cond_kernel<N, true, 4>), grid, dim3(SC_NT), lds, (hipStream_t)stream, a);          \
   } while (0)
+#define SC_LAUNCH_PAR(N)                                                                                                  \
+  do {                                                                                                                    \
+    if (inreg) hipLaunchKernelGGL((sc_cond_kernel<N, false, 4, true>), grid, dim3(SC_NT), lds, (hipStream_t)stream, a);   \
+    else hipLaunchKernelGGL((sc_cond_kernel<N, true, 4, true>), grid, dim3(SC_NT), lds, (hipStream_t)stream, a);          \
+  } while (0)
   if (RT == 2) hipLaunchKernelGGL((sc_cond_kernel<3, true, 2>), grid, dim3(SC_NT), lds, (hipStream_t)stream, a);
+  else if (par && NGT == 3) SC_LAUNCH_PAR(3);
+  else if (par) SC_LAUNCH_PAR(4);
   else if (NGT == 3) SC_LAUNCH(3);
   else SC_LAUNCH(4);
 #undef SC_LAUNCH
+#undef SC_LAUNCH_PAR
   LFI_LAUNCH_CHECK("sampler conditioning");
   return LFI_OK;
 }

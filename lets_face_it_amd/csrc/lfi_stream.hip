@@ -8,7 +8,9 @@
 // steps, leaving the other rows alone: conversations join and leave one batched session independently. Two more copy listed rows'
 // live state out of a session into plain fp32 records and back into any session of the same model (SampleStream.save_rows /
 // load_rows): conversations move between sessions, pause on the host, branch and roll back. One more installs the chosen one of every
-// row's candidates for a frame (SampleStream.commit, after step_candidates).
+// row's candidates for a frame (SampleStream.commit, after step_candidates). Two more stand around N candidate rollouts over a chunk of
+// frames (SampleStream.rollout_candidates / commit): each row's faces sequence and state broadcast to its candidates, and the chosen
+// candidate's frames, window and state installed.
 #include "lfi_common.h"
 
 #include <vector>
@@ -508,6 +510,123 @@ __global__ __launch_bounds__(256) void stream_commit_cand_kernel(int B, int ncan
   stream_guard_fold_block(m, guard);
 }
 
+// ---- N candidate rollouts of n frames per row (SampleStream.rollout_candidates / commit / discard). V = B * ncand virtual rows, row
+// v = b * ncand + j: candidate j of session row b. Nothing the session owns is written before the commit.
+//
+// In: workgroup (v, part). Part 0: the first `start` frames of the parent's faces sequence (parent_seq, B x (start + n) x C, as
+// stream_chunk_in_kernel left it) go to the candidate's own sequence (cand_seq, V x (start + n) x C), whose frames start .. are the
+// chain's to write. Part 1 (has_prev): the parent's h / c of every flow step go to the candidate's state ([Ks][V][H]). Part 2: the
+// candidate's n noise rows (n x V x C, frame-major, read where the caller keeps them) are folded into the guard word.
+__global__ __launch_bounds__(256) void stream_cand_seq_in_kernel(int B, int ncand, int n, int start, int C, int Ks, int H,
+                                                                const float* __restrict__ parent_seq, float* __restrict__ cand_seq,
+                                                                const float* __restrict__ h, const float* __restrict__ cstate,
+                                                                float* __restrict__ cand_h, float* __restrict__ cand_c, int has_prev,
+                                                                const float* __restrict__ noise, unsigned* __restrict__ guard) {
+  const long v = blockIdx.x, V = (long)B * ncand, b = v / ncand;
+  const int part = blockIdx.y;
+  unsigned m = 0u;
+  if (part == 0) {
+    const long T = (long)start + n, live = (long)start * C;
+    const float* src = parent_seq + b * T * C;
+    float* dst = cand_seq + v * T * C;
+    for (long j = threadIdx.x; j < live; j += 256) dst[j] = src[j];
+  } else if (part == 1) {
+    if (has_prev) {
+      for (int e = threadIdx.x; e < Ks * H; e += 256) {
+        const int k = e / H, c = e - k * H;
+        const long src = ((long)k * B + b) * H + c, dst = ((long)k * V + v) * H + c;
+        cand_h[dst] = h[src];
+        if (cstate) cand_c[dst] = cstate[src];
+      }
+    }
+  } else {
+    for (int f = 0; f < n; ++f) {
+      const float* row = noise + ((long)f * V + v) * C;
+      for (int j = threadIdx.x; j < C; j += 256) {
+        const unsigned a = stream_abs_bits(row[j]);
+        m = a > m ? a : m;
+      }
+    }
+  }
+  stream_guard_fold_block(m, guard);
+}
+
+// Of two (summed NLL, index) pairs the one a commit prefers: the smaller sum; a NaN sum loses to any number; equal sums and two NaNs
+// go to the lower index.
+__device__ __forceinline__ bool stream_cand_better(float a, int ia, float b, int ib) {
+  if (a < b || (b != b && a == a)) return true;
+  if (b < a || (a != a && b == b)) return false;
+  return ia < ib;
+}
+
+// Commit: workgroup r, session row r. j = the clamped choice[r], or (choice == NULL) the candidate of least summed NLL - every sum
+// runs over the frames in ascending order in fp32 (one thread per candidate, no reassociation), ties to the lowest index, a NaN sum
+// never wins unless all are NaN, then 0. Then candidate (r, j)'s n frames go to out (B x n x C) and into the guard word, the last
+// hist frames of its sequence (they end at frame start + n; hist <= start + n) into the row's faces window, its h / c of every flow
+// step into the session's, its n NLL words to out_nll (n x B), j to out_choice, and the row's frame counter moves by 2 n. Every word
+// has one writer.
+__global__ __launch_bounds__(256) void stream_commit_cand_seq_kernel(int B, int ncand, int n, int start, int C, int Ks, int H,
+                                                                    const int* __restrict__ choice, const float* __restrict__ cand_seq,
+                                                                    const float* __restrict__ cand_nll, const float* __restrict__ cand_h,
+                                                                    const float* __restrict__ cand_c, float* __restrict__ face_win,
+                                                                    int hist, float* __restrict__ h, float* __restrict__ cstate,
+                                                                    float* __restrict__ frame_nb, float* __restrict__ out,
+                                                                    float* __restrict__ out_nll, int* __restrict__ out_choice,
+                                                                    unsigned* __restrict__ guard) {
+  __shared__ float s_sum[256];
+  __shared__ int s_idx[256];
+  __shared__ int s_j;
+  const long r = blockIdx.x, V = (long)B * ncand;
+  const int tid = threadIdx.x;
+  if (choice) {
+    if (tid == 0) s_j = min(max(choice[r], 0), ncand - 1);
+  } else {
+    float best = 0.0f;
+    int bi = -1;                                   // (no candidate of this thread's yet)
+    for (int i = tid; i < ncand; i += 256) {
+      float sum = 0.0f;
+      for (int f = 0; f < n; ++f) sum = __fadd_rn(sum, cand_nll[(long)f * V + r * ncand + i]);
+      if (bi < 0 || stream_cand_better(sum, i, best, bi)) { best = sum; bi = i; }
+    }
+    s_sum[tid] = best; s_idx[tid] = bi;
+    __syncthreads();
+    if (tid == 0) {
+      for (int t = 1; t < 256 && t < ncand; ++t)
+        if (stream_cand_better(s_sum[t], s_idx[t], best, bi)) { best = s_sum[t]; bi = s_idx[t]; }
+      s_j = bi;
+    }
+  }
+  __syncthreads();
+  const int j = s_j;
+  const long v = r * ncand + j, T = (long)start + n;
+  const float* seq = cand_seq + v * T * C;
+  if (tid == 0) {
+    out_choice[r] = j;
+    if (frame_nb) frame_nb[r] += 2.0f * (float)n;
+  }
+  for (int f = tid; f < n; f += 256) out_nll[(long)f * B + r] = cand_nll[(long)f * V + v];
+  unsigned m = 0u;
+  const float* gen = seq + (long)start * C;
+  float* dst = out + r * (long)n * C;
+  for (long e = tid; e < (long)n * C; e += 256) {
+    const float x = gen[e];
+    dst[e] = x;
+    const unsigned a = stream_abs_bits(x);
+    m = a > m ? a : m;
+  }
+  const long tot = (long)hist * C;
+  const float* tail = seq + T * C - tot;
+  float* win = face_win + r * tot;
+  for (long e = tid; e < tot; e += 256) win[e] = tail[e];
+  for (int e = tid; e < Ks * H; e += 256) {
+    const int k = e / H, c = e - k * H;
+    const long src = ((long)k * V + v) * H + c, to = ((long)k * B + r) * H + c;
+    h[to] = cand_h[src];
+    if (cstate) cstate[to] = cand_c[src];
+  }
+  stream_guard_fold_block(m, guard);
+}
+
 // The checks and the launch of a chunk entry point: windows in (kChunkIn) or out.
 int stream_chunk_launch(const char* what, unsigned kind, int B, int n, int start, int count, float* const* win, float* const* seq,
                         const int* hist, const int* dim, const int* lead, const StreamChunkOpts& o, float* frame_nb, unsigned* guard,
@@ -730,5 +849,38 @@ extern "C" int lfi_stream_commit_cand(int B, int ncand, int C, int Ks, int H, co
   hipLaunchKernelGGL(stream_commit_cand_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, B, ncand, C, Ks, H, choice, cand_frames, cand_nll,
                      cand_h, cand_c, face_win, hist, h, cstate, out_frame, out_nll, out_choice, guard_bits);
   LFI_LAUNCH_CHECK("lfi_stream_commit_cand");
+  return LFI_OK;
+}
+
+extern "C" int lfi_stream_cand_seq_in(int B, int ncand, int n, int start, int C, int Ks, int H, const float* parent_seq, float* cand_seq,
+                                      const float* h, const float* cstate, float* cand_h, float* cand_c, int first_frame,
+                                      const float* noise, unsigned* guard_bits, void* stream) {
+  LFI_REQUIRE(B > 0 && B <= 65535, "lfi_stream_cand_seq_in: batch %d (1 .. 65535)", B);
+  LFI_REQUIRE(ncand >= 1 && (long)B * ncand <= (1L << 22), "lfi_stream_cand_seq_in: %d candidates per row at batch %d", ncand, B);
+  LFI_REQUIRE(n >= 1 && start >= 0 && (long)start + n < (1L << 30), "lfi_stream_cand_seq_in: %d frames from frame %d", n, start);
+  LFI_REQUIRE(C > 0 && Ks > 0 && H > 0 && first_frame >= 0, "lfi_stream_cand_seq_in: C = %d, Ks = %d, H = %d, first_frame = %d", C, Ks, H,
+              first_frame);
+  LFI_REQUIRE(parent_seq && cand_seq && h && cand_h && noise, "lfi_stream_cand_seq_in: null pointer");
+  LFI_REQUIRE(!cstate || cand_c, "lfi_stream_cand_seq_in: cstate without cand_c");
+  hipLaunchKernelGGL(stream_cand_seq_in_kernel, dim3(B * ncand, 3), dim3(256), 0, (hipStream_t)stream, B, ncand, n, start, C, Ks, H, parent_seq,
+                     cand_seq, h, cstate, cand_h, cand_c, first_frame > 0 ? 1 : 0, noise, guard_bits);
+  LFI_LAUNCH_CHECK("lfi_stream_cand_seq_in");
+  return LFI_OK;
+}
+
+extern "C" int lfi_stream_commit_cand_seq(int B, int ncand, int n, int start, int C, int Ks, int H, const int* choice,
+                                          const float* cand_seq, const float* cand_nll, const float* cand_h, const float* cand_c,
+                                          float* face_win, int hist, float* h, float* cstate, float* frame_nb, float* out, float* out_nll,
+                                          int* out_choice, unsigned* guard_bits, void* stream) {
+  LFI_REQUIRE(B > 0 && B <= 65535, "lfi_stream_commit_cand_seq: batch %d (1 .. 65535)", B);
+  LFI_REQUIRE(ncand >= 1 && (long)B * ncand <= (1L << 22), "lfi_stream_commit_cand_seq: %d candidates per row at batch %d", ncand, B);
+  LFI_REQUIRE(n >= 1 && start >= 0 && (long)start + n < (1L << 30), "lfi_stream_commit_cand_seq: %d frames from frame %d", n, start);
+  LFI_REQUIRE(C > 0 && Ks > 0 && H > 0 && hist >= 1 && hist <= start + n,
+              "lfi_stream_commit_cand_seq: C = %d, Ks = %d, H = %d, hist = %d (1 .. start + n = %d)", C, Ks, H, hist, start + n);
+  LFI_REQUIRE(cand_seq && cand_nll && cand_h && face_win && h && out && out_nll && out_choice, "lfi_stream_commit_cand_seq: null pointer");
+  LFI_REQUIRE(!cstate || cand_c, "lfi_stream_commit_cand_seq: cstate without cand_c");
+  hipLaunchKernelGGL(stream_commit_cand_seq_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, B, ncand, n, start, C, Ks, H, choice, cand_seq,
+                     cand_nll, cand_h, cand_c, face_win, hist, h, cstate, frame_nb, out, out_nll, out_choice, guard_bits);
+  LFI_LAUNCH_CHECK("lfi_stream_commit_cand_seq");
   return LFI_OK;
 }

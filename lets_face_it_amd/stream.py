@@ -26,6 +26,9 @@ _ABSENT = object()       # (an argument a call does not take, where None is a va
 _MAX_CANDIDATES = 256    # candidates per row of one step_candidates() call
 _PENDING = ("SampleStream: %d candidates per row are pending (step_candidates): commit() one of them, or reset(), before any other "
             "call of the session")
+_PENDING_ROLLOUTS = ("SampleStream: %d candidate rollouts of %d frames per row are pending (rollout_candidates): commit() one of them, "
+                     "discard() them, or reset(), before any other call of the session")
+_MAX_VIRTUAL_ROWS = 1 << 22   # B * ncand of one rollout_candidates() call: the limit of lfi_flow_sample_cand_seq_work_floats
 
 
 def _stream():
@@ -163,7 +166,9 @@ class SampleStream:
     step runs), so training, inference() and other sessions can run between steps. Weights are frozen: a parameter change after the
     open (GlowEngine.param_version) makes step() raise."""
 
-    _pending = None          # ncand of the candidates step_candidates() left and commit() has not installed yet
+    # what commit() has not installed yet: None, ncand (an int) of the one-frame candidates step_candidates() left, or the rollouts
+    # rollout_candidates() left - a namespace of their kind, ncand, n and buffers
+    _pending = None
 
     def __init__(self, eng, seed, noise_fn, masks_fn=None, bound=None, return_nll=False):
         check_return_nll(return_nll)
@@ -274,7 +279,13 @@ class SampleStream:
         if self.eng.param_version != self.param_version or (self._bound is not None and not self._bound()):
             raise RuntimeError(_PARAMS_CHANGED)
         if self._pending is not None and not pending_ok:
-            raise RuntimeError(_PENDING % self._pending)
+            raise RuntimeError(self._pending_message())
+
+    def _pending_message(self):
+        pend = self._pending
+        if getattr(pend, "kind", None) == "rollouts":
+            return _PENDING_ROLLOUTS % (pend.ncand, pend.n)
+        return _PENDING % pend
 
     # ---- session-owned engine state, on a stream that is not the legacy default one (the session's private stream for a caller on it)
     @contextlib.contextmanager
@@ -294,7 +305,8 @@ class SampleStream:
 
     # ---- public surface
     def reset(self, seed):
-        """Start a new sequence from `seed` (same batch size); the captured graph is kept. Pending candidates are dropped."""
+        """Start a new sequence from `seed` (same batch size); the captured graph is kept. Pending candidates and pending rollouts
+        are dropped."""
         self._check_usable(pending_ok=True)
         self._check_seed(seed)
         with self._owned():
@@ -599,12 +611,23 @@ class SampleStream:
         integer tensor of B ints in that range, copied in asynchronously. -> (frame (B, C), nll (B,), choice (B,) int32): the
         installed candidates. One launch (lfi_stream_commit_cand), no host wait: the frame enters the newest slot of the faces window,
         the candidate's h / c become the row's, `steps` += 1 - the session is exactly where step(frame, noise[r, choice[r]]) per row
-        would have left it, and no longer pending."""
+        would have left it, and no longer pending.
+
+        With ROLLOUTS pending (rollout_candidates): the same three forms of choice; None picks, per row, the rollout of least SUMMED
+        NLL on the device - the sum runs over the frames in ascending order in fp32, ties to the lowest index, a NaN sum never wins
+        unless all are NaN, then 0. -> (out (B, n, C), nll (n, B), choice (B,) int32). The session is exactly where
+        step_many(frames, noise[:, r, choice[r]]) per row would have left it: the conditioning windows advance by the n frames, the
+        faces window holds the chosen sequence's last hist1 + 1 frames (old frames among them when n is small), h / c are the
+        chosen candidate's after its last frame, the frame counter += 2 n, `steps` += n, and the committed frames are folded into
+        the range guard. Two launches (lfi_stream_chunk_out for the conditioning windows, lfi_stream_commit_cand_seq), no host
+        wait."""
         s, eng, B = self.eng.spec, self.eng, self.B
         self._check_usable(pending_ok=True)
         ncand = self._pending
         if ncand is None:
             raise RuntimeError("SampleStream: commit() without pending candidates (step_candidates comes first)")
+        if getattr(ncand, "kind", None) == "rollouts":
+            return self._commit_rollouts(ncand, choice)
         dev, host = self._check_choice(choice, ncand)
         with self._owned():
             cand = self._cand[ncand]
@@ -630,6 +653,176 @@ class SampleStream:
         """step_candidates(frame, ncand, noise) followed by commit(): every row's candidate of least NLL becomes its frame t. ->
         commit()'s (frame, nll, choice)."""
         self.step_candidates(frame, ncand, noise)
+        return self.commit()
+
+    def _check_rollout_noise(self, noise, n, ncand):
+        """The prior draws of rollout_candidates(), (n, B, ncand, C) frame-major with n >= 1 (None: whatever it has) -> n. The wording
+        of _check_noise_many."""
+        B, C_ = self.B, self.eng.spec.C
+        ok = (torch.is_tensor(noise) and noise.is_cuda and noise.device == self.device and noise.dtype == torch.float32
+              and noise.is_contiguous() and noise.dim() == 4 and noise.shape[0] >= 1 and tuple(noise.shape[1:]) == (B, ncand, C_))
+        if not ok or (n is not None and noise.shape[0] != n):
+            raise ValueError("noise: expected contiguous float32 GPU tensor (%s, B=%d, ncand=%d, %d) on %s, frame-major, got %s %s on %s"
+                             % ("n>=1" if n is None else "n=%d" % n, B, ncand, C_, self.device, tuple(getattr(noise, "shape", ())),
+                                getattr(noise, "dtype", type(noise)), getattr(noise, "device", None)))
+        return int(noise.shape[0])
+
+    def _rollout_cap(self, ncand):
+        """Frames one rollout_candidates() call takes for ncand candidates per row - a rollout is ONE round, its candidates live in
+        the chunk workspaces until commit() / discard(). _chunk_cap()'s formula with the B * ncand virtual rows in place of B for
+        everything that is per candidate (gic, the tiles, the hand-over words) and B for what the candidates share (the static
+        pre-activations, the features); never more than _chunk_cap(); LFI_OBSERVE_CHUNK_FRAMES caps it as it caps a chunk round."""
+        cap = self._chunk_cap()
+        if os.environ.get("LFI_OBSERVE_CHUNK_FRAMES"):
+            return cap
+        s = self.eng.spec
+        G = (4 if s.rnn_type == "lstm" else 3) * s.H
+        per_frame = self.B * (s.Ks * s.D + s.ldf) + self.B * ncand * s.Ks * (G + s.C + 1)
+        return min(cap, max(8, min(256, (64 << 20) // per_frame)))
+
+    @translate_oom
+    def rollout_candidates(self, frames, ncand, noise=None):
+        """ncand candidate ROLLOUTS of n frames for every row (best-of-N over a short gesture, under conditioning known or
+        hypothesised ahead), of which commit() installs one and discard() drops all. frames: as step_many()'s, {modality: (B, n,
+        dim)}; ncand: an int in 1 .. 256; noise: (n, B, ncand, C) contiguous float32 on the session's device, the prior draws already
+        * eps, or None: n * ncand draws of the session's own, frame-major, then candidate. -> (faces, nll): faces (B, ncand, n, C),
+        nll (n, B, ncand) float32 in bits - both always, whatever return_nll the session was opened with. Candidate j of row r is
+        the continuation step_many(frames, noise[:, :, j]) generates for row r: within a row the candidates share the conditioning
+        frames, the dropout masks of a train-mode session (drawn once per call, as step_many draws them, before the noise) and the
+        incoming windows and h / c; they differ in their prior draws and in everything those cause - from the second frame on each
+        has its own faces window and its own h / c. Bit for bit where the fused front end and the one-launch chain run (rows never
+        mix in either); with ncand = 1 on every path (the same launches on the same shapes); elsewhere to the session's gates (the
+        front-end GEMMs run over B * ncand rows and may tile differently).
+
+        THE SESSION DOES NOT MOVE - unlike step_candidates(), which advances the windows: a rollout under hypothesised conditioning
+        must be droppable. Nothing the session owns is written: not the conditioning windows, not the faces window, h / c, the frame
+        counter or `steps`. The call leaves the session PENDING: until commit(), discard() or reset() every other call raises
+        RuntimeError.
+
+        Per call: lfi_stream_chunk_gen_in (the windows as sequences in the chunk workspaces), the static part in sequence mode ONCE
+        for the n frames of the B rows - not for B * ncand - lfi_stream_cand_seq_in (each row's faces sequence and h / c broadcast
+        to its candidates, the noise through the range guard) and lfi_flow_sample_cand_seq: the sampler over B * ncand virtual rows
+        that read their parent row's static pre-activations in place. Eager launches, no graph, no host wait; `replays` is untouched
+        and the per-frame graphs stay valid. ONE round only: n is at most _rollout_cap(ncand) frames, and B * ncand at most 2^22 -
+        beyond either, ValueError. Everything is checked before the first launch: a refused call leaves the session as it was."""
+        s, eng, B = self.eng.spec, self.eng, self.B
+        self._check_usable()
+        ncand = self._check_ncand(ncand)
+        srcs, n, _ = self._check_frames(frames)
+        if noise is None and n is None:
+            raise ValueError("noise: a model without conditioning windows takes its frame count from the noise, (n, B=%d, ncand=%d, %d)"
+                             % (B, ncand, s.C))
+        if noise is not None:
+            n = self._check_rollout_noise(noise, n, ncand)
+        V = B * ncand
+        if V > _MAX_VIRTUAL_ROWS:
+            raise ValueError("ncand: %d candidates for each of %d rows are %d virtual rows, more than one call takes (at most %d)"
+                             % (ncand, B, V, _MAX_VIRTUAL_ROWS))
+        cap = self._rollout_cap(ncand)
+        if n > cap:
+            raise ValueError("frames: %d frames of %d candidates for each of %d rows are more than the one round a rollout is (at most "
+                             "%d frames)" % (n, ncand, B, cap))
+        used = list(srcs)
+        srcs.append(None)                       # (the faces window has no source: the chain writes the candidates' frames)
+        with self._chunk_call(n, used) as rounds:
+            (_, _, masks), = rounds             # (n <= _rollout_cap() <= _chunk_cap(): one round)
+            L = eng.L
+            if noise is None:
+                noise = torch.stack([torch.stack([self._noise_fn(B, s.C) for _ in range(ncand)], 1) for _ in range(n)]).contiguous()
+            used.append(noise)
+            k, T = len(self._wins), s.start + n
+            dims = eng._flow_dims(B, n)
+            floats = L.lfi_flow_sample_cand_seq_work_floats(C.byref(dims), ncand)
+            if floats <= 0:
+                raise ValueError("ncand: %d candidates for each of %d rows are more than one call takes" % (ncand, B))
+            seqs, seq_p, src_p = self._chunk_seqs(srcs, n)
+            ev = eng._tic("stream_chunk_in")
+            # (the guard fold of gen_in reads an (n, B, C) block: the first n * B * C of the candidates' draws, all of which
+            # lfi_stream_cand_seq_in folds anyway)
+            check(L.lfi_stream_chunk_gen_in(B, n, s.start, k, self._row_win, src_p, seq_p, self._row_hist, self._row_dim, self._lead,
+                                            k - 1, noise.data_ptr(), s.C, self.guard.data_ptr(), _stream()), "lfi_stream_chunk_gen_in")
+            eng._toc("stream_chunk_in", ev)
+            pre = self._chunk_static(seqs, n, masks)
+            dv = eng._flow_dims(V, n)
+            dv.gemm_precision = self.frame_precision
+            p = eng._flow_params()
+            r = types.SimpleNamespace(
+                kind="rollouts", ncand=ncand, n=n, seq_p=seq_p,
+                seq=eng._buf("rollout_seq", V * T * s.C)[:V * T * s.C].view(B, ncand, T, s.C),
+                nll=eng._buf("rollout_nll", n * V)[:n * V].view(n, B, ncand),
+                h=eng._buf("rollout_h", s.Ks * V * s.H),
+                c=eng._buf("rollout_c", s.Ks * V * s.H) if self.cs is not None else None,
+                choice=eng._buf_i32("rollout_choice", B)[:B])
+            work = eng._buf("rollout_work", floats)
+            p1work = eng._buf("rollout_p1work", L.lfi_flow_sample_p1_work_floats(C.byref(dv), C.byref(self._p1), self.hist1))
+            nll_work = eng._buf("rollout_nll_work", L.lfi_flow_sample_nll_work_floats(C.byref(dv)))
+            ev = eng._tic("stream_rollout_in")
+            check(L.lfi_stream_cand_seq_in(B, ncand, n, s.start, s.C, s.Ks, s.H, seqs["p1_face"].data_ptr(), r.seq.data_ptr(),
+                                           self.h.data_ptr(), ptr(self.cs), r.h.data_ptr(), ptr(r.c), self._first_frame,
+                                           noise.data_ptr(), self.guard.data_ptr(), _stream()), "lfi_stream_cand_seq_in")
+            eng._toc("stream_rollout_in", ev)
+            ev = eng._tic("stream_rollout_chain")
+            check(L.lfi_flow_sample_cand_seq(C.byref(dv), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
+                                             pre.data_ptr(), noise.data_ptr(), r.seq.data_ptr(), T, s.start, n, self._first_frame,
+                                             r.h.data_ptr(), ptr(r.c), C.byref(self._p1), p1work.data_ptr(), work.data_ptr(),
+                                             r.nll.data_ptr(), nll_work.data_ptr(), ncand, _stream()), "lfi_flow_sample_cand_seq")
+            eng._toc("stream_rollout_chain", ev)
+            faces, nll = r.seq[:, :, s.start:].contiguous(), r.nll.clone()
+            self._pending = r
+        self._record_out(faces, nll)
+        return faces, nll
+
+    def _commit_rollouts(self, r, choice):
+        """commit() with rollouts pending: lfi_stream_chunk_out over the conditioning windows (they advance by the n frames the
+        rollout was conditioned on) and lfi_stream_commit_cand_seq - the chosen candidate's frames, the tail of its faces sequence,
+        its h / c, its NLL words, the frame counter += 2 n - then `steps` += n. -> (out (B, n, C), nll (n, B), choice (B,) int32)."""
+        s, eng, B = self.eng.spec, self.eng, self.B
+        n, ncand = r.n, r.ncand
+        dev, host = self._check_choice(choice, ncand)
+        with self._owned():
+            L = eng.L
+            if dev is not None:
+                r.choice.copy_(dev)
+                dev.record_stream(torch.cuda.current_stream(self.device))
+            elif host is not None:
+                r.choice.copy_(torch.tensor(host, dtype=torch.int32).pin_memory(), non_blocking=True)
+            out = torch.empty(B, n, s.C, dtype=torch.float32, device=self.device)
+            nll = torch.empty(n, B, dtype=torch.float32, device=self.device)
+            picked = torch.empty(B, dtype=torch.int32, device=self.device)
+            k = len(self._wins) - 1             # the conditioning windows: every window but the last, the faces window
+            ev = eng._tic("stream_rollout_commit")
+            if k:
+                check(L.lfi_stream_chunk_out(B, n, s.start, k, self._row_win, r.seq_p, self._row_hist, self._row_dim, self._lead, None,
+                                             _stream()), "lfi_stream_chunk_out")
+            check(L.lfi_stream_commit_cand_seq(B, ncand, n, s.start, s.C, s.Ks, s.H, None if choice is None else r.choice.data_ptr(),
+                                               r.seq.data_ptr(), r.nll.data_ptr(), r.h.data_ptr(), ptr(r.c), self.faces.data_ptr(),
+                                               self.hist1 + 1, self.h.data_ptr(), ptr(self.cs), ptr(self.frame_nb), out.data_ptr(),
+                                               nll.data_ptr(), picked.data_ptr(), self.guard.data_ptr(), _stream()),
+                  "lfi_stream_commit_cand_seq")
+            eng._toc("stream_rollout_commit", ev)
+            self._publish_guard()
+            self._pending = None
+            self.steps += n
+        self._record_out(out, nll, picked)
+        return out, nll, picked
+
+    def discard(self):
+        """Drop the pending rollouts (rollout_candidates): the session stays exactly where it was before them - every row's
+        save_rows record, `steps` and what the next call generates - and is no longer pending. No launch. One-frame candidates
+        (step_candidates) cannot be discarded: their call has moved the windows already."""
+        self._check_usable(pending_ok=True)
+        pend = self._pending
+        if pend is None:
+            raise RuntimeError("SampleStream: discard() without pending rollouts (rollout_candidates comes first)")
+        if getattr(pend, "kind", None) != "rollouts":
+            raise RuntimeError("SampleStream: discard() with %d one-frame candidates per row pending (step_candidates): their call has "
+                               "moved the session's windows already - commit() one of them, or reset()" % pend)
+        self._pending = None
+
+    def rollout_best_of(self, frames, ncand, noise=None):
+        """rollout_candidates(frames, ncand, noise) followed by commit(): every row's rollout of least summed NLL becomes its next
+        n frames. -> commit()'s (out, nll, choice)."""
+        self.rollout_candidates(frames, ncand, noise)
         return self.commit()
 
     def _check_chunk(self, x, name, cols, n=None):

@@ -6,6 +6,7 @@ alternative without a session: re-running SeqGlow.inference over the whole prefi
                                  [--observe 1,16,256] [--rows 1,16,256] [--observe-many 16,64,250]
                                  [--step-many 4,16,64] [--observe-ragged 16,64,250] [--rows-many 4,16,64]
                                  [--candidates 16,8 [--passes 5]]
+                                 [--rollouts 16,8,8 [--passes 5]]
 
 Per batch size: the wall-clock time from step() to the generated frame on the host (a synchronise after every step: what a live agent
 waits for), its GPU time (HIP events around the step), and a per-kernel breakdown from the engine's enable_timing on an eager session
@@ -73,7 +74,17 @@ r * ncand: save_rows(home rows), load_rows(every row, entries = row // ncand), s
 times (the repeats are made before the clock starts), the arg-min per conversation read on the host, save_rows(the winners'
 rows), load_rows(home rows). Per pass: the median frame's wall clock (a synchronise after the frame) and GPU time (HIP events). Then
 the stream_advance / stream_static / stream_chain timers of both arms from the engine's enable_timing on eager sessions
-(LFI_NO_GRAPH=1), and the shader clock under the new arm's load."""
+(LFI_NO_GRAPH=1), and the shader clock under the new arm's load.
+
+--rollouts B,ncand,n: this leg ALONE, written to --out (default: printed only): best-of-N over n frames for B conversations, two
+arms alternated as whole passes, --passes of each (the recipe first) of --steps timed rollouts after --warmup untimed ones, a
+caller on the legacy default stream. (new) rollout_candidates(frames, ncand, noise) + commit() on a session of B rows. (recipe) what
+INTEGRATION.md prescribes with rows, on a session of B * ncand rows opened with return_nll=True, conversation r at home in row
+r * ncand: save_rows(home rows), load_rows(every row, entries = row // ncand), step_many() with every row's conditioning repeated
+ncand times (the repeats are made before the clock starts), the arg-min of the summed NLL per conversation read on the host,
+save_rows(the winners' rows), load_rows(home rows). Per pass: the median rollout's wall clock (a synchronise after it) and GPU time
+(HIP events), per committed frame. Then where the new arm's GPU time goes, from the engine's enable_timing: windows in, static part,
+candidates in, front end + chain, commit; the front end alone from a call with LFI_CHUNK_ONLY=front, the chain by difference."""
 import argparse
 import contextlib
 import os
@@ -105,7 +116,8 @@ def main():
     ap.add_argument("--observe-ragged", default=None, help="chunk lengths of the ragged observe_many() leg: runs this leg alone")
     ap.add_argument("--rows-many", default=None, help="frames per call of the step_rows_many() leg, e.g. 4,16,64: runs this leg alone")
     ap.add_argument("--candidates", default=None, help="B,ncand of the best-of-N leg, e.g. 16,8: runs this leg alone")
-    ap.add_argument("--passes", type=int, default=5, help="with --candidates: whole passes per arm, alternated")
+    ap.add_argument("--rollouts", default=None, help="B,ncand,n of the best-of-N-over-n-frames leg, e.g. 16,8,8: runs this leg alone")
+    ap.add_argument("--passes", type=int, default=5, help="with --candidates / --rollouts: whole passes per arm, alternated")
     ap.add_argument("--reps", type=int, default=7, help="with --observe-many / --step-many / --observe-ragged: timed rounds per (batch size, chunk length)")
     a = ap.parse_args()
     resources = chain_kernel_resources() if a.observe_ragged else None     # (compiles; before the GPU is initialised)
@@ -138,6 +150,16 @@ def main():
     if a.candidates:
         B, ncand = (int(v) for v in a.candidates.split(","))
         text = candidates_report(m, dev, B, ncand, a.passes, a.steps, a.warmup, dims, start, C, torch.cuda.get_device_name(dev), bench, helper)
+        bench.stop_smi_helper(helper)
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text)
+        return
+    if a.rollouts:
+        B, ncand, n = (int(v) for v in a.rollouts.split(","))
+        text = rollouts_report(m, dev, B, ncand, n, a.passes, a.steps, a.warmup, dims, start, C, torch.cuda.get_device_name(dev))
         bench.stop_smi_helper(helper)
         print(text)
         if a.out:
@@ -926,6 +948,129 @@ def candidates_report(m, dev, B, ncand, passes, steps, warmup, dims, start, C, d
               "rows, chain over %d virtual rows). The save / load launches of the recipe and the commit launch carry no timer: they are "
               "the rest of the frame's GPU time." % (V, B, V, B, V), "",
               "GPU state under the new calls' load: %s" % (clk if clk else "not read (no rocm-smi helper)")]
+    return "\n".join(lines) + "\n"
+
+
+def rollouts_report(m, dev, B, ncand, n, passes, steps, warmup, dims, start, C, device_name):
+    """The --rollouts report: per pass the median rollout of rollout_candidates + commit() and of the save / load / step_many / save /
+    load recipe, per committed frame, alternated as whole passes; then where the new calls' GPU time goes."""
+    import torch
+    s = m.spec
+    eng = m._ensure_engine(dev)
+    V, total = B * ncand, warmup + steps
+    gd = torch.Generator().manual_seed(B * 1000 + ncand * 10 + n)
+    # every rollout runs under the same n frames of conditioning and its own draws, from wherever the last commit left the session
+    data = {k: torch.randn(B, start + n, d, generator=gd).to(dev) for k, d in dims.items()}
+    seed = {k: v[:, :start].contiguous() for k, v in data.items()}
+    frames = {k: v[:, start:].contiguous() for k, v in data.items() if k != "p1_face"}
+    noise = (torch.randn(8, n, B, ncand, C, generator=gd) * 0.8).to(dev)
+    seed_v = {k: v.repeat_interleave(ncand, 0).contiguous() for k, v in seed.items()}
+    frames_v = {k: v.repeat_interleave(ncand, 0).contiguous() for k, v in frames.items()}
+    noise_v = noise.view(8, n, V, C)
+    home, every, parent = [r * ncand for r in range(B)], list(range(V)), [v // ncand for v in range(V)]
+    base = torch.tensor(home, device=dev)
+
+    def new_rollout(st, i):
+        st.rollout_candidates(frames, ncand, noise[i % 8])
+        return st.commit()[0]
+
+    def recipe_rollout(st, i):
+        st.load_rows(every, st.save_rows(home), parent)
+        out, nll = st.step_many(frames_v, noise_v[i % 8])
+        tot = nll[0].clone()
+        for f in range(1, n):
+            tot += nll[f]
+        win = (base + tot.view(B, ncand).argmin(1)).tolist()        # (the arg-min on the host side: the row lists are host data)
+        st.load_rows(home, st.save_rows(win))
+        return out[win]
+
+    def run(st, fn):
+        wall, gpu = [], []
+        for i in range(total):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e0.record()
+            fn(st, i)
+            e1.record()
+            e1.synchronize()
+            t1 = time.perf_counter()
+            if i >= warmup:
+                wall.append((t1 - t0) * 1e3 / n)
+                gpu.append(e0.elapsed_time(e1) / n)
+        return statistics.median(wall), statistics.median(gpu)
+
+    series = {"recipe": [], "new": []}
+    with m.open_stream(seed) as st_new, m.open_stream(seed_v, return_nll=True) as st_old:
+        arms = (("recipe", st_old, seed_v, recipe_rollout), ("new", st_new, seed, new_rollout))
+        for p in range(passes):
+            for name, st, sd, fn in arms:
+                st.reset(sd)
+                series[name].append(run(st, fn))
+        # where the new calls' GPU time goes: the engine's events around every group of launches
+        st_new.reset(seed)
+        for i in range(3):
+            new_rollout(st_new, i)
+        eng.enable_timing(True)
+        for i in range(steps):
+            new_rollout(st_new, i)
+        split = eng.timing_summary()
+        eng.enable_timing(False)
+        # the front end alone (LFI_CHUNK_ONLY=front: no chain is launched; what the call returns is not meaningful and is dropped)
+        os.environ["LFI_CHUNK_ONLY"] = "front"
+        try:
+            eng.enable_timing(True)
+            for i in range(steps):
+                st_new.rollout_candidates(frames, ncand, noise[i % 8])
+                st_new.discard()
+            front = eng.timing_summary().get("stream_rollout_chain")
+        finally:
+            eng.enable_timing(False)
+            del os.environ["LFI_CHUNK_ONLY"]
+        # the recipe's static part and chain, the same way
+        st_old.reset(seed_v)
+        for i in range(3):
+            recipe_rollout(st_old, i)
+        eng.enable_timing(True)
+        for i in range(steps):
+            recipe_rollout(st_old, i)
+        split_old = eng.timing_summary()
+        eng.enable_timing(False)
+    lines = ["# Best-of-N over n frames: rollout_candidates + commit() against the save / load recipe (tools/stream_latency.py --rollouts "
+             "%d,%d,%d)" % (B, ncand, n), "",
+             "final_model.yaml as shipped (C = %d, S = %d, K = %d, H = %d, D = %d), engine precision %s; B = %d conversations, ncand = %d "
+             "candidates of n = %d frames (the recipe's session has %d rows); %d whole passes per arm, alternated, the recipe first; a "
+             "pass is the median of %d timed rollouts after %d untimed ones, divided by n: ms per COMMITTED frame. wall = call to result "
+             "on the host (a synchronise after the rollout), GPU = HIP events around it. Device %s."
+             % (C, s.S, s.Ks, s.H, s.D, m.precision, B, ncand, n, V, passes, steps, warmup, device_name), "",
+             "| pass | recipe: wall ms / frame | recipe: GPU ms / frame | new: wall ms / frame | new: GPU ms / frame |", "|---|---|---|---|---|"]
+    for p in range(passes):
+        (rw, rg), (nw, ng) = series["recipe"][p], series["new"][p]
+        lines.append("| %d | %.4f | %.4f | %.4f | %.4f |" % (p + 1, rw, rg, nw, ng))
+    for i, what in ((0, "wall"), (1, "GPU")):
+        new_med = statistics.median(v[i] for v in series["new"])
+        low = min(v[i] for v in series["recipe"])
+        lines += ["", "%s: the new calls' median over the passes %.4f ms, the recipe's lowest pass %.4f ms (%.2f x): %s."
+                  % (what, new_med, low, low / new_med, "below it" if new_med < low else "NOT below it")]
+
+    def per_call(summary, tag):
+        v = summary.get(tag)
+        return v[0] * v[1] / steps if v else 0.0
+
+    both = per_call(split, "stream_rollout_chain")
+    fr = front[0] * front[1] / steps if front else 0.0
+    lines += ["", "## Where a rollout's GPU time goes (enable_timing, HIP events; ms per call of n = %d frames, a kind's launches summed)" % n, "",
+              "| part | new: rollout_candidates + commit | recipe: step_many over %d rows |" % V, "|---|---|---|",
+              "| windows in (lfi_stream_chunk_gen_in) | %.4f | %.4f |" % (per_call(split, "stream_chunk_in"), per_call(split_old, "stream_chunk_in")),
+              "| static part (window encoders + static cond_transform columns; %d rows against %d) | %.4f | %.4f |"
+              % (B, V, per_call(split, "stream_chunk_static"), per_call(split_old, "stream_chunk_static")),
+              "| candidates in (lfi_stream_cand_seq_in) | %.4f | - |" % per_call(split, "stream_rollout_in"),
+              "| front end + chain (lfi_flow_sample_cand_seq / lfi_flow_sample_seq_nll, %d rows both) | %.4f | %.4f |"
+              % (V, both, per_call(split_old, "stream_chunk_gen_chain")),
+              "| - front end alone (LFI_CHUNK_ONLY=front) | %.4f | - |" % fr,
+              "| - chain (the difference) | %.4f | - |" % (both - fr),
+              "| commit (lfi_stream_chunk_out + lfi_stream_commit_cand_seq) | %.4f | - |" % per_call(split, "stream_rollout_commit"),
+              "", "The recipe's save_rows / load_rows launches and its window launch out carry no timer: they are the rest of its GPU time."]
     return "\n".join(lines) + "\n"
 
 
