@@ -312,6 +312,13 @@ int lfi_flow_seq_bwd(const lfi_flow_dims* d, const lfi_flow_params* p, const flo
  * written: the thin dW_ih[:, :Ch] product reads it). lfi_flow_bwd_emits_planes(d) = 1 when the dims allow it (bf16x3 persistent
  * walk, H and B multiples of 32). */
 int lfi_flow_bwd_emits_planes(const lfi_flow_dims* d);
+/* Which kernels a call with these dims takes under the environment switches as they stand (host only, no device call; the
+ * launchers decide through the same function). which 0: lfi_flow_seq_fwd, 1: lfi_flow_seq_bwd / _bwd_planes -> 0 = generic
+ * diagonal cells, 1 = register-resident diagonal cells, 2 = persistent walk with exact f32 recurrent products, 3 = persistent walk
+ * with bf16x3 recurrent products. which 2: the thin products of lfi_flow_param_grads -> 0 = four split-K products, 1 = one pass
+ * over the backward stash (gemm_precision bit 16 set, as that call is given it). Bad dims or `which`: -1.
+ * (FlowStep.normal_flow and its autograd, glow/models.py:311-342) */
+int lfi_flow_walk_variant(const lfi_flow_dims* d, int which);
 int lfi_flow_seq_bwd_planes(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep,
                             const float* stash, float gscale, float* bstash, void* dgi_planes,
                             int hi_only /* 1: the hi planes only (lfi_pgemm_desc.out_hi_only) */, void* stream);

@@ -1708,9 +1708,10 @@ __global__ __launch_bounds__(256) void flow_prep_invconv_kernel(FlowK f, float* 
         Winv[kc + idx] = (float)M[(long)i * 2 * C + C + j];
       }
     if (tid == 0) {
-      float s = 0.0f;
-      for (int c = 0; c < C; ++c) s += f.p.an_logs[(long)k * C + c];
-      ldpart[k] = (float)C * (s + (float)logabs);
+      // (in fp64: the sum is scaled by C - the log-det is counted C times - and its rounding with it)
+      double s = 0.0;
+      for (int c = 0; c < C; ++c) s += (double)f.p.an_logs[(long)k * C + c];
+      ldpart[k] = (float)((double)C * (s + logabs));
     }
     return;
   }
@@ -1740,9 +1741,11 @@ __global__ __launch_bounds__(256) void flow_prep_invconv_kernel(FlowK f, float* 
     Wtk[(long)j * C + i] = s;
   }
   if (tid == 0) {
-    float s = 0.0f;
-    for (int c = 0; c < C; ++c) s += f.p.an_logs[(long)k * C + c] + ls[c];
-    ldpart[k] = (float)C * s;
+    // in fp64: the log|s| of a well-conditioned W are of size 1 and cancel to a small sum, which is then scaled by C (the log-det
+    // is counted C times) - a serial fp32 sum left 1e-6 of the per-frame NLL here, the same offset in every frame
+    double s = 0.0;
+    for (int c = 0; c < C; ++c) s += (double)f.p.an_logs[(long)k * C + c] + (double)ls[c];
+    ldpart[k] = (float)((double)C * s);
   }
   if (!Winv) return;
   // fp64 triangular inverses by substitution, one column per thread
@@ -1977,6 +1980,22 @@ FlowPipeKernel flow_pipe_bwd_pick(bool lstm, bool x3) {
   return x3 ? flow_pipe_bwd_kernel<3, true> : flow_pipe_bwd_kernel<3, false>;
 }
 
+// ---- which walk a call takes (lfi_flow_walk_variant's codes): the ONE place the three entry points and the query decide it.
+// 0 generic diagonal cells, 1 register-resident diagonal cells, 2 persistent walk with exact f32 recurrent products, 3 persistent
+// walk with bf16x3 recurrent products. backward: the backward walk's rule (flow_x3_bwd_walk) instead of the forward walk's.
+int flow_walk_code(const lfi_flow_dims* d, const FlowK& f, bool backward) {
+  if (!flow_fast_ok(f.C, f.H, f.Cout) || flow_force_generic()) return 0;
+  if (!flow_pipe_enabled()) return 1;
+  return (backward ? flow_x3_bwd_walk(d, f) : flow_x3_fwd_walk(d, f)) ? 3 : 2;
+}
+// LFI_FLOW_WGRAD_FUSED=0: the thin weight-gradient products as four batched split-K launches + a column-sum pass (rounds 2 - 5)
+bool flow_wgrad_fused_enabled() { return lfi_env_on("LFI_FLOW_WGRAD_FUSED"); }
+// the thin products of lfi_flow_param_grads in one pass (lfi_wgrad.hip): bf16 gradient rows, GRU, the shapes that file is built for
+bool flow_wgrad_one_pass(const lfi_flow_dims* d, const FlowK& f) {
+  return ((d->gemm_precision >> 16) & 1) && !f.lstm && flow_wgrad_fused_enabled() &&
+         lfi_internal_flow_wgrad_ok(f.B, f.N, f.C, f.Ch, f.Cout, f.H, f.G, f.ldc, f.ldo) != 0;
+}
+
 // start state of a persistent walk: header and progress words cleared (LFI_PIPE_FORCE_ABORT=1: the abort word already set)
 int flow_pipe_reset(const FlowK& f, hipStream_t st, const char* who) {
   hipError_t me = hipMemsetAsync(f.pipe, 0, (size_t)pipe_words(f) * sizeof(unsigned), st);
@@ -2086,19 +2105,20 @@ extern "C" int lfi_flow_seq_fwd(const lfi_flow_dims* d, const lfi_flow_params* p
   bind_stash(&f, stash);
   f.x0 = x0; f.T = T; f.start = start; f.gic = gic;
   hipStream_t st = (hipStream_t)stream;
-  const bool fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
+  const int variant = flow_walk_code(d, f, false);
+  const bool fast = variant >= 1;
   const Carve cv = carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout);
   const CarveF cf = carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout);
   const size_t lds = (size_t)(fast ? cf.total : cv.total) * sizeof(float);
   const FlowDiagKernel diag = flow_diag_fwd_pick(fast, f.lstm);
   if ((rc = set_flow_lds(diag, lds, "lfi_flow_seq_fwd"))) return rc;
-  const bool pipe = fast && flow_pipe_enabled();
+  const bool pipe = variant >= 2;
   if (pipe) {
     long off[8];
     f.pipe = reinterpret_cast<unsigned*>(stash + align4(stash_offsets(f, off)));
     f.pipe_fence = flow_pipe_fence();
     const size_t plds = (size_t)pipe_fwd_lds_floats(f.C, f.C16, f.H16, f.Ch16, f.Cout, f.Co16) * sizeof(float);
-    const FlowPipeKernel walk = flow_pipe_fwd_pick(f.lstm, flow_x3_fwd_walk(d, f));
+    const FlowPipeKernel walk = flow_pipe_fwd_pick(f.lstm, variant == 3);
     if ((rc = set_flow_lds(walk, plds, "lfi_flow_seq_fwd"))) return rc;
     if ((rc = flow_pipe_reset(f, st, "lfi_flow_seq_fwd"))) return rc;
     hipLaunchKernelGGL(walk, dim3(f.Ks * f.nbt), dim3(NT), plds, st, f);
@@ -2123,10 +2143,19 @@ extern "C" int lfi_flow_seq_fwd(const lfi_flow_dims* d, const lfi_flow_params* p
 // batch tiles that pair up into whole 32-row plane tiles (B a multiple of 32).
 static bool flow_bwd_planes_ok(const lfi_flow_dims* d) {
   if (!d || !flow_x3_bwd_planes(d) || d->B % 32 != 0) return false;
-  const int Ch = d->C / 2, C2 = d->C - Ch, Cout = d->affine ? 2 * C2 : C2;
-  return flow_fast_ok(d->C, d->H, Cout) && !flow_force_generic() && flow_pipe_enabled();
+  FlowK f = {};
+  lfi_flow_params p = {};
+  return fill_flow(d, &p, nullptr, &f, "lfi_flow_bwd_emits_planes") == LFI_OK && flow_walk_code(d, f, true) == 3;
 }
 extern "C" int lfi_flow_bwd_emits_planes(const lfi_flow_dims* d) { return flow_bwd_planes_ok(d) ? 1 : 0; }
+
+extern "C" int lfi_flow_walk_variant(const lfi_flow_dims* d, int which) {
+  FlowK f = {};
+  lfi_flow_params p = {};
+  if (which < 0 || which > 2 || fill_flow(d, &p, nullptr, &f, "lfi_flow_walk_variant")) return -1;
+  if (which == 2) return flow_wgrad_one_pass(d, f) ? 1 : 0;
+  return flow_walk_code(d, f, which == 1);
+}
 
 extern "C" int lfi_flow_seq_bwd(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* stash,
                                 float gscale, float* bstash, void* stream) {
@@ -2149,18 +2178,19 @@ extern "C" int lfi_flow_seq_bwd_planes(const lfi_flow_dims* d, const lfi_flow_pa
   f.g16 = (dgi_rows && ((d->gemm_precision >> 16) & 1)) ? 1 : 0;
   f.gscale = gscale;
   hipStream_t st = (hipStream_t)stream;
-  const bool fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
+  const int variant = flow_walk_code(d, f, true);
+  const bool fast = variant >= 1;
   const CarveB cv = carve_bwd(f.C, f.H, f.Cout, f.G);
   const CarveFB cf = carve_fast_bwd(f.C16, f.H16, f.Co16, f.Cout, f.NG);
   const size_t lds = (size_t)(fast ? cf.total : cv.total) * sizeof(float);
   const FlowDiagKernel diag = flow_diag_bwd_pick(fast, f.lstm);
   if ((rc = set_flow_lds(diag, lds, "lfi_flow_seq_bwd"))) return rc;
-  const bool pipe = fast && flow_pipe_enabled();
+  const bool pipe = variant >= 2;
   if (pipe) {
     long off[10];
     f.pipe = reinterpret_cast<unsigned*>(bstash + align4(bstash_offsets(f, off)));
     f.pipe_fence = flow_pipe_fence();
-    const bool x3 = flow_x3_bwd_walk(d, f);
+    const bool x3 = variant == 3;
     // + the bf16 hi / lo image of d lin (Q1's bf16 x 3 operand): 2 x MB rows of 32 ceil(Co16 / 32) + 8 bf16
     const size_t plds = x3 ? (((size_t)cf.total + 3) & ~(size_t)3) * sizeof(float) + (size_t)2 * MB * (32 * ((f.Co16 + 31) / 32) + 8) * 2 : lds;
     const FlowPipeKernel walk = flow_pipe_bwd_pick(f.lstm, x3);
@@ -2193,9 +2223,6 @@ extern "C" long lfi_flow_param_grads_work_floats(const lfi_flow_dims* d) {
     fused = lfi_internal_flow_wgrad_work_floats(f.B, f.N, f.Ks, 0) + lfi_internal_flow_wgrad_work_floats(f.B, f.N, f.Ks, 1) + 32;
   return (long)f.Ks * f.C * f.C + gemm_ws + cs + 16 + gemm_ws + 16 + fused;
 }
-
-// LFI_FLOW_WGRAD_FUSED=0: the thin weight-gradient products as four batched split-K launches + a column-sum pass (rounds 2 - 5)
-bool flow_wgrad_fused_enabled() { return lfi_env_on("LFI_FLOW_WGRAD_FUSED"); }
 
 extern "C" int lfi_flow_param_grads(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, const float* stash,
                                     const float* bstash, const float* c, long ldc, float gscale, const lfi_flow_grads* g,
@@ -2250,8 +2277,7 @@ extern "C" int lfi_flow_param_grads(const lfi_flow_dims* d, const lfi_flow_param
   // w_hh | w_fl | b_fl in line on `stream` (its workgroups hold a CU each: beside the caller's MFMA-bound dgi^T c product on the
   // other stream both ran at half speed, profiles/round6_thin_products_ab.md), w_ih[:, :Ch] | dW (two workgroups per CU) on
   // bias_stream, where dW's reader, the LU-gradient kernel, follows (LFI_FLOW_WGRAD_IH=main: in line as well).
-  const bool fused = g16 && !f.lstm && flow_wgrad_fused_enabled() &&
-                     lfi_internal_flow_wgrad_ok(B, f.N, C, Ch, Cout, H, G, f.ldc, f.ldo) != 0;
+  const bool fused = flow_wgrad_one_pass(d, f);
   if (fused) {
     float* part0 = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(gws2 + gws_floats) + 63) & ~(uintptr_t)63);
     float* part1 = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(part0 + lfi_internal_flow_wgrad_work_floats(B, f.N, Ks, 0)) + 63) & ~(uintptr_t)63);
@@ -2318,7 +2344,7 @@ extern "C" int lfi_flow_param_grads(const lfi_flow_dims* d, const lfi_flow_param
   // biases and the per-tile partial sums: column sums over the backward stash only (HBM streams), independent of the
   // products above - on bias_stream when the caller has forked one after the backward walk
   if (!fused && (rc = lfi_colsum_f32(f.bDlin, f.ldo, (long)F * f.ldo, F, Cout, Ks, g->b_fl, Cout, 1.0f, accumulate, cws, bs))) return rc;
-  if (flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic() && flow_pipe_enabled()) {
+  if (flow_walk_code(d, f, true) >= 2) {
     // the persistent backward walk left per-workgroup sums of dgi | dgh: [Ks][nbt][2][G]
     if ((rc = lfi_colsum_f32(f.bPbias, 2 * G, (long)f.nbt * 2 * G, f.nbt, G, Ks, g->b_ih, G, 1.0f, accumulate, cws, bs))) return rc;
     if ((rc = lfi_colsum_f32(f.bPbias + G, 2 * G, (long)f.nbt * 2 * G, f.nbt, G, Ks, g->b_hh, G, 1.0f, accumulate, cws, bs))) return rc;
