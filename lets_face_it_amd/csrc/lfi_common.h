@@ -72,6 +72,12 @@ extern "C" __attribute__((visibility("hidden"))) int lfi_internal_flow_wgrad(int
                                                                               float* w_ih, float* w_fl, float* b_fl, float* dW,
                                                                               int accumulate, void* stream);
 
+// ---- internal: the window encoders' recurrent weights, re-laid into `work` as the fused kernels read them (lfi_encoder.hip), called by
+// lfi_encode_windows_fwd (lfi_encoder_fwd.hip) and lfi_encode_windows_bwd (lfi_encoder_bwd.hip) through enc_build_weights
+// (lfi_encoder_common.h). `weights` is an EncWeights of that header.
+extern "C" __attribute__((visibility("hidden"))) void lfi_internal_enc_build_weights(int weights, const float* whh, int hid, int Kp, int Jp,
+                                                                                     int fwd, float* work, void* stream);
+
 // ---- device side -----------------------------------------------------------
 // Operand planes (lfi_planes_from_f32, lfi_pgemm.hip): byte offset inside a 1-KB block (32 rows x 16 columns, bf16, row-major
 // 32-byte rows) of the 16-byte chunk ch (columns 8 ch .. + 7) of row r. The two chunks of a row trade places in rows 8-15 and

@@ -26,7 +26,7 @@ constexpr int SC_PITCH = SC_D * 2 + 16;     // bytes per row of a c plane in LDS
 constexpr int SC_NT = 512;
 
 // 16-byte k-chunk of lane group q in MFMA step m of a row of nchunk chunks: the chunks of the groups that share a ds_read_b128
-// cycle lie half a row apart (a multiple of 256 bytes at D = 512), rows advance by one 16-byte slot: all 64 banks (lfi_encoder.hip,
+// cycle lie half a row apart (a multiple of 256 bytes at D = 512), rows advance by one 16-byte slot: all 64 banks (lfi_encoder_common.h,
 // enc_chunk16: the same rule)
 __host__ __device__ inline int sc_chunk(int m, int q, int nchunk) { return 2 * m + (q >> 1) + (nchunk >> 1) * (q & 1); }
 

@@ -155,7 +155,7 @@ def run_model(inp, dims, lstm=False, three_products=False, two_products=False, s
     three_products  both operands of h W_hh^T and of dgh W_hh are split into bf16 hi + lo, summed as hi hi + hi lo + lo hi
                     (lfi_enc_desc.precision = 1; lfi_gemm_desc.precision = 1 on the unfused and LSTM loops)
     bwd_exact       with three_products: only the forward product is split, dgh W_hh is exact - the accumulator-layout backward
-                    kernel "runs the exact-f32 ... kernel, whatever the engine's GEMM mode" (enc_plan_bwd in lfi_encoder.hip)
+                    kernel "runs the exact-f32 ... kernel, whatever the engine's GEMM mode" (enc_plan_bwd in lfi_encoder_common.h)
     two_products    dgh W_hh takes the gate derivatives rounded to bf16 and the weights as hi + lo (lfi_enc_desc.bwd_two_products)
     stash_f16       r, z, n and W_hn h + b_hn are rounded to fp16 between forward and backward (lfi_enc_desc.stash_f16)
     grads_bf16      dgi and dgh are rounded to bf16 before the scatter and the dW_hh sum (lfi_encode_windows_grad_stash_bf16);

@@ -5,7 +5,7 @@ times on the same inputs, outputs compared bit for bit.
 Until round 5 that was enc_gru_bwd_fused_kernel<true> (bf16x3), which differed launch to launch in an SLP-vectorised build
 (profiles/round5_enc_bwd_repro.txt: 19 of 19). Round 6 deleted it: the switch now selects the exact-f32 accumulator-layout kernel, and
 this tool is the check that the fallback is bit-identical in the tree's build and in the SLP build (LFI_SLP=1 tools/build_variant.sh
-slp lfi_encoder.hip) alike - profiles/round6_enc_bwd_repro.txt."""
+slp lfi_encoder_bwd.hip) alike - profiles/round6_enc_bwd_repro.txt."""
 import argparse
 import ctypes as C
 import os

@@ -2,8 +2,9 @@
 """Times the window encoders' fused recurrence kernels alone, through the C ABI, at the headline shape (B=256, T=80, 56 timesteps):
    python tools/enc_probe.py [--mod p2_face|p2_speech] [--reps 20]
 per configuration (gate stash fp32 / fp16 / none, forward and BPTT) the mean launch time over --reps launches (HIP events on the
-launch stream). With an ingredient-removal library (LFI_LIB_PATH=build/var/liblfi_<variant>.so, tools/build_variant.sh) the results
-are garbage and only the times mean anything."""
+launch stream). With an ingredient-removal library (LFI_LIB_PATH=build/var/liblfi_<variant>.so, tools/build_variant.sh <variant>
+lfi_encoder_fwd.hip -DLFI_ENC_EXP_... / -DLFI_T16_..., or lfi_encoder_bwd.hip -DLFI_ENC_BWD_...; -DLFI_ENC_EXP_M16 and
+-DLFI_ENC_EXP_NO_GATEMATH reach both: lfi_encoder_fwd.hip,lfi_encoder_bwd.hip) the results are garbage and only the times mean anything."""
 import argparse
 import ctypes as C
 import os

@@ -1,5 +1,5 @@
 """Phase stamps of the wide forward window-encoder kernel (library built with -DLFI_ENC_STAMPS: tools/build_variant.sh stamps
-lfi_encoder.hip -DLFI_ENC_STAMPS; LFI_LIB_PATH=build/var/liblfi_stamps.so LFI_ENC_R64=0 python tools/enc_stamps.py):
+lfi_encoder_fwd.hip -DLFI_ENC_STAMPS; LFI_LIB_PATH=build/var/liblfi_stamps.so LFI_ENC_R64=0 python tools/enc_stamps.py):
 s_memtime of wave 0 of workgroup 0 at the phase boundaries of steps 4..11."""
 import ctypes as C
 import os

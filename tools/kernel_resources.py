@@ -18,9 +18,9 @@ def main():
         args, extra = args[:i], args[i + 1:]
     src = args[0]
     flt = args[1] if len(args) > 1 else ""
-    flags = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include")]
-    if os.path.basename(src) == "lfi_encoder.hip":
-        flags.append("-fno-slp-vectorize")     # as the Makefile builds it
+    # as the Makefile builds it: its print-flags target is the one record of the per-file flags
+    flags = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "lets_face_it_amd", "csrc"), "print-flags", "SRC=" + os.path.basename(src)],
+                           capture_output=True, text=True, check=True).stdout.split()
     cmd = ["hipcc"] + flags + extra + ["-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
     out = subprocess.run(cmd, capture_output=True, text=True).stderr
     cur, rows = None, []
