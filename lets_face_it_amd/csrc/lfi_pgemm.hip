@@ -41,6 +41,10 @@
 // whenever K has whole pairs of k-tiles in every split; the two whose
 // result leaves as planes only write them straight from the accumulators (gemm_epilogue_direct16). LFI_PGEMM_16 / _16T / _DIRECT = 0
 // bring this kernel and the through-LDS epilogue back.
+// gemm_planes16t_kernel reads every fragment of its main loop by inline assembly (pg_frag_tr_asm / pg_frag_row_asm below): the
+// builtin transposing read made hipcc drain the VM counter - the LDS-DMA ring - in front of it, twice per pair of k-tiles. Its
+// loop now holds no wait but the counted ones at the barriers and no scratch (tools/main_loop_waits.py).
+// LFI_PGEMM_TR_ASM=0 brings the builtin reads back (gemm_planes16t_builtin_kernel).
 #include "lfi_gemm_common.h"
 #include <type_traits>
 
@@ -64,6 +68,61 @@ __device__ __forceinline__ bf16x8 pg_frag(const char* blk, int uoff, int toff) {
   r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
   return r;
 }
+
+// The transposed fragment of gemm_planes16t_kernel's main loop (the step's four backward products), read by inline assembly.
+// Why: hipcc takes the builtin above for a read that may alias any LDS-DMA in flight and puts s_waitcnt vmcnt(0) in front of the
+// first one of every half-phase - the ring's look-ahead of two tiles is drained twice per pair and the counted waits at the barriers
+// never bind (tools/main_loop_waits.py shows the wait; profiles/pgemm_tr_reads.md). An asm read the compiler cannot see into gets no
+// such wait - and no lgkmcnt bookkeeping either, so the RULE is: a pg_trf is two register pairs the hardware fills LATER; nothing may
+// touch them before a hand-placed s_waitcnt lgkmcnt(0) that lies behind the read. pg_behind_wait(), called right after that wait,
+// passes the registers through an empty asm statement: volatile asm statements keep their order (read < wait < pg_behind_wait), and
+// every later use depends on pg_behind_wait's outputs, so no use - not even a register copy - can be placed in front of the wait.
+// pg_val() makes the MFMA operand of either fragment form (for a pg_trf: the two pairs side by side, no instruction when the
+// register allocator put them there - it does, tools/main_loop_waits.py would show the v_mov otherwise as a changed loop).
+// The address is a VGPR (base + the lane's toff, or toff ^ 128 for k rows + 4) + an immediate (ring slot, block): < 64 KB.
+// The general gemm_planes_kernel above (one k-tile per phase) and the AT / BT forms of gemm_planes16_kernel (three products; the reason
+// stands in front of that kernel) are not on the step's path and keep the builtin. gemm_planes16t_kernel's prologue reads use the asm
+// form as well (one fragment type per kernel); the wait behind them is named there.
+typedef unsigned pu32x2 __attribute__((ext_vector_type(2)));
+struct pg_trf { pu32x2 lo, hi; };
+template <int N> using pg_ic = std::integral_constant<int, N>;
+
+__device__ __forceinline__ unsigned pg_lds_addr(const char* p) { return (unsigned)(uintptr_t)(plds_void*)p; }
+
+template <int OFF>
+__device__ __forceinline__ pg_trf pg_frag_tr_asm(unsigned a0, unsigned a1) {
+  static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
+  pg_trf f;
+  asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%4\n\tds_read_b64_tr_b16 %1, %3 offset:%4"
+               : "=&v"(f.lo), "=&v"(f.hi) : "v"(a0), "v"(a1), "n"(OFF) : "memory");
+  return f;
+}
+// The by-row fragment of a loop that has asm reads beside it: ds_read_b128 by inline assembly too, under the same rule. Left to the
+// compiler it is counted on lgkmcnt WITHOUT the asm reads issued after it: the compiler's own waits in front of the MFMA rows
+// (lgkmcnt(2), (1), (0) for fragments that the phase-closing lgkmcnt(0) has long retired - it cannot see that wait either) then
+// stall on the asm reads just issued. With every read of the loop in asm the compiler has nothing to count and places no wait.
+struct pg_rf { gu32x4 q; };
+template <int OFF>
+__device__ __forceinline__ pg_rf pg_frag_row_asm(unsigned a) {
+  static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
+  pg_rf f;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(f.q) : "v"(a), "n"(OFF) : "memory");
+  return f;
+}
+__device__ __forceinline__ bf16x8 pg_val(const pg_rf& f) { return __builtin_bit_cast(bf16x8, f.q); }
+__device__ __forceinline__ void pg_behind_wait(pg_rf (&f)[4]) { asm volatile("" : "+v"(f[0].q), "+v"(f[1].q), "+v"(f[2].q), "+v"(f[3].q)); }
+__device__ __forceinline__ bf16x8 pg_val(const bf16x8& f) { return f; }
+__device__ __forceinline__ bf16x8 pg_val(const pg_trf& f) {
+  const gu32x4 q = {f.lo[0], f.lo[1], f.hi[0], f.hi[1]};
+  return __builtin_bit_cast(bf16x8, q);
+}
+__device__ __forceinline__ void pg_behind_wait(bf16x8 (&)[4]) {}   // (compiler-counted reads: nothing to do)
+__device__ __forceinline__ void pg_behind_wait(pg_trf (&f)[4]) {
+  asm volatile("" : "+v"(f[0].lo), "+v"(f[0].hi), "+v"(f[1].lo), "+v"(f[1].hi), "+v"(f[2].lo), "+v"(f[2].hi), "+v"(f[3].lo), "+v"(f[3].hi));
+}
+// f(pg_ic<0>{}) .. f(pg_ic<3>{}): an unrolled loop whose index is a compile-time constant (the asm read's offset is an immediate)
+template <class F>
+__device__ __forceinline__ void pg_for4(F&& f) { f(pg_ic<0>{}); f(pg_ic<1>{}); f(pg_ic<2>{}); f(pg_ic<3>{}); }
 
 #ifdef LFI_PG_EXP_16
 // timing-only experiment (garbage results): the same operand registers through two v_mfma_f32_16x16x32_bf16 (same FLOP, same
@@ -247,6 +306,11 @@ __global__ __launch_bounds__(512, 4) void gemm_planes_kernel(GemmArgs g) {
 // AT / BT: that operand in transposed use (a pair of k-tiles is then ONE 32-row block of its buffer; DMA row swap and
 // ds_read_b64_tr_b16 as in gemm_planes16t_kernel below) - the three-product form of the weight-gradient and feature-gradient
 // products (engine_backward_products = 3: small batches, three_products_everywhere).
+// These AT / BT forms KEEP the builtin transposing read and with it the compiler's vmcnt(0) in every half-phase (see pg_frag_tr_asm
+// above; the step does not run them). Three products rotate the a_lo / a_hi register sets from pair to pair, the allocation sits at
+// 128 VGPRs, and of the four forms built with the asm reads two spilled more than with the builtin (tools/kernel_resources.py:
+// <false, true, .., 2, 4> 0 -> 24 bytes of scratch per lane, <true, true, .., 2, 4> 0 -> 28; <true, false> went 52 / 60 -> 0):
+// profiles/pgemm_tr_reads.md.
 template <bool AT, bool BT, bool COLP, int WMT, int WNT, int TRP = 0>
 __global__ __launch_bounds__(512, 4) void gemm_planes16_kernel(GemmArgs g) {
   constexpr int NA = 4 * WMT;   // A blocks per sub-slot (2 WMT mn tiles x 2 k-tiles); B: 4 WNT
@@ -410,8 +474,10 @@ __global__ __launch_bounds__(512, 4) void gemm_planes16_kernel(GemmArgs g) {
 // source address); lane 16 g + 4 q + p of ds_read_b64_tr_b16 addresses k row 16 (g & 1) + 8 (g >> 1) + q (then + 4), columns 4 p .. + 3:
 // the same k assignment as the row-use read (k-tile g & 1, chunk g >> 1), and the two 16-lane groups of a 32-lane half land in
 // opposite halves of the 256-byte bank row.
-template <bool AT, bool COLP, int WMT, int WNT, int TRP = 0>
-__global__ __launch_bounds__(512, 4) void gemm_planes16t_kernel(GemmArgs g) {
+// TRA: the transposed fragments by inline assembly (pg_frag_tr_asm; gemm_planes16t_kernel, the default) or by the builtin
+// (gemm_planes16t_builtin_kernel: LFI_PGEMM_TR_ASM=0, the loop as it was - with the compiler's vmcnt(0) in every half-phase).
+template <bool AT, bool COLP, int WMT, int WNT, int TRP, bool TRA>
+__device__ __forceinline__ void gemm_planes16t_body(const GemmArgs& g) {
   constexpr int NA = 4 * WMT, NY = WNT / 2;   // A blocks per sub-slot; DMA pieces per wave of the lo sub-slot (its 4 WNT B blocks)
   static_assert(WMT * WNT == 8 && NA + 4 * WNT == 24, "eight waves, 24 blocks per slot");
   const int tid = threadIdx.x;
@@ -522,11 +588,22 @@ __global__ __launch_bounds__(512, 4) void gemm_planes16t_kernel(GemmArgs g) {
   };
   const char* ldsA = lds + (wm * 4) * 1024;
   const char* ldsB = lds + NA * 1024 + (wn * 4) * 1024;
-  auto fragA = [&](int slot, int i) -> bf16x8 {
-    if constexpr (AT) return pg_frag<true>(ldsA + slot * QSLOT + i * 1024, 0, toff);
+  // TRA: a transposed fragment is read by inline assembly (pg_frag_tr_asm: no vmcnt(0) in front of it, and NOT counted on lgkmcnt
+  // by the compiler: see the waits below), and A's by-row fragment beside it as well (pg_frag_row_asm). !TRA: builtin and C++ load
+  using FragA = std::conditional_t<TRA, std::conditional_t<AT, pg_trf, pg_rf>, bf16x8>;
+  using FragB = std::conditional_t<TRA, pg_trf, bf16x8>;
+  auto fragA = [&](auto S, auto I) -> FragA {
+    constexpr int slot = decltype(S)::value, i = decltype(I)::value;
+    if constexpr (AT && TRA) return pg_frag_tr_asm<slot * QSLOT + i * 1024>(pg_lds_addr(ldsA) + toff, pg_lds_addr(ldsA) + (toff ^ 128));
+    else if constexpr (AT) return pg_frag<true>(ldsA + slot * QSLOT + i * 1024, 0, toff);
+    else if constexpr (TRA) return pg_frag_row_asm<slot * QSLOT + (i >> 1) * 2048 + (i & 1) * 512>(pg_lds_addr(ldsA) + fo);
     else return *reinterpret_cast<const bf16x8*>(ldsA + slot * QSLOT + (i >> 1) * 2048 + (i & 1) * 512 + fo);
   };
-  auto fragB = [&](int slot, int i) -> bf16x8 { return pg_frag<true>(ldsB + slot * QSLOT + i * 1024, 0, toff); };
+  auto fragB = [&](auto S, auto I) -> FragB {
+    constexpr int slot = decltype(S)::value, i = decltype(I)::value;
+    if constexpr (TRA) return pg_frag_tr_asm<slot * QSLOT + i * 1024>(pg_lds_addr(ldsB) + toff, pg_lds_addr(ldsB) + (toff ^ 128));
+    else return pg_frag<true>(ldsB + slot * QSLOT + i * 1024, 0, toff);
+  };
 
   f32x4 acc[4][4];
   gu32x2 sw = {0u, 0u};   // TRP >= 4 with sign words: this lane's word of the wave's patch (the act-2 mask), fetched ahead of the main loop
@@ -538,13 +615,24 @@ __global__ __launch_bounds__(512, 4) void gemm_planes16t_kernel(GemmArgs g) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
+  // The counted waits, from what ONE wave has in flight. dmaX is 3 pieces, dmaY is NY (2 on 128 x 256 tiles, 1 on 256 x 128); a
+  // wave's pieces land in issue order; with the asm reads (TRA) these waits are the only ones in the loop, so they are what binds:
+  //   fill:          [sign word] X0 (3), Y0 (NY), X1 (3) issued -> vmcnt(NY + 3) = 5 / 4: X0 (and the sign word) landed, Y0 and X1 in flight
+  //   prologue:      X0 read                                     -> vmcnt(3): Y0 landed, X1 (3) in flight
+  //   phase 2 p:     Y(p+1) issued (NY), Y(p) read               -> vmcnt(NY) = 2 / 1: X(p+1) landed, Y(p+1) in flight
+  //   phase 2 p + 1: X(p+2) issued (3), X(p+1) read              -> vmcnt(3): Y(p+1) landed, X(p+2) in flight
+  // Each is followed by lgkmcnt(0) and the barrier: behind it EVERY wave's pieces of the sub-slot the next phase reads have landed, and
+  // every fragment read of the closing phase (compiler-counted or not) has returned - a fragment is used one phase after it is read.
+  // The counts assume that nothing else of this wave rides the VM counter inside the loop: no scratch access (tools/main_loop_waits.py;
+  // tests/test_pgemm_main_loop_asm.py holds the step's instantiations to that).
   if (npair > 0) {
-    bf16x8 ah[4], bh[4];
+    FragA ah[4];
+    FragB bh[4];
     if (!filled) {
       // (the sign word first: it is the OLDEST load in flight, so every counted wait below that covers a DMA piece covers it too)
       if constexpr (TRP >= 4) sw = gemm_sign_word_load(g, m0, n0, wm, wn, lanev, batch);
       dmaX(0, 0); dmaY(0, 1); dmaX(1, 2);
-      if (NY == 2) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+      if (NY == 2) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");   // NY + 3
       else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     } else {
       // Prefetched fill: in issue order this wave has in flight [sign word][dmaX(0, 0): 3][dmaY(0, 1): NY][dmaX(1, 2): 3] and then the
@@ -555,45 +643,46 @@ __global__ __launch_bounds__(512, 4) void gemm_planes16t_kernel(GemmArgs g) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { ah[i] = fragA(0, i); bh[i] = fragB(0, i); }
-    asm volatile("s_waitcnt vmcnt(3)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+    pg_for4([&](auto I) { constexpr int i = decltype(I)::value; ah[i] = fragA(pg_ic<0>{}, I); bh[i] = fragB(pg_ic<0>{}, I); });
+    asm volatile("s_waitcnt vmcnt(3)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");   // lgkmcnt(0): the prologue's reads of ah, bh
+    pg_behind_wait(ah); pg_behind_wait(bh);
     __builtin_amdgcn_s_barrier();
 
     // one pair; SX = ring slot of its sub-slot 2 p (2 p + 1: the next slot; the next pair's first: the one after)
     auto pair = [&](auto SX, int p) {
       constexpr int sx = decltype(SX)::value, sy = (sx + 1) % 3, sn = (sx + 2) % 3;
-      bf16x8 bl[4], nah[4], nbh[4];
+      FragA nah[4];
+      FragB bl[4], nbh[4];
       // ---- phase 2 p: a_hi b_hi
       dmaY(p + 1, sx);
       __builtin_amdgcn_sched_barrier(0);
+      pg_for4([&](auto I) {
+        constexpr int i = decltype(I)::value;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = PG_MFMA16X(ah[i], bh[j], acc[i][j]);
+        for (int j = 0; j < 4; ++j) acc[i][j] = PG_MFMA16X(pg_val(ah[i]), pg_val(bh[j]), acc[i][j]);
         __builtin_amdgcn_sched_barrier(0);
-        bl[i] = fragB(sy, i);
+        bl[i] = fragB(pg_ic<sy>{}, I);
         __builtin_amdgcn_sched_barrier(0);
-      }
+      });
+      // vmcnt(NY): see the table above. lgkmcnt(0): this phase's reads of bl (used in phase 2 p + 1)
       if (NY == 2) asm volatile("s_waitcnt vmcnt(2)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(1)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+      pg_behind_wait(bl);
       __builtin_amdgcn_s_barrier();
       // ---- phase 2 p + 1: a_hi b_lo
       dmaX(p + 2, sy);
       __builtin_amdgcn_sched_barrier(0);
+      pg_for4([&](auto I) {
+        constexpr int i = decltype(I)::value;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = PG_MFMA16X(ah[i], bl[j], acc[i][j]);
+        for (int j = 0; j < 4; ++j) acc[i][j] = PG_MFMA16X(pg_val(ah[i]), pg_val(bl[j]), acc[i][j]);
         __builtin_amdgcn_sched_barrier(0);
-        if (i == 0) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) nbh[q] = fragB(sn, q);
-        }
-        nah[i] = fragA(sn, i);
+        if constexpr (i == 0) pg_for4([&](auto Q) { nbh[decltype(Q)::value] = fragB(pg_ic<sn>{}, Q); });
+        nah[i] = fragA(pg_ic<sn>{}, I);
         __builtin_amdgcn_sched_barrier(0);
-      }
-      asm volatile("s_waitcnt vmcnt(3)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+      });
+      asm volatile("s_waitcnt vmcnt(3)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");   // lgkmcnt(0): this phase's reads of nbh, nah (used in the next pair)
+      pg_behind_wait(nbh); pg_behind_wait(nah);
       __builtin_amdgcn_s_barrier();
 #pragma unroll
       for (int i = 0; i < 4; ++i) { ah[i] = nah[i]; bh[i] = nbh[i]; }
@@ -641,6 +730,17 @@ __global__ __launch_bounds__(512, 4) void gemm_planes16t_kernel(GemmArgs g) {
     break;
   }
   }
+}
+
+template <bool AT, bool COLP, int WMT, int WNT, int TRP = 0>
+__global__ __launch_bounds__(512, 4) void gemm_planes16t_kernel(GemmArgs g) {
+  gemm_planes16t_body<AT, COLP, WMT, WNT, TRP, true>(g);
+}
+// LFI_PGEMM_TR_ASM=0: the same products with the builtin reads (every form but the persistent walk, which has the asm reads only)
+template <bool AT, bool COLP, int WMT, int WNT, int TRP = 0>
+__global__ __launch_bounds__(512, 4) void gemm_planes16t_builtin_kernel(GemmArgs g) {
+  static_assert(TRP != 5, "the persistent walk is not built with the builtin reads");
+  gemm_planes16t_body<AT, COLP, WMT, WNT, TRP, false>(g);
 }
 
 // fp32 (rows x cols, row pitch ldx) -> bf16 hi / lo planes, zero padded to rows_pad x 16 nkt: block ((rt * nkt + kt) * 2 + plane),
@@ -758,11 +858,15 @@ int launch_planes(const GemmArgs& a, int at, int bt, dim3 grid, size_t lds, hipS
     attr = true;
   }
   if (bt && planes16t_ok(a)) {
+    // LFI_PGEMM_TR_ASM=0: the transposed fragments by the builtin again (read per call, like LFI_PGEMM_16T: the tests compare the two)
+    const bool tra = lfi_env_on("LFI_PGEMM_TR_ASM");
     static bool attr16t = false;
     if (!attr16t) {
       hipError_t e1 = hipFuncSetAttribute((const void*)gemm_planes16t_kernel<false, COLP, WMT, WNT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       hipError_t e2 = hipFuncSetAttribute((const void*)gemm_planes16t_kernel<true, COLP, WMT, WNT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e1 != hipSuccess || e2 != hipSuccess) {
+      hipError_t e3 = hipFuncSetAttribute((const void*)gemm_planes16t_builtin_kernel<false, COLP, WMT, WNT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipError_t e4 = hipFuncSetAttribute((const void*)gemm_planes16t_builtin_kernel<true, COLP, WMT, WNT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
         lfi_set_error("lfi_gemm_planes: cannot reserve %zu bytes of LDS", lds);
         return LFI_ERR_LAUNCH;
       }
@@ -772,6 +876,7 @@ int launch_planes(const GemmArgs& a, int at, int bt, dim3 grid, size_t lds, hipS
       static bool attr4 = false;
       if (!attr4) {
         if (hipFuncSetAttribute((const void*)gemm_planes16t_kernel<false, true, 2, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+            hipFuncSetAttribute((const void*)gemm_planes16t_builtin_kernel<false, true, 2, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
             hipFuncSetAttribute((const void*)gemm_planes16t_kernel<false, true, 2, 4, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
           lfi_set_error("lfi_gemm_planes: cannot reserve %zu bytes of LDS", lds);
           return LFI_ERR_LAUNCH;
@@ -784,9 +889,13 @@ int launch_planes(const GemmArgs& a, int at, int bt, dim3 grid, size_t lds, hipS
         GemmArgs ap = a;
         ap.pbatch = (int)grid.y;
         hipLaunchKernelGGL((gemm_planes16t_kernel<false, true, 2, 4, 5>), dim3((unsigned)wgs), dim3(512), lds, st, ap);
-      } else hipLaunchKernelGGL((gemm_planes16t_kernel<false, true, 2, 4, 4>), grid, dim3(512), lds, st, a);
-    } else if (at) hipLaunchKernelGGL((gemm_planes16t_kernel<true, COLP, WMT, WNT>), grid, dim3(512), lds, st, a);
-    else hipLaunchKernelGGL((gemm_planes16t_kernel<false, COLP, WMT, WNT>), grid, dim3(512), lds, st, a);
+      } else if (tra) hipLaunchKernelGGL((gemm_planes16t_kernel<false, true, 2, 4, 4>), grid, dim3(512), lds, st, a);
+      else hipLaunchKernelGGL((gemm_planes16t_builtin_kernel<false, true, 2, 4, 4>), grid, dim3(512), lds, st, a);
+    } else if (tra) {
+      if (at) hipLaunchKernelGGL((gemm_planes16t_kernel<true, COLP, WMT, WNT>), grid, dim3(512), lds, st, a);
+      else hipLaunchKernelGGL((gemm_planes16t_kernel<false, COLP, WMT, WNT>), grid, dim3(512), lds, st, a);
+    } else if (at) hipLaunchKernelGGL((gemm_planes16t_builtin_kernel<true, COLP, WMT, WNT>), grid, dim3(512), lds, st, a);
+    else hipLaunchKernelGGL((gemm_planes16t_builtin_kernel<false, COLP, WMT, WNT>), grid, dim3(512), lds, st, a);
   } else if (!at && !bt && planes16_ok(a) && !COLP && planes16_direct_mode(a)) {
     static bool attrd16 = false;
     if (!attrd16) {
