@@ -742,6 +742,13 @@ int lfi_sgd_clip_step(float* p, const float* g, float* buf, long n, const double
 int lfi_rmsprop_clip_step(float* p, const float* g, float* sq, float* buf, float* gavg, long n, const double* sumsq, float clip,
                           float gmul, float lr, float alpha, float eps, float weight_decay, float momentum, void* stream);
 
+/* Running average of the flat parameter buffer (Polyak / EMA), one launch behind whichever optimiser step ran, eager or inside a
+ * captured step: ema[i] += a * (p[i] - ema[i]) in fp32 with a = (float)(1.0 - (double)decay), the lerp of
+ * torch.optim.swa_utils.get_ema_multi_avg_fn(decay). 0 <= decay < 1 (NaN refused); the two ranges must not overlap; either pointer may
+ * sit at any 4-byte offset (16-byte loads and stores when both are 16-byte aligned); n == 0 succeeds without a launch. The first
+ * average is a copy of the parameters and is the caller's to make (GlowEngine.ema_update). */
+int lfi_ema_update(float* ema, const float* p, long n, float decay, void* stream);
+
 /* The training step as a captured hipGraph (lets_face_it_amd/glow/lets_face_it_glow.py, fused_training_step): what changes from
  * one optimiser step to the next - the dropout-mask key, Adam's bias-corrected step size - lives in a 32-byte device block
  * (u64 seed, u64 mask offset, f32 step_size = lr / (1 - beta1^t), f32 1 / sqrt(1 - beta2^t)) that lfi_set_step_params fills with

@@ -207,6 +207,7 @@ def lib():
         "lfi_adam_clip_step_ex": (i, [vp, vp, vp, vp, vp, l, vp, f, f, f, f, f, f, f, i, vp, vp]),
         "lfi_sgd_clip_step": (i, [vp, vp, vp, l, vp, f, f, f, f, f, f, i, i, vp]),
         "lfi_rmsprop_clip_step": (i, [vp, vp, vp, vp, vp, l, vp, f, f, f, f, f, f, f, vp]),
+        "lfi_ema_update": (i, [vp, vp, l, f, vp]),
         "lfi_actnorm_forward": (i, [vp, i, i, vp, vp, i, vp, vp, vp]),
         "lfi_invconv_work_floats": (l, [i]),
         "lfi_invconv_weights": (i, [i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]),
@@ -243,7 +244,7 @@ EXPORTS = [
     "lfi_flow_sample_cand_seq_work_floats", "lfi_flow_sample_cand_seq", "lfi_stream_cand_seq_in", "lfi_stream_commit_cand_seq",
     "lfi_flow_step_rows_work_floats", "lfi_flow_step_rows_from", "lfi_absmax_f32", "lfi_stream_advance", "lfi_stream_advance_rows", "lfi_stream_reset_rows", "lfi_stream_row_floats",
     "lfi_stream_save_rows", "lfi_stream_load_rows", "lfi_stream_create_partial", "lfi_stream_destroy", "lfi_grad_sumsq", "lfi_adam_clip_step", "lfi_adam_clip_step_ex",
-    "lfi_sgd_clip_step", "lfi_rmsprop_clip_step", "lfi_set_step_params", "lfi_dropout_masks_dev", "lfi_adam_clip_step_dev", "lfi_selftest_mfma", "lfi_debug_set_stamps",
+    "lfi_sgd_clip_step", "lfi_rmsprop_clip_step", "lfi_ema_update", "lfi_set_step_params", "lfi_dropout_masks_dev", "lfi_adam_clip_step_dev", "lfi_selftest_mfma", "lfi_debug_set_stamps",
     "lfi_gather_sequences", "lfi_jerk_mean", "lfi_actnorm_forward", "lfi_invconv_work_floats", "lfi_invconv_weights",
 ]
 

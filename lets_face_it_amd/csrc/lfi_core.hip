@@ -350,7 +350,49 @@ __global__ __launch_bounds__(256) void rmsprop_clip_kernel(float* __restrict__ p
     }
   }
 }
+
+// Running average of the flat parameter buffer (Polyak / EMA): ema += a (p - ema), a = 1 - decay, the lerp of
+// torch.optim.swa_utils.get_ema_multi_avg_fn. Two reads, one write per element, nothing else: VEC moves 16 bytes per lane (both
+// pointers 16-byte aligned, checked by the caller) and leaves the n % 4 tail to the first lanes of the grid as single floats.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float a) {
+  const long t0 = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+  if (VEC) {
+    const long n4 = n >> 2;
+    float4* __restrict__ e4 = reinterpret_cast<float4*>(ema);
+    const float4* __restrict__ p4 = reinterpret_cast<const float4*>(p);
+    for (long i = t0; i < n4; i += stride) {
+      float4 e = e4[i];
+      const float4 q = p4[i];
+      e.x += a * (q.x - e.x);
+      e.y += a * (q.y - e.y);
+      e.z += a * (q.z - e.z);
+      e.w += a * (q.w - e.w);
+      e4[i] = e;
+    }
+    const long i = (n4 << 2) + t0;   // tail: at most three floats
+    if (i < n) ema[i] += a * (p[i] - ema[i]);
+  } else {
+    for (long i = t0; i < n; i += stride) ema[i] += a * (p[i] - ema[i]);
+  }
+}
 }  // namespace
+
+extern "C" int lfi_ema_update(float* ema, const float* p, long n, float decay, void* stream) {
+  LFI_REQUIRE(n >= 0, "lfi_ema_update: n < 0");
+  LFI_REQUIRE(decay >= 0.0f && decay < 1.0f, "lfi_ema_update: decay must lie in [0, 1) (NaN is refused)");
+  if (n == 0) return LFI_OK;
+  LFI_REQUIRE(ema && p, "lfi_ema_update: null pointer");
+  const uintptr_t e0 = (uintptr_t)ema, p0 = (uintptr_t)p, bytes = (uintptr_t)n * sizeof(float);
+  LFI_REQUIRE(e0 + bytes <= p0 || p0 + bytes <= e0, "lfi_ema_update: the average and the parameters overlap");
+  const float a = (float)(1.0 - (double)decay);
+  const bool vec = ((e0 | p0) & 15) == 0;
+  const int blocks = (int)min(2048L, (long)lfi_cdiv(vec ? (n + 3) / 4 : n, 256));
+  if (vec) hipLaunchKernelGGL(ema_update_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ema, p, n, a);
+  else hipLaunchKernelGGL(ema_update_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ema, p, n, a);
+  LFI_LAUNCH_CHECK("lfi_ema_update");
+  return LFI_OK;
+}
 
 extern "C" int lfi_sgd_clip_step(float* p, const float* g, float* buf, long n, const double* sumsq, float clip, float gmul, float lr,
                                  float momentum, float dampening, float weight_decay, int nesterov, int step_count, void* stream) {

@@ -207,6 +207,11 @@ class GlowEngine:
         self.adam_m = None
         self.adam_v = None
         self.step_count = 0
+        # running average of `params` (Polyak / EMA, ema_update): n_params floats, None while off; `ema_updates` counts its updates,
+        # the first of which is a copy. While swap_ema() holds the average in `params` every training entry point raises.
+        self.ema = None
+        self.ema_updates = 0
+        self._ema_swapped = False
         # bumped by every optimiser step, parameter load and data-dependent ActNorm init: a streaming sampling session (SampleStream)
         # records it at open and refuses to step once it has moved (its prepared weights are those of the open)
         self.param_version = 0
@@ -950,6 +955,7 @@ class GlowEngine:
 
         after_flow: optional callable, invoked once every gradient of the flow block (self.grads[self.flow_offset:]) has
         been enqueued and before the window encoders' BPTT starts (the trainer launches that bucket's all-reduce there)."""
+        self._refuse_while_swapped("GlowEngine.backward")
         ctx = self._last
         if ctx is None or not ctx.with_stash:
             raise _lib.LfiError("backward() needs a preceding forward(with_stash=True)")
@@ -1305,6 +1311,7 @@ class GlowEngine:
         hyper_dev: device pointer to (step_size, 1 / sqrt(1 - beta2^t)) - a captured step; the caller keeps step_count.
         weight_decay / amsgrad: torch.optim.Adam's (the reference forwards Optim["args"]["adam"] verbatim); the running maximum of
         the second moment lives in `opt_aux`."""
+        self._refuse_while_swapped("GlowEngine.optimizer_step")
         self._claim_optimizer("adam")
         self.bump_param_version()
         if self.adam_m is None:
@@ -1339,6 +1346,7 @@ class GlowEngine:
     def optimizer_step_sgd(self, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, clip=0.0, gmul=1.0):
         """clip_grad_norm_(clip) + torch.optim.SGD on the flat buffers (lets_face_it_glow.py:61-72 with Optim.name = "sgd";
         final_model.yaml:98-99: momentum 0.9). The momentum buffer lives in `adam_m` (one optimiser per model)."""
+        self._refuse_while_swapped("GlowEngine.optimizer_step_sgd")
         self._claim_optimizer("sgd")
         self.bump_param_version()
         # torch.optim.SGD's "first step" (buf = g) is "no momentum buffer yet", not "step 1": a reference checkpoint carries a
@@ -1362,6 +1370,7 @@ class GlowEngine:
     def optimizer_step_rmsprop(self, lr, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, centered=False, clip=0.0, gmul=1.0):
         """clip_grad_norm_(clip) + torch.optim.RMSprop on the flat buffers (Optim.name = "rmsprop"; final_model.yaml:96-97: eps 1e-8).
         Square average in `adam_v`, momentum buffer in `adam_m`, the centered variant's gradient average in `opt_aux`."""
+        self._refuse_while_swapped("GlowEngine.optimizer_step_rmsprop")
         self._claim_optimizer("rmsprop")
         self.bump_param_version()
         if self.adam_v is None:
@@ -1380,11 +1389,55 @@ class GlowEngine:
                                            self.n_params, self.sumsq.data_ptr(), float(clip or 0.0), gmul, lr, float(alpha), float(eps),
                                            float(weight_decay), float(momentum), st), "lfi_rmsprop_clip_step")
 
+    # ------------------------------------------------------------------ weight averaging (Polyak / EMA of the flat parameter buffer)
+    def _refuse_while_swapped(self, what):
+        if self._ema_swapped:
+            raise RuntimeError("%s while the averaged weights are swapped in (swap_ema / SeqGlow.ema_weights): training "
+                               "on the average is always a bug - leave the context first" % what)
+
+    def _launch_ema_update(self, decay):
+        """The launch alone, uncounted: ema_update, and the node a captured training step records behind its optimiser."""
+        check(self.L.lfi_ema_update(self.ema.data_ptr(), self.params.data_ptr(), self.n_params, float(decay), _stream()), "lfi_ema_update")
+
+    @translate_oom
+    def ema_update(self, decay):
+        """One update of the running average behind an optimiser step: ema += (1 - decay) (params - ema), one launch on the current
+        stream (lfi_ema_update; the lerp of torch.optim.swa_utils.get_ema_multi_avg_fn). The first update allocates `ema` as a copy of
+        `params`, as AveragedModel does while n_averaged == 0 - an allocation, so never inside a stream capture: whoever captures
+        makes sure `ema` exists first. A loop that drives its own torch optimiser calls this after optimizer.step()."""
+        self._refuse_while_swapped("GlowEngine.ema_update")
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:      # (NaN fails both comparisons)
+            raise ValueError("ema_update: decay must lie in [0, 1), got %r" % decay)
+        if self.ema is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ema_update: the first update allocates the average; it cannot run inside a stream capture")
+            self.ema = self.params.detach().clone()
+        else:
+            self._launch_ema_update(decay)
+        self.ema_updates += 1
+
+    def swap_ema(self):
+        """Exchange the contents of `params` and `ema` in place (every module tensor, cached pointer and captured graph keeps its
+        address) and move the parameter version: `prep`, folded weights, parameter planes and open streaming sessions see a parameter
+        change exactly as after an optimiser step. Not on the step path: torch copies through one temporary. While the average sits in
+        `params` the optimiser steps, ema_update and backward raise; the flag is part of no checkpoint."""
+        if self.ema is None:
+            raise RuntimeError("swap_ema: no averaged weights exist (Optim.ema_decay unset, or no update has run yet)")
+        tmp = self.params.clone()
+        self.params.copy_(self.ema)
+        self.ema.copy_(tmp)
+        self._ema_swapped = not self._ema_swapped
+        self.bump_param_version()
+
     def optimizer_state(self):
         """The optimiser's state buffers and step count (checkpoints, engine re-binds). Adam: first / second moments, `opt_aux` =
         amsgrad's running maximum; SGD: `adam_m` = momentum buffer; RMSprop: `adam_v` = square average, `adam_m` = momentum buffer,
         `opt_aux` = centered gradient average. `optimizer` names whose state this is (None before the first step) - another
-        optimiser refuses to step it. Buffers are None before the first step."""
+        optimiser refuses to step it. Buffers are None before the first step. `ema` / `ema_updates`: the running average of the
+        parameters and its update count (None / 0 while off)."""
+        if self._ema_swapped:
+            raise RuntimeError("optimizer_state while the averaged weights are swapped in: `ema` holds the raw parameters now")
         aux = self.__dict__.get("opt_aux")
         return {"step_count": int(self.step_count),
                 "optimizer": self.__dict__.get("_opt_name"),
@@ -1394,7 +1447,9 @@ class GlowEngine:
                 # of steps 1..k
                 "mask_calls": int(self._mask_calls),
                 "adam_m": None if self.adam_m is None else self.adam_m.detach().clone(),
-                "adam_v": None if self.adam_v is None else self.adam_v.detach().clone()}
+                "adam_v": None if self.adam_v is None else self.adam_v.detach().clone(),
+                "ema": None if self.ema is None else self.ema.detach().clone(),
+                "ema_updates": int(self.ema_updates)}
 
     def load_optimizer_state(self, state):
         self.step_count = int(state.get("step_count", 0))
@@ -1402,7 +1457,9 @@ class GlowEngine:
         self._opt_name = state.get("optimizer")     # None (older checkpoints, fresh state): the first step claims it
         # (checkpoints from before round 6 carry no flag: a momentum buffer that exists has been written)
         self._momentum_inited = bool(state.get("momentum_inited", state.get("adam_m") is not None))
-        for name in ("adam_m", "adam_v", "opt_aux"):
+        # (a state without the average - older and reference checkpoints - leaves it unset: it restarts as a copy at the next update)
+        self.ema_updates = int(state.get("ema_updates", 0)) if state.get("ema") is not None else 0
+        for name in ("adam_m", "adam_v", "opt_aux", "ema"):
             t = state.get(name)
             if t is None:
                 setattr(self, name, None)

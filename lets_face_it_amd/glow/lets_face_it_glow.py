@@ -24,10 +24,26 @@ def _recorded_event():
     return ev
 
 
+def ema_decay_of(hparams):
+    """Optim["ema_decay"]: the decay of the running average of the weights (Polyak / EMA), a float in (0, 1); absent, None or 0 =
+    off (returns None). Anything else raises ValueError."""
+    value = (getattr(hparams, "Optim", None) or {}).get("ema_decay")
+    if value is None or (isinstance(value, (int, float)) and not isinstance(value, bool) and value == 0):
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 < float(value) < 1.0:
+        raise ValueError("Optim.ema_decay must be a float in (0, 1), or absent / None / 0 for no weight averaging; got %r" % (value,))
+    return float(value)
+
+
 class LetsFaceItGlow(nn.Module):
     def __init__(self, hparams, dataset_root=None, test=None):
         super().__init__()
         test_params(hparams)
+        # Weight averaging: after every optimiser step of fused_training_step the engine's `ema` buffer moves towards the parameters
+        # by (1 - ema_decay) (first step: a copy). Sampling and validation reach it through seq_glow.ema_weights(), checkpoints
+        # through ema_state_dict(). The plain training_step + external optimiser path gets no automatic update: such a loop calls
+        # model.seq_glow.engine.ema_update(decay) after its own optimizer.step().
+        self.ema_decay = ema_decay_of(hparams)
         if dataset_root is not None:
             hparams.dataset_root = dataset_root
         if test is not None:
@@ -137,7 +153,7 @@ class LetsFaceItGlow(nn.Module):
         cur.wait_stream(own)
 
     def _graph_key(self, batch, negative, eng):
-        return (bool(negative), eng.precision, str(eng.backward_products), tuple(sorted(eng.pass_skip.items())),
+        return (bool(negative), eng.precision, str(eng.backward_products), tuple(sorted(eng.pass_skip.items())), self.ema_decay,
                 tuple((k, tuple(v.shape)) for k, v in sorted(batch.items())))
 
     def _graph_allowed(self, sg, eng, world_size, allreduce):
@@ -228,6 +244,8 @@ class LetsFaceItGlow(nn.Module):
                            hyper_dev=st["params"].data_ptr() + 16, weight_decay=float(a.get("weight_decay", 0) or 0),
                            amsgrad=bool(a.get("amsgrad", False)))
         eng.step_count += 1
+        if self.ema_decay:
+            eng.ema_update(self.ema_decay)
         if st["dropout"]:
             eng._mask_calls += 1
         sg._fwd_counter += 1
@@ -251,6 +269,8 @@ class LetsFaceItGlow(nn.Module):
         a = self.hparams.Optim["args"]["adam"]
         clip = float(getattr(self.hparams, "gradient_clip_val", 0) or 0)
         sign = -0.1 if negative else 1.0
+        # (with weight averaging on, the average exists by now: its first value is an allocation + copy, which cannot be captured, and
+        # fused_training_step keeps a step that has to make it on the eager path)
         torch.cuda.synchronize(dev)
         with torch.cuda.graph(st["graph"]):
             masks = eng.draw_masks(B, N, 0, key_dev=st["params"]) if eng.has_dropout() else None
@@ -260,8 +280,19 @@ class LetsFaceItGlow(nn.Module):
             eng.optimizer_step(0.0, float(a["betas"][0]), float(a["betas"][1]), float(a["eps"]), clip=clip, gmul=1.0,
                                hyper_dev=st["params"].data_ptr() + 16, weight_decay=float(a.get("weight_decay", 0) or 0),
                                amsgrad=bool(a.get("amsgrad", False)))
+            if self.ema_decay:
+                # the decay is a constant of the run: a plain kernel argument inside the graph. Capturing executes nothing: the
+                # launch is recorded here, each replay counts its update (_replay_step)
+                eng._launch_ema_update(self.ema_decay)
         st["dropout"] = masks is not None
+        st["ema"] = bool(self.ema_decay)
+        # what the optimiser and averaging nodes write, by address: kept alive, and compared before every replay (fused_training_step)
+        st["state_bufs"] = self._step_state_bufs(eng)
         return st
+
+    @staticmethod
+    def _step_state_bufs(eng):
+        return (eng.adam_m, eng.adam_v, eng.__dict__.get("opt_aux"), eng.ema)
 
     def _replay_step(self, st, batch, lr, negative, eng):
         from .. import _lib
@@ -275,6 +306,8 @@ class LetsFaceItGlow(nn.Module):
                                              torch.cuda.current_stream().cuda_stream), "lfi_set_step_params")
         st["graph"].replay()
         eng.step_count += 1
+        if st["ema"]:
+            eng.ema_updates += 1
         eng.bump_param_version()
         if st["dropout"]:
             eng._mask_calls += 1
@@ -295,6 +328,10 @@ class LetsFaceItGlow(nn.Module):
         the torch.distributed work handle when async_op, or None.
         """
         sg = self.seq_glow
+        if sg.engine is not None:
+            # inside seq_glow.ema_weights(): refused here, before anything moves - a replayed step graph would otherwise run Adam on the
+            # average without passing any of the engine's own checks (they ran when the graph was captured)
+            sg.engine._refuse_while_swapped("LetsFaceItGlow.fused_training_step")
         negative = self._negative_branch()
         if negative:
             batch = derange_batch(batch, self.missmatched_modalities)
@@ -302,7 +339,8 @@ class LetsFaceItGlow(nn.Module):
         eng = sg._ensure_engine(x.device)
         B, T = x.shape[0], x.shape[1]
         N = T - sg.spec.start
-        if self._graph_allowed(sg, eng, world_size, allreduce):
+        # a step that has to MAKE the average (its first value: an allocation + copy, counted as update 1) stays eager
+        if self._graph_allowed(sg, eng, world_size, allreduce) and not (self.ema_decay and eng.ema is None):
             graphs = self.__dict__.setdefault("_step_graphs", {})
             if graphs.get("engine") is not eng:      # a re-bound engine (.to() / .float()): its buffers are gone
                 graphs.clear()
@@ -313,6 +351,12 @@ class LetsFaceItGlow(nn.Module):
             if dp:
                 key = ("dp",) + key
             st = graphs.get(key)
+            if st is not None and "state_bufs" in st and any(a is not b for a, b in zip(st["state_bufs"], self._step_state_bufs(eng))):
+                # the graph holds the optimiser's state buffers and the average by address: a state load since the capture
+                # (load_optimizer_state) replaced them, and a replay would go on reading and writing the old ones
+                st = None
+                for k in [k for k, v in graphs.items() if isinstance(v, dict)]:
+                    del graphs[k]
             if st is None and graphs.get(("seen",) + key, 0) >= 2 and not graphs.get("broken"):
                 try:
                     st = graphs[key] = capture(key, batch, negative, eng)
@@ -395,6 +439,8 @@ class LetsFaceItGlow(nn.Module):
         else:
             eng.backward(sign / nll.numel())
         self._fused_optimizer_step(eng, lr, 1.0 / world_size)
+        if self.ema_decay:
+            eng.ema_update(self.ema_decay)      # (data parallelism: every rank averages identical parameters - no collective)
         self.global_step += 1
         self.log("train_loss", loss)
         return loss.detach()
@@ -442,16 +488,30 @@ class LetsFaceItGlow(nn.Module):
             self.parameters(), lr=self.hparams.lr, **self.hparams.Optim["args"][name])
         return [optimizer], get_scheduler(self.hparams.Optim["Schedule"], optimizer)
 
+    def ema_state_dict(self):
+        """state_dict() with every parameter of the flat buffer replaced by its averaged value (seq_glow.ema_state_dict); buffers -
+        invconv.p, sign_s, last_missmatched_nll - as they are. Same keys as state_dict(): what load_state_dict takes."""
+        out = {k: v.detach().clone() for k, v in self.state_dict().items()}
+        for k, v in self.seq_glow.ema_state_dict().items():
+            out["seq_glow." + k] = v
+        return out
+
     @classmethod
-    def load_from_checkpoint(cls, path, dataset_root=None, test=None, map_location="cpu"):
+    def load_from_checkpoint(cls, path, dataset_root=None, test=None, map_location="cpu", weights="raw"):
         """Accepts a Lightning checkpoint of the reference ({'state_dict', 'hyper_parameters' | 'hparams'}) or one
-        written by lets_face_it_amd.trainer.Trainer.save_checkpoint."""
+        written by lets_face_it_amd.trainer.Trainer.save_checkpoint. weights="ema" loads the checkpoint's `ema_state_dict` - the
+        running average of the weights, written when Optim.ema_decay was set - as the model's parameters: a serving process or
+        generate_motion gets the averaged model with no averaging machinery at all. KeyError if the file holds none."""
         from argparse import Namespace
+        if weights not in ("raw", "ema"):
+            raise ValueError("weights must be 'raw' or 'ema', got %r" % (weights,))
         ckpt = torch.load(path, map_location=map_location, weights_only=False)
+        if weights == "ema" and ckpt.get("ema_state_dict") is None:
+            raise KeyError("checkpoint %s holds no 'ema_state_dict' (it was written without Optim.ema_decay)" % path)
         hp = ckpt.get("hyper_parameters") or ckpt.get("hparams")
         if isinstance(hp, dict):
             hp = Namespace(**hp)
         model = cls(hp, dataset_root=dataset_root, test=test)
-        model.load_state_dict(ckpt["state_dict"])
+        model.load_state_dict(ckpt["ema_state_dict" if weights == "ema" else "state_dict"])
         model.seq_glow.glow.set_actnorm_init(True)  # a trained checkpoint must not re-initialise ActNorm
         return model

@@ -15,6 +15,8 @@ Differences that are deliberate:
   * The recurrent state of the coupling nets lives in the engine for the duration of one call, so an instance is
     re-entrant across calls (the reference keeps it on f_seq.hidden, models.py:193-194).
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -444,6 +446,10 @@ class SeqGlow(nn.Module):
         # optimiser state carried over. A no-op move (same device, same dtype: Trainer.fit's model.to(device) on a second
         # fit()) leaves the parameters aliased to the flat buffer and the engine — Adam moments, step count, captured
         # sampling graphs — stays as it is.
+        if self.engine is not None and self.engine._ema_swapped:
+            # refused before any tensor moves: a re-bind would take the averaged values in the module tensors for the raw parameters
+            raise RuntimeError("SeqGlow: .to() / .float() / .cuda() inside ema_weights() while the averaged weights are swapped in - "
+                               "move the module outside the block")
         out = super()._apply(fn, *args, **kwargs)
         if self.engine is not None and not self._still_bound():
             # only Adam's moments + counters survive (on the host): the dropped engine's workspaces and stashes - tens of GB
@@ -452,6 +458,53 @@ class SeqGlow(nn.Module):
             self._stale_opt = (self.engine.n_params, {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in st.items()})
             self.engine = None
             self.glow.flow._engine = None
+        return out
+
+    # ------------------------------------------------------------------ averaged weights (Polyak / EMA; GlowEngine.ema_update)
+    def _ema_engine(self):
+        eng = self.engine
+        if eng is None:      # dropped by a .to() / .float(): the re-bind carries the average over with the optimiser state
+            p = next(self.parameters())
+            if p.is_cuda:
+                eng = self._ensure_engine(p.device)
+        if eng is None or eng.ema is None:
+            raise RuntimeError("SeqGlow: no averaged weights exist (hparams.Optim['ema_decay'] is unset, or no training step has "
+                               "run since)")
+        return eng
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Everything inside runs on the running average of the weights instead of the last optimiser step's: forward(),
+        inference(), open_stream(), invert(), state_dict(). Swaps the flat buffers on entry and back on exit (also on exceptions):
+        afterwards the parameters are bit-identical to before. The swap counts as a parameter change, so a streaming session opened
+        outside refuses to step inside and one opened inside refuses to step after the exit. Training inside raises (the engine's
+        backward, optimiser steps and ema_update, and fused_training_step before it does anything); so do .to() / .float() / .cuda()
+        (moving the module is for outside the block), a nested entry, and an entry while no average exists."""
+        eng = self._ema_engine()
+        if eng._ema_swapped:
+            raise RuntimeError("SeqGlow.ema_weights: already inside an ema_weights() block")
+        eng.swap_ema()
+        try:
+            yield self
+        finally:
+            if eng._ema_swapped:
+                eng.swap_ema()
+
+    def ema_state_dict(self):
+        """state_dict() - the reference's key names - with every parameter that lives in the flat buffer replaced by its averaged
+        value, read out by name through the engine's layout; buffers (invconv.p, sign_s) are copied as they are. Own storage."""
+        eng = self._ema_engine()
+        if eng._ema_swapped:
+            raise RuntimeError("SeqGlow.ema_state_dict inside ema_weights(): state_dict() is the average there")
+        slot = {t.data_ptr(): (name, k) for name, k, t in self._named_flat()}
+        out = {}
+        for key, v in self.state_dict().items():
+            name, k = slot.get(v.data_ptr(), (None, None))
+            if name is None or not v.is_floating_point():
+                out[key] = v.detach().clone()
+                continue
+            avg = eng.view(name, eng.ema)
+            out[key] = (avg if k is None else avg[k]).reshape(v.shape).clone()
         return out
 
     # ------------------------------------------------------------------ helpers

@@ -5,6 +5,7 @@ One process per GPU; with WORLD_SIZE > 1 the flat gradient buffer is all-reduced
 and ActNorm's data-dependent init statistics and the mismatched-NLL switch are all-reduced so every rank holds
 identical parameters and takes identical branches.
 """
+import contextlib
 import itertools
 import os
 import random
@@ -177,11 +178,18 @@ class Trainer:
         if loader is None:
             return None
         model.eval()
+        # With weight averaging on (Optim.ema_decay) validation runs on the running average of the weights: val_loss and everything
+        # the callbacks do (MimicryLogger: sampling, jerk, mismatched-NLL probes, invertibility). Validation["use_ema"] = False keeps
+        # the raw weights; without an average the code path is the plain one.
+        eng = getattr(getattr(model, "seq_glow", None), "engine", None)
+        use_ema = (getattr(eng, "ema", None) is not None
+                   and bool((getattr(self.hparams, "Validation", None) or {}).get("use_ema", True)))
+        weights = model.seq_glow.ema_weights() if use_ema else contextlib.nullcontext()
         # under data parallelism the loader hands every rank ITS share of the validation windows (WindowLoader: one shared order,
         # rank r takes elements r, r + world, ...); the loss is summed over ranks below. The callbacks (MimicryLogger: sampling,
         # invertibility, the mismatched-NLL probes, rendering) issue no collective and run on rank 0 only, on rank 0's first batch
         total = torch.zeros(2, dtype=torch.float64, device=self.device)
-        with torch.no_grad():
+        with weights, torch.no_grad():
             for i, batch in enumerate(loader()):
                 batch = {k: v.to(self.device).float().contiguous() for k, v in batch.items()}
                 out = model.validation_step(batch, i)
@@ -201,14 +209,19 @@ class Trainer:
     def save_checkpoint(self, model, path):
         """Weights (state_dict incl. the `last_missmatched_nll` buffer), hparams, epoch / step counters and the fused
         optimiser's state (Adam moments over the flat parameter buffer + step count: with betas[1] = 0.9999 a resumed run
-        that restarted them would take ~10^4 steps to get its second moments back)."""
+        that restarted them would take ~10^4 steps to get its second moments back). With weight averaging on, `ema_state_dict` holds
+        the averaged weights under state_dict's keys (LetsFaceItGlow.load_from_checkpoint(..., weights="ema")); the flat average and
+        its update count travel inside `optimizer_state` (resume)."""
         if self.rank == 0:
             eng = model.seq_glow.engine
             opt = None
             if eng is not None:
                 opt = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in eng.optimizer_state().items()}
+            extra = {}
+            if getattr(eng, "ema", None) is not None:
+                extra["ema_state_dict"] = {k: v.detach().cpu() for k, v in model.ema_state_dict().items()}
             tmp = path + ".tmp"
-            torch.save({"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
+            torch.save({**extra, "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
                         "hparams": vars(self.hparams), "epoch": self.epoch, "global_step": self.global_step,
                         "optimizer_state": opt, "actnorm_inited": bool(model.seq_glow.glow.actnorm_inited()),
                         # the negative-example branch draws from Python's `random`, derange_batch from torch's CPU generator,
@@ -258,7 +271,8 @@ class Trainer:
         return cls._flat_optimizer_state(model, eng, opt_state, "adam")
 
     def resume(self, model, path):
-        """Continue a run from a checkpoint of save_checkpoint: weights, ActNorm's inited flag, Adam state, epoch and step."""
+        """Continue a run from a checkpoint of save_checkpoint: weights, ActNorm's inited flag, Adam state, the running average of
+        the weights and its update count (inside the optimiser state), epoch and step."""
         ckpt = torch.load(path, map_location="cpu", weights_only=False)
         model.load_state_dict(ckpt["state_dict"])
         model.to(self.device)
@@ -281,6 +295,10 @@ class Trainer:
             import warnings
             warnings.warn("checkpoint %s holds no optimiser state: Adam's moments restart from zero (with betas[1] = 0.9999 "
                           "the second moments need ~10^4 steps to recover)" % path)
+        if getattr(model, "ema_decay", None) and getattr(eng, "ema", None) is None:
+            import warnings
+            warnings.warn("checkpoint %s holds no averaged weights while Optim.ema_decay is set: the average restarts as a copy of the "
+                          "parameters at the first update" % path)
         rng = ckpt.get("rng")
         if rng:
             random.setstate(rng["python"])
