@@ -478,6 +478,15 @@ int lfi_flow_score_seq_from(const lfi_flow_dims* d, const lfi_flow_params* p, co
  * Allocation-free; every argument is checked before the first launch. */
 long lfi_flow_score_chunk_work_floats(const lfi_flow_dims* d, const lfi_p1enc* p1, int hist1);
 int lfi_flow_score_chunk_ok(const lfi_flow_dims* d);
+/* Host-only query (no GPU touched; d == NULL: 0): what the per-frame drivers above and below - lfi_flow_sample_seq{,_from,_nll},
+ * lfi_flow_sample_cand_from / _cand_seq, lfi_flow_score_seq_from / _chunk / _chunk_rows, lfi_flow_step_rows_from / _seq - decide from d
+ * and the switches read at the call, as bits: 1 = the register-resident cells (C, Cout <= 64, H <= 128; LFI_FLOW_GENERIC not 1),
+ * 2 = one launch per frame's chain (bit 1 and LFI_SAMPLE_CHAIN not 0; lfi_flow_score_chunk_ok is this bit), 4 = reverse cells with
+ * three fp16 products (gemm_precision bit 0, GRU, whole 32-k blocks, LFI_PIPE_X3 not 0), 8 = their weights read as the fp16 fragment
+ * images of lfi_flow_prep (bits 2 and 4, LFI_SAMPLE_WFRAG16 not 0), 16 = forward cells with three fp16 products (bit 4 and
+ * (gemm_precision & 0xff) == 9 only: the observed frame is caller data, see lfi_flow_score_seq_from). Bits 4 .. 16 are used where
+ * bit 2 is set. */
+int lfi_flow_frame_plan(const lfi_flow_dims* d);
 int lfi_flow_score_seq_chunk(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep,
                              const float* wct, long E, int hist1, float* pre_static,
                              float* faces, int seq_len, int start, int nframes, int first_frame,

@@ -168,6 +168,7 @@ def lib():
                                         vp, vp, vp, vp]),
         "lfi_flow_score_chunk_work_floats": (l, [P(FlowDims), P(P1Enc), i]),
         "lfi_flow_score_chunk_ok": (i, [P(FlowDims)]),
+        "lfi_flow_frame_plan": (i, [P(FlowDims)]),
         "lfi_flow_score_seq_chunk": (i, [P(FlowDims), P(FlowParams), vp, vp, l, i, vp, vp, i, i, i, i, vp, vp, P(P1Enc), vp, vp,
                                          vp, vp, vp, vp]),
         "lfi_flow_score_seq_chunk_rows": (i, [P(FlowDims), P(FlowParams), vp, vp, l, i, vp, vp, i, i, i, i, vp, vp, P(P1Enc), vp, vp,
@@ -236,7 +237,7 @@ EXPORTS = [
     "lfi_actnorm_init_stats", "lfi_actnorm_init_apply", "lfi_flow_step", "lfi_flow_seq_rev_ok", "lfi_flow_seq_rev_work_floats",
     "lfi_flow_seq_rev", "lfi_flow_sample_work_floats",
     "lfi_flow_sample_p1_work_floats", "lfi_flow_sample_seq", "lfi_flow_sample_seq_from", "lfi_flow_sample_nll_work_floats", "lfi_flow_sample_seq_nll", "lfi_flow_score_work_floats", "lfi_flow_score_seq_from",
-    "lfi_flow_score_chunk_work_floats", "lfi_flow_score_chunk_ok", "lfi_flow_score_seq_chunk", "lfi_stream_chunk_in", "lfi_stream_chunk_out",
+    "lfi_flow_score_chunk_work_floats", "lfi_flow_score_chunk_ok", "lfi_flow_frame_plan", "lfi_flow_score_seq_chunk", "lfi_stream_chunk_in", "lfi_stream_chunk_out",
     "lfi_stream_chunk_gen_in", "lfi_stream_chunk_gen_out",
     "lfi_flow_score_seq_chunk_rows", "lfi_stream_chunk_in_rows", "lfi_stream_chunk_out_rows",
     "lfi_flow_step_rows_seq", "lfi_stream_chunk_roles_in",

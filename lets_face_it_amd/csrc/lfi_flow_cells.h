@@ -969,23 +969,28 @@ inline long prep_padded_floats(const lfi_flow_dims* d) {
          + d->Ks * (Ch16 * NG * H16 + H16 * NG * H16 + H16 * Co16 + C16 * C16) + 8;   // + the fp16 hi/lo images of pwz / pwh / pwfl / pWinv
 }
 
-inline int fill_flow(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, FlowK* f, const char* who) {
-  LFI_REQUIRE(d && p, "%s: null dims/params", who);
-  LFI_REQUIRE(d->B > 0 && d->N > 0 && d->C >= 2 && d->H > 0 && d->D > 0 && d->Ks > 0, "%s: bad dims", who);
+// the sizes and widths that follow from dims alone (fill_flow; the host-only queries and flow_frame_plan, which have no params)
+inline void flow_widths(const lfi_flow_dims* d, FlowK* f) {
   f->B = d->B; f->N = d->N; f->C = d->C; f->H = d->H; f->D = d->D; f->Ks = d->Ks;
   f->affine = d->affine; f->lstm = d->lstm; f->eps = d->scale_eps;
   f->Ch = d->C / 2; f->C2 = d->C - f->Ch; f->Cout = d->affine ? 2 * f->C2 : f->C2;
   f->G = (d->lstm ? 4 : 3) * d->H; f->I = f->Ch + d->D; f->F = d->N * d->B; f->nbt = lfi_cdiv(d->B, MB);
+  f->NG = d->lstm ? 4 : 3;
+  f->ldc = (f->C + 3) & ~3; f->ldo = (f->Cout + 3) & ~3;
+  f->C16 = (f->C + 15) & ~15; f->Ch16 = (f->Ch + 15) & ~15; f->H16 = (f->H + 15) & ~15; f->Co16 = (f->Cout + 15) & ~15;
+  if (f->Ch16 == 0) f->Ch16 = 16;
+}
+
+inline int fill_flow(const lfi_flow_dims* d, const lfi_flow_params* p, const float* prep, FlowK* f, const char* who) {
+  LFI_REQUIRE(d && p, "%s: null dims/params", who);
+  LFI_REQUIRE(d->B > 0 && d->N > 0 && d->C >= 2 && d->H > 0 && d->D > 0 && d->Ks > 0, "%s: bad dims", who);
+  flow_widths(d, f);
   f->p = *p;
   f->stamps = g_lfi_stamps;
   {
     const char* e = getenv("LFI_STAMP_K");
     f->stamp_k = e ? atoi(e) : f->Ks / 2;
   }
-  f->NG = d->lstm ? 4 : 3;
-  f->ldc = (f->C + 3) & ~3; f->ldo = (f->Cout + 3) & ~3;
-  f->C16 = (f->C + 15) & ~15; f->Ch16 = (f->Ch + 15) & ~15; f->H16 = (f->H + 15) & ~15; f->Co16 = (f->Cout + 15) & ~15;
-  if (f->Ch16 == 0) f->Ch16 = 16;
   if (prep) {
     const long cc = (long)d->Ks * d->C * d->C;
     const float* q = prep;
@@ -1079,6 +1084,38 @@ inline bool flow_x3_bwd_planes(const lfi_flow_dims* d) {
 // z1, h and, for the inverse 1x1 convolution, the channels, so C16 joins the 32-k conditions - the shapes of flow_x3h_images_ok
 inline bool flow_x3_rev_cell(const lfi_flow_dims* d, const FlowK& f) {
   return (d->gemm_precision & 1) && flow_x3h_images_ok(f) && flow_pipe_x3_enabled();
+}
+
+// ---- what a per-frame driver of a streaming session or a sampler decides from dims and the switches of the moment (nothing cached):
+// sample_seq_run, lfi_flow_sample_cand_from, lfi_flow_score_seq_from, step_rows_frames (lfi_flow_chain.hip) and the two chunk drivers
+// take every answer from here, and so do their *_pick functions. What depends on pointers or on the call - the fused front end, the
+// staged window, the window-fragment hand-over, the nll form of the chain - stays with SampleFront and the drivers.
+struct FramePlan {
+  bool fast;    // the register-resident cells (flow_fast_ok); LFI_FLOW_GENERIC=1 keeps the streaming cells
+  bool chain;   // one launch for a frame's whole chain; LFI_SAMPLE_CHAIN=0 (and the streaming cells) keep one launch per flow step
+  bool x3;      // reverse cells: three fp16 products of two-piece operands, at per-frame arithmetic 9 and 5 (flow_x3_rev_cell)
+  bool xw;      // ... their weights from the fp16 fragment images lfi_flow_prep left, no split in every workgroup (LFI_SAMPLE_WFRAG16=0: split)
+  bool x3f;     // forward cells: three fp16 products for per-frame arithmetic 9 ONLY. The reverse cells keep them at 5 as well - their
+                // operands are bounded (the prior draw, h in (-1, 1)) - but the forward chain's first operand is actnorm of a frame the
+                // CALLER supplies: a value beyond fp16's range would turn into inf - inf = NaN in the split and stay in h / c. 5 is the
+                // arithmetic a session falls back to when its range guard trips and must have no range caveat: it takes the exact-f32
+                // cell (as 0 and the LSTM cell do), which is at least as accurate as six bf16 products.
+  size_t lds_fast, lds_gen;   // dynamic LDS of the register-resident cells' carve and of the streaming cells'
+  // lfi_flow_frame_plan's answer (include/lfi.h)
+  int bits() const { return (fast ? 1 : 0) | (chain ? 2 : 0) | (x3 ? 4 : 0) | (xw ? 8 : 0) | (x3f ? 16 : 0); }
+};
+inline FramePlan flow_frame_plan(const lfi_flow_dims* d) {
+  FlowK f = {};
+  flow_widths(d, &f);
+  FramePlan pl = {};
+  pl.fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
+  pl.chain = pl.fast && lfi_env_on("LFI_SAMPLE_CHAIN");
+  pl.x3 = flow_x3_rev_cell(d, f);
+  pl.xw = pl.x3 && pl.chain && flow_sample_wfrag16_enabled();
+  pl.x3f = pl.x3 && (d->gemm_precision & 0xff) == 9;
+  pl.lds_fast = (size_t)carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total * sizeof(float);
+  pl.lds_gen = (size_t)carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout).total * sizeof(float);
+  return pl;
 }
 
 // What lfi_flow_sample_seq_nll, lfi_flow_score_seq_from and lfi_flow_step_rows_from (and lfi_flow_score_seq_chunk, lfi_flow_chunk.hip) ask of the arguments they share, in one order.
@@ -1578,6 +1615,52 @@ inline ChunkCarve chunk_carve(const lfi_flow_dims* d, const lfi_p1enc* p1, int h
   c.pipe = o; c.pipe_words = up4((long)PIPE_HDR + (long)d->Ks * nbt); o += c.pipe_words;
   c.total = o;
   return c;
+}
+
+// What lfi_flow_score_seq_chunk and its ragged form do between fill_flow and the launch of their chain, once for both: the checks
+// (ptrs_ok: the caller's own list), the carve, the unit's kernel (`pick`, of the plan's bits) and its LDS, the front end ONCE - the
+// windows of all frames (row n * B + b: frames [start + n - hist1, start + n) of sample b), then the products - and the chain-state
+// clear. Leaves the fields the two kernel-argument structs share in *sc, the kernel and its LDS in *kernel / *lds; *kernel stays null
+// where the caller has no chain to launch:
+// (diagnostics, tools/stream_latency.py: LFI_CHUNK_ONLY=front / chain launches one of the two parts alone, so that events around the
+// call time it - the chain then reads the gic an earlier whole call left in the work area. Results are not meaningful.)
+template <typename SC, typename Kf>
+int chunk_front(const char* who, const lfi_flow_dims* d, const lfi_flow_params* p, const FlowK& f, bool ptrs_ok, const float* wct, long E,
+                int hist1, float* pre_static, float* faces, int seq_len, int start, int nframes, int first_frame, float* h, float* cstate,
+                const lfi_p1enc* p1, float* chunk_work, float* z, float* nll, void* stream, Kf (*pick)(const FramePlan&, bool), SC* sc,
+                Kf* kernel, size_t* lds) {
+  int rc;
+  if ((rc = frame_args_check(who, who, d, ptrs_ok, E, hist1, start, nframes, seq_len, cstate, first_frame))) return rc;
+  LFI_REQUIRE(nframes >= 1 && nframes <= d->N, "%s: %d frames, the work area holds d->N = %d", who, nframes, d->N);
+  LFI_REQUIRE(hist1 >= 1, "%s: bad frame range (hist1 %d)", who, hist1);
+  LFI_REQUIRE((long)nframes * f.B < (1L << 24), "%s: %d frames x batch %d: too many rows for one launch", who, nframes, f.B);
+  const FramePlan pl = flow_frame_plan(d);
+  LFI_REQUIRE(pl.chain, "%s: C, Cout <= 64 and hidden_channels <= 128 only, LFI_SAMPLE_CHAIN not 0 "
+              "(lfi_flow_score_chunk_ok); otherwise lfi_flow_score_seq_from", who);
+  const int B = f.B, C = f.C;
+  const int p1kind = p1 ? p1->kind : 0;
+  LFI_REQUIRE(p1kind >= 0 && p1kind <= 3, "%s: bad p1_face encoder kind %d", who, p1kind);
+  LFI_REQUIRE(p1kind == 0 || p1->hid > 0, "%s: encoded p1_face window with hid %d", who, p1->hid);
+  const ChunkCarve cv = chunk_carve(d, p1, hist1, nframes);
+  float* base = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(chunk_work) + 15) & ~(uintptr_t)15);
+  unsigned* pipe = reinterpret_cast<unsigned*>(base + cv.pipe);
+  const Kf chain_kernel = pick(pl, f.lstm);
+  if ((rc = set_flow_lds(chain_kernel, pl.lds_fast, who))) return rc;
+  const char* only = getenv("LFI_CHUNK_ONLY");
+  const bool run_front = !(only && only[0] == 'c'), run_chain = !(only && only[0] == 'f');
+  if (run_front) {
+    if ((rc = lfi_gather_windows(faces, B, seq_len, C, nframes, start, hist1, 0, nullptr, base + cv.wstage, cv.ldw, 0, stream))) return rc;
+    if ((rc = lfi_internal_sample_front_rows(d, p, p1, wct, E, hist1, f.wc, nframes * B, base + cv.wstage, cv.ldw, pre_static, base + cv.gic,
+                                             base + cv.p1work, stream))) return rc;
+  }
+  if (!run_chain) return LFI_OK;
+  hipError_t me = hipMemsetAsync(pipe, 0, (size_t)cv.pipe_words * sizeof(unsigned), (hipStream_t)stream);
+  LFI_REQUIRE(me == hipSuccess, "%s: hipMemsetAsync: %s", who, hipGetErrorString(me));
+  sc->frame0 = faces + (long)start * C; sc->ld_frame = (long)seq_len * C; sc->nframes = nframes;
+  sc->tiles = base + cv.tiles; sc->q = base + cv.q; sc->gic = base + cv.gic;
+  sc->h = h; sc->cstate = cstate; sc->has_prev = first_frame > 0 ? 1 : 0; sc->pipe = pipe; sc->z = z; sc->nll = nll;
+  *kernel = chain_kernel; *lds = pl.lds_fast;
+  return LFI_OK;
 }
 
 }  // namespace

@@ -733,32 +733,31 @@ FlowStepKernel flow_step_rev_pick(bool fast, bool lstm) {
   return lstm ? flow_step_rev_fast_kernel<4> : flow_step_rev_fast_kernel<3>;
 }
 FlowRevWalkKernel flow_rev_walk_pick(bool lstm) { return lstm ? flow_rev_walk_kernel<4> : flow_rev_walk_kernel<3>; }
+// (the chains' forms by the frame plan's bits, FramePlan in lfi_flow_cells.h: x3 / xw the reverse cells', x3f the forward cells'; the
+// LSTM cell exact in all)
 template <bool NLL>
-FlowRevChainKernel flow_rev_chain_pick_(bool lstm, bool x3, bool xw) {
+FlowRevChainKernel flow_rev_chain_pick_(const FramePlan& pl, bool lstm) {
   if (lstm) return flow_rev_chain_kernel<4, false, false, NLL>;
-  if (xw) return flow_rev_chain_kernel<3, true, true, NLL>;
-  return x3 ? flow_rev_chain_kernel<3, true, false, NLL> : flow_rev_chain_kernel<3, false, false, NLL>;
+  if (pl.xw) return flow_rev_chain_kernel<3, true, true, NLL>;
+  return pl.x3 ? flow_rev_chain_kernel<3, true, false, NLL> : flow_rev_chain_kernel<3, false, false, NLL>;
 }
-FlowRevChainKernel flow_rev_chain_pick(bool lstm, bool x3, bool xw, bool nll) {
-  return nll ? flow_rev_chain_pick_<true>(lstm, x3, xw) : flow_rev_chain_pick_<false>(lstm, x3, xw);
+FlowRevChainKernel flow_rev_chain_pick(const FramePlan& pl, bool lstm, bool nll) {
+  return nll ? flow_rev_chain_pick_<true>(pl, lstm) : flow_rev_chain_pick_<false>(pl, lstm);
 }
-// the candidate chain: flow_rev_chain_pick's rule
-FlowCandChainKernel flow_cand_chain_pick(bool lstm, bool x3, bool xw) {
+FlowCandChainKernel flow_cand_chain_pick(const FramePlan& pl, bool lstm) {
   if (lstm) return flow_cand_chain_kernel<4, false, false>;
-  if (xw) return flow_cand_chain_kernel<3, true, true>;
-  return x3 ? flow_cand_chain_kernel<3, true, false> : flow_cand_chain_kernel<3, false, false>;
+  if (pl.xw) return flow_cand_chain_kernel<3, true, true>;
+  return pl.x3 ? flow_cand_chain_kernel<3, true, false> : flow_cand_chain_kernel<3, false, false>;
 }
-FlowFwdChainKernel flow_fwd_chain_pick(bool lstm, bool x3) {
+FlowFwdChainKernel flow_fwd_chain_pick(const FramePlan& pl, bool lstm) {
   if (lstm) return flow_fwd_chain_kernel<4, false>;
-  return x3 ? flow_fwd_chain_kernel<3, true> : flow_fwd_chain_kernel<3, false>;
+  return pl.x3f ? flow_fwd_chain_kernel<3, true> : flow_fwd_chain_kernel<3, false>;
 }
-// the two chains' own rules side by side: the reverse cells' form as flow_rev_chain_pick has it (x3: fp16 pieces at precisions 9 and 5,
-// xw: from the fragment images), the forward cells' as flow_fwd_chain_pick has it (x3f: precision 9 only); the LSTM cell exact in both
-FlowRowsChainKernel flow_rows_chain_pick(bool lstm, bool x3, bool xw, bool x3f) {
+FlowRowsChainKernel flow_rows_chain_pick(const FramePlan& pl, bool lstm) {
   if (lstm) return flow_rows_chain_kernel<4, false, false, false>;
-  if (!x3) return flow_rows_chain_kernel<3, false, false, false>;
-  if (xw) return x3f ? flow_rows_chain_kernel<3, true, true, true> : flow_rows_chain_kernel<3, true, true, false>;
-  return x3f ? flow_rows_chain_kernel<3, true, false, true> : flow_rows_chain_kernel<3, true, false, false>;
+  if (!pl.x3) return flow_rows_chain_kernel<3, false, false, false>;
+  if (pl.xw) return pl.x3f ? flow_rows_chain_kernel<3, true, true, true> : flow_rows_chain_kernel<3, true, true, false>;
+  return pl.x3f ? flow_rows_chain_kernel<3, true, false, true> : flow_rows_chain_kernel<3, true, false, false>;
 }
 
 }  // namespace
@@ -1077,6 +1076,8 @@ extern "C" long lfi_flow_sample_nll_work_floats(const lfi_flow_dims* d) {
   return 2L * d->B + 8;   // the two ping-pong hand-over arrays of the chain (the first is the per-step launches' accumulator)
 }
 
+extern "C" int lfi_flow_frame_plan(const lfi_flow_dims* d) { return d ? flow_frame_plan(d).bits() : 0; }
+
 // A frame's rows of pre_static for the candidates of lfi_flow_sample_cand_seq, where the front end overwrites what it reads (every
 // path but the fused kernel): workgroup v copies parent row v / ncand (KD floats) to row v of a one-frame scratch. 16-byte words
 // where both sides allow it.
@@ -1093,7 +1094,13 @@ __global__ __launch_bounds__(256) void cand_pre_bcast_kernel(const float* __rest
 }
 
 namespace {
-constexpr long kCandSeqMaxRows = 1L << 22;   // virtual rows of one lfi_flow_sample_cand_seq call (lfi_flow_sample_cand_from's limit)
+constexpr long kCandMaxRows = 1L << 22;   // virtual rows of one lfi_flow_sample_cand_from / lfi_flow_sample_cand_seq call
+// launch_rev_steps from the prior draws `noise` (f.B x C), then the finish of the frame's NLL from the cells' accumulator (nll null: neither)
+void launch_rev_frame(const FlowK& f, FlowStepKernel cell, size_t lds, hipStream_t st, const float* gic, float* h, float* cstate, int has_prev,
+                      float* xa, float* xb, const float* noise, float* out, long ld_out, float* acc, float* nll) {
+  launch_rev_steps(f, cell, lds, st, gic, h, cstate, has_prev, xa, xb, noise, f.C, out, ld_out, nll ? acc : nullptr);
+  if (nll) hipLaunchKernelGGL(sample_nll_finish_kernel, dim3(lfi_cdiv(f.B, 256)), dim3(256), 0, st, noise, acc, f.ldconst, f.B, f.C, nll);
+}
 // where the one-frame scratch of lfi_flow_sample_cand_seq lies in its work area: behind the sampler's own carve, 16-byte aligned
 inline long cand_seq_scratch_offset(const lfi_flow_dims* dv) { return (lfi_flow_sample_work_floats(dv) + 3) & ~3L; }
 
@@ -1111,21 +1118,18 @@ int sample_seq_run(const char* who, const char* who_from, const char* who_nll, c
                              E, hist1, start, nframes, seq_len, cstate, first_frame))) return rc;
   LFI_REQUIRE(!nll || nll_work, "%s: nll needs nll_work (lfi_flow_sample_nll_work_floats)", who_nll);
   if (ncand) {
-    LFI_REQUIRE(ncand >= 1 && d->B % ncand == 0 && (long)d->B <= kCandSeqMaxRows,
-                "%s: %d candidates per row do not divide the %d virtual rows (at most %ld)", who, ncand, d->B, kCandSeqMaxRows);
+    LFI_REQUIRE(ncand >= 1 && d->B % ncand == 0 && (long)d->B <= kCandMaxRows,
+                "%s: %d candidates per row do not divide the %d virtual rows (at most %ld)", who, ncand, d->B, kCandMaxRows);
     LFI_REQUIRE((reinterpret_cast<uintptr_t>(work) & 15) == 0, "%s: work is not 16-byte aligned", who);
   }
   const int B = f.B, C = f.C, D = f.D, Ks = f.Ks;
   const int Bp = ncand ? B / ncand : B;          // rows of pre_static per frame
   hipStream_t st = (hipStream_t)stream;
-  const bool fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
-  const Carve cv = carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout);
-  const size_t lds = (size_t)(fast ? carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total : cv.total) * sizeof(float);
-  const FlowStepKernel cell = flow_step_rev_pick(fast, f.lstm);
+  const FramePlan pl = flow_frame_plan(d);
+  const bool chain = pl.chain;
+  const size_t lds = pl.fast ? pl.lds_fast : pl.lds_gen;
+  const FlowStepKernel cell = flow_step_rev_pick(pl.fast, f.lstm);
   if ((rc = set_flow_lds(cell, lds, "lfi_flow_sample_seq"))) return rc;
-  // LFI_SAMPLE_CHAIN=0 keeps one launch per flow step
-  const bool chain = fast && lfi_env_on("LFI_SAMPLE_CHAIN");
-  const bool x3 = flow_x3_rev_cell(d, f);
   // the per-frame conditioning (sample_front_*): the carve of `work`, the fused kernel's weight fragments once per call
   SampleFront sf = {};
   if ((rc = sample_front_setup(&sf, d, p, &f, wct, E, hist1, pre_static, faces, seq_len, p1, p1work, work, chain, nframes, stream,
@@ -1142,11 +1146,8 @@ int sample_seq_run(const char* who, const char* who_from, const char* who_nll, c
   const bool run_chain = !(only && only[0] == 'f');
   // LFI_SAMPLE_XF_CHAIN=0 keeps the window-fragment kernel in front of every frame's conditioning
   const bool xf_chain = sf.fused && chain && lfi_env_on("LFI_SAMPLE_XF_CHAIN");
-  // the reverse cells' weights as the fp16 fragment images lfi_flow_prep left (no split in every workgroup of every frame; x3 is true
-  // only for the shapes that have them, flow_x3h_images_ok)
-  const bool xw = x3 && chain && flow_sample_wfrag16_enabled();
   // one launch for the whole chain of a frame; with nll the cells also pass the rows' running log-density down the chain
-  const FlowRevChainKernel chain_kernel = flow_rev_chain_pick(f.lstm, x3, xw, nll != nullptr);
+  const FlowRevChainKernel chain_kernel = flow_rev_chain_pick(pl, f.lstm, nll != nullptr);
   if (chain && (rc = set_flow_lds(chain_kernel, lds, nll ? who_nll : who))) return rc;
   for (int n = 0; n < nframes; ++n) {
     const int t = start + n;
@@ -1174,11 +1175,8 @@ int sample_seq_run(const char* who, const char* who_from, const char* who_nll, c
       hipLaunchKernelGGL(chain_kernel, dim3(Ks * f.nbt), dim3(NT), lds, st, f, rcn);
       continue;
     }
-    launch_rev_steps(f, cell, lds, st, sf.gic, h, cstate, first_frame + n > 0 ? 1 : 0, sf.xa, sf.xb, noise + (long)n * B * C, C,
-                     faces + (long)t * C, (long)seq_len * C, nll ? nll_work : nullptr);
-    if (nll)
-      hipLaunchKernelGGL(sample_nll_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, noise + (long)n * B * C, nll_work,
-                         f.ldconst, B, C, nll + (long)n * B);
+    launch_rev_frame(f, cell, lds, st, sf.gic, h, cstate, first_frame + n > 0 ? 1 : 0, sf.xa, sf.xb, noise + (long)n * B * C,
+                     faces + (long)t * C, (long)seq_len * C, nll_work, nll ? nll + (long)n * B : nullptr);
   }
   LFI_LAUNCH_CHECK(who);
   return LFI_OK;
@@ -1198,7 +1196,7 @@ extern "C" int lfi_flow_sample_seq_nll(const lfi_flow_dims* d, const lfi_flow_pa
 // ---- N candidate ROLLOUTS of nframes frames per session row (SampleStream.rollout_candidates): the sampler over V = B * ncand virtual
 // rows whose static conditioning is their parent row's, read in place
 extern "C" long lfi_flow_sample_cand_seq_work_floats(const lfi_flow_dims* d, int ncand) {
-  if (!d || ncand < 1 || d->B < 1 || (long)d->B * ncand > kCandSeqMaxRows) return 0;
+  if (!d || ncand < 1 || d->B < 1 || (long)d->B * ncand > kCandMaxRows) return 0;
   lfi_flow_dims dv = *d;
   dv.B = d->B * ncand;
   return cand_seq_scratch_offset(&dv) + (long)dv.B * dv.Ks * dv.D + 8;
@@ -1238,7 +1236,6 @@ CandWork cand_work_carve(float* base, long V, long C, long G, long Ks) {
   w.total = o + 8;
   return w;
 }
-constexpr long kCandMaxRows = 1L << 22;   // virtual rows of one call
 }  // namespace
 
 extern "C" long lfi_flow_sample_cand_work_floats(const lfi_flow_dims* d, int ncand) {
@@ -1266,14 +1263,11 @@ extern "C" int lfi_flow_sample_cand_from(const lfi_flow_dims* d, const lfi_flow_
   const int B = f.B, C = f.C, H = f.H, Ks = f.Ks, G = f.G;
   const int V = B * ncand, nbtv = lfi_cdiv(V, MB);
   hipStream_t st = (hipStream_t)stream;
-  const bool fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
-  const bool chain = fast && lfi_env_on("LFI_SAMPLE_CHAIN");
-  const bool x3 = flow_x3_rev_cell(d, f);
-  const bool xw = x3 && chain && flow_sample_wfrag16_enabled();
-  const size_t lds = (size_t)(fast ? carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total : carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout).total) *
-                     sizeof(float);
-  const FlowCandChainKernel chain_kernel = flow_cand_chain_pick(f.lstm, x3, xw);
-  const FlowStepKernel cell = flow_step_rev_pick(fast, f.lstm);
+  const FramePlan pl = flow_frame_plan(d);
+  const bool chain = pl.chain;
+  const size_t lds = pl.fast ? pl.lds_fast : pl.lds_gen;
+  const FlowCandChainKernel chain_kernel = flow_cand_chain_pick(pl, f.lstm);
+  const FlowStepKernel cell = flow_step_rev_pick(pl.fast, f.lstm);
   if ((rc = chain ? set_flow_lds(chain_kernel, lds, who) : set_flow_lds(cell, lds, who))) return rc;
   const CandWork cw = cand_work_carve(cand_work, V, C, G, Ks);
   // the front end for the session's B rows, unchanged; the chain's words are the candidate area's (sized for V)
@@ -1294,8 +1288,7 @@ extern "C" int lfi_flow_sample_cand_from(const lfi_flow_dims* d, const lfi_flow_
                        cw.gicv, cand_h, cand_c);
     FlowK fv = f;   // the cells over V rows
     fv.B = V; fv.F = V; fv.nbt = nbtv;
-    launch_rev_steps(fv, cell, lds, st, cw.gicv, cand_h, cand_c, has_prev, cw.xa, cw.xb, noise, C, cand_frames, C, cw.qa);
-    hipLaunchKernelGGL(sample_nll_finish_kernel, dim3(lfi_cdiv(V, 256)), dim3(256), 0, st, noise, cw.qa, f.ldconst, V, C, cand_nll);
+    launch_rev_frame(fv, cell, lds, st, cw.gicv, cand_h, cand_c, has_prev, cw.xa, cw.xb, noise, cand_frames, C, cw.qa, cand_nll);
   }
   LFI_LAUNCH_CHECK(who);
   return LFI_OK;
@@ -1318,6 +1311,15 @@ __global__ __launch_bounds__(256) void score_finish_kernel(const float* __restri
   nll[b] = -(ldconst[0] + acc[b] + lp) / LN2_F;
 }
 
+namespace {
+// launch_fwd_steps of the streaming forward cell on the frame at `frame`, then the finish: the frame's NLL, its latent where z is not null
+void launch_fwd_frame(const FlowK& f, size_t lds, hipStream_t st, const float* gic, float* h, float* cstate, int has_prev, float* xa,
+                      float* xb, const float* frame, long ld_frame, float* acc, float* z, float* nll) {
+  const float* zlast = launch_fwd_steps(f, flow_step_kernel<false>, lds, st, gic, h, cstate, has_prev, xa, xb, frame, ld_frame, acc);
+  hipLaunchKernelGGL(score_finish_kernel, dim3(lfi_cdiv(f.B, 256)), dim3(256), 0, st, zlast, acc, f.ldconst, f.B, f.C, z, nll);
+}
+}  // namespace
+
 extern "C" long lfi_flow_score_work_floats(const lfi_flow_dims* d) {
   if (!d) return 0;
   return 2L * d->B + 8;   // the two ping-pong log-det hand-over arrays of the forward chain (the first: the per-step launches' accumulator)
@@ -1338,16 +1340,10 @@ extern "C" int lfi_flow_score_seq_from(const lfi_flow_dims* d, const lfi_flow_pa
   hipStream_t st = (hipStream_t)stream;
   // the register-resident chain for the shapes the sampler's chain takes; otherwise (and with LFI_SAMPLE_CHAIN=0) Ks launches of the
   // streaming forward cell + the finish
-  const bool chain = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic() && lfi_env_on("LFI_SAMPLE_CHAIN");
-  // three fp16 products for per-frame arithmetic 9 only. The reverse cells keep them at 5 as well - their operands are bounded (the
-  // prior draw, h in (-1, 1)) - but this chain's first operand is actnorm of a frame the CALLER supplies: a value beyond fp16's range
-  // would turn into inf - inf = NaN in the split and stay in h / c. 5 is the arithmetic a session falls back to when its range guard
-  // trips and must have no range caveat: it takes the exact-f32 cell (as 0 and the LSTM cell do), which is at least as accurate as
-  // six bf16 products.
-  const bool x3 = flow_x3_rev_cell(d, f) && (d->gemm_precision & 0xff) == 9;
-  const size_t lds = (size_t)(chain ? carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total : carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout).total) *
-                     sizeof(float);
-  const FlowFwdChainKernel chain_kernel = flow_fwd_chain_pick(f.lstm, x3);
+  const FramePlan pl = flow_frame_plan(d);
+  const bool chain = pl.chain;
+  const size_t lds = chain ? pl.lds_fast : pl.lds_gen;
+  const FlowFwdChainKernel chain_kernel = flow_fwd_chain_pick(pl, f.lstm);
   if ((rc = chain ? set_flow_lds(chain_kernel, lds, "lfi_flow_score_seq_from") : set_flow_lds(flow_step_kernel<false>, lds, "lfi_flow_score_seq_from")))
     return rc;
   SampleFront sf = {};
@@ -1368,9 +1364,7 @@ extern "C" int lfi_flow_score_seq_from(const lfi_flow_dims* d, const lfi_flow_pa
       hipLaunchKernelGGL(chain_kernel, dim3(Ks * f.nbt), dim3(NT), lds, st, f, fc);
       continue;
     }
-    const float* zlast = launch_fwd_steps(f, flow_step_kernel<false>, lds, st, sf.gic, h, cstate, has_prev, sf.xa, sf.xb, faces + (long)t * C,
-                                          (long)seq_len * C, qa);
-    hipLaunchKernelGGL(score_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, zlast, qa, f.ldconst, B, C, zn, nll + (long)n * B);
+    launch_fwd_frame(f, lds, st, sf.gic, h, cstate, has_prev, sf.xa, sf.xb, faces + (long)t * C, (long)seq_len * C, qa, zn, nll + (long)n * B);
   }
   LFI_LAUNCH_CHECK("lfi_flow_score_seq_from");
   return LFI_OK;
@@ -1458,15 +1452,10 @@ int step_rows_frames(const char* who, const lfi_flow_dims* d, const lfi_flow_par
   LFI_REQUIRE((reinterpret_cast<uintptr_t>(rows_work) & 3) == 0, "%s: rows_work is not 4-byte aligned", who);
   const int B = f.B, C = f.C, D = f.D, H = f.H, Ks = f.Ks;
   hipStream_t st = (hipStream_t)stream;
-  const bool fast = flow_fast_ok(f.C, f.H, f.Cout) && !flow_force_generic();
-  const bool chain = fast && lfi_env_on("LFI_SAMPLE_CHAIN");
-  // each direction's own rule (lfi_flow_sample_seq_nll, lfi_flow_score_seq_from)
-  const bool x3 = flow_x3_rev_cell(d, f);
-  const bool xw = x3 && chain && flow_sample_wfrag16_enabled();
-  const bool x3f = x3 && (d->gemm_precision & 0xff) == 9;
-  const size_t lds_fast = (size_t)carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total * sizeof(float);
-  const size_t lds_gen = (size_t)carve_fwd(f.C, f.H, f.Ch, f.C2, f.Cout).total * sizeof(float);
-  const FlowRowsChainKernel chain_kernel = flow_rows_chain_pick(f.lstm, x3, xw, x3f);
+  const FramePlan pl = flow_frame_plan(d);
+  const bool fast = pl.fast, chain = pl.chain;
+  const size_t lds_fast = pl.lds_fast, lds_gen = pl.lds_gen;
+  const FlowRowsChainKernel chain_kernel = flow_rows_chain_pick(pl, f.lstm);   // (each direction's own form)
   const FlowStepKernel rev_cell = flow_step_rev_pick(fast, f.lstm);
   if (chain) {
     if ((rc = set_flow_lds(chain_kernel, lds_fast, who))) return rc;
@@ -1507,11 +1496,9 @@ int step_rows_frames(const char* who, const lfi_flow_dims* d, const lfi_flow_par
       if (me == hipSuccess && f.lstm) me = hipMemcpyAsync(rw.cs, cstate, state_bytes, hipMemcpyDeviceToDevice, st);
       LFI_REQUIRE(me == hipSuccess, "%s: hipMemcpyAsync: %s", who, hipGetErrorString(me));
     }
-    const float* zlast = launch_fwd_steps(f, flow_step_kernel<false>, lds_gen, st, sf.gic, rw.hs, rw.cs, has_prev, rw.xa, rw.xb, frame, ld_frame, rw.qa);
-    hipLaunchKernelGGL(score_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, zlast, rw.qa, f.ldconst, B, C, (float*)nullptr, rw.fnll);
+    launch_fwd_frame(f, lds_gen, st, sf.gic, rw.hs, rw.cs, has_prev, rw.xa, rw.xb, frame, ld_frame, rw.qa, nullptr, rw.fnll);
     // ---- the reverse direction on the state itself, its frame aside (the observing rows' frame stays in `faces`)
-    launch_rev_steps(f, rev_cell, fast ? lds_fast : lds_gen, st, sf.gic, h, cstate, has_prev, sf.xa, sf.xb, noise_n, C, rw.gframe, C, nll_work);
-    hipLaunchKernelGGL(sample_nll_finish_kernel, dim3(lfi_cdiv(B, 256)), dim3(256), 0, st, noise_n, nll_work, f.ldconst, B, C, nll_n);
+    launch_rev_frame(f, rev_cell, fast ? lds_fast : lds_gen, st, sf.gic, h, cstate, has_prev, sf.xa, sf.xb, noise_n, rw.gframe, C, nll_work, nll_n);
     hipLaunchKernelGGL(rows_merge_kernel, dim3(B), dim3(256), 0, st, role, B, C, H, Ks, h, cstate, rw.hs, rw.cs, frame, ld_frame,
                        rw.gframe, nll_n, rw.fnll);
   }

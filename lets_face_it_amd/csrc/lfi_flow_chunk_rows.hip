@@ -54,9 +54,9 @@ __global__ __launch_bounds__(NT) void flow_fwd_seq_rows_chain_kernel(FlowK f, Fw
 }
 
 typedef void (*FlowFwdSeqRowsChainKernel)(FlowK, FwdSeqRowsChain);
-FlowFwdSeqRowsChainKernel flow_fwd_seq_rows_chain_pick(bool lstm, bool x3) {
+FlowFwdSeqRowsChainKernel flow_fwd_seq_rows_chain_pick(const FramePlan& pl, bool lstm) {
   if (lstm) return flow_fwd_seq_rows_chain_kernel<4, false>;
-  return x3 ? flow_fwd_seq_rows_chain_kernel<3, true> : flow_fwd_seq_rows_chain_kernel<3, false>;
+  return pl.x3f ? flow_fwd_seq_rows_chain_kernel<3, true> : flow_fwd_seq_rows_chain_kernel<3, false>;
 }
 
 }  // namespace
@@ -70,42 +70,15 @@ extern "C" int lfi_flow_score_seq_chunk_rows(const lfi_flow_dims* d, const lfi_f
   const char* who = "lfi_flow_score_seq_chunk_rows";
   int rc = fill_flow(d, p, prep, &f, who);
   if (rc) return rc;
-  if ((rc = frame_args_check(who, who, d, prep && wct && pre_static && faces && h && chunk_work && nll && lengths, E, hist1, start, nframes,
-                             seq_len, cstate, first_frame))) return rc;
-  LFI_REQUIRE(nframes >= 1 && nframes <= d->N, "%s: %d frames, the work area holds d->N = %d", who, nframes, d->N);
-  LFI_REQUIRE(hist1 >= 1, "%s: bad frame range (hist1 %d)", who, hist1);
-  LFI_REQUIRE((long)nframes * f.B < (1L << 24), "%s: %d frames x batch %d: too many rows for one launch", who, nframes, f.B);
-  LFI_REQUIRE(lfi_flow_score_chunk_ok(d), "%s: C, Cout <= 64 and hidden_channels <= 128 only, LFI_SAMPLE_CHAIN not 0 "
-              "(lfi_flow_score_chunk_ok); otherwise lfi_flow_score_seq_from", who);
-  const int B = f.B, C = f.C, Ks = f.Ks;
-  const long F = (long)nframes * B;
-  hipStream_t st = (hipStream_t)stream;
-  const int p1kind = p1 ? p1->kind : 0;
-  LFI_REQUIRE(p1kind >= 0 && p1kind <= 3, "%s: bad p1_face encoder kind %d", who, p1kind);
-  LFI_REQUIRE(p1kind == 0 || p1->hid > 0, "%s: encoded p1_face window with hid %d", who, p1->hid);
-  const ChunkCarve cv = chunk_carve(d, p1, hist1, nframes);
-  float* base = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(chunk_work) + 15) & ~(uintptr_t)15);
-  unsigned* pipe = reinterpret_cast<unsigned*>(base + cv.pipe);
-  const bool x3 = flow_x3_rev_cell(d, f) && (d->gemm_precision & 0xff) == 9;   // lfi_flow_score_seq_from's rule
-  const size_t lds = (size_t)carve_fast_fwd(f.C, f.C16, f.H16, f.Ch16, f.Cout).total * sizeof(float);
-  const FlowFwdSeqRowsChainKernel chain_kernel = flow_fwd_seq_rows_chain_pick(f.lstm, x3);
-  if ((rc = set_flow_lds(chain_kernel, lds, who))) return rc;
-  // (LFI_CHUNK_ONLY=front / chain, tools/stream_latency.py: as lfi_flow_score_seq_chunk)
-  const char* only = getenv("LFI_CHUNK_ONLY");
-  const bool run_front = !(only && only[0] == 'c'), run_chain = !(only && only[0] == 'f');
-  if (run_front) {
-    if ((rc = lfi_gather_windows(faces, B, seq_len, C, nframes, start, hist1, 0, nullptr, base + cv.wstage, cv.ldw, 0, stream))) return rc;
-    if ((rc = lfi_internal_sample_front_rows(d, p, p1, wct, E, hist1, f.wc, (int)F, base + cv.wstage, cv.ldw, pre_static, base + cv.gic,
-                                             base + cv.p1work, stream))) return rc;
-  }
-  if (!run_chain) return LFI_OK;
-  hipError_t me = hipMemsetAsync(pipe, 0, (size_t)cv.pipe_words * sizeof(unsigned), st);
-  LFI_REQUIRE(me == hipSuccess, "%s: hipMemsetAsync: %s", who, hipGetErrorString(me));
   FwdSeqRowsChain sc = {};
-  sc.frame0 = faces + (long)start * C; sc.ld_frame = (long)seq_len * C; sc.nframes = nframes;
-  sc.tiles = base + cv.tiles; sc.q = base + cv.q; sc.gic = base + cv.gic;
-  sc.h = h; sc.cstate = cstate; sc.has_prev = first_frame > 0 ? 1 : 0; sc.pipe = pipe; sc.z = z; sc.nll = nll; sc.lengths = lengths;
-  hipLaunchKernelGGL(chain_kernel, dim3(Ks * f.nbt), dim3(NT), lds, st, f, sc);
+  FlowFwdSeqRowsChainKernel chain_kernel = nullptr;
+  size_t lds = 0;
+  // (chunk_front, lfi_flow_cells.h: as lfi_flow_score_seq_chunk; no kernel: LFI_CHUNK_ONLY=front)
+  if ((rc = chunk_front(who, d, p, f, prep && wct && pre_static && faces && h && chunk_work && nll && lengths, wct, E, hist1, pre_static, faces,
+                        seq_len, start, nframes, first_frame, h, cstate, p1, chunk_work, z, nll, stream, flow_fwd_seq_rows_chain_pick, &sc,
+                        &chain_kernel, &lds)) || !chain_kernel) return rc;
+  sc.lengths = lengths;
+  hipLaunchKernelGGL(chain_kernel, dim3(f.Ks * f.nbt), dim3(NT), lds, (hipStream_t)stream, f, sc);
   LFI_LAUNCH_CHECK(who);
   return LFI_OK;
 }

@@ -265,13 +265,25 @@ class SampleStream:
             if x.device != p1.device:
                 raise ValueError("%s: on %s, the seed's p1_face on %s" % (e.name, x.device, p1.device))
 
+    def _check_tensor(self, x, name, axes, note=""):
+        """The one check of a tensor argument, before any launch: contiguous float32 on the session's device, one axis per entry of
+        axes - (its wording in the message, which takes the size as %d; the size, None: any number from one). note: what the message
+        adds about the layout. -> the size of the first axis."""
+        if not (torch.is_tensor(x) and x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.is_contiguous()
+                and x.dim() == len(axes) and all(got >= 1 if want is None else got == want for got, (_, want) in zip(x.shape, axes))):
+            raise ValueError("%s: expected contiguous float32 GPU tensor (%s) on %s%s, got %s %s on %s"
+                             % (name, ", ".join(text if want is None else text % want for text, want in axes), self.device, note,
+                                tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x)), getattr(x, "device", None)))
+        return int(x.shape[0])
+
+    @staticmethod
+    def _frames_axis(n):
+        """The axis of a chunk's frames: n of them, or (None) any number from one."""
+        return ("n>=1", None) if n is None else ("n=%d", n)
+
     def _check_matrix(self, x, name, cols, rows=None):
         """A step's frame / noise (rows = B) or the records of saved rows (rows None: any number from one)."""
-        if not (torch.is_tensor(x) and x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.is_contiguous()
-                and x.dim() == 2 and (x.shape[0] >= 1 if rows is None else x.shape[0] == rows) and x.shape[1] == cols):
-            raise ValueError("%s: expected contiguous float32 GPU tensor (%s) on %s, got %s %s on %s"
-                             % (name, "n>=1, R=%d" % cols if rows is None else "B=%d, %d" % (rows, cols), self.device,
-                                tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x)), getattr(x, "device", None)))
+        self._check_tensor(x, name, (("n>=1", None), ("R=%d", cols)) if rows is None else (("B=%d", rows), ("%d", cols)))
 
     def _check_usable(self, pending_ok=False):
         if self.closed:
@@ -525,13 +537,9 @@ class SampleStream:
         return ncand
 
     def _check_cand_noise(self, noise, ncand):
-        """The candidates' prior draws, (B, ncand, C). The wording of _check_matrix."""
+        """The candidates' prior draws, (B, ncand, C)."""
         B, C_ = self.B, self.eng.spec.C
-        if not (torch.is_tensor(noise) and noise.is_cuda and noise.device == self.device and noise.dtype == torch.float32
-                and noise.is_contiguous() and tuple(noise.shape) == (B, ncand, C_)):
-            raise ValueError("noise: expected contiguous float32 GPU tensor (B=%d, ncand=%d, %d) on %s, got %s %s on %s"
-                             % (B, ncand, C_, self.device, tuple(getattr(noise, "shape", ())), getattr(noise, "dtype", type(noise)),
-                                getattr(noise, "device", None)))
+        self._check_tensor(noise, "noise", (("B=%d", B), ("ncand=%d", ncand), ("%d", C_)))
 
     def _cand_buffers(self, ncand):
         """The buffers of step_candidates() for `ncand` candidates per row: at the first use of that ncand, outside capture, and kept -
@@ -603,6 +611,14 @@ class SampleStream:
             return choice, None
         return None, _index_list("choice", choice, ncand, "the row's candidates", count=self.B, distinct=False)
 
+    def _upload_choice(self, buf, dev, host):
+        """commit()'s choice (_check_choice's pair) into the (B,) int32 device buffer the commit kernel reads; neither: the kernel picks."""
+        if dev is not None:
+            buf.copy_(dev)
+            dev.record_stream(torch.cuda.current_stream(self.device))
+        elif host is not None:
+            buf.copy_(torch.tensor(host, dtype=torch.int32).pin_memory(), non_blocking=True)
+
     @translate_oom
     def commit(self, choice=None):
         """Install one of the pending candidates of every row (step_candidates) as the row's frame t. choice: None - each row's
@@ -631,11 +647,7 @@ class SampleStream:
         dev, host = self._check_choice(choice, ncand)
         with self._owned():
             cand = self._cand[ncand]
-            if dev is not None:
-                cand.choice.copy_(dev)
-                dev.record_stream(torch.cuda.current_stream(self.device))
-            elif host is not None:
-                cand.choice.copy_(torch.tensor(host, dtype=torch.int32).pin_memory(), non_blocking=True)
+            self._upload_choice(cand.choice, dev, host)
             out = torch.empty(B, s.C, dtype=torch.float32, device=self.device)
             nll = torch.empty(B, dtype=torch.float32, device=self.device)
             picked = torch.empty(B, dtype=torch.int32, device=self.device)
@@ -656,16 +668,9 @@ class SampleStream:
         return self.commit()
 
     def _check_rollout_noise(self, noise, n, ncand):
-        """The prior draws of rollout_candidates(), (n, B, ncand, C) frame-major with n >= 1 (None: whatever it has) -> n. The wording
-        of _check_noise_many."""
+        """The prior draws of rollout_candidates(), (n, B, ncand, C) frame-major with n >= 1 (None: whatever it has) -> n."""
         B, C_ = self.B, self.eng.spec.C
-        ok = (torch.is_tensor(noise) and noise.is_cuda and noise.device == self.device and noise.dtype == torch.float32
-              and noise.is_contiguous() and noise.dim() == 4 and noise.shape[0] >= 1 and tuple(noise.shape[1:]) == (B, ncand, C_))
-        if not ok or (n is not None and noise.shape[0] != n):
-            raise ValueError("noise: expected contiguous float32 GPU tensor (%s, B=%d, ncand=%d, %d) on %s, frame-major, got %s %s on %s"
-                             % ("n>=1" if n is None else "n=%d" % n, B, ncand, C_, self.device, tuple(getattr(noise, "shape", ())),
-                                getattr(noise, "dtype", type(noise)), getattr(noise, "device", None)))
-        return int(noise.shape[0])
+        return self._check_tensor(noise, "noise", (self._frames_axis(n), ("B=%d", B), ("ncand=%d", ncand), ("%d", C_)), ", frame-major")
 
     def _rollout_cap(self, ncand):
         """Frames one rollout_candidates() call takes for ncand candidates per row - a rollout is ONE round, its candidates live in
@@ -781,11 +786,7 @@ class SampleStream:
         dev, host = self._check_choice(choice, ncand)
         with self._owned():
             L = eng.L
-            if dev is not None:
-                r.choice.copy_(dev)
-                dev.record_stream(torch.cuda.current_stream(self.device))
-            elif host is not None:
-                r.choice.copy_(torch.tensor(host, dtype=torch.int32).pin_memory(), non_blocking=True)
+            self._upload_choice(r.choice, dev, host)
             out = torch.empty(B, n, s.C, dtype=torch.float32, device=self.device)
             nll = torch.empty(n, B, dtype=torch.float32, device=self.device)
             picked = torch.empty(B, dtype=torch.int32, device=self.device)
@@ -826,13 +827,8 @@ class SampleStream:
         return self.commit()
 
     def _check_chunk(self, x, name, cols, n=None):
-        """A chunk's frames of one modality, (B, n, cols) with n >= 1 (None: whatever it has) -> n. The wording of _check_matrix."""
-        ok = (torch.is_tensor(x) and x.is_cuda and x.device == self.device and x.dtype == torch.float32 and x.is_contiguous()
-              and x.dim() == 3 and x.shape[0] == self.B and x.shape[1] >= 1 and x.shape[2] == cols)
-        if not ok or (n is not None and x.shape[1] != n):
-            raise ValueError("%s: expected contiguous float32 GPU tensor (B=%d, %s, %d) on %s, got %s %s on %s"
-                             % (name, self.B, "n>=1" if n is None else "n=%d" % n, cols, self.device,
-                                tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x)), getattr(x, "device", None)))
+        """A chunk's frames of one modality, (B, n, cols) with n >= 1 (None: whatever it has) -> n."""
+        self._check_tensor(x, name, (("B=%d", self.B), self._frames_axis(n), ("%d", cols)))
         return int(x.shape[1])
 
     def _check_lengths(self, lengths, n):
@@ -866,13 +862,7 @@ class SampleStream:
     def _check_noise_many(self, noise, n):
         """The prior draws of a chunk call, (n, B, C) frame-major with n >= 1 (None: whatever it has) -> n."""
         B, C_ = self.B, self.eng.spec.C
-        ok = (torch.is_tensor(noise) and noise.is_cuda and noise.device == self.device and noise.dtype == torch.float32
-              and noise.is_contiguous() and noise.dim() == 3 and noise.shape[0] >= 1 and tuple(noise.shape[1:]) == (B, C_))
-        if not ok or (n is not None and noise.shape[0] != n):
-            raise ValueError("noise: expected contiguous float32 GPU tensor (%s, B=%d, %d) on %s, frame-major, got %s %s on %s"
-                             % ("n>=1" if n is None else "n=%d" % n, B, C_, self.device, tuple(getattr(noise, "shape", ())),
-                                getattr(noise, "dtype", type(noise)), getattr(noise, "device", None)))
-        return int(noise.shape[0])
+        return self._check_tensor(noise, "noise", (self._frames_axis(n), ("B=%d", B), ("%d", C_)), ", frame-major")
 
     def _chunk_cap(self):
         """Frames one launch of the chunk chain takes: its hand-over slots are per frame and never reused inside a launch, and the
@@ -1468,64 +1458,55 @@ class SampleStream:
         dims.gemm_precision = self.frame_precision
         return dims, eng._flow_params()
 
+    def _frame_args(self, dims, p, first_frame, noise=None):
+        """What every per-frame chain's argument list starts with (_chain_args' counterpart for the session's own one-frame buffers):
+        the frame at slot hist1 of the hist1 + 1 frame faces window, from the session's live h / c. noise: the prior draws of a
+        chain that generates."""
+        s, eng = self.eng.spec, self.eng
+        args = (C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1, self.pre.data_ptr())
+        if noise is not None:
+            args += (noise.data_ptr(),)
+        return args + (self.faces.data_ptr(), self.hist1 + 1, self.hist1, 1, first_frame, self.h.data_ptr(), ptr(self.cs),
+                       C.byref(self._p1), self.p1work.data_ptr(), self.work.data_ptr())
+
     def _launch(self, masks, first_frame):
         """The static part, then the reverse chain for one frame: session-owned memory only."""
-        eng, s = self.eng, self.eng.spec
-        dims, p = self._static(masks)
+        eng = self.eng
+        args = self._frame_args(*self._static(masks), first_frame, self.noise)
         ev = eng._tic("stream_chain")
         if self.return_nll:
-            check(eng.L.lfi_flow_sample_seq_nll(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
-                                                self.pre.data_ptr(), self.noise.data_ptr(), self.faces.data_ptr(), self.hist1 + 1,
-                                                self.hist1, 1, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
-                                                self.p1work.data_ptr(), self.work.data_ptr(), self.nll.data_ptr(),
-                                                self.nll_work.data_ptr(), _stream()), "lfi_flow_sample_seq_nll")
-            eng._toc("stream_chain", ev)
-            return
-        check(eng.L.lfi_flow_sample_seq_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
-                                             self.pre.data_ptr(), self.noise.data_ptr(), self.faces.data_ptr(), self.hist1 + 1,
-                                             self.hist1, 1, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
-                                             self.p1work.data_ptr(), self.work.data_ptr(), _stream()), "lfi_flow_sample_seq_from")
+            check(eng.L.lfi_flow_sample_seq_nll(*args, self.nll.data_ptr(), self.nll_work.data_ptr(), _stream()), "lfi_flow_sample_seq_nll")
+        else:
+            check(eng.L.lfi_flow_sample_seq_from(*args, _stream()), "lfi_flow_sample_seq_from")
         eng._toc("stream_chain", ev)
 
     def _launch_observe(self, want_z, masks, first_frame):
         """The static part, then the forward chain on the observed frame the faces window holds: session-owned memory only. The latent
         is written only when it is wanted (z = NULL otherwise)."""
-        eng, s = self.eng, self.eng.spec
-        dims, p = self._static(masks)
+        eng = self.eng
+        args = self._frame_args(*self._static(masks), first_frame)
         ev = eng._tic("stream_observe_chain")
-        check(eng.L.lfi_flow_score_seq_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
-                                            self.pre.data_ptr(), self.faces.data_ptr(), self.hist1 + 1, self.hist1, 1, first_frame,
-                                            self.h.data_ptr(), ptr(self.cs), C.byref(self._p1), self.p1work.data_ptr(),
-                                            self.work.data_ptr(), self.score_work.data_ptr(), self.obs_z.data_ptr() if want_z else None,
+        check(eng.L.lfi_flow_score_seq_from(*args, self.score_work.data_ptr(), self.obs_z.data_ptr() if want_z else None,
                                             self.obs_nll.data_ptr(), _stream()), "lfi_flow_score_seq_from")
         eng._toc("stream_observe_chain", ev)
 
     def _launch_rows(self, masks, first_frame):
         """The static part, then both chains in one launch, each on the rows of its role (self.role): session-owned memory only."""
-        eng, s = self.eng, self.eng.spec
-        dims, p = self._static(masks)
+        eng = self.eng
+        args = self._frame_args(*self._static(masks), first_frame, self.noise)
         ev = eng._tic("stream_rows_chain")
-        check(eng.L.lfi_flow_step_rows_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
-                                            self.pre.data_ptr(), self.noise.data_ptr(), self.faces.data_ptr(), self.hist1 + 1,
-                                            self.hist1, 1, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
-                                            self.p1work.data_ptr(), self.work.data_ptr(), self.rows_nll.data_ptr(),
-                                            self.rows_nll_work.data_ptr(), self.role.data_ptr(), self.rows_work.data_ptr(), _stream()),
-              "lfi_flow_step_rows_from")
+        check(eng.L.lfi_flow_step_rows_from(*args, self.rows_nll.data_ptr(), self.rows_nll_work.data_ptr(), self.role.data_ptr(),
+                                            self.rows_work.data_ptr(), _stream()), "lfi_flow_step_rows_from")
         eng._toc("stream_rows_chain", ev)
 
     def _launch_cand(self, ncand, masks, first_frame):
         """The static part for B windows, then the front end for B rows and the candidate chain over B * ncand virtual rows: the
         session's faces window and h / c are read only, what the candidates leave goes to that ncand's buffers."""
-        eng, s = self.eng, self.eng.spec
-        cand = self._cand[ncand]
-        dims, p = self._static(masks)
+        eng, cand = self.eng, self._cand[ncand]
+        args = self._frame_args(*self._static(masks), first_frame, cand.noise)
         ev = eng._tic("stream_chain")
-        check(eng.L.lfi_flow_sample_cand_from(C.byref(dims), C.byref(p), eng.prep.data_ptr(), eng.wct_f.data_ptr(), s.ldf, self.hist1,
-                                              self.pre.data_ptr(), cand.noise.data_ptr(), self.faces.data_ptr(), self.hist1 + 1,
-                                              self.hist1, 1, first_frame, self.h.data_ptr(), ptr(self.cs), C.byref(self._p1),
-                                              self.p1work.data_ptr(), self.work.data_ptr(), None, None, ncand, cand.frames.data_ptr(),
-                                              cand.nll.data_ptr(), cand.h.data_ptr(), ptr(cand.c), cand.work.data_ptr(), _stream()),
-              "lfi_flow_sample_cand_from")
+        check(eng.L.lfi_flow_sample_cand_from(*args, None, None, ncand, cand.frames.data_ptr(), cand.nll.data_ptr(), cand.h.data_ptr(),
+                                              ptr(cand.c), cand.work.data_ptr(), _stream()), "lfi_flow_sample_cand_from")
         eng._toc("stream_chain", ev)
 
     def _publish_guard(self):

@@ -1,6 +1,6 @@
 """Host dispatch pinned (no GPU): for a fixed list of encoder descriptors, flow dims and switch settings the library answers every
 host-only query - which forward kernel, bias_part rows, bf16 gradient stash, fp16 gate stash, compact dgi, the walks' planes and
-reverse-walk predicates, every *_floats size - exactly as the commit named in tests/host_dispatch_expected.py did, where each switch
+reverse-walk predicates, the per-frame drivers' plan, every *_floats size - exactly as the commit named in tests/host_dispatch_expected.py did, where each switch
 setting was recorded in a fresh process (tools/record_host_dispatch.py). Here the switches change inside ONE process: equal answers also
 show that no switch is cached at its first read."""
 import importlib.util
@@ -73,3 +73,27 @@ def test_wide_switches_flipped_mid_process_agree_with_a_fresh_process(monkeypatc
                 differs.add(("variant",) + tuple(sw))
     # the check has teeth: each switch changes the recorded answer of at least one descriptor
     assert ("f16", "LFI_ENC_WIDE") in differs and ("f16", "LFI_ENC_WIDE_BWD") in differs and ("variant", "LFI_ENC_WIDE") in differs
+
+
+def test_frame_plan_switches_flipped_mid_process_agree_with_a_fresh_process(monkeypatch):
+    """lfi_flow_frame_plan - what every per-frame driver of a sampler or a streaming session decides from dims and switches - reads its
+    four switches at the call: flipped back and forth inside one process it answers as a fresh process under each setting does, and
+    each switch changes the recorded plan of at least one descriptor. The forward cells' three fp16 products (bit 16) are recorded for
+    per-frame arithmetic 9 alone: at 5, the range guard's fallback, an observed frame beyond fp16's range would leave NaN in h / c."""
+    L = _lib()
+    plan = E.FLOW_QUERIES.index("frame_plan")
+    flips = ({"LFI_SAMPLE_CHAIN": "0"}, {"LFI_SAMPLE_WFRAG16": "0"}, {"LFI_FLOW_GENERIC": "1"}, {"LFI_PIPE_X3": "0"})
+    differs = set()
+    for sw in ({},) + flips + ({},) + flips[::-1] + ({},):
+        _set(monkeypatch, sw)
+        want = E.EXPECTED[E.SWITCHES.index(sw)]["flow"]
+        for (name, dims), w, d in zip(E.FLOW_DIMS, want, E.EXPECTED[0]["flow"]):
+            g = rec.flow_answers(L, dims)[plan]
+            assert g == w[plan], "%s under %s: %#x, a fresh process answers %#x" % (name, sw or "defaults", g, w[plan])
+            if w[plan] != d[plan]:
+                differs.update(sw)
+    assert differs == {k for sw in flips for k in sw}
+    for row in E.EXPECTED:
+        for (name, dims), w in zip(E.FLOW_DIMS, row["flow"]):
+            assert not (w[plan] & 16) or (dims[-1] & 0xff) == 9, "%s: forward three-product cells recorded" % name
+    assert any(w[plan] & 16 for w in E.EXPECTED[0]["flow"])     # (and the bit is recorded somewhere: the rule is exercised)

@@ -21,6 +21,7 @@ SWITCHES = [
     {},
     {"LFI_ENC_WIDE": "0"}, {"LFI_ENC_WIDE_BWD": "0"}, {"LFI_ENC_R64": "0"}, {"LFI_ENC_M16": "0"}, {"LFI_ENC_T16": "0"}, {"LFI_ENC_T16": "2"},
     {"LFI_FLOW_GENERIC": "1"}, {"LFI_FLOW_PIPE": "0"}, {"LFI_PIPE_X3": "0"}, {"LFI_INVERT_WALK": "0"},
+    {"LFI_SAMPLE_CHAIN": "0"}, {"LFI_SAMPLE_WFRAG16": "0"},
 ]
 SWITCH_NAMES = sorted({k for s in SWITCHES for k in s})
 
@@ -61,7 +62,7 @@ def flow_dims():
 ENC_QUERIES = ["fwd_variant m0 s0", "fwd_variant m1 s0", "fwd_variant m0 s1", "fwd_variant m1 s1", "bias_rows", "grad_stash_bf16",
                "stash_f16_ok", "compact_dgi", "work_floats"]
 FLOW_QUERIES = ["bwd_emits_planes", "seq_rev_ok", "prep_floats", "stash_floats", "bstash_floats", "param_grads_work_floats",
-                "seq_rev_work_floats", "sample_work_floats", "sample_nll_work_floats"]
+                "seq_rev_work_floats", "sample_work_floats", "sample_nll_work_floats", "frame_plan"]
 
 
 def enc_answers(L, desc):
@@ -77,7 +78,7 @@ def flow_answers(L, dims):
     d = C.byref(FlowDims(*dims))
     return [L.lfi_flow_bwd_emits_planes(d), L.lfi_flow_seq_rev_ok(d), L.lfi_flow_prep_floats(d), L.lfi_flow_stash_floats(d),
             L.lfi_flow_bstash_floats(d), L.lfi_flow_param_grads_work_floats(d), L.lfi_flow_seq_rev_work_floats(d),
-            L.lfi_flow_sample_work_floats(d), L.lfi_flow_sample_nll_work_floats(d)]
+            L.lfi_flow_sample_work_floats(d), L.lfi_flow_sample_nll_work_floats(d), L.lfi_flow_frame_plan(d)]
 
 
 def answers(L):
