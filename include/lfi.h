@@ -770,6 +770,56 @@ int lfi_dropout_masks_dev(int count, float* const* out, const long* n, const flo
 int lfi_adam_clip_step_dev(float* p, const float* g, float* m, float* v, long n, const double* sumsq, float clip, float gmul,
                            float beta1, float beta2, float eps, const float* hyper /* = params + 16 bytes */, void* stream);
 
+/* ---------------------------------------------------------------- non-finite step guard
+ * A step whose flat gradient (after the all-reduce, after gmul) holds a NaN or an Inf is not taken: parameters, optimiser state and
+ * the running average keep their bits, Adam's t does not advance, a momentum buffer / average that did not exist still does not.
+ * This is torch.optim + clip_grad_norm_ + the EMA lerp with optimizer.step() and the EMA update not called on that step. The decision
+ * is taken on the device from the fp64 sum of squares (fp64 cannot overflow on 2^63 squares of fp32 values: the sum is finite exactly
+ * when every element is; gradients of +-3e38 are legal) and lives, with everything that depends on it, in a guard record of
+ * LFI_GUARD_SLOTS 8-byte slots that the caller allocates (8-byte aligned) and seeds:
+ *   SKIPPED, CONSECUTIVE, APPLIED  u64 counters (steps skipped / skipped in a row / taken);
+ *   LAST_NORM   fp64 sqrt(sumsq) * |gmul| of the last decide, before the clip (NaN / Inf on a skipped step);
+ *   MAX_NORM    fp64, the largest finite norm seen;
+ *   APPLY       u64, 1 = take this step, 0 = skip it;
+ *   STEP_FLOATS two fp32: step_size = lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t) for t = APPLIED, what the guarded Adam reads;
+ *   MOMENTUM_LIVE, AVERAGE_LIVE  u64: bit 0 = the momentum buffer / the average held a value BEFORE this step (what this step's
+ *               kernels read: 0 makes SGD set buf = g and the averaging copy), bit 1 = it holds one after it. Seed with 0 or 3.
+ * lfi_grad_guard = lfi_grad_sumsq (same stage 1, a second stage with the same adds in the same order: sumsq[0] has the same bits)
+ * whose last workgroup moves the record. flags: bit 0 = the optimiser behind it keeps a momentum buffer that a taken step
+ * initialises (SGD with momentum), bit 1 = an averaging update follows. step_size / inv_sqrt_bc2 are the host's floats for ITS step
+ * count t_host (1-based), computed as lfi_adam_clip_step computes them: they are taken as they are while APPLIED + 1 == t_host - every
+ * step until one has been skipped and the host has not yet read the record - and otherwise re-based on the device in fp64 to
+ * t = APPLIED + 1: step_size * (1 - beta1^t_host) / (1 - beta1^t), 1 / sqrt(1 - beta2^t). Optimisers without bias correction pass 0 / 0.
+ * The _dev form reads the two floats and t_host from a step-params block (lfi_set_step_params_t): a captured step.
+ * The _guard optimisers and lfi_ema_update_guard are lfi_adam_clip_step_ex (vmax NULL and weight_decay 0: lfi_adam_clip_step) /
+ * lfi_sgd_clip_step / lfi_rmsprop_clip_step / lfi_ema_update - same arithmetic, same bits - that return before their first load when
+ * APPLY == 0 and take the step floats, "first step" and copy-versus-lerp from the record. Refused calls launch nothing. */
+#define LFI_GUARD_SKIPPED 0
+#define LFI_GUARD_CONSECUTIVE 1
+#define LFI_GUARD_APPLIED 2
+#define LFI_GUARD_LAST_NORM 3
+#define LFI_GUARD_MAX_NORM 4
+#define LFI_GUARD_APPLY 5
+#define LFI_GUARD_STEP_FLOATS 6
+#define LFI_GUARD_MOMENTUM_LIVE 7
+#define LFI_GUARD_AVERAGE_LIVE 8
+#define LFI_GUARD_SLOTS 9
+int lfi_grad_guard(const float* g, long n, double* sumsq, double* work /* 1024 doubles */, void* rec, float gmul, int flags,
+                   float beta1, float beta2, float step_size, float inv_sqrt_bc2, unsigned long long t_host, void* stream);
+int lfi_grad_guard_dev(const float* g, long n, double* sumsq, double* work /* 1024 doubles */, void* rec, float gmul, int flags,
+                       float beta1, float beta2, const void* step_params, void* stream);
+int lfi_adam_clip_step_guard(float* p, const float* g, float* m, float* v, float* vmax, long n, const double* sumsq, float clip,
+                             float gmul, float beta1, float beta2, float eps, float weight_decay, const void* rec, void* stream);
+int lfi_sgd_clip_step_guard(float* p, const float* g, float* buf, long n, const double* sumsq, float clip, float gmul, float lr,
+                            float momentum, float dampening, float weight_decay, int nesterov, const void* rec, void* stream);
+int lfi_rmsprop_clip_step_guard(float* p, const float* g, float* sq, float* buf, float* gavg, long n, const double* sumsq, float clip,
+                                float gmul, float lr, float alpha, float eps, float weight_decay, float momentum, const void* rec,
+                                void* stream);
+int lfi_ema_update_guard(float* ema, const float* p, long n, float decay, const void* rec, void* stream);
+/* lfi_set_step_params plus the step number the two floats belong to, in the block's last 8 bytes (u64 t_host, 1-based). */
+int lfi_set_step_params_t(void* params, unsigned long long seed, unsigned long long offset, float step_size, float inv_sqrt_bc2,
+                          unsigned long long t_host, void* stream);
+
 /* ---------------------------------------------------------------- callers either side of the flow (SURVEY.md par. 8f)
  * Window sampler, replaces MimicryDataset.__getitem__ + DataLoader collation (code/glow_pytorch/mimicry_data_module.py:45-78):
  * one modality of a split lives in HBM as ONE (rows x dim) matrix, the recording bins back to back; a training window is T

@@ -209,6 +209,13 @@ def lib():
         "lfi_sgd_clip_step": (i, [vp, vp, vp, l, vp, f, f, f, f, f, f, i, i, vp]),
         "lfi_rmsprop_clip_step": (i, [vp, vp, vp, vp, vp, l, vp, f, f, f, f, f, f, f, vp]),
         "lfi_ema_update": (i, [vp, vp, l, f, vp]),
+        "lfi_grad_guard": (i, [vp, l, vp, vp, vp, f, i, f, f, f, f, C.c_ulonglong, vp]),
+        "lfi_grad_guard_dev": (i, [vp, l, vp, vp, vp, f, i, f, f, vp, vp]),
+        "lfi_adam_clip_step_guard": (i, [vp, vp, vp, vp, vp, l, vp, f, f, f, f, f, f, vp, vp]),
+        "lfi_sgd_clip_step_guard": (i, [vp, vp, vp, l, vp, f, f, f, f, f, f, i, vp, vp]),
+        "lfi_rmsprop_clip_step_guard": (i, [vp, vp, vp, vp, vp, l, vp, f, f, f, f, f, f, f, vp, vp]),
+        "lfi_ema_update_guard": (i, [vp, vp, l, f, vp, vp]),
+        "lfi_set_step_params_t": (i, [vp, C.c_ulonglong, C.c_ulonglong, f, f, C.c_ulonglong, vp]),
         "lfi_actnorm_forward": (i, [vp, i, i, vp, vp, i, vp, vp, vp]),
         "lfi_invconv_work_floats": (l, [i]),
         "lfi_invconv_weights": (i, [i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]),
@@ -247,7 +254,13 @@ EXPORTS = [
     "lfi_stream_save_rows", "lfi_stream_load_rows", "lfi_stream_create_partial", "lfi_stream_destroy", "lfi_grad_sumsq", "lfi_adam_clip_step", "lfi_adam_clip_step_ex",
     "lfi_sgd_clip_step", "lfi_rmsprop_clip_step", "lfi_ema_update", "lfi_set_step_params", "lfi_dropout_masks_dev", "lfi_adam_clip_step_dev", "lfi_selftest_mfma", "lfi_debug_set_stamps",
     "lfi_gather_sequences", "lfi_jerk_mean", "lfi_actnorm_forward", "lfi_invconv_work_floats", "lfi_invconv_weights",
+    "lfi_grad_guard", "lfi_grad_guard_dev", "lfi_adam_clip_step_guard", "lfi_sgd_clip_step_guard", "lfi_rmsprop_clip_step_guard",
+    "lfi_ema_update_guard", "lfi_set_step_params_t",
 ]
+
+# slots of the non-finite step guard's device record (include/lfi.h, LFI_GUARD_*): 8 bytes each
+GUARD_SKIPPED, GUARD_CONSECUTIVE, GUARD_APPLIED, GUARD_LAST_NORM, GUARD_MAX_NORM = 0, 1, 2, 3, 4
+GUARD_APPLY, GUARD_STEP_FLOATS, GUARD_MOMENTUM_LIVE, GUARD_AVERAGE_LIVE, GUARD_SLOTS = 5, 6, 7, 8, 9
 
 
 def translate_oom(fn):

@@ -376,6 +376,183 @@ __global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema
     for (long i = t0; i < n; i += stride) ema[i] += a * (p[i] - ema[i]);
   }
 }
+
+// ------------------------------------------------------------------ non-finite step guard
+// A step whose flat gradient holds a NaN or an Inf is not taken, decided on the device from the fp64 sum of squares the clip already
+// needs (fp64 cannot overflow on squares of fp32 values, so "the sum is finite" is "every element is finite"). The decision and
+// everything that depends on it live in a record of LFI_GUARD_SLOTS 8-byte slots (include/lfi.h). guard_decide_kernel is
+// sumsq_stage2 - the same loads, adds and order, so sumsq[0] has the same bits - whose lane 0 then moves the record. The guarded
+// optimiser and averaging kernels below are the arithmetic of the kernels above, statement by statement, behind `apply == 0 ->
+// return`; they are separate kernels so that the unguarded instruction streams stay the ones every parity figure was measured on.
+__global__ __launch_bounds__(256) void guard_decide_kernel(const double* __restrict__ part, int nparts, double* __restrict__ out,
+                                                           unsigned long long* __restrict__ rec, float gmul, int flags, float beta1,
+                                                           float beta2, float step_size, float inv_sqrt_bc2,
+                                                           unsigned long long t_host, const unsigned long long* __restrict__ step_params) {
+  __shared__ double red[4];
+  // everything the last lane needs from the record and the step-params block is asked for first: the loads travel under the sum
+  double* recd = reinterpret_cast<double*>(rec);
+  unsigned long long skipped = rec[LFI_GUARD_SKIPPED], consecutive = rec[LFI_GUARD_CONSECUTIVE], applied = rec[LFI_GUARD_APPLIED];
+  const unsigned long long live[2] = {rec[LFI_GUARD_MOMENTUM_LIVE], rec[LFI_GUARD_AVERAGE_LIVE]};
+  const double max_norm = recd[LFI_GUARD_MAX_NORM];
+  if (step_params) {      // a captured step: the host's floats and its t live in the step-params block
+    const float* f = reinterpret_cast<const float*>(step_params + 2);
+    step_size = f[0];
+    inv_sqrt_bc2 = f[1];
+    t_host = step_params[3];
+  }
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
+  s = wave_sum_d(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double total = (red[0] + red[1]) + (red[2] + red[3]);
+  out[0] = total;
+  const double norm = sqrt(total) * (double)fabsf(gmul);
+  const bool apply = fabs(norm) <= 1.79769313486231570815e308;      // false for NaN and Inf
+  recd[LFI_GUARD_LAST_NORM] = norm;
+  if (apply) {
+    // the host's floats belong to ITS step count: right until a step has been skipped that the host has not yet heard of. From then
+    // on they are re-based in fp64 to t = applied + 1: step_size = lr / (1 - beta1^t) = host's * (1 - beta1^t_host) / (1 - beta1^t)
+    // (the learning rate itself never comes here: a captured step holds only the product), 1 / sqrt(1 - beta2^t) directly.
+    const unsigned long long t = applied + 1;
+    if (t != t_host) {
+      const double b1 = (double)beta1, b2 = (double)beta2;
+      step_size = (float)((double)step_size * (1.0 - pow(b1, (double)t_host)) / (1.0 - pow(b1, (double)t)));
+      inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(b2, (double)t)));
+    }
+    float* recf = reinterpret_cast<float*>(rec + LFI_GUARD_STEP_FLOATS);
+    recf[0] = step_size;
+    recf[1] = inv_sqrt_bc2;
+    applied = t;
+    consecutive = 0;
+    if (!(norm <= max_norm)) recd[LFI_GUARD_MAX_NORM] = norm;
+  } else {
+    ++skipped;
+    ++consecutive;
+  }
+  rec[LFI_GUARD_SKIPPED] = skipped;
+  rec[LFI_GUARD_CONSECUTIVE] = consecutive;
+  rec[LFI_GUARD_APPLIED] = applied;
+  rec[LFI_GUARD_APPLY] = apply ? 1ull : 0ull;
+  // live flags: bit 0 = what THIS step's kernels read (the state before the step), bit 1 = the state after it. A kernel cannot flip
+  // its own flag (its later workgroups would read the new value), so the flip is made here, one step late for bit 0.
+  for (int k = 0; k < 2; ++k) {
+    const unsigned long long before = (live[k] >> 1) & 1ull;
+    const unsigned long long after = before | ((apply && ((flags >> k) & 1)) ? 1ull : 0ull);
+    rec[LFI_GUARD_MOMENTUM_LIVE + k] = before | (after << 1);
+  }
+}
+
+template <bool WD, bool AMS>
+__global__ __launch_bounds__(256) void adam_guard_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, float* __restrict__ vmax, long n,
+                                                         const double* __restrict__ sumsq, float clip, float gmul, float beta1,
+                                                         float beta2, float eps, float weight_decay,
+                                                         const unsigned long long* __restrict__ rec) {
+  if (rec[LFI_GUARD_APPLY] == 0) return;
+  const float* hyper = reinterpret_cast<const float*>(rec + LFI_GUARD_STEP_FLOATS);
+  const float step_size = hyper[0], inv_sqrt_bc2 = hyper[1];
+  const float coef = clip_coef(sumsq, clip, gmul);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float pi = p[i];
+    float gi = g[i] * coef;
+    if (WD) gi = gi + weight_decay * pi;
+    const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
+    const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    float vd = vi;
+    if (AMS) {
+      vd = fmaxf(vmax[i], vi);
+      vmax[i] = vd;
+    }
+    const float denom = sqrtf(vd) * inv_sqrt_bc2 + eps;
+    p[i] = pi - step_size * (mi / denom);
+  }
+}
+
+__global__ __launch_bounds__(256) void sgd_guard_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long n,
+                                                        const double* __restrict__ sumsq, float clip, float gmul, float lr,
+                                                        float momentum, float dampening, float weight_decay, int nesterov,
+                                                        const unsigned long long* __restrict__ rec) {
+  if (rec[LFI_GUARD_APPLY] == 0) return;
+  const int first = (rec[LFI_GUARD_MOMENTUM_LIVE] & 1ull) == 0;      // "no momentum buffer yet", as the device knows it
+  const float coef = clip_coef(sumsq, clip, gmul);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float pi = p[i];
+    float gi = g[i] * coef;
+    if (weight_decay != 0.0f) gi = gi + weight_decay * pi;
+    if (momentum != 0.0f) {
+      const float bi = first ? gi : momentum * buf[i] + (1.0f - dampening) * gi;
+      buf[i] = bi;
+      gi = nesterov ? gi + momentum * bi : bi;
+    }
+    p[i] = pi - lr * gi;
+  }
+}
+
+__global__ __launch_bounds__(256) void rmsprop_guard_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sq,
+                                                            float* __restrict__ buf, float* __restrict__ gavg, long n,
+                                                            const double* __restrict__ sumsq, float clip, float gmul, float lr,
+                                                            float alpha, float eps, float weight_decay, float momentum,
+                                                            const unsigned long long* __restrict__ rec) {
+  if (rec[LFI_GUARD_APPLY] == 0) return;
+  const float coef = clip_coef(sumsq, clip, gmul);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float pi = p[i];
+    float gi = g[i] * coef;
+    if (weight_decay != 0.0f) gi = gi + weight_decay * pi;
+    const float si = alpha * sq[i] + (1.0f - alpha) * gi * gi;
+    sq[i] = si;
+    float avg;
+    if (gavg) {
+      const float ga = gavg[i] + (1.0f - alpha) * (gi - gavg[i]);
+      gavg[i] = ga;
+      avg = sqrtf(si - ga * ga) + eps;
+    } else {
+      avg = sqrtf(si) + eps;
+    }
+    if (momentum > 0.0f) {
+      const float bi = momentum * buf[i] + gi / avg;
+      buf[i] = bi;
+      p[i] = pi - lr * bi;
+    } else {
+      p[i] = pi - lr * (gi / avg);
+    }
+  }
+}
+
+// the averaging behind a guarded optimiser: nothing on a skipped step, a copy while the record says "no average yet", else the lerp
+template <bool VEC>
+__global__ __launch_bounds__(256) void ema_guard_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float a,
+                                                        const unsigned long long* __restrict__ rec) {
+  if (rec[LFI_GUARD_APPLY] == 0) return;
+  const bool copy = (rec[LFI_GUARD_AVERAGE_LIVE] & 1ull) == 0;      // (ema + 1 * (p - ema) is not p in floating point: a real copy)
+  const long t0 = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+  if (VEC) {
+    const long n4 = n >> 2;
+    float4* __restrict__ e4 = reinterpret_cast<float4*>(ema);
+    const float4* __restrict__ p4 = reinterpret_cast<const float4*>(p);
+    for (long i = t0; i < n4; i += stride) {
+      const float4 q = p4[i];
+      if (copy) {
+        e4[i] = q;
+        continue;
+      }
+      float4 e = e4[i];
+      e.x += a * (q.x - e.x);
+      e.y += a * (q.y - e.y);
+      e.z += a * (q.z - e.z);
+      e.w += a * (q.w - e.w);
+      e4[i] = e;
+    }
+    const long i = (n4 << 2) + t0;   // tail: at most three floats
+    if (i < n) ema[i] = copy ? p[i] : ema[i] + a * (p[i] - ema[i]);
+  } else {
+    for (long i = t0; i < n; i += stride) ema[i] = copy ? p[i] : ema[i] + a * (p[i] - ema[i]);
+  }
+}
 }  // namespace
 
 extern "C" int lfi_ema_update(float* ema, const float* p, long n, float decay, void* stream) {
@@ -482,3 +659,109 @@ extern "C" int lfi_adam_clip_step_dev(float* p, const float* g, float* m, float*
   LFI_LAUNCH_CHECK("lfi_adam_clip_step_dev");
   return LFI_OK;
 }
+
+// ------------------------------------------------------------------ non-finite step guard: entry points
+static int grad_guard_launch(const char* who, const float* g, long n, double* sumsq, double* work, void* rec, float gmul, int flags,
+                             float beta1, float beta2, float step_size, float inv_sqrt_bc2, unsigned long long t_host,
+                             const void* step_params, void* stream) {
+  LFI_REQUIRE(g && sumsq && work && n >= 0, "%s: bad arguments", who);
+  LFI_REQUIRE(rec && (reinterpret_cast<uintptr_t>(rec) & 7) == 0, "%s: null / misaligned guard record", who);
+  LFI_REQUIRE((flags & ~3) == 0, "%s: unknown flag bits %d", who, flags);
+  LFI_REQUIRE(beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f, "%s: betas must lie in [0, 1) (NaN is refused)", who);
+  hipStream_t st = (hipStream_t)stream;
+  const int blocks = (int)min((long)SUMSQ_BLOCKS, (long)lfi_cdiv(n > 0 ? n : 1, 256));
+  hipLaunchKernelGGL(sumsq_stage1, dim3(blocks), dim3(256), 0, st, g, n, work);
+  LFI_LAUNCH_CHECK(who);
+  hipLaunchKernelGGL(guard_decide_kernel, dim3(1), dim3(256), 0, st, (const double*)work, blocks, sumsq,
+                     reinterpret_cast<unsigned long long*>(rec), gmul, flags, beta1, beta2, step_size, inv_sqrt_bc2, t_host,
+                     reinterpret_cast<const unsigned long long*>(step_params));
+  LFI_LAUNCH_CHECK(who);
+  return LFI_OK;
+}
+
+extern "C" int lfi_grad_guard(const float* g, long n, double* sumsq, double* work, void* rec, float gmul, int flags, float beta1,
+                              float beta2, float step_size, float inv_sqrt_bc2, unsigned long long t_host, void* stream) {
+  LFI_REQUIRE(t_host >= 1, "lfi_grad_guard: t_host is 1-based");
+  return grad_guard_launch("lfi_grad_guard", g, n, sumsq, work, rec, gmul, flags, beta1, beta2, step_size, inv_sqrt_bc2, t_host,
+                           nullptr, stream);
+}
+
+extern "C" int lfi_grad_guard_dev(const float* g, long n, double* sumsq, double* work, void* rec, float gmul, int flags, float beta1,
+                                  float beta2, const void* step_params, void* stream) {
+  LFI_REQUIRE(step_params && (reinterpret_cast<uintptr_t>(step_params) & 7) == 0, "lfi_grad_guard_dev: null / misaligned step params");
+  return grad_guard_launch("lfi_grad_guard_dev", g, n, sumsq, work, rec, gmul, flags, beta1, beta2, 0.0f, 0.0f, 0ull, step_params,
+                           stream);
+}
+
+#define LFI_REQUIRE_GUARD_REC(who) \
+  LFI_REQUIRE(rec && (reinterpret_cast<uintptr_t>(rec) & 7) == 0, who ": null / misaligned guard record")
+
+extern "C" int lfi_adam_clip_step_guard(float* p, const float* g, float* m, float* v, float* vmax, long n, const double* sumsq,
+                                        float clip, float gmul, float beta1, float beta2, float eps, float weight_decay,
+                                        const void* rec, void* stream) {
+  LFI_REQUIRE(p && g && m && v && n >= 0, "lfi_adam_clip_step_guard: bad arguments");
+  LFI_REQUIRE(clip <= 0.0f || sumsq, "lfi_adam_clip_step_guard: clipping needs sumsq");
+  LFI_REQUIRE(weight_decay >= 0.0f, "lfi_adam_clip_step_guard: weight_decay < 0 (torch.optim.Adam raises too)");
+  LFI_REQUIRE_GUARD_REC("lfi_adam_clip_step_guard");
+  const int blocks = (int)min(2048L, (long)lfi_cdiv(n > 0 ? n : 1, 256));
+  const bool wd = weight_decay != 0.0f, ams = vmax != nullptr;
+#define LFI_ADAM_GUARD(W, A)                                                                                                     \
+  hipLaunchKernelGGL((adam_guard_kernel<W, A>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, n, sumsq, clip, \
+                     gmul, beta1, beta2, eps, weight_decay, reinterpret_cast<const unsigned long long*>(rec))
+  if (wd && ams) LFI_ADAM_GUARD(true, true);
+  else if (wd) LFI_ADAM_GUARD(true, false);
+  else if (ams) LFI_ADAM_GUARD(false, true);
+  else LFI_ADAM_GUARD(false, false);
+#undef LFI_ADAM_GUARD
+  LFI_LAUNCH_CHECK("lfi_adam_clip_step_guard");
+  return LFI_OK;
+}
+
+extern "C" int lfi_sgd_clip_step_guard(float* p, const float* g, float* buf, long n, const double* sumsq, float clip, float gmul,
+                                       float lr, float momentum, float dampening, float weight_decay, int nesterov, const void* rec,
+                                       void* stream) {
+  LFI_REQUIRE(p && g && n >= 0, "lfi_sgd_clip_step_guard: bad arguments");
+  LFI_REQUIRE(momentum == 0.0f || buf, "lfi_sgd_clip_step_guard: momentum needs its buffer");
+  LFI_REQUIRE(clip <= 0.0f || sumsq, "lfi_sgd_clip_step_guard: clipping needs sumsq");
+  LFI_REQUIRE(!nesterov || (momentum > 0.0f && dampening == 0.0f),
+              "lfi_sgd_clip_step_guard: nesterov needs momentum > 0 and dampening 0");
+  LFI_REQUIRE_GUARD_REC("lfi_sgd_clip_step_guard");
+  const int blocks = (int)min(2048L, (long)lfi_cdiv(n > 0 ? n : 1, 256));
+  hipLaunchKernelGGL(sgd_guard_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, sumsq, clip, gmul, lr, momentum,
+                     dampening, weight_decay, nesterov ? 1 : 0, reinterpret_cast<const unsigned long long*>(rec));
+  LFI_LAUNCH_CHECK("lfi_sgd_clip_step_guard");
+  return LFI_OK;
+}
+
+extern "C" int lfi_rmsprop_clip_step_guard(float* p, const float* g, float* sq, float* buf, float* gavg, long n, const double* sumsq,
+                                           float clip, float gmul, float lr, float alpha, float eps, float weight_decay,
+                                           float momentum, const void* rec, void* stream) {
+  LFI_REQUIRE(p && g && sq && n >= 0, "lfi_rmsprop_clip_step_guard: bad arguments");
+  LFI_REQUIRE(momentum <= 0.0f || buf, "lfi_rmsprop_clip_step_guard: momentum needs its buffer");
+  LFI_REQUIRE(clip <= 0.0f || sumsq, "lfi_rmsprop_clip_step_guard: clipping needs sumsq");
+  LFI_REQUIRE_GUARD_REC("lfi_rmsprop_clip_step_guard");
+  const int blocks = (int)min(2048L, (long)lfi_cdiv(n > 0 ? n : 1, 256));
+  hipLaunchKernelGGL(rmsprop_guard_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, sq, buf, gavg, n, sumsq, clip, gmul,
+                     lr, alpha, eps, weight_decay, momentum, reinterpret_cast<const unsigned long long*>(rec));
+  LFI_LAUNCH_CHECK("lfi_rmsprop_clip_step_guard");
+  return LFI_OK;
+}
+
+extern "C" int lfi_ema_update_guard(float* ema, const float* p, long n, float decay, const void* rec, void* stream) {
+  LFI_REQUIRE(n >= 0, "lfi_ema_update_guard: n < 0");
+  LFI_REQUIRE(decay >= 0.0f && decay < 1.0f, "lfi_ema_update_guard: decay must lie in [0, 1) (NaN is refused)");
+  LFI_REQUIRE_GUARD_REC("lfi_ema_update_guard");
+  if (n == 0) return LFI_OK;
+  LFI_REQUIRE(ema && p, "lfi_ema_update_guard: null pointer");
+  const uintptr_t e0 = (uintptr_t)ema, p0 = (uintptr_t)p, bytes = (uintptr_t)n * sizeof(float);
+  LFI_REQUIRE(e0 + bytes <= p0 || p0 + bytes <= e0, "lfi_ema_update_guard: the average and the parameters overlap");
+  const float a = (float)(1.0 - (double)decay);
+  const bool vec = ((e0 | p0) & 15) == 0;
+  const int blocks = (int)min(2048L, (long)lfi_cdiv(vec ? (n + 3) / 4 : n, 256));
+  const unsigned long long* r = reinterpret_cast<const unsigned long long*>(rec);
+  if (vec) hipLaunchKernelGGL(ema_guard_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ema, p, n, a, r);
+  else hipLaunchKernelGGL(ema_guard_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ema, p, n, a, r);
+  LFI_LAUNCH_CHECK("lfi_ema_update_guard");
+  return LFI_OK;
+}
+#undef LFI_REQUIRE_GUARD_REC

@@ -171,6 +171,26 @@ extern "C" int lfi_set_step_params(void* params, unsigned long long seed, unsign
   LFI_LAUNCH_CHECK("lfi_set_step_params");
   return LFI_OK;
 }
+// With the non-finite step guard on, the block's last 8 bytes hold the step number the two floats were computed for (u64 t_host):
+// lfi_grad_guard_dev compares it with the device's own count of applied steps.
+namespace {
+__global__ void set_step_params_t_kernel(unsigned long long* p, unsigned long long seed, unsigned long long offset, float step_size,
+                                         float inv_sqrt_bc2, unsigned long long t_host) {
+  p[0] = seed; p[1] = offset;
+  float* f = reinterpret_cast<float*>(p + 2);
+  f[0] = step_size; f[1] = inv_sqrt_bc2;
+  p[3] = t_host;
+}
+}  // namespace
+extern "C" int lfi_set_step_params_t(void* params, unsigned long long seed, unsigned long long offset, float step_size,
+                                     float inv_sqrt_bc2, unsigned long long t_host, void* stream) {
+  LFI_REQUIRE(params && (reinterpret_cast<uintptr_t>(params) & 7) == 0, "lfi_set_step_params_t: null / misaligned buffer");
+  LFI_REQUIRE(t_host >= 1, "lfi_set_step_params_t: t_host is 1-based");
+  hipLaunchKernelGGL(set_step_params_t_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, reinterpret_cast<unsigned long long*>(params),
+                     seed, offset, step_size, inv_sqrt_bc2, t_host);
+  LFI_LAUNCH_CHECK("lfi_set_step_params_t");
+  return LFI_OK;
+}
 static int dropout_masks_launch(int count, float* const* out, const long* n, const float* keep, unsigned long long seed,
                                 unsigned long long offset, const unsigned long long* key, void* stream) {
   LFI_REQUIRE(count >= 0 && count <= 4, "lfi_dropout_masks: %d segments (at most 4)", count);

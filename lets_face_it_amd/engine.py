@@ -212,6 +212,11 @@ class GlowEngine:
         self.ema = None
         self.ema_updates = 0
         self._ema_swapped = False
+        # non-finite step guard (enable_step_guard): the device record of include/lfi.h (LFI_GUARD_SLOTS 8-byte slots), None while
+        # off; `_guard_counts`: counters of a loaded state, waiting for the record to be made
+        self.guard = None
+        self._guard_averaging = False
+        self._guard_counts = None
         # bumped by every optimiser step, parameter load and data-dependent ActNorm init: a streaming sampling session (SampleStream)
         # records it at open and refuses to step once it has moved (its prepared weights are those of the open)
         self.param_version = 0
@@ -1320,6 +1325,16 @@ class GlowEngine:
         if amsgrad and self.__dict__.get("opt_aux") is None:
             self.opt_aux = torch.zeros_like(self.params)
         st = _stream()
+        if self.guard is not None:
+            floats = (0.0, 0.0) if hyper_dev is not None else self.adam_step_floats(lr, beta1, beta2, self.step_count + 1)
+            self._guard_decide(gmul, 0, beta1, beta2, floats, hyper_dev)
+            if hyper_dev is None:
+                self.step_count += 1
+            check(self.L.lfi_adam_clip_step_guard(self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(),
+                                                  self.adam_v.data_ptr(), ptr(self.opt_aux if amsgrad else None), self.n_params,
+                                                  self.sumsq.data_ptr(), float(clip or 0.0), gmul, beta1, beta2, eps,
+                                                  float(weight_decay), self.guard.data_ptr(), st), "lfi_adam_clip_step_guard")
+            return
         if clip and clip > 0:
             check(self.L.lfi_grad_sumsq(self.grads.data_ptr(), self.n_params, self.sumsq.data_ptr(),
                                         self.sumsq_work.data_ptr(), st), "lfi_grad_sumsq")
@@ -1355,6 +1370,17 @@ class GlowEngine:
         if momentum and self.adam_m is None:
             self.adam_m = torch.zeros_like(self.params)
         st = _stream()
+        if self.guard is not None:
+            # "first" is the device's to know: a skipped first step leaves the next one the first (the record's live flag)
+            self._guard_decide(gmul, 1 if momentum else 0)
+            self.step_count += 1
+            check(self.L.lfi_sgd_clip_step_guard(self.params.data_ptr(), self.grads.data_ptr(), ptr(self.adam_m if momentum else None),
+                                                 self.n_params, self.sumsq.data_ptr(), float(clip or 0.0), gmul, lr, float(momentum),
+                                                 float(dampening), float(weight_decay), 1 if nesterov else 0, self.guard.data_ptr(),
+                                                 st), "lfi_sgd_clip_step_guard")
+            if momentum:
+                self._momentum_inited = True      # (the host's belief; guard_state() puts the device's in its place)
+            return
         if clip and clip > 0:
             check(self.L.lfi_grad_sumsq(self.grads.data_ptr(), self.n_params, self.sumsq.data_ptr(),
                                         self.sumsq_work.data_ptr(), st), "lfi_grad_sumsq")
@@ -1380,6 +1406,15 @@ class GlowEngine:
         if centered and self.__dict__.get("opt_aux") is None:
             self.opt_aux = torch.zeros_like(self.params)
         st = _stream()
+        if self.guard is not None:
+            self._guard_decide(gmul, 0)
+            self.step_count += 1
+            check(self.L.lfi_rmsprop_clip_step_guard(self.params.data_ptr(), self.grads.data_ptr(), self.adam_v.data_ptr(),
+                                                     ptr(self.adam_m if momentum else None), ptr(self.opt_aux if centered else None),
+                                                     self.n_params, self.sumsq.data_ptr(), float(clip or 0.0), gmul, lr, float(alpha),
+                                                     float(eps), float(weight_decay), float(momentum), self.guard.data_ptr(), st),
+                  "lfi_rmsprop_clip_step_guard")
+            return
         if clip and clip > 0:
             check(self.L.lfi_grad_sumsq(self.grads.data_ptr(), self.n_params, self.sumsq.data_ptr(),
                                         self.sumsq_work.data_ptr(), st), "lfi_grad_sumsq")
@@ -1397,6 +1432,10 @@ class GlowEngine:
 
     def _launch_ema_update(self, decay):
         """The launch alone, uncounted: ema_update, and the node a captured training step records behind its optimiser."""
+        if self.guard is not None:
+            check(self.L.lfi_ema_update_guard(self.ema.data_ptr(), self.params.data_ptr(), self.n_params, float(decay),
+                                              self.guard.data_ptr(), _stream()), "lfi_ema_update_guard")
+            return
         check(self.L.lfi_ema_update(self.ema.data_ptr(), self.params.data_ptr(), self.n_params, float(decay), _stream()), "lfi_ema_update")
 
     @translate_oom
@@ -1413,6 +1452,10 @@ class GlowEngine:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("ema_update: the first update allocates the average; it cannot run inside a stream capture")
             self.ema = self.params.detach().clone()
+            if self.guard is not None:
+                # the buffer exists from the first step on, as without the guard; whether that step made it an average (a copy of
+                # the parameters it produced), and whether later ones lerp or still have to copy, is the record's live flag
+                self._launch_ema_update(decay)
         else:
             self._launch_ema_update(decay)
         self.ema_updates += 1
@@ -1422,7 +1465,9 @@ class GlowEngine:
         address) and move the parameter version: `prep`, folded weights, parameter planes and open streaming sessions see a parameter
         change exactly as after an optimiser step. Not on the step path: torch copies through one temporary. While the average sits in
         `params` the optimiser steps, ema_update and backward raise; the flag is part of no checkpoint."""
-        if self.ema is None:
+        if self.guard is not None and not self._ema_swapped:
+            self.guard_state()      # (a buffer whose every update was skipped holds no average yet)
+        if self.ema is None or (self.guard is not None and self.ema_updates == 0 and not self._ema_swapped):
             raise RuntimeError("swap_ema: no averaged weights exist (Optim.ema_decay unset, or no update has run yet)")
         tmp = self.params.clone()
         self.params.copy_(self.ema)
@@ -1439,7 +1484,14 @@ class GlowEngine:
         if self._ema_swapped:
             raise RuntimeError("optimizer_state while the averaged weights are swapped in: `ema` holds the raw parameters now")
         aux = self.__dict__.get("opt_aux")
-        return {"step_count": int(self.step_count),
+        guard = {}
+        if self.guard is not None:
+            # one device wait; puts the device's counts in place of the host's beliefs below
+            guard = {"guard": {k: v for k, v in self.guard_state().items() if k in ("skipped", "consecutive", "applied", "max_norm")}}
+        elif self._guard_counts:
+            guard = {"guard": dict(self._guard_counts)}
+        live = self.ema is not None and (self.guard is None or self.ema_updates > 0)
+        return {**guard, "step_count": int(self.step_count),
                 "optimizer": self.__dict__.get("_opt_name"),
                 "momentum_inited": bool(self.__dict__.get("_momentum_inited", False)),
                 "opt_aux": None if aux is None else aux.detach().clone(),
@@ -1448,8 +1500,8 @@ class GlowEngine:
                 "mask_calls": int(self._mask_calls),
                 "adam_m": None if self.adam_m is None else self.adam_m.detach().clone(),
                 "adam_v": None if self.adam_v is None else self.adam_v.detach().clone(),
-                "ema": None if self.ema is None else self.ema.detach().clone(),
-                "ema_updates": int(self.ema_updates)}
+                "ema": self.ema.detach().clone() if live else None,
+                "ema_updates": int(self.ema_updates) if live else 0}
 
     def load_optimizer_state(self, state):
         self.step_count = int(state.get("step_count", 0))
@@ -1467,6 +1519,61 @@ class GlowEngine:
             if t.numel() != self.n_params:
                 raise ValueError("optimizer state holds %d floats, the model has %d parameters" % (t.numel(), self.n_params))
             setattr(self, name, t.to(device=self.device, dtype=torch.float32).reshape(-1).clone())
+        # the guard's counters (absent - older checkpoints - means zeros); `applied` and the live flags follow from the state above
+        self._guard_counts = dict(state["guard"]) if state.get("guard") else None
+        if self.guard is not None:
+            self._seed_guard()
+
+    # ------------------------------------------------------------------ non-finite step guard
+    def enable_step_guard(self, averaging=False):
+        """Skip optimiser steps whose gradient holds a NaN or an Inf, decided on the device (include/lfi.h, lfi_grad_guard): from now
+        on optimizer_step*, ema_update and the captured step's nodes are the guarded entry points, and every step launches the decide
+        kernel whether or not it clips. Allocates the record and seeds it: `applied` from step_count, the live flags from
+        _momentum_inited and ema_updates, the counters from a loaded state (else zero). averaging: an ema_update follows every
+        optimiser step (the decide kernel keeps the average's live flag). Idempotent; never inside a stream capture."""
+        self._guard_averaging = bool(averaging)
+        if self.guard is None:
+            self.guard = torch.zeros(_lib.GUARD_SLOTS, dtype=torch.int64, device=self.device)
+            self._seed_guard()
+
+    def _seed_guard(self):
+        c = self._guard_counts or {}
+        host = torch.zeros(_lib.GUARD_SLOTS, dtype=torch.int64)
+        host[_lib.GUARD_SKIPPED] = int(c.get("skipped", 0))
+        host[_lib.GUARD_CONSECUTIVE] = int(c.get("consecutive", 0))
+        host[_lib.GUARD_APPLIED] = int(self.step_count)
+        host.view(torch.float64)[_lib.GUARD_MAX_NORM] = float(c.get("max_norm", 0.0))
+        host[_lib.GUARD_MOMENTUM_LIVE] = 3 if self.adam_m is not None and self.__dict__.get("_momentum_inited", False) else 0
+        host[_lib.GUARD_AVERAGE_LIVE] = 3 if self.ema is not None and self.ema_updates > 0 else 0
+        self.guard.copy_(host)      # (in place: a captured step holds the record by address)
+
+    def _guard_decide(self, gmul, flags, beta1=0.0, beta2=0.0, floats=(0.0, 0.0), hyper_dev=None):
+        """Sum of squares + the decision for this step (two launches, as lfi_grad_sumsq's: the second stage IS the
+        decision). hyper_dev: the floats of a captured step's params block (its base is 16 bytes below), t_host beside them."""
+        flags |= 2 if self._guard_averaging else 0
+        g, n, ss, work, rec = self.grads.data_ptr(), self.n_params, self.sumsq.data_ptr(), self.sumsq_work.data_ptr(), self.guard.data_ptr()
+        if hyper_dev is not None:
+            check(self.L.lfi_grad_guard_dev(g, n, ss, work, rec, gmul, flags, beta1, beta2, hyper_dev - 16, _stream()),
+                  "lfi_grad_guard_dev")
+        else:
+            check(self.L.lfi_grad_guard(g, n, ss, work, rec, gmul, flags, beta1, beta2, floats[0], floats[1], self.step_count + 1,
+                                        _stream()), "lfi_grad_guard")
+
+    def guard_state(self):
+        """{skipped, consecutive, applied, last_norm, max_norm} as the device holds them: one copy of the record, one wait. Also puts
+        the device's counts in place of the host's beliefs - step_count = applied, ema_updates less the skipped steps it counted (0
+        while the average is not live), SGD's "momentum buffer written" - so that the next step's t_host matches again."""
+        if self.guard is None:
+            raise RuntimeError("guard_state: the step guard is off (enable_step_guard / Optim.skip_nonfinite)")
+        host = self.guard.cpu()
+        f64 = host.view(torch.float64)
+        applied = int(host[_lib.GUARD_APPLIED])
+        unseen = int(self.step_count) - applied      # steps the host counted that were not taken
+        self.step_count = applied
+        self.ema_updates = max(1, self.ema_updates - unseen) if int(host[_lib.GUARD_AVERAGE_LIVE]) >> 1 else 0
+        self._momentum_inited = bool(int(host[_lib.GUARD_MOMENTUM_LIVE]) >> 1)
+        return {"skipped": int(host[_lib.GUARD_SKIPPED]), "consecutive": int(host[_lib.GUARD_CONSECUTIVE]), "applied": applied,
+                "last_norm": float(f64[_lib.GUARD_LAST_NORM]), "max_norm": float(f64[_lib.GUARD_MAX_NORM])}
 
     def grad_norm(self):
         check(self.L.lfi_grad_sumsq(self.grads.data_ptr(), self.n_params, self.sumsq.data_ptr(),

@@ -35,10 +35,50 @@ def ema_decay_of(hparams):
     return float(value)
 
 
+def track_grad_norm_of(hparams):
+    """Lightning's `track_grad_norm`: -1 (absent, None) = off, 2 = the Trainer's log line carries the 2-norm of the flat gradient and
+    the number of skipped steps, both read from the step guard's record. No other norm is kept: NotImplementedError."""
+    value = getattr(hparams, "track_grad_norm", None)
+    if value is None or (not isinstance(value, bool) and isinstance(value, (int, float)) and value == -1):
+        return -1
+    if not isinstance(value, bool) and isinstance(value, (int, float)) and value == 2:
+        return 2
+    raise NotImplementedError("track_grad_norm must be -1 (off) or 2 (the 2-norm the clip computes anyway); got %r" % (value,))
+
+
+def skip_nonfinite_of(hparams):
+    """Whether optimiser steps whose gradient holds a NaN or an Inf are skipped on the device (the non-finite step guard):
+    Optim["skip_nonfinite"], a bool - absent, None or False = off. `terminate_on_nan: true` implies it (the Trainer stops at the first
+    skip it observes, with clean weights), and so does `track_grad_norm: 2` (the norm is read from the guard's record). Anything but a
+    bool raises ValueError."""
+    value = (getattr(hparams, "Optim", None) or {}).get("skip_nonfinite")
+    if value is not None and not isinstance(value, bool):
+        raise ValueError("Optim.skip_nonfinite must be true or false (absent / None = false); got %r" % (value,))
+    terminate = getattr(hparams, "terminate_on_nan", None)
+    if terminate is not None and not isinstance(terminate, bool):
+        raise ValueError("terminate_on_nan must be true or false; got %r" % (terminate,))
+    return bool(value) or bool(terminate) or track_grad_norm_of(hparams) == 2
+
+
+def max_consecutive_skips_of(hparams):
+    """Optim["max_consecutive_skips"]: how many steps in a row the guard may skip before the Trainer stops the run (a run that skips
+    everything trains nothing); an int >= 1, default 10."""
+    value = (getattr(hparams, "Optim", None) or {}).get("max_consecutive_skips")
+    if value is None:
+        return 10
+    if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+        raise ValueError("Optim.max_consecutive_skips must be an integer >= 1 (default 10); got %r" % (value,))
+    return value
+
+
 class LetsFaceItGlow(nn.Module):
     def __init__(self, hparams, dataset_root=None, test=None):
         super().__init__()
         test_params(hparams)
+        # Non-finite step guard: with it on, fused_training_step - eager, captured, data-parallel - skips a step whose reduced gradient
+        # holds a NaN or an Inf, on the device, without a host wait (GlowEngine.enable_step_guard). Off: every launch as before.
+        self.skip_nonfinite = skip_nonfinite_of(hparams)
+        max_consecutive_skips_of(hparams)      # (validated here, read by the Trainer)
         # Weight averaging: after every optimiser step of fused_training_step the engine's `ema` buffer moves towards the parameters
         # by (1 - ema_decay) (first step: a copy). Sampling and validation reach it through seq_glow.ema_weights(), checkpoints
         # through ema_state_dict(). The plain training_step + external optimiser path gets no automatic update: such a loop calls
@@ -101,6 +141,10 @@ class LetsFaceItGlow(nn.Module):
         value = value.reshape(()).to(self.last_missmatched_nll.device)
         if self.nll_sync_hook is not None:
             value = self.nll_sync_hook(value)
+        if self.skip_nonfinite:
+            # a NaN here would switch the negative-example branch off for good (`_last_mm() > 0` is false ever after): the step that
+            # produced it is skipped, and the buffer keeps its value - chosen on the device, no host read
+            value = torch.where(torch.isfinite(value), value, self.last_missmatched_nll.to(value.dtype))
         self.last_missmatched_nll.copy_(value)
         self._mm_host = None  # re-read (one wait, after negative steps only)
         self._mm_pending = None
@@ -154,6 +198,7 @@ class LetsFaceItGlow(nn.Module):
 
     def _graph_key(self, batch, negative, eng):
         return (bool(negative), eng.precision, str(eng.backward_products), tuple(sorted(eng.pass_skip.items())), self.ema_decay,
+                bool(self.skip_nonfinite),
                 tuple((k, tuple(v.shape)) for k, v in sorted(batch.items())))
 
     def _graph_allowed(self, sg, eng, world_size, allreduce):
@@ -222,15 +267,13 @@ class LetsFaceItGlow(nn.Module):
         return st
 
     def _replay_dp_step(self, st, batch, lr, negative, eng, world_size, allreduce):
-        from .. import _lib
         sg = self.seq_glow
         for k, v in st["in"].items():
             v.copy_(batch[k], non_blocking=True)
         a = self.hparams.Optim["args"]["adam"]
         step_size, inv_sqrt_bc2 = eng.adam_step_floats(lr, float(a["betas"][0]), float(a["betas"][1]), eng.step_count + 1)
         seed = (torch.initial_seed() + sg.mask_seed_offset) & (2 ** 64 - 1)
-        _lib.check(eng.L.lfi_set_step_params(st["params"].data_ptr(), seed, eng._mask_calls + 1, step_size, inv_sqrt_bc2,
-                                             torch.cuda.current_stream().cuda_stream), "lfi_set_step_params")
+        self._set_step_params(st, eng, seed, step_size, inv_sqrt_bc2)
         off = eng.flow_offset
         st["graph"].replay()                                     # masks, forward, the flow's backward
         pending = allreduce(eng.grads[off:], async_op=True)      # travels under graph B
@@ -257,6 +300,19 @@ class LetsFaceItGlow(nn.Module):
         self.global_step += 1
         self.log("train_loss", mean)
         return mean.detach()
+
+    @staticmethod
+    def _set_step_params(st, eng, seed, step_size, inv_sqrt_bc2):
+        """What differs between replays, into the graph's 32-byte device block. With the step guard on the block also carries the step
+        number the two floats were computed for: the decide node compares it with the device's own count of applied steps."""
+        from .. import _lib
+        stream = torch.cuda.current_stream().cuda_stream
+        if eng.guard is not None:
+            _lib.check(eng.L.lfi_set_step_params_t(st["params"].data_ptr(), seed, eng._mask_calls + 1, step_size, inv_sqrt_bc2,
+                                                   eng.step_count + 1, stream), "lfi_set_step_params_t")
+        else:
+            _lib.check(eng.L.lfi_set_step_params(st["params"].data_ptr(), seed, eng._mask_calls + 1, step_size, inv_sqrt_bc2, stream),
+                       "lfi_set_step_params")
 
     def _capture_step(self, key, batch, negative, eng):
         from .. import _lib
@@ -295,15 +351,13 @@ class LetsFaceItGlow(nn.Module):
         return (eng.adam_m, eng.adam_v, eng.__dict__.get("opt_aux"), eng.ema)
 
     def _replay_step(self, st, batch, lr, negative, eng):
-        from .. import _lib
         sg = self.seq_glow
         for k, v in st["in"].items():
             v.copy_(batch[k], non_blocking=True)
         a = self.hparams.Optim["args"]["adam"]
         step_size, inv_sqrt_bc2 = eng.adam_step_floats(lr, float(a["betas"][0]), float(a["betas"][1]), eng.step_count + 1)
         seed = (torch.initial_seed() + sg.mask_seed_offset) & (2 ** 64 - 1)
-        _lib.check(eng.L.lfi_set_step_params(st["params"].data_ptr(), seed, eng._mask_calls + 1, step_size, inv_sqrt_bc2,
-                                             torch.cuda.current_stream().cuda_stream), "lfi_set_step_params")
+        self._set_step_params(st, eng, seed, step_size, inv_sqrt_bc2)
         st["graph"].replay()
         eng.step_count += 1
         if st["ema"]:
@@ -337,6 +391,8 @@ class LetsFaceItGlow(nn.Module):
             batch = derange_batch(batch, self.missmatched_modalities)
         x = batch["p1_face"]
         eng = sg._ensure_engine(x.device)
+        if self.skip_nonfinite and (eng.guard is None or eng._guard_averaging != bool(self.ema_decay)):
+            eng.enable_step_guard(averaging=bool(self.ema_decay))
         B, T = x.shape[0], x.shape[1]
         N = T - sg.spec.start
         # a step that has to MAKE the average (its first value: an allocation + copy, counted as update 1) stays eager

@@ -39,6 +39,9 @@ class Trainer:
         self.epoch = 0
         self.batches_into_epoch = 0   # batches of the current epoch already trained on (a max_steps checkpoint taken mid-epoch)
         self._epoch_rng = None        # torch's CPU generator state at the start of the current epoch (see fit)
+        # non-finite step guard (_read_guard): skips known at the last look at the device's record, and the last step known clean
+        self._guard_seen = 0
+        self._guard_clean_step = 0
 
     # ------------------------------------------------------------------ distributed plumbing
     def setup_distributed(self):
@@ -99,8 +102,37 @@ class Trainer:
             return lr
         raise NotImplementedError("Unimplemented Scheduler!")
 
+    # ------------------------------------------------------------------ non-finite step guard
+    def _read_guard(self, model):
+        """One look at the step guard's device record (GlowEngine.guard_state: one wait), at the points where the loop waits anyway:
+        the log line, before validation, before a checkpoint. None while the guard is off. Stops the run - last.ckpt written first,
+        its weights are clean: skipped steps changed nothing - at the first skip seen with `terminate_on_nan`, otherwise once
+        Optim["max_consecutive_skips"] (default 10) steps in a row were skipped: a run that skips everything must not train nothing
+        for a day. Every rank reads the same counts (the decision is taken on the reduced gradient), so every rank stops."""
+        from .glow.lets_face_it_glow import max_consecutive_skips_of
+        eng = getattr(getattr(model, "seq_glow", None), "engine", None)
+        if getattr(eng, "guard", None) is None:
+            return None
+        gs = eng.guard_state()
+        new, self._guard_seen = gs["skipped"] - self._guard_seen, gs["skipped"]
+        first, self._guard_clean_step = self._guard_clean_step + 1, (self.global_step if new <= 0 else self._guard_clean_step)
+        why = None
+        if new > 0 and bool(getattr(self.hparams, "terminate_on_nan", False)):
+            why = "terminate_on_nan"
+        elif gs["consecutive"] >= max_consecutive_skips_of(self.hparams):
+            why = "%d steps in a row skipped (Optim.max_consecutive_skips = %d)" % (gs["consecutive"],
+                                                                                    max_consecutive_skips_of(self.hparams))
+        if why is not None:
+            self._checkpoint(model, read_guard=False)
+            raise ValueError("non-finite gradient: %d optimiser step(s) between step %d and step %d were skipped (%d in all, last "
+                             "gradient norm %r); stopping: %s. The weights are those of the last step taken."
+                             % (max(new, 0), first, self.global_step, gs["skipped"], gs["last_norm"], why))
+        return gs
+
     # ------------------------------------------------------------------ loop
     def fit(self, model, datamodule):
+        from .glow.lets_face_it_glow import track_grad_norm_of
+        track_norm = track_grad_norm_of(self.hparams) == 2      # (any value but -1 / 2 raises NotImplementedError here, at the start)
         self.setup_distributed()
         model.to(self.device)
         model.train()
@@ -114,6 +146,7 @@ class Trainer:
             torch.cuda.manual_seed(torch.initial_seed() + self.rank)
             model.seq_glow.mask_seed_offset = self.rank
         step = self.global_step
+        self._guard_clean_step = step
         for epoch in range(self.epoch, self.max_epochs):
             self.epoch = epoch
             lr = self.lr_at(epoch)
@@ -156,19 +189,25 @@ class Trainer:
                 step += 1
                 self.global_step = step
                 self.batches_into_epoch = bi + 1
-                if self.rank == 0 and step % self.log_every == 0:
-                    torch.cuda.synchronize()
-                    print("epoch %d step %d lr %.3e loss %.4f  %.0f frames/s" %
-                          (epoch, step, lr, float(loss), frames / (time.time() - t0)), flush=True)
+                if step % self.log_every == 0:
+                    gs = self._read_guard(model)      # (every rank: they stop together)
+                    if self.rank == 0:
+                        torch.cuda.synchronize()
+                        norm = " grad_norm %.4e skipped %d" % (gs["last_norm"], gs["skipped"]) if track_norm and gs else ""
+                        print("epoch %d step %d lr %.3e loss %.4f%s  %.0f frames/s" %
+                              (epoch, step, lr, float(loss), norm, frames / (time.time() - t0)), flush=True)
                 if self.max_steps and step >= int(self.max_steps):
                     self._checkpoint(model)
                     return
+            self._read_guard(model)
             self.validate(model, datamodule)
             self.epoch = epoch + 1          # a checkpoint written now resumes with the next epoch
             self.batches_into_epoch = 0
             self._checkpoint(model)
 
-    def _checkpoint(self, model):
+    def _checkpoint(self, model, read_guard=True):
+        if read_guard:
+            self._read_guard(model)      # (stops a run whose last steps were all skipped; writes this checkpoint on its way out)
         if self.checkpoint_dir and self.rank == 0:
             os.makedirs(self.checkpoint_dir, exist_ok=True)
             self.save_checkpoint(model, os.path.join(self.checkpoint_dir, "last.ckpt"))
@@ -182,7 +221,7 @@ class Trainer:
         # the callbacks do (MimicryLogger: sampling, jerk, mismatched-NLL probes, invertibility). Validation["use_ema"] = False keeps
         # the raw weights; without an average the code path is the plain one.
         eng = getattr(getattr(model, "seq_glow", None), "engine", None)
-        use_ema = (getattr(eng, "ema", None) is not None
+        use_ema = (getattr(eng, "ema", None) is not None and getattr(eng, "ema_updates", 1) > 0
                    and bool((getattr(self.hparams, "Validation", None) or {}).get("use_ema", True)))
         weights = model.seq_glow.ema_weights() if use_ema else contextlib.nullcontext()
         # under data parallelism the loader hands every rank ITS share of the validation windows (WindowLoader: one shared order,
@@ -211,14 +250,14 @@ class Trainer:
         optimiser's state (Adam moments over the flat parameter buffer + step count: with betas[1] = 0.9999 a resumed run
         that restarted them would take ~10^4 steps to get its second moments back). With weight averaging on, `ema_state_dict` holds
         the averaged weights under state_dict's keys (LetsFaceItGlow.load_from_checkpoint(..., weights="ema")); the flat average and
-        its update count travel inside `optimizer_state` (resume)."""
+        its update count travel inside `optimizer_state` (resume), and so do the step guard's counters (`guard`)."""
         if self.rank == 0:
             eng = model.seq_glow.engine
             opt = None
             if eng is not None:
                 opt = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in eng.optimizer_state().items()}
             extra = {}
-            if getattr(eng, "ema", None) is not None:
+            if getattr(eng, "ema", None) is not None and getattr(eng, "ema_updates", 1) > 0:      # (0: every update so far skipped)
                 extra["ema_state_dict"] = {k: v.detach().cpu() for k, v in model.ema_state_dict().items()}
             tmp = path + ".tmp"
             torch.save({**extra, "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
@@ -308,5 +347,6 @@ class Trainer:
         self.batches_into_epoch = int(ckpt.get("batches_into_epoch", 0))
         self.epoch = int(ckpt.get("epoch", 0))
         self.global_step = int(ckpt.get("global_step", 0))
+        self._guard_seen = int(((ckpt.get("optimizer_state") or {}).get("guard") or {}).get("skipped", 0))
         model.global_step = self.global_step
         return model

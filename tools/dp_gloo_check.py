@@ -15,6 +15,7 @@ import torch.distributed as dist  # noqa: E402
 
 GRAPH = "--graph" in sys.argv   # the data-parallel step as two replayed hipGraphs with the collectives between them vs eager launches
 NCCL1 = "--nccl1" in sys.argv   # ONE rank on backend "nccl" (= RCCL): the collectives' launch path on this ROCm, no transport
+GUARD = "--guard" in sys.argv   # the non-finite step guard under data parallelism: one rank's shard poisoned, every rank skips
 FINAL = "--final" in sys.argv or NCCL1   # final_model.yaml widths at BASELINE's synthetic dims, batch 256 per rank, T = 80
 
 
@@ -135,6 +136,58 @@ def run_graph_leg(rank, world, dev, graph, steps=8):
     return eng.params.detach().clone(), eng.adam_m.detach().clone(), eng.adam_v.detach().clone(), replayed
 
 
+def run_guard_leg(rank, world, dev, steps=4, poisoned_step=2, poisoned_rank=1, graph=False):
+    """`steps` data-parallel steps (graph: as two replayed hipGraphs from the third on) with Optim.skip_nonfinite; on step `poisoned_step` (1-based) the shard of `poisoned_rank`
+    alone holds a NaN (one element of p1_face at a modelled frame). The decision is taken after the all-reduce, so every rank must
+    skip that step and no other, and hold the parameters of every other rank after every step.
+    -> (True when all of that held, final parameters, steps that ran on captured graphs)"""
+    from argparse import Namespace
+    from lets_face_it_amd import _lib
+    from lets_face_it_amd.glow.lets_face_it_glow import LetsFaceItGlow
+    from lets_face_it_amd.trainer import Trainer
+    from helpers import Fixture
+    fx = Fixture("mid")
+    hp = fx.hp
+    hp["gradient_clip_val"] = 20
+    hp["Train"]["use_negative_nll_loss"] = False
+    hp["Optim"]["skip_nonfinite"] = True
+    torch.manual_seed(0)
+    m = LetsFaceItGlow(Namespace(**hp))
+    m.seq_glow.load_state_dict(fx.state_dict(torch.float32))
+    m.to(dev).train()
+    m.seq_glow.precision = "f32"
+    m.step_graph = graph
+    tr = Trainer(Namespace(**hp), device=dev)
+    m.seq_glow.allreduce_hook = tr.allreduce_stats
+    m.nll_sync_hook = tr.sync_scalar
+    tr.broadcast_parameters(m)
+    eng = m.seq_glow._ensure_engine(dev)
+    B, ok, replayed = 16, True, 0
+    torch.manual_seed(11)
+    for step, full in enumerate(_batches(fx, steps, world * B), start=1):
+        shard = {k: v[rank * B:(rank + 1) * B].to(dev).contiguous() for k, v in full.items()}
+        if step == poisoned_step and rank == poisoned_rank:
+            shard["p1_face"][3, fx.start + 2, 1] = float("nan")
+        before = eng.params.detach().clone()
+        m.fused_training_step(shard, 1e-3, world, tr.allreduce_grads)
+        torch.cuda.synchronize()
+        replayed += 1 if any(isinstance(v, dict) and v.get("dp") for v in (m.__dict__.get("_step_graphs") or {}).values()) else 0
+        apply = int(eng.guard.cpu()[_lib.GUARD_APPLY])
+        unchanged = torch.equal(eng.params, before)
+        p = eng.params.detach().cpu()
+        gathered = [torch.zeros_like(p) for _ in range(world)]
+        dist.all_gather(gathered, p)
+        same = all(torch.equal(gathered[0], g) for g in gathered)
+        want_skip = step == poisoned_step
+        print("guard rank %d step %d: apply %d, parameters unchanged %s, ranks identical %s" % (rank, step, apply, unchanged, same), flush=True)
+        ok = ok and same and apply == (0 if want_skip else 1) and unchanged == want_skip
+    gs = eng.guard_state()
+    print("guard rank %d: skipped %d consecutive %d applied %d step_count %d" % (rank, gs["skipped"], gs["consecutive"], gs["applied"],
+                                                                                 eng.step_count), flush=True)
+    ok = ok and (gs["skipped"], gs["consecutive"], gs["applied"], eng.step_count) == (1, 0, steps - 1, steps - 1)
+    return ok, eng.params.detach().clone(), replayed
+
+
 def main():
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     dev = torch.device("cuda", 0)
@@ -142,6 +195,24 @@ def main():
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     dist.init_process_group("nccl" if NCCL1 else "gloo", rank=rank, world_size=world)
     print("rank %d of %d up (%s)" % (rank, world, dist.get_backend()), flush=True)
+    if GUARD:
+        if GRAPH:      # eight steps, the sixth - a replay - poisoned: the two-graph step against the eager data-parallel step
+            ok_e, pe, _ = run_guard_leg(rank, world, dev, steps=8, poisoned_step=6)
+            ok_g, pg, replayed = run_guard_leg(rank, world, dev, steps=8, poisoned_step=6, graph=True)
+            same = torch.equal(pe, pg)
+            print("guard rank %d: graph leg bit-identical to the eager leg: %s; steps on captured graphs: %d" % (rank, same, replayed),
+                  flush=True)
+            ok = ok_e and ok_g and same and replayed >= 3
+        else:
+            ok = run_guard_leg(rank, world, dev)[0]
+        flag = torch.tensor([1.0 if ok else 0.0], dtype=torch.float64)
+        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+        if rank == 0:
+            print("guarded data-parallel steps: the poisoned step skipped on every rank, ranks identical after every step: %s"
+                  % bool(flag[0] > 0), flush=True)
+        dist.barrier()
+        dist.destroy_process_group()
+        sys.exit(0 if flag[0] > 0 else 1)
     if GRAPH and os.environ.get("DP_CHECK_EAGER_TWICE") == "1":      # diagnosis: is a SECOND eager model in the process the same as the first?
         pa = run_graph_leg(rank, world, dev, False, steps=2)[0]
         pb = run_graph_leg(rank, world, dev, False, steps=2)[0]
