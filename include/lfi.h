@@ -820,6 +820,38 @@ int lfi_ema_update_guard(float* ema, const float* p, long n, float decay, const 
 int lfi_set_step_params_t(void* params, unsigned long long seed, unsigned long long offset, float step_size, float inv_sqrt_bc2,
                           unsigned long long t_host, void* stream);
 
+/* ---------------------------------------------------------------- per-array statistics, and the blame record of a skipped step
+ * lfi_segment_stats looks once at many fp32 arrays: the nseg segments (offset, length: int64 pairs in DEVICE memory, in floats,
+ * disjoint, inside [0, n), any 4-byte position, gaps allowed and never read) of the flat buffer `flat` of n floats, then nextra
+ * (<= 8) further arrays given as host lists of pointers and lengths (passed by value, as lfi_absmax_f32's). Array i of the
+ * nseg + nextra fills record i of `out`, LFI_SEG_SLOTS 8-byte slots:
+ *   SUMSQ  fp64 sum of squares of its FINITE elements;   NAN / INF  u64 counts of NaNs / of +-Inf;
+ *   FIRST  u64 index within the array of its first non-finite element, all ones when it has none.
+ * A zero-length array yields zeros and FIRST = all ones. Three launches for any number of arrays: arrays are cut into chunks of
+ * lfi_segment_stats_chunk() floats, one workgroup per chunk leaves its partials in `work` (lfi_segment_stats_work_floats floats,
+ * 8-byte aligned), one workgroup sums each array's partials in chunk order. No atomics: the same input gives the same bits on every
+ * run and from either entry point. Null pointers, nseg < 0, nextra > 8, negative lengths and misaligned records / work buffers are
+ * refused before any launch; an empty call succeeds.
+ * lfi_segment_stats_guard is the same work behind the step guard: `rec` is the guard record (read only), `blame` a record of
+ * LFI_BLAME_HEAD + LFI_SEG_SLOTS * (nseg + nextra) slots: FILLED (u64 0 / 1), STEP (u64, 1-based number of the step the table
+ * belongs to: APPLIED + SKIPPED as the decide kernel left them), then the table above. While rec's APPLY is 1, or FILLED is 1, every
+ * workgroup of every launch returns before its first load of data and nothing is written (the FIRST skipped step since the host
+ * cleared the header is the one kept). Otherwise the table is filled, then STEP, then FILLED: the call's last store. */
+#define LFI_SEG_SUMSQ 0
+#define LFI_SEG_NAN 1
+#define LFI_SEG_INF 2
+#define LFI_SEG_FIRST 3
+#define LFI_SEG_SLOTS 4
+#define LFI_BLAME_FILLED 0
+#define LFI_BLAME_STEP 1
+#define LFI_BLAME_HEAD 2
+long lfi_segment_stats_chunk(void);
+long lfi_segment_stats_work_floats(long n, int nseg, int nextra, const long* xlen);
+int lfi_segment_stats(const float* flat, long n, const long* segs, int nseg, int nextra, const float* const* xptrs, const long* xlen,
+                      void* out, void* work, void* stream);
+int lfi_segment_stats_guard(const float* flat, long n, const long* segs, int nseg, int nextra, const float* const* xptrs,
+                            const long* xlen, const void* rec, void* blame, void* work, void* stream);
+
 /* ---------------------------------------------------------------- callers either side of the flow (SURVEY.md par. 8f)
  * Window sampler, replaces MimicryDataset.__getitem__ + DataLoader collation (code/glow_pytorch/mimicry_data_module.py:45-78):
  * one modality of a split lives in HBM as ONE (rows x dim) matrix, the recording bins back to back; a training window is T

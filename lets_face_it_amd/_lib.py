@@ -216,6 +216,10 @@ def lib():
         "lfi_rmsprop_clip_step_guard": (i, [vp, vp, vp, vp, vp, l, vp, f, f, f, f, f, f, f, vp, vp]),
         "lfi_ema_update_guard": (i, [vp, vp, l, f, vp, vp]),
         "lfi_set_step_params_t": (i, [vp, C.c_ulonglong, C.c_ulonglong, f, f, C.c_ulonglong, vp]),
+        "lfi_segment_stats_chunk": (l, []),
+        "lfi_segment_stats_work_floats": (l, [l, i, i, P(l)]),
+        "lfi_segment_stats": (i, [vp, l, vp, i, i, P(vp), P(l), vp, vp, vp]),
+        "lfi_segment_stats_guard": (i, [vp, l, vp, i, i, P(vp), P(l), vp, vp, vp, vp]),
         "lfi_actnorm_forward": (i, [vp, i, i, vp, vp, i, vp, vp, vp]),
         "lfi_invconv_work_floats": (l, [i]),
         "lfi_invconv_weights": (i, [i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]),
@@ -256,11 +260,17 @@ EXPORTS = [
     "lfi_gather_sequences", "lfi_jerk_mean", "lfi_actnorm_forward", "lfi_invconv_work_floats", "lfi_invconv_weights",
     "lfi_grad_guard", "lfi_grad_guard_dev", "lfi_adam_clip_step_guard", "lfi_sgd_clip_step_guard", "lfi_rmsprop_clip_step_guard",
     "lfi_ema_update_guard", "lfi_set_step_params_t",
+    "lfi_segment_stats_chunk", "lfi_segment_stats_work_floats", "lfi_segment_stats", "lfi_segment_stats_guard",
 ]
 
 # slots of the non-finite step guard's device record (include/lfi.h, LFI_GUARD_*): 8 bytes each
 GUARD_SKIPPED, GUARD_CONSECUTIVE, GUARD_APPLIED, GUARD_LAST_NORM, GUARD_MAX_NORM = 0, 1, 2, 3, 4
 GUARD_APPLY, GUARD_STEP_FLOATS, GUARD_MOMENTUM_LIVE, GUARD_AVERAGE_LIVE, GUARD_SLOTS = 5, 6, 7, 8, 9
+# slots of one per-array record of lfi_segment_stats (LFI_SEG_*) and of the blame record's header in front of them (LFI_BLAME_*)
+SEG_SUMSQ, SEG_NAN, SEG_INF, SEG_FIRST, SEG_SLOTS = 0, 1, 2, 3, 4
+BLAME_FILLED, BLAME_STEP, BLAME_HEAD = 0, 1, 2
+SEG_NONE = 2 ** 64 - 1      # FIRST of an array without a non-finite element
+SEG_MAX_EXTRA = 8
 
 
 def translate_oom(fn):

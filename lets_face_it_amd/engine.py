@@ -217,6 +217,11 @@ class GlowEngine:
         self.guard = None
         self._guard_averaging = False
         self._guard_counts = None
+        # blame record of the first skipped step (enable_step_blame; include/lfi.h, lfi_segment_stats_guard), None while off. A
+        # diagnostic: part of no optimiser state and no checkpoint
+        self.blame = None
+        self._owner = None            # weak reference to the SeqGlow bound to this engine (flat_segments)
+        self._segments = None         # (state_dict keys, device table of (offset, length) pairs), made once
         # bumped by every optimiser step, parameter load and data-dependent ActNorm init: a streaming sampling session (SampleStream)
         # records it at open and refuses to step once it has moved (its prepared weights are those of the open)
         self.param_version = 0
@@ -925,6 +930,7 @@ class GlowEngine:
         ctx.cond, ctx.cbuf, ctx.gic, ctx.stash, ctx.dims, ctx.with_stash, ctx.chain = cond, cbuf, gic, stash, dims, with_stash, chain
         ctx.enc_stash_f16 = dict(self._enc_stash_f16)
         ctx.signs = self._c_signs if (chain and with_stash) else None
+        ctx.nll = nll      # (with ctx.batch: what the blame launch behind the step guard's decision looks at)
         self._last = ctx
         return z, nll
 
@@ -1558,6 +1564,8 @@ class GlowEngine:
         else:
             check(self.L.lfi_grad_guard(g, n, ss, work, rec, gmul, flags, beta1, beta2, floats[0], floats[1], self.step_count + 1,
                                         _stream()), "lfi_grad_guard")
+        if self.blame is not None:
+            self._launch_blame(gmul)
 
     def guard_state(self):
         """{skipped, consecutive, applied, last_norm, max_norm} as the device holds them: one copy of the record, one wait. Also puts
@@ -1574,6 +1582,136 @@ class GlowEngine:
         self._momentum_inited = bool(int(host[_lib.GUARD_MOMENTUM_LIVE]) >> 1)
         return {"skipped": int(host[_lib.GUARD_SKIPPED]), "consecutive": int(host[_lib.GUARD_CONSECUTIVE]), "applied": applied,
                 "last_norm": float(f64[_lib.GUARD_LAST_NORM]), "max_norm": float(f64[_lib.GUARD_MAX_NORM])}
+
+    # ------------------------------------------------------------------ blame: which inputs, frames and tensors a skipped step held
+    def flat_segments(self):
+        """[(state_dict key, offset, numel)] of every parameter of the bound SeqGlow in named_parameters() order, each located by its
+        data pointer in the flat buffer (Trainer._flat_optimizer_state does the same for optimiser state)."""
+        owner = self._owner() if self._owner is not None else None
+        if owner is None:
+            raise RuntimeError("flat_segments: this engine is bound to no SeqGlow (module-level flow runtimes have no state_dict keys)")
+        base, out = self.params.data_ptr(), []
+        for key, p in owner.named_parameters():
+            off = (p.data_ptr() - base) // 4
+            if (p.data_ptr() - base) % 4 or not (0 <= off and off + p.numel() <= self.n_params):
+                raise ValueError("parameter %s does not live in the engine's flat buffer" % key)
+            out.append((key, int(off), int(p.numel())))
+        return out
+
+    def _segment_table(self):
+        if self._segments is None:
+            segs = self.flat_segments()
+            table = torch.tensor([[o, n] for _, o, n in segs], dtype=torch.int64).reshape(-1).to(self.device)
+            self._segments = ([k for k, _, _ in segs], table)
+        return self._segments
+
+    def _stats_work(self, lens):
+        """Work buffer of lfi_segment_stats for the gradient segments plus extra arrays of these lengths (kept per size: a captured
+        step holds its buffer by address)."""
+        keys, _ = self._segment_table()
+        xl = (C.c_long * max(len(lens), 1))(*lens)
+        floats = self.L.lfi_segment_stats_work_floats(self.n_params, len(keys), len(lens), xl)
+        if floats < 0:
+            raise _lib.LfiError("lfi_segment_stats_work_floats: %s" % self.L.lfi_last_error().decode())
+        pool = self.__dict__.setdefault("_stats_works", {})
+        w = pool.get(floats)
+        if w is None:
+            w = pool[floats] = torch.zeros((floats + 1) // 2, dtype=torch.int64, device=self.device)
+        return w
+
+    def enable_step_blame(self):
+        """From now on every step-guard decision is followed by lfi_segment_stats_guard over the gradient segments, the step's input
+        tensors and its per-frame NLL: the first skipped step leaves a blame record (blame_state), taken steps return before their
+        first load. Uploads the segment table once and allocates the record. Needs the step guard; idempotent; never inside a
+        stream capture."""
+        if self.guard is None:
+            raise RuntimeError("enable_step_blame: the step guard is off (enable_step_guard / Optim.skip_nonfinite first)")
+        if self.blame is None:
+            keys, _ = self._segment_table()
+            self._stats_work([])
+            self._blame_layouts = []      # [(first launch that used it, [(input name, shape)], nll shape | None)]
+            self._blame_launches = 0
+            self._blame_gmul = 1.0
+            self.blame = torch.zeros(_lib.BLAME_HEAD + _lib.SEG_SLOTS * (len(keys) + _lib.SEG_MAX_EXTRA), dtype=torch.int64,
+                                     device=self.device)
+
+    def _launch_blame(self, gmul):
+        """Right behind _guard_decide, same stream (one more node of a captured step): the arrays are the gradient segments, then the
+        float32 tensors of the batch the last forward() saw - sorted by name, at most seven - then its per-frame NLL."""
+        keys, table = self._segment_table()
+        ctx = self._last
+        inputs, nll = [], None
+        if ctx is not None:
+            for name, t in sorted(ctx.batch.items()):
+                if torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.is_contiguous():
+                    inputs.append((name, t))
+            inputs = inputs[:_lib.SEG_MAX_EXTRA - 1]
+            nll = getattr(ctx, "nll", None)
+        arrays = [t for _, t in inputs] + ([nll] if nll is not None else [])
+        layout = ([(name, tuple(t.shape)) for name, t in inputs], None if nll is None else tuple(nll.shape))
+        n = len(arrays)
+        ptrs, lens = (C.c_void_p * max(n, 1))(), (C.c_long * max(n, 1))()
+        for i, t in enumerate(arrays):
+            ptrs[i], lens[i] = t.data_ptr(), t.numel()
+        work = self._stats_work([t.numel() for t in arrays])
+        check(self.L.lfi_segment_stats_guard(self.grads.data_ptr(), self.n_params, table.data_ptr(), len(keys), n, ptrs, lens,
+                                             self.guard.data_ptr(), self.blame.data_ptr(), work.data_ptr(), _stream()),
+              "lfi_segment_stats_guard")
+        self._blame_gmul = float(gmul)
+        if torch.cuda.is_current_stream_capturing():
+            self._blame_captured = layout      # (nothing ran: whoever replays the graph counts its launches, _count_blame_launch)
+        else:
+            self._count_blame_launch(layout)
+
+    def _count_blame_launch(self, layout):
+        """One blame launch has been enqueued with these arrays behind the gradient segments: blame_state() finds the names and shapes
+        that belong to a record's step number by counting launches back from the guard's counters."""
+        self._blame_launches += 1
+        if not self._blame_layouts or self._blame_layouts[-1][1:] != layout:
+            self._blame_layouts.append((self._blame_launches,) + layout)
+
+    def blame_state(self, clear=True):
+        """The blame record of the first skipped step since the last clear: one copy, one wait. None while nothing was skipped, else
+        {step, inputs: {name: {nan, inf, first: (row, frame, column)}}, nll: {nan, inf, count, first: (frame, row)}, gradients:
+        [{key, nan, inf, first}], norms: {key: norm of the finite part x |gmul|}, tensors} (lets_face_it_amd/blame.py). clear: the
+        header is zeroed in stream order, so the next skipped step fills the record again."""
+        if self.blame is None:
+            raise RuntimeError("blame_state: blame is off (enable_step_blame / print_nan_grads)")
+        from . import blame as _blame
+        both = torch.cat([self.blame, self.guard]).cpu()      # (one copy: the guard's counters tie launches to step numbers)
+        host, rec = both[:self.blame.numel()], both[self.blame.numel():]
+        # the record's STEP is APPLIED + SKIPPED, which moves by one per decision, i.e. per blame launch
+        now = int(rec[_lib.GUARD_APPLIED]) + int(rec[_lib.GUARD_SKIPPED])
+        if int(host[_lib.BLAME_FILLED]) == 0:
+            return None
+        launch = self._blame_launches - (now - int(host[_lib.BLAME_STEP]))
+        layouts = self._blame_layouts or [(0, [], None)]
+        layout = next((lay for lay in reversed(layouts) if lay[0] <= launch), layouts[0])
+        keys, _ = self._segment_table()
+        state = _blame.decode(host.tolist(), keys, layout[1], layout[2], self._blame_gmul)
+        if clear:
+            self.blame[:_lib.BLAME_HEAD].zero_()
+            self._blame_layouts = self._blame_layouts[-1:]
+        return state
+
+    def grad_tensor_stats(self):
+        """[{key, sumsq, nan, inf, first}] per parameter tensor over `grads` as it stands (lfi_segment_stats: three launches, one
+        wait). The optimiser kernels take the gradient as const: after a step the buffer still holds that step's reduced gradient."""
+        from . import blame as _blame
+        keys, table = self._segment_table()
+        out = self.__dict__.get("_stats_out")
+        if out is None:
+            out = self._stats_out = torch.zeros(_lib.SEG_SLOTS * len(keys), dtype=torch.int64, device=self.device)
+        work = self._stats_work([])
+        check(self.L.lfi_segment_stats(self.grads.data_ptr(), self.n_params, table.data_ptr(), len(keys), 0, None, None,
+                                       out.data_ptr(), work.data_ptr(), _stream()), "lfi_segment_stats")
+        words = out.cpu().tolist()
+        return [dict(key=k, **_blame.record_of(words, i)) for i, k in enumerate(keys)]
+
+    def grad_tensor_norms(self, gmul=1.0):
+        """{state_dict key: 2-norm of the finite part of that tensor's gradient x |gmul|}: Lightning's track_grad_norm per tensor."""
+        g = abs(float(gmul))
+        return {r["key"]: math.sqrt(r["sumsq"]) * g for r in self.grad_tensor_stats()}
 
     def grad_norm(self):
         check(self.L.lfi_grad_sumsq(self.grads.data_ptr(), self.n_params, self.sumsq.data_ptr(),

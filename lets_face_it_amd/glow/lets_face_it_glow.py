@@ -46,18 +46,28 @@ def track_grad_norm_of(hparams):
     raise NotImplementedError("track_grad_norm must be -1 (off) or 2 (the 2-norm the clip computes anyway); got %r" % (value,))
 
 
+def print_nan_grads_of(hparams):
+    """Lightning's `print_nan_grads`: true = the first skipped step leaves a blame record on the device - which input tensors, which
+    frames of the per-frame NLL and which gradient tensors held a NaN or an Inf (GlowEngine.enable_step_blame) - and the Trainer prints
+    it. A bool; absent, None or False = off. Anything else raises ValueError."""
+    value = getattr(hparams, "print_nan_grads", None)
+    if value is not None and not isinstance(value, bool):
+        raise ValueError("print_nan_grads must be true or false; got %r" % (value,))
+    return bool(value)
+
+
 def skip_nonfinite_of(hparams):
     """Whether optimiser steps whose gradient holds a NaN or an Inf are skipped on the device (the non-finite step guard):
     Optim["skip_nonfinite"], a bool - absent, None or False = off. `terminate_on_nan: true` implies it (the Trainer stops at the first
-    skip it observes, with clean weights), and so does `track_grad_norm: 2` (the norm is read from the guard's record). Anything but a
-    bool raises ValueError."""
+    skip it observes, with clean weights), and so do `track_grad_norm: 2` (the norm is read from the guard's record) and
+    `print_nan_grads: true` (the blame record is written behind the guard's decision). Anything but a bool raises ValueError."""
     value = (getattr(hparams, "Optim", None) or {}).get("skip_nonfinite")
     if value is not None and not isinstance(value, bool):
         raise ValueError("Optim.skip_nonfinite must be true or false (absent / None = false); got %r" % (value,))
     terminate = getattr(hparams, "terminate_on_nan", None)
     if terminate is not None and not isinstance(terminate, bool):
         raise ValueError("terminate_on_nan must be true or false; got %r" % (terminate,))
-    return bool(value) or bool(terminate) or track_grad_norm_of(hparams) == 2
+    return bool(value) or bool(terminate) or track_grad_norm_of(hparams) == 2 or print_nan_grads_of(hparams)
 
 
 def max_consecutive_skips_of(hparams):
@@ -78,6 +88,9 @@ class LetsFaceItGlow(nn.Module):
         # Non-finite step guard: with it on, fused_training_step - eager, captured, data-parallel - skips a step whose reduced gradient
         # holds a NaN or an Inf, on the device, without a host wait (GlowEngine.enable_step_guard). Off: every launch as before.
         self.skip_nonfinite = skip_nonfinite_of(hparams)
+        # Blame (print_nan_grads): one more launch behind the guard's decision, which returns at once on a taken step and on a skipped
+        # one records where the non-finite values sat. Off: no new launch.
+        self.print_nan_grads = print_nan_grads_of(hparams)
         max_consecutive_skips_of(hparams)      # (validated here, read by the Trainer)
         # Weight averaging: after every optimiser step of fused_training_step the engine's `ema` buffer moves towards the parameters
         # by (1 - ema_decay) (first step: a copy). Sampling and validation reach it through seq_glow.ema_weights(), checkpoints
@@ -198,7 +211,7 @@ class LetsFaceItGlow(nn.Module):
 
     def _graph_key(self, batch, negative, eng):
         return (bool(negative), eng.precision, str(eng.backward_products), tuple(sorted(eng.pass_skip.items())), self.ema_decay,
-                bool(self.skip_nonfinite),
+                bool(self.skip_nonfinite), bool(self.print_nan_grads),
                 tuple((k, tuple(v.shape)) for k, v in sorted(batch.items())))
 
     def _graph_allowed(self, sg, eng, world_size, allreduce):
@@ -254,6 +267,7 @@ class LetsFaceItGlow(nn.Module):
                     raise RuntimeError("engine.backward did not reach its after_flow point")
                 gb.capture_end()
                 state["open"] = None
+                st["ctx"] = eng._last      # (the inputs and the NLL of THIS graph: what a blame launch behind its replays looks at)
         except Exception:
             if state["open"] is not None:      # leave capture mode before the error travels on
                 try:
@@ -283,6 +297,7 @@ class LetsFaceItGlow(nn.Module):
         if pending is not None:
             pending.wait()
         clip = float(getattr(self.hparams, "gradient_clip_val", 0) or 0)
+        eng._last = st["ctx"]
         eng.optimizer_step(0.0, float(a["betas"][0]), float(a["betas"][1]), float(a["eps"]), clip=clip, gmul=1.0 / world_size,
                            hyper_dev=st["params"].data_ptr() + 16, weight_decay=float(a.get("weight_decay", 0) or 0),
                            amsgrad=bool(a.get("amsgrad", False)))
@@ -342,6 +357,7 @@ class LetsFaceItGlow(nn.Module):
                 eng._launch_ema_update(self.ema_decay)
         st["dropout"] = masks is not None
         st["ema"] = bool(self.ema_decay)
+        st["blame"] = eng.__dict__.pop("_blame_captured", None)      # (the arrays of the graph's blame node, None without one)
         # what the optimiser and averaging nodes write, by address: kept alive, and compared before every replay (fused_training_step)
         st["state_bufs"] = self._step_state_bufs(eng)
         return st
@@ -360,6 +376,8 @@ class LetsFaceItGlow(nn.Module):
         self._set_step_params(st, eng, seed, step_size, inv_sqrt_bc2)
         st["graph"].replay()
         eng.step_count += 1
+        if st["blame"] is not None:
+            eng._count_blame_launch(st["blame"])
         if st["ema"]:
             eng.ema_updates += 1
         eng.bump_param_version()
@@ -393,6 +411,8 @@ class LetsFaceItGlow(nn.Module):
         eng = sg._ensure_engine(x.device)
         if self.skip_nonfinite and (eng.guard is None or eng._guard_averaging != bool(self.ema_decay)):
             eng.enable_step_guard(averaging=bool(self.ema_decay))
+        if self.print_nan_grads and eng.blame is None:
+            eng.enable_step_blame()
         B, T = x.shape[0], x.shape[1]
         N = T - sg.spec.start
         # a step that has to MAKE the average (its first value: an allocation + copy, counted as update 1) stays eager

@@ -16,6 +16,7 @@ Differences that are deliberate:
     re-entrant across calls (the reference keeps it on f_seq.hidden, models.py:193-194).
 """
 import contextlib
+import weakref
 
 import torch
 import torch.nn as nn
@@ -417,6 +418,7 @@ class SeqGlow(nn.Module):
         if old is not None and old[0] == eng.n_params:
             eng.load_optimizer_state(old[1])   # .to()/.float() mid-training keeps Adam's moments, step count and mask counter
         self.engine = eng
+        eng._owner = weakref.ref(self)      # (GlowEngine.flat_segments names the flat buffer's tensors by this module's keys)
         self.glow.flow._engine = eng  # module-level Glow / FlowNet calls (one timestep) run on the same buffers
         # autograd sees each Parameter; map them to gradient views of the flat gradient buffer
         self._param_map = []

@@ -7,6 +7,7 @@ identical parameters and takes identical branches.
 """
 import contextlib
 import itertools
+import math
 import os
 import random
 import time
@@ -116,6 +117,16 @@ class Trainer:
         gs = eng.guard_state()
         new, self._guard_seen = gs["skipped"] - self._guard_seen, gs["skipped"]
         first, self._guard_clean_step = self._guard_clean_step + 1, (self.global_step if new <= 0 else self._guard_clean_step)
+        # blame (print_nan_grads): the first skipped step since the last look left a record of where its non-finite values sat
+        blame = ""
+        fetch = getattr(eng, "blame_state", None) if new > 0 and getattr(eng, "blame", None) is not None else None
+        if fetch is not None:
+            from .blame import report
+            state = fetch()
+            if state is not None:
+                blame = report(state)
+                if self.rank == 0:
+                    print("non-finite gradient: " + blame, flush=True)
         why = None
         if new > 0 and bool(getattr(self.hparams, "terminate_on_nan", False)):
             why = "terminate_on_nan"
@@ -125,9 +136,22 @@ class Trainer:
         if why is not None:
             self._checkpoint(model, read_guard=False)
             raise ValueError("non-finite gradient: %d optimiser step(s) between step %d and step %d were skipped (%d in all, last "
-                             "gradient norm %r); stopping: %s. The weights are those of the last step taken."
-                             % (max(new, 0), first, self.global_step, gs["skipped"], gs["last_norm"], why))
+                             "gradient norm %r); stopping: %s. The weights are those of the last step taken.%s"
+                             % (max(new, 0), first, self.global_step, gs["skipped"], gs["last_norm"], why,
+                                " First skipped " + blame if blame else ""))
         return gs
+
+    def _log_tensor_norms(self, model):
+        """Lightning's track_grad_norm: 2 - `grad_2.0_norm/<state_dict key>` per parameter tensor and `grad_2.0_norm_total`, through
+        model.log, from the gradient the last step's optimiser read (GlowEngine.grad_tensor_norms: after the all-reduce, x 1 / world)."""
+        eng = getattr(getattr(model, "seq_glow", None), "engine", None)
+        norms_of, log = getattr(eng, "grad_tensor_norms", None), getattr(model, "log", None)
+        if norms_of is None or log is None:
+            return
+        norms = norms_of(1.0 / self.world_size)
+        for key, value in norms.items():
+            log("grad_2.0_norm/" + key, value)
+        log("grad_2.0_norm_total", math.sqrt(sum(v * v for v in norms.values())))
 
     # ------------------------------------------------------------------ loop
     def fit(self, model, datamodule):
@@ -191,6 +215,8 @@ class Trainer:
                 self.batches_into_epoch = bi + 1
                 if step % self.log_every == 0:
                     gs = self._read_guard(model)      # (every rank: they stop together)
+                    if track_norm and gs:
+                        self._log_tensor_norms(model)
                     if self.rank == 0:
                         torch.cuda.synchronize()
                         norm = " grad_norm %.4e skipped %d" % (gs["last_norm"], gs["skipped"]) if track_norm and gs else ""

@@ -16,6 +16,7 @@ import torch.distributed as dist  # noqa: E402
 GRAPH = "--graph" in sys.argv   # the data-parallel step as two replayed hipGraphs with the collectives between them vs eager launches
 NCCL1 = "--nccl1" in sys.argv   # ONE rank on backend "nccl" (= RCCL): the collectives' launch path on this ROCm, no transport
 GUARD = "--guard" in sys.argv   # the non-finite step guard under data parallelism: one rank's shard poisoned, every rank skips
+BLAME = "--blame" in sys.argv   # the guard's blame record under data parallelism: every rank names the gradient tensors, one the input
 FINAL = "--final" in sys.argv or NCCL1   # final_model.yaml widths at BASELINE's synthetic dims, batch 256 per rank, T = 80
 
 
@@ -136,7 +137,7 @@ def run_graph_leg(rank, world, dev, graph, steps=8):
     return eng.params.detach().clone(), eng.adam_m.detach().clone(), eng.adam_v.detach().clone(), replayed
 
 
-def run_guard_leg(rank, world, dev, steps=4, poisoned_step=2, poisoned_rank=1, graph=False):
+def run_guard_leg(rank, world, dev, steps=4, poisoned_step=2, poisoned_rank=1, graph=False, blame=False):
     """`steps` data-parallel steps (graph: as two replayed hipGraphs from the third on) with Optim.skip_nonfinite; on step `poisoned_step` (1-based) the shard of `poisoned_rank`
     alone holds a NaN (one element of p1_face at a modelled frame). The decision is taken after the all-reduce, so every rank must
     skip that step and no other, and hold the parameters of every other rank after every step.
@@ -151,6 +152,8 @@ def run_guard_leg(rank, world, dev, steps=4, poisoned_step=2, poisoned_rank=1, g
     hp["gradient_clip_val"] = 20
     hp["Train"]["use_negative_nll_loss"] = False
     hp["Optim"]["skip_nonfinite"] = True
+    if blame:
+        hp["print_nan_grads"] = True
     torch.manual_seed(0)
     m = LetsFaceItGlow(Namespace(**hp))
     m.seq_glow.load_state_dict(fx.state_dict(torch.float32))
@@ -185,6 +188,20 @@ def run_guard_leg(rank, world, dev, steps=4, poisoned_step=2, poisoned_rank=1, g
     print("guard rank %d: skipped %d consecutive %d applied %d step_count %d" % (rank, gs["skipped"], gs["consecutive"], gs["applied"],
                                                                                  eng.step_count), flush=True)
     ok = ok and (gs["skipped"], gs["consecutive"], gs["applied"], eng.step_count) == (1, 0, steps - 1, steps - 1)
+    if blame:
+        # the gradient is blamed after the all-reduce: the same tensors on every rank; inputs and NLL are each rank's own shard
+        st = eng.blame_state()
+        grads = None if st is None else [(g["key"], g["nan"], g["inf"], g["first"]) for g in st["gradients"]]
+        everyone = [None] * world
+        dist.all_gather_object(everyone, grads)
+        same = st is not None and len(grads) > 0 and all(e == grads for e in everyone)
+        inputs = {} if st is None else {k: v["first"] for k, v in st["inputs"].items()}
+        nll_bad = -1 if st is None or st["nll"] is None else st["nll"]["nan"] + st["nll"]["inf"]
+        print("blame rank %d: step %d, gradient tensors blamed %d (same on every rank %s), inputs %s, non-finite NLL entries %d"
+              % (rank, -1 if st is None else st["step"], 0 if grads is None else len(grads), same, sorted(inputs.items()), nll_bad), flush=True)
+        want_inputs = {"p1_face": (3, fx.start + 2, 1)} if rank == poisoned_rank else {}
+        ok = ok and same and st["step"] == poisoned_step and inputs == want_inputs and (nll_bad > 0) == (rank == poisoned_rank)
+        ok = ok and eng.blame_state() is None      # (cleared by the read)
     return ok, eng.params.detach().clone(), replayed
 
 
@@ -195,14 +212,16 @@ def main():
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     dist.init_process_group("nccl" if NCCL1 else "gloo", rank=rank, world_size=world)
     print("rank %d of %d up (%s)" % (rank, world, dist.get_backend()), flush=True)
-    if GUARD:
-        if GRAPH:      # eight steps, the sixth - a replay - poisoned: the two-graph step against the eager data-parallel step
+    if GUARD or BLAME:
+        if GRAPH and not BLAME:      # eight steps, the sixth - a replay - poisoned: the two-graph step against the eager data-parallel step
             ok_e, pe, _ = run_guard_leg(rank, world, dev, steps=8, poisoned_step=6)
             ok_g, pg, replayed = run_guard_leg(rank, world, dev, steps=8, poisoned_step=6, graph=True)
             same = torch.equal(pe, pg)
             print("guard rank %d: graph leg bit-identical to the eager leg: %s; steps on captured graphs: %d" % (rank, same, replayed),
                   flush=True)
             ok = ok_e and ok_g and same and replayed >= 3
+        elif BLAME:      # eager leg only, three steps, rank 1's shard poisoned on the second
+            ok = run_guard_leg(rank, world, dev, steps=3, blame=True)[0]
         else:
             ok = run_guard_leg(rank, world, dev)[0]
         flag = torch.tensor([1.0 if ok else 0.0], dtype=torch.float64)
