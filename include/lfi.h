@@ -852,6 +852,25 @@ int lfi_segment_stats(const float* flat, long n, const long* segs, int nseg, int
 int lfi_segment_stats_guard(const float* flat, long n, const long* segs, int nseg, int nextra, const float* const* xptrs,
                             const long* xlen, const void* rec, void* blame, void* work, void* stream);
 
+/* ---------------------------------------------------------------- per-row keyed sampling noise (a counter-based prior for samplers)
+ * rng: DEVICE memory, B x 2 64-bit words, (key, position) per row. For row r with key K, the frame at position p, candidate k
+ * (0 for a plain step) and channel c:
+ *   o[0..3] = Philox4x32-10 with key words (lo32(K), hi32(K)) and counter words (c >> 2, lo32(p), hi32(p), k)
+ *   u_j = (o_j >> 9) * 2^-23 + 2^-24                       exact in fp32, inside (0, 1), never 0 or 1
+ *   g0 = sqrt(-2 ln u0) cos(2 pi u1), g1 = sqrt(-2 ln u0) sin(2 pi u1); g2, g3 likewise from (u2, u3); channel c takes g[c & 3]
+ *   z = eps * g, |g| <= sqrt(48 ln 2) ~ 5.77               accurate logf / sqrtf / sincospif, fp32 throughout
+ * lfi_row_noise: out[i * stride_frame + r * stride_row + k * stride_cand + c] = eps * g(key_r, pos_r + i, k, c) for i < n, r < B,
+ * k < max(ncand, 1), c < C (strides in floats): (B, C), (B, ncand, C), (n, B, C) and (n, B, ncand, C) are all one call, padded
+ * layouts too. `out` may sit at any 4-byte address; nothing but the addressed elements is written. With advance > 0 the SAME
+ * launch then sets pos_r += advance (every read of a row's position precedes its write: one workgroup per row, a barrier between);
+ * n == 0 with advance > 0 only advances. One launch, deterministic, no atomics, capturable. Null pointers, negative sizes or
+ * strides and ncand > 256 are refused before the launch; B == 0, and nothing to write with advance == 0, succeed without one.
+ * lfi_row_rng_advance: pos_r += lens ? max(lens[r], 0) : delta (lens: B ints on the device) - for frames a row takes without a
+ * draw (observed frames, a caller's own noise). */
+int lfi_row_noise(unsigned long long* rng /* device, B x 2: (key, pos) */, int B, int n, int ncand, int C, float eps, float* out,
+                  long stride_frame, long stride_row, long stride_cand, int advance, void* stream);
+int lfi_row_rng_advance(unsigned long long* rng, int B, long delta, const int* lens /* device int32 B, or null */, void* stream);
+
 /* ---------------------------------------------------------------- callers either side of the flow (SURVEY.md par. 8f)
  * Window sampler, replaces MimicryDataset.__getitem__ + DataLoader collation (code/glow_pytorch/mimicry_data_module.py:45-78):
  * one modality of a split lives in HBM as ONE (rows x dim) matrix, the recording bins back to back; a training window is T

@@ -223,6 +223,8 @@ def lib():
         "lfi_actnorm_forward": (i, [vp, i, i, vp, vp, i, vp, vp, vp]),
         "lfi_invconv_work_floats": (l, [i]),
         "lfi_invconv_weights": (i, [i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]),
+        "lfi_row_noise": (i, [vp, i, i, i, i, f, vp, l, l, l, i, vp]),
+        "lfi_row_rng_advance": (i, [vp, i, l, vp, vp]),
         "lfi_gather_sequences": (i, [vp, l, i, vp, i, i, vp, vp]),
         "lfi_jerk_mean": (i, [vp, i, i, i, vp, vp, vp]),
         "lfi_selftest_mfma": (i, [vp, vp]),
@@ -261,6 +263,7 @@ EXPORTS = [
     "lfi_grad_guard", "lfi_grad_guard_dev", "lfi_adam_clip_step_guard", "lfi_sgd_clip_step_guard", "lfi_rmsprop_clip_step_guard",
     "lfi_ema_update_guard", "lfi_set_step_params_t",
     "lfi_segment_stats_chunk", "lfi_segment_stats_work_floats", "lfi_segment_stats", "lfi_segment_stats_guard",
+    "lfi_row_noise", "lfi_row_rng_advance",
 ]
 
 # slots of the non-finite step guard's device record (include/lfi.h, LFI_GUARD_*): 8 bytes each

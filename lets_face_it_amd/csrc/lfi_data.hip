@@ -3,6 +3,7 @@
 // (code/glow_pytorch/mimicry_logger.py:187-196 -> glow/utils.py:53-58). Both are pure HBM streaming: coalesced row copies
 // and a fixed-order two-stage reduction (no float atomics, reproducible).
 #include "lfi_common.h"
+#include "lfi_philox.h"
 
 namespace {
 
@@ -76,17 +77,8 @@ __global__ __launch_bounds__(256) void pad_rows_kernel(const float* __restrict__
 // Dropout multipliers of the window encoders (nn.Dropout on ones(B, hist), glow/models.py:56-58): out[i] = 1 / keep with
 // probability keep, else 0. Counter-based Philox4x32-10 keyed on (seed, call offset): element i is output (i & 3) of counter
 // (i >> 2, segment, offset), so a launch is reproducible from (seed, offset) alone and all modalities share one launch.
+// (philox4x32_10: lfi_philox.h, shared with the per-row sampling noise of lfi_noise.hip)
 struct MaskSegs { float* out[4]; long n[4]; float keep[4]; int count; };
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&o)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
 // key: a DEVICE pair (seed, offset) when non-null (lfi_dropout_masks_dev: a captured hipGraph replays the launch with the
 // values the host put there before the replay), else the two arguments
 __global__ __launch_bounds__(256) void dropout_masks_kernel(MaskSegs m, unsigned long long seed, unsigned long long offset,
