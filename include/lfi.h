@@ -870,6 +870,22 @@ int lfi_segment_stats_guard(const float* flat, long n, const long* segs, int nse
 int lfi_row_noise(unsigned long long* rng /* device, B x 2: (key, pos) */, int B, int n, int ncand, int C, float eps, float* out,
                   long stride_frame, long stride_row, long stride_cand, int advance, void* stream);
 int lfi_row_rng_advance(unsigned long long* rng, int B, long delta, const int* lens /* device int32 B, or null */, void* stream);
+/* The row state moves with the row (SampleStream open / reset / reset_rows / save_rows / load_rows of a keyed session). rows,
+ * entries, keys and positions are HOST lists that travel in the kernel arguments, 128 rows per launch (a longer list is several
+ * launches): allocation-free, no host staging, no host wait. Only the listed rows are written; one thread owns one listed row,
+ * plain 8-byte stores. Every argument, every row and entry included, is checked before the first launch: null pointers, negative
+ * sizes, a row outside 0 .. B - 1 or listed twice, an entry outside 0 .. nsaved - 1 are argument errors; nrows == 0 succeeds
+ * without a launch.
+ * seed: rng[rows[j]] = (keys[j], positions ? positions[j] : 0); rows == NULL lists rows 0 .. nrows - 1; keys == NULL keeps every
+ * listed row's key and sets only its position.
+ * save: out[j] = rng[rows[j]], out nrows x 2 64-bit words on the device; rng is not written.
+ * load: rng[rows[j]] = saved[entries[j]] (saved: nsaved x 2 words on the device; an entry may repeat - a branch); with keys (host)
+ * the row takes keys[j] and the saved entry's position - a branch that draws differently from its sibling. */
+int lfi_row_rng_seed_rows(unsigned long long* rng, int B, int nrows, const int* rows, const unsigned long long* keys,
+                          const unsigned long long* positions, void* stream);
+int lfi_row_rng_save_rows(const unsigned long long* rng, int B, int nrows, const int* rows, unsigned long long* out, void* stream);
+int lfi_row_rng_load_rows(unsigned long long* rng, int B, int nrows, const int* rows, const int* entries, int nsaved,
+                          const unsigned long long* saved, const unsigned long long* keys, void* stream);
 
 /* ---------------------------------------------------------------- callers either side of the flow (SURVEY.md par. 8f)
  * Window sampler, replaces MimicryDataset.__getitem__ + DataLoader collation (code/glow_pytorch/mimicry_data_module.py:45-78):

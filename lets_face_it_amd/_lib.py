@@ -225,6 +225,9 @@ def lib():
         "lfi_invconv_weights": (i, [i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]),
         "lfi_row_noise": (i, [vp, i, i, i, i, f, vp, l, l, l, i, vp]),
         "lfi_row_rng_advance": (i, [vp, i, l, vp, vp]),
+        "lfi_row_rng_seed_rows": (i, [vp, i, i, P(i), P(C.c_ulonglong), P(C.c_ulonglong), vp]),
+        "lfi_row_rng_save_rows": (i, [vp, i, i, P(i), vp, vp]),
+        "lfi_row_rng_load_rows": (i, [vp, i, i, P(i), P(i), i, vp, P(C.c_ulonglong), vp]),
         "lfi_gather_sequences": (i, [vp, l, i, vp, i, i, vp, vp]),
         "lfi_jerk_mean": (i, [vp, i, i, i, vp, vp, vp]),
         "lfi_selftest_mfma": (i, [vp, vp]),
@@ -263,7 +266,7 @@ EXPORTS = [
     "lfi_grad_guard", "lfi_grad_guard_dev", "lfi_adam_clip_step_guard", "lfi_sgd_clip_step_guard", "lfi_rmsprop_clip_step_guard",
     "lfi_ema_update_guard", "lfi_set_step_params_t",
     "lfi_segment_stats_chunk", "lfi_segment_stats_work_floats", "lfi_segment_stats", "lfi_segment_stats_guard",
-    "lfi_row_noise", "lfi_row_rng_advance",
+    "lfi_row_noise", "lfi_row_rng_advance", "lfi_row_rng_seed_rows", "lfi_row_rng_save_rows", "lfi_row_rng_load_rows",
 ]
 
 # slots of the non-finite step guard's device record (include/lfi.h, LFI_GUARD_*): 8 bytes each

@@ -1,8 +1,8 @@
 // Per-row keyed sampling noise: a counter-based source of the prior draws of a sampler whose rows are independent conversations.
 // Every draw is a pure function of (the row's 64-bit key, the frame's 64-bit position, the candidate, the channel), so what a
 // conversation draws does not depend on the row it sits in, the batch size or what else drew before it, and the state - two words
-// per row - can travel with the row. The streaming sessions do not draw from it yet (they use the process generator); this unit is
-// the generator and its C entry points. The definition ("Keyed sampling noise"; tests/row_noise_reference.py restates it
+// per row - can travel with the row. Keyed streaming sessions (open_stream(row_seeds=...)) and inference(row_seeds=...) draw from it;
+// this unit is the generator, the row-state moves (seed / save / load of listed rows) and their C entry points. The definition ("Keyed sampling noise"; tests/row_noise_reference.py restates it
 // in numpy and the GPU tests hold the kernel to that):
 //   o[0..3] = philox4x32_10(counter (c >> 2, lo32(p), hi32(p), k), key (lo32(K), hi32(K)))
 //   u_j = (o_j >> 9) * 2^-23 + 2^-24              exact in fp32, in (0, 1), never 0 or 1
@@ -12,6 +12,8 @@
 // flag on the unit. Plain HBM streaming with 4-byte vector stores (no alignment assumption on `out`); no atomics, no scratch.
 #include "lfi_common.h"
 #include "lfi_philox.h"
+
+#include <vector>
 
 namespace {
 
@@ -61,7 +63,131 @@ __global__ __launch_bounds__(256) void row_rng_advance_kernel(unsigned long long
   rng[2 * (long)r + 1] += d;
 }
 
+// Row state that moves with the row (seed / save / load of listed rows): the lists travel in the kernel arguments, kRngListRows per
+// launch - 2.5 KB of the 4 KB an argument block may hold - so there is no host staging and no host wait. One thread owns one listed
+// row (no row is listed twice: checked on the host), plain 8-byte stores.
+constexpr int kRngListRows = 128;
+
+struct RngSeedList {
+  int rows[kRngListRows];
+  unsigned long long keys[kRngListRows];
+  unsigned long long pos[kRngListRows];
+};
+
+struct RngLoadList {
+  int rows[kRngListRows];
+  int entries[kRngListRows];
+  unsigned long long keys[kRngListRows];
+};
+
+struct RngRowList {
+  int rows[kRngListRows];
+};
+
+__global__ __launch_bounds__(kRngListRows) void row_rng_seed_rows_kernel(unsigned long long* rng, RngSeedList l, int n, int with_keys) {
+  const int j = threadIdx.x;
+  if (j >= n) return;
+  const long r = l.rows[j];
+  if (with_keys) rng[2 * r] = l.keys[j];
+  rng[2 * r + 1] = l.pos[j];
+}
+
+__global__ __launch_bounds__(kRngListRows) void row_rng_save_rows_kernel(const unsigned long long* __restrict__ rng, RngRowList l, int n,
+                                                                         unsigned long long* __restrict__ out) {
+  const int j = threadIdx.x;
+  if (j >= n) return;
+  const long r = l.rows[j];
+  out[2 * j] = rng[2 * r];
+  out[2 * j + 1] = rng[2 * r + 1];
+}
+
+__global__ __launch_bounds__(kRngListRows) void row_rng_load_rows_kernel(unsigned long long* rng, RngLoadList l, int n,
+                                                                         const unsigned long long* __restrict__ saved, int with_keys) {
+  const int j = threadIdx.x;
+  if (j >= n) return;
+  const long r = l.rows[j], e = l.entries[j];
+  rng[2 * r] = with_keys ? l.keys[j] : saved[2 * e];
+  rng[2 * r + 1] = saved[2 * e + 1];
+}
+
+// The checks the three row-list entry points share, before any launch: sizes, the state's address, every listed row inside the batch
+// and none twice (rows == nullptr: the identity list, where the entry point allows it).
+int row_rng_check_rows(const char* what, const void* rng, int B, int nrows, const int* rows, bool rows_optional) {
+  LFI_REQUIRE(B >= 0 && nrows >= 0, "%s: negative size (B %d, nrows %d)", what, B, nrows);
+  LFI_REQUIRE(rng && (reinterpret_cast<uintptr_t>(rng) & 7) == 0, "%s: null pointer / misaligned rng", what);
+  if (nrows == 0) return LFI_OK;
+  LFI_REQUIRE(nrows <= B, "%s: %d rows listed for a batch of %d", what, nrows, B);
+  LFI_REQUIRE(rows || rows_optional, "%s: null pointer (rows)", what);
+  if (!rows) return LFI_OK;
+  std::vector<unsigned char> seen(B, 0);
+  for (int j = 0; j < nrows; ++j) {
+    LFI_REQUIRE(rows[j] >= 0 && rows[j] < B, "%s: row %d of the list is %d, outside the batch (0 .. %d)", what, j, rows[j], B - 1);
+    LFI_REQUIRE(!seen[rows[j]], "%s: row %d is listed twice", what, rows[j]);
+    seen[rows[j]] = 1;
+  }
+  return LFI_OK;
+}
+
 }  // namespace
+
+extern "C" int lfi_row_rng_seed_rows(unsigned long long* rng, int B, int nrows, const int* rows, const unsigned long long* keys,
+                                     const unsigned long long* positions, void* stream) {
+  const char* what = "lfi_row_rng_seed_rows";
+  if (int rc = row_rng_check_rows(what, rng, B, nrows, rows, true)) return rc;
+  for (int j0 = 0; j0 < nrows; j0 += kRngListRows) {
+    const int n = nrows - j0 < kRngListRows ? nrows - j0 : kRngListRows;
+    RngSeedList l = {};
+    for (int j = 0; j < n; ++j) {
+      l.rows[j] = rows ? rows[j0 + j] : j0 + j;
+      l.keys[j] = keys ? keys[j0 + j] : 0ull;
+      l.pos[j] = positions ? positions[j0 + j] : 0ull;
+    }
+    hipLaunchKernelGGL(row_rng_seed_rows_kernel, dim3(1), dim3(kRngListRows), 0, (hipStream_t)stream, rng, l, n, keys ? 1 : 0);
+    LFI_LAUNCH_CHECK(what);
+  }
+  return LFI_OK;
+}
+
+extern "C" int lfi_row_rng_save_rows(const unsigned long long* rng, int B, int nrows, const int* rows, unsigned long long* out,
+                                     void* stream) {
+  const char* what = "lfi_row_rng_save_rows";
+  if (int rc = row_rng_check_rows(what, rng, B, nrows, rows, false)) return rc;
+  if (nrows == 0) return LFI_OK;
+  LFI_REQUIRE(out && (reinterpret_cast<uintptr_t>(out) & 7) == 0, "%s: null pointer / misaligned out", what);
+  for (int j0 = 0; j0 < nrows; j0 += kRngListRows) {
+    const int n = nrows - j0 < kRngListRows ? nrows - j0 : kRngListRows;
+    RngRowList l = {};
+    for (int j = 0; j < n; ++j) l.rows[j] = rows[j0 + j];
+    hipLaunchKernelGGL(row_rng_save_rows_kernel, dim3(1), dim3(kRngListRows), 0, (hipStream_t)stream, rng, l, n, out + 2 * (long)j0);
+    LFI_LAUNCH_CHECK(what);
+  }
+  return LFI_OK;
+}
+
+extern "C" int lfi_row_rng_load_rows(unsigned long long* rng, int B, int nrows, const int* rows, const int* entries, int nsaved,
+                                     const unsigned long long* saved, const unsigned long long* keys, void* stream) {
+  const char* what = "lfi_row_rng_load_rows";
+  LFI_REQUIRE(nsaved >= 0, "%s: negative size (nsaved %d)", what, nsaved);
+  if (int rc = row_rng_check_rows(what, rng, B, nrows, rows, false)) return rc;
+  if (nrows == 0) return LFI_OK;
+  LFI_REQUIRE(entries, "%s: null pointer (entries)", what);
+  LFI_REQUIRE(saved && (reinterpret_cast<uintptr_t>(saved) & 7) == 0, "%s: null pointer / misaligned saved", what);
+  for (int j = 0; j < nrows; ++j)
+    LFI_REQUIRE(entries[j] >= 0 && entries[j] < nsaved, "%s: entry %d of the list is %d, outside the saved rows (0 .. %d)", what, j,
+                entries[j], nsaved - 1);
+  for (int j0 = 0; j0 < nrows; j0 += kRngListRows) {
+    const int n = nrows - j0 < kRngListRows ? nrows - j0 : kRngListRows;
+    RngLoadList l = {};
+    for (int j = 0; j < n; ++j) {
+      l.rows[j] = rows[j0 + j];
+      l.entries[j] = entries[j0 + j];
+      l.keys[j] = keys ? keys[j0 + j] : 0ull;
+    }
+    hipLaunchKernelGGL(row_rng_load_rows_kernel, dim3(1), dim3(kRngListRows), 0, (hipStream_t)stream, rng, l, n, saved, keys ? 1 : 0);
+    LFI_LAUNCH_CHECK(what);
+  }
+  return LFI_OK;
+}
 
 extern "C" int lfi_row_noise(unsigned long long* rng, int B, int n, int ncand, int C, float eps, float* out, long stride_frame,
                              long stride_row, long stride_cand, int advance, void* stream) {

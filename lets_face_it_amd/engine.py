@@ -27,7 +27,7 @@ import torch
 
 from . import _lib
 from ._lib import EncDesc, FlowDims, FlowGrads, FlowParams, GemmDesc, P1Enc, PGemmDesc, check, ptr, translate_oom
-from .stream import SampleStream, StreamRows, check_return_nll  # noqa: F401 - StreamRows: callers import it from here
+from .stream import SampleStream, StreamRows, check_return_nll, row_keys  # noqa: F401 - StreamRows: callers import it from here
 
 ENC_ORDER = ("p1_face", "p2_face", "p1_speech", "p2_speech")  # FeatureEncoder concat order (models.py:127-143)
 FLOW_FIELDS = ("an_bias", "an_logs", "inv_l", "inv_u", "inv_logs", "inv_w", "w_ih", "w_hh", "b_ih", "b_hh",
@@ -2127,9 +2127,58 @@ class GlowEngine:
 
     # ------------------------------------------------------------------ streaming sampling
     @translate_oom
-    def open_stream(self, seed, noise_fn, masks_fn=None, bound=None, return_nll=False):
+    def open_stream(self, seed, noise_fn, masks_fn=None, bound=None, return_nll=False, row_seeds=None, eps=None):
         """A SampleStream over this engine (SeqGlow.open_stream): seed = {modality: (B, >= start, dim)} holding the first `start`
         frames of every modality; noise_fn(B, C) draws a step's prior noise (already * eps); masks_fn(B, N) the window encoders'
         dropout masks (None = none); bound() is False once the owning module has re-bound to another engine; return_nll (fixed for
-        the session): step() -> (frame, nll), as sample()'s."""
-        return SampleStream(self, seed, noise_fn, masks_fn, bound, return_nll)
+        the session): step() -> (frame, nll), as sample()'s. row_seeds (B keys in [0, 2**64)) with eps: a KEYED session, which draws
+        with row_noise from a (key, position) per row instead of noise_fn."""
+        return SampleStream(self, seed, noise_fn, masks_fn, bound, return_nll, row_seeds=row_seeds, eps=eps)
+
+    # ------------------------------------------------------------------ keyed sampling noise
+    def row_rng(self, row_seeds, positions=None):
+        """A keyed-noise row state for len(row_seeds) rows -> a new (B, 2) int64 tensor on the engine's device, (key, position) per
+        row as bit patterns: what a session opened with these row_seeds holds after every row took positions[r] frames (None: 0).
+        row_seeds: ints in [0, 2**64) or a 1-D CPU integer tensor (bit patterns); positions: ints in [0, 2**64). One launch, the
+        lists in its arguments."""
+        keys = row_keys(row_seeds, len(row_seeds))
+        B = len(keys)
+        pos = None
+        if positions is not None:
+            pos = row_keys(positions, B)
+        rng = torch.zeros(B, 2, dtype=torch.int64, device=self.device)
+        check(self.L.lfi_row_rng_seed_rows(rng.data_ptr(), B, B, None, (C.c_ulonglong * B)(*keys),
+                                           None if pos is None else (C.c_ulonglong * B)(*pos), _stream()), "lfi_row_rng_seed_rows")
+        return rng
+
+    def row_noise(self, rng, n=None, ncand=None, eps=1.0, advance=0, out=None):
+        """Keyed prior draws, already * eps: ONE lfi_row_noise launch on the current stream. rng: a (B, 2)
+        int64 tensor on the engine's device, (key, position) per row (row_rng makes one; a keyed session holds one). -> float32
+        (B, C), (B, ncand, C), (n, B, C) or (n, B, ncand, C) according to which of n / ncand are given: element [i, r, k] is the
+        draw of row r's key at position pos_r + i, candidate k (k = 0, i = 0 where the axis is absent). These are exactly the
+        tensors a keyed session draws for step / step_candidates / step_many / rollout_candidates, so a caller can build the noise=
+        argument that reproduces one. advance > 0: the same launch then moves every row's position by that much (rng is written).
+        out: a contiguous float32 tensor of the result's shape on the device to write into (default: a new one)."""
+        s = self.spec
+        if not (torch.is_tensor(rng) and rng.is_cuda and rng.device == self.device and rng.dtype == torch.int64 and rng.dim() == 2
+                and rng.shape[1] == 2 and rng.shape[0] >= 1 and rng.is_contiguous()):
+            raise ValueError("rng: expected a contiguous int64 GPU tensor (B, 2) on %s, got %s %s on %s"
+                             % (self.device, tuple(getattr(rng, "shape", ())), getattr(rng, "dtype", type(rng)), getattr(rng, "device", None)))
+        for name, v, top in (("n", n, 1 << 20), ("ncand", ncand, 256)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= top):
+                raise ValueError("%s: expected None or an int in 1 .. %d, got %r" % (name, top, v))
+        if isinstance(advance, bool) or not isinstance(advance, int) or advance < 0:
+            raise ValueError("advance: expected an int >= 0, got %r" % (advance,))
+        B = int(rng.shape[0])
+        shape = (() if n is None else (n,)) + (B,) + (() if ncand is None else (ncand,)) + (s.C,)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype == torch.float32
+                  and tuple(out.shape) == shape and out.is_contiguous()):
+            raise ValueError("out: expected a contiguous float32 GPU tensor %s on %s, got %s %s on %s"
+                             % (shape, self.device, tuple(getattr(out, "shape", ())), getattr(out, "dtype", type(out)),
+                                getattr(out, "device", None)))
+        K = 1 if ncand is None else ncand
+        check(self.L.lfi_row_noise(rng.data_ptr(), B, 1 if n is None else n, 0 if ncand is None else ncand, s.C, float(eps), out.data_ptr(),
+                                   B * K * s.C, K * s.C, 0 if ncand is None else s.C, advance, _stream()), "lfi_row_noise")
+        return out

@@ -568,18 +568,28 @@ class SeqGlow(nn.Module):
     def loss(self, objective, z):
         return (-(objective + modules.GaussianDiag.logp_simplified(z))) / _LN2
 
-    def inference(self, seq_len, data=None, noise=None, return_nll=False):
+    def inference(self, seq_len, data=None, noise=None, return_nll=False, row_seeds=None):
         """Autoregressive sampling (models.py:567-596). noise: optional (seq_len - start, B, C) prior draws * eps.
+        row_seeds (B ints in [0, 2**64), or a 1-D CPU integer tensor of bit patterns): KEYED noise instead - one lfi_row_noise launch
+        of layout (n, B, C) at positions 0 .. n - 1 with eps = hparams.Infer["eps"], so row r draws exactly what a session opened
+        with open_stream(row_seeds=...) draws for the same key frame by frame, whatever the batch it sits in. noise and row_seeds
+        together are a ValueError. The dropout masks of train mode stay on the process generator.
         return_nll=True -> (frames, nll): nll (seq_len - start, B) float32 on the device, the orientation of forward()'s stacked
         `losses`, holds every generated frame's NLL in bits - what forward() reports for that frame when the generated sequence is fed
         back teacher-forced (loss(), models.py:563-565), at no extra pass. It is the model's own density of the frame (temperature
         1) evaluated at the prior draw z the sampler was given (`noise`, already * eps), not a density of the tempered sampling
         distribution."""
         _engine.check_return_nll(return_nll)
+        if noise is not None and row_seeds is not None:
+            raise ValueError("inference: noise and row_seeds are both given: the prior draws are either the caller's or keyed")
         seed = data["p1_face"]
+        B = seed.shape[0]
+        keys = None if row_seeds is None else _engine.row_keys(row_seeds, B)
         eng = self._ensure_engine(seed.device)
         start = get_longest_history(self.hparams.Conditioning)
-        B = seed.shape[0]
+        if keys is not None:
+            with torch.no_grad():
+                noise = eng.row_noise(eng.row_rng(keys), n=seq_len - start, eps=self.hparams.Infer["eps"])
         if noise is None:
             shape = torch.zeros(seq_len - start, B, self.spec.C, device=seed.device)
             noise = modules.GaussianDiag.sample(shape, self.hparams.Infer["eps"])
@@ -587,7 +597,7 @@ class SeqGlow(nn.Module):
         with torch.no_grad():
             return eng.sample(seq_len, data, noise.contiguous().float(), masks, return_nll=return_nll)
 
-    def open_stream(self, seed, eps=None, return_nll=False):
+    def open_stream(self, seed, eps=None, return_nll=False, row_seeds=None):
         """Streaming autoregressive sampling: inference() one frame per call, for a live agent whose speech and interlocutor arrive
         frame by frame. seed: a dict like inference()'s `data` holding the first start = get_longest_history(...) frames of every
         modality (p1_face: B x start x C). Returns a lets_face_it_amd.engine.SampleStream: step(frame, noise=None) with frame =
@@ -647,7 +657,25 @@ class SeqGlow(nn.Module):
         (out, nll), out (B, n, C) the frames that entered the faces window, given or generated, nll (n, B). It leaves the session
         where n step_rows() calls leave it (steps += n): the static part once per chunk, runs of frames every row observes on the
         chunk forward chain, everything else on the rows chain frame by frame (st.last_plan shows the split); eager launches, no
-        graph. All six kinds of call alternate freely."""
+        graph. All six kinds of call alternate freely.
+
+        row_seeds (B ints in [0, 2**64), or a 1-D CPU integer tensor taken as bit patterns; keys may repeat) opens a KEYED session:
+        row r holds (key_r, position 0) in a (B, 2) int64 device tensor, and every call that draws when noise is None - step,
+        step_rows, step_many, step_rows_many, step_candidates / step_best_of, rollout_candidates / rollout_best_of - draws with ONE
+        lfi_row_noise launch from the row state instead of the process generator, scaled by eps: a draw is a pure function of (key,
+        position, candidate, channel), so what a conversation generates does not depend on the row it sits in, the batch size, what
+        other sessions drew or the form of the call (n step() calls, one step_many(n) and candidate 0 of rollout_candidates(n) use
+        the same noise; candidate 0 of step_candidates is step()'s). The position counts the frames a row has taken, observed or
+        generated, with or without a noise= of the caller's: step / observe / step_rows +1, step_many / observe_many /
+        step_rows_many +n, a ragged observe_many +lengths[r]; step_candidates and rollout_candidates move nothing, commit moves +1
+        / +n, discard +0. Key and position travel with the row: save_rows sets StreamRows.rng ((n, 2) int64; cpu(), to(), select()
+        and state_dict() carry it), load_rows restores it - load_rows(rows, saved, entries, row_seeds=[...]) gives a branch a key of
+        its own at the entry's position, and rows without rng need row_seeds. reset(seed, row_seeds=None) and reset_rows(rows,
+        seed, row_seeds=None) give new keys at position 0; with None a row keeps its key and REPLAYS its draws from position 0, so
+        a new conversation should be given its own key. row_rng() reads the state back (the one call that waits). All draws are
+        eager launches in front of the captured graphs, which are unchanged; no host wait is added. The dropout masks of a
+        train-mode session stay on the process generator: out of the keys' scope. Without row_seeds the session is unkeyed and
+        draws as before from the process generator (torch.manual_seed); row_seeds arguments on it are a ValueError."""
         _engine.check_return_nll(return_nll)
         p1 = seed.get("p1_face") if isinstance(seed, dict) else None
         if p1 is None:
@@ -662,7 +690,7 @@ class SeqGlow(nn.Module):
 
         with torch.no_grad():
             return eng.open_stream(seed, noise_fn, lambda B, N: self._draw_masks(B, N, dev), lambda: self.engine is eng,
-                                   return_nll=return_nll)
+                                   return_nll=return_nll, row_seeds=row_seeds, eps=eps)
 
     def invert(self, z_seq, data):
         """-> (reconstr_seq: list[N] of (B, C), backward_loss (1,))   (models.py:617-645)"""

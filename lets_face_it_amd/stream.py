@@ -75,6 +75,63 @@ def _index_list(name, idx, bound, where, count=None, distinct=True):
     return idx
 
 
+_KEY_MASK = (1 << 64) - 1
+_POSITION_MOVES = {"step": 1, "observe": 1, "step_rows": 1, "step_many": "n", "observe_many": "n", "step_rows_many": "n",
+                   "step_candidates": 0, "rollout_candidates": 0, "commit": "n", "discard": 0, "reset": 0}
+_UNKEYED = "row_seeds: the session was opened without row_seeds (it draws from the process generator): open it with open_stream(row_seeds=...)"
+
+
+def key_to_word(key):
+    """A row key in [0, 2**64) -> the int64 with the same bit pattern, what the (B, 2) int64 row state holds (2**63 -> -2**63)."""
+    if isinstance(key, bool) or not isinstance(key, int):
+        raise ValueError("row_seeds: expected ints in [0, 2**64), got %s %r" % (type(key).__name__, key))
+    if not 0 <= key <= _KEY_MASK:
+        raise ValueError("row_seeds: %d outside [0, 2**64)" % key)
+    return key - (1 << 64) if key >> 63 else key
+
+
+def word_to_key(word):
+    """key_to_word's inverse: an int64 of the row state -> the key in [0, 2**64)."""
+    return int(word) & _KEY_MASK
+
+
+def row_keys(row_seeds, count):
+    """The row_seeds argument (open_stream / reset / reset_rows / load_rows / inference), host data checked before any launch: a
+    sequence of `count` ints in [0, 2**64) - bools and floats are refused - or a 1-D CPU integer tensor of `count` entries taken as
+    bit patterns (an int64 -1 is the key 2**64 - 1). Keys may repeat. -> the keys as a list of ints in [0, 2**64)."""
+    vals = _host_ints("row_seeds", row_seeds, strict=True)
+    if len(vals) != count:
+        raise ValueError("row_seeds: %d listed for %d rows" % (len(vals), count))
+    if torch.is_tensor(row_seeds):
+        return [v & _KEY_MASK for v in vals]
+    for v in vals:
+        key_to_word(v)
+    return vals
+
+
+def row_position_advance(kind, n=1, lengths=None):
+    """The position rules of the keyed noise as one pure function: how far a call of `kind` moves a row's
+    position - the number of frames the row has taken since it was seeded, observed or generated, whoever supplied the noise. step,
+    observe, step_rows: 1; step_many, observe_many, step_rows_many: n, a ragged observe_many lengths[r] per row; step_candidates
+    and rollout_candidates: 0 (their draws are at (p, k) and (p + i, k), nothing is taken yet); commit: n - 1 after
+    step_candidates, the rollouts' frame count after rollout_candidates; discard and the pending draws a reset() drops: 0. -> an
+    int for every row, or (ragged) a list with one int per row."""
+    move = _POSITION_MOVES.get(kind)
+    if move is None:
+        raise ValueError("row_position_advance: %r is not a kind of session call (%s)" % (kind, ", ".join(_POSITION_MOVES)))
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+        raise ValueError("row_position_advance: n = %r is not a frame count" % (n,))
+    if lengths is not None:
+        if kind != "observe_many":
+            raise ValueError("row_position_advance: only observe_many takes lengths, not %s" % kind)
+        lens = [operator.index(v) for v in lengths]
+        bad = [v for v in lens if not 0 <= v <= n]
+        if bad:
+            raise ValueError("row_position_advance: lengths %s outside 0 .. %d" % (bad, n))
+        return lens
+    return n if move == "n" else move
+
+
 def plan_rows_many(all_observe, min_run):
     """The plan of a step_rows_many() round, a pure function of the mask (no device): all_observe[i] is true where EVERY row observes
     frame i. Maximal runs of at least min_run such frames go to the chunk forward chain (n + Ks - 1 cell times and one front end for
@@ -101,12 +158,21 @@ class StreamRows:
     R). A record is, in order: every conditioning window of SampleStream.mods (hist x in_dim each), the faces window ((hist1 + 1) x
     C), h (Ks x H), c (Ks x H, LSTM only), the frame counter (one float, only with use_frame_nb) - the layout lfi_stream_row_floats
     defines. Plain fp32 values: independent of the session's batch size and per-frame arithmetic. load_rows puts entries back into
-    rows of any session of the same model; cpu() / to(device) pause and resume, state_dict() / from_state_dict() store."""
+    rows of any session of the same model; cpu() / to(device) pause and resume, state_dict() / from_state_dict() store.
 
-    def __init__(self, data, signature, _engine=None, _param_version=None):
+    `rng`: the rows' keyed-noise state, an (n, 2) int64 tensor beside `data` - (key, position) per entry as bit patterns - from a
+    keyed session (open_stream(row_seeds=...)); None from an unkeyed one and for rows stored before the keys existed. It is not part
+    of the float record or of `signature`."""
+
+    def __init__(self, data, signature, _engine=None, _param_version=None, rng=None):
         self.data = data
         self.signature = self._canonical(signature)
         self._engine, self._param_version = _engine, _param_version   # (same-process check only: not part of state_dict())
+        if rng is not None and not (torch.is_tensor(rng) and rng.dtype == torch.int64 and rng.dim() == 2
+                                    and tuple(rng.shape) == (int(data.shape[0]), 2)):
+            raise ValueError("StreamRows: rng: expected an int64 tensor (%d, 2), (key, position) per entry, got %s %s"
+                             % (int(data.shape[0]), tuple(getattr(rng, "shape", ())), getattr(rng, "dtype", type(rng))))
+        self.rng = rng
 
     @staticmethod
     def _canonical(sig):
@@ -119,34 +185,37 @@ class StreamRows:
     def __len__(self):
         return int(self.data.shape[0])
 
-    def _like(self, data):
-        return StreamRows(data, self.signature, self._engine, self._param_version)
+    def _like(self, data, rng=None):
+        return StreamRows(data, self.signature, self._engine, self._param_version, rng=rng)
 
     def cpu(self):
-        return self._like(self.data.cpu())
+        return self._like(self.data.cpu(), None if self.rng is None else self.rng.cpu())
 
     def to(self, device):
-        return self._like(self.data.to(device).contiguous())
+        return self._like(self.data.to(device).contiguous(), None if self.rng is None else self.rng.to(device).contiguous())
 
     def select(self, indices):
         """The listed entries (repeats allowed), as a new StreamRows."""
         idx = torch.as_tensor(indices, dtype=torch.long, device=self.data.device).reshape(-1)
-        return self._like(self.data.index_select(0, idx))
+        return self._like(self.data.index_select(0, idx), None if self.rng is None else self.rng.index_select(0, idx.to(self.rng.device)))
 
     def state_dict(self):
-        """One tensor and plain Python values (torch.save-able). Whether the weights are the ones the rows were saved under is the
-        caller's responsibility once the rows leave the process."""
+        """One tensor and plain Python values (torch.save-able), and the key "rng" only for rows that carry keyed-noise state.
+        Whether the weights are the ones the rows were saved under is the caller's responsibility once the rows leave the process."""
         d = dict(zip(_ROW_FIELDS, self.signature))
         d["windows"] = [list(w) for w in d["windows"]]
         d["data"] = self.data
+        if self.rng is not None:
+            d["rng"] = self.rng
         return d
 
     @classmethod
     def from_state_dict(cls, d):
+        """state_dict()'s inverse; "rng" may be absent (rows of an unkeyed session, rows stored before the keys existed)."""
         missing = [k for k in _ROW_FIELDS + ("data",) if k not in d]
         if missing:
             raise KeyError("StreamRows.from_state_dict: missing %s" % missing)
-        return cls(d["data"], tuple(d[k] for k in _ROW_FIELDS))
+        return cls(d["data"], tuple(d[k] for k in _ROW_FIELDS), rng=d.get("rng"))
 
 
 class SampleStream:
@@ -169,8 +238,12 @@ class SampleStream:
     # what commit() has not installed yet: None, ncand (an int) of the one-frame candidates step_candidates() left, or the rollouts
     # rollout_candidates() left - a namespace of their kind, ncand, n and buffers
     _pending = None
+    # a keyed session's noise state (row_seeds): one (B, 2) int64 device tensor, (key, position) per row as bit patterns, allocated at
+    # the open and never reallocated; None: the session draws from the process generator through noise_fn
+    rng = None
+    eps = None
 
-    def __init__(self, eng, seed, noise_fn, masks_fn=None, bound=None, return_nll=False):
+    def __init__(self, eng, seed, noise_fn, masks_fn=None, bound=None, return_nll=False, row_seeds=None, eps=None):
         check_return_nll(return_nll)
         self.return_nll = return_nll            # fixed for the session: part of what the captured graph launches
         s = eng.spec
@@ -183,6 +256,13 @@ class SampleStream:
         self.start = s.start
         self.mods = [e for e in s.encoders if e.name not in ("p1_face", "frame_nb")]
         self._check_seed(seed)
+        keys = None
+        if row_seeds is not None:
+            keys = row_keys(row_seeds, B)
+            if isinstance(eps, bool) or not isinstance(eps, (int, float)):
+                raise TypeError("eps: a keyed session (row_seeds) scales its own draws: expected a number, got %s %r"
+                                % (type(eps).__name__, eps))
+            self.eps = float(eps)
         self.device = eng.device
         self.closed = False
         self.param_version = eng.param_version
@@ -249,6 +329,11 @@ class SampleStream:
                 check(-1, "lfi_stream_row_floats")
             self.row_signature = (s.C, s.H, s.Ks, s.rnn_type, bool(s.use_frame_nb), tuple((e.name, e.hist, e.in_dim) for e in self.mods),
                                   self.hist1, int(R))
+            if keys is not None:
+                # the keyed session's state and the one-frame draw's buffer (the other layouts' are sized by their calls)
+                self.rng = torch.zeros(B, 2, dtype=torch.int64, device=self.device)
+                self.draw = eng._buf("stream_noise_draw", f)[:f].view(B, s.C)
+                self._seed_rng(None, keys)
             self._fill(seed)
 
     # ---- validation (before any launch; the wording of GlowEngine._check_input)
@@ -316,24 +401,37 @@ class SampleStream:
                 eng.precision = keep_precision
 
     # ---- public surface
-    def reset(self, seed):
+    def reset(self, seed, row_seeds=None):
         """Start a new sequence from `seed` (same batch size); the captured graph is kept. Pending candidates and pending rollouts
-        are dropped."""
+        are dropped (their draws moved no position). A keyed session (open_stream(row_seeds=...)): with row_seeds - B keys, as
+        open_stream's - every row takes its new key at position 0; with None every row KEEPS its key and restarts at position 0,
+        which REPLAYS the same draws: the rows generate what they generated after the open, given the same seed and conditioning. A
+        new conversation should be given its own key. row_seeds on an unkeyed session is a ValueError."""
         self._check_usable(pending_ok=True)
         self._check_seed(seed)
+        keys = self._check_row_seeds(row_seeds, self.B)
         with self._owned():
+            if self.rng is not None:
+                self._seed_rng(None, keys)
             self._fill(seed)
 
-    def reset_rows(self, rows, seed):
+    def reset_rows(self, rows, seed, row_seeds=None):
         """Start new sequences in the listed batch rows only, between steps (a conversation joins a batched session in a row another
         one left). rows: a sequence of distinct ints in [0, B), or a CPU integer tensor; seed: as reset()'s, with batch len(rows) -
         entry j goes to session row rows[j]. Every other row carries on undisturbed. One launch (lfi_stream_reset_rows), no host wait;
         the captured graph, `steps` (frames since the open / reset(), which also index injected masks) and the per-frame arithmetic
-        are kept. A seed beyond the fp16 pieces' range is reported by the next steps' range guard, as a frame's would be."""
+        are kept. A seed beyond the fp16 pieces' range is reported by the next steps' range guard, as a frame's would be.
+
+        A keyed session (open_stream(row_seeds=...)): with row_seeds - len(rows) keys, entry j for row rows[j] - the listed rows take
+        those keys at position 0; with None a listed row KEEPS its key and restarts at position 0, which REPLAYS the same draws: the
+        row draws again what it drew after it was first seeded. A new conversation that joins in the row should be given its own
+        key. The other rows' (key, position) are undisturbed. One more small launch (lfi_row_rng_seed_rows, the keys in its
+        arguments), no host wait. row_seeds on an unkeyed session is a ValueError."""
         s, eng = self.eng.spec, self.eng
         self._check_usable()
         rows = _index_list("rows", rows, self.B, "the session's batch")
         n = len(rows)
+        keys = self._check_row_seeds(row_seeds, n)
         p1 = seed.get("p1_face") if isinstance(seed, dict) else None
         if p1 is None:
             raise KeyError("batch is missing modality 'p1_face'")
@@ -349,6 +447,8 @@ class SampleStream:
             check(eng.L.lfi_stream_reset_rows(self.B, n, row_a, len(self._row_win), self._row_win, self._seed_p, self._seed_ld,
                                               self._row_hist, self._row_dim, self._lead, self.h.data_ptr(), ptr(self.cs), s.Ks, s.H,
                                               ptr(self.frame_nb), self.guard.data_ptr(), _stream()), "lfi_stream_reset_rows")
+            if self.rng is not None:
+                self._seed_rng(rows, keys)
             if self._stream is not None and torch.cuda.current_stream(self.device) == self._stream:
                 for x in seeds:
                     x.record_stream(self._stream)
@@ -369,24 +469,45 @@ class SampleStream:
                                              self.h.data_ptr(), ptr(self.cs), s.Ks, s.H, ptr(self.frame_nb),
                                              1 - self._first_frame, out.data_ptr(), R, _stream()),
                   "lfi_stream_save_rows")
+            rng = None
+            if self.rng is not None:            # a keyed session: the rows' (key, position) travel beside their records
+                rng = torch.empty(n, 2, dtype=torch.int64, device=self.device)
+                check(eng.L.lfi_row_rng_save_rows(self.rng.data_ptr(), self.B, n, row_a, rng.data_ptr(), _stream()), "lfi_row_rng_save_rows")
         if self._stream is not None:
             out.record_stream(torch.cuda.current_stream(self.device))
-        return StreamRows(out, self.row_signature, weakref.ref(eng), self.param_version)
+            if rng is not None:
+                rng.record_stream(torch.cuda.current_stream(self.device))
+        return StreamRows(out, self.row_signature, weakref.ref(eng), self.param_version, rng=rng)
 
-    def load_rows(self, rows, saved, entries=None):
+    def load_rows(self, rows, saved, entries=None, row_seeds=None):
         """Put saved conversations into the listed rows, between steps: entry entries[j] of `saved` (a StreamRows of this model, from
         any session, batch size or device round trip) goes to session row rows[j]; entries defaults to range(len(rows)) and may
         repeat (a branch). Only the listed rows are written; one launch per 256 rows (lfi_stream_load_rows), no host wait; `steps`,
         the captured graph and the per-frame arithmetic are kept, and a value beyond the fp16 pieces' range is reported by the next
         steps' range guard, as a reseed's would be. Everything is checked before the first launch: a refused call leaves the
         session as it was. Into a session that has not stepped yet, h / c of every row are zeroed first and the first step runs as
-        a continuing one (a zeroed row is a first frame's state)."""
+        a continuing one (a zeroed row is a first frame's state).
+
+        A keyed session (open_stream(row_seeds=...)): key and position arrive with the entry (saved.rng), so a moved row draws on
+        exactly what it would have drawn where it was, and two rows loaded from one entry draw the SAME noise. row_seeds - len(rows)
+        keys, entry j for row rows[j] - gives row rows[j] the new key and the entry's position: a branch that draws differently
+        from its sibling from the next frame on. Saved rows without rng (from an unkeyed session, or stored before the keys
+        existed) need row_seeds and start at position 0; without it, ValueError. One more small launch (lfi_row_rng_load_rows /
+        lfi_row_rng_seed_rows, lists and keys in its arguments). An unkeyed session ignores saved.rng and refuses row_seeds."""
         s, eng = self.eng.spec, self.eng
         self._check_usable()
         rows = _index_list("rows", rows, self.B, "the session's batch")
         n = len(rows)
         if not isinstance(saved, StreamRows):
             raise TypeError("saved: expected a StreamRows (SampleStream.save_rows), got %s" % type(saved).__name__)
+        keys = self._check_row_seeds(row_seeds, n)
+        srng = saved.rng if self.rng is not None else None
+        if self.rng is not None and srng is None and keys is None:
+            raise ValueError("saved: the rows carry no keyed-noise state (rng is None: saved by an unkeyed session, or stored before "
+                             "the keys existed) and the session is keyed: give row_seeds, one key per listed row (position 0)")
+        if srng is not None and not (srng.is_cuda and srng.device == self.device and srng.is_contiguous()):
+            raise ValueError("saved.rng: expected a contiguous int64 tensor (%d, 2) on %s, got one on %s (StreamRows.to(device) moves "
+                             "it with the records)" % (len(saved), self.device, srng.device))
         for name, mine, theirs in zip(_ROW_FIELDS, self.row_signature, saved.signature):
             if mine != theirs:
                 raise ValueError("saved: layout signature differs in %s: the session's is %r, the saved rows' %r" % (name, mine, theirs))
@@ -401,6 +522,14 @@ class SampleStream:
             check(eng.L.lfi_stream_load_rows(self.B, n, row_a, ent_a, len(saved), len(self._row_win), self._row_win, self._row_hist,
                                              self._row_dim, self.h.data_ptr(), ptr(self.cs), s.Ks, s.H, ptr(self.frame_nb),
                                              x.data_ptr(), R, self.guard.data_ptr(), _stream()), "lfi_stream_load_rows")
+            if srng is not None:
+                key_a = None if keys is None else (C.c_ulonglong * n)(*keys)
+                check(eng.L.lfi_row_rng_load_rows(self.rng.data_ptr(), self.B, n, row_a, ent_a, len(saved), srng.data_ptr(), key_a,
+                                                  _stream()), "lfi_row_rng_load_rows")
+                if self._stream is not None and torch.cuda.current_stream(self.device) == self._stream:
+                    srng.record_stream(self._stream)
+            elif self.rng is not None:
+                self._seed_rng(rows, keys)
             if self.steps == 0:
                 self._resumed = True    # the session's first _launch then keeps h / c (first_frame = 1)
             if self._stream is not None and torch.cuda.current_stream(self.device) == self._stream:
@@ -423,6 +552,49 @@ class SampleStream:
             self.cs.zero_()
         if resumed:
             self._resumed = True
+
+    # ---- keyed noise (row_seeds): eager launches on the step's stream inside _owned(), never inside a captured region; host lists go
+    # to the device by value in the kernel arguments
+    def _check_row_seeds(self, row_seeds, count):
+        """The row_seeds argument of reset / reset_rows / load_rows, before any launch -> the keys as a list, or None."""
+        if row_seeds is None:
+            return None
+        if self.rng is None:
+            raise ValueError(_UNKEYED)
+        return row_keys(row_seeds, count)
+
+    def _seed_rng(self, rows, keys):
+        """(key, position 0) into the listed rows (None: every row) of the row state; keys None: each row keeps its key."""
+        n = self.B if rows is None else len(rows)
+        row_a = None if rows is None else (C.c_int * n)(*rows)
+        key_a = None if keys is None else (C.c_ulonglong * n)(*keys)
+        check(self.eng.L.lfi_row_rng_seed_rows(self.rng.data_ptr(), self.B, n, row_a, key_a, None, _stream()), "lfi_row_rng_seed_rows")
+
+    def _rng_advance(self, kind, n=1, lens=None, words=None):
+        """A keyed session's positions move by row_position_advance(kind, n, lens) for frames taken WITHOUT a draw of the session's
+        own (observed frames, a caller's noise=, a commit): lfi_row_rng_advance. words: the ragged lengths on the device."""
+        if self.rng is None:
+            return
+        move = row_position_advance(kind, n, lens)
+        if lens is None and move == 0:
+            return
+        check(self.eng.L.lfi_row_rng_advance(self.rng.data_ptr(), self.B, 0 if lens is not None else move,
+                                             None if lens is None else words.data_ptr(), _stream()), "lfi_row_rng_advance")
+
+    def _draw(self, kind, out, n=None, ncand=None):
+        """A keyed session's own draw for a call of `kind`, already * eps: ONE lfi_row_noise launch into the session-owned `out` of the
+        call's layout - (B, C), (B, ncand, C), (n, B, C) or (n, B, ncand, C) - at positions p .. p + n - 1, candidates 0 .. ncand - 1,
+        that moves the positions by row_position_advance(kind, n) in the same launch. -> out."""
+        return self.eng.row_noise(self.rng, n=n, ncand=ncand, eps=self.eps, advance=row_position_advance(kind, 1 if n is None else n),
+                                  out=out)
+
+    def row_rng(self):
+        """The keyed session's row state -> a (B, 2) int64 CPU copy, (key, position) per row as bit patterns (word_to_key gives the key
+        in [0, 2**64)). The one call of the keyed path that waits for the device: for tests and logging."""
+        self._check_usable(pending_ok=True)
+        if self.rng is None:
+            raise ValueError(_UNKEYED)
+        return self.rng.cpu()
 
     def _fill(self, seed):
         s, h1 = self.eng.spec, self.hist1
@@ -451,6 +623,7 @@ class SampleStream:
         self.faces = self.noise = self.windows = self.cond = self.pre = self.h = self.cs = self.work = self.p1work = self._wins = None
         self.nll = self.nll_work = self.score_work = self.obs_z = self.obs_nll = None
         self.role = self.rows_work = self.rows_nll = self.rows_nll_work = None
+        self.rng = self.draw = None
 
     def __enter__(self):
         return self
@@ -485,7 +658,9 @@ class SampleStream:
         with self._owned():
             self._check_guard()
             if noise is None:
-                noise = self._noise_fn(self.B, s.C).contiguous()
+                noise = self._noise_fn(self.B, s.C).contiguous() if self.rng is None else self._draw("step", self.draw)
+            else:
+                self._rng_advance("step")
             self._advance(srcs, noise, None)
             out = self.faces[:, self.hist1].clone()
             nll = self.nll.clone() if self.return_nll else None
@@ -520,6 +695,7 @@ class SampleStream:
                 self.score_work = eng._buf("stream_score_work", eng.L.lfi_flow_score_work_floats(C.byref(dims)))
                 self.obs_z = eng._buf("stream_obs_z", self.B * s.C)[:self.B * s.C].view(self.B, s.C)
                 self.obs_nll = eng._buf("stream_obs_nll", self.B)[:self.B]
+            self._rng_advance("observe")
             self._advance(srcs, None, face, return_z)
             nll = self.obs_nll.clone()
             z = self.obs_z.clone() if return_z else None
@@ -559,6 +735,7 @@ class SampleStream:
                 h=eng._buf("stream_cand_h" + tag, s.Ks * V * s.H),
                 c=eng._buf("stream_cand_c" + tag, s.Ks * V * s.H) if self.cs is not None else None,
                 work=eng._buf("stream_cand_work" + tag, floats),
+                draw=eng._buf("stream_cand_draw" + tag, V * s.C)[:V * s.C].view(B, ncand, s.C) if self.rng is not None else None,
                 choice=eng._buf_i32("stream_cand_choice" + tag, B)[:B])
         return c
 
@@ -590,7 +767,9 @@ class SampleStream:
         with self._owned():
             self._check_guard()
             cand = self._cand_buffers(ncand)
-            if noise is None:
+            if noise is None and self.rng is not None:
+                noise = self._draw("step_candidates", cand.draw, ncand=ncand)
+            elif noise is None:
                 noise = torch.stack([self._noise_fn(self.B, s.C) for _ in range(ncand)], 1).contiguous()
             self._advance(srcs, noise, None, ncand=ncand)
             faces, nll = cand.frames.clone(), cand.nll.clone()
@@ -656,6 +835,7 @@ class SampleStream:
                                                self.faces.data_ptr(), self.hist1 + 1, self.h.data_ptr(), ptr(self.cs), out.data_ptr(),
                                                nll.data_ptr(), picked.data_ptr(), self.guard.data_ptr(), _stream()),
                   "lfi_stream_commit_cand")
+            self._rng_advance("commit", 1)
             self._pending = None
             self.steps += 1
         self._record_out(out, nll, picked)
@@ -732,7 +912,10 @@ class SampleStream:
         with self._chunk_call(n, used) as rounds:
             (_, _, masks), = rounds             # (n <= _rollout_cap() <= _chunk_cap(): one round)
             L = eng.L
-            if noise is None:
+            if noise is None and self.rng is not None:
+                f = n * V * s.C
+                noise = self._draw("rollout_candidates", eng._buf("rollout_noise_draw", f)[:f].view(n, B, ncand, s.C), n=n, ncand=ncand)
+            elif noise is None:
                 noise = torch.stack([torch.stack([self._noise_fn(B, s.C) for _ in range(ncand)], 1) for _ in range(n)]).contiguous()
             used.append(noise)
             k, T = len(self._wins), s.start + n
@@ -801,6 +984,7 @@ class SampleStream:
                                                nll.data_ptr(), picked.data_ptr(), self.guard.data_ptr(), _stream()),
                   "lfi_stream_commit_cand_seq")
             eng._toc("stream_rollout_commit", ev)
+            self._rng_advance("commit", n)
             self._publish_guard()
             self._pending = None
             self.steps += n
@@ -965,7 +1149,9 @@ class SampleStream:
         srcs.append(None)                       # (the faces window has no source: the chain writes its frames)
         with self._chunk_call(n, used) as rounds:
             if noise is None:
-                noise = self._draw_noise(n)
+                noise = self._draw_noise(n, "step_many")
+            else:
+                self._rng_advance("step_many", n)
             used.append(noise)
             out = torch.empty(self.B, n, s.C, dtype=torch.float32, device=self.device)
             nll = torch.empty(n, self.B, dtype=torch.float32, device=self.device) if self.return_nll else None
@@ -1056,7 +1242,9 @@ class SampleStream:
         used = list(srcs)
         with self._chunk_call(n, used) as rounds:
             if noise is None:
-                noise = self._draw_noise(n)
+                noise = self._draw_noise(n, "step_rows_many")
+            else:
+                self._rng_advance("step_rows_many", n)
             used.append(noise)
             out = torch.empty(self.B, n, s.C, dtype=torch.float32, device=self.device)
             nll = torch.empty(n, self.B, dtype=torch.float32, device=self.device)
@@ -1092,8 +1280,12 @@ class SampleStream:
             for x in used:
                 x.record_stream(torch.cuda.current_stream(self.device))
 
-    def _draw_noise(self, n):
-        """n prior draws of the session's own, stacked (n, B, C): the random numbers n one-frame calls consume."""
+    def _draw_noise(self, n, kind):
+        """n prior draws of the session's own, stacked (n, B, C): the random numbers n one-frame calls consume. A keyed session: one
+        launch into the chunk's own buffer, the positions move by the call's n in it."""
+        if self.rng is not None:
+            f = n * self.B * self.eng.spec.C
+            return self._draw(kind, self.eng._buf("chunk_noise_draw", f)[:f].view(n, self.B, self.eng.spec.C), n=n)
         return torch.stack([self._noise_fn(self.B, self.eng.spec.C) for _ in range(n)]).contiguous()
 
     def _round(self, srcs, m, masks, chain, lens=None, noise=None, roles=None, out=None, o=0):
@@ -1137,6 +1329,8 @@ class SampleStream:
             name = "lfi_stream_chunk_gen_out"
             more = (gen, out.data_ptr() + 4 * o * s.C, out.shape[1] * s.C, ptr(self.frame_nb), self.guard.data_ptr())
         check(getattr(eng.L, name)(*head, seq_p, *tabs, *more, _stream()), name)
+        if noise is None:                       # (an observe_many round: frames taken without a draw)
+            self._rng_advance("observe_many", m, lens, words)
         self.steps += m
         return done
 
@@ -1365,7 +1559,9 @@ class SampleStream:
                 self.rows_nll_work = eng._buf("stream_rows_nll_work", eng.L.lfi_flow_sample_nll_work_floats(C.byref(dims)))
                 self.role = eng._buf_i32("stream_role", self.B)
             if noise is None:
-                noise = self._noise_fn(self.B, s.C).contiguous()
+                noise = self._noise_fn(self.B, s.C).contiguous() if self.rng is None else self._draw("step_rows", self.draw)
+            else:
+                self._rng_advance("step_rows")
             if not observed.is_cuda:
                 observed = observed.pin_memory().to(self.device, non_blocking=True)
             self._advance(srcs, noise, face, observed=observed)
