@@ -397,7 +397,13 @@ int lfi_invconv_weights(int C, const float* inv_l, const float* inv_u, const flo
  * recomputed for every generated frame. kind 0: "none" (raw window); 1: "mlp" = LeakyReLU(window W1^T + b1);
  * 2: "rnn" = GRU from h0 = 0 over the window (output folded: the hidden state once); 3: "lstm" = nn.LSTM likewise
  * (glow/models.py:27-33,65-69; four gate blocks in w_ih / w_hh / b_ih / b_hh). `col` = first column of the
- * p1_face block in the (folded) feature layout / in wct; eval mode (no dropout), as SeqGlow.inference runs. */
+ * p1_face block in the (folded) feature layout / in wct; eval mode (no dropout), as SeqGlow.inference runs.
+ * Arithmetic of the in-sampler encoder by d->gemm_precision, which the drivers hand on unchanged: the mlp's product, the recurrent
+ * kinds' input projection and e wct[:, col : col + hid]^T are lfi_gemm_f32 products at that precision; it is also the
+ * lfi_enc_desc.precision of the recurrence, where 1 -> bf16x3 recurrence; any other value -> exact f32 recurrence; loops take the GEMM
+ * mode as given (the fused GRU kernels, hid <= 256, know only "== 1"; the unfused GRU loop, hid > 256, and the LSTM loop pass the
+ * value to their per-step lfi_gemm_f32, where 5 and 9 mean what they mean there). The features lie in p1work with row pitch
+ * (hid + 3) & ~3; the padding columns are never read. */
 typedef struct {
   int kind, hid;
   const float *w1, *b1;                        /* mlp: [hid][hist1*C], [hid] */

@@ -1121,12 +1121,15 @@ inline FramePlan flow_frame_plan(const lfi_flow_dims* d) {
 // What lfi_flow_sample_seq_nll, lfi_flow_score_seq_from and lfi_flow_step_rows_from (and lfi_flow_score_seq_chunk, lfi_flow_chunk.hip) ask of the arguments they share, in one order.
 // who_from: the name first_frame is reported under (the sampler's is its _from entry point); ptrs_ok: the caller's own list of
 // pointers that must not be null. A rule on the frame count itself is the caller's and follows this check.
+// What has to fit into the E columns of wct is what the window product reads of them: hist1 * C columns from p1->col for a raw
+// window, p1->hid for an encoded one (its features, not its frames - a feature vector may well be narrower than the window).
 inline int frame_args_check(const char* who, const char* who_from, const lfi_flow_dims* d, bool ptrs_ok, long E, int hist1, int start,
-                     int nframes, int seq_len, const float* cstate, int first_frame) {
+                     int nframes, int seq_len, const float* cstate, int first_frame, const lfi_p1enc* p1) {
   LFI_REQUIRE(first_frame >= 0, "%s: negative first_frame", who_from);
   LFI_REQUIRE(ptrs_ok, "%s: null pointer", who);
   LFI_REQUIRE(hist1 >= 0 && hist1 <= start && start + nframes <= seq_len, "%s: bad frame range", who);
-  LFI_REQUIRE((long)hist1 * d->C <= E, "%s: window wider than the feature vector", who);
+  const long p1cols = p1 && p1->kind != 0 ? (long)p1->hid : (long)hist1 * d->C, p1col = p1 ? p1->col : 0;
+  LFI_REQUIRE(p1col >= 0 && p1col + p1cols <= E, "%s: window wider than the feature vector", who);
   LFI_REQUIRE(!d->lstm || cstate, "%s: the LSTM cell needs cstate", who);
   return LFI_OK;
 }
@@ -1630,7 +1633,7 @@ int chunk_front(const char* who, const lfi_flow_dims* d, const lfi_flow_params* 
                 const lfi_p1enc* p1, float* chunk_work, float* z, float* nll, void* stream, Kf (*pick)(const FramePlan&, bool), SC* sc,
                 Kf* kernel, size_t* lds) {
   int rc;
-  if ((rc = frame_args_check(who, who, d, ptrs_ok, E, hist1, start, nframes, seq_len, cstate, first_frame))) return rc;
+  if ((rc = frame_args_check(who, who, d, ptrs_ok, E, hist1, start, nframes, seq_len, cstate, first_frame, p1))) return rc;
   LFI_REQUIRE(nframes >= 1 && nframes <= d->N, "%s: %d frames, the work area holds d->N = %d", who, nframes, d->N);
   LFI_REQUIRE(hist1 >= 1, "%s: bad frame range (hist1 %d)", who, hist1);
   LFI_REQUIRE((long)nframes * f.B < (1L << 24), "%s: %d frames x batch %d: too many rows for one launch", who, nframes, f.B);

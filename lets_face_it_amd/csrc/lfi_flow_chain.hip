@@ -1115,7 +1115,7 @@ int sample_seq_run(const char* who, const char* who_from, const char* who_nll, c
   int rc = fill_flow(d, p, prep, &f, who);
   if (rc) return rc;
   if ((rc = frame_args_check(who, who_from, d, prep && wct && pre_static && noise && faces && h && work,
-                             E, hist1, start, nframes, seq_len, cstate, first_frame))) return rc;
+                             E, hist1, start, nframes, seq_len, cstate, first_frame, p1))) return rc;
   LFI_REQUIRE(!nll || nll_work, "%s: nll needs nll_work (lfi_flow_sample_nll_work_floats)", who_nll);
   if (ncand) {
     LFI_REQUIRE(ncand >= 1 && d->B % ncand == 0 && (long)d->B <= kCandMaxRows,
@@ -1254,7 +1254,7 @@ extern "C" int lfi_flow_sample_cand_from(const lfi_flow_dims* d, const lfi_flow_
   int rc = fill_flow(d, p, prep, &f, who);
   if (rc) return rc;
   if ((rc = frame_args_check(who, who, d, prep && wct && pre_static && noise && faces && h && work && cand_frames && cand_nll && cand_h && cand_work,
-                             E, hist1, start, nframes, seq_len, cstate, first_frame))) return rc;
+                             E, hist1, start, nframes, seq_len, cstate, first_frame, p1))) return rc;
   LFI_REQUIRE(nframes == 1, "%s: %d frames (one frame per call)", who, nframes);
   LFI_REQUIRE(ncand >= 1 && (long)d->B * ncand <= kCandMaxRows, "%s: %d candidates per row (1 .. %ld at batch %d)", who, ncand,
               kCandMaxRows / d->B, d->B);
@@ -1334,7 +1334,7 @@ extern "C" int lfi_flow_score_seq_from(const lfi_flow_dims* d, const lfi_flow_pa
   if (rc) return rc;
   const char* who = "lfi_flow_score_seq_from";
   if ((rc = frame_args_check(who, who, d, prep && wct && pre_static && faces && h && work && score_work && nll, E, hist1, start, nframes,
-                             seq_len, cstate, first_frame))) return rc;
+                             seq_len, cstate, first_frame, p1))) return rc;
   LFI_REQUIRE(nframes >= 0, "%s: bad frame range", who);
   const int B = f.B, C = f.C, D = f.D, Ks = f.Ks;
   hipStream_t st = (hipStream_t)stream;
@@ -1447,7 +1447,7 @@ int step_rows_frames(const char* who, const lfi_flow_dims* d, const lfi_flow_par
   int rc = fill_flow(d, p, prep, &f, who);
   if (rc) return rc;
   if ((rc = frame_args_check(who, who, d, prep && wct && pre_static && noise && faces && h && work && nll && nll_work && observed && rows_work,
-                             E, hist1, start, nframes, seq_len, cstate, first_frame))) return rc;
+                             E, hist1, start, nframes, seq_len, cstate, first_frame, p1))) return rc;
   LFI_REQUIRE(nframes >= 1, "%s: %d frames (at least one)", who, nframes);
   LFI_REQUIRE((reinterpret_cast<uintptr_t>(rows_work) & 3) == 0, "%s: rows_work is not 4-byte aligned", who);
   const int B = f.B, C = f.C, D = f.D, H = f.H, Ks = f.Ks;

@@ -38,13 +38,16 @@ def window_rows(dims, device=None):
     return (b * dims.T + pos0 + n).unsqueeze(1) + torch.arange(dims.hist, device=device).unsqueeze(0)
 
 
-def windows_forward(Xp, whh, b_ih, b_hh, mask, dims, lstm=False, taps=None):
+def windows_forward(Xp, whh, b_ih, b_hh, mask, dims, lstm=False, taps=None, h0=None, mm=torch.matmul, sig=torch.sigmoid, tanh=torch.tanh):
     """-> (hseq [hist][F][hid], features [F][hid (1 + dup)]). mask: (F x hist) multipliers of the INPUT, or None.
     taps: a list that receives per step the pre-activation tensors (gi, gh) (LSTM: (pre, pre)), each with its gradient retained when
-    it needs one: their .grad after backward() is dgi[s] / dgh[s]."""
+    it needs one: their .grad after backward() is dgi[s] / dgh[s].
+    h0 (F x hid, default zero: the definition), mm, sig, tanh: the state the recurrence starts from, the product h W_hh^T and the gate
+    non-linearities, for an arithmetic model or a planted defect built on this recurrence (tests/frame_reference.py); the defaults
+    are the definition."""
     F, hid = dims.N * dims.B, dims.hid
     rows = window_rows(dims, Xp.device)
-    h = Xp.new_zeros(F, hid)
+    h = Xp.new_zeros(F, hid) if h0 is None else h0
     c = Xp.new_zeros(F, hid)
     hs = []
     for s in range(dims.hist):
@@ -52,7 +55,7 @@ def windows_forward(Xp, whh, b_ih, b_hh, mask, dims, lstm=False, taps=None):
         if mask is not None:
             x = mask[:, s].to(Xp.dtype).unsqueeze(1) * x
         gi = x + b_ih
-        gh = h @ whh.t() + b_hh
+        gh = mm(h, whh.t()) + b_hh
         if lstm:
             pre = gi + gh
             if taps is not None:
@@ -60,17 +63,17 @@ def windows_forward(Xp, whh, b_ih, b_hh, mask, dims, lstm=False, taps=None):
                     pre.retain_grad()
                 taps.append((pre, pre))
             i, f, g, o = pre[:, :hid], pre[:, hid:2 * hid], pre[:, 2 * hid:3 * hid], pre[:, 3 * hid:]
-            c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
-            h = torch.sigmoid(o) * torch.tanh(c)
+            c = sig(f) * c + sig(i) * tanh(g)
+            h = sig(o) * tanh(c)
         else:
             if taps is not None:
                 if gi.requires_grad:
                     gi.retain_grad()
                     gh.retain_grad()
                 taps.append((gi, gh))
-            r = torch.sigmoid(gi[:, :hid] + gh[:, :hid])
-            z = torch.sigmoid(gi[:, hid:2 * hid] + gh[:, hid:2 * hid])
-            n = torch.tanh(gi[:, 2 * hid:] + r * gh[:, 2 * hid:])
+            r = sig(gi[:, :hid] + gh[:, :hid])
+            z = sig(gi[:, hid:2 * hid] + gh[:, hid:2 * hid])
+            n = tanh(gi[:, 2 * hid:] + r * gh[:, 2 * hid:])
             h = (1.0 - z) * n + z * h
         hs.append(h)
     return torch.stack(hs), (torch.cat([h, h], dim=1) if dims.dup else h)

@@ -7,6 +7,10 @@ through. Written from glow/models.py as include/lfi.h cites it (reverse_flow :34
 Frame n of a run (t = start + n), on the B rows of the session:
 
     c      = LeakyReLU_0.01(pre_static[n] + faces[:, t - hist1:t].reshape(B, hist1 C) @ wct[:, col:col + hist1 C]^T)      (B x Ks D)
+             or, with the window behind a ModalityEncoder of hid units (lfi_p1enc kind mlp / rnn / lstm, inp["p1enc"]):
+    e      = LeakyReLU_0.01(window @ W1^T + b1)   |   the state behind the window's last frame of a GRU / an LSTM from h = c = 0
+             over its hist1 frames (encoder_reference.windows_forward: the recurrence is not written a second time)      (B x hid)
+    c      = LeakyReLU_0.01(pre_static[n] + e @ wct[:, col:col + hid]^T)
     gic[k] = c[:, k D:(k + 1) D] @ W_ih[k][:, Ch:]^T + b_ih[k]
     generate (steps Ks-1 .. 0 from the prior draw noise[n]):  [z1 | z2'] -> cell(z1, gic[k], state k) -> o -> z2 = z2' / scale - shift
                                                               (additive: z2' - o) -> a = [z1 | z2] W^-1 -> x = a exp(-logs) - bias
@@ -19,12 +23,14 @@ of a ragged chunk behind its length: nothing of it moves).
 
 A run is a dict: x (N x B x C, the frame: generated or given), z (N x B x C: the prior draw or the latent), nll (N x B), h and cstate
 (Ks x N x B x H, the state AFTER each frame; cstate None for the GRU cell), c (N x B x Ks D), gic (N x Ks x B x G), raw_scale
-(N x Ks x B x C2, the coupling's sigmoid before the clamp; None when additive) and logdet_const.
+(N x Ks x B x C2, the coupling's sigmoid before the clamp; None when additive), logdet_const and, with an encoder, e (N x B x hid: for
+the input conditions, not a compared part - where the kernels keep it is not ABI).
 """
 import math
 
 import torch
 
+import encoder_reference as er
 import flow_reference as fr
 from flow_reference import (CLAMP_EPS, EPS, F32_FACTOR, LN2, LOG2PI, MB, MODEL_FACTOR, Dims, _fast_sigmoid, _fast_tanh,  # noqa: F401
                             _invconv, _prod3, derived, failures, make_inputs, rel_l2, tail_start, worst)
@@ -42,18 +48,42 @@ def roles_ragged(d, lengths):
     return torch.where(n < torch.as_tensor(lengths).unsqueeze(0), OBS, ABSENT)
 
 
-def make_frame_inputs(d, hist1, dense=False, seed=0, clamp=False):
+ENCS = ("none", "mlp", "rnn", "lstm")        # lfi_p1enc.kind 0 .. 3
+
+
+def make_frame_inputs(d, hist1, dense=False, seed=0, clamp=False, enc="none", ehid=0, col=0):
     """flow_reference.make_inputs' parameters and seed frames (x0 is `faces`, B x seq_len x C with seq_len = d.T), plus what a per-frame
     driver is given: wct (Ks D x E, the window's columns from `col`), pre_static (N x B x Ks D) and the prior draws (N x B x C).
-    Scales of a trained model: the pre-activation of c has a standard deviation of about 0.5."""
+    Scales of a trained model: the pre-activation of c has a standard deviation of about 0.5.
+
+    enc "mlp" / "rnn" / "lstm" (lfi_p1enc.kind 1 / 2 / 3): the window goes through a ModalityEncoder of ehid units first, whose
+    parameters are inp["p1enc"] - mlp: w1 (ehid x hist1 C), b1; rnn / lstm: w_ih (ng ehid x C), w_hh (ng ehid x ehid), b_ih, b_hh,
+    ng = 3 / 4 - and its features meet the columns [col, col + ehid) of wct. E >= col + ehid + 4 and every column of wct is drawn
+    alike: a column outside the block is wrong to read, and reading it shows. Scales: the features have a mean magnitude of a few
+    tenths and their term has about the variance of pre_static (tests/test_frame_reference_cpu.py checks both on the fp64 runs)."""
+    assert enc in ENCS
     inp = make_inputs(d, dense=dense, seed=seed, clamp=clamp)
     g = torch.Generator().manual_seed(seed + 1000)
     K1 = hist1 * d.C
-    E = ((K1 + 3) & ~3) + 4
-    inp["wct"] = torch.randn(d.Ks * d.D, E, generator=g) * (0.3 / math.sqrt(K1))
+    if enc == "none":
+        assert ehid == 0 and col == 0
+        E = ((K1 + 3) & ~3) + 4
+        inp["wct"] = torch.randn(d.Ks * d.D, E, generator=g) * (0.3 / math.sqrt(K1))
+    else:
+        assert ehid > 0 and col >= 0
+        E = ((col + ehid + 3) & ~3) + 4
+        inp["wct"] = torch.randn(d.Ks * d.D, E, generator=g) * (1.5 / math.sqrt(ehid))
     inp["pre_static"] = torch.randn(d.N, d.B, d.Ks * d.D, generator=g) * 0.4
     inp["noise"] = torch.randn(d.N, d.B, d.C, generator=g)
-    inp["hist1"], inp["col"] = hist1, 0
+    inp["hist1"], inp["col"] = hist1, col
+    if enc == "mlp":
+        inp["p1enc"] = {"kind": enc, "hid": ehid, "w1": torch.randn(ehid, K1, generator=g) * (0.8 / math.sqrt(K1)),
+                        "b1": torch.randn(ehid, generator=g) * 0.1}
+    elif enc != "none":
+        ng = 4 if enc == "lstm" else 3
+        inp["p1enc"] = {"kind": enc, "hid": ehid, "w_ih": torch.randn(ng * ehid, d.C, generator=g) * (1.0 / math.sqrt(d.C)),
+                        "w_hh": torch.randn(ng * ehid, ehid, generator=g) * (1.0 / math.sqrt(ehid)),
+                        "b_ih": torch.randn(ng * ehid, generator=g) * 0.1, "b_hh": torch.randn(ng * ehid, generator=g) * 0.3}
     del inp["gic"], inp["c"]
     return inp
 
@@ -110,6 +140,30 @@ def _window(faces, t, hist1):
     return faces[:, t - hist1:t].reshape(faces.shape[0], -1)
 
 
+def _enc_window(faces, t, hist1):
+    """The same frames as the encoder reads them: B x hist1 x C, oldest first (ModalityEncoder.forward, glow/models.py:55-80)."""
+    return faces[:, t - hist1:t]
+
+
+def _enc_state0(last, zero):
+    """The state the window's recurrence starts from: zero at every frame (last: where the previous frame's recurrence ended)."""
+    return zero
+
+
+def _enc_features(hseq):
+    """The features of a recurrent encoder: its state behind the window's last frame (output folded: the hidden state once)."""
+    return hseq[-1]
+
+
+def _enc_mlp_act(y):
+    return torch.nn.functional.leaky_relu(y, 0.01)
+
+
+def _enc_cols(wct, col, ehid):
+    """The columns of wct the features meet."""
+    return wct[:, col:col + ehid]
+
+
 def _halves(y, Ch):
     """(pass-through half, transformed half)."""
     return y[:, :Ch], y[:, Ch:]
@@ -137,7 +191,8 @@ def _nll(logdet_const, logdet_coupling, z):
     return -(logdet_const + logdet_coupling + (-0.5 * (z ** 2 + LOG2PI)).sum(dim=1)) / LN2
 
 
-def _run(inp, d, roles, dtype, given=None, fast_gates=False, w_fp32=False, x3h_rev=False, x3h_fwd=False, front=0):
+def _run(inp, d, roles, dtype, given=None, fast_gates=False, w_fp32=False, x3h_rev=False, x3h_fwd=False, front=0,
+         enc_three_products=False, enc_loop_front=False):
     Ch, C2, Cout, NG, G, I = derived(d)
     B, N, H, Ks, C, D = d.B, d.N, d.H, d.Ks, d.C, d.D
     hist1, col = inp["hist1"], inp["col"]
@@ -153,6 +208,13 @@ def _run(inp, d, roles, dtype, given=None, fast_gates=False, w_fp32=False, x3h_r
     wct, pre_static, noise = (inp[k].detach().to(dtype) for k in ("wct", "pre_static", "noise"))
     sig, tanh = (_fast_sigmoid, _fast_tanh) if fast_gates else (torch.sigmoid, torch.tanh)
     fmm = {0: torch.matmul, 1: _prod3, 5: _prod6, 9: _prod3h}[front]
+    enc = inp.get("p1enc")
+    if enc is not None:
+        ekind, ehid = enc["kind"], enc["hid"]
+        ew = {k: v.detach().to(dtype) for k, v in enc.items() if torch.is_tensor(v)}
+        emm = _prod3 if enc_three_products else fmm if enc_loop_front else torch.matmul
+        edims = er.Dims(B, hist1, 1, hist1 - 1, hist1, ehid, 0, 0)       # one window per row: its hist1 frames, from h = c = 0
+        e_last = None
 
     def cmm(x3h):
         return _prod3h if x3h else torch.matmul
@@ -187,12 +249,24 @@ def _run(inp, d, roles, dtype, given=None, fast_gates=False, w_fp32=False, x3h_r
 
     zero = faces.new_zeros(B, H)
     state = [(zero, zero) for _ in range(Ks)]
-    out = {k: [] for k in ("x", "z", "nll", "c", "gic", "h", "cstate", "raw_scale")}
+    out = {k: [] for k in ("x", "z", "nll", "c", "gic", "h", "cstate", "raw_scale") + (("e",) if enc is not None else ())}
     for n in range(N):
         t = d.start + n
         role = roles[n]
         gen_rows, obs_rows, absent = role == GEN, role == OBS, role == ABSENT
-        c = torch.nn.functional.leaky_relu(pre_static[n] + fmm(_window(faces, t, hist1), wct[:, col:col + K1].t()), 0.01)
+        if enc is None:
+            c = torch.nn.functional.leaky_relu(pre_static[n] + fmm(_window(faces, t, hist1), wct[:, col:col + K1].t()), 0.01)
+        else:
+            win = _enc_window(faces, t, hist1)
+            if ekind == "mlp":
+                e = _enc_mlp_act(fmm(win.reshape(B, K1), ew["w1"].t()) + ew["b1"])
+            else:
+                Xp = fmm(win.reshape(B * hist1, C), ew["w_ih"].t())          # row b hist1 + s: frame s of row b's window
+                hseq, _ = er.windows_forward(Xp, ew["w_hh"], ew["b_ih"], ew["b_hh"], None, edims, lstm=ekind == "lstm",
+                                             h0=_enc_state0(e_last, faces.new_zeros(B, ehid)), mm=emm, sig=sig, tanh=tanh)
+                e, e_last = _enc_features(hseq), hseq[-1]
+            c = torch.nn.functional.leaky_relu(pre_static[n] + fmm(e, _enc_cols(wct, col, ehid).t()), 0.01)
+            out["e"].append(e)
         gic = [fmm(c[:, k * D:(k + 1) * D], par["w_ih"][k][:, Ch:].t()) + par["b_ih"][k] for k in range(Ks)]
         st_in = [_state_in(state, k, n) for k in range(Ks)]
         new = [None] * Ks
@@ -289,6 +363,16 @@ def run_model(inp, d, roles, given=None, **flags):
                  products of FP16 pieces (11 + 11 mantissa bits, 2^-22 relative" - which is also the fused kernel's arithmetic
                  (lfi_sample.hip: "Arithmetic as the per-frame GEMMs it replaces (lfi_gemm_desc.precision 9)", c kept "as fp16 hi / lo
                  pieces")
+
+    and, where the window goes through an encoder (inp["p1enc"]), that encoder's, as encoder_reference.run_model words them:
+
+    front        also the mlp's product window W1^T, the recurrent kinds' input projection window W_ih^T and e wct[:, col:col + hid]^T
+                 (lfi_internal_sample_front_rows hands d->gemm_precision to all of them)
+    enc_three_products  both operands of h W_hh^T are split into bf16 hi + lo, summed as hi hi + hi lo + lo hi: the fused GRU kernels
+                 at lfi_enc_desc.precision = 1 - "1 -> bf16x3 recurrence; any other value -> exact f32 recurrence" (lfi.h, lfi_p1enc)
+    enc_loop_front  h W_hh^T per history step at `front`'s arithmetic: the unfused loop (hid > 256) and the LSTM loop - "loops take the
+                 GEMM mode as given"
+    fast_gates   covers the encoder's sigmoid and tanh too (ENC_SIG / ENC_TANH are sigmoidf_ / tanhf_)
 
     With every flag off this IS run_exact(inp, d, roles, torch.float64)."""
     with torch.no_grad():

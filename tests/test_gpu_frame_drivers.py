@@ -1,8 +1,8 @@
 """The per-frame flow drivers - lfi_flow_sample_seq_nll, lfi_flow_score_seq_from, lfi_flow_score_seq_chunk, lfi_flow_score_seq_chunk_rows
 and lfi_flow_step_rows_from: the kernels of lfi_flow_chain.hip, lfi_flow_chunk.hip, lfi_flow_chunk_rows.hip, lfi_sample.hip and the frame
 cells of lfi_flow_cells.h - against an fp64 flow written from the definition (tests/frame_reference.py), through the C ABI in the order
-stream.py / engine.py call it: lfi_flow_prep(with_inverse = 1), then the drivers, on a raw prev_p1_face window. An error per frame and per
-(flow step, frame) cell of the recurrent state, for the rows of the last batch tile and for each role group on their own.
+stream.py / engine.py call it: lfi_flow_prep(with_inverse = 1), then the drivers, on a raw prev_p1_face window or on one that goes
+through a ModalityEncoder per frame (lfi_p1enc kind mlp / rnn / lstm). An error per frame and per (flow step, frame) cell of the recurrent state, for the rows of the last batch tile and for each role group on their own.
 (SeqGlow.inference, glow/models.py:567-596; FlowStep.reverse_flow :345-373.)
 
 Bound, for every case, leg and part, every error a relative L2 with no floor against the fp64 run:
@@ -15,6 +15,16 @@ fp16 products) and lfi_flow_score_chunk_ok. Which front end ran is read from pre
 conditioning kernel (it never writes c), otherwise it holds c, one more compared part. Every work area has exactly the size its
 *_floats query returns, between two guard bands; outputs start as NaN or a sentinel.
 
+The encoded kinds (ENC_CASES): what joins the tested leaf kernels - lfi_internal_sample_front_rows, sample_front_setup / _frame,
+chunk_front / chunk_carve and lfi_flow_sample_p1_work_floats. The per-frame legs read the window straight out of `faces` ((t - hist1) C
+floats into a row of pitch seq_len C: 16-byte aligned on every other frame at C = 50), the chunk legs from an aligned stage with
+N B rows; the feature buffer has pitch (hid + 3) & ~3 and p1work starts as NaN between guard bands, so a padding column or a slot
+nobody wrote poisons c; wct's block starts at `col`, every other column is non-zero. Their front end is always the GEMMs, so c[n] is a
+compared part everywhere - the part that sees the encoder most directly. Which window-encoder kernel a recurrent kind reaches
+(lfi_encode_windows_fwd_variant on the descriptor the front end builds, for B and for N B rows) is asserted before the launch too:
+lfi_enc_desc.precision is gemm_precision, of which the fused GRU kernels know only "== 1" (bf16x3 recurrence; anything else is the
+exact f32 recurrence) while the unfused and LSTM loops hand it to their per-step GEMM - model_flags says which.
+
 Legs, one set of inputs per case: gen (lfi_flow_sample_seq_nll frame by frame, and again with nll = NULL: bit-identical frames and
 state), gen1 (the N frames in one call: the window-fragment hand-over from a frame's chain to the next frame's conditioning), obs
 (lfi_flow_score_seq_from over the fp64 run's frames rounded to fp32, frame by frame, and once as one call with z = NULL), chunk (dense
@@ -22,9 +32,9 @@ in one call and in two, ragged with lengths 0 .. N - 1 behind a dense first fram
 change from frame to frame).
 
 Not covered here: lfi_flow_sample_cand_from / _cand_seq and lfi_flow_step_rows_seq - tests/test_gpu_stream_candidates.py, _rollouts.py and
-_rows_many.py hold them bit for bit to the entry points above, whose bodies they share; the encoded lfi_p1enc kinds - their GEMMs and
-window encoders have fp64 tests of their own (tests/test_gpu_encoder_kernels.py); the window movers of lfi_stream.hip - exact copies,
-tested with torch.equal (tests/test_gpu_stream_windows.py). No case abandons a chain on purpose: a chain that gives up leaves NaN,
+_rows_many.py hold them bit for bit to the entry points above, whose bodies they share; the 64-window encoder kernels (variants 3 - 5:
+8192 windows a call at least, fp64 cases of their own in tests/test_gpu_encoder_kernels.py); the window movers of lfi_stream.hip - exact
+copies, tested with torch.equal (tests/test_gpu_stream_windows.py). No case abandons a chain on purpose: a chain that gives up leaves NaN,
 which the comparison rejects.
 """
 import ctypes as C
@@ -47,15 +57,17 @@ HIST1, START = 3, 4
 FUSED, GEMMS = "fused", "GEMMs"
 SENT = 1234.5       # frame slots nobody has written yet, z / nll behind a row's length (finite: a dense front end may read a slot)
 
-Case = namedtuple("Case", "id C H Ks B N D affine lstm dense p env clamp roles expect front")
+Case = namedtuple("Case", "id C H Ks B N D affine lstm dense p env clamp roles expect front enc ehid col hist1 evar")
 
 
-def case(id, p, expect, front, C=50, H=128, Ks=3, B=33, N=4, D=512, affine=1, lstm=0, dense=0, env=None, clamp=0, roles=0):
-    """expect: lfi_flow_frame_plan's bits; front: the front end lfi_flow_sample_seq_nll / _score_seq_from / _step_rows_from take."""
-    return Case(id, C, H, Ks, B, N, D, affine, lstm, dense, p, env or {}, clamp, roles, expect, front)
+def case(id, p, expect, front, C=50, H=128, Ks=3, B=33, N=4, D=512, affine=1, lstm=0, dense=0, env=None, clamp=0, roles=0,
+         enc="none", ehid=0, col=0, hist1=HIST1, evar=None):
+    """expect: lfi_flow_frame_plan's bits; front: the front end lfi_flow_sample_seq_nll / _score_seq_from / _step_rows_from take;
+    enc, ehid, col, hist1: the lfi_p1enc the window goes through; evar: lfi_encode_windows_fwd_variant of a recurrent kind."""
+    return Case(id, C, H, Ks, B, N, D, affine, lstm, dense, p, env or {}, clamp, roles, expect, front, enc, ehid, col, hist1, evar)
 
 
-CASES = [
+RAW_CASES = [
     case("final-9", 9, 31, FUSED, B=65, roles=1),          # five 16-row tiles and two 64-row conditioning tiles, each ending in one row
     case("final-9-unfused", 9, 31, GEMMS, env={"LFI_SAMPLE_FUSED": "0"}),
     case("final-9-wfrag0", 9, 23, FUSED, env={"LFI_SAMPLE_WFRAG16": "0"}),
@@ -78,6 +90,38 @@ CASES = [
     case("tiles", 9, 31, FUSED, B=130, roles=1),           # nine batch tiles and three conditioning tiles, the last of two rows
     case("one", 9, 31, FUSED, B=1, Ks=1, N=1),
 ]
+
+
+def enc_case(id, enc, ehid, col, p, expect, evar=None, hist1=HIST1, **kw):
+    return case(id, p, expect, GEMMS, enc=enc, ehid=ehid, col=col, hist1=hist1, evar=evar, **kw)
+
+
+# The encoded kinds, at the smallest shapes that still reach each path (none is a workload shape). expect: what the same flow shape
+# has above. evar, by hand from enc_plan_fwd (lfi_encoder_common.h): an LSTM and hid > 256 -> 0, the loop of one GEMM + one gate kernel
+# per history step; precision 1, hid % 4 == 0, ldcond = hid4 and col = 0 multiples of 4, aligned -> 2, the 32-window row-layout kernel
+# (the 64-window kernels want >= 128 workgroups of 64 windows); everything else -> 1, the accumulator-layout kernel, bf16x3 at
+# precision 1 and exact f32 otherwise. With C = 50 and N = 4 the window start (t - hist1) C is 16-byte aligned on two frames and not on
+# the other two.
+ENC_CASES = [
+    enc_case("mlp30-9", "mlp", 30, 6, 9, 31, roles=1),        # hid % 4 = 2 (hid4 = 32), wct + col misaligned, two tiles + one row
+    enc_case("mlp30-1", "mlp", 30, 6, 1, 15),                 # bf16x3 front products
+    enc_case("mlp30-0", "mlp", 30, 6, 0, 3, B=17),            # exact front, per-step plan
+    enc_case("rnn128-1", "rnn", 128, 0, 1, 15, evar=2, roles=1),      # row-layout GRU kernel, bf16x3 recurrence
+    enc_case("rnn128-9", "rnn", 128, 0, 9, 31, evar=1, roles=1),      # precision 9: exact f32 recurrence, front at fp16x3
+    enc_case("rnn50-1", "rnn", 50, 6, 1, 15, evar=1),         # hid % 4 != 0: accumulator layout with bf16x3, hid4 = 52
+    enc_case("rnn260-9", "rnn", 260, 0, 9, 31, evar=0, B=5),  # hid > 256: the unfused loop, hs and per-step GEMMs at 9
+    enc_case("lstm64-9", "lstm", 64, 0, 9, 31, evar=0),       # LSTM loop, gate + cell stash inside p1work
+    enc_case("lstm30-1", "lstm", 30, 6, 1, 15, evar=0, B=17),         # LSTM with padded pitch and misaligned col
+    enc_case("rnn-hist1", "rnn", 128, 0, 9, 31, evar=1, hist1=1, B=17),       # one-step recurrence from zero
+    enc_case("rnn-hist4", "rnn", 64, 4, 9, 31, evar=1, hist1=4, B=17),        # the first frame's window starts at frame 0 of faces
+    enc_case("rnn-lstmflow", "rnn", 64, 0, 0, 3, evar=1, B=17, lstm=1, H=64, D=64),       # the LSTM cell's chain, cstate carried
+    # (not in the issue's table: the same without a chain plan - the encoded front end in front of launch_rev_frame)
+    enc_case("rnn-lstmflow-steps", "rnn", 64, 0, 0, 1, evar=1, B=17, lstm=1, H=64, D=64, env={"LFI_SAMPLE_CHAIN": "0"}),
+    enc_case("rnn-tiles", "rnn", 128, 0, 9, 31, evar=1, B=130, roles=1),      # nine batch tiles; the chunk leg encodes 520 windows
+    enc_case("mlp-one", "mlp", 12, 0, 9, 31, B=1, Ks=1, N=1),                 # one row, one frame
+    enc_case("rnn-odd", "rnn", 12, 3, 0, 3, evar=1, C=15, H=24, Ks=4, B=6, D=20, dense=1, roles=1),   # every window start 4-byte aligned only
+]
+CASES = RAW_CASES + ENC_CASES
 SEED = 4      # the clamp case's conditions hold at this seed (tests/test_frame_reference_cpu.py checks them)
 
 
@@ -95,7 +139,26 @@ def model_flags(c):
     """The roundings the case's kernels document, by the plan bits the case asserts: the chains' three-product forms "are used where
     bit 2 is set" (lfi.h); every other cell is the exact f32 MFMA. The front end's products run at the case's gemm_precision."""
     chain = bool(c.expect & 2)
-    return dict(fast_gates=True, w_fp32=True, front=c.p, x3h_rev=chain and bool(c.expect & 4), x3h_fwd=chain and bool(c.expect & 16))
+    flags = dict(fast_gates=True, w_fp32=True, front=c.p, x3h_rev=chain and bool(c.expect & 4), x3h_fwd=chain and bool(c.expect & 16))
+    if c.enc in ("rnn", "lstm"):
+        # lfi.h beside lfi_p1enc: "1 -> bf16x3 recurrence; any other value -> exact f32 recurrence; loops take the GEMM mode as given"
+        fused = c.enc == "rnn" and c.evar in (1, 2)
+        flags.update(enc_three_products=fused and c.p == 1, enc_loop_front=not fused)
+    return flags
+
+
+def enc_desc(c, rows):
+    """The descriptor lfi_internal_sample_front_rows builds for `rows` windows of a recurrent kind (the GRU without a gate stash)."""
+    from lets_face_it_amd._lib import EncDesc
+    ed = EncDesc()
+    ed.B, ed.T, ed.N, ed.start, ed.hist, ed.hid = rows, c.hist1, 1, c.hist1 - 1, c.hist1, c.ehid
+    ed.ldcond, ed.col, ed.precision, ed.dup, ed.lstm = (c.ehid + 3) & ~3, 0, c.p, 0, int(c.enc == "lstm")
+    return ed
+
+
+def enc_variants(L, c):
+    """lfi_encode_windows_fwd_variant for the per-frame legs' B windows and the chunk legs' N B (host only)."""
+    return [int(L.lfi_encode_windows_fwd_variant(C.byref(enc_desc(c, rows)), 0, 0)) for rows in (c.B, c.N * c.B)]
 
 
 def ragged_lengths(c):
@@ -128,11 +191,11 @@ _refs = {}      # one input set's references at a time (the cases of a shape are
 def references(c):
     """inp, and per leg the roles, the given frames and the fp64 / fp32 runs - on the host, at most 8 threads."""
     d = ref_dims(c)
-    key = (d, c.dense, c.clamp, c.roles)
+    key = (d, c.dense, c.clamp, c.roles, c.enc, c.ehid, c.col, c.hist1)
     if key not in _refs:
         _refs.clear()
         torch.set_num_threads(min(8, torch.get_num_threads()))
-        inp = fq.make_frame_inputs(d, HIST1, dense=bool(c.dense), seed=SEED, clamp=bool(c.clamp))
+        inp = fq.make_frame_inputs(d, c.hist1, dense=bool(c.dense), seed=SEED, clamp=bool(c.clamp), enc=c.enc, ehid=c.ehid, col=c.col)
         legs = {}
         for name, roles in leg_roles(c).items():
             given = None if name == "gen" else legs["gen"]["exact"]["x"].float()
@@ -155,7 +218,7 @@ class Session:
 
     def __init__(self, c, dev, ref):
         from lets_face_it_amd import _lib
-        from lets_face_it_amd._lib import FlowParams, check
+        from lets_face_it_amd._lib import FlowParams, P1Enc, check
         self.c, self.dev, self.L, self.check = c, dev, _lib.lib(), check
         self.d = d = ref_dims(c)
         self.dims = flow_dims(c)
@@ -174,6 +237,19 @@ class Session:
         self.work = self.guarded("work", self.L.lfi_flow_sample_work_floats(C.byref(self.dims)))
         self.nll_work = self.guarded("nll_work", self.L.lfi_flow_sample_nll_work_floats(C.byref(self.dims)))
         self.pre = self.guarded("pre_static", c.N * c.B * self.KD)
+        # the encoder the window goes through: its parameters, and a p1work of exactly the size asked for that starts as NaN
+        self.p1, self.p1work = None, None
+        if c.enc != "none":
+            self.enc = {k: v.to(dev).contiguous() for k, v in inp["p1enc"].items() if torch.is_tensor(v)}
+            self.p1 = P1Enc()
+            self.p1.kind, self.p1.hid, self.p1.col = fq.ENCS.index(c.enc), c.ehid, c.col
+            for name, t in self.enc.items():
+                setattr(self.p1, name, t.data_ptr())
+            self.p1work = self.guarded("p1work", self.L.lfi_flow_sample_p1_work_floats(C.byref(self.dims), C.byref(self.p1), c.hist1),
+                                       float("nan"))
+
+    def p1ref(self):
+        return C.byref(self.p1) if self.p1 is not None else None
 
     def guarded(self, name, n, fill=0.0):
         g = Guarded(n, self.dev, fill)
@@ -206,14 +282,16 @@ class Session:
         assert front == expect, ("front end", front, expect)
         return None if front == FUSED else got.clone()
 
-    def args(self, s, n, nframes, noise=False, N=None):
-        """The arguments every driver shares up to p1work, for frames n .. n + nframes - 1 of the session."""
+    def args(self, s, n, nframes, noise=False, N=None, p1work=True):
+        """The arguments every driver shares up to p1work (p1work = False: NULL, as stream.py calls the chunk drivers, which carve
+        their own), for frames n .. n + nframes - 1 of the session."""
         c, o = self.c, lambda g, per: g.ptr() + 4 * n * per
         dims = self.dims if N is None else flow_dims(c, N)
-        a = [C.byref(dims), C.byref(self.p), self.prep.ptr(), self.wct.data_ptr(), self.E, HIST1, o(self.pre, c.B * self.KD)]
+        a = [C.byref(dims), C.byref(self.p), self.prep.ptr(), self.wct.data_ptr(), self.E, c.hist1, o(self.pre, c.B * self.KD)]
         if noise:
             a.append(self.noise.data_ptr() + 4 * n * c.B * c.C)
-        return a + [s["faces"].ptr(), self.T, START + n, nframes, n, s["h"].ptr(), s["cstate"].ptr() if c.lstm else None, None, None]
+        return a + [s["faces"].ptr(), self.T, START + n, nframes, n, s["h"].ptr(), s["cstate"].ptr() if c.lstm else None, self.p1ref(),
+                    self.p1work.ptr() if p1work and self.p1work is not None else None]
 
     def state(self, s):
         c = self.c
@@ -253,6 +331,9 @@ def run_case(c, dev, monkeypatch):
     chunk_ok = bool(L.lfi_flow_score_chunk_ok(C.byref(dims)))
     assert chunk_ok == bool(c.expect & 2), ("lfi_flow_score_chunk_ok", chunk_ok)
     assert Ks * -(-B // 16) <= 64, "the chains must be co-resident many times over"
+    if c.enc in ("rnn", "lstm"):
+        assert enc_variants(L, c) == [c.evar, c.evar], ("window-encoder kernel", enc_variants(L, c), c.evar)
+    assert c.enc == "none" or c.front == GEMMS
 
     ref = references(c)
     flags = model_flags(c)
@@ -323,19 +404,21 @@ def run_case(c, dev, monkeypatch):
 
     # ---- leg 4: the chunk chains (their front end is always the GEMMs: pre_static holds c afterwards)
     if chunk_ok:
-        cw = S.guarded("chunk_work", L.lfi_flow_score_chunk_work_floats(C.byref(dims), None, HIST1))
+        # (an encoded window: the chunk's own p1work lies inside chunk_work, so that starts as NaN too)
+        cw_fill = 0.0 if c.enc == "none" else float("nan")
+        cw = S.guarded("chunk_work", L.lfi_flow_score_chunk_work_floats(C.byref(dims), S.p1ref(), c.hist1), cw_fill)
         s = S.fresh(given)
         S.upload()
-        check(L.lfi_flow_score_seq_chunk(*S.args(s, 0, N), None, cw.ptr(), s["z"].ptr(), s["nll"].ptr(), S.st), "score_seq_chunk")
+        check(L.lfi_flow_score_seq_chunk(*S.args(s, 0, N, p1work=False), None, cw.ptr(), s["z"].ptr(), s["nll"].ptr(), S.st), "score_seq_chunk")
         cs = [S.front_of(0, N, GEMMS)]
         judge("obs", "chunk", S.run_of(s, {N - 1: S.state(s)}, cs, z=True, x=False))
         if N >= 2:
             n0 = N // 2
-            cw2 = S.guarded("chunk_work 2", L.lfi_flow_score_chunk_work_floats(C.byref(flow_dims(c, N - n0)), None, HIST1))
+            cw2 = S.guarded("chunk_work 2", L.lfi_flow_score_chunk_work_floats(C.byref(flow_dims(c, N - n0)), S.p1ref(), c.hist1), cw_fill)
             s, cs, states = S.fresh(given), [], {}
             for a, cnt in ((0, n0), (n0, N - n0)):
                 S.upload()
-                check(L.lfi_flow_score_seq_chunk(*S.args(s, a, cnt, N=N - n0), None, cw2.ptr(), s["z"].ptr() + 4 * a * B * Cc,
+                check(L.lfi_flow_score_seq_chunk(*S.args(s, a, cnt, N=N - n0, p1work=False), None, cw2.ptr(), s["z"].ptr() + 4 * a * B * Cc,
                                                  s["nll"].ptr() + 4 * a * B, S.st), "score_seq_chunk 2")
                 cs.append(S.front_of(a, a + cnt, GEMMS))
                 states[a + cnt - 1] = S.state(s)
@@ -347,11 +430,11 @@ def run_case(c, dev, monkeypatch):
             s["z"].t.fill_(SENT)
             s["nll"].t.fill_(SENT)
             S.upload()
-            check(L.lfi_flow_score_seq_chunk(*S.args(s, 0, 1), None, cw.ptr(), s["z"].ptr(), s["nll"].ptr(), S.st), "score_seq_chunk first")
+            check(L.lfi_flow_score_seq_chunk(*S.args(s, 0, 1, p1work=False), None, cw.ptr(), s["z"].ptr(), s["nll"].ptr(), S.st), "score_seq_chunk first")
             cs.append(S.front_of(0, 1, GEMMS))
             h0, c0 = S.state(s)
             S.upload()
-            check(L.lfi_flow_score_seq_chunk_rows(*S.args(s, 1, N - 1), None, cw.ptr(), s["z"].ptr() + 4 * B * Cc, s["nll"].ptr() + 4 * B,
+            check(L.lfi_flow_score_seq_chunk_rows(*S.args(s, 1, N - 1, p1work=False), None, cw.ptr(), s["z"].ptr() + 4 * B * Cc, s["nll"].ptr() + 4 * B,
                                                   ldev.data_ptr(), S.st), "score_seq_chunk_rows")
             cs.append(S.front_of(1, N, GEMMS))
             h1, c1 = S.state(s)
@@ -418,12 +501,26 @@ def test_frame_drivers_vs_fp64(gpu_device, monkeypatch, c):
 def test_case_list_covers_the_table():
     """The list itself: every plan-bit combination of the table and both front ends, both sizes of sc_cond_kernel, the LSTM cell in
     chain and per-step form, a one-row last tile behind full ones in both tile sizes, C = 64, padding hidden units, the clamp,
-    additive, dense and N = 1."""
-    assert {c.expect for c in CASES} >= {31, 23, 15, 3, 21, 20, 0} and {c.front for c in CASES} == {FUSED, GEMMS}
-    assert {(3 + c.lstm) * c.H for c in CASES if c.front == FUSED} == {384, 512}
-    assert any(c.lstm and c.expect & 2 for c in CASES) and any(c.lstm and not c.expect & 2 for c in CASES)
-    assert any(c.B > 16 and c.B % 16 == 1 and c.B > 64 and c.B % 64 == 1 for c in CASES)
-    assert any(c.C == 64 for c in CASES) and any(c.H % 16 for c in CASES) and any(c.clamp for c in CASES)
-    assert any(not c.affine for c in CASES) and any(c.dense for c in CASES) and any(c.N == 1 for c in CASES)
-    assert {c.id for c in CASES if c.roles} == {"final-9", "final-5", "final-9-steps", "lstm128", "tiles", "odd"}
-    assert all(c.Ks * -(-c.B // 16) <= 64 for c in CASES)
+    additive, dense and N = 1 among the raw-window cases; among the encoded ones every kind, the three window-encoder kernels a
+    frame driver can reach and both recurrences of the fused ones, a padded feature pitch, a column offset that is no multiple of 4,
+    windows that start 16-byte aligned on some frames only, every gemm_precision, one-step and start-of-faces windows, one row."""
+    assert {c.expect for c in RAW_CASES} >= {31, 23, 15, 3, 21, 20, 0} and {c.front for c in RAW_CASES} == {FUSED, GEMMS}
+    assert {(3 + c.lstm) * c.H for c in RAW_CASES if c.front == FUSED} == {384, 512}
+    assert any(c.lstm and c.expect & 2 for c in RAW_CASES) and any(c.lstm and not c.expect & 2 for c in RAW_CASES)
+    assert any(c.B > 16 and c.B % 16 == 1 and c.B > 64 and c.B % 64 == 1 for c in RAW_CASES)
+    assert any(c.C == 64 for c in RAW_CASES) and any(c.H % 16 for c in RAW_CASES) and any(c.clamp for c in RAW_CASES)
+    assert any(not c.affine for c in RAW_CASES) and any(c.dense for c in RAW_CASES) and any(c.N == 1 for c in RAW_CASES)
+    assert {c.id for c in RAW_CASES if c.roles} == {"final-9", "final-5", "final-9-steps", "lstm128", "tiles", "odd"}
+    assert all(c.Ks * -(-c.B // 16) <= 64 for c in RAW_CASES)
+    E = ENC_CASES
+    assert len(RAW_CASES) == 21 and len(E) >= 15 and len({c.id for c in CASES}) == len(CASES)
+    assert all(c.front == GEMMS and c.hist1 <= START for c in E) and all(c.enc == "none" and c.hist1 == HIST1 for c in RAW_CASES)
+    assert {c.enc for c in E} == {"mlp", "rnn", "lstm"} and {c.p for c in E if c.enc == "mlp"} == {0, 1, 9}
+    assert {(c.evar, c.p == 1) for c in E if c.enc == "rnn"} >= {(2, True), (1, True), (1, False), (0, False)}
+    assert all((c.evar is None) == (c.enc == "mlp") and (c.enc != "lstm" or c.evar == 0) for c in E)
+    for kind in ("mlp", "rnn", "lstm"):
+        assert any(c.enc == kind and c.ehid % 4 and c.col % 4 for c in E), kind
+    assert all(c.N >= 4 for c in E if c.C == 50 and c.B > 1) and any(c.C % 4 and c.C != 50 for c in E)
+    assert {c.hist1 for c in E} >= {1, 3, 4} and any(c.hist1 == START for c in E) and any(c.B == 1 for c in E)
+    assert any(c.lstm and c.expect & 2 for c in E) and any(c.lstm and not c.expect & 2 for c in E) and any(c.B > 128 for c in E)
+    assert all(c.Ks * -(-c.B // 16) <= 64 for c in E)
